@@ -12,9 +12,12 @@ curve is quoted on (configs[3] = 32 images per GPU x N). Weak scaling: per-GPU w
 data on the path; the weight arena is broadcast once over RCCL (ctpn_broadcast_weights_rank of the C ABI) before the
 timed region. torch.distributed (gloo) is rendezvous / barrier / MAX-of-a-scalar plumbing only.
 
-Rank 0 prints ONE JSON line. Extra objects:
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times exactly --steps steps, writes the last timed step's output with
+--dump-outputs DIR and prints the line: the headline fields, its configuration and
   roofline       the dominant kernel (implicit-GEMM conv, MFMA-bound), measured live with hipEvents on the ctx stream over the
-                 timed region;
+                 timed region (the shader clock and package power next to it only with --full).
+Everything else takes runs of its own and comes with --full:
+  stages_ms_per_step  per-stage times from an extra untimed pass after the timed region (--stage-events after);
   cpu_baseline   the oracle (CPU port of the reference path) timed on this host's cores on a bounded sample of the same workload
                  (N = 1 only);
   accuracy       the device outputs of the SAME sample images against that oracle run (cls_prob, rois, text lines);
@@ -23,6 +26,7 @@ Rank 0 prints ONE JSON line. Extra objects:
                  batch 32 -- each with its accuracy against the oracle --, batch-1 throughput (pipelined) and the single-image SYNCHRONOUS latency (the reference's calling convention), and the PCIe-inclusive rate (page-locked and pageable).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -38,6 +42,9 @@ CONV_GFLOP_PER_IMAGE_600x900 = 337.264  # 13 implicit-GEMM convs: 339.130 (SURVE
 CONV1_1_GFLOP_PER_IMAGE_600x900 = 1.866  # inside conv1_2's launch when the ctx computes conv1_1 in its window stage (16-bit modes, uint8 feed)
 PEAK = {"bf16": 2500.0, "fp16": 2500.0, "split": 2500.0, "fp32": 157.3}   # dense MFMA TFLOP/s of the opcode each mode issues, MI355X_MICROARCH.md
 MFMA_PER_PRODUCT = {"bf16": 1, "fp16": 1, "split": 3, "fp32": 1}        # split precision spends three bf16 MFMAs per algorithmic product
+LINE_CAPACITY = 512                 # text lines per image that a collect of the timed path returns at most
+ROIS_PER_IMAGE = 1000               # rois per image at most (RPN_POST_NMS_TOP_N)
+DUMP_BYTES = 64 << 20               # --dump-outputs writes at most this much over all ranks
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -233,10 +240,10 @@ def run_config(ctpn_amd, torch, dev, ctx, imgs, shape, steps, warmup, mode, host
             else:
                 ctx.detect_submit(device_ptr=imgs.data_ptr(), shape=shape, slot=k & 1)
             if k > 0:
-                out = ctx.detect_collect((k - 1) & 1, mode=mode, line_capacity=512)
+                out = ctx.detect_collect((k - 1) & 1, mode=mode, line_capacity=LINE_CAPACITY)
         if k_steps > 0:
             # the LAST step's rois come back too (they are in the slot's one D2H copy anyway): the caller checks the timed batch's output
-            out = ctx.detect_collect((k_steps - 1) & 1, mode=mode, line_capacity=512, want_rois=True)
+            out = ctx.detect_collect((k_steps - 1) & 1, mode=mode, line_capacity=LINE_CAPACITY, want_rois=True)
         return out
 
     run(warmup)
@@ -275,6 +282,27 @@ def timed_batch_equals_sample(lines, rois, sample):
     s_rois, s_lines = sample
     k = min(len(s_rois), len(rois))
     return bool(k > 0 and all(np.array_equal(rois[i], s_rois[i]) and np.array_equal(lines[i], s_lines[i]) for i in range(k)))
+
+
+def dump_outputs(out_dir, lines, rois, first_image, rank, world):
+    """--dump-outputs: what a caller of the timed path received in the last timed step, one row per roi / text line with the image's
+    index in the global batch (its seed - 1) in column 0: rois.npy (float32: index, score, x1, y1, x2, y2) and text_lines.npy (float64:
+    index, then the line's 8 coordinates and score). Rank r > 0 writes rois_rank<r>.npy / text_lines_rank<r>.npy. At most DUMP_BYTES over
+    all ranks: a batch whose worst case exceeds its share is written for a fixed, seeded sample of its images, whatever they contain."""
+    per_image = ROIS_PER_IMAGE * 6 * 4 + LINE_CAPACITY * 10 * 8
+    n = len(lines)
+    keep = np.arange(n)
+    if n * per_image > DUMP_BYTES // world:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // world // per_image, replace=False))
+
+    def rows(arrs, cols, dtype):
+        parts = [np.concatenate([np.full((len(arrs[i]), 1), first_image + i, dtype), np.asarray(arrs[i], dtype).reshape(-1, cols)], 1)
+                 for i in keep]
+        return np.concatenate(parts) if parts else np.zeros((0, cols + 1), dtype)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rois%s.npy" % suffix), rows(rois, 5, np.float32))
+    np.save(os.path.join(out_dir, "text_lines%s.npy" % suffix), rows(lines, 9, np.float64))
 
 
 def secondary_config(ctpn_amd, torch, dev, arena, precision, B, H, W, mode, steps, warmup, host=False, pinned=True, options=None, sample=None):
@@ -473,6 +501,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100, help="timed steps (default 100: 0.9 s at 8.8 ms per step; the first steps of a cold part run at lower clocks, see other_configs.sustained_600_steps)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the per-stage pass, shader clock and power, cpu_baseline, accuracy, "
+                         "timed_batch_equals_sample and (N = 1) other_configs. A plain run does only the headline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's rois and text lines to DIR/rois.npy, DIR/text_lines.npy")
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--width", type=int, default=900)
@@ -480,11 +513,11 @@ def main():
                     help="ctpn_create precision: bf16 (BASELINE.json's dtype; the headline), fp16 (same MFMA rate, 3 more mantissa bits), split ((hi, lo) "
                          "bf16 pairs, three MFMAs per product: parity-grade), fp32 (exact-fp32 MFMA: the correctness gate)")
     ap.add_argument("--mode", default="H", choices=["H", "O"])
-    ap.add_argument("--cpu-images", type=int, default=6, help="images in the CPU-baseline / accuracy sample (0 disables both)")
+    ap.add_argument("--cpu-images", type=int, default=6, help="with --full: images in the CPU-baseline / accuracy sample (0 disables both)")
     ap.add_argument("--host-images", action="store_true",
                     help="feed host uint8 batches instead of HBM-resident ones (PCIe-inclusive rate; never the headline value)")
     ap.add_argument("--stage-events", default="after", choices=["after", "inline", "off"],
-                    help="per-stage hipEvent pairs: in an extra untimed pass after the timed region (default), inside it, or not at all")
+                    help="per-stage hipEvent pairs: in an extra untimed pass after the timed region (default; with --full only), inside it, or not at all")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=INT",
                     help="per-ctx option of the C ABI for the headline ctx (ctpn_set_option), e.g. --option lstm_split=0; repeatable")
     ap.add_argument("--lstm-exact", action="store_true",
@@ -495,7 +528,7 @@ def main():
     ap.add_argument("--zero-data", action="store_true",
                     help="DIAGNOSTIC, not a benchmark: all-zero weights and images (every MFMA operand is zero). The kernels execute the same "
                          "instructions in the same cycles; what changes is the power they draw and with it the clock (tools/r3_clock.sh)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs runs after the headline (N = 1 runs them by default)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other_configs runs after the headline (N = 1 runs them by default)")
     ap.add_argument("--latency-only", action="store_true", help="print only the single-image synchronous latency object (bf16, then with --option's options) and exit")
     ap.add_argument("--rccl-timeout", type=int, default=60, help="N > 1: seconds the RCCL weight broadcast may take before this rank gives it up and falls back to gloo")
     ap.add_argument("--weights-via", default="rccl", choices=["rccl", "gloo"],
@@ -521,6 +554,8 @@ def main():
     # (WORLD_SIZE set) the world size must be the one asked for: a 1-rank line must never be labelled as anything else.
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         import socket
         with socket.socket() as so:
@@ -664,11 +699,16 @@ def main():
         torch.cuda.synchronize()
         D.barrier()
 
-    # shader clock and package power over the headline run (rank 0's device; 50 ms period: a sysfs read per card): roofline.sclk_mhz_mean
-    with GpuSampler(dev_index, period=0.05) as head_smp:
+    # a plain run keeps the conv-stack event pair of the timed region (roofline) but takes no per-stage pass after it
+    stage_events = args.stage_events if (args.full or args.stage_events != "after") else "conv_only"
+    # --full: shader clock and package power over the headline run (rank 0's device; 50 ms period: a sysfs read per card): roofline.sclk_mhz_mean
+    head_smp = GpuSampler(dev_index, period=0.05) if args.full else contextlib.nullcontext()
+    with head_smp:
         elapsed_local, prof, prof_stage, stage_steps, (lines, last_rois) = run_config(ctpn_amd, torch, dev, ctx, imgs, shape, args.steps, args.warmup, args.mode,
-                                                                                       host_images=imgs_host, stage_events=args.stage_events, sync=sync)
-    head_clock = head_smp.summary()
+                                                                                       host_images=imgs_host, stage_events=stage_events, sync=sync)
+    head_clock = head_smp.summary() if args.full else {"sclk_mhz_mean": None, "package_power_w_mean": None, "samples": 0, "source": "not sampled (--full)"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lines, last_rois, lo, rank, world)
     elapsed = D.max_over_ranks(elapsed_local, "cpu")
     per_rank = D.gather_over_ranks([elapsed_local / args.steps * 1e3, t_bcast * 1e3, ctx.host_threads()], "cpu")
     fused1 = args.precision in ("bf16", "fp16") and ctx.get_option("conv1_kernel") == 2 and ctx.get_option("conv1_fuse") == 1 and ctx.get_option("keep_acts") == 0
@@ -734,13 +774,14 @@ def main():
                          "clock_samples": head_clock["samples"], "clock_source": head_clock["source"],
                          "frac_of_clock_adjusted_peak": (round(achieved / (PEAK[args.precision] * head_clock["sclk_mhz_mean"] / 2400.0), 4)
                                                          if head_clock["sclk_mhz_mean"] else None)},
-            "stages_ms_per_step": {k: round((prof_stage["conv_gemm"]["ms"] if k == "conv_gemm" else v["ms"]) / stage_steps, 4) for k, v in prof_stage.items()},
-            "stage_events": args.stage_events,
+            "stage_events": stage_events,
         }
+        if stage_events != "conv_only":
+            out["stages_ms_per_step"] = {k: round((prof_stage["conv_gemm"]["ms"] if k == "conv_gemm" else v["ms"]) / stage_steps, 4) for k, v in prof_stage.items()}
         if world > 1 and args.baseline_value:
             out["weak_scaling_efficiency"] = round(out["value"] / (world * args.baseline_value), 4)
             out["weak_scaling_baseline_images_per_s"] = args.baseline_value
-        if world == 1:
+        if world == 1 and args.full:
             oracle_out = None
             if args.cpu_images > 0:
                 out["cpu_baseline"], oracle_out = cpu_baseline(arena, H, W, args.cpu_images, args.mode)

@@ -98,3 +98,26 @@ def test_bench_gpus_n_launches_n_ranks_itself():
     assert p.returncode != 0 and "must agree" in p.stderr
     p = _bench(["--gpus", "1", "--print-launch"], env={"WORLD_SIZE": "2", "RANK": "0"})
     assert p.returncode != 0 and "must agree" in p.stderr
+
+
+def test_bench_dump_outputs_per_rank_files_and_size_cap(tmp_path):
+    """bench.dump_outputs: one row per roi / text line behind the image's global index; rank r > 0 writes its own files; a shard whose
+    worst case exceeds its share of the 64 MB is written for a fixed, seeded sample of its images, the same whatever they contain."""
+    import bench
+    rng = np.random.default_rng(3)
+    lines = [rng.random((k, 9)) for k in (0, 3, 1)]
+    rois = [rng.random((k, 5)).astype(np.float32) for k in (5, 0, 2)]
+    bench.dump_outputs(str(tmp_path), lines, rois, 4, 1, 2)
+    r, l = np.load(str(tmp_path / "rois_rank1.npy")), np.load(str(tmp_path / "text_lines_rank1.npy"))
+    assert r.dtype == np.float32 and r.shape == (7, 6) and l.dtype == np.float64 and l.shape == (4, 10)
+    for i in range(3):
+        assert np.array_equal(r[r[:, 0] == 4 + i][:, 1:], rois[i]) and np.array_equal(l[l[:, 0] == 4 + i][:, 1:], lines[i])
+    per_image = bench.ROIS_PER_IMAGE * 6 * 4 + bench.LINE_CAPACITY * 10 * 8
+    n = bench.DUMP_BYTES // per_image + 40
+    kept = []
+    for fill in (0.0, 1.0):
+        bench.dump_outputs(str(tmp_path), [np.full((1, 9), fill)] * n, [np.full((1, 5), fill, np.float32)] * n, 0, 0, 1)
+        idx = np.load(str(tmp_path / "text_lines.npy"))[:, 0]
+        assert len(idx) == bench.DUMP_BYTES // per_image and np.array_equal(np.load(str(tmp_path / "rois.npy"))[:, 0], idx)
+        kept.append(idx)
+    assert np.array_equal(kept[0], kept[1]) and np.all(np.diff(kept[0]) > 0)

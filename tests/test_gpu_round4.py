@@ -47,6 +47,27 @@ def test_bench_one_rank_line_says_one_rank():
     assert d["n_gpus"] == 1 and d["config"]["parallelism"].startswith("1 rank") and d["config"]["weight_broadcast"] == "none (1 rank)"
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path, arena):
+    """A plain run times exactly --steps steps (13 conv launches each inside the timed region) and measures nothing else: the CPU
+    baseline, accuracy, stage pass, clock sampling and other configurations come with --full. --dump-outputs writes the last timed step's
+    rois and text lines, which are the bytes a synchronous ctpn_detect returns for the same seeded images."""
+    d = _bench_no_launcher(["--steps", "3", "--warmup", "1", "--batch", "2", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 3 and d["roofline"]["launches"] == 13 * 3 and abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3e-3)) < 0.02 * d["value"]
+    for key in ("cpu_baseline", "accuracy", "timed_batch_equals_sample", "other_configs", "stages_ms_per_step"):
+        assert key not in d, key
+    assert d["roofline"]["clock_samples"] == 0
+    rois, lines = np.load(str(tmp_path / "rois.npy")), np.load(str(tmp_path / "text_lines.npy"))
+    assert rois.dtype == np.float32 and lines.dtype == np.float64 and len(lines) == d["config"]["lines_rank0_last_step"]
+    imgs = np.stack([np.random.default_rng(1 + i).integers(0, 256, size=(600, 900, 3), dtype=np.uint8) for i in range(2)])
+    with ctpn_amd.Context(0, 2, 600, 900, "bf16") as ctx:
+        ctx.load_weights(arena)
+        want_lines, want_rois = ctx.detect(imgs, want_rois=True, line_capacity=512)
+    for i in range(2):
+        assert len(want_rois[i]) > 0
+        assert np.array_equal(rois[rois[:, 0] == i][:, 1:], want_rois[i])
+        assert np.array_equal(lines[lines[:, 0] == i][:, 1:], want_lines[i])
+
+
 def test_bench_refuses_more_ranks_than_devices():
     if B.device_count() >= 2:
         pytest.skip("one-GPU boxes only")

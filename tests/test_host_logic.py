@@ -22,10 +22,9 @@ def test_cfg_defaults_and_yaml_merge(root):
     assert np.allclose(cfg.PIXEL_MEANS.ravel(), [102.9801, 115.9465, 122.7717])
     C.cfg_from_file(os.path.join(root, "text-detection-ctpn_amd", "ctpn", "text.yml"))
     assert cfg.TEST.DETECT_MODE == "H" and cfg.USE_GPU_NMS is True
-    ref_yml = "/root/reference/ctpn/text.yml"
-    if os.path.exists(ref_yml):                       # the reference's own file is accepted unchanged
-        C.cfg_from_file(ref_yml)
-        assert cfg.TRAIN.SOLVER == "Adam" and cfg.TEST.checkpoints_path == "checkpoints/"
+    # the reference's own ctpn/text.yml (tests/golden/reference_text.yml, byte for byte) is accepted unchanged
+    C.cfg_from_file(os.path.join(root, "tests", "golden", "reference_text.yml"))
+    assert cfg.TRAIN.SOLVER == "Adam" and cfg.TEST.checkpoints_path == "checkpoints/"
     with pytest.raises(KeyError):
         C._merge_a_into_b(C.AttrDict({"NOT_A_KEY": 1}), cfg)
     with pytest.raises(ValueError):
@@ -87,17 +86,18 @@ def test_connector_constants_agree(root):
     assert Config.TEXT_PROPOSALS_WIDTH * Config.MIN_NUM_PROPOSALS == 32 and (Config.SCALE, Config.MAX_SCALE) == (600, 1200)
 
 
-def test_demo_output_format_and_resize():
+def test_demo_output_format_and_resize(golden_dir):
     from ctpn_amd.ctpn import demo
     recs = np.array([[100.9, 50.2, 300.7, 50.2, 100.9, 90.8, 300.7, 90.8, 0.95],
                      [52.0, 50.0, 300.0, 50.0, 52.0, 90.0, 300.0, 90.0, 0.95]])   # |x1 - y1| < 5 -> skipped (demo.py:32 quirk)
     assert demo.result_lines(recs, 1.5) == ["67,33,200,60\r\n"]
     assert demo.result_lines(recs, 1.5) == P.draw_boxes_lines(recs, 1.5)
-    fix = "/root/reference/data/results/res_006.txt"
-    if os.path.exists(fix):                             # same line syntax as the reference's recorded outputs
-        import re
-        for line in open(fix, newline="").read().split("\n")[:-1]:
-            assert re.fullmatch(r"\d+,\d+,\d+,\d+\r", line)
+    # same line syntax as the reference's recorded outputs (its data/results/res_006.txt, committed in demo_files.npz)
+    import re
+    fix = np.load(os.path.join(golden_dir, "demo_files.npz"))["result_txt_006_jpg"].tobytes().decode()
+    assert fix
+    for line in fix.split("\n")[:-1]:
+        assert re.fullmatch(r"\d+,\d+,\d+,\d+\r", line)
     # resize_im: the factor is host logic, the output size comes from the library's host arithmetic (cvRound), the pixels
     # from the GPU kernel (tests/test_gpu_parity.py::test_resize_matches_oracle)
     from ctpn_amd import _binding as B

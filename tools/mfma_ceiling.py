@@ -51,7 +51,7 @@ def main():
             print(json.dumps(row), flush=True)
     bench = None
     with GpuSampler(0, period=0.05) as smp:
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.bench_steps), "--warmup", "20", "--cpu-images", "0", "--no-other-configs"],
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.bench_steps), "--warmup", "20", "--full", "--cpu-images", "0", "--no-other-configs"],
                            capture_output=True, text=True, timeout=600)
     if r.returncode == 0:
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

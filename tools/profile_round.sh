@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collect the judged artefacts of one round on the GPU box in ONE gpurun call (run from the repo root):
 #   gpurun --timeout 2400 -- 'bash tools/profile_round.sh r06'
-# Writes gpurun_out/<tag>/{pytest_gpu.txt, bench_n1.json (the default line: headline + accuracy + cpu_baseline + other_configs),
+# Writes into $OUT: {pytest_gpu.txt, bench_n1.json (the --full line: headline + accuracy + cpu_baseline + other_configs),
 # decode_throughput_kinds.json (files in / lines out per file kind), kernel_stats.csv, layers.csv / layers.txt, timeline.txt (bf16), timeline_sync.txt + latency.json (one
 # synchronous single-image call, tools/r5_latency.sh), pmc.json};
 # copy what is judged into profiles/<tag>_*.
@@ -14,11 +14,11 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 STEPS=4
 (time timeout 900 python -m pytest tests -m gpu -q 2>&1 | grep -v "^RCCL\|^HIP version\|^ROCm\|^Hostname\|^Librccl" | tail -8) > $OUT/pytest_gpu.txt 2>&1
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 CTPN_NO_TORCH=1 timeout 120 python tools/file_kinds_throughput.py --images 768 --distinct 64 --out $OUT/decode_throughput_kinds.json > /dev/null 2> $OUT/kinds.err
 cd /tmp
 for p in bf16; do
-  rocprofv3 --kernel-trace --stats -d $OUT/raw_$p -o trace -- python $R/bench.py --precision $p --steps 8 --warmup 2 --cpu-images 0 --no-other-configs > $OUT/bench_under_trace_$p.json 2> $OUT/trace_$p.err
+  rocprofv3 --kernel-trace --stats -d $OUT/raw_$p -o trace -- python $R/bench.py --precision $p --steps 8 --warmup 2 --full --cpu-images 0 --no-other-configs > $OUT/bench_under_trace_$p.json 2> $OUT/trace_$p.err
 done
 for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"; do
   name=$(echo $grp | cut -d' ' -f1)
@@ -34,7 +34,7 @@ bash tools/r5_latency.sh $TAG > /dev/null 2>&1
 # round 6: the drop-in's default precision (split) profiled like the headline -- per-layer times, one synchronous single-image call -- the MFMA
 # ceiling of this box next to one bench run (tools/mfma_ceiling.py), and the two-batches-in-flight check of every precision
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/raw_split -o trace -- python $R/bench.py --precision split --steps 4 --warmup 1 --cpu-images 0 --no-other-configs > $OUT/bench_under_trace_split.json 2> $OUT/trace_split.err
+rocprofv3 --kernel-trace --stats -d $OUT/raw_split -o trace -- python $R/bench.py --precision split --steps 4 --warmup 1 --full --cpu-images 0 --no-other-configs > $OUT/bench_under_trace_split.json 2> $OUT/trace_split.err
 cd $R
 python tools/rocprof_layers.py $OUT/raw_split/trace_results.db $OUT/layers_split.csv > $OUT/layers_split.txt
 python tools/timeline.py $OUT/raw_split/trace_results.db 3 > $OUT/timeline_split.txt 2>&1

@@ -11,7 +11,7 @@ for v in "$@"; do
   (
     if [ "$envs" != "-" ]; then IFS=,; for kv in $envs; do export "$kv"; done; unset IFS; fi
     cd $R
-    python bench.py --cpu-images 0 --no-other-configs > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+    python bench.py --full --cpu-images 0 --no-other-configs > $OUT/bench_$name.json 2> $OUT/bench_$name.err
     python -c "import json;d=json.load(open('$OUT/bench_$name.json'));print('$name', d['value'], d['ms_per_step'], d['roofline']['frac'], d['stages_ms_per_step']['conv_gemm'], d['stages_ms_per_step']['conv_first'], d['stages_ms_per_step']['gemm'])" || tail -5 $OUT/bench_$name.err
     cd /tmp
     rocprofv3 --kernel-trace --stats -d $OUT/raw_$name -o trace -- python $R/bench.py --steps 6 --warmup 2 --cpu-images 0 --no-other-configs > /dev/null 2> $OUT/trace_$name.err

@@ -5,7 +5,7 @@ TAG=${1:-ab}; shift; R=$PWD; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; : > $OUT/ab.
 for rep in 1 2; do
 for o in "" "$@"; do
   args=""; for kv in $o; do args="$args --option $kv"; done
-  python $R/bench.py --steps 60 --warmup 5 --cpu-images 0 --no-other-configs $args > $OUT/b.json 2> $OUT/b.err
+  python $R/bench.py --steps 60 --warmup 5 --full --cpu-images 0 --no-other-configs $args > $OUT/b.json 2> $OUT/b.err
   python3 - "$o" $OUT/b.json >> $OUT/ab.txt <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][0])

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 timeout 420 python -m pytest tests/test_gpu_fuse.py -x -q > "$OUT/pytest_fuse.txt" 2>&1
 echo "pytest exit $?" >> "$OUT/pytest_fuse.txt"
 tail -5 "$OUT/pytest_fuse.txt"
-B="python bench.py --steps 30 --warmup 10 --cpu-images 0 --no-other-configs"
+B="python bench.py --steps 30 --warmup 10 --full --cpu-images 0 --no-other-configs"
 CTPN_CONV1_FUSE=1 timeout 200 $B > "$OUT/bench_fused.json" 2> "$OUT/bench_fused.err"
 CTPN_CONV1_FUSE=0 timeout 200 $B > "$OUT/bench_stored_q.json" 2> "$OUT/bench_stored_q.err"
 CTPN_CONV1_FUSE=1 timeout 200 $B > "$OUT/bench_fused_b.json" 2> "$OUT/bench_fused_b.err"

@@ -1,7 +1,7 @@
 """CPU: the host side of libctpn_hip.so under AddressSanitizer (the reference has no sanitizer run at all; VERDICT r2
 missing #7). `make -C text-detection-ctpn_amd/csrc asan` builds libctpn_hip_asan.so (host code instrumented, device code not);
 tools/run_asan.sh runs the ABI / host-logic / property tests against it in a child interpreter with the ASan runtime preloaded. Any
-heap overflow, use-after-free or stack overflow in ctpn_api.hip's host code (worker pool, slots, writers, connector) aborts the child."""
+heap overflow, use-after-free or stack overflow in the api_*.hip units' host code (worker pool, slots, writers, connector) aborts the child."""
 import os
 import subprocess
 

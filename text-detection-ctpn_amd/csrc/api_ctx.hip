@@ -1,0 +1,397 @@
+// C ABI of libctpn_hip.so, context unit: error slot, create / destroy, options, synchronisation, profile read-out, and the process-wide
+// CTPN_DEBUG_SYNC / CTPN_ROCTX helpers. See include/ctpn_hip.h for the contract and the reference interfaces each entry point replaces.
+#include "ctx.h"
+
+namespace ctpn {
+
+static thread_local std::string t_err;
+void set_error(const std::string& s) { t_err = s; }
+int fail(int code, const std::string& s) { t_err = s; return code; }
+
+static int env_int(const char* name, int dflt) { const char* v = std::getenv(name); return v && *v ? std::atoi(v) : dflt; }
+
+static int dev_alloc(ctpn_ctx* c, void** p, size_t bytes, bool zero) {
+  if (bytes == 0) bytes = 256;
+  CTPN_HIP_TRY(hipMalloc(p, bytes));
+  c->allocs.push_back(*p);
+  if (zero) CTPN_HIP_TRY(hipMemsetAsync(*p, 0, bytes, c->stream));
+  return CTPN_OK;
+}
+
+int debug_sync() { static const int v = env_int("CTPN_DEBUG_SYNC", 0); return v; }
+// CTPN_ROCTX=1: roctx ranges (rocprofv3 --marker-trace). librocprofiler-sdk-roctx.so is dlopen'ed on first use, so the library has no
+// link-time dependency on the profiler SDK: an install without it still loads, and CTPN_ROCTX=1 there is a silent no-op.
+const RoctxApi& roctx_api() {
+  static const RoctxApi api = [] {
+    RoctxApi a;
+    if (!env_int("CTPN_ROCTX", 0)) return a;
+    void* h = dlopen("librocprofiler-sdk-roctx.so", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) h = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_NOW | RTLD_GLOBAL);
+    if (!h) {
+      const char* rp = std::getenv("ROCM_PATH");
+      const std::string p = std::string(rp && *rp ? rp : "/opt/rocm") + "/lib/librocprofiler-sdk-roctx.so";
+      h = dlopen(p.c_str(), RTLD_NOW | RTLD_GLOBAL);
+    }
+    if (h) {
+      a.push = (int (*)(const char*))dlsym(h, "roctxRangePushA");
+      a.pop = (int (*)())dlsym(h, "roctxRangePop");
+      if (!a.push || !a.pop) { a.push = nullptr; a.pop = nullptr; }
+    }
+    return a;
+  }();
+  return api;
+}
+int roctx_on() { return roctx_api().push != nullptr; }
+
+static int prof_drain(ctpn_ctx* c) {
+  if (c->pending.empty()) return CTPN_OK;
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  for (auto& r : c->pending) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
+      c->prof_ms[r.kind] += ms; c->prof_n[r.kind] += r.launches; c->prof_work[r.kind] += r.work;
+    }
+    c->free_events.push_back(r.a); c->free_events.push_back(r.b);
+  }
+  c->pending.clear();
+  return CTPN_OK;
+}
+
+// one block for everything a submitted batch returns (device side and, mirrored, every slot's page-locked host side)
+struct PackLayout { size_t tlb, tls, keep, kcnt, rois, rcnt, total; };
+static PackLayout pack_layout(size_t mb, size_t post) {
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  PackLayout L; size_t o = 0;
+  L.tlb = o; o = al(o + mb * post * 4 * sizeof(float));
+  L.tls = o; o = al(o + mb * post * sizeof(float));
+  L.keep = o; o = al(o + mb * post * sizeof(int));
+  L.kcnt = o; o = al(o + mb * sizeof(int));
+  L.rois = o; o = al(o + mb * post * 5 * sizeof(float));
+  L.rcnt = o; o = al(o + mb * sizeof(int));
+  L.total = o;
+  return L;
+}
+
+static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, int max_w, int precision, bool postproc_only) {
+  if (!out) return fail(CTPN_ERR_ARG, "ctpn_create: out is null");
+  *out = nullptr;
+  if (max_batch <= 0 || max_h < 16 || max_w < 16) return fail(CTPN_ERR_ARG, "ctpn_create: max_batch > 0 and max_h, max_w >= 16 required");
+  if (precision < CTPN_PREC_FP32 || precision > CTPN_PREC_SPLIT) return fail(CTPN_ERR_ARG, "ctpn_create: unknown precision");
+  int ndev = ctpn_device_count();
+  if (ndev <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_create: no HIP device visible (this library has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) {
+    // the usual cause on a multi-GPU node: a rank whose LOCAL_RANK is not among the devices its environment lets it see
+    const char* hv = getenv("HIP_VISIBLE_DEVICES");
+    const char* rv = getenv("ROCR_VISIBLE_DEVICES");
+    return fail(CTPN_ERR_ARG, "ctpn_create: device_id " + std::to_string(device_id) + " out of range: " + std::to_string(ndev) +
+                " device(s) visible (HIP_VISIBLE_DEVICES=" + (hv ? hv : "unset") + ", ROCR_VISIBLE_DEVICES=" + (rv ? rv : "unset") + "); one process per GPU needs LOCAL_RANK < that count");
+  }
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  hipDeviceProp_t prop;
+  CTPN_HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
+    return fail(CTPN_ERR_NODEVICE, std::string("ctpn_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
+
+  ctpn_ctx* c = new ctpn_ctx();
+  c->device = device_id; c->max_batch = max_batch; c->max_h = max_h; c->max_w = max_w;
+  c->prec = prec_dtype(precision);
+  c->es = dtype_bytes(c->prec);
+  c->wx_row_bytes = c->prec == DType::SPLIT ? (size_t)3 * 512 * 2 : (size_t)512 * c->es;
+  // 16-bit throughput modes: the recurrent product h Wh on split-bf16 MFMAs by default (state, gates, accumulation fp32; three bf16 terms per
+  // product: |lstm_out - exact-fp32 kernel| < 3e-5, two orders below the modes' own conv rounding; 0.32 -> 0.16 ms per 32-image batch).
+  // split precision takes the split-bf16 recurrence too since round 6: it IS this mode's arithmetic ((hi, lo) bf16 pairs, three MFMA terms, fp32
+  // accumulate: what its convolutions do), the bench's accuracy object does not move (cls_prob 3.48e-5, 100 % lines either way) and a lone image
+  // saves 0.2 ms of its 2.05 (343 -> 138 us at batch 32). fp32 keeps the exact kernel; option lstm_split = 0 restores it anywhere.
+  c->lstm_split = (dtype_is_half(c->prec) || c->prec == DType::SPLIT) ? 1 : 0;
+  c->tail_confine = 0;
+  c->postproc_only = postproc_only;
+  {
+    // host workers: the node's cores divided by the ranks that share it (torchrun exports LOCAL_WORLD_SIZE), CTPN_HOST_THREADS
+    // overrides; CTPN_AFFINITY=1 pins them to the block of cores [local_rank * budget, ...)
+    const unsigned hw = std::thread::hardware_concurrency();
+    c->host_threads = ctpn_host_thread_budget((int)(hw ? hw : 1), env_int("LOCAL_WORLD_SIZE", 1), env_int("CTPN_HOST_THREADS", 0));
+    const int first_cpu = env_int("CTPN_AFFINITY", 0) ? env_int("LOCAL_RANK", 0) * c->host_threads : -1;
+    c->pool.reset(new HostPool(c->host_threads, first_cpu));
+  }
+  int rc = CTPN_OK;
+  auto A = [&](void** p, size_t bytes, bool zero) { if (rc == CTPN_OK) rc = dev_alloc(c, p, bytes, zero); };
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(CTPN_ERR_HIP, "hipStreamCreate failed"); }
+  // (the proposal stream at the highest stream priority was measured in round 2: no effect -- placement is by free resources)
+  // (the proposal stream at the highest stream priority: measured in round 6 with the tail confined -- 1163 against 1164 images/s in split precision,
+  // -0.2 % in bf16: the dispatcher does not hand CUs to the 1024-thread NMS workgroups any sooner. Not used.)
+  if (hipStreamCreateWithFlags(&c->stream_p, hipStreamNonBlocking) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return fail(CTPN_ERR_HIP, "hipStreamCreate failed"); }
+  if (hipEventCreateWithFlags(&c->ev_conv, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess) {
+    ctpn_destroy(c); return fail(CTPN_ERR_HIP, "ctpn_create: events");
+  }
+  for (auto& sl : c->slot) {
+    const size_t mb = (size_t)max_batch;
+    const PackLayout L = pack_layout(mb, (size_t)c->post_max);
+    bool ok = hipHostMalloc((void**)&sl.pack, L.total) == hipSuccess;
+    if (ok) {
+      sl.tlb = (float*)(sl.pack + L.tlb); sl.tls = (float*)(sl.pack + L.tls); sl.keep = (int*)(sl.pack + L.keep); sl.kcnt = (int*)(sl.pack + L.kcnt);
+      sl.rois = (float*)(sl.pack + L.rois); sl.rcnt = (int*)(sl.pack + L.rcnt);
+    }
+    ok = ok &&
+              hipHostMalloc((void**)&sl.im_info, mb * 3 * sizeof(float)) == hipSuccess &&
+              hipHostMalloc((void**)&sl.crecs, mb * 2 * CONN_CAP * 9 * sizeof(double)) == hipSuccess &&
+              hipHostMalloc((void**)&sl.ccnt, mb * 3 * sizeof(int)) == hipSuccess &&
+              hipEventCreateWithFlags(&sl.ev_heads, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&sl.ev_decoded, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { ctpn_destroy(c); return fail(CTPN_ERR_HIP, "ctpn_create: pinned host buffers / events"); }
+  }
+
+  const int hf = lvl(max_h, 4), wf = lvl(max_w, 4);
+  c->m5_max = (size_t)max_batch * hf * wf;
+  if (!postproc_only) {
+  A((void**)&c->arena, (size_t)CTPN_WEIGHT_FLOATS * sizeof(float), false);
+  A((void**)&c->w_first, 27 * 64 * sizeof(float), false);
+  A(&c->w_first_frags, CF_FRAGS_TOTAL, true);
+  for (int i = 0; i < 14; ++i) {
+    A((void**)&c->b_conv[i], (size_t)kConvs[i].co * sizeof(float), true);
+    // 16-bit / fp32: [Co][9 Ci] elements; split precision: [Co][9][3 Ci] bf16
+    if (i > 0) A(&c->wt_conv[i], (size_t)kConvs[i].co * 9 * kConvs[i].ci * (c->prec == DType::SPLIT ? 6 : c->es), true);
+  }
+  A(&c->wt_x, (size_t)1024 * c->wx_row_bytes, true);
+  if (dtype_is_half(c->prec)) A(&c->wt_xf, (size_t)1024 * 512 * 2, true);
+  A((void**)&c->b_x, 1024 * sizeof(float), true);
+  A((void**)&c->wh, (size_t)2 * 128 * 512 * sizeof(float), true);
+  A((void**)&c->wt_fc, (size_t)512 * 256 * sizeof(float), true);
+  A((void**)&c->b_fc, 512 * sizeof(float), true);
+  A((void**)&c->wt_h, (size_t)64 * 512 * sizeof(float), true);
+  A((void**)&c->b_h, 64 * sizeof(float), true);
+  A((void**)&c->wt_fold, (size_t)64 * 256 * sizeof(float), true);
+  A((void**)&c->b_fold, 64 * sizeof(float), true);
+
+  for (int i = 0; i < 14; ++i) {
+    const int hl = lvl(max_h, kConvs[i].level), wl = lvl(max_w, kConvs[i].level);
+    // + slack: the weights-in-registers conv kernel fetches edge tiles' input windows without clamping (conv3x3.hip), i.e. up to
+    // 8 bordered rows + one window row past the last image; those pixels only feed outputs that are never stored
+    // bytes per pixel: channels x element size; split precision: [hi | lo] planes = 4 bytes per channel, and rpn_conv/3x3 (which feeds the
+    // LSTM projection GEMM) [hi | lo | hi] = 6
+    const size_t pix_b = (size_t)kConvs[i].co * ((c->prec == DType::SPLIT && i == 13) ? 6 : c->es);
+    c->act_conv_bytes[i] = ((size_t)max_batch * (hl + 2) * (wl + 2) + act_slack_pixels(wl)) * pix_b;
+    const size_t front = act_front_pixels(wl) * pix_b;
+    A(&c->act_conv[i], front + c->act_conv_bytes[i], true);
+    if (c->act_conv[i]) c->act_conv[i] = (char*)c->act_conv[i] + front;     // allocs[] keeps the pointer hipFree needs
+  }
+  {
+    const int pool_src[4] = {1, 3, 6, 9};
+    for (int p = 0; p < 4; ++p) {
+      const int hl = lvl(max_h, p + 1), wl = lvl(max_w, p + 1);
+      c->act_pool_bytes[p] = ((size_t)max_batch * (hl + 2) * (wl + 2) + act_slack_pixels(wl)) * kConvs[pool_src[p]].co * c->es;
+      const size_t front = act_front_pixels(wl) * kConvs[pool_src[p]].co * c->es;
+      A(&c->act_pool[p], front + c->act_pool_bytes[p], true);
+      if (c->act_pool[p]) c->act_pool[p] = (char*)c->act_pool[p] + front;
+    }
+  }
+  if (dtype_is_half(c->prec)) { c->q_img_bytes = conv1_q_bytes(max_batch, max_h, max_w); A(&c->q_img, c->q_img_bytes, true); }
+  A((void**)&c->img_dev, (size_t)max_batch * max_h * max_w * 3 * sizeof(float), false);
+  c->img_dev_b[0] = c->img_dev;
+  A((void**)&c->img_dev_b[1], (size_t)max_batch * max_h * max_w * 3 * sizeof(float), false);
+  if (rc == CTPN_OK) {
+    bool ok = hipStreamCreateWithFlags(&c->stream_c, hipStreamNonBlocking) == hipSuccess;
+    for (int b = 0; b < 2 && ok; ++b)
+      ok = hipEventCreateWithFlags(&c->ev_copied[b], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_consumed[b], hipEventDisableTiming) == hipSuccess;
+    if (!ok) rc = fail(CTPN_ERR_HIP, "ctpn_create: copy stream / events");
+  }
+  A((void**)&c->xp, c->m5_max * 1024 * sizeof(float), false);
+  A((void**)&c->lstm_out, c->m5_max * 256 * sizeof(float), false);
+  A((void**)&c->fc_out, c->m5_max * 512 * sizeof(float), false);
+  A((void**)&c->heads, c->m5_max * 64 * sizeof(float), true);
+  }  // !postproc_only
+  A((void**)&c->cls_prob, c->m5_max * 20 * sizeof(float), false);
+  A((void**)&c->bbox_pred, c->m5_max * 40 * sizeof(float), false);
+  A((void**)&c->cls_in, c->m5_max * 20 * sizeof(float), false);
+  A((void**)&c->bbox_in, c->m5_max * 40 * sizeof(float), false);
+  c->npad_max = next_pow2(hf * wf * 10);
+  A((void**)&c->keys, (size_t)max_batch * c->npad_max * sizeof(unsigned long long), false);
+  A((void**)&c->keys_tmp, (size_t)max_batch * c->npad_max * sizeof(unsigned long long), false);
+  A((void**)&c->boxes4, (size_t)max_batch * hf * wf * 10 * 4 * sizeof(float), false);
+  A((void**)&c->sorted_boxes, (size_t)max_batch * c->topn_max * 4 * sizeof(float), false);
+  A((void**)&c->sorted_scores, (size_t)max_batch * c->topn_max * sizeof(float), false);
+  A((void**)&c->valid_counts, (size_t)max_batch * sizeof(int), true);
+  A((void**)&c->keep_idx, (size_t)max_batch * c->topn_max * sizeof(int), false);
+  {
+    // what a submitted batch hands back to the host -- connector front end (tl_*), rois and their counts -- as views into one block
+    const PackLayout L = pack_layout((size_t)max_batch, (size_t)c->post_max);
+    c->pack_bytes = L.total;
+    A((void**)&c->out_pack, L.total, true);
+    if (c->out_pack) {
+      c->tl_boxes = (float*)(c->out_pack + L.tlb); c->tl_scores = (float*)(c->out_pack + L.tls); c->tl_keep = (int*)(c->out_pack + L.keep);
+      c->tl_keep_counts = (int*)(c->out_pack + L.kcnt); c->rois = (float*)(c->out_pack + L.rois); c->keep_counts = (int*)(c->out_pack + L.rcnt);
+    }
+  }
+  A((void**)&c->kept_spill, (size_t)max_batch * c->topn_max * 4 * sizeof(float), false);
+  A((void**)&c->sorted_anchor, (size_t)max_batch * c->topn_max * sizeof(int), false);
+  A((void**)&c->roi_anchor, (size_t)max_batch * c->post_max * sizeof(int), true);
+  A((void**)&c->tl_counts, (size_t)max_batch * sizeof(int), true);
+  A((void**)&c->tl_spill, (size_t)max_batch * c->post_max * 4 * sizeof(float), false);
+  A((void**)&c->nms_mw_scratch, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, true);
+  A((void**)&c->nms_colid, (size_t)NMS_MW_CAP_BATCH * ((c->topn_max + 15) & ~15), true);
+  A((void**)&c->conn_recs, (size_t)max_batch * 2 * CONN_CAP * 9 * sizeof(double), false);
+  A((void**)&c->conn_counts, (size_t)max_batch * 3 * sizeof(int), true);
+  A((void**)&c->conn_scratch, (size_t)max_batch * 1024 * 20 * sizeof(double), false);
+  A((void**)&c->im_info_dev, (size_t)max_batch * 3 * sizeof(float), true);
+  if (rc == CTPN_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_create: sync failed");
+  if (rc != CTPN_OK) { ctpn_destroy(c); return rc; }
+  *out = c;
+  return CTPN_OK;
+}
+
+// ---- options: behaviour switches of ONE ctx (two ctxs in a process can choose differently; nothing here is read from the environment) ----
+// one row per option, in ABI order (ctpn_option_name's index): name, the member it sets, the range ctpn_set_option accepts
+struct Option { const char* name; int ctpn_ctx::* member; int lo, hi; };
+static const Option kOptions[] = {
+    {"keep_acts", &ctpn_ctx::keep_acts, 0, 1},
+    {"conv1_kernel", &ctpn_ctx::conv1_mfma, 0, 2},
+    {"conv1_fuse", &ctpn_ctx::conv1_fuse, 0, 1},
+    {"lstm_split", &ctpn_ctx::lstm_split, 0, 1},
+    {"nms_columns", &ctpn_ctx::nms_columns, 0, 3},
+    {"nms_check", &ctpn_ctx::nms_check, 0, 1},
+    {"connect_device", &ctpn_ctx::connect_device, 0, 1},
+    {"tail_overlap", &ctpn_ctx::tail_overlap, 0, 1},
+    {"conv_p64", &ctpn_ctx::conv_p64, 0, 1},
+    {"tail_confine", &ctpn_ctx::tail_confine, 0, 1},
+    {"nms_prefix", &ctpn_ctx::nms_prefix, 0, 1},
+    {"debug_hog", &ctpn_ctx::debug_hog, 0, 200000},
+    {"debug_nms", &ctpn_ctx::debug_nms, 0, 15},
+    {"split_edge", &ctpn_ctx::split_edge, 0, 1},
+};
+static const Option* find_option(const std::string& k) {
+  for (const Option& o : kOptions) if (k == o.name) return &o;
+  return nullptr;
+}
+
+}  // namespace ctpn
+
+// =============================================================================================
+extern "C" {
+
+int ctpn_abi_version(void) { return CTPN_ABI_VERSION; }
+const char* ctpn_last_error(void) { return t_err.c_str(); }
+int ctpn_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+int ctpn_host_thread_budget(int cpu_count, int local_world_size, int requested) {
+  if (requested > 0) return requested > 256 ? 256 : requested;
+  if (cpu_count < 1) cpu_count = 1;
+  if (local_world_size < 1) local_world_size = 1;
+  int b = cpu_count / local_world_size;
+  return b < 1 ? 1 : (b > 32 ? 32 : b);      // 32 = images per batch of the benchmark configuration: more threads have nothing to do
+}
+
+int ctpn_create(ctpn_ctx** out, int device_id, int max_batch, int max_h, int max_w, int precision) {
+  return create_impl(out, device_id, max_batch, max_h, max_w, precision, false);
+}
+
+int ctpn_create_postproc(ctpn_ctx** out, int device_id, int max_batch, int max_hf, int max_wf) {
+  if (max_hf < 1 || max_wf < 1 || max_hf > (1 << 20) / 16 || max_wf > (1 << 20) / 16) return fail(CTPN_ERR_ARG, "ctpn_create_postproc: feature-map size out of range");
+  return create_impl(out, device_id, max_batch, max_hf * 16, max_wf * 16, CTPN_PREC_FP32, true);
+}
+
+int ctpn_option_count(void) { return (int)(sizeof(kOptions) / sizeof(kOptions[0])); }
+const char* ctpn_option_name(int index) { return index >= 0 && index < ctpn_option_count() ? kOptions[index].name : nullptr; }
+int ctpn_set_option(ctpn_ctx* c, const char* key, int value) {
+  if (!c || !key) return fail(CTPN_ERR_ARG, "ctpn_set_option: null pointer");
+  const Option* o = find_option(key);
+  if (!o) return fail(CTPN_ERR_ARG, std::string("ctpn_set_option: unknown option ") + key);
+  if (value < o->lo || value > o->hi) return fail(CTPN_ERR_ARG, std::string("ctpn_set_option: value out of range for ") + key);
+  if (c->*(o->member) == value) return CTPN_OK;
+  // a switch changes what the queued work would read / which stream runs it: drain first
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  for (auto& sl : c->slot) if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_set_option: a submitted batch has not been collected");
+  c->tail_pending = false;
+  c->nms_mw_dirty = true;           // both streams are drained: the next proposal launch re-zeroes the multi-workgroup NMS's scratch (8 KB memset)
+  c->*(o->member) = value;
+  return CTPN_OK;
+}
+int ctpn_get_option(ctpn_ctx* c, const char* key, int* value_out) {
+  if (!c || !key || !value_out) return fail(CTPN_ERR_ARG, "ctpn_get_option: null pointer");
+  const Option* o = find_option(key);
+  if (!o) return fail(CTPN_ERR_ARG, std::string("ctpn_get_option: unknown option ") + key);
+  *value_out = c->*(o->member);
+  return CTPN_OK;
+}
+
+int ctpn_host_threads(ctpn_ctx* c, int* threads_out) {
+  if (!c || !threads_out) return fail(CTPN_ERR_ARG, "null pointer");
+  *threads_out = c->host_threads;
+  return CTPN_OK;
+}
+
+int ctpn_destroy(ctpn_ctx* c) {
+  if (!c) return CTPN_OK;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->stream_p) (void)hipStreamSynchronize(c->stream_p);
+  if (c->stream_c) { (void)hipStreamSynchronize(c->stream_c); (void)hipStreamDestroy(c->stream_c); }
+  for (int b = 0; b < 2; ++b) { if (c->pin_stage[b]) (void)hipHostFree(c->pin_stage[b]); if (c->ev_h2d_done[b]) (void)hipEventDestroy(c->ev_h2d_done[b]); }
+  for (int b = 0; b < 2; ++b) { if (c->ev_copied[b]) (void)hipEventDestroy(c->ev_copied[b]); if (c->ev_consumed[b]) (void)hipEventDestroy(c->ev_consumed[b]); }
+  for (auto& sl : c->slot) {
+    for (void* p : {(void*)sl.pack, (void*)sl.im_info, (void*)sl.crecs, (void*)sl.ccnt}) if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : {sl.ev_heads, sl.ev_decoded, sl.ev_done}) if (e) (void)hipEventDestroy(e);
+  }
+  for (hipEvent_t e : {c->ev_conv, c->ev_tail}) if (e) (void)hipEventDestroy(e);
+  for (auto& j : c->jpeg) {
+    if (j.coef_host) (void)hipHostFree(j.coef_host);
+    if (j.qt_host) (void)hipHostFree(j.qt_host);
+    for (void* p : {(void*)j.coef_dev, (void*)j.qt_dev, (void*)j.out_dev}) if (p) (void)hipFree(p);
+    for (hipEvent_t e : {j.ev_h2d, j.ev_ready, j.ev_consumed}) if (e) (void)hipEventDestroy(e);
+  }
+  for (void* p : {(void*)c->jpeg_planes, (void*)c->jpeg_raw}) if (p) (void)hipFree(p);
+  for (void* p : c->jpeg_retired) (void)hipFree(p);
+  if (c->stream_p) (void)hipStreamDestroy(c->stream_p);
+  for (auto& r : c->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+  for (auto e : c->free_events) (void)hipEventDestroy(e);
+  for (void* p : c->allocs) (void)hipFree(p);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+  return CTPN_OK;
+}
+
+int ctpn_sync(ctpn_ctx* c) {
+  if (!c) return fail(CTPN_ERR_ARG, "null ctx");
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  if (c->stream_c) CTPN_HIP_TRY(hipStreamSynchronize(c->stream_c));      // staged copies, ctpn_decode_jpeg_batch
+  return CTPN_OK;
+}
+int ctpn_stream(ctpn_ctx* c, void** stream_out) {
+  if (!c || !stream_out) return fail(CTPN_ERR_ARG, "null pointer");
+  *stream_out = (void*)c->stream;
+  return CTPN_OK;
+}
+
+int ctpn_profile_enable(ctpn_ctx* c, int on) {
+  if (!c) return fail(CTPN_ERR_ARG, "null ctx");
+  if (!on) { int rc = prof_drain(c); if (rc) return rc; }
+  c->prof = on != 0;
+  c->prof_mode = on == 2 ? 2 : 1;
+  return CTPN_OK;
+}
+int ctpn_profile_reset(ctpn_ctx* c) {
+  if (!c) return fail(CTPN_ERR_ARG, "null ctx");
+  int rc = prof_drain(c);
+  if (rc) return rc;
+  for (int k = 0; k < CTPN_KIND_COUNT; ++k) { c->prof_ms[k] = 0; c->prof_n[k] = 0; c->prof_work[k] = 0; }
+  return CTPN_OK;
+}
+int ctpn_profile_read(ctpn_ctx* c, int kind, double* ms, long long* launches, double* work) {
+  if (!c) return fail(CTPN_ERR_ARG, "null ctx");
+  if (kind < 0 || kind >= CTPN_KIND_COUNT) return fail(CTPN_ERR_ARG, "kind out of range");
+  int rc = prof_drain(c);
+  if (rc) return rc;
+  if (ms) *ms = c->prof_ms[kind];
+  if (launches) *launches = c->prof_n[kind];
+  if (work) *work = c->prof_work[kind];
+  return CTPN_OK;
+}
+
+}  // extern "C"

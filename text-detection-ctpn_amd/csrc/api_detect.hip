@@ -1,0 +1,196 @@
+// C ABI of libctpn_hip.so, detect unit: forward + proposal layer + connector front end as one asynchronous submit / collect pair, the
+// synchronous ctpn_detect on top of it, the host connector's entry point and the device connector's test hook.
+#include "ctx.h"
+
+namespace ctpn {
+
+// lone: a synchronous ctpn_detect with nothing else in flight on this ctx -- the proposal layer and the connector front end then follow the
+// forward on ITS stream instead of hopping to the proposal stream (an event record + a cross-queue wait: ~12 us of a lone image's millisecond;
+// the second stream exists to run the tail under the NEXT batch's convolutions, and there is no next batch here)
+static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone) {
+  if (!c) return fail(CTPN_ERR_ARG, "ctpn_detect_submit: null ctx");
+  if (slot < 0 || slot > 1) return fail(CTPN_ERR_ARG, "ctpn_detect_submit: slot must be 0 or 1");
+  ctpn_ctx::Slot& sl = c->slot[slot];
+  if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_detect_submit: slot still holds an uncollected batch");
+  int rc = forward_impl(c, images, 0, images_on_device, n, h, w, c->tail_overlap != 0);
+  if (rc) {
+    // a forward that failed midway may have consumed the cross-stream hand-over state (tail_pending is cleared when the wait is ENQUEUED,
+    // the events are recorded later): drain both streams so that a retry starts from a quiet ctx, keeping the first error text
+    const std::string first = ctpn_last_error();
+    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stream_p);
+    c->tail_pending = false; c->ev_last_decoded = nullptr; c->ev_last_done = nullptr;
+    return fail(rc, first);
+  }
+  for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)h; sl.im_info[3 * i + 1] = (float)w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
+  const int post = c->post_max;
+  hipStream_t p = lone ? c->stream : c->stream_p;
+  if (!lone) {
+    CTPN_HIP_TRY(hipEventRecord(sl.ev_heads, c->stream));
+    CTPN_HIP_TRY(hipStreamWaitEvent(p, sl.ev_heads, 0));
+  }
+  // cfg.TEST.* defaults (reference lib/fast_rcnn/config.py:175-183)
+  rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, 12000, post, 0.7f, 8.0f, p, sl.ev_decoded);
+  if (rc) return rc;
+  c->ev_last_decoded = sl.ev_decoded;
+  // TextDetector.detect front end on device: score > 0.7 prefix, boxes / scale, NMS 0.2 (detectors.py:21-30)
+  {
+    Timed t(c, CTPN_KIND_NMS, (double)n * post * 24.0, p);
+    if ((rc = launch_lines_prep(c->rois, c->keep_counts, c->im_info_dev, post, 0.7f, c->tl_boxes, c->tl_scores, c->tl_counts, n, p))) return rc;
+    float max_scale = 0.f;
+    for (int i = 0; i < n; ++i) max_scale = sl.im_info[3 * i + 2] > max_scale ? sl.im_info[3 * i + 2] : max_scale;
+    if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, 0.2f, max_scale)) {
+      if ((rc = launch_nms_columns(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
+                                   c->tl_spill, n, lvl(w, 4), p, nullptr, nullptr, c->im_info_dev, nms_multi_wg(c, n, 0) ? c->nms_mw_scratch : nullptr))) return rc;
+    } else if ((rc = launch_nms(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
+                                c->tl_spill, n, p))) return rc;
+  }
+  if (c->connect_device) {
+    // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect)
+    if ((rc = launch_connect(c->tl_boxes, c->tl_scores, c->tl_keep, c->tl_keep_counts, post, c->im_info_dev, c->conn_recs, c->conn_counts,
+                             c->conn_scratch, CONN_CAP, n, p))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs, c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt, c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
+  }
+  CTPN_HIP_TRY(hipMemcpyAsync(sl.pack, c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));      // tl_* (host connector), rois, counts: one copy
+  CTPN_HIP_TRY(hipEventRecord(sl.ev_done, p));
+  c->ev_last_done = sl.ev_done;
+  sl.n = n; sl.h = h; sl.w = w; sl.busy = true;
+  return CTPN_OK;
+}
+static int detect_submit_impl(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone) {
+  const int rc = detect_submit_body(c, images, images_on_device, n, h, w, scales, slot, lone);
+  if (rc != CTPN_OK && c) c->nms_mw_dirty = true;        // an error anywhere in a submit (the connector NMS's launch included): see common.h, NMS_MW_OVERFLOW_OFF
+  return rc;
+}
+
+}  // namespace ctpn
+
+extern "C" {
+
+int ctpn_text_lines(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode, int device_id, double* recs_out,
+                    int capacity, int* count_out) {
+  if (!count_out) return fail(CTPN_ERR_ARG, "ctpn_text_lines: count_out is null");
+  *count_out = 0;
+  if (r > 0 && (!boxes || !scores)) return fail(CTPN_ERR_ARG, "ctpn_text_lines: null input");
+  std::vector<double> recs;
+  int rc = text_lines_host(boxes, scores, r, im_h, im_w, mode, device_id, recs);
+  if (rc) return rc;
+  const int cnt = (int)(recs.size() / 9);
+  *count_out = cnt;
+  if (cnt > capacity) return fail(CTPN_ERR_CAPACITY, "ctpn_text_lines: more lines than capacity");
+  if (cnt && !recs_out) return fail(CTPN_ERR_ARG, "ctpn_text_lines: recs_out is null");
+  if (cnt) std::memcpy(recs_out, recs.data(), recs.size() * sizeof(double));
+  return CTPN_OK;
+}
+
+int ctpn_detect_submit(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot) {
+  return detect_submit_impl(c, images, images_on_device, n, h, w, scales, slot, false);
+}
+
+int ctpn_detect_collect(ctpn_ctx* c, int slot, int mode, double* recs_out, int line_capacity, int* line_counts, float* rois_out,
+                        int* roi_counts) {
+  if (!c || !recs_out || !line_counts) return fail(CTPN_ERR_ARG, "ctpn_detect_collect: null pointer");
+  if (slot < 0 || slot > 1) return fail(CTPN_ERR_ARG, "ctpn_detect_collect: slot must be 0 or 1");
+  if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "ctpn_detect_collect: mode must be H(0) or O(1)");
+  ctpn_ctx::Slot& sl = c->slot[slot];
+  if (!sl.busy) return fail(CTPN_ERR_STATE, "ctpn_detect_collect: nothing was submitted to this slot");
+  CTPN_HIP_TRY(hipEventSynchronize(sl.ev_done));
+  sl.busy = false;
+  const int n = sl.n, h = sl.h, w = sl.w, post = c->post_max;
+  if (rois_out) std::memcpy(rois_out, sl.rois, (size_t)n * post * 5 * sizeof(float));
+  if (roi_counts) std::memcpy(roi_counts, sl.rcnt, (size_t)n * sizeof(int));
+  if (c->connect_device) {
+    for (int i = 0; i < n; ++i) {
+      if (sl.ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
+      const int cnt = sl.ccnt[3 * i + (mode == CTPN_MODE_O ? 1 : 0)];
+      line_counts[i] = cnt;
+      if (cnt > line_capacity || cnt > CONN_CAP) return fail(CTPN_ERR_CAPACITY, "ctpn_detect: more lines than line_capacity");
+      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * CONN_CAP * 9, (size_t)cnt * 9 * sizeof(double));
+    }
+    return CTPN_OK;
+  }
+  std::vector<int> status(n, 0);
+  std::vector<std::string> errs(n);
+  auto work = [&](int i) {
+    const int nk = sl.kcnt[i];
+    std::vector<float> kb((size_t)nk * 4), ks(nk);
+    for (int j = 0; j < nk; ++j) {
+      const int src = sl.keep[(size_t)i * post + j];
+      std::memcpy(&kb[4 * j], &sl.tlb[((size_t)i * post + src) * 4], 4 * sizeof(float));
+      ks[j] = sl.tls[(size_t)i * post + src];
+    }
+    std::vector<double> recs;
+    int st = connect_lines(kb.data(), ks.data(), nk, h, w, mode, recs);
+    if (st) { status[i] = st; errs[i] = ctpn_last_error(); return; }
+    const int cnt = (int)(recs.size() / 9);
+    line_counts[i] = cnt;
+    if (cnt > line_capacity) { status[i] = CTPN_ERR_CAPACITY; errs[i] = "ctpn_detect: more lines than line_capacity"; return; }
+    if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, recs.data(), recs.size() * sizeof(double));
+  };
+  c->pool->run(n, work);      // persistent workers of the ctx (ctpn_host_thread_budget), one image per task
+  for (int i = 0; i < n; ++i) if (status[i]) return fail(status[i], errs[i]);
+  return CTPN_OK;
+}
+
+int ctpn_detect(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int mode,
+                double* recs_out, int line_capacity, int* line_counts, float* rois_out, int* roi_counts) {
+  if (!c || !recs_out || !line_counts) return fail(CTPN_ERR_ARG, "ctpn_detect: null pointer");
+  if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "ctpn_detect: mode must be H(0) or O(1)");
+  int slot = c->slot[0].busy ? 1 : 0;
+  const bool lone = !c->slot[0].busy && !c->slot[1].busy && c->tail_overlap == 0;
+  int rc = detect_submit_impl(c, images, images_on_device, n, h, w, scales, slot, lone);
+  if (rc) return rc;
+  return ctpn_detect_collect(c, slot, mode, recs_out, line_capacity, line_counts, rois_out, roi_counts);
+}
+
+// TextDetector.detect entirely on the device for one image's rois (the asynchronous detect path with option connect_device = 1):
+// lines_prep_kernel (score > 0.7 prefix, boxes / scale) -> nms_kernel (0.2) -> connect_kernel. Test hook: lets the parity
+// tests feed the reference-generated rois straight into connect_kernel.
+int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im_w, float scale, int mode, double* recs_out,
+                       int capacity, int* count_out) {
+  if (!count_out) return fail(CTPN_ERR_ARG, "ctpn_debug_connect: count_out is null");
+  *count_out = 0;
+  if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "ctpn_debug_connect: mode must be H(0) or O(1)");
+  if (r < 0 || r > 1000 || (r > 0 && !rois)) return fail(CTPN_ERR_ARG, "ctpn_debug_connect: 0 <= r <= 1000 rows of [score,x1,y1,x2,y2]");
+  const int ndev = ctpn_device_count();
+  if (ndev <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_connect: no HIP device visible (this library has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev) return fail(CTPN_ERR_ARG, "ctpn_debug_connect: device_id out of range");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  const int post = 1000;
+  char* buf = nullptr;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_rois = take((size_t)(post + 1) * 5 * 4), o_cnt = take(16), o_info = take(16), o_tlb = take((size_t)post * 16), o_tls = take((size_t)post * 4),
+               o_tlc = take(16), o_keep = take((size_t)post * 4), o_kc = take(16), o_spill = take((size_t)post * 16),
+               o_recs = take((size_t)2 * CONN_CAP * 9 * 8), o_cc = take(16), o_scr = take((size_t)1024 * 20 * 8);
+  CTPN_HIP_TRY(hipMalloc((void**)&buf, off));
+  hipStream_t st = nullptr;
+  int rc = CTPN_OK;
+  auto done = [&](int code) { if (st) (void)hipStreamDestroy(st); (void)hipFree(buf); return code; };
+#define DC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(CTPN_ERR_HIP, std::string("ctpn_debug_connect: ") + hipGetErrorString(e_))); } while (0)
+  DC_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  DC_TRY(hipMemsetAsync(buf, 0, off, st));
+  const float info[3] = {(float)im_h, (float)im_w, scale};
+  if (r) DC_TRY(hipMemcpyAsync(buf + o_rois, rois, (size_t)r * 5 * 4, hipMemcpyHostToDevice, st));
+  DC_TRY(hipMemcpyAsync(buf + o_cnt, &r, 4, hipMemcpyHostToDevice, st));
+  DC_TRY(hipMemcpyAsync(buf + o_info, info, 12, hipMemcpyHostToDevice, st));
+  if ((rc = launch_lines_prep((const float*)(buf + o_rois), (const int*)(buf + o_cnt), (const float*)(buf + o_info), post, 0.7f, (float*)(buf + o_tlb),
+                              (float*)(buf + o_tls), (int*)(buf + o_tlc), 1, st))) return done(rc);
+  if ((rc = launch_nms((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_tlc), post, 0.2f, post, (int*)(buf + o_keep), post,
+                       (int*)(buf + o_kc), nullptr, (float*)(buf + o_spill), 1, st))) return done(rc);
+  if ((rc = launch_connect((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_keep), (const int*)(buf + o_kc), post,
+                           (const float*)(buf + o_info), (double*)(buf + o_recs), (int*)(buf + o_cc), (double*)(buf + o_scr), CONN_CAP, 1, st))) return done(rc);
+  int cc[3] = {0, 0, 0};
+  DC_TRY(hipMemcpyAsync(cc, buf + o_cc, 12, hipMemcpyDeviceToHost, st));
+  DC_TRY(hipStreamSynchronize(st));
+  if (cc[2] != 0) return done(fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)"));
+  const int cnt = cc[mode == CTPN_MODE_O ? 1 : 0];
+  *count_out = cnt;
+  if (cnt > capacity || cnt > CONN_CAP) return done(fail(CTPN_ERR_CAPACITY, "ctpn_debug_connect: more lines than capacity"));
+  if (cnt && !recs_out) return done(fail(CTPN_ERR_ARG, "ctpn_debug_connect: recs_out is null"));
+  if (cnt) DC_TRY(hipMemcpy(recs_out, buf + o_recs + (size_t)(mode == CTPN_MODE_O ? 1 : 0) * CONN_CAP * 9 * 8, (size_t)cnt * 9 * 8, hipMemcpyDeviceToHost));
+#undef DC_TRY
+  return done(CTPN_OK);
+}
+
+}  // extern "C"

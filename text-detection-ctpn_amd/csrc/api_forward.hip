@@ -1,0 +1,292 @@
+// C ABI of libctpn_hip.so, forward unit: image staging, the network forward on the ctx's streams, tensor read-back.
+#include "ctx.h"
+
+namespace ctpn {
+
+// host copy on a few pool threads: one core moves ~10 GB/s, a 52 MB batch would cost 5 ms of the submitting thread
+static void parallel_memcpy(HostPool* pool, void* dst, const void* src, size_t bytes) {
+  const size_t chunk = (size_t)8 << 20;
+  const int nt = (int)std::min<size_t>(8, (bytes + chunk - 1) / chunk);
+  if (nt <= 1 || !pool) { std::memcpy(dst, src, bytes); return; }
+  const size_t per = ((bytes + nt - 1) / nt + 63) & ~(size_t)63;
+  pool->run(nt, [=](int i) {
+    const size_t lo = (size_t)i * per, hi = std::min(bytes, lo + per);
+    if (lo < hi) std::memcpy((char*)dst + lo, (const char*)src + lo, hi - lo);
+  }, 8);
+}
+
+int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p) {
+  if (!c || !images) return fail(CTPN_ERR_ARG, "null pointer");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_forward: post-processing-only ctx (ctpn_create_postproc) has no network");
+  if (!c->weights_loaded) return fail(CTPN_ERR_STATE, "ctpn_forward: weights not loaded");
+  if (n <= 0 || n > c->max_batch || h < 16 || w < 16 || h > c->max_h || w > c->max_w)
+    return fail(CTPN_ERR_CAPACITY, "ctpn_forward: batch/size outside what the ctx was created for (h, w >= 16)");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  int rc;
+  hipStream_t ts = tail_on_p ? c->stream_p : s;      // stream of the recurrent tail
+  if (!tail_on_p) {
+    // a forward that keeps everything on `s` rewrites xp / lstm_out / heads there: after their readers on stream_p -- the previous
+    // asynchronous batch's tail (if it ran there) and its decode kernel. The decode kernel reads `heads` only, so that wait sits in front of
+    // the GEMM that writes `heads`, at the END of this forward (at its start it put the cross-stream round trip heads -> decode -> next
+    // forward, ~45 us, between every two batches: round 4's batch-1 and batch-32 timelines)
+    if (c->tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; }
+  }
+  auto wait_decoded = [&]() -> int {
+    if (!tail_on_p && c->ev_last_decoded) CTPN_HIP_TRY(hipStreamWaitEvent(ts, c->ev_last_decoded, 0));
+    return CTPN_OK;
+  };
+  // borders must be zero for this geometry
+  if (c->gn != n || c->gh != h || c->gw != w) {
+    if (c->tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; }   // it still reads rpn_conv's output
+    for (int i = 0; i < 14; ++i) CTPN_HIP_TRY(hipMemsetAsync(c->act_conv[i], 0, c->act_conv_bytes[i], s));
+    for (int p = 0; p < 4; ++p) CTPN_HIP_TRY(hipMemsetAsync(c->act_pool[p], 0, c->act_pool_bytes[p], s));
+    if (c->q_img) CTPN_HIP_TRY(hipMemsetAsync(c->q_img, 0, c->q_img_bytes, s));      // the zero frame around every image (only image pixels are rewritten)
+    c->gn = n; c->gh = h; c->gw = w;
+  }
+  const void* img = images;
+  int staged = -1;
+  if (!images_on_device) {
+    // Host images cross PCIe on their own stream into one of two staging buffers, so the copy of this batch overlaps the
+    // previous batch's convolutions (the forward stream only waits for the copy event). A buffer is reused two calls later,
+    // after the conv1_1 launch that read it (ev_consumed).
+    staged = c->img_flip;
+    c->img_flip ^= 1;
+    if (c->consumed_valid[staged]) CTPN_HIP_TRY(hipStreamWaitEvent(c->stream_c, c->ev_consumed[staged], 0));
+    const size_t bytes = (size_t)n * h * w * 3 * (is_f32 ? 4 : 1);
+    const void* src = images;
+    hipPointerAttribute_t attr;
+    const bool locked = hipPointerGetAttributes(&attr, images) == hipSuccess && attr.type == hipMemoryTypeHost;
+    if (!locked) {
+      // A pageable source makes the runtime stage the copy itself and serialise it with the other streams (measured: 13.5
+      // instead of 11.4 ms / step). Stage it here instead: host memcpy into a page-locked buffer of the ctx (this thread,
+      // while the GPU works on the previous batch), then a truly asynchronous copy.
+      (void)hipGetLastError();
+      if (c->pin_stage_bytes[staged] < bytes) {
+        if (c->pin_stage[staged]) { CTPN_HIP_TRY(hipStreamSynchronize(c->stream_c)); CTPN_HIP_TRY(hipHostFree(c->pin_stage[staged])); c->pin_stage[staged] = nullptr; }
+        CTPN_HIP_TRY(hipHostMalloc(&c->pin_stage[staged], bytes));
+        c->pin_stage_bytes[staged] = bytes;
+        if (!c->ev_h2d_done[staged]) CTPN_HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d_done[staged], hipEventDisableTiming));
+        c->h2d_valid[staged] = false;
+      }
+      if (c->h2d_valid[staged]) CTPN_HIP_TRY(hipEventSynchronize(c->ev_h2d_done[staged]));   // the copy that last read this staging buffer
+      parallel_memcpy(c->pool.get(), c->pin_stage[staged], images, bytes);
+      src = c->pin_stage[staged];
+    }
+    CTPN_HIP_TRY(hipMemcpyAsync(c->img_dev_b[staged], src, bytes, hipMemcpyHostToDevice, c->stream_c));
+    if (!locked) { CTPN_HIP_TRY(hipEventRecord(c->ev_h2d_done[staged], c->stream_c)); c->h2d_valid[staged] = true; }
+    CTPN_HIP_TRY(hipEventRecord(c->ev_copied[staged], c->stream_c));
+    CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_copied[staged], 0));
+    img = c->img_dev_b[staged];
+  }
+  c->n = n; c->h = h; c->w = w;
+  int jpeg_src = -1;
+  if (images_on_device && c->jpeg_ready)
+    for (int b = 0; b < 2; ++b)
+      if (c->jpeg[b].ready_valid && images == (const void*)c->jpeg[b].out_dev) {      // decoded on stream_c: the forward waits for its kernels, not the host
+        CTPN_HIP_TRY(hipStreamWaitEvent(s, c->jpeg[b].ev_ready, 0));
+        jpeg_src = b;
+      }
+  bool via_q = false, fuse1 = false;
+  {
+    Timed t(c, CTPN_KIND_CONV_FIRST, (double)n * h * w * (3.0 + 64.0 * c->es));
+    // 16-bit modes: "conv1_kernel" picks exact-pixel MFMA through the q-image (2, uint8 feed) / split-operand MFMA (1) / VALU (0); split precision always takes the
+    // split-operand MFMA kernel (fp32-class sums, stored as (hi, lo) planes); fp32: the VALU kernel
+    const bool frags = c->prec == DType::SPLIT || (c->conv1_mfma && dtype_is_half(c->prec));
+    // uint8 feed of the 16-bit modes ("conv1_kernel" = 2): bytes -> q-image; conv1_1 then runs inside conv1_2's window stage (the production
+    // path: its 69 MB per image are never stored) or, with keep_acts / "conv1_fuse" = 0, stand-alone from the q-image: the same bytes
+    via_q = !is_f32 && dtype_is_half(c->prec) && c->conv1_mfma >= 2 && c->q_img != nullptr;
+    fuse1 = via_q && c->conv1_fuse && !c->keep_acts && conv1_fusable(c->prec, n, h, w, 64, 64, true, false);
+    if (via_q) {
+      if ((rc = launch_image_to_q((const uint8_t*)img, c->q_img, c->prec, n, h, w, s))) return rc;
+      if (!fuse1 && (rc = launch_conv_first_from_q(c->q_img, conv1_p_frags(c->w_first_frags, c->prec), c->act_conv[0], c->prec, n, h, w, 0, w, s))) return rc;
+    } else if ((rc = launch_conv_first(img, is_f32, c->w_first, c->b_conv[0], c->act_conv[0], c->prec, n, h, w, s,
+                                       frags ? c->w_first_frags : nullptr))) return rc;
+  }
+  c->act_valid[0] = !fuse1;      // fused: conv1_1's map exists only inside conv1_2's LDS windows
+  if (jpeg_src >= 0) {           // the images came from ctpn_decode_jpeg_batch: its buffer may be rewritten once the first layer has read it
+    CTPN_HIP_TRY(hipEventRecord(c->jpeg[jpeg_src].ev_consumed, s));
+    c->jpeg[jpeg_src].consumed_valid = true;
+  }
+  if (staged >= 0) {
+    CTPN_HIP_TRY(hipEventRecord(c->ev_consumed[staged], s));
+    c->consumed_valid[staged] = true;
+  }
+  // the previous batch's tail (stream_p) overlaps conv1_1 only: the conv stack starts on an otherwise idle chip (its timed window too)
+  // and rpn_conv's output, which lstm_pre reads, is not rewritten under it
+  if (c->tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; }
+  if (c->tail_confine && c->ev_last_done) CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_last_done, 0));      // option "tail_confine": see its declaration
+  const void* cur = c->act_conv[0];
+  int pool_i = 0;
+  hipEvent_t stack_a = nullptr, stack_b = nullptr;
+  double stack_flops = 0.0;
+  const bool stack_timed = c->prof && c->prof_mode == 2;
+  if (stack_timed) {
+    auto get = [&]() { hipEvent_t e; if (!c->free_events.empty()) { e = c->free_events.back(); c->free_events.pop_back(); } else { (void)hipEventCreate(&e); } return e; };
+    stack_a = get(); stack_b = get();
+    CTPN_HIP_TRY(hipEventRecord(stack_a, s));
+  }
+  for (int i = 1; i < 14; ++i) {
+    const int hl = lvl(h, kConvs[i].level), wl = lvl(w, kConvs[i].level);
+    double flops = 2.0 * (double)n * hl * wl * 9.0 * kConvs[i].ci * kConvs[i].co;
+    if (fuse1 && i == 1) flops += 2.0 * (double)n * h * w * 27.0 * 64.0;      // conv1_1 is part of this launch
+    stack_flops += flops;
+    const bool fuse = kConvs[i].pool_after != 0;
+    void* full = (!fuse || c->keep_acts) ? c->act_conv[i] : nullptr;
+    {
+      Timed t(c, CTPN_KIND_CONV_GEMM, flops);
+      const bool f1 = fuse1 && i == 1;
+      if ((rc = launch_conv3x3(cur, c->wt_conv[i], c->b_conv[i], full, fuse ? c->act_pool[pool_i] : nullptr, c->prec, n, hl, wl,
+                               kConvs[i].ci, kConvs[i].co, 1, s, (c->prec == DType::SPLIT && i == 13) ? 1 : 0,
+                               f1 ? c->q_img : nullptr, f1 ? conv1_p_frags(c->w_first_frags, c->prec) : nullptr, (c->conv_p64 ? 1 : 0) | (c->split_edge ? 2 : 0)))) return rc;
+    }
+    c->act_valid[i] = full != nullptr;
+    cur = fuse ? c->act_pool[pool_i] : c->act_conv[i];
+    if (fuse) ++pool_i;
+  }
+  if (stack_timed) {
+    CTPN_HIP_TRY(hipEventRecord(stack_b, s));
+    ProfRec r{CTPN_KIND_CONV_GEMM, stack_a, stack_b, stack_flops};
+    r.launches = 13;
+    c->pending.push_back(r);
+  }
+  const int hf = lvl(h, 4), wf = lvl(w, 4);
+  const long long M5 = (long long)n * hf * wf;
+  {  // lstm_pre: x_t @ kernel[:512] + bias for both directions (on `s` also when the tail overlaps: next to conv1_1 this MFMA GEMM took
+     // 644 us instead of 174, measured -- only the latency-bound recurrence and the small heads GEMM move to stream_p)
+    IGemm g{};
+    // split precision: rpn_conv/3x3 stored [hi | lo | hi] pixels, wt_x rows are [hi | hi | lo]: a plain bf16 GEMM over K = 1536
+    const bool sp = c->prec == DType::SPLIT;
+    g.a = cur; g.wt = c->wt_x; g.bias = c->b_x; g.out = c->xp;
+    g.M = M5; g.Ci = sp ? 1536 : 512; g.ntaps = 1; g.Co = 1024; g.a_plain = 0; g.H = hf; g.W = wf; g.tap_base_y = 1; g.tap_base_x = 1;
+    g.out_bordered = 0; g.ldc = 1024; g.relu = 0;
+    Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 512 * 1024);
+    // 16-bit modes: lstm_pre is stored as fp16 (half the 272 MB round trip between this GEMM and the recurrence; see bilstm.hip) and
+    // computed by the resident-weight-slice kernel (lstm_pre.hip); fp32 and split precision: the im2col GEMM
+    if (dtype_is_half(c->prec)) { if ((rc = launch_lstm_pre(cur, c->wt_xf, c->b_x, c->xp, c->prec, n, hf, wf, s))) return rc; }
+    else if ((rc = launch_igemm(g, sp ? DType::BF16 : c->prec, DType::F32, s))) return rc;
+  }
+  if (tail_on_p) {
+    CTPN_HIP_TRY(hipEventRecord(c->ev_conv, s));
+    CTPN_HIP_TRY(hipStreamWaitEvent(ts, c->ev_conv, 0));
+  }
+  {
+    Timed t(c, CTPN_KIND_BILSTM, (double)M5 * (1024.0 + 256.0) * 4.0, ts);
+    // "lstm_split": the recurrent product on split-bf16 MFMAs (fp32-class; v_exp / v_rcp gate math, 1 ulp each) in every mode but the fp32 gate,
+    // whose kernel (and split precision's with lstm_split = 0) is exact-fp32 MFMA with exact gates
+    const bool half = dtype_is_half(c->prec);
+    if ((rc = launch_bilstm(c->xp, half ? 1 : 0, c->wh, c->lstm_out, n * hf, wf, ts, (c->lstm_split && c->prec != DType::F32) ? 1 : 0, half ? 1 : 0))) return rc;
+  }
+  const bool fold_heads = dtype_is_half(c->prec) && !c->keep_acts;
+  if (fold_heads) {  // lstm_out (256) -> bbox (40) | cls (20) through the pre-multiplied FC x heads matrix
+    IGemm g{};
+    g.a = c->lstm_out; g.wt = c->wt_fold; g.bias = c->b_fold; g.out = c->heads;
+    g.M = M5; g.Ci = 256; g.ntaps = 1; g.Co = 60; g.a_plain = 1; g.lda = 256; g.out_bordered = 0; g.ldc = 64; g.relu = 0;
+    if ((rc = wait_decoded())) return rc;
+    Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 256 * 60, ts);
+    if ((rc = launch_igemm(g, DType::F32, DType::F32, ts))) return rc;
+  } else {
+  {  // lstm_o FC 256 -> 512 (no activation, reference network.py:110-113)
+    IGemm g{};
+    g.a = c->lstm_out; g.wt = c->wt_fc; g.bias = c->b_fc; g.out = c->fc_out;
+    g.M = M5; g.Ci = 256; g.ntaps = 1; g.Co = 512; g.a_plain = 1; g.lda = 256; g.out_bordered = 0; g.ldc = 512; g.relu = 0;
+    Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 256 * 512, ts);
+    if ((rc = launch_igemm(g, DType::F32, DType::F32, ts))) return rc;
+  }
+  {  // rpn_bbox_pred (40) | rpn_cls_score (20) in one 512 -> 60 GEMM
+    IGemm g{};
+    g.a = c->fc_out; g.wt = c->wt_h; g.bias = c->b_h; g.out = c->heads;
+    g.M = M5; g.Ci = 512; g.ntaps = 1; g.Co = 60; g.a_plain = 1; g.lda = 512; g.out_bordered = 0; g.ldc = 64; g.relu = 0;
+    if ((rc = wait_decoded())) return rc;
+    Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 512 * 60, ts);
+    if ((rc = launch_igemm(g, DType::F32, DType::F32, ts))) return rc;
+  }
+  }
+  if (tail_on_p) { CTPN_HIP_TRY(hipEventRecord(c->ev_tail, ts)); c->tail_pending = true; }
+  c->fc_valid = !fold_heads;
+  c->forward_done = true;
+  c->proposals_done = false;
+  return CTPN_OK;
+}
+
+}  // namespace ctpn
+
+extern "C" {
+
+int ctpn_forward(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w) {
+  return forward_impl(c, images, 0, images_on_device, n, h, w);
+}
+int ctpn_forward_blob(ctpn_ctx* c, const float* blob, int blob_on_device, int n, int h, int w) {
+  return forward_impl(c, blob, 1, blob_on_device, n, h, w);
+}
+
+int ctpn_feat_shape(ctpn_ctx* c, int* n, int* hf, int* wf) {
+  if (!c) return fail(CTPN_ERR_ARG, "null ctx");
+  if (!c->forward_done) return fail(CTPN_ERR_STATE, "no forward yet");
+  if (n) *n = c->n; if (hf) *hf = lvl(c->h, 4); if (wf) *wf = lvl(c->w, 4);
+  return CTPN_OK;
+}
+
+int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capacity, int shape4[4]) {
+  if (!c || !name || !out_host) return fail(CTPN_ERR_ARG, "null pointer");
+  if (!c->forward_done) return fail(CTPN_ERR_STATE, "ctpn_get_tensor: no forward yet");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  const std::string nm(name);
+  const int n = c->n, hf = lvl(c->h, 4), wf = lvl(c->w, 4);
+  const void* src = nullptr; int H = 0, W = 0, C = 0, ld = 0; bool bordered = false; DType t = DType::F32;
+  for (int i = 0; i < 14; ++i) if (nm == kConvs[i].name && !c->act_valid[i])
+    return fail(CTPN_ERR_STATE, "ctpn_get_tensor: " + nm + (i == 0 ? " is computed inside conv1_2's window stage" : " is fused with its max-pool") + " and not stored; set the ctx option keep_acts = 1 (ctpn_set_option)");
+  for (int i = 0; i < 14; ++i) if (nm == kConvs[i].name) { src = c->act_conv[i]; H = lvl(c->h, kConvs[i].level); W = lvl(c->w, kConvs[i].level); C = kConvs[i].co; ld = C; bordered = true; t = c->prec; }
+  const int pool_src[4] = {1, 3, 6, 9};
+  for (int p = 0; p < 4; ++p) if (nm == kPoolNames[p]) { src = c->act_pool[p]; H = lvl(c->h, p + 1); W = lvl(c->w, p + 1); C = kConvs[pool_src[p]].co; ld = C; bordered = true; t = c->prec; }
+  if (nm == "lstm_pre") { src = c->xp; H = hf; W = wf; C = 1024; ld = 1024; if (dtype_is_half(c->prec)) t = DType::F16; }
+  if (nm == "lstm_out") { src = c->lstm_out; H = hf; W = wf; C = 256; ld = 256; }
+  if (nm == "lstm_o" && !c->fc_valid)
+    return fail(CTPN_ERR_STATE, "ctpn_get_tensor: lstm_o is folded into the heads GEMM in the 16-bit modes; set the ctx option keep_acts = 1 (ctpn_set_option)");
+  if (nm == "lstm_o") { src = c->fc_out; H = hf; W = wf; C = 512; ld = 512; }
+  if (nm == "heads") { src = c->heads; H = hf; W = wf; C = 60; ld = 64; }
+  if (nm == "rpn_cls_prob_reshape") { src = c->cls_prob; H = hf; W = wf; C = 20; ld = 20; }
+  if (nm == "rpn_bbox_pred") { src = c->bbox_pred; H = hf; W = wf; C = 40; ld = 40; }
+  if (!src) return fail(CTPN_ERR_ARG, "ctpn_get_tensor: unknown tensor name " + nm);
+  if ((src == c->cls_prob || src == c->bbox_pred) && !c->proposals_done)
+    return fail(CTPN_ERR_STATE, "ctpn_get_tensor: " + nm + " is produced by ctpn_proposals (the softmax is fused into the decode kernel)");
+  const size_t need = (size_t)n * H * W * C;
+  if (shape4) { shape4[0] = n; shape4[1] = H; shape4[2] = W; shape4[3] = C; }
+  if (capacity < need) return fail(CTPN_ERR_CAPACITY, "ctpn_get_tensor: output buffer too small");
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  // split precision: a pixel is [hi(C) | lo(C)] bf16 (rpn_conv/3x3: [hi | lo | hi]); the value is hi + lo
+  const bool split = t == DType::SPLIT;
+  if (split) ld = (src == c->act_conv[13] ? 3 : 2) * C;
+  const int es = split ? 2 : dtype_bytes(t);
+  const int Hs = bordered ? H + 2 : H, Ws = bordered ? W + 2 : W;
+  const size_t bytes = (size_t)n * Hs * Ws * ld * es;
+  std::vector<char> tmp(bytes);
+  CTPN_HIP_TRY(hipMemcpy(tmp.data(), src, bytes, hipMemcpyDeviceToHost));
+  const int o = bordered ? 1 : 0;
+  for (int in = 0; in < n; ++in)
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x) {
+        const size_t sp = (((size_t)in * Hs + y + o) * Ws + x + o) * ld;
+        float* d = out_host + (((size_t)in * H + y) * W + x) * C;
+        if (src == c->xp) {                      // device layout: permuted gate columns -> TF's i | j | f | o order (fp16 in the 16-bit modes)
+          if (es == 2) {
+            const uint16_t* sh = (const uint16_t*)tmp.data() + sp;
+            for (int ch = 0; ch < 1024; ++ch) d[ch] = host_f16_to_f32(sh[(ch & ~511) + lstm_gate_col(ch & 511)]);
+          } else {
+            const float* sf = (const float*)tmp.data() + sp;
+            for (int ch = 0; ch < 1024; ++ch) d[ch] = sf[(ch & ~511) + lstm_gate_col(ch & 511)];
+          }
+        } else if (es == 4) {
+          std::memcpy(d, (const float*)tmp.data() + sp, (size_t)C * 4);
+        } else {
+          const uint16_t* sb = (const uint16_t*)tmp.data() + sp;
+          if (split) for (int ch = 0; ch < C; ++ch) d[ch] = host_bf16_to_f32(sb[ch]) + host_bf16_to_f32(sb[C + ch]);
+          else if (t == DType::F16) for (int ch = 0; ch < C; ++ch) d[ch] = host_f16_to_f32(sb[ch]);
+          else for (int ch = 0; ch < C; ++ch) d[ch] = host_bf16_to_f32(sb[ch]);
+        }
+      }
+  return CTPN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,205 @@
+// C ABI of libctpn_hip.so, proposal unit: the proposal layer's orchestration (decode, sort, gather, NMS), its entry points, the stand-alone NMS seam.
+#include "ctx.h"
+
+namespace ctpn {
+
+static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
+                                  int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s, hipEvent_t ev_decoded) {
+  if (!s) s = c->stream;
+  if (!im_info) return fail(CTPN_ERR_ARG, "proposals: null pointer");
+  if (pre_nms_topn <= 0 || pre_nms_topn > c->topn_max) return fail(CTPN_ERR_CAPACITY, "proposals: pre_nms_topn must be in 1..12000");
+  if (post_nms_topn <= 0 || post_nms_topn > c->post_max) return fail(CTPN_ERR_CAPACITY, "proposals: post_nms_topn must be in 1..1000");
+  const int per_img = hf * wf * 10;
+  const int npad = next_pow2(per_img);
+  if (npad > c->npad_max) return fail(CTPN_ERR_CAPACITY, "proposals: feature map larger than the ctx was created for");
+  if (n > 4) CTPN_HIP_TRY(hipMemcpyAsync(c->im_info_dev, im_info, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));      // (<= 4: in decode_kernel's arguments)
+  ProposalCfg pc{n, hf, wf, pre_nms_topn, post_nms_topn, nms_thresh, min_size};
+  int rc;
+  bool mw = nms_multi_wg(c, n, hf) && nms_columns_ok(wf, pre_nms_topn, nms_thresh);
+  if (c->nms_mw_scratch && c->nms_mw_dirty) {
+    // in stream order in front of everything that follows; both streams that ever use the block are drained by whoever set the flag
+    CTPN_HIP_TRY(hipMemsetAsync(c->nms_mw_scratch, 0, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, s));
+    c->nms_mw_dirty = false;
+  }
+  const bool seg_sort = !(c->nms_columns == 2 || c->nms_columns == 0);      // options 0 / 2 pin the one-workgroup forms of sort and NMS
+  const double nanch = (double)n * per_img;
+  {
+    Timed t(c, CTPN_KIND_DECODE, nanch * (60.0 * 4 / 10 + 8 + 16), s);
+    if ((rc = launch_decode(heads, 64, heads_are_probs, c->cls_in, c->bbox_in, c->im_info_dev, heads_are_probs ? nullptr : c->cls_prob,
+                            heads_are_probs ? nullptr : c->bbox_pred, c->keys, c->boxes4, pc, npad, s, seg_sort && sort_is_segmented(n, per_img), n <= 4 ? im_info : nullptr))) return rc;
+  }
+  if (ev_decoded) CTPN_HIP_TRY(hipEventRecord(ev_decoded, s));
+  {
+    Timed t(c, CTPN_KIND_SORT, (double)n * npad * 16.0, s);
+    int in_tmp = 0;
+    if ((rc = launch_sort_keys(c->keys, c->keys_tmp, n, npad, per_img, s, seg_sort ? &in_tmp : nullptr))) return rc;
+    const unsigned long long* sorted_keys = in_tmp ? c->keys_tmp : c->keys;
+    // boxes whose x was clipped onto the image's last pixel column (im_info narrower than the feature map: only ctpn_proposals_from_host can
+    // say so) pile up in ONE column group, which may then exceed the multi-workgroup kernel's list: those calls keep the one-workgroup form
+    for (int i = 0; i < n; ++i) mw = mw && im_info[3 * i + 1] >= (float)((wf - 1) * 16 + 1);
+    if ((rc = launch_gather_sorted(sorted_keys, c->boxes4, c->sorted_boxes, c->sorted_scores, c->sorted_anchor, c->valid_counts, n, npad, per_img, pre_nms_topn, s,
+                                   mw ? c->nms_colid : nullptr, wf))) return rc;
+  }
+  if (c->debug_hog > 0 && c->nms_mw_scratch) {
+    // values above 50000: the hog also keeps writing its 84 KB of LDS (usec = value - 50000); above 100000: it gathers random 16-byte pieces of the
+    // largest activation buffer instead (usec = value - 100000, twice the workgroups): the NMS kernel's memory traffic for as long as asked
+    const int hv = c->debug_hog;
+    const int usec = hv > 100000 ? hv - 100000 : hv > 50000 ? hv - 50000 : hv, touch = hv > 100000 ? 4 : hv > 50000 ? 2 : 0;
+    const void* src = nullptr; size_t src_bytes = 0;
+    for (int i = 0; i < 14; ++i) if (c->act_conv[i] && c->act_conv_bytes[i] > src_bytes) { src = c->act_conv[i]; src_bytes = c->act_conv_bytes[i]; }
+    if ((rc = launch_hog((unsigned*)(c->nms_colid), touch == 4 ? 2 * n : n, usec, touch, s, src, src_bytes))) return rc;       // (sink: never written; any device pointer)
+  }
+  {
+    Timed t(c, CTPN_KIND_NMS, (double)n * pre_nms_topn * 24.0, s);
+    if (c->nms_columns && nms_columns_ok(wf, pre_nms_topn, nms_thresh)) {
+      // 16 waves per image (a 4-wave footprint that co-resides with the persistent convolutions took 1.9 ms instead of 0.66 ms and slowed
+      // conv1_2 by 8 % through the shared SIMDs in round 2: removed)
+      if ((rc = launch_nms_columns(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, c->keep_idx,
+                                   c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, wf, s, c->sorted_anchor, c->roi_anchor, nullptr,
+                                   mw ? c->nms_mw_scratch : nullptr, mw ? c->nms_colid : nullptr, c->nms_prefix ? 4096 : 0, c->debug_nms))) return rc;
+      if (c->nms_check) {
+        // option "nms_check" (debug; synchronises the stream): the column decomposition presumes boxes on the 16-px anchor grid (common.h). Re-run the generic
+        // kernel on the same candidates and fail loudly if the keep lists differ.
+        std::vector<int> k1((size_t)n * c->topn_max), c1(n), k2((size_t)n * c->topn_max), c2(n);
+        int* keep2 = nullptr; int* cnt2 = nullptr; float* spill2 = nullptr;
+        struct Free3 { int*& a; int*& b; float*& c; ~Free3() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } guard{keep2, cnt2, spill2};   // every early return frees
+        CTPN_HIP_TRY(hipStreamSynchronize(s));
+        CTPN_HIP_TRY(hipMemcpy(k1.data(), c->keep_idx, k1.size() * sizeof(int), hipMemcpyDeviceToHost));
+        CTPN_HIP_TRY(hipMemcpy(c1.data(), c->keep_counts, c1.size() * sizeof(int), hipMemcpyDeviceToHost));
+        CTPN_HIP_TRY(hipMalloc((void**)&keep2, k2.size() * sizeof(int)));
+        CTPN_HIP_TRY(hipMalloc((void**)&cnt2, c2.size() * sizeof(int)));
+        CTPN_HIP_TRY(hipMalloc((void**)&spill2, (size_t)n * c->topn_max * 4 * sizeof(float)));
+        rc = launch_nms(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, keep2, c->topn_max, cnt2, nullptr, spill2, n, s);
+        if (rc == CTPN_OK && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(k2.data(), keep2, k2.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                              hipMemcpy(c2.data(), cnt2, c2.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
+          rc = fail(CTPN_ERR_HIP, "nms_check: copy back failed");
+        if (rc) return rc;
+        if (mw) {
+          // the multi-workgroup form's sticky overflow words (a column with more candidates than the kernel's list)
+          for (int i = 0; i < n; ++i) {
+            unsigned ov = 0;
+            CTPN_HIP_TRY(hipMemcpy(&ov, c->nms_mw_scratch + (size_t)i * NMS_MW_SCRATCH_BYTES + NMS_MW_OVERFLOW_OFF, 4, hipMemcpyDeviceToHost));
+            if (ov) {
+              c->nms_mw_dirty = true;
+              return fail(CTPN_ERR_STATE, "nms_check: a column held more candidates than the multi-workgroup NMS's list (1024): keep lists are incomplete");
+            }
+          }
+        }
+        for (int i = 0; i < n; ++i) {
+          bool same = c1[i] == c2[i];
+          for (int k = 0; same && k < c1[i]; ++k) same = k1[(size_t)i * c->topn_max + k] == k2[(size_t)i * c->topn_max + k];
+          if (!same) return fail(CTPN_ERR_STATE, "nms_check: column-decomposed NMS differs from the generic kernel (boxes off the 16-px anchor grid?)");
+        }
+      }
+    } else if ((rc = launch_nms(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, c->keep_idx,
+                                c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, s, c->sorted_anchor, c->roi_anchor))) return rc;
+  }
+  c->last_post = post_nms_topn; c->last_prop_n = n;
+  if (!heads_are_probs) c->proposals_done = true;
+  return CTPN_OK;
+}
+int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
+                      int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s,
+                      hipEvent_t ev_decoded) {
+  const int rc = enqueue_proposals_impl(c, heads, heads_are_probs, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size, s, ev_decoded);
+  if (rc != CTPN_OK) c->nms_mw_dirty = true;       // whatever failed, nobody vouches for the multi-workgroup NMS's scratch any more (common.h)
+  return rc;
+}
+
+static int run_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
+                         int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* rois_out, int* counts_out) {
+  if (!rois_out || !counts_out) return fail(CTPN_ERR_ARG, "proposals: null pointer");
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));   // the asynchronous detect path shares the proposal buffers
+  int rc = enqueue_proposals(c, heads, heads_are_probs, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size);
+  if (rc) return rc;
+  hipStream_t s = c->stream;
+  CTPN_HIP_TRY(hipMemcpyAsync(counts_out, c->keep_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+  CTPN_HIP_TRY(hipMemcpyAsync(rois_out, c->rois, (size_t)n * post_nms_topn * 5 * sizeof(float), hipMemcpyDeviceToHost, s));
+  CTPN_HIP_TRY(hipStreamSynchronize(s));
+  return CTPN_OK;
+}
+
+}  // namespace ctpn
+
+// ---- standalone NMS (B1 seam) ----------------------------------------------------------------
+namespace {
+struct NmsCache {
+  std::mutex mu;
+  hipStream_t stream = nullptr;
+  int cap = 0;
+  float* boxes = nullptr; float* spill = nullptr; int* keep = nullptr; int* counts = nullptr;  // counts[0] = n in, counts[1] = n kept
+};
+NmsCache g_nms[16];
+}  // namespace
+
+extern "C" {
+
+int ctpn_proposals(ctpn_ctx* c, const float* im_info, int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size,
+                   float* rois_out, int* counts_out) {
+  if (!c) return fail(CTPN_ERR_ARG, "null ctx");
+  if (!c->forward_done) return fail(CTPN_ERR_STATE, "ctpn_proposals: no forward yet");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  return run_proposals(c, c->heads, 0, c->n, lvl(c->h, 4), lvl(c->w, 4), im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size,
+                       rois_out, counts_out);
+}
+
+int ctpn_proposals_from_host(ctpn_ctx* c, const float* cls_prob, const float* bbox_pred, int n, int hf, int wf, const float* im_info,
+                             int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* rois_out, int* counts_out) {
+  if (!c || !cls_prob || !bbox_pred) return fail(CTPN_ERR_ARG, "null pointer");
+  if (n <= 0 || n > c->max_batch || hf <= 0 || wf <= 0 || (size_t)n * hf * wf > c->m5_max)
+    return fail(CTPN_ERR_CAPACITY, "ctpn_proposals_from_host: shape outside what the ctx was created for");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  const size_t m = (size_t)n * hf * wf;
+  CTPN_HIP_TRY(hipMemcpyAsync(c->cls_in, cls_prob, m * 20 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  CTPN_HIP_TRY(hipMemcpyAsync(c->bbox_in, bbox_pred, m * 40 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  return run_proposals(c, nullptr, 1, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size, rois_out, counts_out);
+}
+
+int ctpn_proposal_anchors(ctpn_ctx* c, int* anchors_out, int post_nms_topn) {
+  if (!c || !anchors_out) return fail(CTPN_ERR_ARG, "null pointer");
+  if (c->last_prop_n <= 0) return fail(CTPN_ERR_STATE, "ctpn_proposal_anchors: no ctpn_proposals / ctpn_proposals_from_host call yet");
+  if (post_nms_topn != c->last_post) return fail(CTPN_ERR_ARG, "ctpn_proposal_anchors: post_nms_topn differs from the proposals call");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  CTPN_HIP_TRY(hipMemcpyAsync(anchors_out, c->roi_anchor, (size_t)c->last_prop_n * post_nms_topn * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  return CTPN_OK;
+}
+
+int ctpn_nms(int* keep_out, int* num_out, const float* boxes_host, int boxes_num, int boxes_dim, float thresh, int device_id) {
+  if (!keep_out || !num_out) return fail(CTPN_ERR_ARG, "ctpn_nms: null output");
+  *num_out = 0;
+  if (boxes_num == 0) return CTPN_OK;
+  if (!boxes_host || boxes_num < 0 || boxes_dim < 4) return fail(CTPN_ERR_ARG, "ctpn_nms: boxes must be N x (>=4)");
+  const int ndev = ctpn_device_count();
+  if (ndev <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_nms: no HIP device visible (this library has no CPU fallback)");
+  if (device_id < 0 || device_id >= ndev || device_id >= 16) return fail(CTPN_ERR_ARG, "ctpn_nms: device_id out of range");
+  NmsCache& nc = g_nms[device_id];
+  std::lock_guard<std::mutex> lk(nc.mu);
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  if (!nc.stream) CTPN_HIP_TRY(hipStreamCreateWithFlags(&nc.stream, hipStreamNonBlocking));
+  if (nc.cap < boxes_num) {
+    if (nc.boxes) { (void)hipFree(nc.boxes); (void)hipFree(nc.spill); (void)hipFree(nc.keep); (void)hipFree(nc.counts); nc.boxes = nullptr; nc.cap = 0; }
+    const int cap = boxes_num < 16384 ? 16384 : boxes_num;
+    CTPN_HIP_TRY(hipMalloc((void**)&nc.boxes, (size_t)cap * 4 * sizeof(float)));
+    CTPN_HIP_TRY(hipMalloc((void**)&nc.spill, (size_t)cap * 4 * sizeof(float)));
+    CTPN_HIP_TRY(hipMalloc((void**)&nc.keep, (size_t)cap * sizeof(int)));
+    CTPN_HIP_TRY(hipMalloc((void**)&nc.counts, 2 * sizeof(int)));
+    nc.cap = cap;
+  }
+  std::vector<float> b4((size_t)boxes_num * 4);
+  for (int i = 0; i < boxes_num; ++i) std::memcpy(&b4[(size_t)i * 4], boxes_host + (size_t)i * boxes_dim, 4 * sizeof(float));
+  CTPN_HIP_TRY(hipMemcpyAsync(nc.boxes, b4.data(), b4.size() * sizeof(float), hipMemcpyHostToDevice, nc.stream));
+  CTPN_HIP_TRY(hipMemcpyAsync(nc.counts, &boxes_num, sizeof(int), hipMemcpyHostToDevice, nc.stream));
+  int rc = launch_nms(nc.boxes, nullptr, nc.counts, boxes_num, thresh, boxes_num, nc.keep, boxes_num, nc.counts + 1, nullptr, nc.spill, 1, nc.stream);
+  if (rc) return rc;
+  int nk = 0;
+  CTPN_HIP_TRY(hipMemcpyAsync(&nk, nc.counts + 1, sizeof(int), hipMemcpyDeviceToHost, nc.stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(nc.stream));
+  if (nk < 0 || nk > boxes_num) return fail(CTPN_ERR_HIP, "ctpn_nms: device returned an impossible keep count");
+  CTPN_HIP_TRY(hipMemcpy(keep_out, nc.keep, (size_t)nk * sizeof(int), hipMemcpyDeviceToHost));
+  *num_out = nk;
+  return CTPN_OK;
+}
+
+}  // extern "C"

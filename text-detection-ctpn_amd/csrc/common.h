@@ -235,14 +235,15 @@ int launch_nms(const float* sorted_boxes, const float* sorted_scores, const int*
 // PRECONDITION (not checked by nms_columns_ok, which only looks at ncols / stride / thresh): every box lies on the 16-px anchor grid,
 // x1 in [16 c, 16 c + 16) and x2 <= 16 c + 16 for its column c (/ im_scale for the connector variant) -- true for decode_kernel's output
 // (bbox_transform_inv leaves x alone), NOT for arbitrary boxes: those go through launch_nms (the ctpn_nms seam always does).
-// option nms_check = 1 (debug) re-runs the generic kernel after the proposal layer's column launch (ctpn_api.hip) and fails loudly on a mismatch.
+// option nms_check = 1 (debug) re-runs the generic kernel after the proposal layer's column launch (api_proposals.hip) and fails loudly on a mismatch.
 int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, const int* counts_in, int stride, float thresh, int max_keep,
                        int* keep_idx, int keep_stride, int* keep_counts, float* rois_out, float* kept_spill, int n_img, int ncols, hipStream_t s,
                        const int* sorted_anchor = nullptr, int* roi_anchor = nullptr,
                        const float* col_scale = nullptr /* im_info rows: the connector's boxes / im_scale variant */,
                        void* mw_scratch = nullptr /* n_img x NMS_MW_SCRATCH_BYTES, zeroed: the multi-workgroup form for small batches (one column per wave) */,
                        const unsigned char* colid = nullptr /* launch_gather_sorted's column ids (needed above 1024 candidates) */,
-                       int prefix = 0 /* > 0: try the first `prefix` ranks first (they usually hold max_keep survivors); same result either way */);
+                       int prefix = 0 /* > 0: try the first `prefix` ranks first (they usually hold max_keep survivors); same result either way */,
+                       int dbg = 0 /* option debug_nms (diagnostic, WRONG proposals): parts mask of nms_columns_kernel<16, ..> (proposal.hip) */);
 constexpr size_t NMS_MW_SCRATCH_BYTES = 2048;       // per image: survivor mask (one bit per rank) + ticket; zero between launches
 // ... and one STICKY word the kernel sets when a column held more candidates than its list (keep lists are then wrong): zero unless a caller
 // broke launch_nms_columns' precondition; read and cleared by the host (option nms_check). The block's zero state between launches is
@@ -254,8 +255,7 @@ constexpr size_t NMS_MW_FLAG_OFF = 2032;            // prefix pass: "the prefix 
 constexpr int NMS_MW_MAX_BATCH = 4;                 // batches up to this size spread their columns over the machine; larger ones fill it with images
 constexpr int NMS_MW_CAP_BATCH = 32;                // ... unless option nms_columns = 3 asks for the multi-workgroup form explicitly: buffers are sized for this many images
 bool nms_columns_ok(int ncols, int stride, float thresh);
-int launch_hog(unsigned* sink, int n_wg, int usec, int touch, hipStream_t s, const void* src = nullptr, size_t src_bytes = 0);
-extern int g_debug_nms;      // diagnostic parts mask of nms_columns_kernel<16, ..> (proposal.hip)      // diagnostic: the one-workgroup NMS's footprint without its work (proposal.hip)
+int launch_hog(unsigned* sink, int n_wg, int usec, int touch, hipStream_t s, const void* src = nullptr, size_t src_bytes = 0);      // diagnostic: the one-workgroup NMS's footprint without its work (proposal.hip)
 bool nms_columns_tl_ok(int ncols, int stride, float thresh, float max_scale);
 
 // host text connector (text_connector.cpp)

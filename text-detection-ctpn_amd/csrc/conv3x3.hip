@@ -64,7 +64,7 @@ int launch_lds_dma_check(const void* src, void* out_clobber, void* out_keep, int
   return CTPN_OK;
 }
 
-// conv1_2 as the launch ctpn_api.hip may hand a q-image to: the weights-in-registers kernel's pooled form without a full-resolution output
+// conv1_2 as the launch api_forward.hip may hand a q-image to: the weights-in-registers kernel's pooled form without a full-resolution output
 bool conv1_fusable(DType t, int n, int h, int w, int ci, int co, bool pool, bool keep_full) {
   return dtype_is_half(t) && ci == 64 && co == 64 && pool && !keep_full && n >= 1;
 }

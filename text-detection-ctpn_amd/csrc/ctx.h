@@ -1,0 +1,355 @@
+// Internal to the host units of libctpn_hip.so (api_*.hip): the context struct, the small types and inline helpers more than one of them
+// uses, and the declarations of the few functions that cross them. The kernel units do not include this file; what they share with the host
+// units is in common.h.
+#pragma once
+#include <atomic>
+#include <condition_variable>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+#include <pthread.h>
+#include <sched.h>
+
+#include <dlfcn.h>
+
+#include "common.h"
+
+namespace ctpn {
+
+// ---------------------------------------------------------------------------------------------
+// network description (reference lib/networks/VGGnet_test.py:20-43)
+// ---------------------------------------------------------------------------------------------
+struct ConvSpec { const char* name; int ci, co, level; int pool_after; };
+static const ConvSpec kConvs[14] = {
+    {"conv1_1", 3, 64, 0, 0},    {"conv1_2", 64, 64, 0, 1},   {"conv2_1", 64, 128, 1, 0},  {"conv2_2", 128, 128, 1, 1},
+    {"conv3_1", 128, 256, 2, 0}, {"conv3_2", 256, 256, 2, 0}, {"conv3_3", 256, 256, 2, 1}, {"conv4_1", 256, 512, 3, 0},
+    {"conv4_2", 512, 512, 3, 0}, {"conv4_3", 512, 512, 3, 1}, {"conv5_1", 512, 512, 4, 0}, {"conv5_2", 512, 512, 4, 0},
+    {"conv5_3", 512, 512, 4, 0}, {"rpn_conv/3x3", 512, 512, 4, 0}};
+static const char* kPoolNames[4] = {"pool1", "pool2", "pool3", "pool4"};
+
+struct ProfRec { int kind; hipEvent_t a, b; double work; int launches = 1; };
+
+// ---------------------------------------------------------------------------------------------
+// Host worker pool of one ctx: created once, sized by ctpn_host_thread_budget (cores of the node / ranks on the node).
+// Runs the per-image host part of the connector (ctpn_detect_collect) and the staging copies of pageable host images.
+// Before: up to hardware_concurrency() std::threads were created and joined per collect -- 256 per step on an 8-rank node.
+// ---------------------------------------------------------------------------------------------
+class HostPool {
+ public:
+  HostPool(int nthreads, int first_cpu) : n_(nthreads < 1 ? 1 : nthreads) {
+    for (int t = 1; t < n_; ++t) {
+      th_.emplace_back([this] { loop(); });
+      if (first_cpu >= 0) pin(th_.back().native_handle(), first_cpu + t);
+    }
+  }
+  ~HostPool() {
+    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; ++gen_; }
+    cv_.notify_all();
+    for (auto& t : th_) t.join();
+  }
+  int size() const { return n_; }
+  // fn(i) for every i in [0, n); returns when all are done. The calling thread works too. max_par bounds the parallelism.
+  void run(int n, const std::function<void(int)>& fn, int max_par = 0) {
+    if (n <= 0) return;
+    const int par = std::min(n, max_par > 0 ? std::min(max_par, n_) : n_);
+    if (par <= 1) { for (int i = 0; i < n; ++i) fn(i); return; }
+    std::lock_guard<std::mutex> serial(run_mu_);
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      fn_ = &fn; total_ = n; next_.store(0); done_.store(0); helpers_ = par - 1; ++gen_;
+    }
+    cv_.notify_all();
+    work();
+    std::unique_lock<std::mutex> lk(mu_);
+    done_cv_.wait(lk, [&] { return done_.load() >= total_ && active_ == 0; });
+    helpers_ = 0;      // a worker that wakes up late must not join a finished job
+    fn_ = nullptr;
+  }
+
+ private:
+  static void pin(pthread_t h, int cpu) {
+    cpu_set_t set; CPU_ZERO(&set);
+    const unsigned ncpu = std::thread::hardware_concurrency();
+    CPU_SET((int)(ncpu > 0 ? (unsigned)cpu % ncpu : (unsigned)cpu), &set);
+    (void)pthread_setaffinity_np(h, sizeof(set), &set);
+  }
+  void work() {
+    for (;;) {
+      const int i = next_.fetch_add(1);
+      if (i >= total_) break;
+      (*fn_)(i);
+      done_.fetch_add(1);
+    }
+  }
+  void loop() {
+    unsigned long long seen = 0;
+    for (;;) {
+      {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return gen_ != seen; });
+        seen = gen_;
+        if (stop_) return;
+        if (helpers_ <= 0) continue;
+        --helpers_; ++active_;
+      }
+      work();
+      { std::lock_guard<std::mutex> lk(mu_); --active_; }
+      done_cv_.notify_all();
+    }
+  }
+  const int n_;
+  std::vector<std::thread> th_;
+  std::mutex mu_, run_mu_;
+  std::condition_variable cv_, done_cv_;
+  const std::function<void(int)>* fn_ = nullptr;
+  int total_ = 0, helpers_ = 0, active_ = 0;
+  std::atomic<int> next_{0}, done_{0};
+  unsigned long long gen_ = 0;
+  bool stop_ = false;
+};
+
+}  // namespace ctpn
+
+using namespace ctpn;
+
+struct ctpn_ctx {
+  int device = 0;
+  int max_batch = 0, max_h = 0, max_w = 0;
+  DType prec = DType::BF16;
+  int es = 2;                       // bytes per activation element (split precision: a (hi, lo) bf16 pair = 4)
+  hipStream_t stream = nullptr;     // network forward
+  hipStream_t stream_p = nullptr;   // proposal layer + connector front end of the asynchronous detect path
+  std::vector<void*> allocs;
+  // asynchronous detect: two slots of pinned host buffers + events
+  struct Slot {
+    // the batch's results in ONE page-locked block, laid out like the device's out_pack: a single device-to-host copy per submit
+    // (six copies before: ~30 us of host calls per batch, which at batch 1 is 4 % of the step on a slow host)
+    char* pack = nullptr;
+    float* tlb = nullptr; float* tls = nullptr; int* keep = nullptr; int* kcnt = nullptr; float* rois = nullptr; int* rcnt = nullptr;      // views into pack
+    float* im_info = nullptr;
+    double* crecs = nullptr; int* ccnt = nullptr;      // device connector results: [n][2 modes][CONN_CAP][9], [n][3]
+    hipEvent_t ev_heads = nullptr, ev_decoded = nullptr, ev_done = nullptr;
+    int n = 0, h = 0, w = 0; bool busy = false;
+  } slot[2];
+  hipEvent_t ev_last_decoded = nullptr;  // decode of the most recent submit (it reads `heads`, which the next forward rewrites)
+  hipEvent_t ev_last_done = nullptr;     // the whole proposal tail (stream_p) of the most recent submit
+  // "tail_confine" (default 0; was 1 in split precision during round 6): forward k + 1 waits, BEHIND its conv1_1, for the proposal tail of batch k,
+  // which then overlaps conv1_1 only. History: the reversed-batch test of round 6 found that a batch in flight could change another batch's bits --
+  // the proposal NMS of batch k running beside the persistent conv kernels of batch k + 1 (in split precision by default timing, in bf16 as soon as
+  // the NMS was delayed into conv3_x / conv4_x). This switch removed the CONDITION. The CAUSE was in the conv kernels: the last k-slice group's
+  // fragment reads were in flight across the step barrier while the LDS-DMA behind it recycled the strip they read, ordered by latency only
+  // (conv3x3_impl.h, INVARIANT in conv3x3_p_kernel; profiles/r06_barrier_war.txt). Fixed there; the switch stays for A/B runs.
+  int tail_confine = 0;
+  // asynchronous detect, option tail_overlap = 1 (opt-in): the recurrent tail of batch k (BiLSTM + heads: 0.37 ms of latency-bound kernels
+  // on 148 of 256 CUs) runs on stream_p, next to conv1_1 of batch k + 1 (HBM-write-bound) instead of in front of it. Measured, round 3,
+  // same box: +0.6 % images/s (3420-3425 vs 3397-3405) -- side by side the BiLSTM takes 0.51-0.73 ms instead of 0.33 and conv1_1 0.60
+  // instead of 0.46, and the proposal kernels, which start 0.8 ms later, now run under conv2_x (static persistent tiles) instead of
+  // conv1_2 (dynamic tile claims): the conv stack loses 0.9 points of its roofline. Off by default.
+  int tail_overlap = 0;
+  hipEvent_t ev_conv = nullptr;          // conv stack + lstm_pre of the batch in flight are done (stream -> stream_p)
+  hipEvent_t ev_tail = nullptr;          // the tail of the most recent submit is done (stream_p -> stream: before conv1_2 rewrites what it read)
+  bool tail_pending = false;
+
+  // weights
+  bool weights_loaded = false;
+  float* arena = nullptr;            // fp32 copy of the flat arena
+  float* w_first = nullptr;          // [27][64]
+  void* w_first_frags = nullptr;     // conv1_1 as split-bf16 MFMA A fragments (bf16 mode), 12 KB
+  // options (ctpn_set_option; per ctx, never read from the environment)
+  int conv1_mfma = 2;                // "conv1_kernel" (16-bit modes): 2 = uint8 feed through the q-image (exact integer pixels x 16-bit weights, one MFMA term; conv1_1 inside
+                                     // conv1_2's window stage where "conv1_fuse" allows), 1 = split-bf16 kernel for both feeds, 0 = VALU kernel
+  // ctpn_decode_jpeg_batch: two sets of buffers (decode of batch k + 1 while batch k's forward reads its images), allocated on first use and
+  // grown on demand; a grown buffer's predecessor is retired, not freed (a pointer handed out earlier stays valid until ctpn_destroy)
+  struct JpegBufs {
+    int16_t* coef_host = nullptr; uint16_t* qt_host = nullptr;      // page-locked: what the entropy decoders write
+    int16_t* coef_dev = nullptr; uint16_t* qt_dev = nullptr; uint8_t* out_dev = nullptr;
+    size_t coef_elems = 0, qt_imgs = 0, out_bytes = 0;              // capacities
+    int out_n = 0, out_h = 0, out_w = 0;                            // what out_dev holds
+    hipEvent_t ev_h2d = nullptr, ev_ready = nullptr, ev_consumed = nullptr;
+    bool h2d_valid = false, consumed_valid = false, ready_valid = false;
+  } jpeg[2];
+  uint8_t* jpeg_planes = nullptr;    // component planes between the two kernels (one set: the kernels of both buffers run on stream_c in order)
+  uint8_t* jpeg_raw = nullptr;       // the decoded batch at file size when a resize follows (one set, same reason)
+  size_t jpeg_planes_bytes = 0, jpeg_raw_bytes = 0;
+  std::vector<void*> jpeg_retired;   // device allocations replaced by larger ones
+  int jpeg_flip = 0;
+  bool jpeg_ready = false;
+  int debug_nms = 0;                 // "debug_nms" (diagnostic, WRONG proposals): parts mask of the one-workgroup proposal NMS, see nms_columns_kernel
+  int debug_hog = 0;                 // "debug_hog" (diagnostic, 0 .. 200000; see the launch in enqueue_proposals_impl for the two upper ranges): launch a kernel with the one-workgroup NMS's footprint (1024 threads, 84 KB of LDS, one
+                                     // workgroup per image) that spins this many microseconds without memory traffic in front of the proposal NMS. Results are unaffected;
+                                     // tools/r6_pipeline_race.py uses it to ask what about the tail disturbs the next batch's persistent split layers
+  int nms_prefix = 1;                // "nms_prefix" (round 6): the column NMS of the proposal layer first looks at the 4096 best-scored candidates only; they hold the
+                                     // 1000 survivors asked for unless fewer than a quarter survive (then a full pass follows). Same keep list by construction; 0 = always the full pass
+  int split_edge = 1;                // "split_edge" (round 6): split precision sends ragged tile columns (W = 225 = 14 x 16 + 1, 113 = 7 x 16 + 1, 450 = 28 x 16 + 2,
+                                     // 900 = 28 x 32 + 4) through conv3x3_edge_kernel's split form, like the 16-bit modes, instead of computing a padded tile column
+                                     // (an eighth of conv4_1 / conv4_2). 0 = the padded column (ABI 9's arithmetic for those columns: other last bits)
+  int conv_p64 = 1;                  // "conv_p64" (round 6): split precision's conv1_2 (Co = 64, no weights-in-registers kernel) through the persistent kernel's 64-channel
+                                     // form: 3.56 ms instead of the non-persistent kernel's 4.53 at batch 32 (0 = that kernel, for A/B runs). It made a latent
+                                     // race of the conv kernels frequent enough to find (see tail_confine)
+  int conv1_fuse = 1;                // "conv1_fuse": with conv1_kernel = 2 and keep_acts = 0, compute conv1_1 inside conv1_2 (conv3x3_wr_kernel FUSE); 0 = stand-alone from the q-image (same bytes)
+  void* q_img = nullptr;             // the batch's q-image (common.h), 16-bit modes only
+  size_t q_img_bytes = 0;
+  int lstm_split = 0;                // "lstm_split": the recurrent product on split-bf16 MFMAs (fp32-class, |d| < 3e-5, 0.32 -> 0.16 ms). Default 1 in
+                                     // the 16-bit modes and, since round 6, in split precision (set in create_impl), 0 in fp32 (exact-fp32 MFMA kernel)
+  int nms_check = 0;                 // "nms_check": debug -- re-run the generic NMS kernel behind the column-decomposed one and fail on a mismatch
+  float* b_conv[14] = {nullptr};     // fp32 biases
+  void* wt_conv[14] = {nullptr};     // packed [Co][9*Ci] T (index 0 unused)
+  void* wt_x = nullptr;              // [1024][512] T (split precision: [1024][hi(512) | hi(512) | lo(512)] bf16)
+  size_t wx_row_bytes = 1024;        // bytes of one wt_x row
+  void* wt_xf = nullptr;             // 16-bit modes: wt_x in lstm_pre_kernel's fragment-major order
+  float* b_x = nullptr;              // [1024]
+  float* wh = nullptr;               // [2][128][512]
+  float* wt_fc = nullptr;            // [512][256]
+  float* b_fc = nullptr;
+  float* wt_h = nullptr;             // [64][512]
+  float* b_h = nullptr;              // [64]
+  float* wt_fold = nullptr;          // [64][256]: (lstm_o FC) x (heads) folded, bf16 throughput mode only
+  float* b_fold = nullptr;           // [64]
+
+  // activations
+  void* act_conv[14] = {nullptr};
+  void* act_pool[4] = {nullptr};
+  bool act_valid[14] = {true, true, true, true, true, true, true, true, true, true, true, true, true, true};
+  size_t act_conv_bytes[14] = {0};
+  size_t act_pool_bytes[4] = {0};
+  uint8_t* img_dev = nullptr;        // staging of host images, buffer 0
+  uint8_t* img_dev_b[2] = {nullptr, nullptr};   // ... double-buffered: batch k+1 crosses PCIe on stream_c while batch k is on the convolutions
+  hipStream_t stream_c = nullptr;
+  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
+  bool consumed_valid[2] = {false, false};
+  void* pin_stage[2] = {nullptr, nullptr};      // page-locked staging for pageable caller buffers (lazily allocated)
+  size_t pin_stage_bytes[2] = {0, 0};
+  hipEvent_t ev_h2d_done[2] = {nullptr, nullptr};
+  bool h2d_valid[2] = {false, false};
+  int img_flip = 0;
+  float* xp = nullptr;      // [M5][1024]
+  float* lstm_out = nullptr;  // [M5][256]
+  float* fc_out = nullptr;  // [M5][512]
+  float* heads = nullptr;   // [M5][64]
+  float* cls_prob = nullptr;  // [M5][20]
+  float* bbox_pred = nullptr; // [M5][40]
+  size_t m5_max = 0;
+
+  // proposal buffers
+  int npad_max = 0, topn_max = 12000, post_max = 1000;
+  unsigned long long* keys = nullptr; unsigned long long* keys_tmp = nullptr;
+  float* boxes4 = nullptr;
+  float* sorted_boxes = nullptr;
+  float* sorted_scores = nullptr;
+  int* valid_counts = nullptr;
+  int* keep_idx = nullptr;
+  int* keep_counts = nullptr;
+  float* rois = nullptr;
+  float* kept_spill = nullptr;
+  int* sorted_anchor = nullptr;      // [n][12000] anchor index of every sorted row
+  int* roi_anchor = nullptr;         // [n][1000]  anchor index of every roi (second return of proposal_layer)
+  int last_post = 0, last_prop_n = 0;
+  float* im_info_dev = nullptr;
+  char* out_pack = nullptr; size_t pack_bytes = 0;      // tl_boxes, tl_scores, tl_keep, tl_keep_counts, rois, keep_counts live here (pack_layout)
+  float* tl_boxes = nullptr; float* tl_scores = nullptr; int* tl_counts = nullptr;  // connector front end
+  int* tl_keep = nullptr; int* tl_keep_counts = nullptr; float* tl_spill = nullptr;
+  double* conn_recs = nullptr; int* conn_counts = nullptr; double* conn_scratch = nullptr;   // device connector (connect_kernel)
+  int nms_columns = 1;               // "nms_columns": 1 = column-decomposed NMS (one workgroup per image; batches <= NMS_MW_MAX_BATCH: one column per
+                                     // wave over ncols / 4 workgroups per image), 0 = nms_kernel (A/B), 2 / 3 = force the one-workgroup / the multi-workgroup form
+  char* nms_mw_scratch = nullptr;    // NMS_MW_CAP_BATCH x NMS_MW_SCRATCH_BYTES
+  bool nms_mw_dirty = false;         // the scratch may not be in its zero state (an error between launches, an option change): memset before the next use
+  unsigned char* nms_colid = nullptr;  // NMS_MW_CAP_BATCH x (topn_max rounded up to 16): column group of every sorted box (gather_kernel)
+  int connect_device = 0;            // "connect_device": 1 = graph build / chains / line fit on the GPU (connect_kernel), 0 = host C++
+                                     // (text_connector.cpp; default: it runs on otherwise idle host cores under the next batch's convolutions,
+                                     // the kernel shares the GPU with them: 11.15 vs 11.06 ms / step)
+  bool proposals_done = false;
+  bool postproc_only = false;        // ctpn_create_postproc: proposal / connector buffers only, no network
+  std::unique_ptr<ctpn::HostPool> pool;
+  int host_threads = 1;
+  bool fc_valid = true;
+  int keep_acts = 0;      // "keep_acts": 1 = also store the full-resolution output of pool-fused convs, keep lstm_o (layer-wise parity)
+  float* cls_in = nullptr;  // staging for proposals_from_host
+  float* bbox_in = nullptr;
+
+  // last forward geometry
+  int n = 0, h = 0, w = 0;
+  int gn = -1, gh = -1, gw = -1;  // geometry the borders are currently zeroed for
+  bool forward_done = false;
+
+  // profiling
+  bool prof = false;
+  int prof_mode = 1;                 // 1: a pair of events around every stage; 2: ONE pair around the 13 conv3x3 launches of a forward only
+                                     // (an event pair per launch costs ~0.2 ms of bubbles per step, which a throughput run should not pay)
+  std::vector<ProfRec> pending;
+  std::vector<hipEvent_t> free_events;
+  double prof_ms[CTPN_KIND_COUNT] = {0};
+  long long prof_n[CTPN_KIND_COUNT] = {0};
+  double prof_work[CTPN_KIND_COUNT] = {0};
+};
+
+namespace ctpn {
+
+// 16-bit activation -> fp32 on the host (ctpn_get_tensor, ctpn_debug_conv3x3)
+static inline float host_bf16_to_f32(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; std::memcpy(&f, &u, 4); return f; }
+static inline float host_f16_to_f32(uint16_t b) { _Float16 h; std::memcpy(&h, &b, 2); return (float)h; }
+static inline uint16_t host_f32_to_bf16(float f) {
+  uint32_t u; std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+static inline uint16_t host_f32_to_f16(float f) { const _Float16 h = (_Float16)f; uint16_t b; std::memcpy(&b, &h, 2); return b; }
+static inline DType prec_dtype(int precision) {
+  return precision == CTPN_PREC_FP32 ? DType::F32 : precision == CTPN_PREC_FP16 ? DType::F16 : precision == CTPN_PREC_SPLIT ? DType::SPLIT : DType::BF16;
+}
+
+static inline int lvl(int v, int level) { for (int i = 0; i < level; ++i) v /= 2; return v; }
+// Slack around every activation buffer: the conv kernels fetch input windows without clamping (conv3x3.hip). Behind the last image:
+// 2D tiles read up to 17 (+ 8: half items of the tail round) bordered rows + one window row past it (16 x 16 patches), flat mode's last tile a whole window
+// (256 + 2 (W + 2) + 2 pixels); in front of the first: flat mode's first tile starts one bordered row + 1 pixel early.
+static inline size_t act_slack_pixels(int w) { return (size_t)28 * (w + 2) + 384; }    // behind (+ 8 rows: the second half of a split tail tile)
+static inline size_t act_front_pixels(int w) { return (size_t)(w + 2) + 64; }          // in front
+
+// the column NMS of a small batch spreads its columns over the machine (proposal.hip: nms_column_groups_kernel); option nms_columns = 2 / 3
+// pins one form for A/B runs and the tests
+// hf: rows of the feature map (a column holds hf x 10 candidates at most, the kernel's list 1024), 0 for the connector's <= 1024 boxes
+static inline bool nms_multi_wg(const ctpn_ctx* c, int n, int hf) {
+  return c->nms_mw_scratch && hf * 10 <= 1024 && ((c->nms_columns == 3 && n <= NMS_MW_CAP_BATCH) || (c->nms_columns == 1 && n <= NMS_MW_MAX_BATCH));
+}
+
+// CTPN_DEBUG_SYNC / CTPN_ROCTX: read once per process (api_ctx.hip)
+int debug_sync();
+struct RoctxApi { int (*push)(const char*) = nullptr; int (*pop)() = nullptr; };
+const RoctxApi& roctx_api();
+int roctx_on();
+static const char* kKindNames[CTPN_KIND_COUNT + 1] = {"ctpn:conv_first", "ctpn:conv_gemm", "ctpn:pool", "ctpn:gemm", "ctpn:bilstm",
+                                                     "ctpn:decode", "ctpn:sort", "ctpn:nms", "ctpn:conv_stack"};
+struct Timed {
+  ctpn_ctx* c; int kind; double work; hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
+  Timed(ctpn_ctx* c_, int kind_, double work_, hipStream_t st_ = nullptr) : c(c_), kind(kind_), work(work_), on(c_->prof && (c_->prof_mode == 1 || kind_ == CTPN_KIND_COUNT)), st(st_ ? st_ : c_->stream) {
+    if (debug_sync()) { fprintf(stderr, "[ctpn] launch kind %d work %.3g\n", kind, work); fflush(stderr); }
+    // CTPN_ROCTX=1: a roctx range around the enqueue of every stage (rocprofv3 --marker-trace shows them next to the kernels;
+    // the reference's only instrumentation is the wall-clock Timer of ctpn/demo.py:56-66)
+    if (roctx_on()) (void)roctx_api().push(kKindNames[kind]);
+    if (!on) return;
+    auto get = [&]() { hipEvent_t e; if (!c->free_events.empty()) { e = c->free_events.back(); c->free_events.pop_back(); } else { (void)hipEventCreate(&e); } return e; };
+    a = get(); b = get();
+    (void)hipEventRecord(a, st);
+  }
+  ~Timed() {
+    if (roctx_on()) (void)roctx_api().pop();
+    if (debug_sync()) { hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[ctpn]   done kind %d: %s\n", kind, hipGetErrorString(e)); fflush(stderr); }
+    if (!on) return;
+    (void)hipEventRecord(b, st);
+    c->pending.push_back({kind, a, b, work});
+  }
+};
+
+// the network forward (api_forward.hip); tail_on_p: the recurrent tail runs on stream_p (option tail_overlap)
+int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p = false);
+// the proposal layer in stream order on s (api_proposals.hip; null: the forward's stream); ev_decoded is recorded behind the decode kernel
+int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
+                      int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s = nullptr,
+                      hipEvent_t ev_decoded = nullptr);
+
+}  // namespace ctpn

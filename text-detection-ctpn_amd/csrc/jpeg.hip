@@ -569,7 +569,7 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
-// entry points used by ctpn_api.hip
+// entry points used by api_input.hip
 // ---------------------------------------------------------------------------------------------
 int jpeg_probe(const uint8_t* data, size_t len, int* h, int* w, int* ncomp, int* luma_sampling) {
   JFrame f; std::string why;

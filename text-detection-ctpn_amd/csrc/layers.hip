@@ -455,7 +455,7 @@ int pack_conv1_frags(const float* w27x64_dev, const float* bias_dev, uint4* frag
 // bytes are fetched as ALIGNED dwords (any byte alignment of the image pointer and of W * 3) and passed through LDS; a thread reads the
 // four aligned dwords around its 12 bytes, shifts them into place (v_alignbyte, the shift is uniform per workgroup) and turns them
 // into four pixels (q_B, q_G, q_R, 1.0): two 16-byte stores. Only image pixels are written; the zero frame around them is the buffer's
-// initial state (ctpn_api.hip zeroes it when the geometry changes).
+// initial state (api_forward.hip zeroes it when the geometry changes).
 // ---------------------------------------------------------------------------------------------
 template <typename HF>
 __global__ __launch_bounds__(256) void image_to_q_kernel(const uint8_t* __restrict__ img, uint2* __restrict__ q, int N, int H, int W, int Hq, int Wq, int segs) {

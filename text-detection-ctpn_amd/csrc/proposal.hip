@@ -875,7 +875,7 @@ __global__ __launch_bounds__(MW_WAVES * 64) void nms_column_groups_kernel(
     }
     // a column with more candidates than the list holds would lose the rest silently: the callers' preconditions exclude it (hf x 10 <= 1024
     // and no box clipped onto a neighbour's column: enqueue_proposals), and a caller that breaks them finds this STICKY word set (never cleared
-    // by the kernel; option nms_check reads it, ctpn_api.hip)
+    // by the kernel; option nms_check reads it, api_proposals.hip)
     if (m > MW_LIST && lane == 0) __hip_atomic_fetch_or((unsigned*)(blk + NMS_MW_OVERFLOW_OFF), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     m = m > MW_LIST ? MW_LIST : m;
 
@@ -991,10 +991,9 @@ __global__ __launch_bounds__(MW_WAVES * 64) void nms_column_groups_kernel(
 
 // col_scale (im_info rows [h, w, scale], nullable) selects the connector's variant (stride <= 1024, 4 waves).
 // PRECONDITION: boxes on the 16-px anchor grid (common.h); arbitrary boxes must go through launch_nms.
-int g_debug_nms = 0;        // diagnostic (option debug_nms): process-wide on purpose -- a measurement switch, set right before the launch it applies to
 int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, const int* counts_in, int stride, float thresh, int max_keep,
                        int* keep_idx, int keep_stride, int* keep_counts, float* rois_out, float* kept_spill, int n_img, int ncols, hipStream_t s,
-                       const int* sorted_anchor, int* roi_anchor, const float* col_scale, void* mw_scratch, const unsigned char* colid, int prefix) {
+                       const int* sorted_anchor, int* roi_anchor, const float* col_scale, void* mw_scratch, const unsigned char* colid, int prefix, int dbg) {
   if (!kept_spill) return fail(CTPN_ERR_ARG, "nms: spill buffer (n_img x stride x 4 floats) required");
   if (ncols < 1 || ncols > NC_MAXCOL || stride > NC_MAXN || !(thresh >= 0.1f)) return fail(CTPN_ERR_ARG, "nms_columns: outside the column decomposition's domain");
   if (roi_anchor && (!sorted_anchor || !rois_out)) return fail(CTPN_ERR_ARG, "nms: roi_anchor needs sorted_anchor and rois_out");
@@ -1016,7 +1015,7 @@ int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, co
   } else {
     hipLaunchKernelGGL((nms_columns_kernel<16, NC_MAXN, 128>), dim3(n_img), dim3(1024), 0, s, sorted_boxes, sorted_scores, counts_in, stride, thresh,
                        max_keep, keep_idx, keep_stride, keep_counts, rois_out, (float4*)kept_spill, sorted_anchor, roi_anchor, ncols, nullptr,
-                       (prefix > 0 && max_keep < prefix) ? prefix : 0, g_debug_nms);
+                       (prefix > 0 && max_keep < prefix) ? prefix : 0, dbg);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("nms_columns launch: ") + hipGetErrorString(e));

@@ -160,6 +160,7 @@ def test_weight_arena_views_and_determinism(arena):
     v = ctpn_amd.arena_views(arena)
     assert v["conv1_1/weights"].shape == (3, 3, 3, 64) and v["rpn_conv/3x3/weights"].shape == (3, 3, 512, 512)
     assert v["lstm_o/bidirectional_rnn/bw/lstm_cell/kernel"].shape == (640, 512) and v["rpn_cls_score/weights"].shape == (512, 20)
+    # the benchmark arena's biases are zero on purpose (bench.py's numbers rest on it); non-zero biases: tests/test_gpu_bias_and_saturation.py
     assert float(np.abs(v["conv5_3/biases"]).max()) == 0.0
     again = ctpn_amd.make_synthetic_arena(0)
     assert np.array_equal(arena, again)

@@ -49,6 +49,40 @@ def match_lines(got, ref, px_tol=1.0, score_tol=1e-3):
     return True
 
 
+_LSTM_BIAS = ("lstm_o/bidirectional_rnn/fw/lstm_cell/bias", "lstm_o/bidirectional_rnn/bw/lstm_cell/bias")
+# std of every bias class per recipe: (image_gain, conv, LSTM cell, lstm_o FC, rpn_cls_score, rpn_bbox_pred). "biased" LSTM cell: 0.7, as
+# 0.5 left the TF-order-bias mutant of tests/test_oracle.py below 100 bf16 tolerances of lstm_pre (91; 102 at 0.7)
+STRESS_KINDS = {"biased": (1.0 / 64.0, 0.1, 0.7, 0.5, 0.5, 0.1),
+                "fullscale": (1.0, 0.5, 1.0, 1.0, 1.0, 0.1)}
+
+
+def stress_arena(kind, seed=3):
+    """The benchmark's weight recipe (ctpn_amd.make_synthetic_arena, whose 21 bias vectors are all zero) with EVERY bias of the manifest
+    filled from a seeded generator: distinct per-channel values of both signs, no zero among them.
+      "biased"     image_gain 1/64 like the benchmark arena, so every magnitude stays where the suite's tolerances were set: a wrong, dropped
+                   or mis-ordered bias shows up against those tolerances (tests/test_oracle.py holds the mutants that prove it);
+      "fullscale"  image_gain 1.0, the pixel scale a trained conv1_1 sees: LSTM pre-activations beyond +-88.8 (exp overflows in fp32), gates
+                   at exactly 0 / 1, pair softmax at exactly 1.0f next to 1e-17 (conditions in tests/test_oracle.py)."""
+    import ctpn_amd
+    gain, conv, cell, fc, cls, bbox = STRESS_KINDS[kind]
+    arena = ctpn_amd.make_synthetic_arena(seed, image_gain=gain)
+    v = ctpn_amd.arena_views(arena)
+    # stream 1 of the seed: the benchmark recipe has consumed stream 0 (default_rng(seed)) for the weights, and of the streams 0, 1, 2 .. this
+    # is the first on which "fullscale" meets every condition of tests/test_oracle.py (stream 0: smallest cls_prob 1e-9, asked < 1e-12; the
+    # pair softmax's reach is set by 10 anchor offsets b_fc . W_cls, a draw of ten -- raising image_gain to 4 does not move it, measured)
+    rng = np.random.default_rng([seed, 1])
+    for name, shape, _ in ctpn_amd.MANIFEST:
+        if len(shape) != 1:
+            continue
+        std = cell if name in _LSTM_BIAS else fc if name == "lstm_o/biases" else cls if name == "rpn_cls_score/biases" else \
+            bbox if name == "rpn_bbox_pred/biases" else conv
+        b = (rng.standard_normal(shape) * std).astype(np.float32)
+        while (b == 0).any() or np.unique(b).size != b.size:          # (never taken with the committed seeds; the conditions are tested)
+            b = (rng.standard_normal(shape) * std).astype(np.float32)
+        v[name][...] = b
+    return arena
+
+
 # Fixtures whose rois are dominated by exactly tied scores (fp32-saturated 1.0: 630 of the 1000 rois of the 80 x 120 case).
 # The reference orders ties by numpy's unstable argsort()[::-1] (implementation-defined), this build by ascending index
 # (documented deviation): the SET of text lines is identical, their order follows the tie order -- compare those as sets.

@@ -363,6 +363,40 @@ int    ctpn_decode_jpeg_files(ctpn_ctx* ctx, const char* const* paths, int n, in
 int    ctpn_jpeg_probe_files(const char* const* paths, int n, int* info4, int threads);
 int    ctpn_jpeg_batch_fetch(ctpn_ctx* ctx, const uint8_t* images_dev, uint8_t* host_out, size_t capacity);
 
+/* ---- cv2.imwrite for the annotated result images (reference ctpn/demo.py:28-52: draw_boxes, cv2.resize by 1 / scale, cv2.imwrite), the mirror
+ * image of the JPEG reader above, split where the work splits: BGR -> YCbCr, 2 x 2 chroma downsampling, the 8 x 8 forward DCT and the
+ * quantiser on the device (one launch; the outlines and the resize before it, so annotated pixels never visit the host), baseline Huffman
+ * coding and the file writing on the ctx's worker pool, one image per thread. The arithmetic is libjpeg's, integer for integer (jccolor.c,
+ * jcsample.c h2v2_downsample, jfdctint.c islow, jcdctmgr.c's quantiser, jccoefct.c's dummy blocks, jchuff.c with the standard tables K.3 - K.6),
+ * the marker sequence libjpeg's (SOI, JFIF APP0, DQT 0, DQT 1, SOF0, four DHT, SOS, data, EOI): the files are byte-equal to Pillow's
+ * save(quality = q, subsampling = 2) (libjpeg-turbo), which is what cv2.imwrite writes with its defaults at q = 95. Parity with a real
+ * cv2.imwrite is UNPINNED (cv2 is not installed). Always 4:2:0, three components; no optimised tables, restart markers or EXIF.
+ *   ctpn_jpeg_encode_capacity   upper bound of the bytes one h x w file can need (0 for a bad size): header + 416 bytes per block (a block
+ *                               codes into at most 1660 bits, every byte of which may need a stuffed zero) + padding + EOI
+ *   ctpn_jpeg_entropy_encode    the host half alone (needs no device): coefficients, layout8 and qt EXACTLY as ctpn_jpeg_entropy_decode returns
+ *                               them -- NATURAL order (the device half writes zig-zag order; the library converts where the two meet) -- so
+ *                               decode followed by encode reproduces a baseline 3-component file written with the standard tables byte for
+ *                               byte. *bytes_out is the file size, also when it exceeds capacity (CTPN_ERR_CAPACITY; out == NULL with
+ *                               capacity 0 sizes the file). CTPN_ERR_UNSUPPORTED: other than 3 components, an EXIF orientation, quantisation
+ *                               values above 255, different tables for Cb and Cr
+ *   ctpn_encode_jpeg_batch      n images of h x w x 3 BGR uint8, in HBM (images_on_device) or on the host (copied in the ctx's copy queue) ->
+ *                               n files in caller memory: out[i] holds capacities[i] bytes, bytes_out[i] receives the size (also of a file
+ *                               that did not fit: CTPN_ERR_CAPACITY). quality 1 .. 100 (else CTPN_ERR_ARG)
+ *   ctpn_write_annotated_files  one batch of the demo: the outlines of recs (n x line_capacity x 9 float64, line_counts[i] lines each, as
+ *                               ctpn_detect_collect returns them) drawn exactly as ctpn_draw_boxes draws them, cv2.resize by 1 / scale
+ *                               (nothing for scale 1), and paths[i] written at `quality`. images_dev: n x h x w x 3 in HBM -- a live batch of
+ *                               ctpn_decode_jpeg_batch, or any device buffer whose contents are complete; it is not modified (the drawing
+ *                               goes onto a copy owned by the ctx: the decoder's buffer may still feed a forward). A path that cannot be
+ *                               written is CTPN_ERR_ARG, its name in ctpn_last_error().
+ * The two ctx calls run their device half in the ctx's copy queue, behind the decode that produced the batch and in front of the next one,
+ * and return when the files are coded; their buffers grow to the largest batch seen and are then reused (no allocation per call). */
+size_t ctpn_jpeg_encode_capacity(int h, int w);
+int    ctpn_jpeg_entropy_encode(const int16_t* coef, const int* layout8, const uint16_t* qt, uint8_t* out, size_t capacity, size_t* bytes_out);
+int    ctpn_encode_jpeg_batch(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
+                              const size_t* capacities, size_t* bytes_out);
+int    ctpn_write_annotated_files(ctpn_ctx* ctx, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity,
+                                  const int* line_counts, double scale, const char* const* paths, int quality);
+
 /* ---- cv2.imread for PNG files (reference ctpn/demo.py:59; data/demo holds .jpg and .png). HOST ONLY, by the nature of the format: one
  * DEFLATE stream (zlib's inflate, the library libpng itself sits on) and row filters that chain from row to row -- nothing a GPU is for. One
  * file per host thread, straight into the caller's batch buffer, which ctpn_detect_submit / ctpn_forward take as host images (one

@@ -15,6 +15,7 @@ _LIB = None
 
 CTPN_OK = 0
 CTPN_ERR_UNSUPPORTED = -6
+CTPN_ERR_CAPACITY = -4
 PREC_FP32, PREC_BF16, PREC_FP16, PREC_SPLIT = 0, 1, 2, 3
 PRECISIONS = {"fp32": PREC_FP32, "f32": PREC_FP32, "bf16": PREC_BF16, "fp16": PREC_FP16, "f16": PREC_FP16, "split": PREC_SPLIT}
 
@@ -107,6 +108,11 @@ def _declare(lib):
         "ctpn_jpeg_batch_fetch": (C.c_int, [vp, vp, u8p, C.c_size_t]),
         "ctpn_decode_jpeg_files": (C.c_int, [vp, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(vp), i32p, i32p]),
         "ctpn_jpeg_probe_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, i32p, C.c_int]),
+        "ctpn_jpeg_encode_capacity": (C.c_size_t, [C.c_int, C.c_int]),
+        "ctpn_jpeg_entropy_encode": (C.c_int, [C.POINTER(C.c_int16), i32p, C.POINTER(C.c_uint16), u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "ctpn_encode_jpeg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_size_t)]),
+        "ctpn_write_annotated_files": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_double, C.POINTER(C.c_char_p), C.c_int]),
         "ctpn_debug_png_backend": (C.c_int, [C.c_int]),
         "ctpn_png_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_png_decode": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t]),
@@ -326,6 +332,27 @@ def jpeg_entropy_decode(data):
         planes.append(coef[off: off + bw * bh * 64].reshape(bh, bw, 64))
         off += bw * bh * 64
     return planes, qt, {"h": h, "w": w, "ncomp": nc, "hs": hs, "vs": (bh0 // bh1 if nc == 3 else 1), "orientation": orient}
+
+
+def jpeg_encode_capacity(h, w):
+    """Upper bound of the bytes one h x w JPEG file written by this library can need (ctpn_jpeg_encode_capacity)."""
+    return int(load_library().ctpn_jpeg_encode_capacity(int(h), int(w)))
+
+
+def jpeg_entropy_encode(coef, layout8, qt):
+    """The host half of the JPEG encoder alone (ctpn_jpeg_entropy_encode; no device): the flat int16 coefficient array (natural order),
+    the 8 layout ints and the (3, 64) quantisation tables exactly as ctpn_jpeg_entropy_decode fills them -> the file's bytes."""
+    lib = load_library()
+    coef = np.ascontiguousarray(coef, dtype=np.int16).reshape(-1)
+    l8 = np.ascontiguousarray(layout8, dtype=np.int32).reshape(8)
+    qt = np.ascontiguousarray(qt, dtype=np.uint16).reshape(192)
+    n = C.c_size_t(0)
+    rc = lib.ctpn_jpeg_entropy_encode(_ptr(coef, C.c_int16), _ptr(l8, C.c_int), _ptr(qt, C.c_uint16), None, 0, C.byref(n))
+    if rc != CTPN_ERR_CAPACITY:
+        _check(rc)
+    out = np.empty((max(int(n.value), 1),), np.uint8)
+    _check(lib.ctpn_jpeg_entropy_encode(_ptr(coef, C.c_int16), _ptr(l8, C.c_int), _ptr(qt, C.c_uint16), _ptr(out, C.c_uint8), out.size, C.byref(n)))
+    return out[: n.value].tobytes()
 
 
 def text_lines(boxes, scores, size, mode="H", device_id=0, capacity=4096):
@@ -661,6 +688,46 @@ class Context:
         out = np.empty((n, h, w, 3), np.uint8)
         _check(self._lib.ctpn_jpeg_batch_fetch(self._h, C.c_void_p(int(device_ptr)), _ptr(out, C.c_uint8), out.size))
         return out
+
+    def encode_jpeg_batch(self, images=None, quality=95, device_ptr=None, shape=None):
+        """cv2.imwrite's JPEG bytes of n BGR uint8 images of one size (ctpn_encode_jpeg_batch): colour conversion, chroma downsampling, DCT
+        and quantiser on the device, Huffman coding on the ctx's host pool. images: (n, h, w, 3) on the host, or device_ptr + shape.
+        -> list of n bytes objects, byte-equal to Pillow's save(quality=quality, subsampling=2)."""
+        if device_ptr is None:
+            images = np.ascontiguousarray(images, dtype=np.uint8)
+            if images.ndim != 4 or images.shape[3] != 3:
+                raise ValueError("encode_jpeg_batch wants (n,h,w,3) uint8")
+            shape, src, on_dev = images.shape, images.ctypes.data_as(C.c_void_p), 0
+        else:
+            src, on_dev = C.c_void_p(int(device_ptr)), 1
+        n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+        bound = jpeg_encode_capacity(h, w)
+        sizes = (C.c_size_t * n)()
+        for cap in (min(bound, h * w + 4096), bound):      # a byte per pixel holds any photograph; the proven bound is three times the raw image
+            bufs = np.empty((n, cap), np.uint8)
+            ptrs = (C.c_void_p * n)(*[bufs[i].ctypes.data for i in range(n)])
+            caps = (C.c_size_t * n)(*([cap] * n))
+            rc = self._lib.ctpn_encode_jpeg_batch(self._h, src, on_dev, n, h, w, int(quality), ptrs, caps, sizes)
+            if rc != CTPN_ERR_CAPACITY or cap == bound:
+                break
+        _check(rc)
+        return [bufs[i, : sizes[i]].tobytes() for i in range(n)]
+
+    def write_annotated_files(self, device_ptr, shape, recs, scale, paths, quality=95):
+        """draw_boxes + cv2.resize(1 / scale) + cv2.imwrite (reference ctpn/demo.py:28-52) for a batch of device images
+        (ctpn_write_annotated_files): recs = one (M_i, 9) array per image, paths = one JPEG file name per image. The batch is not modified."""
+        n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+        recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 9) for r in recs]
+        assert len(recs) == n and len(paths) == n
+        cap = max([r.shape[0] for r in recs] + [1])
+        packed = np.zeros((n, cap, 9), np.float64)
+        counts = np.zeros((n,), np.int32)
+        for i, r in enumerate(recs):
+            packed[i, : r.shape[0]] = r
+            counts[i] = r.shape[0]
+        keep, arr = _path_array(list(paths))
+        _check(self._lib.ctpn_write_annotated_files(self._h, C.c_void_p(int(device_ptr)), n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
+                                                    float(scale), arr, int(quality)))
 
     def detect_submit(self, images=None, slot=0, scales=None, device_ptr=None, shape=None):
         """Asynchronous detect, part 1 (ctpn_detect_submit). Returns immediately."""

@@ -347,6 +347,9 @@ int ctpn_destroy(ctpn_ctx* c) {
   }
   for (void* p : {(void*)c->jpeg_planes, (void*)c->jpeg_raw}) if (p) (void)hipFree(p);
   for (void* p : c->jpeg_retired) (void)hipFree(p);
+  for (void* p : {(void*)c->enc.img_dev, (void*)c->enc.rs_dev, (void*)c->enc.coef_dev, (void*)c->enc.recs_dev, (void*)c->enc.cnt_dev, c->enc.qtab_dev}) if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->enc.coef_host, c->enc.qtab_host}) if (p) (void)hipHostFree(p);
+  if (c->enc.ev_done) (void)hipEventDestroy(c->enc.ev_done);
   if (c->stream_p) (void)hipStreamDestroy(c->stream_p);
   for (auto& r : c->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : c->free_events) (void)hipEventDestroy(e);

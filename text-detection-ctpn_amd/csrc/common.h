@@ -280,6 +280,16 @@ int launch_jpeg_pixels(const int16_t* coef_dev, const uint16_t* qt_dev, uint8_t*
 int jpeg_probe(const uint8_t* data, size_t len, int* h, int* w, int* ncomp, int* luma_sampling);
 size_t jpeg_coef_capacity(int h, int w);
 
+// jpeg_enc.hip: BGR images -> JPEG files (quality q, 4:2:0, standard Huffman tables), pixels to quantised coefficients on the device, entropy
+// coding on the host; draw_boxes_kernel = ctpn_draw_boxes on device images
+struct JencQ;
+void jpeg_enc_geom(int h, int w, JpegGeom& g);
+void jpeg_enc_qtables(int quality, uint16_t* qt3x64, JencQ* q2x64);
+size_t jpeg_encode_capacity(int h, int w);
+int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, int vs, const uint16_t* qt3x64, uint8_t* out, size_t capacity, size_t* bytes_out);
+int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JpegGeom& g, int n, hipStream_t s);
+int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* counts_dev, int line_capacity, int n, int h, int w, hipStream_t s);
+
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 }  // namespace ctpn

@@ -179,6 +179,16 @@ struct ctpn_ctx {
   std::vector<void*> jpeg_retired;   // device allocations replaced by larger ones
   int jpeg_flip = 0;
   bool jpeg_ready = false;
+  // ctpn_encode_jpeg_batch / ctpn_write_annotated_files (api_output.hip): ONE set of buffers -- both calls return when their files are coded,
+  // so nothing of a call is in flight when the next one starts -- allocated on first use and grown to the largest batch seen
+  struct EncBufs {
+    uint8_t* img_dev = nullptr; size_t img_bytes = 0;          // the batch's pixels: staged host images, or the copy the outlines are drawn on
+    uint8_t* rs_dev = nullptr; size_t rs_bytes = 0;            // ... resized by 1 / scale
+    int16_t* coef_dev = nullptr; int16_t* coef_host = nullptr; size_t coef_elems = 0;      // quantised coefficients; the host side is page-locked
+    double* recs_dev = nullptr; size_t recs_bytes = 0; int* cnt_dev = nullptr; size_t cnt_n = 0;
+    void* qtab_dev = nullptr; void* qtab_host = nullptr; int qtab_quality = 0;               // JencQ[2][64] of the quality last used
+    hipEvent_t ev_done = nullptr;
+  } enc;
   int debug_nms = 0;                 // "debug_nms" (diagnostic, WRONG proposals): parts mask of the one-workgroup proposal NMS, see nms_columns_kernel
   int debug_hog = 0;                 // "debug_hog" (diagnostic, 0 .. 200000; see the launch in enqueue_proposals_impl for the two upper ranges): launch a kernel with the one-workgroup NMS's footprint (1024 threads, 84 KB of LDS, one
                                      // workgroup per image) that spins this many microseconds without memory traffic in front of the proposal NMS. Results are unaffected;

@@ -149,7 +149,7 @@ def _read(name):
         return f.read()
 
 
-def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8):
+def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host"):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -157,7 +157,11 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     and orientation, all read from the headers (one size, one resize factor, one network shape per batch). PNG files are decoded by the library too, on the host by the nature of the format
     (ctpn_decode_png_files: inflate + row filters, one file per C++ thread, straight into the batch buffer that ctpn_detect_submit copies to
     the device). Files neither decoder takes (CMYK / arithmetic-coded / truncated JPEG, 16-bit PNG, other formats) go through Pillow
-    (lib/utils/image.py), batched the same way; the result files are the same whichever decoder a file went through."""
+    (lib/utils/image.py), batched the same way; the result files are the same whichever decoder a file went through.
+    encode='gpu' (with write_images): the annotated images of device-decoded batches whose output name is a JPEG's are drawn, resized by
+    1 / scale and JPEG-coded by the library at collect time (ctpn_write_annotated_files: kernels in the ctx's copy queue, Huffman coding and
+    file writing on its C++ pool) -- those pixels never reach the host. PNG-named outputs (a lossless DEFLATE stream: host work by nature),
+    batches of the host decoders and the single images keep Pillow's writer; the files are byte-identical either way."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -187,7 +191,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             jobs.append(((h, w), "jpg" if layout[0] > 0 else ("png" if layout == PNG else "host"), f, rs, members[i:i + batch]))
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
-    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0}
+    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_host": 0}
+    dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
     # PNG batches are decoded ONE JOB AHEAD on a helper thread (the C++ decode threads hang off that call; ctypes releases the GIL), so that
     # batch k + 1 inflates while batch k is submitted and batch k - 1 collected. Three batch buffers per shape in a ring: when batch k + 1
     # starts decoding, batch k sits decoded in its buffer and batch k - 1 may still be on its way to the device. THREE slots whatever the
@@ -215,7 +220,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
 
     def emit(nm):
         img, scale = meta.pop(nm)
-        if write_images:
+        if write_images and img is not None:
+            stats["enc_host"] += 1
             D.draw_boxes(img.copy(), nm, results[nm], scale, out_dir)
         else:
             base = os.path.basename(nm)
@@ -225,6 +231,11 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         slot, members = job
         for nm, recs in zip(members, net.ctx.detect_collect(slot, mode=mode, line_capacity=1024)):
             results[nm] = recs
+        if slot in dev_batches:                        # draw + resize + JPEG of the whole batch behind the C ABI; emit() writes the text files
+            ptr, shape, scale = dev_batches.pop(slot)
+            net.ctx.write_annotated_files(ptr, shape, [results[nm] for nm in members], scale,
+                                          [os.path.join(out_dir, os.path.basename(nm)) for nm in members])
+            stats["enc_gpu"] += len(members)
         for nm in members:
             emit(nm)
 
@@ -238,12 +249,15 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                 assert tuple(shape[1:]) == tuple(rs), (shape, rs)
                 net.ctx.detect_submit(device_ptr=ptr, shape=shape, slot=k & 1)
                 stats["gpu"] += len(members)
-                if write_images:
+                if write_images and encode == "gpu" and all(_is_jpeg(nm) for nm in members):      # (the output's format follows its NAME)
+                    dev_batches[k & 1] = (ptr, shape, f)      # (live until the second-next decode: collected one decode from now)
+                elif write_images:
                     imgs = net.ctx.jpeg_batch_fetch(ptr, shape)
             except B.CtpnError as e:                                       # e.g. damaged entropy data: the host decoder's call
                 if e.code not in (B.CTPN_ERR_UNSUPPORTED, -1):
                     raise
                 kind = "host"
+                dev_batches.pop(k & 1, None)
         elif kind == "png":
             try:
                 imgs = png_ahead.pop(k).result()
@@ -276,16 +290,26 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     dt = time.time() - t0
     log('Detection of {:d} images in {:d} batches took {:.3f}s, result files included, after a header scan of {:.3f}s ({:.1f} images/s; {:d} decoded on the device, {:d} PNG files by the library, {:d} on the host)'.format(
         len(names), len(jobs) + len(singles), dt, t_plan, len(names) / max(dt, 1e-9), stats["gpu"], stats["png"], stats["host"] + len(singles)))
+    if write_images:
+        log('Annotated images: {:d} drawn, resized and JPEG-coded by the library (device + C++ pool), {:d} by the host writer (Pillow)'.format(
+            stats["enc_gpu"], stats["enc_host"]))
     return results
 
 
-def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host"):
+def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
+        encode="host"):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
-    buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu)."""
+    buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
+    encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
+    (ctpn_write_annotated_files); 'host' (default): every image through Pillow, as before."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config()
+    if encode not in ("host", "gpu"):
+        raise ValueError("encode must be 'host' or 'gpu'")
+    if encode == "gpu" and decode != "gpu":
+        raise ValueError("encode='gpu' writes the images of device-decoded batches: it needs decode='gpu'")
     if decode == "gpu":
-        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads)
+        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -423,6 +447,8 @@ def main(argv=None):
     ap.add_argument('--decode-threads', type=int, default=8, help='host threads decoding / resizing the next batch')
     ap.add_argument('--decode-procs', type=int, default=0, help='decode in this many worker PROCESSES (shared-memory batches) instead of threads')
     ap.add_argument('--decode', default='host', choices=['host', 'gpu'], help="gpu: JPEG decode + resize_im on the device (ctpn_decode_jpeg_batch)")
+    ap.add_argument('--encode', default='host', choices=['host', 'gpu'],
+                    help="gpu (with --decode gpu): annotated JPEG images drawn, resized and coded by the library (ctpn_write_annotated_files)")
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
                          "throughput choice (3.2 x split's rate, outside the 1e-3 / 1 px bar)")
@@ -437,7 +463,7 @@ def main(argv=None):
     if not names:
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
-        decode_procs=args.decode_procs, decode=args.decode)
+        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode)
     net.close()
 
 

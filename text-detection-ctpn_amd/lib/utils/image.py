@@ -78,6 +78,23 @@ def imwrite(path, bgr):
         im.save(path)
 
 
+def imencode_jpeg_batch(ctx, images, quality=95, device_ptr=None, shape=None):
+    """cv2.imencode('.jpg', img, [IMWRITE_JPEG_QUALITY, quality]) for a batch of BGR uint8 images of one size, on the GPU
+    (ctpn_encode_jpeg_batch): (n, h, w, 3) on the host, or device_ptr + shape -> list of n bytes objects, byte-equal to what imwrite above
+    puts into a .jpg file at the same quality."""
+    return ctx.encode_jpeg_batch(images, quality=quality, device_ptr=device_ptr, shape=shape)
+
+
+def imwrite_jpeg_batch(ctx, paths, images, quality=95, device_ptr=None, shape=None):
+    """imwrite for a batch of JPEG files: encoded by imencode_jpeg_batch, one file per image."""
+    paths = list(paths)
+    files = imencode_jpeg_batch(ctx, images, quality=quality, device_ptr=device_ptr, shape=shape)
+    assert len(files) == len(paths)
+    for path, data in zip(paths, files):
+        with open(path, "wb") as f:
+            f.write(data)
+
+
 def draw_line(img, p0, p1, color, thickness=2):
     """Bresenham-free dense line rasteriser (enough for the annotated demo output)."""
     x0, y0 = p0

@@ -32,7 +32,7 @@ def weights(arena):
 
 
 def test_lds_dma_helper_forms_agree():
-    """conv3x3_impl.h's c3_glds16_saddr puts m0 on its clobber list (two SALU fewer per KiB than saving and restoring it; clang's
+    """conv3x3_base.h's c3_glds16_saddr puts m0 on its clobber list (two SALU fewer per KiB than saving and restoring it; clang's
     -Winline-asm about reserved registers is silenced for that one statement), c3_glds16_asm saves and restores m0 around the same
     global_load_lds_dwordx4. Both forms on the same tiles: the bytes that arrive in LDS are the source bytes, in both. A compiler that
     starts to keep state in m0 across the statement shows up here (and in every conv layer test) instead of as a silent corruption."""

@@ -122,7 +122,7 @@ def test_bilstm_split_h_planes_conflict_free():
 
 
 def test_fused_conv1_producer_covers_the_window_and_stays_inside_its_buffers():
-    """csrc/conv3x3_impl.h, conv3x3_wr_kernel<FUSE>: the index arithmetic of the conv1_1 producer, restated. A tile's 10 x 34-pixel window
+    """csrc/conv3x3_wr.h, conv3x3_wr_kernel<FUSE>: the index arithmetic of the conv1_1 producer, restated. A tile's 10 x 34-pixel window
     is produced by 4 waves x 3 groups of 32 lanes; every window pixel must be written (some twice, with the same value), every write must
     land inside the 48-KiB window buffer at the 144-byte pitch, every operand read inside the 12 x 36-pixel q patch (the plane), and the
     patch's 216 sixteen-byte chunks must be fetched exactly once by the one LDS-DMA per wave."""

@@ -173,7 +173,7 @@ int pack_conv1_frags(const float* w27x64_dev, const float* bias_dev, uint4* frag
 // ---- the q-image: the uint8 feed of the 16-bit modes as 8-byte pixels (q_B, q_G, q_R, P) of the mode's 16-bit type, q_c = p_c - round(mean_c)
 // (an integer, exact in bf16 and fp16), P = 1.0; image pixel (y, x) sits at q pixel (y + 2, x + 2) of an Hq x Wq map whose other pixels are
 // all-zero -- TF's SAME padding of conv1_1 AND the inside-the-image indicator its mean correction needs (layers.hip). 4.4 MB per 600 x 900
-// image instead of the 69 MB of conv1_1's output: what conv1_2 reads when conv1_1 is computed inside its window stage (conv3x3_impl.h).
+// image instead of the 69 MB of conv1_1's output: what conv1_2 reads when conv1_1 is computed inside its window stage (conv3x3_wr.h).
 static inline int conv1_q_h(int h) { return ((h + 7) / 8) * 8 + 4; }
 static inline int conv1_q_w(int w) { return ((w + 63) / 64) * 64 + 8; }
 static inline size_t conv1_q_bytes(int n, int h, int w) { return ((size_t)n * conv1_q_h(h) * conv1_q_w(w) + 1024) * 8; }
@@ -185,7 +185,7 @@ int launch_conv_first_from_q(const void* q, const void* frags, void* out, DType 
 int resize_out_dim(int src, double f);
 int launch_resize_linear(const void* src, void* dst, int is_f32, int n, int h, int w, int dh, int dw, double fx, double fy, hipStream_t s);
 int launch_cvt_bf16(const float* in, uint16_t* out, int n, int hw, hipStream_t s);
-// the two LDS-DMA helper forms of conv3x3_impl.h on `tiles` 1-KiB tiles of src (conv3x3.hip; test hook behind ctpn_debug_lds_dma)
+// the two LDS-DMA helper forms of conv3x3_base.h on `tiles` 1-KiB tiles of src (conv3x3.hip; test hook behind ctpn_debug_lds_dma)
 int launch_lds_dma_check(const void* src, void* out_clobber, void* out_keep, int tiles, hipStream_t s);
 int launch_pack_transpose(const float* src, long long src_ld, void* dst, long long dst_ld, DType dst_t,
                           int rows, int cols, hipStream_t s);

@@ -1,19 +1,19 @@
-// launch_conv3x3: layer-level decisions of the tap-reuse 3x3 convolution (kernels: conv3x3_impl.h, instantiated per arithmetic type in
+// launch_conv3x3: layer-level decisions of the tap-reuse 3x3 convolution (kernels: conv3x3_{tiled,persistent,wr,edge}.h, instantiated per arithmetic type in
 // conv3x3_{f32,bf16,f16,split}.hip) -- which kernel family a layer takes, what happens to the ragged pixel columns of a 2D tiling, and the
 // per-device resources the kernels share.
 //
 // Replaces tf.nn.conv2d + bias_add + relu of Network.conv (reference lib/networks/network.py:160-183) and the Network.max_pool that
 // follows it where one does (network.py:189-196; VGGnet_test.py:23,26,30,34).
-#include "conv3x3_impl.h"
+#include "conv3x3_base.h"
 
 namespace ctpn {
 
 // dump pages (where lanes outside the image store, so that every wave issues the same number of stores) and tile-claim counters of the
 // weights-in-registers kernel, per device, shared by its bf16 and fp16 instantiations
 int c3_wr_resources(int dev, hipStream_t s, char** dump_out, unsigned** claim_out) {
-  static char* dump[C3_MAX_DEV] = {nullptr};
-  static unsigned* claims[C3_MAX_DEV] = {nullptr};
-  static unsigned ticket[C3_MAX_DEV] = {0};
+  static char* dump[CTPN_MAX_DEV] = {nullptr};
+  static unsigned* claims[CTPN_MAX_DEV] = {nullptr};
+  static unsigned ticket[CTPN_MAX_DEV] = {0};
   static std::mutex mu;
   std::lock_guard<std::mutex> lk(mu);
   if (!dump[dev]) CTPN_HIP_TRY(hipMalloc((void**)&dump[dev], (size_t)1024 * 4096));
@@ -32,7 +32,7 @@ int c3_wr_resources(int dev, hipStream_t s, char** dump_out, unsigned** claim_ou
   return CTPN_OK;
 }
 
-// Guard of the LDS-DMA helpers' m0 contract (conv3x3_impl.h: c3_glds16_saddr declares m0 clobbered, c3_glds16_asm saves and restores it):
+// Guard of the LDS-DMA helpers' m0 contract (conv3x3_base.h: c3_glds16_saddr declares m0 clobbered, c3_glds16_asm saves and restores it):
 // every wave stages `rounds` 1-KiB tiles of `src` into LDS with BOTH forms, interleaved with ordinary LDS traffic and a wave-uniform loop
 // the compiler is free to schedule around them, and copies what arrived to out_clobber / out_keep. The two must be the source bytes.
 __global__ __launch_bounds__(256) void c3_lds_dma_check_kernel(const char* __restrict__ src, char* __restrict__ out_clobber,
@@ -132,7 +132,7 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
   static std::mutex strip_mu[16];     // the helper stream and its two events are per device, shared by every ctx on it
   int dev = 0;
   std::unique_lock<std::mutex> strip_lock;
-  // One or two images: the edge kernel runs in the layer's own stream, behind the main launch, in its DEEP form (conv3x3_impl.h) -- no fork,
+  // One or two images: the edge kernel runs in the layer's own stream, behind the main launch, in its DEEP form (conv3x3_edge.h) -- no fork,
   // no join. WHICH columns it takes is still a function of the layer's shape alone, and the deep form issues the same MFMAs in the same
   // order, so a batch and its images run alone still agree bit for bit.
   // Split precision, any batch: in the stream as well. Beside the main launch (forked, in front of it or behind it) the one-wave workgroups

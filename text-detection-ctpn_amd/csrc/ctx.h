@@ -143,7 +143,7 @@ struct ctpn_ctx {
   // the proposal NMS of batch k running beside the persistent conv kernels of batch k + 1 (in split precision by default timing, in bf16 as soon as
   // the NMS was delayed into conv3_x / conv4_x). This switch removed the CONDITION. The CAUSE was in the conv kernels: the last k-slice group's
   // fragment reads were in flight across the step barrier while the LDS-DMA behind it recycled the strip they read, ordered by latency only
-  // (conv3x3_impl.h, INVARIANT in conv3x3_p_kernel; profiles/r06_barrier_war.txt). Fixed there; the switch stays for A/B runs.
+  // (conv3x3_persistent.h, INVARIANT in conv3x3_p_kernel; profiles/r06_barrier_war.txt). Fixed there; the switch stays for A/B runs.
   int tail_confine = 0;
   // asynchronous detect, option tail_overlap = 1 (opt-in): the recurrent tail of batch k (BiLSTM + heads: 0.37 ms of latency-bound kernels
   // on 148 of 256 CUs) runs on stream_p, next to conv1_1 of batch k + 1 (HBM-write-bound) instead of in front of it. Measured, round 3,

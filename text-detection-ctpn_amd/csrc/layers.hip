@@ -4,9 +4,9 @@
 //                  conv_first_kernel        fp32 mode: direct VALU conv, uint8 or float image in, bordered NHWC out
 //                  conv_first_mfma_kernel   split precision, and the float-blob feed of the 16-bit modes: split-bf16 operands on the MFMAs
 //                  image_to_q_kernel (+ conv_first_p_kernel)   uint8 feed of the 16-bit modes: bytes -> q-image (common.h); conv1_1 itself is
-//                                           computed inside conv1_2's window stage (conv3x3_impl.h) and stored only for keep_acts
+//                                           computed inside conv1_2's window stage (conv3x3_wr.h) and stored only for keep_acts
 //   pack       : TF variable layout -> [out][k] rows used by the conv / GEMM kernels, conv1_1's MFMA fragments (one-time, at weight load).
-//   (the 2x2 max-pools are fused into the conv epilogues, conv3x3_impl.h)
+//   (the 2x2 max-pools are fused into the conv epilogues, conv3x3_*.h)
 #include <cstring>
 #include <type_traits>
 

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void lstm_pre_pack_kernel(const uint16_t* __re
   *(uint4*)(dst + (size_t)idx * 8) = *(const uint4*)(src + (size_t)(32 * T + c) * 512 + 16 * q + 8 * h);
 }
 
-// m0 is on the clobber list on purpose (conv3x3_impl.h, c3_glds16_saddr, says why and what guards it): the one -Winline-asm diagnostic
+// m0 is on the clobber list on purpose (conv3x3_base.h, c3_glds16_saddr, says why and what guards it): the one -Winline-asm diagnostic
 // of this file is silenced HERE and nowhere else, so that the build can treat every other warning as an error
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"

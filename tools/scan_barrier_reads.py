@@ -4,7 +4,8 @@
 The conv kernels recycle LDS buffers with LDS-DMA issued right behind a raw s_barrier; a ds_read issued in front of the barrier whose
 s_waitcnt lgkmcnt hipcc has sunk BELOW it is then ordered against that DMA by latency only (profiles/r06_barrier_war.txt: it lost under
 memory-system load from another stream). This script compiles the named .hip files to gfx950 assembly and reports, per kernel, the barriers
-that have ds_read instructions between the last `s_waitcnt lgkmcnt(0)` (or the previous barrier / a label) and the barrier.
+that have ds_read instructions between the last `s_waitcnt lgkmcnt(0)` (or the previous barrier / a label) and the barrier. The conv units
+are compiled by the Makefile's `asm` target, i.e. with the flags their objects get.
 
     python tools/scan_barrier_reads.py [files ...]        (default: every csrc/*.hip that issues LDS-DMA)
 Exit code 1 if a kernel on the list MUST_BE_CLEAN has such a barrier.
@@ -17,7 +18,6 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "text-detection-ctpn_amd", "csrc")
-FLAGS = {"conv3x3": ["-fno-honor-nans", "-mno-amdgpu-ieee"]}
 MUST_BE_CLEAN = ("conv3x3_p_kernel", "conv3x3_kernel")
 
 
@@ -57,12 +57,14 @@ def main():
     files = sys.argv[1:] or [f for f in sorted(os.listdir(CSRC)) if f.endswith(".hip") and (f.startswith("conv3x3_") or "global_load_lds" in open(os.path.join(CSRC, f)).read())]
     rc = 0
     for f in files:
-        src = os.path.join(CSRC, os.path.basename(f))
-        extra = [x for key, fl in FLAGS.items() if os.path.basename(f).startswith(key) for x in fl]
+        unit = os.path.splitext(os.path.basename(f))[0]
         with tempfile.TemporaryDirectory() as td:
-            o = os.path.join(td, "a.s")
-            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-inline-asm", "-S", "--cuda-device-only", "-o", o, src] + extra,
-                           check=True, stderr=subprocess.DEVNULL)
+            o = os.path.join(td, unit + ".s")
+            if unit.startswith("conv3x3"):
+                subprocess.run(["make", "-C", CSRC, "asm", "ASMDIR=" + td, "ASM_UNITS=" + unit], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            else:
+                subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-inline-asm", "-S", "--cuda-device-only", "-o", o,
+                                os.path.join(CSRC, unit + ".hip")], check=True, stderr=subprocess.DEVNULL)
             res = scan(open(o).read())
         for k, (nb, bad) in res.items():
             name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip()

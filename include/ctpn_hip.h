@@ -397,6 +397,36 @@ int    ctpn_encode_jpeg_batch(ctpn_ctx* ctx, const uint8_t* images, int images_o
 int    ctpn_write_annotated_files(ctpn_ctx* ctx, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity,
                                   const int* line_counts, double scale, const char* const* paths, int quality);
 
+/* ---- Rectified crops of the detected text lines, cut out on the device: one image of fixed height per line, what a recogniser behind the
+ * detector reads. Not part of the reference (its demo stops at the outlines); additive to ABI 10. The batch's pixels are in HBM already
+ * (ctpn_decode_jpeg_batch) and stay there: only the crops cross to the host, if at all. The rate of the kernel is unmeasured.
+ * A line is a record [x0,y0,x1,y1,x2,y2,x3,y3,score] as ctpn_text_lines / ctpn_detect_collect return it, in the coordinates of the image
+ * that was fed: P0 top-left, P1 top-right, P2 bottom-left, P3 bottom-right (the order ctpn_draw_boxes connects them).
+ *   width   top = |P1-P0|, bottom = |P3-P2|, left = |P2-P0|, right = |P3-P1| (sqrt(dx*dx + dy*dy), double, no contraction), wlen = (top +
+ *           bottom) / 2, hlen = max((left + right) / 2, 1); Wc = nearbyint(crop_h * wlen / hlen) (half to even) clamped to [1, max_w]: a
+ *           longer line is squeezed to max_w, not cut
+ *   pixel   output pixel (u, v), 0 <= u < Wc, 0 <= v < crop_h: s = (u + 0.5) / Wc, t = (v + 0.5) / crop_h, tx = x0 + s*(x1-x0), bx = x2 +
+ *           s*(x3-x2), X = tx + t*(bx-tx) - 0.5 (Y likewise), in double in this order; then ctpn_resize's uint8 arithmetic at (X, Y): float
+ *           position, 11-bit weights, the same integer formula -- with the image's border replicated on BOTH axes, so a line that hangs
+ *           over the border reads border pixels (an affine box whose size equals its crop's is an exact copy)
+ *   layout  image 0's lines, then image 1's, ...: total x crop_h x max_w x 3 BGR uint8; columns >= Wc hold pad_value. EVERY line gets a
+ *           crop (ctpn_draw_boxes skips thin ones; filtering is the caller's business)
+ *   ctpn_line_crop_width   Wc of one record. Pure: no ctx, no device.
+ *   ctpn_crop_lines        images: n x h x w x 3 BGR uint8 in HBM (images_on_device: a live batch of ctpn_decode_jpeg_batch -- its decode
+ *                          is waited for in the queue --, or any device buffer whose contents are complete) or on the host (copied into a
+ *                          ctx-owned buffer). recs / line_capacity / line_counts as in ctpn_write_annotated_files. crops_out: capacity_bytes
+ *                          bytes on the host, or (crops_on_device) in HBM, 4-byte aligned; widths_out (nullable): total ints. *total_out
+ *                          is always written. crops_out == NULL with capacity_bytes == 0 SIZES the call: widths and total, no launch.
+ *                          Runs in the ctx's copy queue and returns when crops_out is complete (host output: after the copy back; device
+ *                          output: after the kernel). CTPN_ERR_CAPACITY: capacity_bytes < total * crop_h * max_w * 3; CTPN_ERR_STATE: a
+ *                          post-processing-only ctx; CTPN_ERR_ARG: crop_h outside 1 .. 256, max_w < 4, not a multiple of 4 (a thread
+ *                          stores four pixels as three dwords) or > 65535, pad_value outside 0 .. 255, a coordinate that is not finite.
+ *                          No lines at all is CTPN_OK. The buffers grow to the largest call seen and are then reused. */
+int    ctpn_line_crop_width(const double* rec9, int crop_h, int max_w, int* width_out);
+int    ctpn_crop_lines(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
+                       const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device,
+                       size_t capacity_bytes, int* widths_out, int* total_out);
+
 /* ---- cv2.imread for PNG files (reference ctpn/demo.py:59; data/demo holds .jpg and .png). HOST ONLY, by the nature of the format: one
  * DEFLATE stream (zlib's inflate, the library libpng itself sits on) and row filters that chain from row to row -- nothing a GPU is for. One
  * file per host thread, straight into the caller's batch buffer, which ctpn_detect_submit / ctpn_forward take as host images (one

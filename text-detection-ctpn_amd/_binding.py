@@ -113,6 +113,9 @@ def _declare(lib):
         "ctpn_encode_jpeg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
                                              C.POINTER(C.c_size_t)]),
         "ctpn_write_annotated_files": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_double, C.POINTER(C.c_char_p), C.c_int]),
+        "ctpn_line_crop_width": (C.c_int, [f64p, C.c_int, C.c_int, i32p]),
+        "ctpn_crop_lines": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_size_t,
+                                      i32p, i32p]),
         "ctpn_debug_png_backend": (C.c_int, [C.c_int]),
         "ctpn_png_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_png_decode": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t]),
@@ -353,6 +356,36 @@ def jpeg_entropy_encode(coef, layout8, qt):
     out = np.empty((max(int(n.value), 1),), np.uint8)
     _check(lib.ctpn_jpeg_entropy_encode(_ptr(coef, C.c_int16), _ptr(l8, C.c_int), _ptr(qt, C.c_uint16), _ptr(out, C.c_uint8), out.size, C.byref(n)))
     return out[: n.value].tobytes()
+
+
+def line_crop_width(rec, crop_h=32, max_w=512):
+    """Width of the crop ctpn_crop_lines cuts for one text-line record at height crop_h (ctpn_line_crop_width; needs no device)."""
+    r = np.ascontiguousarray(np.asarray(rec, np.float64).reshape(-1)[:9])
+    if r.size < 8:
+        raise ValueError("line_crop_width wants a record of 8 coordinates (+ score)")
+    r = np.concatenate([r, np.zeros(9 - r.size)]) if r.size < 9 else r
+    out = C.c_int(0)
+    _check(load_library().ctpn_line_crop_width(_ptr(r, C.c_double), int(crop_h), int(max_w), C.byref(out)))
+    return out.value
+
+
+def _pack_lines(recs, line_counts, n):
+    """recs: one (M_i, 9) array per image (line_counts None), or an (n, capacity, 9) array with line_counts -> packed array, counts"""
+    if line_counts is None:
+        recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 9) for r in recs]
+        if len(recs) != n:
+            raise ValueError("one array of records per image")
+        packed = np.zeros((n, max([r.shape[0] for r in recs] + [1]), 9), np.float64)
+        counts = np.zeros((n,), np.int32)
+        for i, r in enumerate(recs):
+            packed[i, : r.shape[0]] = r
+            counts[i] = r.shape[0]
+        return packed, counts
+    packed = np.ascontiguousarray(recs, dtype=np.float64)
+    counts = np.ascontiguousarray(line_counts, dtype=np.int32).reshape(-1)
+    if packed.ndim != 3 or packed.shape[0] != n or packed.shape[2] != 9 or counts.shape[0] != n:
+        raise ValueError("recs with line_counts wants (n, capacity, 9) and n counts")
+    return packed, counts
 
 
 def text_lines(boxes, scores, size, mode="H", device_id=0, capacity=4096):
@@ -728,6 +761,39 @@ class Context:
         keep, arr = _path_array(list(paths))
         _check(self._lib.ctpn_write_annotated_files(self._h, C.c_void_p(int(device_ptr)), n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
                                                     float(scale), arr, int(quality)))
+
+    def crop_lines(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None,
+                   out_device_ptr=None, out_capacity=0):
+        """One rectified crop of height crop_h per text line, cut out on the device (ctpn_crop_lines). images: (n, h, w, 3) uint8 on the host,
+        or device_ptr + shape = (n, h, w) -- a live batch of decode_jpeg_batch is cropped where it lies, without a fetch. recs: one (M_i, 9)
+        array per image as detect / detect_collect return them, or an (n, capacity, 9) array with line_counts. -> (crops, widths): crops
+        (total, crop_h, max_w, 3) BGR uint8, lines in image order, columns >= widths[k] of crop k filled with pad_value (a longer line is
+        squeezed to max_w). With out_device_ptr (4-byte aligned, out_capacity bytes) the crops stay in device memory and crops is None."""
+        if device_ptr is None:
+            images = np.ascontiguousarray(images, dtype=np.uint8)
+            if images.ndim == 3:
+                images = images[None]
+            if images.ndim != 4 or images.shape[3] != 3:
+                raise ValueError("crop_lines wants (n,h,w,3) uint8")
+            shape, src, on_dev = images.shape, images.ctypes.data_as(C.c_void_p), 0
+        else:
+            src, on_dev = C.c_void_p(int(device_ptr)), 1
+        n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+        packed, counts = _pack_lines(recs, line_counts, n)
+        widths = np.zeros((max(int(counts.sum()), 1),), np.int32)
+        total = C.c_int(0)
+
+        def call(out, out_on_dev, capacity):
+            _check(self._lib.ctpn_crop_lines(self._h, src, on_dev, n, h, w, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h),
+                                             int(max_w), int(pad_value), out, out_on_dev, capacity, _ptr(widths, C.c_int), C.byref(total)))
+        if out_device_ptr is not None:
+            call(C.c_void_p(int(out_device_ptr)), 1, int(out_capacity))
+            return None, widths[: total.value].copy()
+        call(None, 0, 0)                                   # sizes the call: the widths and the total, on the host
+        crops = np.empty((total.value, int(crop_h), int(max_w), 3), np.uint8)
+        if total.value:
+            call(crops.ctypes.data_as(C.c_void_p), 0, crops.size)
+        return crops, widths[: total.value].copy()
 
     def detect_submit(self, images=None, slot=0, scales=None, device_ptr=None, shape=None):
         """Asynchronous detect, part 1 (ctpn_detect_submit). Returns immediately."""

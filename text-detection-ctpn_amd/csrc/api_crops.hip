@@ -1,0 +1,109 @@
+// C ABI of libctpn_hip.so, crop unit: the detected text lines of a batch cut out of its images ON THE DEVICE, one rectified image of fixed
+// height per line -- what a recogniser behind the detector reads (kernel and descriptor: crop.hip, arithmetic: crop_pixel.h). An output
+// stage in the ctx's copy queue like the annotated writer (api_output.hip): behind the decode that produced the batch, in front of the next.
+#include <climits>
+#include <cmath>
+
+#include "ctx.h"
+
+namespace ctpn {
+
+static int crop_check_geometry(const char* who, int crop_h, int max_w) {
+  if (crop_h < 1 || crop_h > 256) return fail(CTPN_ERR_ARG, std::string(who) + ": crop_h must be 1 .. 256");
+  if (max_w < 4 || (max_w & 3) || max_w > 65535) return fail(CTPN_ERR_ARG, std::string(who) + ": max_w must be a multiple of 4 in 4 .. 65535");
+  return CTPN_OK;
+}
+
+static bool crop_finite(const double* rec9) {
+  for (int k = 0; k < 8; ++k) if (!std::isfinite(rec9[k])) return false;
+  return true;
+}
+
+static int crop_reserve(ctpn_ctx* c, size_t desc_bytes) {
+  auto& K = c->crop;
+  if (!K.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&K.ev_done, hipEventDisableTiming));
+  if (desc_bytes > K.desc_host_bytes) {
+    if (K.desc_host) CTPN_HIP_TRY(hipHostFree(K.desc_host));
+    K.desc_host = nullptr; K.desc_host_bytes = 0;
+    CTPN_HIP_TRY(hipHostMalloc(&K.desc_host, desc_bytes));
+    K.desc_host_bytes = desc_bytes;
+  }
+  return grow_dev(&K.desc_dev, K.desc_bytes, desc_bytes);
+}
+
+}  // namespace ctpn
+
+extern "C" {
+
+int ctpn_line_crop_width(const double* rec9, int crop_h, int max_w, int* width_out) {
+  if (!rec9 || !width_out) return fail(CTPN_ERR_ARG, "ctpn_line_crop_width: null pointer");
+  if (int rc = crop_check_geometry("ctpn_line_crop_width", crop_h, max_w)) return rc;
+  if (!crop_finite(rec9)) return fail(CTPN_ERR_ARG, "ctpn_line_crop_width: a coordinate is not finite");
+  *width_out = crop_line_width(rec9, crop_h, max_w);
+  return CTPN_OK;
+}
+
+int ctpn_crop_lines(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
+                    const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device, size_t capacity_bytes,
+                    int* widths_out, int* total_out) {
+  if (total_out) *total_out = 0;
+  if (!c || !line_counts || !total_out) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: null pointer");
+  if (n <= 0 || h <= 0 || w <= 0 || line_capacity < 0) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: empty batch / bad size");
+  if (int rc = crop_check_geometry("ctpn_crop_lines", crop_h, max_w)) return rc;
+  if (pad_value < 0 || pad_value > 255) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: pad_value must be 0 .. 255");
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (line_counts[i] < 0 || line_counts[i] > line_capacity || (line_counts[i] > 0 && !recs)) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: line count out of range");
+    total += line_counts[i];
+  }
+  if (total > INT_MAX) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: too many lines");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_crop_lines: post-processing-only ctx");
+  // pass 1, host only: every line's width (what the sizing call is for)
+  const size_t line_bytes = (size_t)crop_h * max_w * 3;
+  std::vector<int> widths((size_t)total);
+  for (int i = 0, k = 0; i < n; ++i)
+    for (int j = 0; j < line_counts[i]; ++j, ++k) {
+      const double* r = recs + ((size_t)i * line_capacity + j) * 9;
+      if (!crop_finite(r)) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: image " + std::to_string(i) + ", line " + std::to_string(j) + ": a coordinate is not finite");
+      widths[k] = crop_line_width(r, crop_h, max_w);
+      if (widths_out) widths_out[k] = widths[k];
+    }
+  *total_out = (int)total;
+  if (!crops_out && capacity_bytes == 0) return CTPN_OK;      // the sizing call
+  if (total == 0) return CTPN_OK;
+  const size_t need = (size_t)total * line_bytes;
+  if (capacity_bytes < need) return fail(CTPN_ERR_CAPACITY, "ctpn_crop_lines: the output holds " + std::to_string(capacity_bytes) + " bytes, the crops need " + std::to_string(need));
+  if (!crops_out || !images) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: null pointer");
+  if (crops_on_device && ((uintptr_t)crops_out & 3)) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: a device output must be 4-byte aligned");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  auto& K = c->crop;
+  hipStream_t qs = c->stream_c;
+  int rc;
+  if ((rc = crop_reserve(c, (size_t)total * CROP_DESC_BYTES))) return rc;
+  for (int i = 0, k = 0; i < n; ++i)
+    for (int j = 0; j < line_counts[i]; ++j, ++k)
+      crop_fill_desc(recs + ((size_t)i * line_capacity + j) * 9, i, widths[k], (size_t)k * line_bytes, (char*)K.desc_host + (size_t)k * CROP_DESC_BYTES);
+  CTPN_HIP_TRY(hipMemcpyAsync(K.desc_dev, K.desc_host, (size_t)total * CROP_DESC_BYTES, hipMemcpyHostToDevice, qs));
+  const uint8_t* px = images;
+  if (!images_on_device) {
+    const size_t bytes = (size_t)n * h * w * 3;
+    if ((rc = grow_dev((void**)&K.img_dev, K.img_bytes, bytes))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(K.img_dev, images, bytes, hipMemcpyHostToDevice, qs));
+    px = K.img_dev;
+  } else {
+    // a live batch of ctpn_decode_jpeg_batch was produced in this queue; it is only read here (a forward may read it at the same time)
+    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
+  }
+  uint8_t* out = crops_out;
+  if (!crops_on_device) {
+    if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, need))) return rc;
+    out = K.out_dev;
+  }
+  if ((rc = launch_crop_lines(px, K.desc_dev, (int)total, out, h, w, crop_h, max_w, pad_value, qs))) return rc;
+  if (!crops_on_device) CTPN_HIP_TRY(hipMemcpyAsync(crops_out, K.out_dev, need, hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipEventRecord(K.ev_done, qs));
+  CTPN_HIP_TRY(hipEventSynchronize(K.ev_done));
+  return CTPN_OK;
+}
+
+}  // extern "C"

@@ -350,6 +350,9 @@ int ctpn_destroy(ctpn_ctx* c) {
   for (void* p : {(void*)c->enc.img_dev, (void*)c->enc.rs_dev, (void*)c->enc.coef_dev, (void*)c->enc.recs_dev, (void*)c->enc.cnt_dev, c->enc.qtab_dev}) if (p) (void)hipFree(p);
   for (void* p : {(void*)c->enc.coef_host, c->enc.qtab_host}) if (p) (void)hipHostFree(p);
   if (c->enc.ev_done) (void)hipEventDestroy(c->enc.ev_done);
+  for (void* p : {(void*)c->crop.img_dev, (void*)c->crop.out_dev, c->crop.desc_dev}) if (p) (void)hipFree(p);
+  if (c->crop.desc_host) (void)hipHostFree(c->crop.desc_host);
+  if (c->crop.ev_done) (void)hipEventDestroy(c->crop.ev_done);
   if (c->stream_p) (void)hipStreamDestroy(c->stream_p);
   for (auto& r : c->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : c->free_events) (void)hipEventDestroy(e);

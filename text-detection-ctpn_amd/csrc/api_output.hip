@@ -5,16 +5,6 @@
 
 namespace ctpn {
 
-// (both entry points return when their files are coded: nothing reads the old block any more when one grows)
-static int enc_grow_dev(void** p, size_t& have, size_t need) {
-  if (need <= have) return CTPN_OK;
-  if (*p) CTPN_HIP_TRY(hipFree(*p));
-  *p = nullptr; have = 0;
-  CTPN_HIP_TRY(hipMalloc(p, need));
-  have = need;
-  return CTPN_OK;
-}
-
 static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
   auto& E = c->enc;
   if (!E.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&E.ev_done, hipEventDisableTiming));
@@ -23,7 +13,7 @@ static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
     E.coef_host = nullptr;
     size_t have = E.coef_elems * sizeof(int16_t);
     E.coef_elems = 0;
-    int rc = enc_grow_dev((void**)&E.coef_dev, have, coef_elems * sizeof(int16_t));
+    int rc = grow_dev((void**)&E.coef_dev, have, coef_elems * sizeof(int16_t));
     if (rc) return rc;
     CTPN_HIP_TRY(hipHostMalloc((void**)&E.coef_host, coef_elems * sizeof(int16_t)));
     E.coef_elems = coef_elems;
@@ -116,7 +106,7 @@ int ctpn_encode_jpeg_batch(ctpn_ctx* c, const uint8_t* images, int images_on_dev
   int rc;
   if (!images_on_device) {
     const size_t bytes = (size_t)n * h * w * 3;
-    if ((rc = enc_grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
+    if ((rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
     CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyHostToDevice, c->stream_c));
     px = E.img_dev;
   } else {
@@ -147,12 +137,12 @@ int ctpn_write_annotated_files(ctpn_ctx* c, const uint8_t* images_dev, int n, in
   hipStream_t qs = c->stream_c;
   const size_t bytes = (size_t)n * h * w * 3;
   int rc;
-  if ((rc = enc_grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
-  if (f != 1.0 && (rc = enc_grow_dev((void**)&E.rs_dev, E.rs_bytes, (size_t)n * dh * dw * 3 + 256))) return rc;
+  if ((rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
+  if (f != 1.0 && (rc = grow_dev((void**)&E.rs_dev, E.rs_bytes, (size_t)n * dh * dw * 3 + 256))) return rc;
   const size_t rbytes = std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64);
-  if ((rc = enc_grow_dev((void**)&E.recs_dev, E.recs_bytes, rbytes))) return rc;
+  if ((rc = grow_dev((void**)&E.recs_dev, E.recs_bytes, rbytes))) return rc;
   size_t cnt_bytes = E.cnt_n * sizeof(int);
-  if ((rc = enc_grow_dev((void**)&E.cnt_dev, cnt_bytes, (size_t)n * sizeof(int)))) return rc;
+  if ((rc = grow_dev((void**)&E.cnt_dev, cnt_bytes, (size_t)n * sizeof(int)))) return rc;
   E.cnt_n = cnt_bytes / sizeof(int);
   // a live batch of ctpn_decode_jpeg_batch was produced in this queue; its buffer is not drawn on (a forward may still read it): a copy is
   for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images_dev) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));

@@ -290,6 +290,13 @@ int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, 
 int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JpegGeom& g, int n, hipStream_t s);
 int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* counts_dev, int line_capacity, int n, int h, int w, hipStream_t s);
 
+// crop.hip: rectified crops of text lines out of device images (arithmetic: crop_pixel.h). The host fills one descriptor per line
+// (crop_fill_desc: coordinates, image, width, byte offset of its crop_h x max_w x 3 block); the kernel reads the table from device memory
+constexpr size_t CROP_DESC_BYTES = 80;
+int crop_line_width(const double* rec9, int crop_h, int max_w);
+void crop_fill_desc(const double* rec9, int img, int wc, size_t out_off, void* desc);
+int launch_crop_lines(const uint8_t* imgs_dev, const void* descs_dev, int total, uint8_t* out_dev, int h, int w, int crop_h, int max_w, int pad, hipStream_t s);
+
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 }  // namespace ctpn

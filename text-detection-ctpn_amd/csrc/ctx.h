@@ -189,6 +189,15 @@ struct ctpn_ctx {
     void* qtab_dev = nullptr; void* qtab_host = nullptr; int qtab_quality = 0;               // JencQ[2][64] of the quality last used
     hipEvent_t ev_done = nullptr;
   } enc;
+  // ctpn_crop_lines (api_crops.hip): ONE set of buffers, for the reason the writer's set is one (the call returns when its crops are
+  // complete), allocated on first use and grown to the largest call seen
+  struct CropBufs {
+    uint8_t* img_dev = nullptr; size_t img_bytes = 0;          // staged host images
+    uint8_t* out_dev = nullptr; size_t out_bytes = 0;          // the crops of a call whose output goes to the host
+    void* desc_dev = nullptr; size_t desc_bytes = 0;           // one descriptor per line (common.h CROP_DESC_BYTES)
+    void* desc_host = nullptr; size_t desc_host_bytes = 0;     // ... page-locked
+    hipEvent_t ev_done = nullptr;
+  } crop;
   int debug_nms = 0;                 // "debug_nms" (diagnostic, WRONG proposals): parts mask of the one-workgroup proposal NMS, see nms_columns_kernel
   int debug_hog = 0;                 // "debug_hog" (diagnostic, 0 .. 200000; see the launch in enqueue_proposals_impl for the two upper ranges): launch a kernel with the one-workgroup NMS's footprint (1024 threads, 84 KB of LDS, one
                                      // workgroup per image) that spins this many microseconds without memory traffic in front of the proposal NMS. Results are unaffected;
@@ -325,6 +334,17 @@ static inline size_t act_front_pixels(int w) { return (size_t)(w + 2) + 64; }   
 // hf: rows of the feature map (a column holds hf x 10 candidates at most, the kernel's list 1024), 0 for the connector's <= 1024 boxes
 static inline bool nms_multi_wg(const ctpn_ctx* c, int n, int hf) {
   return c->nms_mw_scratch && hf * 10 <= 1024 && ((c->nms_columns == 3 && n <= NMS_MW_CAP_BATCH) || (c->nms_columns == 1 && n <= NMS_MW_MAX_BATCH));
+}
+
+// a ctx-owned device buffer that grows to the largest size asked for (the output stages: api_output.hip, api_crops.hip). Their calls return
+// when their results are complete, so nothing reads the old block any more when one grows
+static inline int grow_dev(void** p, size_t& have, size_t need) {
+  if (need <= have) return CTPN_OK;
+  if (*p) CTPN_HIP_TRY(hipFree(*p));
+  *p = nullptr; have = 0;
+  CTPN_HIP_TRY(hipMalloc(p, need));
+  have = need;
+  return CTPN_OK;
 }
 
 // CTPN_DEBUG_SYNC / CTPN_ROCTX: read once per process (api_ctx.hip)

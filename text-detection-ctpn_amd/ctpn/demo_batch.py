@@ -10,6 +10,9 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
     lib/rpn_msr/proposal_layer_tf.py:51), software-pipelined over the ctx's two slots; the ctx is sized ONCE for the largest
     batch / shape of the run (growing it mid-run would destroy the slot that still holds an uncollected batch).
 
+  * with --crops DIR every detected line is also cut out as a rectified image of fixed height, `<stem>_<k>.jpg`, for a recogniser behind
+    the detector (ctpn_crop_lines: on the device; batches decoded there are cropped where they lie, without fetching them).
+
     python -m ctpn_amd.ctpn.demo_batch --input data/demo --out data/results --batch 32 [--mode O] [--synthetic 0] [--no-images]
 """
 from __future__ import print_function
@@ -149,7 +152,21 @@ def _read(name):
         return f.read()
 
 
-def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host"):
+def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None):
+    """The text lines of one batch as rectified crops of height crop_h (ctpn_crop_lines: cut out on the device, from host images or from
+    a batch that lies there), each written as <stem>_<k>.jpg -- k counts the image's lines as its res file lists them --, trimmed to its
+    width, by the host writer. A line longer than max_w columns at that height is squeezed to max_w. -> number of files"""
+    crops, widths = ctx.crop_lines(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape)
+    k = 0
+    for nm, rr in zip(names, recs):
+        stem = os.path.basename(nm).split('.')[0]
+        for j in range(len(rr)):
+            imutil.imwrite(os.path.join(crops_dir, '{}_{}.jpg'.format(stem, j)), crops[k, :, :widths[k]])
+            k += 1
+    return k
+
+
+def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -191,8 +208,9 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             jobs.append(((h, w), "jpg" if layout[0] > 0 else ("png" if layout == PNG else "host"), f, rs, members[i:i + batch]))
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
-    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_host": 0}
+    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_host": 0, "crops": 0}
     dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
+    crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images
     # PNG batches are decoded ONE JOB AHEAD on a helper thread (the C++ decode threads hang off that call; ctypes releases the GIL), so that
     # batch k + 1 inflates while batch k is submitted and batch k - 1 collected. Three batch buffers per shape in a ring: when batch k + 1
     # starts decoding, batch k sits decoded in its buffer and batch k - 1 may still be on its way to the device. THREE slots whatever the
@@ -236,6 +254,9 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.write_annotated_files(ptr, shape, [results[nm] for nm in members], scale,
                                           [os.path.join(out_dir, os.path.basename(nm)) for nm in members])
             stats["enc_gpu"] += len(members)
+        if slot in crop_src:                           # (a device batch is live until the second-next decode: this is one decode from its own)
+            ptr, shape, imgs = crop_src.pop(slot)
+            stats["crops"] += write_crops(net.ctx, crops_dir, members, [results[nm] for nm in members], crop_h, images=imgs, device_ptr=ptr, shape=shape)
         for nm in members:
             emit(nm)
 
@@ -275,6 +296,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             meta[nm] = (imgs[i] if imgs is not None and write_images else None, f)
         if pending is not None:
             collect(pending)
+        if crops_dir:
+            crop_src[k & 1] = (ptr, shape, None) if kind == "jpg" else (None, None, imgs)
         pending = (k & 1, members)
     if pending is not None:
         collect(pending)
@@ -286,6 +309,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         scores, boxes = test_ctpn(None, net, img)
         results[nm] = TextDetector().detect(boxes, scores[:, np.newaxis], img.shape[:2])
         meta[nm] = (img, scale)
+        if crops_dir:
+            stats["crops"] += write_crops(net.ctx, crops_dir, [nm], [results[nm]], crop_h, images=img[None])
         emit(nm)
     dt = time.time() - t0
     log('Detection of {:d} images in {:d} batches took {:.3f}s, result files included, after a header scan of {:.3f}s ({:.1f} images/s; {:d} decoded on the device, {:d} PNG files by the library, {:d} on the host)'.format(
@@ -293,23 +318,31 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     if write_images:
         log('Annotated images: {:d} drawn, resized and JPEG-coded by the library (device + C++ pool), {:d} by the host writer (Pillow)'.format(
             stats["enc_gpu"], stats["enc_host"]))
+    if crops_dir:
+        log('Text-line crops: {:d} of height {:d} cut out on the device'.format(stats["crops"], crop_h))
     return results
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host"):
+        encode="host", crops_dir=None, crop_h=32):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
-    (ctpn_write_annotated_files); 'host' (default): every image through Pillow, as before."""
+    (ctpn_write_annotated_files); 'host' (default): every image through Pillow, as before.
+    crops_dir (needs decode='gpu'): every detected line also as a rectified crop of height crop_h, <stem>_<k>.jpg in that directory, cut out
+    on the device at collect time (write_crops); None (default): nothing changes."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config()
     if encode not in ("host", "gpu"):
         raise ValueError("encode must be 'host' or 'gpu'")
     if encode == "gpu" and decode != "gpu":
         raise ValueError("encode='gpu' writes the images of device-decoded batches: it needs decode='gpu'")
+    if crops_dir is not None and decode != "gpu":
+        raise ValueError("crops_dir cuts the lines out of the batches of the device path: it needs decode='gpu'")
     if decode == "gpu":
-        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode)
+        if crops_dir is not None:
+            os.makedirs(crops_dir, exist_ok=True)
+        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -449,6 +482,9 @@ def main(argv=None):
     ap.add_argument('--decode', default='host', choices=['host', 'gpu'], help="gpu: JPEG decode + resize_im on the device (ctpn_decode_jpeg_batch)")
     ap.add_argument('--encode', default='host', choices=['host', 'gpu'],
                     help="gpu (with --decode gpu): annotated JPEG images drawn, resized and coded by the library (ctpn_write_annotated_files)")
+    ap.add_argument('--crops', default=None, metavar='DIR',
+                    help="(with --decode gpu) also write every detected line as a rectified crop <stem>_<k>.jpg of height --crop-height into DIR (ctpn_crop_lines)")
+    ap.add_argument('--crop-height', type=int, default=32)
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
                          "throughput choice (3.2 x split's rate, outside the 1e-3 / 1 px bar)")
@@ -463,7 +499,7 @@ def main(argv=None):
     if not names:
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
-        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode)
+        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, crops_dir=args.crops, crop_h=args.crop_height)
     net.close()
 
 

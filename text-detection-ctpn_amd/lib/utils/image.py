@@ -95,6 +95,14 @@ def imwrite_jpeg_batch(ctx, paths, images, quality=95, device_ptr=None, shape=No
             f.write(data)
 
 
+def crop_text_lines(ctx, images, recs, line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None):
+    """The detected text lines of a batch as rectified images of height crop_h, one per line, for a recogniser -- cut out on the GPU
+    (ctpn_crop_lines): the quadrilateral of every record mapped bilinearly onto crop_h x width pixels with cv2.resize's INTER_LINEAR uint8
+    arithmetic, border replicated. images: (n, h, w, 3) BGR uint8 on the host, or device_ptr + shape for a batch that is on the device
+    already. -> (crops (total, crop_h, max_w, 3), widths (total,)); crop k is crops[k, :, :widths[k]]."""
+    return ctx.crop_lines(images, recs, line_counts, crop_h=crop_h, max_w=max_w, pad_value=pad_value, device_ptr=device_ptr, shape=shape)
+
+
 def draw_line(img, p0, p1, color, thickness=2):
     """Bresenham-free dense line rasteriser (enough for the annotated demo output)."""
     x0, y0 = p0

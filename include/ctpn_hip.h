@@ -317,6 +317,17 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
  * descending score order (what proposal_layer returns), r <= 1000. Test hook for the connector kernel. */
 int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im_w, float scale, int mode, double* recs_out,
                        int capacity, int* count_out);
+/* The text-line tail of ctpn_detect_submit / ctpn_detect_collect on caller-supplied rois: the SAME enqueue function the submit calls
+ * (lines_prep_kernel, the connector's NMS 0.2 in the form options nms_columns and the batch size select, connect_kernel with option
+ * connect_device = 1) on the ctx's proposal stream, then what the collect does (device records, or connect_lines on the host with
+ * connect_device = 0). Works on any ctx, a ctpn_create_postproc one included. rois: n x 1000 x 5 fp32 [score,x1,y1,x2,y2] per image in
+ * descending score order, roi_counts[n] rows of each are valid (0 .. 1000); n <= max_batch; im_h x im_w is every image's network size
+ * (im_w / 16 columns of the anchor grid), scales[n] (NULL: 1.0) the im_info scale the boxes are divided by. recs_out: n x line_capacity
+ * x 9, line_counts[n] as ctpn_detect_collect returns them (the true count also where CTPN_ERR_CAPACITY is returned). keep_out
+ * (nullable): n x 1000 indices into the image's rois that survived the connector's NMS, keep_counts[n] of them. With option nms_check
+ * = 1 a column-decomposed NMS is followed by the generic kernel on the same boxes and a difference is CTPN_ERR_STATE. Test hook. */
+int ctpn_debug_text_lines(ctpn_ctx* ctx, const float* rois, const int* roi_counts, int n, int im_h, int im_w, const float* scales, int mode,
+                          double* recs_out, int line_capacity, int* line_counts, int* keep_out, int* keep_counts);
 
 /* ---- cv2.imread for JPEG files (reference ctpn/demo.py:59), split where the work splits: marker parsing and Huffman decoding on the host
  * (the ctx's worker pool, one image per thread), dequantisation + inverse DCT + chroma upsampling + YCbCr -> BGR on the device. The pixel

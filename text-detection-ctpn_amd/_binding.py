@@ -66,6 +66,7 @@ def _declare(lib):
         "ctpn_host_threads": (C.c_int, [vp, i32p]),
         "ctpn_proposal_anchors": (C.c_int, [vp, i32p, C.c_int]),
         "ctpn_debug_connect": (C.c_int, [C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, f64p, C.c_int, i32p]),
+        "ctpn_debug_text_lines": (C.c_int, [vp, f32p, i32p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f64p, C.c_int, i32p, i32p, i32p]),
         "ctpn_destroy": (C.c_int, [vp]),
         "ctpn_sync": (C.c_int, [vp]),
         "ctpn_stream": (C.c_int, [vp, C.POINTER(vp)]),
@@ -690,6 +691,35 @@ class Context:
         if want_rois:
             return lines, [rois[i, : rcnt[i]].copy() for i in range(n)]
         return lines
+
+    def debug_text_lines(self, rois, size, scales=None, mode="H", line_capacity=512, roi_counts=None):
+        """The text-line tail of detect on caller-supplied rois (ctpn_debug_text_lines): rois is one (R_i, 5) array [score,x1,y1,x2,y2]
+        per image in descending score order (roi_counts: use only that many rows of each), size = (im_h, im_w) of every image.
+        -> (lines, keeps): per image the (M, 9) records of `mode` and the roi indices the connector's NMS kept. On CTPN_ERR_CAPACITY the
+        raised CtpnError carries the true counts as .line_counts."""
+        n = len(rois)
+        packed = np.zeros((n, 1000, 5), np.float32)
+        rcnt = np.zeros((n,), np.int32)
+        for i, r in enumerate(rois):
+            r = _f32(r).reshape(-1, 5)
+            packed[i, : r.shape[0]] = r
+            rcnt[i] = r.shape[0] if roi_counts is None else int(roi_counts[i])
+        sc = _f32(scales if scales is not None else np.ones((n,), np.float32)).reshape(-1)
+        if sc.shape[0] != n:
+            raise ValueError("one scale per image")
+        recs = np.zeros((n, max(line_capacity, 1), 9), np.float64)
+        lcnt = np.zeros((n,), np.int32)
+        keep = np.zeros((n, 1000), np.int32)
+        kcnt = np.zeros((n,), np.int32)
+        m = MODE_O if str(mode).upper().startswith("O") else MODE_H
+        try:
+            _check(self._lib.ctpn_debug_text_lines(self._h, _ptr(packed, C.c_float), _ptr(rcnt, C.c_int), int(n), int(size[0]), int(size[1]),
+                                                   _ptr(sc, C.c_float), m, _ptr(recs, C.c_double), int(line_capacity), _ptr(lcnt, C.c_int),
+                                                   _ptr(keep, C.c_int), _ptr(kcnt, C.c_int)))
+        except CtpnError as e:
+            e.line_counts = lcnt.copy()
+            raise
+        return [recs[i, : lcnt[i]].copy() for i in range(n)], [keep[i, : kcnt[i]].copy() for i in range(n)]
 
     def decode_jpeg_batch(self, files, h=None, w=None, fx=1.0, fy=1.0):
         """resize_im(cv2.imread(f)) of n JPEG files of one size on the device (ctpn_decode_jpeg_batch): Huffman decoding on the ctx's host

@@ -1,8 +1,41 @@
 // C ABI of libctpn_hip.so, detect unit: forward + proposal layer + connector front end as one asynchronous submit / collect pair, the
-// synchronous ctpn_detect on top of it, the host connector's entry point and the device connector's test hook.
+// synchronous ctpn_detect on top of it, the host connector's entry point and the test hooks of the device connector and of the whole text-line tail.
 #include "ctx.h"
 
 namespace ctpn {
+
+// The text-line tail of a batch whose rois, counts and im_info are on the device (c->rois, c->keep_counts, c->im_info_dev; sl.im_info holds the
+// host copy of im_info): TextDetector.detect's front end -- score > 0.7 prefix, boxes / scale, NMS 0.2 (detectors.py:21-30) -- and, with option
+// connect_device, the connector, in stream order on p. detect_submit_body and the test hook ctpn_debug_text_lines both call it.
+// nms_form (nullable): 0 = the generic NMS kernel ran, 1 = the one-workgroup column form, 2 = the multi-workgroup column form.
+static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hipStream_t p, int* nms_form = nullptr) {
+  const int post = c->post_max;
+  int rc;
+  {
+    Timed t(c, CTPN_KIND_NMS, (double)n * post * 24.0, p);
+    if ((rc = launch_lines_prep(c->rois, c->keep_counts, c->im_info_dev, post, 0.7f, c->tl_boxes, c->tl_scores, c->tl_counts, n, p))) return rc;
+    float max_scale = 0.f;
+    for (int i = 0; i < n; ++i) max_scale = sl.im_info[3 * i + 2] > max_scale ? sl.im_info[3 * i + 2] : max_scale;
+    if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, 0.2f, max_scale)) {
+      const bool mw = nms_multi_wg(c, n, 0);
+      if (nms_form) *nms_form = mw ? 2 : 1;
+      if ((rc = launch_nms_columns(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
+                                   c->tl_spill, n, lvl(w, 4), p, nullptr, nullptr, c->im_info_dev, mw ? c->nms_mw_scratch : nullptr))) return rc;
+    } else {
+      if (nms_form) *nms_form = 0;
+      if ((rc = launch_nms(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
+                           c->tl_spill, n, p))) return rc;
+    }
+  }
+  if (c->connect_device) {
+    // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect)
+    if ((rc = launch_connect(c->tl_boxes, c->tl_scores, c->tl_keep, c->tl_keep_counts, post, c->im_info_dev, c->conn_recs, c->conn_counts,
+                             c->conn_scratch, CONN_CAP, n, p))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs, c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt, c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
+  }
+  return CTPN_OK;
+}
 
 // lone: a synchronous ctpn_detect with nothing else in flight on this ctx -- the proposal layer and the connector front end then follow the
 // forward on ITS stream instead of hopping to the proposal stream (an event record + a cross-queue wait: ~12 us of a lone image's millisecond;
@@ -32,25 +65,7 @@ static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_
   rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, 12000, post, 0.7f, 8.0f, p, sl.ev_decoded);
   if (rc) return rc;
   c->ev_last_decoded = sl.ev_decoded;
-  // TextDetector.detect front end on device: score > 0.7 prefix, boxes / scale, NMS 0.2 (detectors.py:21-30)
-  {
-    Timed t(c, CTPN_KIND_NMS, (double)n * post * 24.0, p);
-    if ((rc = launch_lines_prep(c->rois, c->keep_counts, c->im_info_dev, post, 0.7f, c->tl_boxes, c->tl_scores, c->tl_counts, n, p))) return rc;
-    float max_scale = 0.f;
-    for (int i = 0; i < n; ++i) max_scale = sl.im_info[3 * i + 2] > max_scale ? sl.im_info[3 * i + 2] : max_scale;
-    if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, 0.2f, max_scale)) {
-      if ((rc = launch_nms_columns(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
-                                   c->tl_spill, n, lvl(w, 4), p, nullptr, nullptr, c->im_info_dev, nms_multi_wg(c, n, 0) ? c->nms_mw_scratch : nullptr))) return rc;
-    } else if ((rc = launch_nms(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
-                                c->tl_spill, n, p))) return rc;
-  }
-  if (c->connect_device) {
-    // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect)
-    if ((rc = launch_connect(c->tl_boxes, c->tl_scores, c->tl_keep, c->tl_keep_counts, post, c->im_info_dev, c->conn_recs, c->conn_counts,
-                             c->conn_scratch, CONN_CAP, n, p))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs, c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
-    CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt, c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
-  }
+  if ((rc = enqueue_text_lines(c, sl, n, w, p))) return rc;
   CTPN_HIP_TRY(hipMemcpyAsync(sl.pack, c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));      // tl_* (host connector), rois, counts: one copy
   CTPN_HIP_TRY(hipEventRecord(sl.ev_done, p));
   c->ev_last_done = sl.ev_done;
@@ -61,6 +76,83 @@ static int detect_submit_impl(ctpn_ctx* c, const uint8_t* images, int images_on_
   const int rc = detect_submit_body(c, images, images_on_device, n, h, w, scales, slot, lone);
   if (rc != CTPN_OK && c) c->nms_mw_dirty = true;        // an error anywhere in a submit (the connector NMS's launch included): see common.h, NMS_MW_OVERFLOW_OFF
   return rc;
+}
+
+// the lines of a batch whose tail has finished, from what it left in the slot's page-locked buffers: the device connector's records (option
+// connect_device), or connect_lines on the host workers over the connector NMS's survivors. ctpn_detect_collect and ctpn_debug_text_lines.
+static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int h, int w, int mode, double* recs_out, int line_capacity, int* line_counts) {
+  const int post = c->post_max;
+  if (c->connect_device) {
+    for (int i = 0; i < n; ++i) {
+      if (sl.ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
+      const int cnt = sl.ccnt[3 * i + (mode == CTPN_MODE_O ? 1 : 0)];
+      line_counts[i] = cnt;
+      if (cnt > line_capacity || cnt > CONN_CAP) return fail(CTPN_ERR_CAPACITY, "ctpn_detect: more lines than line_capacity");
+      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * CONN_CAP * 9, (size_t)cnt * 9 * sizeof(double));
+    }
+    return CTPN_OK;
+  }
+  std::vector<int> status(n, 0);
+  std::vector<std::string> errs(n);
+  auto work = [&](int i) {
+    const int nk = sl.kcnt[i];
+    std::vector<float> kb((size_t)nk * 4), ks(nk);
+    for (int j = 0; j < nk; ++j) {
+      const int src = sl.keep[(size_t)i * post + j];
+      std::memcpy(&kb[4 * j], &sl.tlb[((size_t)i * post + src) * 4], 4 * sizeof(float));
+      ks[j] = sl.tls[(size_t)i * post + src];
+    }
+    std::vector<double> recs;
+    int st = connect_lines(kb.data(), ks.data(), nk, h, w, mode, recs);
+    if (st) { status[i] = st; errs[i] = ctpn_last_error(); return; }
+    const int cnt = (int)(recs.size() / 9);
+    line_counts[i] = cnt;
+    if (cnt > line_capacity) { status[i] = CTPN_ERR_CAPACITY; errs[i] = "ctpn_detect: more lines than line_capacity"; return; }
+    if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, recs.data(), recs.size() * sizeof(double));
+  };
+  c->pool->run(n, work);      // persistent workers of the ctx (ctpn_host_thread_budget), one image per task
+  for (int i = 0; i < n; ++i) if (status[i]) return fail(status[i], errs[i]);
+  return CTPN_OK;
+}
+
+// The tail of ctpn_detect_submit + ctpn_detect_collect on caller-supplied rois: enqueue_text_lines and lines_of_slot, the functions those two
+// call, on the proposal stream and slot 0's page-locked buffers. Test hook (tests/test_gpu_text_line_tail.py).
+static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_counts, int n, int im_h, int im_w, const float* scales, int mode,
+                                 double* recs_out, int line_capacity, int* line_counts, int* keep_out, int* keep_counts) {
+  if (!rois || !roi_counts || !recs_out || !line_counts) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: null pointer");
+  if (keep_out && !keep_counts) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: keep_out without keep_counts");
+  if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: mode must be H(0) or O(1)");
+  if (n <= 0 || n > c->max_batch) return fail(CTPN_ERR_CAPACITY, "ctpn_debug_text_lines: 1 <= n <= max_batch images");
+  if (im_h < 1 || im_w < 16 || line_capacity < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: im_h >= 1, im_w >= 16, line_capacity >= 0 required");
+  const int post = c->post_max;
+  for (int i = 0; i < n; ++i)
+    if (roi_counts[i] < 0 || roi_counts[i] > post) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: 0 <= roi_counts[i] <= 1000 rows of [score,x1,y1,x2,y2]");
+  if (c->slot[0].busy || c->slot[1].busy) return fail(CTPN_ERR_STATE, "ctpn_debug_text_lines: a submitted batch has not been collected");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));      // the proposal entry points use these buffers on the forward's stream
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  ctpn_ctx::Slot& sl = c->slot[0];
+  hipStream_t p = c->stream_p;
+  for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)im_h; sl.im_info[3 * i + 1] = (float)im_w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
+  if (c->nms_mw_scratch && c->nms_mw_dirty) {       // as enqueue_proposals does in front of a submit's tail
+    CTPN_HIP_TRY(hipMemsetAsync(c->nms_mw_scratch, 0, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, p));
+    c->nms_mw_dirty = false;
+  }
+  CTPN_HIP_TRY(hipMemcpyAsync(c->im_info_dev, sl.im_info, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, p));
+  CTPN_HIP_TRY(hipMemcpyAsync(c->rois, rois, (size_t)n * post * 5 * sizeof(float), hipMemcpyHostToDevice, p));
+  CTPN_HIP_TRY(hipMemcpyAsync(c->keep_counts, roi_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, p));
+  int form = 0, rc;
+  if ((rc = enqueue_text_lines(c, sl, n, im_w, p, &form))) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(sl.pack, c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));
+  CTPN_HIP_TRY(hipStreamSynchronize(p));
+  for (int i = 0; i < n; ++i)
+    if (sl.kcnt[i] < 0 || sl.kcnt[i] > post) return fail(CTPN_ERR_HIP, "ctpn_debug_text_lines: device returned an impossible keep count");
+  if (keep_counts) std::memcpy(keep_counts, sl.kcnt, (size_t)n * sizeof(int));
+  if (keep_out) std::memcpy(keep_out, sl.keep, (size_t)n * post * sizeof(int));
+  // option nms_check, as in the proposal layer: the generic kernel on the same prepared boxes must keep the same rows
+  if (c->nms_check && form != 0 &&
+      (rc = nms_check_generic(c, c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, sl.keep, post, sl.kcnt, n, form == 2, p, "connector NMS"))) return rc;
+  return lines_of_slot(c, sl, n, im_h, im_w, mode, recs_out, line_capacity, line_counts);
 }
 
 }  // namespace ctpn
@@ -99,37 +191,7 @@ int ctpn_detect_collect(ctpn_ctx* c, int slot, int mode, double* recs_out, int l
   const int n = sl.n, h = sl.h, w = sl.w, post = c->post_max;
   if (rois_out) std::memcpy(rois_out, sl.rois, (size_t)n * post * 5 * sizeof(float));
   if (roi_counts) std::memcpy(roi_counts, sl.rcnt, (size_t)n * sizeof(int));
-  if (c->connect_device) {
-    for (int i = 0; i < n; ++i) {
-      if (sl.ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
-      const int cnt = sl.ccnt[3 * i + (mode == CTPN_MODE_O ? 1 : 0)];
-      line_counts[i] = cnt;
-      if (cnt > line_capacity || cnt > CONN_CAP) return fail(CTPN_ERR_CAPACITY, "ctpn_detect: more lines than line_capacity");
-      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * CONN_CAP * 9, (size_t)cnt * 9 * sizeof(double));
-    }
-    return CTPN_OK;
-  }
-  std::vector<int> status(n, 0);
-  std::vector<std::string> errs(n);
-  auto work = [&](int i) {
-    const int nk = sl.kcnt[i];
-    std::vector<float> kb((size_t)nk * 4), ks(nk);
-    for (int j = 0; j < nk; ++j) {
-      const int src = sl.keep[(size_t)i * post + j];
-      std::memcpy(&kb[4 * j], &sl.tlb[((size_t)i * post + src) * 4], 4 * sizeof(float));
-      ks[j] = sl.tls[(size_t)i * post + src];
-    }
-    std::vector<double> recs;
-    int st = connect_lines(kb.data(), ks.data(), nk, h, w, mode, recs);
-    if (st) { status[i] = st; errs[i] = ctpn_last_error(); return; }
-    const int cnt = (int)(recs.size() / 9);
-    line_counts[i] = cnt;
-    if (cnt > line_capacity) { status[i] = CTPN_ERR_CAPACITY; errs[i] = "ctpn_detect: more lines than line_capacity"; return; }
-    if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, recs.data(), recs.size() * sizeof(double));
-  };
-  c->pool->run(n, work);      // persistent workers of the ctx (ctpn_host_thread_budget), one image per task
-  for (int i = 0; i < n; ++i) if (status[i]) return fail(status[i], errs[i]);
-  return CTPN_OK;
+  return lines_of_slot(c, sl, n, h, w, mode, recs_out, line_capacity, line_counts);
 }
 
 int ctpn_detect(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int mode,
@@ -191,6 +253,20 @@ int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im
   if (cnt) DC_TRY(hipMemcpy(recs_out, buf + o_recs + (size_t)(mode == CTPN_MODE_O ? 1 : 0) * CONN_CAP * 9 * 8, (size_t)cnt * 9 * 8, hipMemcpyDeviceToHost));
 #undef DC_TRY
   return done(CTPN_OK);
+}
+
+int ctpn_debug_text_lines(ctpn_ctx* c, const float* rois, const int* roi_counts, int n, int im_h, int im_w, const float* scales, int mode,
+                          double* recs_out, int line_capacity, int* line_counts, int* keep_out, int* keep_counts) {
+  if (!c) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: null ctx");
+  const int rc = debug_text_lines_body(c, rois, roi_counts, n, im_h, im_w, scales, mode, recs_out, line_capacity, line_counts, keep_out, keep_counts);
+  if (rc != CTPN_OK) {
+    // as detect_submit_impl: nobody vouches for the multi-workgroup NMS's scratch after an error; leave the proposal stream quiet
+    const std::string first = ctpn_last_error();
+    (void)hipStreamSynchronize(c->stream_p);
+    c->nms_mw_dirty = true;
+    return fail(rc, first);
+  }
+  return rc;
 }
 
 }  // extern "C"

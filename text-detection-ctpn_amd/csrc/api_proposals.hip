@@ -3,6 +3,38 @@
 
 namespace ctpn {
 
+// Option nms_check behind a column-decomposed NMS launch on s (the proposal layer's here, the connector's in api_detect.hip): re-run the generic
+// kernel on the same candidates and fail loudly if the keep lists differ. keep1 / cnt1: the column form's lists, on the host, rows of keep_stride;
+// mw: the multi-workgroup form ran; what: the NMS's name in the error text. Synchronises s. The caller marks nms_mw_dirty on an error return.
+int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, const int* counts, int stride, float thresh, int post_topn,
+                      const int* keep1, int keep_stride, const int* cnt1, int n, bool mw, hipStream_t s, const char* what) {
+  std::vector<int> k2((size_t)n * keep_stride), c2(n);
+  int* keep2 = nullptr; int* cnt2 = nullptr; float* spill2 = nullptr;
+  struct Free3 { int*& a; int*& b; float*& c; ~Free3() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } guard{keep2, cnt2, spill2};   // every early return frees
+  CTPN_HIP_TRY(hipMalloc((void**)&keep2, k2.size() * sizeof(int)));
+  CTPN_HIP_TRY(hipMalloc((void**)&cnt2, c2.size() * sizeof(int)));
+  CTPN_HIP_TRY(hipMalloc((void**)&spill2, (size_t)n * keep_stride * 4 * sizeof(float)));
+  int rc = launch_nms(boxes, scores, counts, stride, thresh, post_topn, keep2, keep_stride, cnt2, nullptr, spill2, n, s);
+  if (rc) return rc;
+  CTPN_HIP_TRY(hipStreamSynchronize(s));
+  CTPN_HIP_TRY(hipMemcpy(k2.data(), keep2, k2.size() * sizeof(int), hipMemcpyDeviceToHost));
+  CTPN_HIP_TRY(hipMemcpy(c2.data(), cnt2, c2.size() * sizeof(int), hipMemcpyDeviceToHost));
+  if (mw) {
+    // the multi-workgroup form's sticky overflow words (a column with more candidates than the kernel's list)
+    for (int i = 0; i < n; ++i) {
+      unsigned ov = 0;
+      CTPN_HIP_TRY(hipMemcpy(&ov, c->nms_mw_scratch + (size_t)i * NMS_MW_SCRATCH_BYTES + NMS_MW_OVERFLOW_OFF, 4, hipMemcpyDeviceToHost));
+      if (ov) return fail(CTPN_ERR_STATE, "nms_check: a column held more candidates than the multi-workgroup NMS's list (1024): keep lists are incomplete");
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    bool same = cnt1[i] == c2[i];
+    for (int k = 0; same && k < c2[i]; ++k) same = keep1[(size_t)i * keep_stride + k] == k2[(size_t)i * keep_stride + k];
+    if (!same) return fail(CTPN_ERR_STATE, std::string("nms_check: column-decomposed ") + what + " differs from the generic kernel (boxes off the 16-px anchor grid?)");
+  }
+  return CTPN_OK;
+}
+
 static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
                                   int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s, hipEvent_t ev_decoded) {
   if (!s) s = c->stream;
@@ -58,38 +90,13 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
                                    c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, wf, s, c->sorted_anchor, c->roi_anchor, nullptr,
                                    mw ? c->nms_mw_scratch : nullptr, mw ? c->nms_colid : nullptr, c->nms_prefix ? 4096 : 0, c->debug_nms))) return rc;
       if (c->nms_check) {
-        // option "nms_check" (debug; synchronises the stream): the column decomposition presumes boxes on the 16-px anchor grid (common.h). Re-run the generic
-        // kernel on the same candidates and fail loudly if the keep lists differ.
-        std::vector<int> k1((size_t)n * c->topn_max), c1(n), k2((size_t)n * c->topn_max), c2(n);
-        int* keep2 = nullptr; int* cnt2 = nullptr; float* spill2 = nullptr;
-        struct Free3 { int*& a; int*& b; float*& c; ~Free3() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } guard{keep2, cnt2, spill2};   // every early return frees
+        // option "nms_check" (debug; synchronises the stream): the column decomposition presumes boxes on the 16-px anchor grid (common.h)
+        std::vector<int> k1((size_t)n * c->topn_max), c1(n);
         CTPN_HIP_TRY(hipStreamSynchronize(s));
         CTPN_HIP_TRY(hipMemcpy(k1.data(), c->keep_idx, k1.size() * sizeof(int), hipMemcpyDeviceToHost));
         CTPN_HIP_TRY(hipMemcpy(c1.data(), c->keep_counts, c1.size() * sizeof(int), hipMemcpyDeviceToHost));
-        CTPN_HIP_TRY(hipMalloc((void**)&keep2, k2.size() * sizeof(int)));
-        CTPN_HIP_TRY(hipMalloc((void**)&cnt2, c2.size() * sizeof(int)));
-        CTPN_HIP_TRY(hipMalloc((void**)&spill2, (size_t)n * c->topn_max * 4 * sizeof(float)));
-        rc = launch_nms(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, keep2, c->topn_max, cnt2, nullptr, spill2, n, s);
-        if (rc == CTPN_OK && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(k2.data(), keep2, k2.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-                              hipMemcpy(c2.data(), cnt2, c2.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess))
-          rc = fail(CTPN_ERR_HIP, "nms_check: copy back failed");
-        if (rc) return rc;
-        if (mw) {
-          // the multi-workgroup form's sticky overflow words (a column with more candidates than the kernel's list)
-          for (int i = 0; i < n; ++i) {
-            unsigned ov = 0;
-            CTPN_HIP_TRY(hipMemcpy(&ov, c->nms_mw_scratch + (size_t)i * NMS_MW_SCRATCH_BYTES + NMS_MW_OVERFLOW_OFF, 4, hipMemcpyDeviceToHost));
-            if (ov) {
-              c->nms_mw_dirty = true;
-              return fail(CTPN_ERR_STATE, "nms_check: a column held more candidates than the multi-workgroup NMS's list (1024): keep lists are incomplete");
-            }
-          }
-        }
-        for (int i = 0; i < n; ++i) {
-          bool same = c1[i] == c2[i];
-          for (int k = 0; same && k < c1[i]; ++k) same = k1[(size_t)i * c->topn_max + k] == k2[(size_t)i * c->topn_max + k];
-          if (!same) return fail(CTPN_ERR_STATE, "nms_check: column-decomposed NMS differs from the generic kernel (boxes off the 16-px anchor grid?)");
-        }
+        if ((rc = nms_check_generic(c, c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, k1.data(), c->topn_max,
+                                    c1.data(), n, mw, s, "NMS"))) return rc;
       }
     } else if ((rc = launch_nms(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, c->keep_idx,
                                 c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, s, c->sorted_anchor, c->roi_anchor))) return rc;

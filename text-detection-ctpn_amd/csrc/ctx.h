@@ -381,5 +381,8 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
 int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
                       int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s = nullptr,
                       hipEvent_t ev_decoded = nullptr);
+// option nms_check behind a column-decomposed NMS launch on s (api_proposals.hip): the generic kernel on the same candidates must give keep1 / cnt1
+int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, const int* counts, int stride, float thresh, int post_topn,
+                      const int* keep1, int keep_stride, const int* cnt1, int n, bool mw, hipStream_t s, const char* what);
 
 }  // namespace ctpn

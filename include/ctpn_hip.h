@@ -111,6 +111,37 @@ int         ctpn_set_option(ctpn_ctx* ctx, const char* key, int value);
 int         ctpn_get_option(ctpn_ctx* ctx, const char* key, int* value_out);
 int         ctpn_option_count(void);
 const char* ctpn_option_name(int index);
+/* Parameters of ONE ctx's detection tail (additive in ABI 10): what the reference reads at run time from cfg.TEST.RPN_* (ctpn/text.yml,
+ * lib/fast_rcnn/config.py:175-183) and from TextLineCfg (lib/text_connector/text_connect_cfg.py:4-12), as doubles by the reference's
+ * names. ctpn_detect, ctpn_detect_submit / ctpn_detect_collect and ctpn_debug_text_lines read them -- the proposal layer's arguments,
+ * lines_prep_kernel, the connector's NMS, connect_kernel and the collect's host connector alike; ctpn_proposals and
+ * ctpn_proposals_from_host keep taking their four values as arguments. A fresh ctx holds the defaults, with which every entry point
+ * computes bit for bit what it did while the values were compiled in.
+ *   name                       default  accepted
+ *   RPN_PRE_NMS_TOP_N          12000    integral, 1 .. 12000 (the ctx's buffers are sized for the default)
+ *   RPN_POST_NMS_TOP_N         1000     integral, 1 .. 1000  (likewise; the device connector holds 1024 proposals per image in LDS)
+ *   RPN_NMS_THRESH             0.7      0 .. 1 (below 0.1 the generic NMS kernel runs instead of the column decomposition: same keep lists)
+ *   RPN_MIN_SIZE               8        >= 0
+ *   TEXT_PROPOSALS_MIN_SCORE   0.7      finite
+ *   TEXT_PROPOSALS_NMS_THRESH  0.2      0 .. 1 (below 0.15 the generic NMS kernel runs: same keep lists)
+ *   MAX_HORIZONTAL_GAP         50       integral, 0 .. 4096
+ *   MIN_V_OVERLAPS             0.7      finite
+ *   MIN_SIZE_SIM               0.7      finite
+ *   MIN_RATIO                  0.5      finite
+ *   LINE_MIN_SCORE             0.9      finite
+ *   MIN_LINE_WIDTH             32       finite; TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPOSALS -- the reference only ever uses the product
+ * A value is used in the precision of the reference's comparison: RPN_NMS_THRESH, RPN_MIN_SIZE, TEXT_PROPOSALS_MIN_SCORE,
+ * TEXT_PROPOSALS_NMS_THRESH, MIN_V_OVERLAPS, MIN_SIZE_SIM and the gap are rounded to fp32 ONCE, when set (they must stay finite in fp32:
+ * |value| <= 3e38); MIN_RATIO, LINE_MIN_SCORE and MIN_LINE_WIDTH are compared in fp64 (filter_boxes). No kernel bounds a value more tightly
+ * than the table says. ctpn_set_param follows ctpn_set_option's contract: the ctx drains its streams first, CTPN_ERR_STATE while a submitted
+ * batch is uncollected, CTPN_ERR_ARG for an unknown name, a NaN or a value outside its range. ctpn_get_param returns the value as set.
+ * With RPN_POST_NMS_TOP_N below 1000, rois_out / keep_out of ctpn_detect*, ctpn_debug_text_lines still hold 1000 rows per image (fewer of
+ * them valid). ctpn_param_count / ctpn_param_name enumerate the names; ctpn_param_default needs no ctx and no device. */
+int         ctpn_set_param(ctpn_ctx* ctx, const char* name, double value);
+int         ctpn_get_param(ctpn_ctx* ctx, const char* name, double* value_out);
+int         ctpn_param_count(void);
+const char* ctpn_param_name(int index);
+int         ctpn_param_default(const char* name, double* value_out);
 /* Host worker threads of a ctx (per-image connector work of ctpn_detect_collect, staging copies of pageable images): one
  * persistent pool per ctx, created in ctpn_create. Size = ctpn_host_thread_budget(hardware cores, LOCAL_WORLD_SIZE of the
  * launcher (torchrun), CTPN_HOST_THREADS): `requested` if > 0, else cores / ranks-on-this-node clamped to [1, 32].
@@ -240,10 +271,16 @@ int ctpn_nms(int* keep_out, int* num_out, const float* boxes_host, int boxes_num
  * device_id >= 0 (reference: nms_wrapper.nms -> gpu_nms, detectors.py:29). Host C++ otherwise. */
 int ctpn_text_lines(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode,
                     int device_id, double* recs_out, int capacity, int* count_out);
-/* The connector's constants as compiled in (the reference's TextLineCfg, lib/text_connector/text_connect_cfg.py:4-12, reads them at run time):
+/* The same with a configuration of the caller's (the reference's TextLineCfg, which it reads at run time): cfg8 in the order
+ * ctpn_connector_constants reports, NULL = the defaults (ctpn_text_lines is that case). Ranges and precisions as for ctpn_set_param's
+ * parameters of the same names (cfg8[0] is MIN_LINE_WIDTH); a value outside them is CTPN_ERR_ARG. Stateless: no ctx is read. */
+int ctpn_text_lines_cfg(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode,
+                        int device_id, const double* cfg8, double* recs_out, int capacity, int* count_out);
+/* The connector's DEFAULTS (the reference's TextLineCfg, lib/text_connector/text_connect_cfg.py:4-12):
  * out8 = {TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPOSALS, MIN_RATIO, LINE_MIN_SCORE, MAX_HORIZONTAL_GAP, TEXT_PROPOSALS_MIN_SCORE,
- * TEXT_PROPOSALS_NMS_THRESH, MIN_V_OVERLAPS, MIN_SIZE_SIM}. The Python mirror's TextDetector compares its Config with them and raises if a
- * caller has edited one: an edit that would silently do nothing is worse than an error. Needs no device. */
+ * TEXT_PROPOSALS_NMS_THRESH, MIN_V_OVERLAPS, MIN_SIZE_SIM}, the fp32 ones as their fp32 values. The Python mirror's TextDetector() compares the
+ * module-level Config with them and raises if a caller has edited one (an edit that would silently do nothing is worse than an error);
+ * TextDetector(config=...) is the way to run another configuration. Needs no device. */
 int ctpn_connector_constants(double* out8);
 
 /* ---- result files ---------------------------------------------------------------------------
@@ -259,7 +296,8 @@ int ctpn_draw_boxes(uint8_t* img_bgr, int h, int w, const double* recs, int n_li
  * Replaces the body of ctpn() in ctpn/demo.py:55-68 between imread/resize and draw_boxes for a
  * batch: forward -> proposals -> (boxes / scale) -> text lines. scales: n floats (im_scales[0] of
  * lib/fast_rcnn/test.py:57, 1.0 when the image is already at network resolution).
- * recs_out: n x line_capacity x 9 float64, line_counts: n ints; rois_out/roi_counts may be NULL. */
+ * recs_out: n x line_capacity x 9 float64, line_counts: n ints; rois_out (n x 1000 x 5) / roi_counts may be NULL.
+ * The proposal layer's four values and the connector's thresholds are the ctx's parameters (ctpn_set_param). */
 int ctpn_detect(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w,
                 const float* scales, int mode, double* recs_out, int line_capacity, int* line_counts,
                 float* rois_out, int* roi_counts);
@@ -321,7 +359,7 @@ int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im
  * (lines_prep_kernel, the connector's NMS 0.2 in the form options nms_columns and the batch size select, connect_kernel with option
  * connect_device = 1) on the ctx's proposal stream, then what the collect does (device records, or connect_lines on the host with
  * connect_device = 0). Works on any ctx, a ctpn_create_postproc one included. rois: n x 1000 x 5 fp32 [score,x1,y1,x2,y2] per image in
- * descending score order, roi_counts[n] rows of each are valid (0 .. 1000); n <= max_batch; im_h x im_w is every image's network size
+ * descending score order, roi_counts[n] rows of each are valid (0 .. RPN_POST_NMS_TOP_N); n <= max_batch; im_h x im_w is every image's network size
  * (im_w / 16 columns of the anchor grid), scales[n] (NULL: 1.0) the im_info scale the boxes are divided by. recs_out: n x line_capacity
  * x 9, line_counts[n] as ctpn_detect_collect returns them (the true count also where CTPN_ERR_CAPACITY is returned). keep_out
  * (nullable): n x 1000 indices into the image's rois that survived the connector's NMS, keep_counts[n] of them. With option nms_check

@@ -58,6 +58,11 @@ def _declare(lib):
         "ctpn_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
         "ctpn_option_count": (C.c_int, []),
         "ctpn_option_name": (C.c_char_p, [C.c_int]),
+        "ctpn_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
+        "ctpn_get_param": (C.c_int, [C.c_void_p, C.c_char_p, f64p]),
+        "ctpn_param_count": (C.c_int, []),
+        "ctpn_param_name": (C.c_char_p, [C.c_int]),
+        "ctpn_param_default": (C.c_int, [C.c_char_p, f64p]),
         "ctpn_last_error": (C.c_char_p, []),
         "ctpn_device_count": (C.c_int, []),
         "ctpn_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -92,6 +97,7 @@ def _declare(lib):
         "ctpn_write_result_file": (C.c_int, [C.c_char_p, f64p, C.c_int, C.c_double, i32p]),
         "ctpn_draw_boxes": (C.c_int, [u8p, C.c_int, C.c_int, f64p, C.c_int]),
         "ctpn_text_lines": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p]),
+        "ctpn_text_lines_cfg": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, C.c_int, i32p]),
         "ctpn_connector_constants": (C.c_int, [f64p]),
         "ctpn_detect": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f64p, C.c_int, i32p,
                                   f32p, i32p]),
@@ -174,6 +180,18 @@ def device_count():
 def option_names():
     lib = load_library()
     return [lib.ctpn_option_name(i).decode() for i in range(lib.ctpn_option_count())]
+
+
+def param_names():
+    """Names of a ctx's detection-tail parameters (ctpn_param_name), in ABI order."""
+    lib = load_library()
+    return [lib.ctpn_param_name(i).decode() for i in range(lib.ctpn_param_count())]
+
+
+def param_default(name):
+    v = C.c_double(0.0)
+    _check(load_library().ctpn_param_default(name.encode(), C.byref(v)))
+    return v.value
 
 
 def manifest_from_library():
@@ -389,21 +407,55 @@ def _pack_lines(recs, line_counts, n):
     return packed, counts
 
 
-def text_lines(boxes, scores, size, mode="H", device_id=0, capacity=4096):
-    """B4 seam: TextDetector.detect (reference lib/text_connector/detectors.py:19-35)."""
+def connector_cfg8(config):
+    """config: None, a sequence of 8 values in CONNECTOR_CONSTANT_NAMES' order, a {TextLineCfg name: value} dict (missing names: the defaults;
+    MIN_LINE_WIDTH or TEXT_PROPOSALS_WIDTH / MIN_NUM_PROPOSALS for the width), or any object with TextLineCfg's attributes -> the 8 doubles
+    ctpn_text_lines_cfg takes (None stays None)."""
+    if config is None:
+        return None
+    if isinstance(config, (list, tuple, np.ndarray)):
+        out = np.ascontiguousarray(config, dtype=np.float64).reshape(-1)
+        if out.shape[0] != 8:
+            raise ValueError("a connector configuration holds 8 values")
+        return out
+    get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+    if isinstance(config, dict):
+        known = set(CONNECTOR_PARAM_NAMES) | {"TEXT_PROPOSALS_WIDTH", "MIN_NUM_PROPOSALS", "SCALE", "MAX_SCALE"}
+        unknown = sorted(set(config) - known)
+        if unknown:
+            raise ValueError("unknown connector parameter(s): " + ", ".join(unknown))
+    out = np.array([param_default(n) for n in CONNECTOR_PARAM_NAMES], np.float64)
+    for k, name in enumerate(CONNECTOR_PARAM_NAMES):
+        v = get(name, None)
+        if name == "MIN_LINE_WIDTH" and v is None and (get("TEXT_PROPOSALS_WIDTH", None) is not None or get("MIN_NUM_PROPOSALS", None) is not None):
+            v = float(get("TEXT_PROPOSALS_WIDTH", 16)) * float(get("MIN_NUM_PROPOSALS", 2))
+        if v is not None:
+            out[k] = float(v)
+    return out
+
+
+def text_lines(boxes, scores, size, mode="H", device_id=0, capacity=4096, config=None):
+    """B4 seam: TextDetector.detect (reference lib/text_connector/detectors.py:19-35). config: see connector_cfg8 (None: the defaults)."""
     lib = load_library()
+    cfg8 = connector_cfg8(config)
     b = _f32(boxes).reshape(-1, 4)
     s = _f32(scores).reshape(-1)
     recs = np.zeros((capacity, 9), np.float64)
     cnt = C.c_int(0)
     m = MODE_O if str(mode).upper().startswith("O") else MODE_H
-    _check(lib.ctpn_text_lines(_ptr(b, C.c_float), _ptr(s, C.c_float), int(b.shape[0]), int(size[0]), int(size[1]), m,
-                               int(device_id), _ptr(recs, C.c_double), capacity, C.byref(cnt)))
+    if cfg8 is None:
+        _check(lib.ctpn_text_lines(_ptr(b, C.c_float), _ptr(s, C.c_float), int(b.shape[0]), int(size[0]), int(size[1]), m,
+                                   int(device_id), _ptr(recs, C.c_double), capacity, C.byref(cnt)))
+    else:
+        _check(lib.ctpn_text_lines_cfg(_ptr(b, C.c_float), _ptr(s, C.c_float), int(b.shape[0]), int(size[0]), int(size[1]), m,
+                                       int(device_id), _ptr(cfg8, C.c_double), _ptr(recs, C.c_double), capacity, C.byref(cnt)))
     return recs[: cnt.value].copy()
 
 
 CONNECTOR_CONSTANT_NAMES = ("TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPOSALS", "MIN_RATIO", "LINE_MIN_SCORE", "MAX_HORIZONTAL_GAP", "TEXT_PROPOSALS_MIN_SCORE",
                             "TEXT_PROPOSALS_NMS_THRESH", "MIN_V_OVERLAPS", "MIN_SIZE_SIM")
+# the same eight as ctx parameters (ctpn_set_param), in the same order
+CONNECTOR_PARAM_NAMES = ("MIN_LINE_WIDTH",) + CONNECTOR_CONSTANT_NAMES[1:]
 
 
 def connector_constants():
@@ -535,6 +587,15 @@ class Context:
     def get_option(self, key):
         v = C.c_int(0)
         _check(self._lib.ctpn_get_option(self._h, key.encode(), C.byref(v)))
+        return v.value
+
+    def set_param(self, name, value):
+        """One parameter of the detection tail (ctpn_set_param): cfg.TEST.RPN_* / TextLineCfg of the reference, by its name."""
+        _check(self._lib.ctpn_set_param(self._h, name.encode(), float(value)))
+
+    def get_param(self, name):
+        v = C.c_double(0.0)
+        _check(self._lib.ctpn_get_param(self._h, name.encode(), C.byref(v)))
         return v.value
 
     def host_threads(self):

@@ -106,6 +106,7 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   c->lstm_split = (dtype_is_half(c->prec) || c->prec == DType::SPLIT) ? 1 : 0;
   c->tail_confine = 0;
   c->postproc_only = postproc_only;
+  for (int i = 0; i < TAIL_PARAM_COUNT; ++i) c->tail_raw[i] = tail_param(i)->dflt;
   {
     // host workers: the node's cores divided by the ranks that share it (torchrun exports LOCAL_WORLD_SIZE), CTPN_HOST_THREADS
     // overrides; CTPN_AFFINITY=1 pins them to the block of cores [local_rank * budget, ...)
@@ -317,6 +318,38 @@ int ctpn_get_option(ctpn_ctx* c, const char* key, int* value_out) {
   const Option* o = find_option(key);
   if (!o) return fail(CTPN_ERR_ARG, std::string("ctpn_get_option: unknown option ") + key);
   *value_out = c->*(o->member);
+  return CTPN_OK;
+}
+
+// ---- the detection tail's parameters: doubles by name, ctpn_set_option's contract ----
+int ctpn_set_param(ctpn_ctx* c, const char* name, double value) {
+  if (!c || !name) return fail(CTPN_ERR_ARG, "ctpn_set_param: null pointer");
+  const int idx = tail_param_index(name);
+  if (idx < 0) return fail(CTPN_ERR_ARG, std::string("ctpn_set_param: unknown parameter ") + name);
+  if (!tail_param_ok(idx, value)) return fail(CTPN_ERR_ARG, std::string("ctpn_set_param: value out of range for ") + name);
+  if (c->tail_raw[idx] == value) return CTPN_OK;
+  // the queued tail reads these (and lays its buffers out by RPN_POST_NMS_TOP_N): drain first
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  for (auto& sl : c->slot) if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_set_param: a submitted batch has not been collected");
+  c->tail_pending = false;
+  c->nms_mw_dirty = true;
+  c->tail_raw[idx] = value;
+  switch (idx) {
+    case TP_RPN_PRE_NMS_TOP_N: c->rpn_pre = (int)value; break;
+    case TP_RPN_POST_NMS_TOP_N: c->rpn_post = (int)value; break;
+    case TP_RPN_NMS_THRESH: c->rpn_nms_thresh = (float)value; break;
+    case TP_RPN_MIN_SIZE: c->rpn_min_size = (float)value; break;
+    default: connector_cfg_set(c->conn, idx, value); break;
+  }
+  return CTPN_OK;
+}
+int ctpn_get_param(ctpn_ctx* c, const char* name, double* value_out) {
+  if (!c || !name || !value_out) return fail(CTPN_ERR_ARG, "ctpn_get_param: null pointer");
+  const int idx = tail_param_index(name);
+  if (idx < 0) return fail(CTPN_ERR_ARG, std::string("ctpn_get_param: unknown parameter ") + name);
+  *value_out = c->tail_raw[idx];
   return CTPN_OK;
 }
 

@@ -5,32 +5,34 @@
 namespace ctpn {
 
 // The text-line tail of a batch whose rois, counts and im_info are on the device (c->rois, c->keep_counts, c->im_info_dev; sl.im_info holds the
-// host copy of im_info): TextDetector.detect's front end -- score > 0.7 prefix, boxes / scale, NMS 0.2 (detectors.py:21-30) -- and, with option
-// connect_device, the connector, in stream order on p. detect_submit_body and the test hook ctpn_debug_text_lines both call it.
+// host copy of im_info): TextDetector.detect's front end -- score > TEXT_PROPOSALS_MIN_SCORE prefix, boxes / scale, NMS TEXT_PROPOSALS_NMS_THRESH
+// (detectors.py:21-30) -- and, with option connect_device, the connector, in stream order on p; thresholds from the ctx's parameters
+// (ctpn_set_param), rows per image = RPN_POST_NMS_TOP_N. detect_submit_body and the test hook ctpn_debug_text_lines both call it.
 // nms_form (nullable): 0 = the generic NMS kernel ran, 1 = the one-workgroup column form, 2 = the multi-workgroup column form.
 static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hipStream_t p, int* nms_form = nullptr) {
-  const int post = c->post_max;
+  const int post = c->rpn_post;
+  const float tl_thresh = c->conn.nms_thresh;
   int rc;
   {
     Timed t(c, CTPN_KIND_NMS, (double)n * post * 24.0, p);
-    if ((rc = launch_lines_prep(c->rois, c->keep_counts, c->im_info_dev, post, 0.7f, c->tl_boxes, c->tl_scores, c->tl_counts, n, p))) return rc;
+    if ((rc = launch_lines_prep(c->rois, c->keep_counts, c->im_info_dev, post, c->conn.min_score, c->tl_boxes, c->tl_scores, c->tl_counts, n, p))) return rc;
     float max_scale = 0.f;
     for (int i = 0; i < n; ++i) max_scale = sl.im_info[3 * i + 2] > max_scale ? sl.im_info[3 * i + 2] : max_scale;
-    if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, 0.2f, max_scale)) {
+    if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, tl_thresh, max_scale)) {
       const bool mw = nms_multi_wg(c, n, 0);
       if (nms_form) *nms_form = mw ? 2 : 1;
-      if ((rc = launch_nms_columns(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
+      if ((rc = launch_nms_columns(c->tl_boxes, c->tl_scores, c->tl_counts, post, tl_thresh, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
                                    c->tl_spill, n, lvl(w, 4), p, nullptr, nullptr, c->im_info_dev, mw ? c->nms_mw_scratch : nullptr))) return rc;
     } else {
       if (nms_form) *nms_form = 0;
-      if ((rc = launch_nms(c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
+      if ((rc = launch_nms(c->tl_boxes, c->tl_scores, c->tl_counts, post, tl_thresh, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
                            c->tl_spill, n, p))) return rc;
     }
   }
   if (c->connect_device) {
     // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect)
     if ((rc = launch_connect(c->tl_boxes, c->tl_scores, c->tl_keep, c->tl_keep_counts, post, c->im_info_dev, c->conn_recs, c->conn_counts,
-                             c->conn_scratch, CONN_CAP, n, p))) return rc;
+                             c->conn_scratch, CONN_CAP, n, c->conn, p))) return rc;
     CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs, c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
     CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt, c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
   }
@@ -55,14 +57,13 @@ static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_
     return fail(rc, first);
   }
   for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)h; sl.im_info[3 * i + 1] = (float)w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
-  const int post = c->post_max;
   hipStream_t p = lone ? c->stream : c->stream_p;
   if (!lone) {
     CTPN_HIP_TRY(hipEventRecord(sl.ev_heads, c->stream));
     CTPN_HIP_TRY(hipStreamWaitEvent(p, sl.ev_heads, 0));
   }
-  // cfg.TEST.* defaults (reference lib/fast_rcnn/config.py:175-183)
-  rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, 12000, post, 0.7f, 8.0f, p, sl.ev_decoded);
+  // cfg.TEST.RPN_* (reference lib/fast_rcnn/config.py:175-183): the ctx's parameters, those defaults unless ctpn_set_param changed them
+  rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded);
   if (rc) return rc;
   c->ev_last_decoded = sl.ev_decoded;
   if ((rc = enqueue_text_lines(c, sl, n, w, p))) return rc;
@@ -81,7 +82,8 @@ static int detect_submit_impl(ctpn_ctx* c, const uint8_t* images, int images_on_
 // the lines of a batch whose tail has finished, from what it left in the slot's page-locked buffers: the device connector's records (option
 // connect_device), or connect_lines on the host workers over the connector NMS's survivors. ctpn_detect_collect and ctpn_debug_text_lines.
 static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int h, int w, int mode, double* recs_out, int line_capacity, int* line_counts) {
-  const int post = c->post_max;
+  const int post = c->rpn_post;
+  const ConnectorCfg cfg = c->conn;      // the workers' copy
   if (c->connect_device) {
     for (int i = 0; i < n; ++i) {
       if (sl.ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
@@ -103,7 +105,7 @@ static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int h, int w, i
       ks[j] = sl.tls[(size_t)i * post + src];
     }
     std::vector<double> recs;
-    int st = connect_lines(kb.data(), ks.data(), nk, h, w, mode, recs);
+    int st = connect_lines(kb.data(), ks.data(), nk, h, w, mode, cfg, recs);
     if (st) { status[i] = st; errs[i] = ctpn_last_error(); return; }
     const int cnt = (int)(recs.size() / 9);
     line_counts[i] = cnt;
@@ -124,9 +126,9 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
   if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: mode must be H(0) or O(1)");
   if (n <= 0 || n > c->max_batch) return fail(CTPN_ERR_CAPACITY, "ctpn_debug_text_lines: 1 <= n <= max_batch images");
   if (im_h < 1 || im_w < 16 || line_capacity < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: im_h >= 1, im_w >= 16, line_capacity >= 0 required");
-  const int post = c->post_max;
+  const int post = c->rpn_post, post_max = c->post_max;      // rows per image on the device / in the caller's arrays
   for (int i = 0; i < n; ++i)
-    if (roi_counts[i] < 0 || roi_counts[i] > post) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: 0 <= roi_counts[i] <= 1000 rows of [score,x1,y1,x2,y2]");
+    if (roi_counts[i] < 0 || roi_counts[i] > post) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: 0 <= roi_counts[i] <= RPN_POST_NMS_TOP_N (1000) rows of [score,x1,y1,x2,y2]");
   if (c->slot[0].busy || c->slot[1].busy) return fail(CTPN_ERR_STATE, "ctpn_debug_text_lines: a submitted batch has not been collected");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream));      // the proposal entry points use these buffers on the forward's stream
@@ -139,7 +141,8 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
     c->nms_mw_dirty = false;
   }
   CTPN_HIP_TRY(hipMemcpyAsync(c->im_info_dev, sl.im_info, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, p));
-  CTPN_HIP_TRY(hipMemcpyAsync(c->rois, rois, (size_t)n * post * 5 * sizeof(float), hipMemcpyHostToDevice, p));
+  if (post == post_max) CTPN_HIP_TRY(hipMemcpyAsync(c->rois, rois, (size_t)n * post * 5 * sizeof(float), hipMemcpyHostToDevice, p));
+  else CTPN_HIP_TRY(hipMemcpy2DAsync(c->rois, (size_t)post * 5 * sizeof(float), rois, (size_t)post_max * 5 * sizeof(float), (size_t)post * 5 * sizeof(float), n, hipMemcpyHostToDevice, p));
   CTPN_HIP_TRY(hipMemcpyAsync(c->keep_counts, roi_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, p));
   int form = 0, rc;
   if ((rc = enqueue_text_lines(c, sl, n, im_w, p, &form))) return rc;
@@ -148,10 +151,10 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
   for (int i = 0; i < n; ++i)
     if (sl.kcnt[i] < 0 || sl.kcnt[i] > post) return fail(CTPN_ERR_HIP, "ctpn_debug_text_lines: device returned an impossible keep count");
   if (keep_counts) std::memcpy(keep_counts, sl.kcnt, (size_t)n * sizeof(int));
-  if (keep_out) std::memcpy(keep_out, sl.keep, (size_t)n * post * sizeof(int));
+  if (keep_out) for (int i = 0; i < n; ++i) std::memcpy(keep_out + (size_t)i * post_max, sl.keep + (size_t)i * post, (size_t)post * sizeof(int));
   // option nms_check, as in the proposal layer: the generic kernel on the same prepared boxes must keep the same rows
   if (c->nms_check && form != 0 &&
-      (rc = nms_check_generic(c, c->tl_boxes, c->tl_scores, c->tl_counts, post, 0.2f, post, sl.keep, post, sl.kcnt, n, form == 2, p, "connector NMS"))) return rc;
+      (rc = nms_check_generic(c, c->tl_boxes, c->tl_scores, c->tl_counts, post, c->conn.nms_thresh, post, sl.keep, post, sl.kcnt, n, form == 2, p, "connector NMS"))) return rc;
   return lines_of_slot(c, sl, n, im_h, im_w, mode, recs_out, line_capacity, line_counts);
 }
 
@@ -159,13 +162,16 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
 
 extern "C" {
 
-int ctpn_text_lines(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode, int device_id, double* recs_out,
-                    int capacity, int* count_out) {
+int ctpn_text_lines_cfg(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode, int device_id, const double* cfg8,
+                        double* recs_out, int capacity, int* count_out) {
   if (!count_out) return fail(CTPN_ERR_ARG, "ctpn_text_lines: count_out is null");
   *count_out = 0;
   if (r > 0 && (!boxes || !scores)) return fail(CTPN_ERR_ARG, "ctpn_text_lines: null input");
+  ConnectorCfg cfg = default_connector_cfg();
+  int rc = connector_cfg_from8(cfg8, cfg);
+  if (rc) return rc;
   std::vector<double> recs;
-  int rc = text_lines_host(boxes, scores, r, im_h, im_w, mode, device_id, recs);
+  rc = text_lines_host(boxes, scores, r, im_h, im_w, mode, device_id, cfg, recs);
   if (rc) return rc;
   const int cnt = (int)(recs.size() / 9);
   *count_out = cnt;
@@ -173,6 +179,11 @@ int ctpn_text_lines(const float* boxes, const float* scores, int r, int im_h, in
   if (cnt && !recs_out) return fail(CTPN_ERR_ARG, "ctpn_text_lines: recs_out is null");
   if (cnt) std::memcpy(recs_out, recs.data(), recs.size() * sizeof(double));
   return CTPN_OK;
+}
+
+int ctpn_text_lines(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode, int device_id, double* recs_out,
+                    int capacity, int* count_out) {
+  return ctpn_text_lines_cfg(boxes, scores, r, im_h, im_w, mode, device_id, nullptr, recs_out, capacity, count_out);
 }
 
 int ctpn_detect_submit(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot) {
@@ -188,8 +199,9 @@ int ctpn_detect_collect(ctpn_ctx* c, int slot, int mode, double* recs_out, int l
   if (!sl.busy) return fail(CTPN_ERR_STATE, "ctpn_detect_collect: nothing was submitted to this slot");
   CTPN_HIP_TRY(hipEventSynchronize(sl.ev_done));
   sl.busy = false;
-  const int n = sl.n, h = sl.h, w = sl.w, post = c->post_max;
-  if (rois_out) std::memcpy(rois_out, sl.rois, (size_t)n * post * 5 * sizeof(float));
+  const int n = sl.n, h = sl.h, w = sl.w, post = c->rpn_post, post_max = c->post_max;
+  // rois_out keeps post_max (1000) rows per image whatever RPN_POST_NMS_TOP_N is; the slot holds them packed
+  if (rois_out) for (int i = 0; i < n; ++i) std::memcpy(rois_out + (size_t)i * post_max * 5, sl.rois + (size_t)i * post * 5, (size_t)post * 5 * sizeof(float));
   if (roi_counts) std::memcpy(roi_counts, sl.rcnt, (size_t)n * sizeof(int));
   return lines_of_slot(c, sl, n, h, w, mode, recs_out, line_capacity, line_counts);
 }
@@ -219,6 +231,7 @@ int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im
   if (device_id < 0 || device_id >= ndev) return fail(CTPN_ERR_ARG, "ctpn_debug_connect: device_id out of range");
   CTPN_HIP_TRY(hipSetDevice(device_id));
   const int post = 1000;
+  const ConnectorCfg cfg = default_connector_cfg();       // a stateless hook: the defaults
   char* buf = nullptr;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
@@ -236,12 +249,12 @@ int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im
   if (r) DC_TRY(hipMemcpyAsync(buf + o_rois, rois, (size_t)r * 5 * 4, hipMemcpyHostToDevice, st));
   DC_TRY(hipMemcpyAsync(buf + o_cnt, &r, 4, hipMemcpyHostToDevice, st));
   DC_TRY(hipMemcpyAsync(buf + o_info, info, 12, hipMemcpyHostToDevice, st));
-  if ((rc = launch_lines_prep((const float*)(buf + o_rois), (const int*)(buf + o_cnt), (const float*)(buf + o_info), post, 0.7f, (float*)(buf + o_tlb),
+  if ((rc = launch_lines_prep((const float*)(buf + o_rois), (const int*)(buf + o_cnt), (const float*)(buf + o_info), post, cfg.min_score, (float*)(buf + o_tlb),
                               (float*)(buf + o_tls), (int*)(buf + o_tlc), 1, st))) return done(rc);
-  if ((rc = launch_nms((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_tlc), post, 0.2f, post, (int*)(buf + o_keep), post,
+  if ((rc = launch_nms((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_tlc), post, cfg.nms_thresh, post, (int*)(buf + o_keep), post,
                        (int*)(buf + o_kc), nullptr, (float*)(buf + o_spill), 1, st))) return done(rc);
   if ((rc = launch_connect((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_keep), (const int*)(buf + o_kc), post,
-                           (const float*)(buf + o_info), (double*)(buf + o_recs), (int*)(buf + o_cc), (double*)(buf + o_scr), CONN_CAP, 1, st))) return done(rc);
+                           (const float*)(buf + o_info), (double*)(buf + o_recs), (int*)(buf + o_cc), (double*)(buf + o_scr), CONN_CAP, 1, cfg, st))) return done(rc);
   int cc[3] = {0, 0, 0};
   DC_TRY(hipMemcpyAsync(cc, buf + o_cc, 12, hipMemcpyDeviceToHost, st));
   DC_TRY(hipStreamSynchronize(st));

@@ -258,17 +258,40 @@ bool nms_columns_ok(int ncols, int stride, float thresh);
 int launch_hog(unsigned* sink, int n_wg, int usec, int touch, hipStream_t s, const void* src = nullptr, size_t src_bytes = 0);      // diagnostic: the one-workgroup NMS's footprint without its work (proposal.hip)
 bool nms_columns_tl_ok(int ncols, int stride, float thresh, float max_scale);
 
+// The connector's configuration (reference TextLineCfg, lib/text_connector/text_connect_cfg.py:4-12), passed down to the host connector and, by
+// value, to connect_kernel. Every member has the type its compiled-in counterpart had before the values became run-time parameters
+// (fp32 where the reference's comparison is fp32, fp64 in filter_boxes), so the defaults compute what the constants did, bit for bit.
+struct ConnectorCfg {
+  float min_score;          // TEXT_PROPOSALS_MIN_SCORE
+  float nms_thresh;         // TEXT_PROPOSALS_NMS_THRESH
+  int max_gap;              // MAX_HORIZONTAL_GAP
+  float min_v_overlaps;     // MIN_V_OVERLAPS
+  float min_size_sim;       // MIN_SIZE_SIM
+  double min_ratio;         // MIN_RATIO
+  double line_min_score;    // LINE_MIN_SCORE
+  double min_width;         // TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPOSALS
+};
+ConnectorCfg default_connector_cfg();      // the reference's values (text_connector.cpp holds them)
+// the tail's parameters by name (ctpn_set_param / ctpn_param_*), in ABI order; table, ranges and conversions in text_connector.cpp
+enum { TP_RPN_PRE_NMS_TOP_N = 0, TP_RPN_POST_NMS_TOP_N, TP_RPN_NMS_THRESH, TP_RPN_MIN_SIZE, TP_MIN_SCORE, TP_NMS_THRESH, TP_MAX_GAP,
+       TP_MIN_V_OVERLAPS, TP_MIN_SIZE_SIM, TP_MIN_RATIO, TP_LINE_MIN_SCORE, TP_MIN_LINE_WIDTH, TAIL_PARAM_COUNT };
+struct TailParam { const char* name; double dflt, lo, hi; bool integral; };
+const TailParam* tail_param(int index);                          // null outside 0 .. TAIL_PARAM_COUNT - 1
+int tail_param_index(const char* name);                          // -1: unknown
+bool tail_param_ok(int index, double v);                         // finite, inside the range, integral where the parameter is
+void connector_cfg_set(ConnectorCfg& c, int index, double v);    // the TP_* of the connector; others are ignored
+int connector_cfg_from8(const double* cfg8, ConnectorCfg& out);  // ctpn_connector_constants' order; null: the defaults
 // host text connector (text_connector.cpp)
 int text_lines_host(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode,
-                    int device_id, std::vector<double>& recs);
+                    int device_id, const ConnectorCfg& cfg, std::vector<double>& recs);
 int connect_lines(const float* kept_boxes, const float* kept_scores, int n, int im_h, int im_w, int mode,
-                  std::vector<double>& recs);
+                  const ConnectorCfg& cfg, std::vector<double>& recs);
 // rois [n_img][post][5] (descending score) -> per image: boxes/scale of the score > min_score prefix + its length
 constexpr int CONN_CAP = 512;   // text lines per image and mode the device connector can return (chains <= proposals / 2 = 500)
 // text-line connector on the device: recs [n_img][2 modes][cap][9] float64, counts [n_img][3] = lines H, lines O, status;
 // scratch [n_img][1024][20] float64
 int launch_connect(const float* boxes, const float* scores, const int* keep, const int* keep_counts, int stride, const float* im_info,
-                   double* recs, int* counts, double* scratch, int cap, int n_img, hipStream_t s);
+                   double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s);
 int launch_lines_prep(const float* rois, const int* roi_counts, const float* im_info, int post, float min_score,
                       float* tl_boxes, float* tl_scores, int* tl_counts, int n_img, hipStream_t s);
 // host greedy NMS used by the connector when device_id < 0 (same predicate as the device kernel)

@@ -281,6 +281,14 @@ struct ctpn_ctx {
   int connect_device = 0;            // "connect_device": 1 = graph build / chains / line fit on the GPU (connect_kernel), 0 = host C++
                                      // (text_connector.cpp; default: it runs on otherwise idle host cores under the next batch's convolutions,
                                      // the kernel shares the GPU with them: 11.15 vs 11.06 ms / step)
+  // the detection tail's parameters (ctpn_set_param; defaults: cfg.TEST.RPN_* and TextLineCfg of the reference), read by ctpn_detect*,
+  // ctpn_debug_text_lines and the collect's host connector. tail_raw: the values as set (ctpn_get_param returns them); the typed members
+  // beside it: what the launches use, converted once at set time. The tail's device buffers and the slots' packs are laid out with
+  // stride rpn_post (<= post_max) per image; ctpn_detect_collect / ctpn_debug_text_lines keep post_max rows per image towards the caller.
+  double tail_raw[TAIL_PARAM_COUNT];
+  int rpn_pre = 12000, rpn_post = 1000;
+  float rpn_nms_thresh = 0.7f, rpn_min_size = 8.0f;
+  ConnectorCfg conn = default_connector_cfg();
   bool proposals_done = false;
   bool postproc_only = false;        // ctpn_create_postproc: proposal / connector buffers only, no network
   std::unique_ptr<ctpn::HostPool> pool;

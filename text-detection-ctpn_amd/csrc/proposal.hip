@@ -1111,13 +1111,21 @@ __global__ __launch_bounds__(256) void lines_prep_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------
 constexpr int CONN_MAX = 1024;          // proposals per image held in LDS (RPN_POST_NMS_TOP_N = 1000)
 
-__device__ __forceinline__ bool conn_meet_v_iou(const float* y1, const float* y2, const float* hh, int a, int b) {
+// connect_kernel's share of ConnectorCfg, by value in the kernel arguments: wave-uniform, read from SGPRs. gap_f = (float)gap (exact: the
+// gap is at most 4096), what the reference's `x1 - MAX_HORIZONTAL_GAP` subtracts from the fp32 x1.
+struct ConnectArgs {
+  int gap; float gap_f;              // MAX_HORIZONTAL_GAP
+  float min_v_overlaps, min_size_sim;
+  double min_ratio, line_min_score, min_width;
+};
+
+__device__ __forceinline__ bool conn_meet_v_iou(const float* y1, const float* y2, const float* hh, int a, int b, const ConnectArgs& ca) {
   const float h1 = hh[a], h2 = hh[b];
   const float y0 = fmaxf(y1[b], y1[a]);
   const float y1m = fminf(y2[b], y2[a]);
   const float ov = fmaxf(0.0f, y1m - y0 + 1.0f) / fminf(h1, h2);
   const float sim = fminf(h1, h2) / fmaxf(h1, h2);
-  return ov >= 0.7f && sim >= 0.7f;       // MIN_V_OVERLAPS, MIN_SIZE_SIM
+  return ov >= ca.min_v_overlaps && sim >= ca.min_size_sim;
 }
 
 // np.polyfit(X, Y, 1) over a chain: double least squares, coefficients rounded to fp32 (same op order as polyfit1 on the host)
@@ -1160,7 +1168,7 @@ __device__ __forceinline__ void conn_sum_rec(int m, float& rs, float& rh, Leaf& 
 __global__ __launch_bounds__(256) void connect_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                                       const int* __restrict__ keep, const int* __restrict__ keep_counts, int stride,
                                                       const float* __restrict__ im_info, double* __restrict__ recs, int* __restrict__ counts,
-                                                      double* __restrict__ scratch, int cap) {
+                                                      double* __restrict__ scratch, int cap, const ConnectArgs ca) {
   __shared__ float sx1[CONN_MAX], sy1[CONN_MAX], sx2[CONN_MAX], sy2[CONN_MAX], sh[CONN_MAX], ss[CONN_MAX];
   __shared__ float spmax[CONN_MAX];
   __shared__ int ssucc[CONN_MAX];
@@ -1186,17 +1194,17 @@ __global__ __launch_bounds__(256) void connect_kernel(const float* __restrict__ 
   int* cnt2 = counts + (size_t)img * 3;                    // lines H, lines O, status
   if (sbad) { if (tid == 0) { cnt2[0] = 0; cnt2[1] = 0; cnt2[2] = -1; } return; }
 
-  // precursors of every node: nearest matching column to the left within 50 px, max score in it
+  // precursors of every node: nearest matching column to the left within MAX_HORIZONTAL_GAP px, max score in it
   for (int b = tid; b < n; b += 256) {
     const int colb = (int)sx1[b];
-    int lo = (int)(sx1[b] - 50.0f);
+    int lo = (int)(sx1[b] - ca.gap_f);
     lo = lo < 0 ? 0 : lo;
     int cbest = -1;
     float pmax = -INFINITY;
     for (int k = 0; k < n; ++k) {
       const int ck = (int)sx1[k];
       if (ck < lo || ck >= colb || ck < cbest) continue;
-      if (!conn_meet_v_iou(sy1, sy2, sh, k, b)) continue;
+      if (!conn_meet_v_iou(sy1, sy2, sh, k, b, ca)) continue;
       if (ck > cbest) { cbest = ck; pmax = ss[k]; }
       else pmax = fmaxf(pmax, ss[k]);
     }
@@ -1204,15 +1212,15 @@ __global__ __launch_bounds__(256) void connect_kernel(const float* __restrict__ 
     spmax[b] = pmax;
   }
   __syncthreads();
-  // successors: nearest matching column to the right within 50 px, first maximum score in index order
+  // successors: nearest matching column to the right within MAX_HORIZONTAL_GAP px, first maximum score in index order
   for (int i = tid; i < n; i += 256) {
     const int coli = (int)sx1[i];
-    const int hi = coli + 50 < im_w - 1 ? coli + 50 : im_w - 1;
+    const int hi = coli + ca.gap < im_w - 1 ? coli + ca.gap : im_w - 1;
     int cbest = 0x7fffffff, best = -1;
     for (int j = 0; j < n; ++j) {
       const int cj = (int)sx1[j];
       if (cj <= coli || cj > hi || cj > cbest) continue;
-      if (!conn_meet_v_iou(sy1, sy2, sh, j, i)) continue;
+      if (!conn_meet_v_iou(sy1, sy2, sh, j, i, ca)) continue;
       if (cj < cbest) { cbest = cj; best = j; }
       else if (ss[j] > ss[best]) best = j;
     }
@@ -1304,7 +1312,7 @@ __global__ __launch_bounds__(256) void connect_kernel(const float* __restrict__ 
       const double* r = o + 10 * m;
       const double heights = (fabs(r[5] - r[1]) + fabs(r[7] - r[3])) / 2.0 + 1;
       const double widths = (fabs(r[2] - r[0]) + fabs(r[6] - r[4])) / 2.0 + 1;
-      o[10 * m + 9] = (widths / heights > 0.5 && r[8] > 0.9 && widths > 32.0) ? 1.0 : 0.0;
+      o[10 * m + 9] = (widths / heights > ca.min_ratio && r[8] > ca.line_min_score && widths > ca.min_width) ? 1.0 : 0.0;
     }
   }
   __syncthreads();
@@ -1327,9 +1335,10 @@ __global__ __launch_bounds__(256) void connect_kernel(const float* __restrict__ 
 }
 
 int launch_connect(const float* boxes, const float* scores, const int* keep, const int* keep_counts, int stride, const float* im_info,
-                   double* recs, int* counts, double* scratch, int cap, int n_img, hipStream_t s) {
+                   double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s) {
   if (stride > CONN_MAX) return fail(CTPN_ERR_ARG, "connect: more proposals per image than the kernel holds in LDS");
-  hipLaunchKernelGGL(connect_kernel, dim3(n_img), dim3(256), 0, s, boxes, scores, keep, keep_counts, stride, im_info, recs, counts, scratch, cap);
+  const ConnectArgs ca{cfg.max_gap, (float)cfg.max_gap, cfg.min_v_overlaps, cfg.min_size_sim, cfg.min_ratio, cfg.line_min_score, cfg.min_width};
+  hipLaunchKernelGGL(connect_kernel, dim3(n_img), dim3(256), 0, s, boxes, scores, keep, keep_counts, stride, im_info, recs, counts, scratch, cap, ca);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("connect launch: ") + hipGetErrorString(e));
   return CTPN_OK;

@@ -23,7 +23,7 @@
 
 namespace ctpn {
 
-namespace {
+// the connector's defaults: TextLineCfg of the reference
 constexpr float kMinScore = 0.7f;        // TEXT_PROPOSALS_MIN_SCORE
 constexpr float kNmsThresh = 0.2f;       // TEXT_PROPOSALS_NMS_THRESH
 constexpr int kMaxGap = 50;              // MAX_HORIZONTAL_GAP
@@ -32,11 +32,71 @@ constexpr float kMinSizeSim = 0.7f;      // MIN_SIZE_SIM
 constexpr double kMinRatio = 0.5;        // MIN_RATIO
 constexpr double kLineMinScore = 0.9;    // LINE_MIN_SCORE
 constexpr double kMinWidth = 16.0 * 2;   // TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPOSALS
+ConnectorCfg default_connector_cfg() { return ConnectorCfg{kMinScore, kNmsThresh, kMaxGap, kMinVOverlaps, kMinSizeSim, kMinRatio, kLineMinScore, kMinWidth}; }
 
+// ---- the tail's run-time parameters (ctpn_set_param and friends; ctpn_text_lines_cfg's cfg8): names, defaults, ranges ----
+// RPN_*: cfg.TEST.* of the reference (lib/fast_rcnn/config.py:175-183); the rest: TextLineCfg (common.h ConnectorCfg). The two top-N values
+// stop at their defaults (what a ctx's buffers and the device connector's CONN_MAX are sized for); the NMS thresholds at 0 (the
+// column-decomposed NMS relies on boxes of non-adjacent columns never suppressing each other); values that are used as fp32 must stay
+// finite when rounded to it.
+static const TailParam kTailParams[TAIL_PARAM_COUNT] = {
+    {"RPN_PRE_NMS_TOP_N", 12000.0, 1.0, 12000.0, true},
+    {"RPN_POST_NMS_TOP_N", 1000.0, 1.0, 1000.0, true},
+    {"RPN_NMS_THRESH", 0.7, 0.0, 1.0, false},
+    {"RPN_MIN_SIZE", 8.0, 0.0, 3.0e38, false},
+    {"TEXT_PROPOSALS_MIN_SCORE", 0.7, -3.0e38, 3.0e38, false},
+    {"TEXT_PROPOSALS_NMS_THRESH", 0.2, 0.0, 1.0, false},
+    {"MAX_HORIZONTAL_GAP", 50.0, 0.0, 4096.0, true},
+    {"MIN_V_OVERLAPS", 0.7, -3.0e38, 3.0e38, false},
+    {"MIN_SIZE_SIM", 0.7, -3.0e38, 3.0e38, false},
+    {"MIN_RATIO", 0.5, -1.0e300, 1.0e300, false},
+    {"LINE_MIN_SCORE", 0.9, -1.0e300, 1.0e300, false},
+    {"MIN_LINE_WIDTH", 32.0, -1.0e300, 1.0e300, false},
+};
+const TailParam* tail_param(int index) { return index >= 0 && index < TAIL_PARAM_COUNT ? &kTailParams[index] : nullptr; }
+int tail_param_index(const char* name) {
+  if (name)
+    for (int i = 0; i < TAIL_PARAM_COUNT; ++i) if (std::strcmp(name, kTailParams[i].name) == 0) return i;
+  return -1;
+}
+bool tail_param_ok(int index, double v) {
+  const TailParam* p = tail_param(index);
+  if (!p || !std::isfinite(v) || v < p->lo || v > p->hi) return false;
+  return !p->integral || v == std::floor(v);
+}
+// one connector value into the struct, in the precision its compiled-in counterpart had (fp32 values are rounded here, once)
+void connector_cfg_set(ConnectorCfg& c, int index, double v) {
+  switch (index) {
+    case TP_MIN_SCORE: c.min_score = (float)v; break;
+    case TP_NMS_THRESH: c.nms_thresh = (float)v; break;
+    case TP_MAX_GAP: c.max_gap = (int)v; break;
+    case TP_MIN_V_OVERLAPS: c.min_v_overlaps = (float)v; break;
+    case TP_MIN_SIZE_SIM: c.min_size_sim = (float)v; break;
+    case TP_MIN_RATIO: c.min_ratio = v; break;
+    case TP_LINE_MIN_SCORE: c.line_min_score = v; break;
+    case TP_MIN_LINE_WIDTH: c.min_width = v; break;
+    default: break;
+  }
+}
+// cfg8 in ctpn_connector_constants' order
+static const int kCfg8Index[8] = {TP_MIN_LINE_WIDTH, TP_MIN_RATIO, TP_LINE_MIN_SCORE, TP_MAX_GAP, TP_MIN_SCORE, TP_NMS_THRESH, TP_MIN_V_OVERLAPS, TP_MIN_SIZE_SIM};
+int connector_cfg_from8(const double* cfg8, ConnectorCfg& out) {
+  out = default_connector_cfg();
+  if (!cfg8) return CTPN_OK;
+  for (int k = 0; k < 8; ++k) {
+    if (!tail_param_ok(kCfg8Index[k], cfg8[k])) return fail(CTPN_ERR_ARG, std::string("connector configuration: value out of range for ") + kTailParams[kCfg8Index[k]].name);
+    connector_cfg_set(out, kCfg8Index[k], cfg8[k]);
+  }
+  return CTPN_OK;
+}
+
+namespace {
 struct Props {
   std::vector<float> x1, y1, x2, y2, h, s;
   std::vector<std::vector<int>> table;  // boxes_table: proposals bucketed by int(x1)
   int im_w = 0;
+  int max_gap = 0;                      // MAX_HORIZONTAL_GAP
+  float min_v_overlaps = 0.f, min_size_sim = 0.f;
   size_t size() const { return x1.size(); }
 };
 
@@ -46,14 +106,14 @@ bool meet_v_iou(const Props& p, int a, int b) {
   const float y1 = std::min(p.y2[b], p.y2[a]);
   const float ov = std::max(0.0f, y1 - y0 + 1.0f) / std::min(h1, h2);
   const float sim = std::min(h1, h2) / std::max(h1, h2);
-  return ov >= kMinVOverlaps && sim >= kMinSizeSim;
+  return ov >= p.min_v_overlaps && sim >= p.min_size_sim;
 }
 
-// first non-empty column to the right of `index` (x1+1 .. x1+50, inside the image)
+// first non-empty column to the right of `index` (x1+1 .. x1+MAX_HORIZONTAL_GAP, inside the image)
 void successions(const Props& p, int index, std::vector<int>& out) {
   out.clear();
   const int x = (int)p.x1[index];
-  const int hi = std::min(x + kMaxGap + 1, p.im_w);
+  const int hi = std::min(x + p.max_gap + 1, p.im_w);
   for (int left = x + 1; left < hi; ++left) {
     for (int adj : p.table[left])
       if (meet_v_iou(p, adj, index)) out.push_back(adj);
@@ -65,7 +125,7 @@ void successions(const Props& p, int index, std::vector<int>& out) {
 void precursors(const Props& p, int index, std::vector<int>& out) {
   out.clear();
   const int x = (int)p.x1[index];
-  const int lo = std::max((int)(p.x1[index] - (float)kMaxGap), 0);
+  const int lo = std::max((int)(p.x1[index] - (float)p.max_gap), 0);
   for (int left = x - 1; left >= lo; --left) {
     for (int adj : p.table[left])
       if (meet_v_iou(p, adj, index)) out.push_back(adj);
@@ -151,15 +211,15 @@ void nms_host(const float* boxes, int n, int dim, float thresh, std::vector<int>
 }
 
 int text_lines_host(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode, int device_id,
-                    std::vector<double>& recs) {
+                    const ConnectorCfg& cfg, std::vector<double>& recs) {
   recs.clear();
   if (r < 0 || im_h <= 0 || im_w <= 0) return fail(CTPN_ERR_ARG, "text_lines: bad size");
   if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "text_lines: mode must be H(0) or O(1)");
 
-  // detect(): score filter, descending sort, NMS 0.2
+  // detect(): score filter, descending sort, NMS
   std::vector<int> order;
   for (int i = 0; i < r; ++i)
-    if (scores[i] > kMinScore) order.push_back(i);
+    if (scores[i] > cfg.min_score) order.push_back(i);
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return scores[a] > scores[b]; });
   const int n0 = (int)order.size();
   if (n0 == 0) return CTPN_OK;
@@ -173,11 +233,11 @@ int text_lines_host(const float* boxes, const float* scores, int r, int im_h, in
   if (device_id >= 0) {
     keep.resize(n0);
     int nk = 0;
-    const int rc = ctpn_nms(keep.data(), &nk, dets.data(), n0, 5, kNmsThresh, device_id);
+    const int rc = ctpn_nms(keep.data(), &nk, dets.data(), n0, 5, cfg.nms_thresh, device_id);
     if (rc) return rc;
     keep.resize(nk);
   } else {
-    nms_host(dets.data(), n0, 5, kNmsThresh, keep);
+    nms_host(dets.data(), n0, 5, cfg.nms_thresh, keep);
   }
 
   const int nk = (int)keep.size();
@@ -186,18 +246,19 @@ int text_lines_host(const float* boxes, const float* scores, int r, int im_h, in
     const float* d = &dets[(size_t)keep[i] * 5];
     kb[4 * i] = d[0]; kb[4 * i + 1] = d[1]; kb[4 * i + 2] = d[2]; kb[4 * i + 3] = d[3]; ks[i] = d[4];
   }
-  return connect_lines(kb.data(), ks.data(), nk, im_h, im_w, mode, recs);
+  return connect_lines(kb.data(), ks.data(), nk, im_h, im_w, mode, cfg, recs);
 }
 
 // graph build + chain extraction + line fit + filter_boxes on proposals that already went through
 // detect()'s score filter, sort and NMS (rows in descending score order)
 int connect_lines(const float* kept_boxes, const float* kept_scores, int n, int im_h, int im_w, int mode,
-                  std::vector<double>& recs) {
+                  const ConnectorCfg& cfg, std::vector<double>& recs) {
   recs.clear();
   if (n < 0 || im_h <= 0 || im_w <= 0) return fail(CTPN_ERR_ARG, "connect_lines: bad size");
   if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "connect_lines: mode must be H(0) or O(1)");
   Props p;
   p.im_w = im_w;
+  p.max_gap = cfg.max_gap; p.min_v_overlaps = cfg.min_v_overlaps; p.min_size_sim = cfg.min_size_sim;
   p.x1.resize(n); p.y1.resize(n); p.x2.resize(n); p.y2.resize(n); p.h.resize(n); p.s.resize(n);
   p.table.assign((size_t)im_w, {});
   for (int i = 0; i < n; ++i) {
@@ -285,7 +346,7 @@ int connect_lines(const float* kept_boxes, const float* kept_scores, int n, int 
     const double* b = &all[i];
     const double heights = (std::fabs(b[5] - b[1]) + std::fabs(b[7] - b[3])) / 2.0 + 1;
     const double widths = (std::fabs(b[2] - b[0]) + std::fabs(b[6] - b[4])) / 2.0 + 1;
-    if (widths / heights > kMinRatio && b[8] > kLineMinScore && widths > kMinWidth) recs.insert(recs.end(), b, b + 9);
+    if (widths / heights > cfg.min_ratio && b[8] > cfg.line_min_score && widths > cfg.min_width) recs.insert(recs.end(), b, b + 9);
   }
   return CTPN_OK;
 }
@@ -300,14 +361,26 @@ namespace {
 inline bool skipped(const double* b) { return std::fabs(b[0] - b[1]) < 5.0 || std::fabs(b[3] - b[0]) < 5.0; }
 }  // namespace
 
-// The connector's constants as compiled into this library (TextLineCfg of the reference, lib/text_connector/text_connect_cfg.py:4-12, minus
-// SCALE / MAX_SCALE, which the Python side reads): the reference reads them at run time, so a caller that edits its Config expects an
-// effect -- lib/text_connector/detectors.py compares its Config with these and fails loudly instead of ignoring the edit.
+// The connector's DEFAULTS (TextLineCfg of the reference, lib/text_connector/text_connect_cfg.py:4-12, minus SCALE / MAX_SCALE, which the
+// Python side reads): what ctpn_text_lines, a NULL cfg8 and a fresh ctx use. The reference reads them at run time, so a caller that edits
+// the module-level Config expects an effect -- lib/text_connector/detectors.py compares it with these and fails loudly instead of ignoring
+// the edit; a configuration of the caller's own goes through ctpn_text_lines_cfg / ctpn_set_param.
 extern "C" int ctpn_connector_constants(double* out8) {
   if (!out8) return ctpn::fail(CTPN_ERR_ARG, "ctpn_connector_constants: null pointer");
-  const double v[8] = {ctpn::kMinWidth, ctpn::kMinRatio, ctpn::kLineMinScore, (double)ctpn::kMaxGap, (double)ctpn::kMinScore, (double)ctpn::kNmsThresh,
-                       (double)ctpn::kMinVOverlaps, (double)ctpn::kMinSizeSim};
+  const ctpn::ConnectorCfg d = ctpn::default_connector_cfg();
+  const double v[8] = {d.min_width, d.min_ratio, d.line_min_score, (double)d.max_gap, (double)d.min_score, (double)d.nms_thresh,
+                       (double)d.min_v_overlaps, (double)d.min_size_sim};
   std::memcpy(out8, v, sizeof(v));
+  return CTPN_OK;
+}
+
+extern "C" int ctpn_param_count(void) { return ctpn::TAIL_PARAM_COUNT; }
+extern "C" const char* ctpn_param_name(int index) { const ctpn::TailParam* p = ctpn::tail_param(index); return p ? p->name : nullptr; }
+extern "C" int ctpn_param_default(const char* name, double* value_out) {
+  if (!name || !value_out) return ctpn::fail(CTPN_ERR_ARG, "ctpn_param_default: null pointer");
+  const ctpn::TailParam* p = ctpn::tail_param(ctpn::tail_param_index(name));
+  if (!p) return ctpn::fail(CTPN_ERR_ARG, std::string("ctpn_param_default: unknown parameter ") + name);
+  *value_out = p->dflt;
   return CTPN_OK;
 }
 

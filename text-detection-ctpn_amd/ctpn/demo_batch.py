@@ -13,7 +13,12 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
   * with --crops DIR every detected line is also cut out as a rectified image of fixed height, `<stem>_<k>.jpg`, for a recogniser behind
     the detector (ctpn_crop_lines: on the device; batches decoded there are cropped where they lie, without fetching them).
 
+  * cfg.TEST.RPN_* of the loaded text.yml go into the ctx's tail parameters (ctpn_set_param), so the batched path honours the file like
+    the single-image path; --connector NAME=VALUE (repeatable; TextLineCfg's names, MIN_LINE_WIDTH for TEXT_PROPOSALS_WIDTH *
+    MIN_NUM_PROPOSALS) sets the connector's thresholds for the batches and for the images that take the single-image path.
+
     python -m ctpn_amd.ctpn.demo_batch --input data/demo --out data/results --batch 32 [--mode O] [--synthetic 0] [--no-images]
+        [--connector LINE_MIN_SCORE=0.8 --connector MAX_HORIZONTAL_GAP=70]
 """
 from __future__ import print_function
 
@@ -75,7 +80,10 @@ def plan(names, batch):
     return jobs, singles, shapes
 
 
-def _check_uint8_feed_config():
+RPN_PARAM_NAMES = ("RPN_PRE_NMS_TOP_N", "RPN_POST_NMS_TOP_N", "RPN_NMS_THRESH", "RPN_MIN_SIZE")
+
+
+def _check_uint8_feed_config(params=None):
     """The batched path feeds uint8 images; the library subtracts the reference's PIXEL_MEANS (lib/fast_rcnn/config.py:200) inside its first
     kernel (csrc/layers.hip), compiled in. The reference subtracts cfg.PIXEL_MEANS at run time (lib/fast_rcnn/test.py:7-11), so an edited
     value must not be ignored silently: it is an error here (the single-image path, lib/fast_rcnn/test.py, subtracts cfg.PIXEL_MEANS in
@@ -84,13 +92,51 @@ def _check_uint8_feed_config():
     if not np.allclose(np.asarray(cfg.PIXEL_MEANS, np.float64).reshape(-1), built, rtol=0, atol=1e-6):
         raise ValueError("cfg.PIXEL_MEANS = %s, but the uint8 batch feed of libctpn_hip.so subtracts %s in its first kernel; use ctpn/demo.py's "
                          "float-blob path for other means" % (np.asarray(cfg.PIXEL_MEANS).reshape(-1).tolist(), built.tolist()))
-    # ctpn_detect / ctpn_detect_submit run the proposal layer with the reference's TEST values (csrc/api_detect.hip: 12000, 1000, 0.7, 8) --
-    # ctpn_proposals, the single-image seam, takes them as arguments (lib/fast_rcnn/test.py)
+    # ctpn_detect / ctpn_detect_submit run the proposal layer with the ctx's parameters (ctpn_set_param; defaults: the reference's TEST values
+    # 12000, 1000, 0.7, 8), which run() sets from `params` -- ctpn_proposals, the single-image seam, takes cfg.TEST.RPN_* as arguments
+    # (lib/fast_rcnn/test.py). The two paths of one run must agree: a cfg.TEST edit that `params` does not carry would reach only one of them
     t = cfg.TEST
     got = (int(t.RPN_PRE_NMS_TOP_N), int(t.RPN_POST_NMS_TOP_N), float(t.RPN_NMS_THRESH), float(t.RPN_MIN_SIZE))
-    if got != (12000, 1000, 0.7, 8.0):
+    used = tuple(ty((params or {}).get(n, B.param_default(n))) for n, ty in zip(RPN_PARAM_NAMES, (int, int, float, float)))
+    if got != used:
         raise ValueError("cfg.TEST.RPN_PRE_NMS_TOP_N / RPN_POST_NMS_TOP_N / RPN_NMS_THRESH / RPN_MIN_SIZE = %r, but the batched path "
-                         "(ctpn_detect) runs the proposal layer with (12000, 1000, 0.7, 8); ctpn/demo.py's single-image path takes any values" % (got,))
+                         "(ctpn_detect) runs the proposal layer with %r; pass the values as run(..., params=rpn_params_from_cfg()) as main() does, "
+                         "or use ctpn/demo.py's single-image path, which reads cfg.TEST" % (got, used))
+
+
+def rpn_params_from_cfg():
+    """cfg.TEST.RPN_* (the loaded text.yml) as tail parameters of the batched path"""
+    t = cfg.TEST
+    return {"RPN_PRE_NMS_TOP_N": int(t.RPN_PRE_NMS_TOP_N), "RPN_POST_NMS_TOP_N": int(t.RPN_POST_NMS_TOP_N), "RPN_NMS_THRESH": float(t.RPN_NMS_THRESH),
+            "RPN_MIN_SIZE": float(t.RPN_MIN_SIZE)}
+
+
+def parse_connector_args(items):
+    """['NAME=VALUE', ...] (--connector) -> {name: float}; names are the connector's parameters (B.CONNECTOR_PARAM_NAMES)"""
+    out = {}
+    for it in items or []:
+        name, sep, value = it.partition("=")
+        if not sep or name not in B.CONNECTOR_PARAM_NAMES:
+            raise ValueError("--connector wants NAME=VALUE with NAME one of %s, got %r" % (", ".join(B.CONNECTOR_PARAM_NAMES), it))
+        out[name] = float(value)
+    return out
+
+
+def _set_tail_params(net, params):
+    """The run's tail parameters into its ctx: `params` over the defaults. Called behind ensure_capacity, which may have replaced the ctx.
+    A run without params touches nothing unless an earlier run on this net left parameters behind (then they go back to the defaults)."""
+    if params is None and not getattr(net, "_tail_params_set", False):
+        return
+    for name in B.param_names():
+        net.ctx.set_param(name, (params or {}).get(name, B.param_default(name)))
+    net._tail_params_set = params is not None
+
+
+def _text_detector(params):
+    """the single-image path's detector under the connector values of `params` (none: the plain TextDetector())"""
+    from ctpn_amd.lib.text_connector.detectors import TextDetector
+    conn = {k: v for k, v in (params or {}).items() if k in B.CONNECTOR_PARAM_NAMES}
+    return TextDetector(config=conn) if conn else TextDetector()
 
 
 def _load(name):
@@ -166,7 +212,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
     return k
 
 
-def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32):
+def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -208,6 +254,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             jobs.append(((h, w), "jpg" if layout[0] > 0 else ("png" if layout == PNG else "host"), f, rs, members[i:i + batch]))
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
+        _set_tail_params(net, params)
     results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_host": 0, "crops": 0}
     dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
     crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images
@@ -305,9 +352,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     for nm in singles:
         img, scale = _load(nm)
         from ctpn_amd.lib.fast_rcnn.test import test_ctpn
-        from ctpn_amd.lib.text_connector.detectors import TextDetector
         scores, boxes = test_ctpn(None, net, img)
-        results[nm] = TextDetector().detect(boxes, scores[:, np.newaxis], img.shape[:2])
+        results[nm] = _text_detector(params).detect(boxes, scores[:, np.newaxis], img.shape[:2])
         meta[nm] = (img, scale)
         if crops_dir:
             stats["crops"] += write_crops(net.ctx, crops_dir, [nm], [results[nm]], crop_h, images=img[None])
@@ -324,15 +370,19 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host", crops_dir=None, crop_h=32):
+        encode="host", crops_dir=None, crop_h=32, params=None):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
     (ctpn_write_annotated_files); 'host' (default): every image through Pillow, as before.
     crops_dir (needs decode='gpu'): every detected line also as a rectified crop of height crop_h, <stem>_<k>.jpg in that directory, cut out
-    on the device at collect time (write_crops); None (default): nothing changes."""
+    on the device at collect time (write_crops); None (default): nothing changes.
+    params: {name: value} of the detection tail (ctpn_set_param: RPN_* and the connector's names) for the ctx of this run; the connector's
+    also reach the images that take the single-image path. None: the defaults."""
     from concurrent.futures import ThreadPoolExecutor
-    _check_uint8_feed_config()
+    _check_uint8_feed_config(params)
+    if params:
+        parse_connector_args(["%s=%r" % (k, float(v)) for k, v in params.items() if k not in RPN_PARAM_NAMES])      # unknown names: an error before any work
     if encode not in ("host", "gpu"):
         raise ValueError("encode must be 'host' or 'gpu'")
     if encode == "gpu" and decode != "gpu":
@@ -342,14 +392,15 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
-        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h)
+        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params)
     if decode_procs > 0 or decode_pool is not None:
-        return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool)
+        return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
     jobs, singles, _ = plan(names, batch)
     if jobs:      # one ctx for the whole run: largest batch x largest shape
         net.ensure_capacity(max(len(m) for _, m in jobs), max(s[0] for s, _ in jobs), max(s[1] for s, _ in jobs))
+        _set_tail_params(net, params)
     results, meta = {}, {}
     t0 = time.time()
     pending = None
@@ -381,9 +432,8 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     for nm in singles:
         img, scale = meta[nm]
         from ctpn_amd.lib.fast_rcnn.test import test_ctpn
-        from ctpn_amd.lib.text_connector.detectors import TextDetector
         scores, boxes = test_ctpn(None, net, img)
-        results[nm] = TextDetector().detect(boxes, scores[:, np.newaxis], img.shape[:2])
+        results[nm] = _text_detector(params).detect(boxes, scores[:, np.newaxis], img.shape[:2])
     dt = time.time() - t0
     for nm in names:
         img, scale = meta[nm]
@@ -396,7 +446,7 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     return results
 
 
-def _run_procs(net, names, out_dir, batch, mode, write_images, log, procs, pool=None):
+def _run_procs(net, names, out_dir, batch, mode, write_images, log, procs, pool=None, params=None):
     from multiprocessing import shared_memory
     own_pool = pool is None
     if own_pool:
@@ -407,6 +457,7 @@ def _run_procs(net, names, out_dir, batch, mode, write_images, log, procs, pool=
     results, meta = {}, {}
     if jobs:
         net.ensure_capacity(max(len(m) for _, m in jobs), max(s[0] for s, _ in jobs), max(s[1] for s, _ in jobs))
+        _set_tail_params(net, params)
     nbytes = max([len(m) * s[0] * s[1] * 3 for s, m in jobs] + [1])
     NB = 4                                                                                  # batches k + 1, k + 2 decode, k is on the GPU, k - 1's pixels are still referenced
     shms = [shared_memory.SharedMemory(create=True, size=nbytes) for _ in range(NB)]
@@ -451,9 +502,8 @@ def _run_procs(net, names, out_dir, batch, mode, write_images, log, procs, pool=
     for nm in singles:
         img, scale = _load(nm)
         from ctpn_amd.lib.fast_rcnn.test import test_ctpn
-        from ctpn_amd.lib.text_connector.detectors import TextDetector
         scores, boxes = test_ctpn(None, net, img)
-        results[nm] = TextDetector().detect(boxes, scores[:, np.newaxis], img.shape[:2])
+        results[nm] = _text_detector(params).detect(boxes, scores[:, np.newaxis], img.shape[:2])
         meta[nm] = (img, scale)
     dt = time.time() - t0
     for nm in names:
@@ -469,7 +519,7 @@ def _run_procs(net, names, out_dir, batch, mode, write_images, log, procs, pool=
     return results
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--input', default='data/demo', help='directory or glob of images')
     ap.add_argument('--out', default='data/results')
@@ -488,7 +538,22 @@ def main(argv=None):
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
                          "throughput choice (3.2 x split's rate, outside the 1e-3 / 1 px bar)")
-    args = ap.parse_args(argv)
+    ap.add_argument('--connector', action='append', default=[], metavar='NAME=VALUE', type=_connector_item,
+                    help="a threshold of the text-line connector (the reference's TextLineCfg; repeatable): " + ", ".join(B.CONNECTOR_PARAM_NAMES) +
+                         ". Sets the ctx's parameters for the batches and the detector of the single-image path")
+    return ap
+
+
+def _connector_item(text):
+    try:
+        parse_connector_args([text])
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     yml = 'ctpn/text.yml' if os.path.exists('ctpn/text.yml') else os.path.join(os.path.dirname(os.path.abspath(__file__)), 'text.yml')
     cfg_from_file(yml)
     if args.precision:
@@ -499,7 +564,8 @@ def main(argv=None):
     if not names:
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
-        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, crops_dir=args.crops, crop_h=args.crop_height)
+        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, crops_dir=args.crops, crop_h=args.crop_height,
+        params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)))
     net.close()
 
 

@@ -27,7 +27,9 @@ Scene = collections.namedtuple("Scene", "name rois h w scale")
 Case = collections.namedtuple("Case", "name seed h w scale lines kind")
 
 # name, seed, h, w, scale, lines, kind. "mixed": the recipe above; "full": no low scores, cut at exactly 1000 rois; "long": every line spans the
-# whole width with one proposal in every column; "low": nothing above 0.7; "empty": no rois at all.
+# whole width with one proposal in every column; "low": nothing above 0.7; "empty": no rois at all; "deep": `lines` disjoint boxes 2 px apart in
+# ONE column with strictly descending scores (all kept), and a lower-scored near-duplicate (IoU 0.875 with its original, disjoint from every
+# other box) of four in five of them, in shuffled score order: each is suppressed by one kept box alone, at every depth of the kept list.
 CASES = [
     Case("g0", 1, 600, 900, 1.0, 12, "mixed"),                  # g0 .. g5: one geometry, the batch tests take them together
     Case("g1", 2, 600, 900, 1.25, 20, "mixed"),
@@ -43,6 +45,7 @@ CASES = [
     Case("big_scale", 12, 352, 1000, 4.5, 10, "mixed"),         # scale above 4: the generic NMS kernel
     Case("low", 13, 600, 900, 1.0, 4, "low"),
     Case("empty", 14, 600, 900, 1.0, 0, "empty"),
+    Case("deep", 15, 608, 64, 1.0, 300, "deep"),                # one column that keeps 300 boxes: the column NMS's kept list past its LDS capacity
 ]
 BATCH_NAMES = ["g0", "g1", "g2", "g3", "g4", "g5"]
 # not in CASES (the oracle, like the reference, raises IndexError on it): g0's rois with a scale below 1, boxes / scale beyond the image
@@ -124,11 +127,16 @@ def make_scene(case):
             slope = float(rng.choice([-1.0, 1.0]) * rng.choice([0.01, 0.02, 0.03]))
             cy = band_h * li + band_h / 2.0 - slope * ncol / 2.0
             _line(rng, rows, 0, ncol - 1, cy, hh, slope, LEVELS[-6:], second=0.3 if li == 0 else 0.0, missing=0.02 if li % 2 else 0.0, wobble=False)
+    elif kind == "deep":
+        ys = 2.0 * np.arange(lines)
+        rows += [[sc, 32.0, y, 47.0, y + 1.0] for sc, y in zip(np.linspace(0.99, 0.80, lines), ys)]
+        dup = rng.permutation(ys[np.arange(lines) % 5 != 0])
+        rows += [[sc, 32.0, y, 47.0, y + 0.75] for sc, y in zip(np.linspace(0.79, 0.71, dup.size), dup)]
     r = np.array(rows, np.float32).reshape(-1, 5)
     n = r.shape[0]
     if kind == "low":
         r[:, 0] = rng.choice(LOW, n)
-    elif kind != "full" and n:
+    elif kind not in ("full", "deep") and n:
         low = rng.random(n) < (0.03 if kind == "long" else 0.1)       # (a long line must not lose three columns in a row)
         r[low, 0] = rng.choice(LOW, int(low.sum()))
     r[:, 2] = np.maximum(r[:, 2], 0)
@@ -157,6 +165,49 @@ def prefix_dets(scene):
 def oracle_keep(scene):
     d = prefix_dets(scene)
     return P.nms(d, P.Cfg.TEXT_PROPOSALS_NMS_THRESH) if d.shape[0] else []
+
+
+def sole_suppressor_depths(dets, keep, thresh, col_scale=1.0):
+    """dets: rows [x1, y1, x2, y2, score] in descending score order, keep: the oracle's greedy NMS of them. For every dropped row that exactly
+    ONE kept row before it overlaps above the threshold (the oracle's fp32 IoU): that kept row's position among the kept rows of its own 16-px
+    column -- how deep into a column's kept list a column NMS has to look to drop it. -> sorted list"""
+    d = np.asarray(dets, np.float32)
+    keep = np.asarray(keep, np.int64)
+    area = (d[:, 2] - d[:, 0] + 1) * (d[:, 3] - d[:, 1] + 1)
+    col = (d[:, 0] * np.float32(col_scale) + np.float32(0.5)).astype(np.int64) >> 4
+    depth = {int(k): int(np.count_nonzero(col[keep[:i]] == col[k])) for i, k in enumerate(keep)}
+    out = []
+    for r in np.setdiff1d(np.arange(d.shape[0]), keep):
+        k = keep[keep < r]
+        w = np.maximum(np.float32(0), np.minimum(d[r, 2], d[k, 2]) - np.maximum(d[r, 0], d[k, 0]) + 1)
+        h = np.maximum(np.float32(0), np.minimum(d[r, 3], d[k, 3]) - np.maximum(d[r, 1], d[k, 1]) + 1)
+        over = k[w * h / (area[r] + area[k] - w * h) > np.float32(thresh)]
+        if over.size == 1:
+            out.append(depth[int(over[0])])
+    return sorted(out)
+
+
+def deep_heads(hf=20, wf=4, kept=150, dups=50, seed=16):
+    """network heads for ONE image of hf x wf cells whose column 0 decodes to `kept` boxes of 8 px stepping 2 px (IoU 7 / 11 < 0.7: all
+    survive, strictly descending scores) and `dups` lower-scored boxes of 7.5 px on top of the LAST `dups` of them (IoU 0.94 with that one,
+    at most 0.67 with its neighbours), assigned to the column's hf x 10 anchors in shuffled order; the other columns decode below min_size.
+    -> cls_prob (1, hf, wf, 20), bbox_pred (1, hf, wf, 40), im_info (3,): the proposal layer's inputs"""
+    assert kept + dups == hf * 10 and 2 * kept + 8 < 16 * hf
+    anc = P.anchors().astype(np.float64)
+    cls = np.zeros((1, hf, wf, 10, 2), np.float32)
+    box = np.zeros((1, hf, wf, 10, 4), np.float32)
+    t = np.arange(kept - dups, kept)
+    y1 = np.concatenate([2.0 * np.arange(kept), 2.0 * t])
+    ph = np.concatenate([np.full(kept, 8.0), np.full(dups, 7.5)])
+    score = np.concatenate([np.linspace(0.99, 0.6, kept), np.linspace(0.5, 0.3, dups)])
+    for j, cell in enumerate(np.random.default_rng(seed).permutation(hf * 10)):
+        y, a = divmod(int(cell), 10)
+        h = anc[a, 3] - anc[a, 1] + 1.0
+        box[0, y, 0, a] = [0.0, (y1[j] + ph[j] / 2.0 - (16 * y + anc[a, 1] + 0.5 * h)) / h, 0.0, np.log(ph[j] / h)]
+        cls[0, y, 0, a] = [1.0 - score[j], score[j]]
+    box[0, :, 1:, :, 3] = np.log(2.0 / (anc[:, 3] - anc[:, 1] + 1.0))
+    cls[0, :, 1:] = [0.9, 0.1]
+    return cls.reshape(1, hf, wf, 20), box.reshape(1, hf, wf, 40), np.array([16.0 * hf, 16.0 * wf, 1.0], np.float32)
 
 
 def oracle_lines(scene, mode):

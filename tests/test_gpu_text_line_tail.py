@@ -15,7 +15,7 @@ asserted there within rtol 3e-7 / atol 1e-5.
     g3          219    32 / 35           beyond      553    10 / 11     (longest chain 263)
     g4          253    31 / 31           big_scale   123    10 / 10
     g5          158    17 / 18           low, empty    0     0 / 0
-    wide        553    72 / 81
+    wide        553    72 / 81           deep        300     0 / 0      (one column)
 """
 import functools
 
@@ -25,6 +25,7 @@ import pytest
 import ctpn_amd
 from ctpn_amd import _binding as B
 import lines_scenes as S
+from oracle import postproc as P
 
 pytestmark = pytest.mark.gpu
 
@@ -82,6 +83,49 @@ def test_keep_lists_of_every_nms_form_equal_the_oracle(ctx, name):
     for nc in (0, 1, 2, 3):
         _, keeps = run(ctx, [sc], "H", nms_columns=nc, nms_check=1)
         assert np.array_equal(keeps[0], want_keep(name)), (name, nc)
+
+
+def test_kept_list_past_its_lds_capacity(ctx):
+    """scene "deep": one 16-px column that keeps 300 boxes, more than a wave of either column form holds in LDS (48: the one-workgroup form,
+    which re-reads the rest from its spill slice; 256: the multi-workgroup form, which re-reads them from the sorted boxes by kept rank),
+    and dropped candidates whose ONLY suppressor sits past those capacities -- asserted on the oracle's own keep list first, so a form that
+    loses or misreads a kept box beyond its capacity keeps a candidate the oracle drops."""
+    sc = SCENES["deep"]
+    assert sc.scale == 1.0 and np.unique(sc.rois[:, 1]).size == 1                  # one image-scale column
+    keep = S.oracle_keep(sc)
+    depths = S.sole_suppressor_depths(S.prefix_dets(sc), keep, 0.2)
+    print("deep: %d rois, %d kept, %d dropped by one kept box alone, %d of them at depth >= 48, %d at depth >= 256"
+          % (sc.rois.shape[0], len(keep), len(depths), sum(d >= 48 for d in depths), sum(d >= 256 for d in depths)))
+    assert len(keep) > 256
+    assert sum(d >= 48 for d in depths) >= 8 and sum(d >= 256 for d in depths) >= 8          # as tests/test_lines_scenes.py holds the scene to
+    for nc in (0, 1, 2, 3):
+        _, keeps = run(ctx, [sc], "H", nms_columns=nc, nms_check=1)
+        assert np.array_equal(keeps[0], want_keep("deep")), nc
+
+
+def test_proposal_kept_list_past_its_lds_capacity():
+    """the same for the proposal layer's instantiation of the one-workgroup column NMS (128 kept boxes per wave in LDS), through
+    ctpn_proposals_from_host on crafted heads (lines_scenes.deep_heads): column 0 keeps 150 boxes, and 50 candidates are dropped by one
+    kept box alone, 22 of them by a box at kept position >= 128 -- on the oracle first. Every form then returns the oracle's anchors (the
+    keep list, exactly) and its boxes (to the last ulp of exp(), as decode always does)."""
+    cls, box, info = S.deep_heads()
+    boxes, scores, _ = P.decode(cls, box, info)
+    ok = np.where((boxes[:, 2] - boxes[:, 0] + 1 >= 8) & (boxes[:, 3] - boxes[:, 1] + 1 >= 8))[0]
+    order = ok[P.desc_order(scores[ok])]
+    dets = np.hstack([boxes[order], scores[order][:, None]])
+    keep = P.nms(dets, 0.7)
+    depths = S.sole_suppressor_depths(dets, keep, 0.7)
+    print("deep heads: %d candidates, %d kept, %d dropped by one kept box alone, %d of them at depth >= 128"
+          % (order.size, len(keep), len(depths), sum(d >= 128 for d in depths)))
+    assert len(keep) > 128 and np.all(dets[keep, 0] < 16) and len(keep) < order.size
+    assert sum(d >= 128 for d in depths) >= 8
+    want = P.proposal_layer(cls, box, info)
+    assert np.array_equal(want[:, 1:], dets[keep, :4])
+    for nc in (0, 1, 2, 3):
+        with ctpn_amd.Context(0, 1, int(info[0]), int(info[1]), "fp32", postproc_only=True, options={"nms_columns": nc, "nms_check": 1}) as c:
+            rois, anchors = c.proposals_from_host(cls, box, info, want_anchors=True)
+        assert np.array_equal(anchors[0], order[keep]), nc
+        assert rois[0].shape == want.shape and np.array_equal(rois[0][:, 0], want[:, 0]) and np.abs(rois[0] - want).max() < 1e-3, nc
 
 
 @pytest.mark.parametrize("mode", ["H", "O"])

@@ -82,6 +82,12 @@ def test_committed_scenes_meet_their_conditions(monkeypatch):
     scales = [c.scale for c in S.CASES]
     assert any(np.log2(s) % 1 != 0 and s < 4 for s in scales) and any(s > 4 for s in scales)                    # not a power of two; the generic fallback
     assert any(float(np.float32(s)) != s for s in scales)                                                       # not an fp32 value: where the division is rounded matters
+    # one column whose kept list outgrows the LDS capacity of both column NMS forms (48 and 256 boxes), and candidates that only a kept box
+    # beyond it drops (tests/test_gpu_text_line_tail.py::test_kept_list_past_its_lds_capacity)
+    deep = next(sc for sc in all_scenes() if sc.name == "deep")
+    depths = S.sole_suppressor_depths(S.prefix_dets(deep), S.oracle_keep(deep), P.Cfg.TEXT_PROPOSALS_NMS_THRESH)
+    assert st["deep"]["kept"] > 256 and np.unique(deep.rois[:, 1]).size == 1 and deep.scale == 1.0
+    assert sum(d >= 48 for d in depths) >= 8 and sum(d >= 256 for d in depths) >= 8
     # a line that filter_boxes drops for each of its three reasons alone (detectors.py:37-49), in both modes
     monkeypatch.setattr(P.Cfg, "MIN_RATIO", -1.0)
     monkeypatch.setattr(P.Cfg, "LINE_MIN_SCORE", -1.0)

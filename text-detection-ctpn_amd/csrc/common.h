@@ -85,6 +85,12 @@ int fail(int code, const std::string& s);
       return ::ctpn::fail(CTPN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// the tail of a launcher: the error of the launch just made, if any, as "<what> launch: <HIP's text>"
+inline int launch_status(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? CTPN_OK : fail(CTPN_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Launch state is PER DEVICE: the ABI promises one ctx per GPU, and one process may hold ctxs on several GPUs. The CU count and the
 // "MaxDynamicSharedMemorySize already raised for this kernel" flags are indexed by the current device (a function attribute set on
@@ -203,7 +209,7 @@ int launch_lstm_pre(const void* a, const void* wt_frag, const float* bias, void*
 int launch_lstm_pre_pack(const void* wt_x, void* wt_frag, hipStream_t s);      // [1024][512] 16-bit rows -> the kernel's fragment-major order (1 MB)
 int lstm_gate_col(int c);     // TF gate column (g * 128 + u) -> permuted column, per direction
 int launch_lstm_permute_rows(const void* src, void* dst, int row_bytes, hipStream_t s);
-// proposal pipeline
+// proposal pipeline, one unit per stage: decode.hip, sort_keys.hip, nms.hip (device helpers they share: proposal_dev.h)
 struct ProposalCfg {
   int n, hf, wf;
   int pre_nms_topn, post_nms_topn;
@@ -231,7 +237,7 @@ int launch_nms(const float* sorted_boxes, const float* sorted_scores, const int*
                float* kept_spill /* [n_img][stride][4] scratch */, int n_img, hipStream_t s,
                const int* sorted_anchor = nullptr /* [n_img][stride] */, int* roi_anchor = nullptr /* [n_img][max_keep] */);
 
-// column-decomposed form for the proposal layer's boxes (16 px anchors on a 16 px grid): same result, see proposal.hip.
+// column-decomposed form for the proposal layer's boxes (16 px anchors on a 16 px grid): same result, see nms.hip.
 // PRECONDITION (not checked by nms_columns_ok, which only looks at ncols / stride / thresh): every box lies on the 16-px anchor grid,
 // x1 in [16 c, 16 c + 16) and x2 <= 16 c + 16 for its column c (/ im_scale for the connector variant) -- true for decode_kernel's output
 // (bbox_transform_inv leaves x alone), NOT for arbitrary boxes: those go through launch_nms (the ctpn_nms seam always does).
@@ -243,7 +249,7 @@ int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, co
                        void* mw_scratch = nullptr /* n_img x NMS_MW_SCRATCH_BYTES, zeroed: the multi-workgroup form for small batches (one column per wave) */,
                        const unsigned char* colid = nullptr /* launch_gather_sorted's column ids (needed above 1024 candidates) */,
                        int prefix = 0 /* > 0: try the first `prefix` ranks first (they usually hold max_keep survivors); same result either way */,
-                       int dbg = 0 /* option debug_nms (diagnostic, WRONG proposals): parts mask of nms_columns_kernel<16, ..> (proposal.hip) */);
+                       int dbg = 0 /* option debug_nms (diagnostic, WRONG proposals): parts mask of nms_columns_kernel<16, ..> (nms.hip) */);
 constexpr size_t NMS_MW_SCRATCH_BYTES = 2048;       // per image: survivor mask (one bit per rank) + ticket; zero between launches
 // ... and one STICKY word the kernel sets when a column held more candidates than its list (keep lists are then wrong): zero unless a caller
 // broke launch_nms_columns' precondition; read and cleared by the host (option nms_check). The block's zero state between launches is
@@ -255,7 +261,7 @@ constexpr size_t NMS_MW_FLAG_OFF = 2032;            // prefix pass: "the prefix 
 constexpr int NMS_MW_MAX_BATCH = 4;                 // batches up to this size spread their columns over the machine; larger ones fill it with images
 constexpr int NMS_MW_CAP_BATCH = 32;                // ... unless option nms_columns = 3 asks for the multi-workgroup form explicitly: buffers are sized for this many images
 bool nms_columns_ok(int ncols, int stride, float thresh);
-int launch_hog(unsigned* sink, int n_wg, int usec, int touch, hipStream_t s, const void* src = nullptr, size_t src_bytes = 0);      // diagnostic: the one-workgroup NMS's footprint without its work (proposal.hip)
+int launch_hog(unsigned* sink, int n_wg, int usec, int touch, hipStream_t s, const void* src = nullptr, size_t src_bytes = 0);      // diagnostic: the one-workgroup NMS's footprint without its work (hog.hip)
 bool nms_columns_tl_ok(int ncols, int stride, float thresh, float max_scale);
 
 // The connector's configuration (reference TextLineCfg, lib/text_connector/text_connect_cfg.py:4-12), passed down to the host connector and, by
@@ -288,7 +294,7 @@ int connect_lines(const float* kept_boxes, const float* kept_scores, int n, int 
                   const ConnectorCfg& cfg, std::vector<double>& recs);
 // rois [n_img][post][5] (descending score) -> per image: boxes/scale of the score > min_score prefix + its length
 constexpr int CONN_CAP = 512;   // text lines per image and mode the device connector can return (chains <= proposals / 2 = 500)
-// text-line connector on the device: recs [n_img][2 modes][cap][9] float64, counts [n_img][3] = lines H, lines O, status;
+// text-line connector on the device (connect.hip): recs [n_img][2 modes][cap][9] float64, counts [n_img][3] = lines H, lines O, status;
 // scratch [n_img][1024][20] float64
 int launch_connect(const float* boxes, const float* scores, const int* keep, const int* keep_counts, int stride, const float* im_info,
                    double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s);

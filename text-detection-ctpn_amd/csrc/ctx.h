@@ -337,7 +337,7 @@ static inline int lvl(int v, int level) { for (int i = 0; i < level; ++i) v /= 2
 static inline size_t act_slack_pixels(int w) { return (size_t)28 * (w + 2) + 384; }    // behind (+ 8 rows: the second half of a split tail tile)
 static inline size_t act_front_pixels(int w) { return (size_t)(w + 2) + 64; }          // in front
 
-// the column NMS of a small batch spreads its columns over the machine (proposal.hip: nms_column_groups_kernel); option nms_columns = 2 / 3
+// the column NMS of a small batch spreads its columns over the machine (nms.hip: nms_column_groups_kernel); option nms_columns = 2 / 3
 // pins one form for A/B runs and the tests
 // hf: rows of the feature map (a column holds hf x 10 candidates at most, the kernel's list 1024), 0 for the connector's <= 1024 boxes
 static inline bool nms_multi_wg(const ctpn_ctx* c, int n, int hf) {

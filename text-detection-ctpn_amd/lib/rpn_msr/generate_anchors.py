@@ -1,6 +1,6 @@
 """The 10 fixed-width CTPN anchors (reference lib/rpn_msr/generate_anchors.py:3-32): width 16, heights
 11..283, centre 7.5, int32 truncation toward zero, python-3 true division. The same table is
-baked into the decode kernel (csrc/proposal.hip: c_anchor_y1 / c_anchor_y2); tests check both against the
+baked into the decode kernel (csrc/decode.hip: c_anchor_y1 / c_anchor_y2); tests check both against the
 fixture generated from the reference."""
 import numpy as np
 

@@ -21,7 +21,7 @@ def check_connector_config():
     for name, built in connector_constants().items():
         if abs(float(mine[name]) - built) > 1e-6 * max(1.0, abs(built)):
             raise ValueError("text_connect_cfg.Config: %s = %r, but libctpn_hip.so was built with %r (the connector's constants are compiled "
-                             "in: csrc/text_connector.cpp, csrc/proposal.hip); to run with other values pass them as TextDetector(config=...)" % (name, mine[name], built))
+                             "in: csrc/text_connector.cpp, csrc/connect.hip); to run with other values pass them as TextDetector(config=...)" % (name, mine[name], built))
 
 
 class TextDetector:

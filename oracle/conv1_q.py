@@ -1,7 +1,7 @@
 """ORACLE (test infrastructure only -- never imported by the product path).
 
 Arithmetic specification of how the 16-bit modes compute conv1_1 from the uint8 feed since round 4: the q-image form
-(text-detection-ctpn_amd/csrc/layers.hip: image_to_q_kernel, pack_conv1_frags, conv_first_p_kernel; csrc/conv3x3_wr.h: the producer
+(text-detection-ctpn_amd/csrc/conv_first_q.hip: image_to_q_kernel, pack_conv1_frags, conv_first_p_kernel; csrc/conv3x3_wr.h: the producer
 inside conv3x3_wr_kernel<FUSE>). Restated here in numpy so that the claim "equal to the reference op up to the 16-bit rounding of the 27
 weights and of the output" is checked on the CPU, layer for layer, borders included.
 

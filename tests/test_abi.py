@@ -115,8 +115,8 @@ def test_no_null_stream_memset_in_the_launch_paths(root):
     conv_hdrs = sorted(f for f in os.listdir(src) if f.startswith("conv3x3") and f.endswith(".h"))      # every conv header, whatever is added later
     assert conv_hdrs and not os.path.exists(os.path.join(src, "conv3x3_impl.h"))
     kernel_units = sorted(f for f in os.listdir(src) if f.endswith(".hip") and not f.startswith("api_"))      # every kernel unit, whatever is added later
-    assert {"conv3x3.hip", "igemm.hip", "bilstm.hip", "preprocess.hip", "layers.hip", "decode.hip", "sort_keys.hip", "nms.hip", "connect.hip",
-            "hog.hip"} <= set(kernel_units) and not os.path.exists(os.path.join(src, "proposal.hip"))
+    assert {"conv3x3.hip", "igemm.hip", "bilstm.hip", "preprocess.hip", "conv_first.hip", "conv_first_q.hip", "pack.hip", "decode.hip", "sort_keys.hip", "nms.hip", "connect.hip",
+            "hog.hip"} <= set(kernel_units) and not os.path.exists(os.path.join(src, "proposal.hip")) and not os.path.exists(os.path.join(src, "layers.hip"))
     for f in kernel_units + ["common.h", "proposal_dev.h"] + conv_hdrs:
         text = open(os.path.join(src, f)).read()
         code = re.sub(r"//[^\n]*", "", text)

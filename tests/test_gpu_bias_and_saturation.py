@@ -439,6 +439,28 @@ def test_recurrence_shapes_reach_every_form():
         assert {lstm_pre_form(p, sh[0] * (sh[1] // 16) * (sh[2] // 16)) for sh in REC_SHAPES} == {"small", "lds"}, p
 
 
+@pytest.mark.parametrize("prec", ["bf16", "split"])
+def test_both_split_forms_of_the_recurrence_give_one_rows_bits(arenas, prec):
+    """bilstm_split_kernel and bilstm_split_few_kernel call one copy of the Wh fragment build, the h reads and the 48 MFMAs (csrc/bilstm.hip):
+    every image's lstm_out in a batch of nine (135 rows, T = 4: the 16-row form, last workgroup ragged) equals the bits of that image forwarded
+    alone (15 rows: the four-row form, last workgroup ragged), with fp16 pre-activations (bf16) and fp32 ones (split precision). lstm_out of a
+    whole forward also needs every layer in front of the recurrence to give a batch the bits of its images alone (the conv dispatch, lstm_pre's
+    forms); test_recurrence_on_the_devices_own_pre_activations holds each form of the recurrence to the oracle on the device's own lstm_pre."""
+    n, h, wd = shape = (9, 240, 64)
+    assert recurrent_form(prec, 1, n * (h // 16))[0] == "split_16" and recurrent_form(prec, 1, h // 16)[0] == "split_few"
+    arena = arenas["biased"][0]
+    imgs = ctpn_amd.weights.synthetic_images(n, h, wd, 29)
+    with ctx_for(arena, shape, prec, keep_acts=1) as ctx:
+        assert ctx.get_option("lstm_split") == 1
+        ctx.forward(imgs)
+        batch = ctx.get_tensor("lstm_out")
+    assert batch.shape == (n, h // 16, wd // 16, 256) and np.isfinite(batch).all() and np.abs(batch).max() > 0
+    with ctx_for(arena, (1, h, wd), prec, keep_acts=1) as ctx:
+        for i in range(n):
+            ctx.forward(imgs[i:i + 1])
+            assert np.array_equal(ctx.get_tensor("lstm_out")[0], batch[i]), i
+
+
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("shape", REC_SHAPES, ids=shape_id)
 @pytest.mark.parametrize("prec,lstm_split", REC_MODES)

@@ -865,7 +865,7 @@ def test_column_nms_variants_equal_generic_nms(arena, n, h, w, scale):
 def test_conv1_exact_pixel_kernel(arena, weights, shape):
     """conv1_1 from the q-image (default for the uint8 feed in the 16-bit modes; stored by conv_first_p_kernel under keep_acts, computed inside
     conv1_2's window stage otherwise): pixels enter the MFMA as exact integers p - round(mean), the fractional part of the mean rides on
-    the pixels' inside-the-image slots (layers.hip, pack_conv1_frags). Its only inexactness is the bf16
+    the pixels' inside-the-image slots (conv_first_q.hip, pack_conv1_frags). Its only inexactness is the bf16
     rounding of the 27 weights -- so it must reproduce the fp32 oracle conv evaluated with bf16-ROUNDED weights to fp32-class
     accuracy (bf16 outputs equal except rounding-boundary flips), on interior and on every border / corner pixel."""
     n, h, w = shape

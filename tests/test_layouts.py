@@ -94,7 +94,7 @@ def _b32_cycles(addr_of_lane):
 
 
 def test_conv_first_plane_copies_sit_on_complementary_banks():
-    """csrc/layers.hip conv_first_mfma_kernel: lane l31 reads 4 dwords at element 3 * l31 (+ 8 for lanes 32..63) of a bf16 plane,
+    """csrc/conv_first.hip conv_first_mfma_kernel: lane l31 reads 4 dwords at element 3 * l31 (+ 8 for lanes 32..63) of a bf16 plane,
     even lanes from copy A, odd lanes from copy B (one element later, CF_PLANE elements further): with (CF_PLANE / 2) % 32 == 14
     the odd lanes' dwords fall on the 16 banks the even lanes leave free."""
     CF_ROW_B, CF_NEL = 198, 6 * 198

@@ -186,19 +186,12 @@ __device__ __forceinline__ void lstm_split(float v, uint32_t& hi, uint32_t& lo) 
   lo = ctpn_cvt_pk_bf16(v - __builtin_bit_cast(float, hi << 16), 0.f) & 0xffffu;
 }
 
-template <bool PRE16>
-__global__ __launch_bounds__(512) void bilstm_split_kernel(const void* __restrict__ xp, const float* __restrict__ wh,
-                                                           float* __restrict__ out, int rows, int T) {
-  __shared__ __attribute__((aligned(16))) uint16_t hb[2][2][LSTM_ROWS][LSTM_BPITCH];   // [buffer][hi|lo][row][k]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int dir = blockIdx.y;
-  const int r = lane & 15, q4 = lane >> 4;
-  const int ucol = 16 * wave + r;           // A operand row: this lane's unit
-  const float* whd = wh + (size_t)dir * 128 * 512;
+// What bilstm_split_kernel and bilstm_split_few_kernel share, one copy each: they must give the same bits for the same row, and from here to
+// the gate pre-activations they run the same code.
+typedef uint16_t LstmHb[2][2][LSTM_ROWS][LSTM_BPITCH];      // h in LDS: [buffer][hi|lo][row][k]
 
-  // Wh fragments: wa[g][kk][part] = 8 bf16 of Wh[k = 32 kk + 8 q4 + j][g * 128 + ucol], j = 0..7
-  uint4 wa[4][4][2];
+// Wh fragments: wa[g][kk][part] = 8 bf16 of Wh[k = 32 kk + 8 q4 + j][g * 128 + ucol], j = 0..7
+__device__ __forceinline__ void lstm_split_wh(const float* whd, int q4, int ucol, uint4 (&wa)[4][4][2]) {
 #pragma unroll
   for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -209,7 +202,42 @@ __global__ __launch_bounds__(512) void bilstm_split_kernel(const void* __restric
       wa[g][kk][0] = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
       wa[g][kk][1] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
     }
+}
+__device__ __forceinline__ void lstm_zero_hb(LstmHb& hb, int tid) {
   for (int i = tid; i < 2 * 2 * LSTM_ROWS * LSTM_BPITCH / 2; i += 512) ((uint32_t*)&hb[0][0][0][0])[i] = 0u;
+}
+// acc[g] += Wh h_{t-1}, gate g: the h_{t-1} fragments (B operand: lane reads h[row = lane & 15][k = 32 kk + 8 q4 .. + 7], hi and lo planes of
+// buffer `cur`), then the 48 MFMAs
+__device__ __forceinline__ void lstm_split_wh_h(const LstmHb& hb, int cur, int r, int q4, const uint4 (&wa)[4][4][2], f32x4 (&acc)[4]) {
+  uint4 hh[4], hl[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    hh[kk] = *(const uint4*)(&hb[cur][0][r][32 * kk + 8 * q4]);
+    hl[kk] = *(const uint4*)(&hb[cur][1][r][32 * kk + 8 * q4]);
+  }
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+    for (int term = 0; term < 3; ++term)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)      // four independent accumulator chains
+        acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lstm_bf16x8, wa[g][kk][term == 0 ? 1 : 0]),
+                                                         __builtin_bit_cast(lstm_bf16x8, term == 1 ? hl[kk] : hh[kk]), acc[g], 0, 0, 0);
+}
+
+template <bool PRE16>
+__global__ __launch_bounds__(512) void bilstm_split_kernel(const void* __restrict__ xp, const float* __restrict__ wh,
+                                                           float* __restrict__ out, int rows, int T) {
+  __shared__ __attribute__((aligned(16))) LstmHb hb;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int dir = blockIdx.y;
+  const int r = lane & 15, q4 = lane >> 4;
+  const int ucol = 16 * wave + r;           // A operand row: this lane's unit
+  const float* whd = wh + (size_t)dir * 128 * 512;
+  uint4 wa[4][4][2];
+  lstm_split_wh(whd, q4, ucol, wa);
+  lstm_zero_hb(hb, tid);
 
   const int row_l = r;
   const int row_g = blockIdx.x * LSTM_ROWS + row_l;
@@ -237,21 +265,7 @@ __global__ __launch_bounds__(512) void bilstm_split_kernel(const void* __restric
       const int tn = dir ? t - 1 : t + 1;
       lstm_load_pre<PRE16>(xrow, (size_t)tn, praw);
     }
-    // h_{t-1} fragments (B operand): lane reads h[row = lane & 15][k = 32 kk + 8 q4 .. + 7], hi and lo planes
-    uint4 hh[4], hl[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      hh[kk] = *(const uint4*)(&hb[cur][0][r][32 * kk + 8 * q4]);
-      hl[kk] = *(const uint4*)(&hb[cur][1][r][32 * kk + 8 * q4]);
-    }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-      for (int term = 0; term < 3; ++term)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)      // four independent accumulator chains
-          acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lstm_bf16x8, wa[g][kk][term == 0 ? 1 : 0]),
-                                                           __builtin_bit_cast(lstm_bf16x8, term == 1 ? hl[kk] : hh[kk]), acc[g], 0, 0, 0);
+    lstm_split_wh_h(hb, cur, r, q4, wa, acc);
     f32x4 h;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -278,7 +292,8 @@ __global__ __launch_bounds__(512) void bilstm_split_kernel(const void* __restric
 // with fewer rows (the 16 x 16 tile's columns are the rows), the gate phase does: here a workgroup takes FOUR rows, so only lanes
 // (lane & 15) < 4 hold valid sums after the MFMAs -- 4 units x 4 gates each -- and one DPP row shift per gate hands units 1 .. 3 to the
 // twelve idle lanes of the 16-lane row: every lane then runs the cell update of ONE (row, unit): 10 transcendentals instead of 40. Same
-// MFMA sequence, same gate formulas, same split of h: bit-identical to bilstm_split_kernel (tests/test_gpu_round6.py). 37 rows are 10
+// MFMA sequence (lstm_split_wh_h, one copy), same gate formulas, same split of h: bit-identical to bilstm_split_kernel
+// (tests/test_gpu_round6.py). 37 rows are 10
 // workgroups per direction instead of 3.
 // ---------------------------------------------------------------------------------------------
 constexpr int LSTM_FEW = 4;
@@ -289,7 +304,7 @@ __device__ __forceinline__ float lstm_row_shr(float v) {      // lane i of a 16-
 template <bool PRE16>
 __global__ __launch_bounds__(512) void bilstm_split_few_kernel(const void* __restrict__ xp, const float* __restrict__ wh,
                                                                float* __restrict__ out, int rows, int T) {
-  __shared__ __attribute__((aligned(16))) uint16_t hb[2][2][LSTM_ROWS][LSTM_BPITCH];   // [buffer][hi|lo][row][k]; rows >= LSTM_FEW stay zero
+  __shared__ __attribute__((aligned(16))) LstmHb hb;      // rows >= LSTM_FEW stay zero
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int dir = blockIdx.y;
@@ -297,17 +312,8 @@ __global__ __launch_bounds__(512) void bilstm_split_few_kernel(const void* __res
   const int ucol = 16 * wave + r;
   const float* whd = wh + (size_t)dir * 128 * 512;
   uint4 wa[4][4][2];
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      uint32_t hi[8], lo[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) lstm_split(whd[(size_t)(32 * kk + 8 * q4 + j) * 512 + g * 128 + ucol], hi[j], lo[j]);
-      wa[g][kk][0] = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
-      wa[g][kk][1] = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
-    }
-  for (int i = tid; i < 2 * 2 * LSTM_ROWS * LSTM_BPITCH / 2; i += 512) ((uint32_t*)&hb[0][0][0][0])[i] = 0u;
+  lstm_split_wh(whd, q4, ucol, wa);
+  lstm_zero_hb(hb, tid);
 
   // MFMA column r < LSTM_FEW: the lane that LOADS the pre-activations of (row r, units u0 .. u0 + 3); after the redistribution lane r'
   // owns (row r' & 3, unit u0 + (r' >> 2))
@@ -335,20 +341,7 @@ __global__ __launch_bounds__(512) void bilstm_split_few_kernel(const void* __res
     f32x4 acc[4];
     lstm_pre_values<PRE16>(praw, acc);
     if (s + 1 < T && ld) lstm_load_pre<PRE16>(xrow, (size_t)(dir ? t - 1 : t + 1), praw);
-    uint4 hh[4], hl[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      hh[kk] = *(const uint4*)(&hb[cur][0][r][32 * kk + 8 * q4]);
-      hl[kk] = *(const uint4*)(&hb[cur][1][r][32 * kk + 8 * q4]);
-    }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-      for (int term = 0; term < 3; ++term)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(lstm_bf16x8, wa[g][kk][term == 0 ? 1 : 0]),
-                                                           __builtin_bit_cast(lstm_bf16x8, term == 1 ? hl[kk] : hh[kk]), acc[g], 0, 0, 0);
+    lstm_split_wh_h(hb, cur, r, q4, wa, acc);
     // gate g of (row r & 3, unit u0 + esel): element esel of lane (r & 3)'s accumulator, i.e. of the lane 4 esel to the left in this row
     float z[4];
 #pragma unroll
@@ -382,35 +375,20 @@ __global__ __launch_bounds__(256) void lstm_permute_rows_kernel(const char* __re
 int launch_lstm_permute_rows(const void* src, void* dst, int row_bytes, hipStream_t s) {
   if (row_bytes <= 0 || row_bytes % 4) return fail(CTPN_ERR_ARG, "lstm_permute_rows: row_bytes must be a positive multiple of 4");
   hipLaunchKernelGGL(lstm_permute_rows_kernel, dim3(1024), dim3(256), 0, s, (const char*)src, (char*)dst, row_bytes);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("lstm_permute_rows launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("lstm_permute_rows");
 }
 
 int launch_bilstm(const void* xp, int xp_is_f16, const float* wh, float* out, int rows, int T, hipStream_t s, int split_bf16, int fast_gates) {
   if (rows <= 0 || T <= 0) return fail(CTPN_ERR_ARG, "bilstm: empty problem");
-  dim3 grid((rows + LSTM_ROWS - 1) / LSTM_ROWS, 2);
+  typedef void (*Kernel)(const void*, const float*, float*, int, int);
+  static const Kernel kernels[4][2] = {      // [form][xp_is_f16]
+      {bilstm_kernel<false, false>, bilstm_kernel<false, true>}, {bilstm_kernel<true, false>, bilstm_kernel<true, true>},
+      {bilstm_split_kernel<false>, bilstm_split_kernel<true>}, {bilstm_split_few_kernel<false>, bilstm_split_few_kernel<true>}};
+  int form = split_bf16 ? 2 : (fast_gates ? 1 : 0), per_wg = LSTM_ROWS;
   // a few rows (one or two 600 x 900 images: 37 / 74): four rows per workgroup, the gate math spread over all lanes; identical bits
-  if (split_bf16 && rows <= 128) {
-    dim3 gf((rows + LSTM_FEW - 1) / LSTM_FEW, 2);
-    if (xp_is_f16) hipLaunchKernelGGL(bilstm_split_few_kernel<true>, gf, dim3(512), 0, s, xp, wh, out, rows, T);
-    else hipLaunchKernelGGL(bilstm_split_few_kernel<false>, gf, dim3(512), 0, s, xp, wh, out, rows, T);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("bilstm launch: ") + hipGetErrorString(e));
-    return CTPN_OK;
-  }
-  if (xp_is_f16) {
-    if (split_bf16) hipLaunchKernelGGL(bilstm_split_kernel<true>, grid, dim3(512), 0, s, xp, wh, out, rows, T);
-    else if (fast_gates) hipLaunchKernelGGL((bilstm_kernel<true, true>), grid, dim3(512), 0, s, xp, wh, out, rows, T);
-    else hipLaunchKernelGGL((bilstm_kernel<false, true>), grid, dim3(512), 0, s, xp, wh, out, rows, T);
-  } else {
-    if (split_bf16) hipLaunchKernelGGL(bilstm_split_kernel<false>, grid, dim3(512), 0, s, xp, wh, out, rows, T);
-    else if (fast_gates) hipLaunchKernelGGL((bilstm_kernel<true, false>), grid, dim3(512), 0, s, xp, wh, out, rows, T);
-    else hipLaunchKernelGGL((bilstm_kernel<false, false>), grid, dim3(512), 0, s, xp, wh, out, rows, T);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("bilstm launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  if (split_bf16 && rows <= 128) { form = 3; per_wg = LSTM_FEW; }
+  hipLaunchKernelGGL(kernels[form][xp_is_f16 ? 1 : 0], dim3((rows + per_wg - 1) / per_wg, 2), dim3(512), 0, s, xp, wh, out, rows, T);
+  return launch_status("bilstm");
 }
 
 }  // namespace ctpn

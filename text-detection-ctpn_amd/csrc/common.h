@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -91,6 +92,18 @@ inline int launch_status(const char* what) {
   return e == hipSuccess ? CTPN_OK : fail(CTPN_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
 }
 
+// fp32 <-> one 16-bit value on the host: RNE, a NaN stays a NaN (ctpn_get_tensor, ctpn_debug_conv3x3; the hi / lo halves of pack_conv1_frags
+// and of conv_first.hip's LUT)
+static inline float host_bf16_to_f32(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; std::memcpy(&f, &u, 4); return f; }
+static inline float host_f16_to_f32(uint16_t b) { _Float16 h; std::memcpy(&h, &b, 2); return (float)h; }
+static inline uint16_t host_f32_to_bf16(float f) {
+  uint32_t u; std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+static inline uint16_t host_f32_to_f16(float f) { const _Float16 h = (_Float16)f; uint16_t b; std::memcpy(&b, &h, 2); return b; }
+
 // ---------------------------------------------------------------------------------------------
 // Launch state is PER DEVICE: the ABI promises one ctx per GPU, and one process may hold ctxs on several GPUs. The CU count and the
 // "MaxDynamicSharedMemorySize already raised for this kernel" flags are indexed by the current device (a function attribute set on
@@ -178,7 +191,7 @@ static inline const void* conv1_p_frags(const void* frags, DType t) { return (co
 int pack_conv1_frags(const float* w27x64_dev, const float* bias_dev, uint4* frags_dev);
 // ---- the q-image: the uint8 feed of the 16-bit modes as 8-byte pixels (q_B, q_G, q_R, P) of the mode's 16-bit type, q_c = p_c - round(mean_c)
 // (an integer, exact in bf16 and fp16), P = 1.0; image pixel (y, x) sits at q pixel (y + 2, x + 2) of an Hq x Wq map whose other pixels are
-// all-zero -- TF's SAME padding of conv1_1 AND the inside-the-image indicator its mean correction needs (layers.hip). 4.4 MB per 600 x 900
+// all-zero -- TF's SAME padding of conv1_1 AND the inside-the-image indicator its mean correction needs (conv_first_q.hip). 4.4 MB per 600 x 900
 // image instead of the 69 MB of conv1_1's output: what conv1_2 reads when conv1_1 is computed inside its window stage (conv3x3_wr.h).
 static inline int conv1_q_h(int h) { return ((h + 7) / 8) * 8 + 4; }
 static inline int conv1_q_w(int w) { return ((w + 63) / 64) * 64 + 8; }

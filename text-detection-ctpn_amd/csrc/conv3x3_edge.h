@@ -232,9 +232,7 @@ static int c3_launch_edge(const void* in, const void* wt, const float* bias, voi
         if (pooled) hipLaunchKernelGGL((conv3x3_edge_kernel<H, true, true, true, 3>), dim3((unsigned)nblk), dim3(64 * 3), 0, s, e);
         else hipLaunchKernelGGL((conv3x3_edge_kernel<H, false, true, true, 3>), dim3((unsigned)nblk), dim3(64 * 3), 0, s, e);
       }
-      hipError_t errk = hipGetLastError();
-      if (errk != hipSuccess) return fail(CTPN_ERR_HIP, std::string("conv3x3 edge launch: ") + hipGetErrorString(errk));
-      return CTPN_OK;
+      return launch_status("conv3x3 edge");
     }
   }
   if (deep) {
@@ -242,8 +240,6 @@ static int c3_launch_edge(const void* in, const void* wt, const float* bias, voi
     else hipLaunchKernelGGL((conv3x3_edge_kernel<H, false, true, SPLIT>), dim3((unsigned)nblk), dim3(64), 0, s, e);
   } else if (pooled) hipLaunchKernelGGL((conv3x3_edge_kernel<H, true, false, SPLIT>), dim3((unsigned)nblk), dim3(64), 0, s, e);
   else hipLaunchKernelGGL((conv3x3_edge_kernel<H, false, false, SPLIT>), dim3((unsigned)nblk), dim3(64), 0, s, e);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(CTPN_ERR_HIP, std::string("conv3x3 edge launch: ") + hipGetErrorString(err));
-  return CTPN_OK;
+  return launch_status("conv3x3 edge");
 }
 }  // namespace ctpn

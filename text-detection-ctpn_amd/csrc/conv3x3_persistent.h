@@ -697,8 +697,6 @@ static int c3_launch_p(Conv3 g, hipStream_t s) {
   auto k = conv3x3_p_kernel<T, T, FLAT, POOL, TW, SPLIT, BN_T, BM_T, HT32>;
   if ((rc = raise_dynamic_lds((const void*)k, C3_LDS_MAX, attr, dev))) return rc;
   hipLaunchKernelGGL(k, dim3((unsigned)workers), dim3(512), lds, s, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("conv3x3_p launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("conv3x3_p");
 }
 }  // namespace ctpn

@@ -317,8 +317,6 @@ static int c3_launch(Conv3 g, hipStream_t s) {
   int dev = 0, rc;
   if ((rc = current_device(dev)) || (rc = raise_dynamic_lds((const void*)k, C3_LDS_MAX, attr, dev))) return rc;
   hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(NTHR), lds, s, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("conv3x3 launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("conv3x3");
 }
 }  // namespace ctpn

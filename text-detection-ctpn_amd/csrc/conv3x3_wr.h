@@ -157,7 +157,7 @@ __host__ __device__ constexpr bool wr_first_touch(int n, int ky) {
 //     image) under tile k + 3, into one of two 4-KiB planes;
 //   * a producer for window k + 2 threaded through the tile's slots: the window's 340 pixels are 4 waves x 85, each wave's 85 as three
 //     32-pixel MFMA groups (the third overlaps the second by 11 pixels: identical values written twice); per group three ds_read2_b64
-//     (tap rows ky = 0..2; lanes 0..31 read q-pixels (x - 1, x), lanes 32..63 (x, x + 1): K-slot order in layers.hip, pack_conv1_frags),
+//     (tap rows ky = 0..2; lanes 0..31 read q-pixels (x - 1, x), lanes 32..63 (x, x + 1): K-slot order in conv_first_q.hip, pack_conv1_frags),
 //     2 x 3 MFMAs (two 32-channel halves, ky = 0, 1, 2 from a zero accumulator) and 2 x 4 epilogue pieces (two packed converts, the
 //     ReLU as a packed integer max, one ds_write_b64 into the window buffer at the 144-byte pixel pitch -- two-way bank-conflicted; the
 //     conflict-free ds_write_b128 form behind v_permlane32_swap measured 0.5 % slower);
@@ -167,7 +167,7 @@ __host__ __device__ constexpr bool wr_first_touch(int n, int ky) {
 // ring's counted waits stay exact: slot n waits with lgkmcnt(7 + the producer's operations of the eight slots before it). A fragment read
 // is consumed >= 9 slots after its issue (the ring wait of that slot covers it), an accumulator is read by the epilogue's VALU >= 2
 // slots after its last MFMA. 18 MFMAs per wave on top of the tile's 144.
-// conv_first_p_kernel (layers.hip) runs the same MFMA sequence on the same operands from global memory: what keep_acts stores.
+// conv_first_p_kernel (conv_first_q.hip) runs the same MFMA sequence on the same operands from global memory: what keep_acts stores.
 // ---------------------------------------------------------------------------------------------
 constexpr int FQ_PW = 36, FQ_ROWB = FQ_PW * 8, FQ_PLANE = 4096;
 constexpr int FQ_PLANE_OFF = WR_NBUF * WR_WIN + 16, FQ_ZERO_OFF = FQ_PLANE_OFF + 2 * FQ_PLANE, FQ_LDS = FQ_ZERO_OFF + 1024;
@@ -836,8 +836,6 @@ static int c3_launch_wr(const Conv3& c, bool pool, hipStream_t s) {
     }
   }
   if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("conv3x3_wr launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("conv3x3_wr");
 }
 }  // namespace ctpn

@@ -55,9 +55,7 @@ int launch_crop_lines(const uint8_t* imgs_dev, const void* descs_dev, int total,
   if ((long long)total * chunks > 0x7fffffffLL) return fail(CTPN_ERR_ARG, "crop_lines: too many lines for one launch");
   hipLaunchKernelGGL(crop_lines_kernel, dim3((unsigned)(total * chunks)), dim3(CROP_THREADS), 0, s, imgs_dev, (const CropDesc*)descs_dev, out_dev, h, w, crop_h,
                      max_w, pad, chunks);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("crop_lines launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("crop_lines");
 }
 
 }  // namespace ctpn

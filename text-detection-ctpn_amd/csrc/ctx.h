@@ -316,16 +316,6 @@ struct ctpn_ctx {
 
 namespace ctpn {
 
-// 16-bit activation -> fp32 on the host (ctpn_get_tensor, ctpn_debug_conv3x3)
-static inline float host_bf16_to_f32(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; std::memcpy(&f, &u, 4); return f; }
-static inline float host_f16_to_f32(uint16_t b) { _Float16 h; std::memcpy(&h, &b, 2); return (float)h; }
-static inline uint16_t host_f32_to_bf16(float f) {
-  uint32_t u; std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline uint16_t host_f32_to_f16(float f) { const _Float16 h = (_Float16)f; uint16_t b; std::memcpy(&b, &h, 2); return b; }
 static inline DType prec_dtype(int precision) {
   return precision == CTPN_PREC_FP32 ? DType::F32 : precision == CTPN_PREC_FP16 ? DType::F16 : precision == CTPN_PREC_SPLIT ? DType::SPLIT : DType::BF16;
 }

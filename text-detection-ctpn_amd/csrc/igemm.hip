@@ -289,9 +289,7 @@ static int launch_cfg(const IGemm& g, hipStream_t s) {
   int dev = 0, rc;
   if ((rc = current_device(dev)) || (rc = raise_dynamic_lds((const void*)k, C::LDS, attr_done, dev))) return rc;
   hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(C::NTHR), C::LDS, s, g, tiles_n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("igemm launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("igemm");
 }
 
 template <typename T, typename OutT>

@@ -625,9 +625,7 @@ int launch_jpeg_pixels(const int16_t* coef_dev, const uint16_t* qt_dev, uint8_t*
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nblk + 31) / 32)), dim3(256), 0, s, coef_dev, qt_dev, planes_dev, g, n);
   const long long groups = ((long long)g.oh * g.ow * n + 3) / 4;
   hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, planes_dev, out_dev, g, n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("jpeg launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("jpeg");
 }
 
 }  // namespace ctpn

@@ -377,17 +377,13 @@ int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qta
   const int mcux = g.bw[1], mcuy = g.bh[1];
   if (n <= 0 || n > 65535 || mcuy > 65535 || mcux <= 0) return fail(CTPN_ERR_ARG, "jpeg encode: grid out of range");
   hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)((mcux + 7) / 8), (unsigned)mcuy, (unsigned)n), dim3(256), 0, s, img_dev, coef_dev, qtab_dev, g);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("jpeg encode launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("jpeg encode");
 }
 
 int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* counts_dev, int line_capacity, int n, int h, int w, hipStream_t s) {
   if (n <= 0) return fail(CTPN_ERR_ARG, "draw_boxes: empty batch");
   hipLaunchKernelGGL(draw_boxes_kernel, dim3((unsigned)n), dim3(256), 0, s, imgs_dev, recs_dev, counts_dev, line_capacity, h, w);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("draw_boxes launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("draw_boxes");
 }
 
 }  // namespace ctpn

@@ -234,9 +234,7 @@ __global__ __launch_bounds__(64) void lstm_pre_small_kernel(LstmPre g) {
 // dst: device buffer of 1 MB (16-bit); src: wt_x [1024][512] 16-bit (gate rows already permuted)
 int launch_lstm_pre_pack(const void* src, void* dst, hipStream_t s) {
   hipLaunchKernelGGL(lstm_pre_pack_kernel, dim3(256), dim3(256), 0, s, (const uint16_t*)src, (uint16_t*)dst);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("lstm_pre pack launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("lstm_pre pack");
 }
 
 // a: bordered NHWC 16-bit map of n x hf x wf cells x 512 channels (dtype t: BF16 or F16); wt: launch_lstm_pre_pack's output;
@@ -258,9 +256,7 @@ int launch_lstm_pre(const void* a, const void* wt, const float* bias, void* out,
   if (cellblks * 2 <= ncu) {                                       // less than half a round of workgroups: one wave per (32 cells, four column tiles)
     if (t == DType::F16) hipLaunchKernelGGL((lstm_pre_small_kernel<h_f16>), dim3((unsigned)(groups * (32 / LPS_NT))), dim3(64), 0, s, g);
     else hipLaunchKernelGGL((lstm_pre_small_kernel<h_bf16>), dim3((unsigned)(groups * (32 / LPS_NT))), dim3(64), 0, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("lstm_pre (small) launch: ") + hipGetErrorString(e));
-    return CTPN_OK;
+    return launch_status("lstm_pre (small)");
   }
   const int lds = g.nbuf * LP_TILE_B + 1024 * 4;
   auto launch = [&](auto kern) -> int {
@@ -272,9 +268,7 @@ int launch_lstm_pre(const void* a, const void* wt, const float* bias, void* out,
   };
   rc = t == DType::F16 ? launch(lstm_pre_kernel<h_f16>) : launch(lstm_pre_kernel<h_bf16>);
   if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("lstm_pre launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("lstm_pre");
 }
 
 }  // namespace ctpn

@@ -80,9 +80,7 @@ int launch_resize_linear(const void* src, void* dst, int is_f32, int n, int h, i
     hipLaunchKernelGGL(resize_linear_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)src, (float*)dst, n, h, w, dh, dw, 1.0 / fx, 1.0 / fy);
   else
     hipLaunchKernelGGL(resize_linear_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, (const uint8_t*)src, (uint8_t*)dst, n, h, w, dh, dw, 1.0 / fx, 1.0 / fy);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CTPN_ERR_HIP, std::string("resize launch: ") + hipGetErrorString(e));
-  return CTPN_OK;
+  return launch_status("resize");
 }
 
 }  // namespace ctpn

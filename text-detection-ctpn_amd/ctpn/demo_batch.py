@@ -85,7 +85,7 @@ RPN_PARAM_NAMES = ("RPN_PRE_NMS_TOP_N", "RPN_POST_NMS_TOP_N", "RPN_NMS_THRESH", 
 
 def _check_uint8_feed_config(params=None):
     """The batched path feeds uint8 images; the library subtracts the reference's PIXEL_MEANS (lib/fast_rcnn/config.py:200) inside its first
-    kernel (csrc/layers.hip), compiled in. The reference subtracts cfg.PIXEL_MEANS at run time (lib/fast_rcnn/test.py:7-11), so an edited
+    kernel (csrc/conv_first.hip, csrc/conv_first_q.hip), compiled in. The reference subtracts cfg.PIXEL_MEANS at run time (lib/fast_rcnn/test.py:7-11), so an edited
     value must not be ignored silently: it is an error here (the single-image path, lib/fast_rcnn/test.py, subtracts cfg.PIXEL_MEANS in
     Python and takes any value)."""
     built = np.array([102.9801, 115.9465, 122.7717])

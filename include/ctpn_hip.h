@@ -412,6 +412,36 @@ int    ctpn_decode_jpeg_files(ctpn_ctx* ctx, const char* const* paths, int n, in
 int    ctpn_jpeg_probe_files(const char* const* paths, int n, int* info4, int threads);
 int    ctpn_jpeg_batch_fetch(ctpn_ctx* ctx, const uint8_t* images_dev, uint8_t* host_out, size_t capacity);
 
+/* ---- the same with the Huffman decode on the device too (jpeg_huff.hip): additive to ABI 10, no option and no default changes. For
+ * SEQUENTIAL files (SOF0 / SOF1: one interleaved scan, what the host half's sequential decoder takes) the host only parses the markers and
+ * makes one linear pass over the scan's bytes (byte stuffing removed, cut at the RSTn markers); bytes, Huffman tables and segment table
+ * cross in one copy (a tenth of the coefficients' bytes) and the self-synchronising parallel decode writes the coefficients where
+ * the IDCT kernel reads them: restart segments cut into subsequences of S bits, one thread each; pass 1 from every subsequence's first
+ * bit, sync rounds from the predecessor's exit state until no state changes (at most `subsequences of the longest segment - 1` rounds),
+ * a scan of the blocks per subsequence, a write pass, a prefix sum of the DC differences. Every file has a flag word: 0 = its coefficients
+ * are the host half's, bit for bit; anything else (an invalid code, a DC category above 11, an AC run past 63, data that ends early, a
+ * block or segment count that does not come out) and the library runs the HOST half on that file alone -- status and message are the
+ * host's, the two paths cannot disagree about a file. A progressive file is CTPN_ERR_UNSUPPORTED here: route it to the calls above.
+ *   ctpn_decode_jpeg_batch_device    ctpn_decode_jpeg_batch's contract, buffers (the same two sets), events and one-layout-per-batch rule;
+ *   ctpn_decode_jpeg_files_device    the images are byte-equal to that call's. The call returns when the flag words are back (it waits for
+ *                                    the entropy kernels, as the host form waits for its worker threads) and the pixel half is queued.
+ *   ctpn_jpeg_entropy_decode_device  the seam the tests use, synchronous: n files of any mix of sizes and layouts; subseq_bits = S, 0 for the
+ *                                    default (1024), else a multiple of 32 in 128 .. 4096. coef_out: host memory, n x coef_capacity_per_file
+ *                                    int16, file i's part filled exactly as ctpn_jpeg_entropy_decode fills it; qt_out n x 192; layout8_out
+ *                                    n x 8; status_out[i] = the status that call returns for file i (per-file outcomes are data: the call
+ *                                    itself fails on bad arguments and HIP errors only), except that a progressive file is
+ *                                    CTPN_ERR_UNSUPPORTED. ctpn_last_error() holds the message of the last file that failed.
+ *   ctpn_jpeg_entropy_device_stats   of the ctx's last device-entropy call: out4 = {files decoded on the device, files handed to the host
+ *                                    half because of a flag, subsequences in total, sync rounds run}.
+ * A post-processing-only ctx is CTPN_ERR_STATE. */
+int    ctpn_decode_jpeg_batch_device(ctpn_ctx* ctx, const uint8_t* const* files, const size_t* sizes, int n, int h, int w, double fx, double fy,
+                                     const uint8_t** images_dev_out, int* out_h, int* out_w);
+int    ctpn_decode_jpeg_files_device(ctpn_ctx* ctx, const char* const* paths, int n, int h, int w, double fx, double fy,
+                                     const uint8_t** images_dev_out, int* out_h, int* out_w);
+int    ctpn_jpeg_entropy_decode_device(ctpn_ctx* ctx, const uint8_t* const* files, const size_t* sizes, int n, int subseq_bits, int16_t* coef_out,
+                                       size_t coef_capacity_per_file, uint16_t* qt_out, int* layout8_out, int* status_out);
+int    ctpn_jpeg_entropy_device_stats(ctpn_ctx* ctx, long long* out4);
+
 /* ---- cv2.imwrite for the annotated result images (reference ctpn/demo.py:28-52: draw_boxes, cv2.resize by 1 / scale, cv2.imwrite), the mirror
  * image of the JPEG reader above, split where the work splits: BGR -> YCbCr, 2 x 2 chroma downsampling, the 8 x 8 forward DCT and the
  * quantiser on the device (one launch; the outlines and the resize before it, so annotated pixels never visit the host), baseline Huffman

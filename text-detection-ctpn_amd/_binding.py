@@ -115,6 +115,12 @@ def _declare(lib):
         "ctpn_jpeg_batch_fetch": (C.c_int, [vp, vp, u8p, C.c_size_t]),
         "ctpn_decode_jpeg_files": (C.c_int, [vp, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(vp), i32p, i32p]),
         "ctpn_jpeg_probe_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, i32p, C.c_int]),
+        "ctpn_decode_jpeg_batch_device": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                    C.POINTER(vp), i32p, i32p]),
+        "ctpn_decode_jpeg_files_device": (C.c_int, [vp, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(vp), i32p, i32p]),
+        "ctpn_jpeg_entropy_decode_device": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_size_t,
+                                                      C.POINTER(C.c_uint16), i32p, i32p]),
+        "ctpn_jpeg_entropy_device_stats": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
         "ctpn_jpeg_encode_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_encode": (C.c_int, [C.POINTER(C.c_int16), i32p, C.POINTER(C.c_uint16), u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "ctpn_encode_jpeg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
@@ -354,6 +360,33 @@ def jpeg_entropy_decode(data):
         planes.append(coef[off: off + bw * bh * 64].reshape(bh, bw, 64))
         off += bw * bh * 64
     return planes, qt, {"h": h, "w": w, "ncomp": nc, "hs": hs, "vs": (bh0 // bh1 if nc == 3 else 1), "orientation": orient}
+
+
+def jpeg_entropy_decode_device(ctx, files, subseq_bits=0, capacity=None):
+    """The device Huffman decoder alone (ctpn_jpeg_entropy_decode_device; synchronous): n files of any mix of sizes and layouts ->
+    (coef (n, capacity) int16, qt (n, 3, 64) uint16, layout8 (n, 8) int32, status (n,) int32), each file's part as ctpn_jpeg_entropy_decode
+    fills it. capacity: int16 elements per file (default: the largest ctpn_jpeg_coef_capacity of the files that parse)."""
+    lib = load_library()
+    files = list(files)
+    keeps = [_bytes_ptr(f) for f in files]
+    n = len(keeps)
+    if capacity is None:
+        capacity = 64
+        for f in files:
+            try:
+                h, w = jpeg_probe(f)[:2]
+                capacity = max(capacity, int(lib.ctpn_jpeg_coef_capacity(h, w)))
+            except CtpnError:
+                pass
+    ptrs = (C.POINTER(C.c_uint8) * n)(*[k[1] for k in keeps])
+    sizes = (C.c_size_t * n)(*[k[2] for k in keeps])
+    coef = np.zeros((n, int(capacity)), np.int16)
+    qt = np.zeros((n, 3, 64), np.uint16)
+    l8 = np.zeros((n, 8), np.int32)
+    st = np.zeros((n,), np.int32)
+    _check(lib.ctpn_jpeg_entropy_decode_device(ctx._h, ptrs, sizes, n, int(subseq_bits), _ptr(coef, C.c_int16), int(capacity), _ptr(qt, C.c_uint16),
+                                               _ptr(l8, C.c_int), _ptr(st, C.c_int)))
+    return coef, qt, l8, st
 
 
 def jpeg_encode_capacity(h, w):
@@ -782,11 +815,27 @@ class Context:
             raise
         return [recs[i, : lcnt[i]].copy() for i in range(n)], [keep[i, : kcnt[i]].copy() for i in range(n)]
 
-    def decode_jpeg_batch(self, files, h=None, w=None, fx=1.0, fy=1.0):
+    def jpeg_entropy_device_stats(self):
+        """Of the last device-entropy call (ctpn_jpeg_entropy_device_stats): dict(device=files decoded on the device, host=files handed to
+        the host half because of a flag, subsequences=..., rounds=sync rounds run)."""
+        out = (C.c_longlong * 4)()
+        _check(self._lib.ctpn_jpeg_entropy_device_stats(self._h, out))
+        return {"device": int(out[0]), "host": int(out[1]), "subsequences": int(out[2]), "rounds": int(out[3])}
+
+    @staticmethod
+    def _entropy_form(entropy):
+        if entropy not in ("host", "device"):
+            raise ValueError("entropy must be 'host' or 'device'")
+        return entropy == "device"
+
+    def decode_jpeg_batch(self, files, h=None, w=None, fx=1.0, fy=1.0, entropy="host"):
         """resize_im(cv2.imread(f)) of n JPEG files of one size on the device (ctpn_decode_jpeg_batch): Huffman decoding on the ctx's host
         pool, IDCT / upsampling / colour conversion / cv2.resize(fx, fy) as HIP kernels. Returns (device pointer, (n, out_h, out_w)) for
         forward / detect / detect_submit (device_ptr=, shape=); the buffer stays valid until the second-next call.
-        CtpnError(code CTPN_ERR_UNSUPPORTED) for CMYK / 4:1:1 / arithmetic-coded / incomplete files: decode those on the host."""
+        CtpnError(code CTPN_ERR_UNSUPPORTED) for CMYK / 4:1:1 / arithmetic-coded / incomplete files: decode those on the host.
+        entropy="device": the Huffman decode runs on the device too (ctpn_decode_jpeg_batch_device; sequential files only, a progressive
+        one is CTPN_ERR_UNSUPPORTED there); the images are byte-equal."""
+        fn = self._lib.ctpn_decode_jpeg_batch_device if self._entropy_form(entropy) else self._lib.ctpn_decode_jpeg_batch
         files = list(files)
         if h is None or w is None:
             h, w = jpeg_probe(files[0])[:2]
@@ -795,15 +844,17 @@ class Context:
         ptrs = (C.POINTER(C.c_uint8) * n)(*[k[1] for k in keeps])
         sizes = (C.c_size_t * n)(*[k[2] for k in keeps])
         out, oh, ow = C.c_void_p(0), C.c_int(0), C.c_int(0)
-        _check(self._lib.ctpn_decode_jpeg_batch(self._h, ptrs, sizes, n, int(h), int(w), float(fx), float(fy), C.byref(out), C.byref(oh), C.byref(ow)))
+        _check(fn(self._h, ptrs, sizes, n, int(h), int(w), float(fx), float(fy), C.byref(out), C.byref(oh), C.byref(ow)))
         return out.value, (n, oh.value, ow.value)
 
-    def decode_jpeg_files(self, paths, h, w, fx=1.0, fy=1.0):
-        """decode_jpeg_batch from paths (ctpn_decode_jpeg_files): the library's worker threads read the files themselves."""
+    def decode_jpeg_files(self, paths, h, w, fx=1.0, fy=1.0, entropy="host"):
+        """decode_jpeg_batch from paths (ctpn_decode_jpeg_files / ctpn_decode_jpeg_files_device): the library's worker threads read the
+        files themselves."""
+        fn = self._lib.ctpn_decode_jpeg_files_device if self._entropy_form(entropy) else self._lib.ctpn_decode_jpeg_files
         paths = list(paths)
         keep, arr = _path_array(paths)
         out, oh, ow = C.c_void_p(0), C.c_int(0), C.c_int(0)
-        _check(self._lib.ctpn_decode_jpeg_files(self._h, arr, len(paths), int(h), int(w), float(fx), float(fy), C.byref(out), C.byref(oh), C.byref(ow)))
+        _check(fn(self._h, arr, len(paths), int(h), int(w), float(fx), float(fy), C.byref(out), C.byref(oh), C.byref(ow)))
         return out.value, (len(paths), oh.value, ow.value)
 
     def jpeg_batch_fetch(self, device_ptr, shape):

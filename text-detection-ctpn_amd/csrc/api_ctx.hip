@@ -379,6 +379,8 @@ int ctpn_destroy(ctpn_ctx* c) {
     for (hipEvent_t e : {j.ev_h2d, j.ev_ready, j.ev_consumed}) if (e) (void)hipEventDestroy(e);
   }
   for (void* p : {(void*)c->jpeg_planes, (void*)c->jpeg_raw}) if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->jh.stage_dev, (void*)c->jh.work_dev}) if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->jh.stage_host, (void*)c->jh.res_host}) if (p) (void)hipHostFree(p);
   for (void* p : c->jpeg_retired) (void)hipFree(p);
   for (void* p : {(void*)c->enc.img_dev, (void*)c->enc.rs_dev, (void*)c->enc.coef_dev, (void*)c->enc.recs_dev, (void*)c->enc.cnt_dev, c->enc.qtab_dev}) if (p) (void)hipFree(p);
   for (void* p : {(void*)c->enc.coef_host, c->enc.qtab_host}) if (p) (void)hipHostFree(p);

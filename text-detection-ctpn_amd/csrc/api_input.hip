@@ -65,13 +65,155 @@ static bool jpeg_read_file(const char* path, std::vector<uint8_t>& buf, size_t l
   return ok;
 }
 
+// ---- device Huffman decode (jpeg_huff.hip): staging, the bounded round loop, the flag words ----
+static inline size_t jh_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Decode files use[0 .. m) (indices into P / data / len; all prepared without error) into coef_dev, file use[j] at int16 offset coef_base[use[j]]
+// (the caller made coef_dev large enough; coef_zero_elems of it are cleared first). One page-locked block -- descriptors, tables, segment and
+// subsequence tables, unstuffed bytes -- crosses in ONE copy; the host's share is one linear pass per file, on the worker pool. Returns when
+// the files' flag words are back: flags_out[use[j]] = 0 means file use[j]'s coefficients stand in coef_dev (complete as far as queue qs is
+// concerned), anything else that the host half has to decode that file. Updates the ctx's stats.
+static int jh_decode(ctpn_ctx* c, const uint8_t* const* data, const size_t* len, std::vector<JhPrep>& P, const std::vector<int>& use, uint32_t S,
+                     int16_t* coef_dev, const std::vector<long long>& coef_base, size_t coef_zero_elems, hipStream_t qs, std::vector<uint32_t>& flags_out) {
+  auto& W = c->jh;
+  const uint32_t WG = (uint32_t)jpeg_huff_workgroup();
+  std::vector<int> dev;                    // the files that go to the device
+  for (int i : use) {
+    if (len[i] - P[i].scan >= ((size_t)1 << 28)) flags_out[i] = JH_FLAG_SEGMENTS;      // bit positions are 32-bit: such a scan is the host half's
+    else dev.push_back(i);
+  }
+  const size_t m = dev.size();
+  long long handed = 0;
+  for (int i : use) if (flags_out[i]) ++handed;
+  c->jh_stats[0] = 0; c->jh_stats[1] = handed; c->jh_stats[2] = 0; c->jh_stats[3] = 0;
+  if (!m) return CTPN_OK;
+  // layout of the staged block (upper bounds: the unstuffed bytes are at most the scan's bytes)
+  size_t nseg = 0, ntab = 0, nbytes = 0, nsub_bound = 0;
+  std::vector<size_t> byte_off(m), seg_off(m), tab_off(m);
+  for (size_t j = 0; j < m; ++j) {
+    const JhPrep& p = P[dev[j]];
+    const size_t raw = len[dev[j]] - p.scan;
+    seg_off[j] = nseg; tab_off[j] = ntab; byte_off[j] = nbytes;
+    nseg += p.nseg; ntab += (size_t)p.ntab; nbytes += jh_up(raw, 4) + 8;
+    nsub_bound += jh_up((raw * 8 + S - 1) / S + p.nseg, WG);
+  }
+  if (nsub_bound > 0x7fffffffu || nbytes > 0xfffffff0u || nseg > 0x2fffffffu) return fail(CTPN_ERR_CAPACITY, "jpeg_huff: batch too large");
+  const size_t o_files = 0, o_segs = jh_up(o_files + m * sizeof(JhFile), 16), o_tabs = jh_up(o_segs + nseg * sizeof(JhSeg), 16),
+               o_bytes = jh_up(o_tabs + ntab * sizeof(JhTable), 16), o_wg = jh_up(o_bytes + nbytes, 16), o_sub = o_wg + nsub_bound / WG * 4,
+               stage_bound = o_sub + nsub_bound * 4;
+  if (stage_bound > W.stage_bytes) {
+    if (W.stage_host) CTPN_HIP_TRY(hipHostFree(W.stage_host));
+    if (W.stage_dev) CTPN_HIP_TRY(hipFree(W.stage_dev));
+    W.stage_host = W.stage_dev = nullptr; W.stage_bytes = 0;
+    const size_t want = stage_bound + stage_bound / 4;
+    CTPN_HIP_TRY(hipHostMalloc((void**)&W.stage_host, want));
+    CTPN_HIP_TRY(hipMalloc((void**)&W.stage_dev, want));
+    W.stage_bytes = want;
+  }
+  const size_t w_res = 0, w_st0 = jh_up(2 * m * 4, 16), w_st1 = w_st0 + nsub_bound * 8, w_entry = w_st1 + nsub_bound * 8, w_begun = w_entry + nsub_bound * 8,
+               w_prefix = w_begun + nsub_bound * 4, work_bound = w_prefix + nsub_bound * 4;
+  if (work_bound > W.work_bytes) {
+    if (W.work_dev) CTPN_HIP_TRY(hipFree(W.work_dev));
+    W.work_dev = nullptr; W.work_bytes = 0;
+    CTPN_HIP_TRY(hipMalloc((void**)&W.work_dev, work_bound + work_bound / 4));
+    W.work_bytes = work_bound + work_bound / 4;
+  }
+  if (2 * m > W.res_words) {
+    if (W.res_host) CTPN_HIP_TRY(hipHostFree(W.res_host));
+    W.res_host = nullptr; W.res_words = 0;
+    CTPN_HIP_TRY(hipHostMalloc((void**)&W.res_host, 2 * m * 4 + 256));
+    W.res_words = 2 * m + 64;
+  }
+  uint8_t* H = W.stage_host;
+  JhFile* hf = (JhFile*)(H + o_files); JhSeg* hs = (JhSeg*)(H + o_segs); JhTable* ht = (JhTable*)(H + o_tabs);
+  uint32_t* hwg = (uint32_t*)(H + o_wg); uint32_t* hsub = (uint32_t*)(H + o_sub);
+  // the linear pass: one file per worker
+  std::vector<int> found(m, 0);
+  c->pool->run((int)m, [&](int j) {
+    const int i = dev[j];
+    const JhPrep& p = P[i];
+    uint8_t* dst = H + o_bytes + byte_off[j];
+    const size_t raw = len[i] - p.scan;
+    uint32_t nb = 0;
+    found[j] = jh_unstuff_segments(data[i] + p.scan, raw, p.dri, p.total_mcus, dst, hs + seg_off[j], (int)p.nseg, &nb);
+    std::memset(dst + nb, 0, jh_up(raw, 4) + 8 - nb);
+    for (uint32_t k = (uint32_t)found[j]; k < p.nseg; ++k) {      // segments the file does not have: empty, so the decode flags them
+      JhSeg& sg = hs[seg_off[j] + k];
+      sg.byte0 = nb; sg.nbits = 0; sg.mcu0 = k * p.dri; sg.nmcu = std::min(p.dri, p.total_mcus - sg.mcu0);
+      sg.sub0 = sg.nsub = sg.file = sg.pad_ = 0;
+    }
+    JhFile& F = hf[j];
+    F = p.file;
+    F.coef_base = coef_base[i];
+    F.bytes_off = (uint32_t)byte_off[j]; F.nwords = (uint32_t)((jh_up(nb, 4) + 8) / 4);
+    F.seg0 = (uint32_t)seg_off[j]; F.nseg = p.nseg; F.tab0 = (uint32_t)tab_off[j]; F.ntab = (uint32_t)p.ntab;
+    std::memcpy(ht + tab_off[j], p.tabs, (size_t)p.ntab * sizeof(JhTable));
+  });
+  // subsequences: every segment at least one, every file's padded to the workgroup size
+  uint32_t nsub = 0, cap = 0;
+  long long real_subs = 0;
+  for (size_t j = 0; j < m; ++j) {
+    const JhPrep& p = P[dev[j]];
+    if ((uint32_t)found[j] < p.nseg) flags_out[dev[j]] |= JH_FLAG_SEGMENTS;
+    for (uint32_t k = 0; k < p.nseg; ++k) {
+      JhSeg& sg = hs[seg_off[j] + k];
+      sg.file = (uint32_t)j; sg.sub0 = nsub; sg.nsub = std::max(1u, (sg.nbits + S - 1) / S);
+      for (uint32_t q = 0; q < sg.nsub; ++q) hsub[nsub + q] = (uint32_t)(seg_off[j] + k);
+      nsub += sg.nsub; real_subs += sg.nsub;
+      cap = std::max(cap, sg.nsub - 1);
+    }
+    const uint32_t padded = (uint32_t)jh_up(nsub, WG);
+    for (; nsub < padded; ++nsub) hsub[nsub] = 0xffffffffu;
+  }
+  if (nsub > nsub_bound) return fail(CTPN_ERR_STATE, "jpeg_huff: subsequence bound exceeded");
+  for (uint32_t w = 0; w < nsub / WG; ++w) { const uint32_t si = hsub[(size_t)w * WG]; hwg[w] = si == 0xffffffffu ? 0xffffffffu : hs[si].file; }
+  const size_t stage_used = o_sub + (size_t)nsub * 4;
+  uint8_t* D = W.stage_dev; uint8_t* K = W.work_dev;
+  JhBatchDev B;
+  B.files = (const JhFile*)(D + o_files); B.segs = (const JhSeg*)(D + o_segs); B.tabs = (const JhTable*)(D + o_tabs);
+  B.wg_file = (const uint32_t*)(D + o_wg); B.sub_seg = (const uint32_t*)(D + o_sub); B.bytes = D + o_bytes;
+  B.st[0] = (JhState*)(K + w_st0); B.st[1] = (JhState*)(K + w_st1); B.entry = (JhState*)(K + w_entry);
+  B.begun = (uint32_t*)(K + w_begun); B.prefix = (uint32_t*)(K + w_prefix);
+  B.flags = (uint32_t*)(K + w_res); B.changed = B.flags + m;
+  B.coef = coef_dev; B.S = S; B.nsub = nsub; B.nseg = (uint32_t)nseg; B.nfiles = (uint32_t)m;
+  CTPN_HIP_TRY(hipMemcpyAsync(D, H, stage_used, hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(K + w_res, 0, 2 * m * 4, qs));
+  int rc;
+  if ((rc = launch_jpeg_huff_round(B, 0, qs))) return rc;
+  // sync rounds: a fixed few, then one check with the results; a file still unsettled then (rare: its components share their tables, or S is
+  // small against its blocks) gets four times as many, up to the cap -- after `subsequences in the longest segment - 1` rounds every state
+  // is the true one, whatever the flags say
+  uint32_t rounds = 0, target = std::min(cap, 6u);
+  for (;;) {
+    for (; rounds < target; ++rounds) if ((rc = launch_jpeg_huff_round(B, (int)rounds + 1, qs))) return rc;
+    CTPN_HIP_TRY(hipMemsetAsync(K + w_res, 0, m * 4, qs));                       // the flag words (not the rounds)
+    CTPN_HIP_TRY(hipMemsetAsync(coef_dev, 0, coef_zero_elems * sizeof(int16_t), qs));
+    if ((rc = launch_jpeg_huff_write(B, (int)rounds, qs))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(W.res_host, K + w_res, 2 * m * 4, hipMemcpyDeviceToHost, qs));
+    CTPN_HIP_TRY(hipStreamSynchronize(qs));
+    bool unsettled = false;
+    if (rounds < cap) for (size_t j = 0; j < m; ++j) if (W.res_host[m + j] >= rounds && rounds > 0) unsettled = true;
+    if (!unsettled) break;
+    target = (uint32_t)std::min<unsigned long long>(cap, (unsigned long long)rounds * 4);
+  }
+  long long ok = 0;
+  for (size_t j = 0; j < m; ++j) {
+    flags_out[dev[j]] |= W.res_host[j];
+    if (flags_out[dev[j]]) ++handed; else ++ok;
+  }
+  c->jh_stats[0] = ok; c->jh_stats[1] = handed; c->jh_stats[2] = real_subs; c->jh_stats[3] = rounds;
+  return CTPN_OK;
+}
+
 // one image's bytes for the host half: from the caller's memory, or read from the file inside the worker thread
 struct JpegSource {
   const uint8_t* const* mem = nullptr; const size_t* sizes = nullptr;
   const char* const* paths = nullptr;
 };
 
-static int jpeg_decode_impl(ctpn_ctx* c, const JpegSource& src, int n, int h, int w, double fx, double fy, const uint8_t** images_dev_out, int* out_h, int* out_w) {
+// dev_entropy: the Huffman decode on the device too (ctpn_decode_jpeg_batch_device); everything from the coefficients on is shared
+static int jpeg_decode_impl(ctpn_ctx* c, const JpegSource& src, int n, int h, int w, double fx, double fy, const uint8_t** images_dev_out, int* out_h, int* out_w,
+                            bool dev_entropy = false) {
   if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_decode_jpeg_batch: post-processing-only ctx");
   if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_batch: empty batch / bad size");
   const bool resize = (fx > 0.0 && fx != 1.0) || (fy > 0.0 && fy != 1.0);
@@ -91,7 +233,24 @@ static int jpeg_decode_impl(ctpn_ctx* c, const JpegSource& src, int n, int h, in
   std::vector<JpegGeom> geo((size_t)n);
   std::vector<int> st((size_t)n, CTPN_OK);
   std::vector<std::string> msg((size_t)n);
-  c->pool->run(n, [&](int i) {
+  // device entropy: the files' parsed frames, and the bytes of files given as paths (kept until the batch is staged)
+  std::vector<JhPrep> prep(dev_entropy ? (size_t)n : 0);
+  std::vector<std::vector<uint8_t>> held(dev_entropy && src.paths ? (size_t)n : 0);
+  std::vector<const uint8_t*> dptr((size_t)n, nullptr);
+  std::vector<size_t> dlen((size_t)n, 0);
+  if (dev_entropy) c->pool->run(n, [&](int i) {
+    try {
+      if (src.paths) {
+        if (!jpeg_read_file(src.paths[i], held[i])) { st[i] = CTPN_ERR_ARG; msg[i] = std::string("cannot read ") + src.paths[i]; return; }
+        dptr[i] = held[i].data(); dlen[i] = held[i].size();
+      } else { dptr[i] = src.mem[i]; dlen[i] = src.sizes[i]; }
+      st[i] = jpeg_huff_prepare(dptr[i], dlen[i], &prep[i]);
+      if (!st[i] && prep[i].coef_count > cap) st[i] = fail(CTPN_ERR_CAPACITY, "jpeg: coefficient buffer too small");
+      if (st[i]) msg[i] = ctpn_last_error();
+      else geo[i] = prep[i].g;
+    } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }
+  });
+  else c->pool->run(n, [&](int i) {
     const uint8_t* data = nullptr; size_t len = 0;
     static thread_local std::vector<uint8_t> filebuf;      // one per worker thread, reused from batch to batch
     try {
@@ -113,8 +272,23 @@ static int jpeg_decode_impl(ctpn_ctx* c, const JpegSource& src, int n, int h, in
   hipStream_t qs = c->stream_c;
   // the device buffers of this set: the forward that read out_dev two calls ago has passed its first layer
   if (J.consumed_valid) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_consumed, 0));
-  CTPN_HIP_TRY(hipMemcpy2DAsync(J.coef_dev, (size_t)g.coef_per_img * sizeof(int16_t), J.coef_host, cap * sizeof(int16_t), (size_t)g.coef_per_img * sizeof(int16_t), (size_t)n,
-                                hipMemcpyHostToDevice, qs));
+  if (dev_entropy) {
+    std::vector<long long> coef_base((size_t)n);
+    std::vector<int> use((size_t)n);
+    std::vector<uint32_t> flags((size_t)n, 0u);
+    for (int i = 0; i < n; ++i) { coef_base[i] = (long long)i * g.coef_per_img; use[i] = i; std::memcpy(J.qt_host + (size_t)i * 192, prep[i].qt, sizeof(prep[i].qt)); }
+    if ((rc = jh_decode(c, dptr.data(), dlen.data(), prep, use, JH_SUBSEQ_DEFAULT, J.coef_dev, coef_base, (size_t)n * g.coef_per_img, qs, flags))) return rc;
+    // a file with a raised flag is the host half's, alone: its status and message are the host's, its coefficients replace the device's
+    for (int i = 0; i < n; ++i) {
+      if (!flags[i]) continue;
+      JpegGeom g2;
+      if ((rc = jpeg_entropy_decode(dptr[i], dlen[i], J.coef_host + (size_t)i * cap, cap, J.qt_host + (size_t)i * 192, &g2)))
+        return fail(rc, "ctpn_decode_jpeg_batch: file " + std::to_string(i) + ": " + ctpn_last_error());
+      CTPN_HIP_TRY(hipMemcpyAsync(J.coef_dev + (size_t)i * g.coef_per_img, J.coef_host + (size_t)i * cap, (size_t)g.coef_per_img * sizeof(int16_t), hipMemcpyHostToDevice, qs));
+    }
+  } else
+    CTPN_HIP_TRY(hipMemcpy2DAsync(J.coef_dev, (size_t)g.coef_per_img * sizeof(int16_t), J.coef_host, cap * sizeof(int16_t), (size_t)g.coef_per_img * sizeof(int16_t), (size_t)n,
+                                  hipMemcpyHostToDevice, qs));
   CTPN_HIP_TRY(hipMemcpyAsync(J.qt_dev, J.qt_host, (size_t)n * 192 * sizeof(uint16_t), hipMemcpyHostToDevice, qs));
   CTPN_HIP_TRY(hipEventRecord(J.ev_h2d, qs));
   J.h2d_valid = true;
@@ -193,6 +367,77 @@ int ctpn_decode_jpeg_files(ctpn_ctx* c, const char* const* paths, int n, int h, 
   for (int i = 0; i < n; ++i) if (!paths[i]) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_files: null path");
   JpegSource src; src.paths = paths;
   return jpeg_decode_impl(c, src, n, h, w, fx, fy, images_dev_out, out_h, out_w);
+}
+
+// ---- the same with the Huffman decode on the device (jpeg_huff.hip) ----
+int ctpn_decode_jpeg_batch_device(ctpn_ctx* c, const uint8_t* const* files, const size_t* sizes, int n, int h, int w, double fx, double fy,
+                                  const uint8_t** images_dev_out, int* out_h, int* out_w) {
+  if (!c || !files || !sizes || !images_dev_out) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_batch_device: null pointer");
+  for (int i = 0; i < n; ++i) if (!files[i]) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_batch_device: null file pointer");
+  JpegSource src; src.mem = files; src.sizes = sizes;
+  return jpeg_decode_impl(c, src, n, h, w, fx, fy, images_dev_out, out_h, out_w, true);
+}
+
+int ctpn_decode_jpeg_files_device(ctpn_ctx* c, const char* const* paths, int n, int h, int w, double fx, double fy, const uint8_t** images_dev_out, int* out_h, int* out_w) {
+  if (!c || !paths || !images_dev_out) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_files_device: null pointer");
+  for (int i = 0; i < n; ++i) if (!paths[i]) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_files_device: null path");
+  JpegSource src; src.paths = paths;
+  return jpeg_decode_impl(c, src, n, h, w, fx, fy, images_dev_out, out_h, out_w, true);
+}
+
+int ctpn_jpeg_entropy_decode_device(ctpn_ctx* c, const uint8_t* const* files, const size_t* sizes, int n, int subseq_bits, int16_t* coef_out,
+                                    size_t coef_capacity_per_file, uint16_t* qt_out, int* layout8_out, int* status_out) {
+  if (!c || !files || !sizes || !coef_out || !qt_out || !layout8_out || !status_out || n <= 0) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_decode_device: null pointer / empty batch");
+  for (int i = 0; i < n; ++i) if (!files[i]) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_decode_device: null file pointer");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_jpeg_entropy_decode_device: post-processing-only ctx");
+  if (subseq_bits == 0) subseq_bits = JH_SUBSEQ_DEFAULT;
+  if (subseq_bits < JH_SUBSEQ_MIN || subseq_bits > JH_SUBSEQ_MAX || subseq_bits % 32) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_decode_device: subseq_bits must be 0 or a multiple of 32 in 128 .. 4096");
+  if (coef_capacity_per_file == 0 || (size_t)n > ((size_t)1 << 40) / coef_capacity_per_file) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_decode_device: bad coefficient capacity");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  std::vector<JhPrep> prep((size_t)n);
+  std::vector<int> use;
+  std::vector<long long> coef_base((size_t)n);
+  std::vector<uint32_t> flags((size_t)n, 0u);
+  for (int i = 0; i < n; ++i) {
+    coef_base[i] = (long long)i * (long long)coef_capacity_per_file;
+    status_out[i] = jpeg_huff_prepare(files[i], sizes[i], &prep[i]);
+    if (!status_out[i] && prep[i].coef_count > coef_capacity_per_file) status_out[i] = fail(CTPN_ERR_CAPACITY, "jpeg: coefficient buffer too small");
+    if (!status_out[i]) use.push_back(i);
+  }
+  c->jh_stats[0] = c->jh_stats[1] = c->jh_stats[2] = c->jh_stats[3] = 0;
+  if (use.empty()) return CTPN_OK;
+  int16_t* coef_dev = nullptr;
+  const size_t elems = (size_t)n * coef_capacity_per_file;
+  CTPN_HIP_TRY(hipMalloc((void**)&coef_dev, elems * sizeof(int16_t)));
+  hipStream_t qs = c->stream_c;
+  int rc = jh_decode(c, files, sizes, prep, use, (uint32_t)subseq_bits, coef_dev, coef_base, elems, qs, flags);
+  for (int i : use) {
+    if (rc) break;
+    if (flags[i]) continue;
+    if (hipMemcpyAsync(coef_out + (size_t)i * coef_capacity_per_file, coef_dev + (size_t)i * coef_capacity_per_file, prep[i].coef_count * sizeof(int16_t), hipMemcpyDeviceToHost, qs) != hipSuccess)
+      rc = fail(CTPN_ERR_HIP, "ctpn_jpeg_entropy_decode_device: copy of the coefficients failed");
+  }
+  if (!rc && hipStreamSynchronize(qs) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_jpeg_entropy_decode_device: queue failed");
+  (void)hipFree(coef_dev);
+  if (rc) return rc;
+  for (int i : use) {
+    int* l8 = layout8_out + 8 * (size_t)i;
+    if (flags[i]) {      // the host half on this file alone: its status, its message, its results
+      status_out[i] = ctpn_jpeg_entropy_decode(files[i], sizes[i], coef_out + (size_t)i * coef_capacity_per_file, coef_capacity_per_file, qt_out + 192 * (size_t)i, l8);
+      continue;
+    }
+    const JpegGeom& g = prep[i].g;
+    const int v[8] = {g.h, g.w, g.ncomp, g.hs0 | ((g.orient - 1) << 8), g.bw[0], g.bw[1], g.bh[0], g.bh[1]};
+    std::memcpy(l8, v, sizeof(v));
+    std::memcpy(qt_out + 192 * (size_t)i, prep[i].qt, sizeof(prep[i].qt));
+  }
+  return CTPN_OK;
+}
+
+int ctpn_jpeg_entropy_device_stats(ctpn_ctx* c, long long* out4) {
+  if (!c || !out4) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_device_stats: null pointer");
+  std::memcpy(out4, c->jh_stats, sizeof(c->jh_stats));
+  return CTPN_OK;
 }
 
 int ctpn_jpeg_batch_fetch(ctpn_ctx* c, const uint8_t* images_dev, uint8_t* host_out, size_t capacity) {

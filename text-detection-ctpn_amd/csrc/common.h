@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../include/ctpn_hip.h"
 #include "jpeg_pixel.h"
+#include "jpeg_huff_dev.h"
 
 namespace ctpn {
 
@@ -321,6 +322,30 @@ int jpeg_entropy_decode(const uint8_t* data, size_t len, int16_t* coef, size_t c
 int launch_jpeg_pixels(const int16_t* coef_dev, const uint16_t* qt_dev, uint8_t* planes_dev, uint8_t* out_dev, const JpegGeom& g, int n, hipStream_t s);
 int jpeg_probe(const uint8_t* data, size_t len, int* h, int* w, int* ncomp, int* luma_sampling);
 size_t jpeg_coef_capacity(int h, int w);
+
+// jpeg_huff.hip: the Huffman decode itself on the device (sequential files; per-thread source: jpeg_huff_dev.h). jpeg.hip prepares a file
+// for it without decoding a code: jparse + one linear pass over the scan's bytes
+struct JhPrep {             // one file after jparse: everything the device decode and the pixel tail need except the scan's bytes
+  JpegGeom g;
+  uint16_t qt[192];
+  JhFile file;              // geometry part filled; offsets are the stager's
+  JhTable tabs[JH_MAX_TABLES];
+  int ntab = 0;
+  size_t scan = 0;          // offset of the entropy-coded data in the file
+  uint32_t dri = 0, total_mcus = 0, nseg = 0;      // restart interval, MCUs, segments the frame needs
+  size_t coef_count = 0;
+};
+int jpeg_huff_prepare(const uint8_t* data, size_t len, JhPrep* out);      // CTPN_ERR_UNSUPPORTED for a progressive file
+struct JhBatchDev {         // device pointers of one staged batch + its work buffers
+  const JhFile* files; const JhSeg* segs; const JhTable* tabs; const uint32_t* wg_file; const uint32_t* sub_seg; const uint8_t* bytes;
+  JhState* st[2]; JhState* entry; uint32_t* begun; uint32_t* prefix;
+  uint32_t* changed; uint32_t* flags;      // per file: the last round that changed an exit state; the JH_FLAG_* word
+  int16_t* coef;
+  uint32_t S, nsub, nseg, nfiles;          // subsequence bits; subsequences (every file's padded to the workgroup size); segments; files
+};
+int jpeg_huff_workgroup();
+int launch_jpeg_huff_round(const JhBatchDev& B, int round, hipStream_t s);
+int launch_jpeg_huff_write(const JhBatchDev& B, int rounds, hipStream_t s);
 
 // jpeg_enc.hip: BGR images -> JPEG files (quality q, 4:2:0, standard Huffman tables), pixels to quantised coefficients on the device, entropy
 // coding on the host; draw_boxes_kernel = ctpn_draw_boxes on device images

@@ -179,6 +179,14 @@ struct ctpn_ctx {
   std::vector<void*> jpeg_retired;   // device allocations replaced by larger ones
   int jpeg_flip = 0;
   bool jpeg_ready = false;
+  // ctpn_decode_jpeg_batch_device / ctpn_jpeg_entropy_decode_device (device Huffman decode, jpeg_huff.hip): ONE set -- these calls read the
+  // files' flag words back before they return, so nothing of theirs is in flight when the next one stages its batch
+  struct JhWork {
+    uint8_t* stage_host = nullptr; uint8_t* stage_dev = nullptr; size_t stage_bytes = 0;      // page-locked block and its device copy: descriptors + tables + bytes
+    uint8_t* work_dev = nullptr; size_t work_bytes = 0;                                      // per file flags / rounds, per subsequence states / counts
+    uint32_t* res_host = nullptr; size_t res_words = 0;                                      // page-locked: what comes back (2 words per file)
+  } jh;
+  long long jh_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_device_stats
   // ctpn_encode_jpeg_batch / ctpn_write_annotated_files (api_output.hip): ONE set of buffers -- both calls return when their files are coded,
   // so nothing of a call is in flight when the next one starts -- allocated on first use and grown to the largest batch seen
   struct EncBufs {

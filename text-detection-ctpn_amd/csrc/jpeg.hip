@@ -37,6 +37,8 @@ struct JHuff {
   int32_t valptr[17];
   int32_t mincode[17];
   uint8_t vals[256];
+  uint8_t counts[16];        // the DHT segment's own form (the device decoder builds its table from it: jh_build_table)
+  int nvals = 0;
   bool present = false;
 };
 
@@ -59,6 +61,8 @@ static bool jhuff_build(JHuff& h, const uint8_t counts[16], const uint8_t* vals,
     code <<= 1;
   }
   h.maxcode[17] = 0x7fffffff;
+  std::memcpy(h.counts, counts, 16);
+  h.nvals = k;
   h.present = true;
   return true;
 }
@@ -614,6 +618,45 @@ int jpeg_entropy_decode(const uint8_t* data, size_t len, int16_t* coef, size_t c
   if ((rc = f.progressive ? jprogressive(data, len, f, coef, why) : jentropy(data, len, f, coef, why))) return fail(rc, "jpeg: " + why);
   for (int c = 0; c < 3; ++c) std::memcpy(qt3x64 + 64 * c, f.qt[f.tq[c < f.ncomp ? c : 0]], 64 * sizeof(uint16_t));
   jgeom(f, *g);
+  return CTPN_OK;
+}
+
+// device entropy decode (jpeg_huff.hip), host part: the same parse and the same refusals as the host half, then the frame in the form the
+// kernels read. No Huffman code is decoded here
+int jpeg_huff_prepare(const uint8_t* data, size_t len, JhPrep* out) {
+  JFrame f; std::string why;
+  const int rc = jparse(data, len, f, why);
+  if (rc) return fail(rc, "jpeg: " + why);
+  if (f.progressive) return fail(CTPN_ERR_UNSUPPORTED, "jpeg: progressive file (the device entropy decoder takes sequential files; use the host-entropy calls)");
+  JhPrep& P = *out;
+  jgeom(f, P.g);
+  for (int c = 0; c < 3; ++c) std::memcpy(P.qt + 64 * c, f.qt[f.tq[c < f.ncomp ? c : 0]], 64 * sizeof(uint16_t));
+  P.scan = f.scan;
+  P.total_mcus = (uint32_t)f.mcux * (uint32_t)f.mcuy;
+  P.dri = (uint32_t)f.dri;
+  P.nseg = P.dri ? (P.total_mcus + P.dri - 1) / P.dri : 1u;
+  P.coef_count = jcoef_count(f);
+  JhFile& F = P.file;
+  std::memset(&F, 0, sizeof(F));
+  F.ncomp = f.ncomp; F.mcux = f.mcux; F.mcuy = f.mcuy;
+  int slot_of[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+  P.ntab = 0;
+  for (int c = 0; c < f.ncomp; ++c) {
+    F.hs[c] = f.hs[c]; F.vs[c] = f.vs[c]; F.bw[c] = P.g.bw[c]; F.coef_off[c] = P.g.coef_off[c];
+    for (int q = 0; q < f.hs[c] * f.vs[c]; ++q) {
+      if (F.bpm >= JH_MAX_PATTERN) return fail(CTPN_ERR_UNSUPPORTED, "jpeg: more than 6 blocks per MCU");
+      F.pat_comp[F.bpm++] = (uint8_t)c;
+    }
+    for (int ac = 0; ac < 2; ++ac) {
+      const int id = ac ? f.ta[c] : f.td[c];
+      if (slot_of[ac][id] < 0) {
+        const JHuff& h = ac ? f.ac[id] : f.dc[id];
+        if (P.ntab >= JH_MAX_TABLES || !jh_build_table(P.tabs[P.ntab], h.counts, h.vals, h.nvals)) return fail(CTPN_ERR_ARG, "jpeg: bad Huffman table");
+        slot_of[ac][id] = P.ntab++;
+      }
+      (ac ? F.ac_tab : F.dc_tab)[c] = (uint8_t)slot_of[ac][id];
+    }
+  }
   return CTPN_OK;
 }
 

@@ -212,7 +212,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
     return k
 
 
-def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None):
+def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host"):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -224,7 +224,10 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     encode='gpu' (with write_images): the annotated images of device-decoded batches whose output name is a JPEG's are drawn, resized by
     1 / scale and JPEG-coded by the library at collect time (ctpn_write_annotated_files: kernels in the ctx's copy queue, Huffman coding and
     file writing on its C++ pool) -- those pixels never reach the host. PNG-named outputs (a lossless DEFLATE stream: host work by nature),
-    batches of the host decoders and the single images keep Pillow's writer; the files are byte-identical either way."""
+    batches of the host decoders and the single images keep Pillow's writer; the files are byte-identical either way.
+    entropy='device' (--decode gpu-entropy): the Huffman decode of the JPEG batches runs on the device too (ctpn_decode_jpeg_files_device);
+    a batch that call refuses -- one with a progressive file in it -- takes the host-entropy call, and what that refuses goes to Pillow, as
+    with decode='gpu'."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -313,7 +316,15 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         imgs = None
         if kind == "jpg":
             try:
-                ptr, shape = net.ctx.decode_jpeg_files(members, h, w, f, f)      # files read + entropy-decoded on the library's pool
+                ptr = None
+                if entropy == "device":
+                    try:
+                        ptr, shape = net.ctx.decode_jpeg_files(members, h, w, f, f, entropy="device")      # Huffman decode on the device too
+                    except B.CtpnError as e:
+                        if e.code != B.CTPN_ERR_UNSUPPORTED:                   # (a progressive file in the batch: the host half's)
+                            raise
+                if ptr is None:
+                    ptr, shape = net.ctx.decode_jpeg_files(members, h, w, f, f)      # files read + entropy-decoded on the library's pool
                 assert tuple(shape[1:]) == tuple(rs), (shape, rs)
                 net.ctx.detect_submit(device_ptr=ptr, shape=shape, slot=k & 1)
                 stats["gpu"] += len(members)
@@ -385,6 +396,9 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         parse_connector_args(["%s=%r" % (k, float(v)) for k, v in params.items() if k not in RPN_PARAM_NAMES])      # unknown names: an error before any work
     if encode not in ("host", "gpu"):
         raise ValueError("encode must be 'host' or 'gpu'")
+    entropy = "device" if decode == "gpu-entropy" else "host"      # gpu-entropy: decode='gpu' with the Huffman decode on the device too
+    if decode == "gpu-entropy":
+        decode = "gpu"
     if encode == "gpu" and decode != "gpu":
         raise ValueError("encode='gpu' writes the images of device-decoded batches: it needs decode='gpu'")
     if crops_dir is not None and decode != "gpu":
@@ -392,7 +406,8 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
-        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params)
+        return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
+                        entropy=entropy)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -529,7 +544,9 @@ def build_parser():
     ap.add_argument('--no-images', action='store_true', help='write only res_<stem>.txt')
     ap.add_argument('--decode-threads', type=int, default=8, help='host threads decoding / resizing the next batch')
     ap.add_argument('--decode-procs', type=int, default=0, help='decode in this many worker PROCESSES (shared-memory batches) instead of threads')
-    ap.add_argument('--decode', default='host', choices=['host', 'gpu'], help="gpu: JPEG decode + resize_im on the device (ctpn_decode_jpeg_batch)")
+    ap.add_argument('--decode', default='host', choices=['host', 'gpu', 'gpu-entropy'],
+                    help="gpu: JPEG decode + resize_im on the device (ctpn_decode_jpeg_batch); gpu-entropy: the same with the Huffman decode on the device too "
+                         "(ctpn_decode_jpeg_files_device; progressive files keep the host-entropy call)")
     ap.add_argument('--encode', default='host', choices=['host', 'gpu'],
                     help="gpu (with --decode gpu): annotated JPEG images drawn, resized and coded by the library (ctpn_write_annotated_files)")
     ap.add_argument('--crops', default=None, metavar='DIR',

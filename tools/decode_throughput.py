@@ -11,6 +11,13 @@ Writes N synthetic 600x900 "document" images (smooth background, dark text-like 
   demo_batch      images/s of ctpn/demo_batch.py::run end to end (header scan, decode on `threads` host threads one batch ahead, H2D,
                   detect_submit / detect_collect, res_*.txt written by the C++ writer), no annotated images
 against `resident`: bench.py's protocol on the same GPU with the uint8 batch already in HBM.
+
+    python tools/decode_throughput.py --entropy both --out profiles/jpeg_entropy_device.txt
+
+--entropy host|device|both measures the decoder alone in its two forms (ctpn_decode_jpeg_batch: Huffman decode on the host pool;
+ctpn_decode_jpeg_batch_device: on the device), in one process, warmed up: the latency of a lone 600x900 4:2:0 quality-90 image from the call
+to its pixels being complete (median of --calls calls), the rate of batch-32 decodes with the host CPU seconds they cost per 1000 images
+(time.process_time: every thread of the process), and the bytes each form sends to the device per image. Nothing else is run.
 """
 import argparse
 import json
@@ -40,8 +47,62 @@ def make_image(seed, h=600, w=900):
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
+def entropy_report(args):
+    """The decoder alone, host-entropy form against device-entropy form (see the module docstring)."""
+    import io
+    from PIL import Image
+    import ctpn_amd
+    from ctpn_amd import _binding as B
+    forms = ["host", "device"] if args.entropy == "both" else [args.entropy]
+    datas = []
+    for i in range(args.batch):
+        buf = io.BytesIO()
+        Image.fromarray(make_image(i)[:, :, ::-1].copy()).save(buf, "JPEG", quality=90)
+        datas.append(buf.getvalue())
+    out = {"height": 600, "width": 900, "batch": args.batch, "calls": args.calls, "mean_file_kb": round(sum(map(len, datas)) / len(datas) / 1024, 1),
+           "host_cpus_usable": len(os.sched_getaffinity(0)), "forms": {}}
+    with ctpn_amd.Context(0, args.batch, 600, 900, args.precision) as ctx:
+        for form in forms:
+            r = {}
+            for _ in range(5):                                                   # warm-up: buffers allocated, kernels loaded
+                ctx.decode_jpeg_batch(datas[:1], 600, 900, entropy=form)
+                ctx.decode_jpeg_batch(datas, 600, 900, entropy=form)
+            ctx.sync()
+            lat = []
+            for k in range(args.calls):
+                t0 = time.perf_counter()
+                ctx.decode_jpeg_batch(datas[k % args.batch: k % args.batch + 1], 600, 900, entropy=form)
+                ctx.sync()                                                       # pixels complete
+                lat.append(time.perf_counter() - t0)
+            r["lone_image_ms_median"] = round(float(np.median(lat)) * 1e3, 4)
+            r["lone_image_ms_min_max"] = [round(min(lat) * 1e3, 4), round(max(lat) * 1e3, 4)]
+            reps = max(8, args.calls // 4)
+            c0, t0 = time.process_time(), time.perf_counter()
+            for k in range(reps):
+                ctx.decode_jpeg_batch(datas, 600, 900, entropy=form)
+            ctx.sync()
+            dt, dc = time.perf_counter() - t0, time.process_time() - c0
+            r["batch_images_per_s"] = round(reps * args.batch / dt, 1)
+            r["host_cpu_s_per_1000_images"] = round(dc / (reps * args.batch) * 1000, 4)
+            if form == "device":
+                r["stats_last_call"] = ctx.jpeg_entropy_device_stats()
+                # what is staged per image: the scan's bytes, the Huffman tables (1336 bytes each), 4 bytes per subsequence, the descriptors
+                scan = [len(d) - d.index(b"\xff\xda") for d in datas]
+                r["h2d_bytes_per_image"] = int(np.mean([n + 4 * 1336 + 4 * (-(-n * 8 // 1024) + 256) + 160 for n in scan]))
+            else:
+                planes = B.jpeg_entropy_decode(datas[0])[0]
+                r["h2d_bytes_per_image"] = int(sum(p.size for p in planes)) * 2 + 384      # the int16 coefficient block + the quantisation tables
+            out["forms"][form] = r
+    txt = json.dumps(out, indent=1)
+    print(txt)
+    if args.out:
+        open(args.out, "w").write(txt + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--entropy", default=None, choices=["host", "device", "both"], help="measure the JPEG decoder alone with its Huffman decode on the host pool / on the device (both: in one process) and nothing else")
+    ap.add_argument("--calls", type=int, default=100, help="(with --entropy) lone-image calls the latency median is taken over")
     ap.add_argument("--images", type=int, default=512)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--out", default=None)
@@ -50,6 +111,8 @@ def main():
     ap.add_argument("--only-gpu", action="store_true", help="JPEG only: demo_batch with worker processes against demo_batch --decode gpu (+ the resident rate)")
     ap.add_argument("--distinct", type=int, default=0, help="encode only this many distinct images and write them under --images names (0 = all distinct)")
     args = ap.parse_args()
+    if args.entropy:
+        return entropy_report(args)
     from PIL import Image
     import ctpn_amd
     from ctpn_amd import _binding as B

@@ -476,6 +476,32 @@ int    ctpn_encode_jpeg_batch(ctpn_ctx* ctx, const uint8_t* images, int images_o
 int    ctpn_write_annotated_files(ctpn_ctx* ctx, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity,
                                   const int* line_counts, double scale, const char* const* paths, int quality);
 
+/* ---- the same with the Huffman coding on the device too (jpeg_huff_enc.hip): additive to ABI 10, no option and no default changes. A block's
+ * code depends only on its own coefficients and on the previous block's DC, which lies in the coefficient array, so there is nothing to
+ * synchronise: a length pass (one thread per block), a prefix sum per image, a write pass that runs the length pass's text once more into
+ * the unstuffed stream, then the 0xFF count per 64-byte chunk, its prefix sum and the stuffed scan body. The host writes header and EOI.
+ * Only the result words (16 bytes per image) and the files' own scan bytes cross to the host -- sizes first, then what they say -- instead
+ * of every coefficient. An image whose flag is raised (a DC difference above 11 bits, an AC coefficient above 10, a count that does not
+ * come out) or that has more than 2^20 blocks is coded by the HOST half alone, so status and message are the host's: the two forms cannot
+ * disagree about an image.
+ *   ctpn_encode_jpeg_batch_device          arguments, contract, queue, events and error codes of ctpn_encode_jpeg_batch /
+ *   ctpn_write_annotated_files_device      ctpn_write_annotated_files; the files are byte-equal to theirs
+ *   ctpn_jpeg_entropy_encode_device        the seam the tests use, synchronous: n coefficient sets of any mix of sizes and of the layouts
+ *                                          ctpn_jpeg_entropy_encode takes, in host memory in NATURAL order: coef[i], layout8 + 8 i and
+ *                                          qt + 192 i are that call's arguments, out[i] / capacities[i] / bytes_out[i] are filled as it fills
+ *                                          them (CTPN_ERR_CAPACITY with the size set for a file that does not fit; out[i] == NULL with
+ *                                          capacity 0 sizes it), status_out[i] is its status. Per-file outcomes are data: the call itself
+ *                                          fails on bad arguments and HIP errors only; ctpn_last_error() holds the last failed file's message
+ *   ctpn_jpeg_entropy_encode_device_stats  of the ctx's last device-entropy encode: out4 = {files coded on the device, files handed to the
+ *                                          host half, blocks coded on the device, bytes copied device to host} */
+int    ctpn_encode_jpeg_batch_device(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
+                                     const size_t* capacities, size_t* bytes_out);
+int    ctpn_write_annotated_files_device(ctpn_ctx* ctx, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity,
+                                         const int* line_counts, double scale, const char* const* paths, int quality);
+int    ctpn_jpeg_entropy_encode_device(ctpn_ctx* ctx, const int16_t* const* coef, const int* layout8, const uint16_t* qt, int n, uint8_t* const* out,
+                                       const size_t* capacities, size_t* bytes_out, int* status_out);
+int    ctpn_jpeg_entropy_encode_device_stats(ctpn_ctx* ctx, long long* out4);
+
 /* ---- Rectified crops of the detected text lines, cut out on the device: one image of fixed height per line, what a recogniser behind the
  * detector reads. Not part of the reference (its demo stops at the outlines); additive to ABI 10. The batch's pixels are in HBM already
  * (ctpn_decode_jpeg_batch) and stay there: only the crops cross to the host, if at all. The rate of the kernel is unmeasured.

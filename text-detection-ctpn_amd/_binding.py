@@ -126,6 +126,12 @@ def _declare(lib):
         "ctpn_encode_jpeg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
                                              C.POINTER(C.c_size_t)]),
         "ctpn_write_annotated_files": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_double, C.POINTER(C.c_char_p), C.c_int]),
+        "ctpn_encode_jpeg_batch_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_size_t)]),
+        "ctpn_write_annotated_files_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_double, C.POINTER(C.c_char_p), C.c_int]),
+        "ctpn_jpeg_entropy_encode_device": (C.c_int, [vp, C.POINTER(C.POINTER(C.c_int16)), i32p, C.POINTER(C.c_uint16), C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
+                                                      C.POINTER(C.c_size_t), i32p]),
+        "ctpn_jpeg_entropy_encode_device_stats": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
         "ctpn_line_crop_width": (C.c_int, [f64p, C.c_int, C.c_int, i32p]),
         "ctpn_crop_lines": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_size_t,
                                       i32p, i32p]),
@@ -408,6 +414,31 @@ def jpeg_entropy_encode(coef, layout8, qt):
     out = np.empty((max(int(n.value), 1),), np.uint8)
     _check(lib.ctpn_jpeg_entropy_encode(_ptr(coef, C.c_int16), _ptr(l8, C.c_int), _ptr(qt, C.c_uint16), _ptr(out, C.c_uint8), out.size, C.byref(n)))
     return out[: n.value].tobytes()
+
+
+def jpeg_entropy_encode_device(ctx, coefs, layouts, qts, capacities=None):
+    """The device Huffman coder alone (ctpn_jpeg_entropy_encode_device; synchronous): n coefficient sets of any mix of sizes and layouts,
+    each as jpeg_entropy_encode takes it -> (files, sizes, status): files[i] = the bytes written into a buffer of capacities[i] bytes
+    (default: sized by a first call with no buffers; None where capacities[i] is 0), sizes[i] = the file's size as the library reports
+    it (also of a file that did not fit), status[i] = that file's status. ctpn_last_error() holds the last failed file's message."""
+    lib = load_library()
+    coefs = [np.ascontiguousarray(c, dtype=np.int16).reshape(-1) for c in coefs]
+    n = len(coefs)
+    l8 = np.ascontiguousarray(np.asarray(layouts, np.int32).reshape(n, 8))
+    qt = np.ascontiguousarray(np.asarray(qts, np.uint16).reshape(n, 192))
+    cptr = (C.POINTER(C.c_int16) * n)(*[_ptr(c, C.c_int16) for c in coefs])
+    sizes = (C.c_size_t * n)()
+    st = np.zeros((n,), np.int32)
+    if capacities is None:
+        _check(lib.ctpn_jpeg_entropy_encode_device(ctx._h, cptr, _ptr(l8, C.c_int), _ptr(qt, C.c_uint16), n, (C.c_void_p * n)(), (C.c_size_t * n)(), sizes, _ptr(st, C.c_int)))
+        capacities = [int(sizes[i]) for i in range(n)]
+        sizes = (C.c_size_t * n)()
+    bufs = [np.zeros((int(cap),), np.uint8) if cap else None for cap in capacities]
+    optr = (C.c_void_p * n)(*[b.ctypes.data if b is not None else None for b in bufs])
+    caps = (C.c_size_t * n)(*[int(cap) for cap in capacities])
+    _check(lib.ctpn_jpeg_entropy_encode_device(ctx._h, cptr, _ptr(l8, C.c_int), _ptr(qt, C.c_uint16), n, optr, caps, sizes, _ptr(st, C.c_int)))
+    files = [b[: min(int(sizes[i]), b.size)].tobytes() if b is not None else None for i, b in enumerate(bufs)]
+    return files, [int(sizes[i]) for i in range(n)], st
 
 
 def line_crop_width(rec, crop_h=32, max_w=512):
@@ -864,10 +895,19 @@ class Context:
         _check(self._lib.ctpn_jpeg_batch_fetch(self._h, C.c_void_p(int(device_ptr)), _ptr(out, C.c_uint8), out.size))
         return out
 
-    def encode_jpeg_batch(self, images=None, quality=95, device_ptr=None, shape=None):
+    def jpeg_encode_device_stats(self):
+        """Of the last device-entropy encode (ctpn_jpeg_entropy_encode_device_stats): dict(device=files coded on the device, host=files handed
+        to the host half, blocks=blocks coded on the device, d2h_bytes=bytes copied device to host)."""
+        out = (C.c_longlong * 4)()
+        _check(self._lib.ctpn_jpeg_entropy_encode_device_stats(self._h, out))
+        return {"device": int(out[0]), "host": int(out[1]), "blocks": int(out[2]), "d2h_bytes": int(out[3])}
+
+    def encode_jpeg_batch(self, images=None, quality=95, device_ptr=None, shape=None, entropy="host"):
         """cv2.imwrite's JPEG bytes of n BGR uint8 images of one size (ctpn_encode_jpeg_batch): colour conversion, chroma downsampling, DCT
         and quantiser on the device, Huffman coding on the ctx's host pool. images: (n, h, w, 3) on the host, or device_ptr + shape.
-        -> list of n bytes objects, byte-equal to Pillow's save(quality=quality, subsampling=2)."""
+        -> list of n bytes objects, byte-equal to Pillow's save(quality=quality, subsampling=2).
+        entropy="device": the Huffman coding runs on the device too (ctpn_encode_jpeg_batch_device); the files are byte-equal."""
+        fn = self._lib.ctpn_encode_jpeg_batch_device if self._entropy_form(entropy) else self._lib.ctpn_encode_jpeg_batch
         if device_ptr is None:
             images = np.ascontiguousarray(images, dtype=np.uint8)
             if images.ndim != 4 or images.shape[3] != 3:
@@ -882,15 +922,17 @@ class Context:
             bufs = np.empty((n, cap), np.uint8)
             ptrs = (C.c_void_p * n)(*[bufs[i].ctypes.data for i in range(n)])
             caps = (C.c_size_t * n)(*([cap] * n))
-            rc = self._lib.ctpn_encode_jpeg_batch(self._h, src, on_dev, n, h, w, int(quality), ptrs, caps, sizes)
+            rc = fn(self._h, src, on_dev, n, h, w, int(quality), ptrs, caps, sizes)
             if rc != CTPN_ERR_CAPACITY or cap == bound:
                 break
         _check(rc)
         return [bufs[i, : sizes[i]].tobytes() for i in range(n)]
 
-    def write_annotated_files(self, device_ptr, shape, recs, scale, paths, quality=95):
+    def write_annotated_files(self, device_ptr, shape, recs, scale, paths, quality=95, entropy="host"):
         """draw_boxes + cv2.resize(1 / scale) + cv2.imwrite (reference ctpn/demo.py:28-52) for a batch of device images
-        (ctpn_write_annotated_files): recs = one (M_i, 9) array per image, paths = one JPEG file name per image. The batch is not modified."""
+        (ctpn_write_annotated_files): recs = one (M_i, 9) array per image, paths = one JPEG file name per image. The batch is not modified.
+        entropy="device": ctpn_write_annotated_files_device, the same files with the Huffman coding on the device."""
+        fn = self._lib.ctpn_write_annotated_files_device if self._entropy_form(entropy) else self._lib.ctpn_write_annotated_files
         n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
         recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 9) for r in recs]
         assert len(recs) == n and len(paths) == n
@@ -901,7 +943,7 @@ class Context:
             packed[i, : r.shape[0]] = r
             counts[i] = r.shape[0]
         keep, arr = _path_array(list(paths))
-        _check(self._lib.ctpn_write_annotated_files(self._h, C.c_void_p(int(device_ptr)), n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
+        _check(fn(self._h, C.c_void_p(int(device_ptr)), n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
                                                     float(scale), arr, int(quality)))
 
     def crop_lines(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None,

@@ -1,11 +1,14 @@
 // C ABI of libctpn_hip.so, output unit: JPEG writing (kernels and the entropy coder: jpeg_enc.hip) and the annotated result images of
 // ctpn/demo.py:28-52 -- outlines (draw_boxes_kernel), cv2.resize by 1 / scale (preprocess.hip), cv2.imwrite -- for a batch on the device.
+// Two entropy forms behind one enc_enqueue / enc_finish: host (the default entry points) and device (the *_device entry points: jpeg_huff_enc.hip).
 #include "ctx.h"
 #include "jpeg_enc_pixel.h"
+#include "jpeg_huff_enc_dev.h"
 
 namespace ctpn {
 
-static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
+// room for coef_elems coefficients on the device and in the page-locked block
+static int enc_reserve_coef(ctpn_ctx* c, size_t coef_elems) {
   auto& E = c->enc;
   if (!E.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&E.ev_done, hipEventDisableTiming));
   if (coef_elems > E.coef_elems) {
@@ -18,6 +21,13 @@ static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
     CTPN_HIP_TRY(hipHostMalloc((void**)&E.coef_host, coef_elems * sizeof(int16_t)));
     E.coef_elems = coef_elems;
   }
+  return CTPN_OK;
+}
+
+static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
+  auto& E = c->enc;
+  const int rc = enc_reserve_coef(c, coef_elems);
+  if (rc) return rc;
   if (!E.qtab_dev) {
     CTPN_HIP_TRY(hipMalloc(&E.qtab_dev, 128 * sizeof(JencQ)));
     CTPN_HIP_TRY(hipHostMalloc(&E.qtab_host, 128 * sizeof(JencQ)));
@@ -30,76 +40,244 @@ static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
   return CTPN_OK;
 }
 
-// device half in the ctx's copy queue: pixels (device, n x h x w x 3) -> coefficients in the page-locked block; no host wait
-static int enc_enqueue(ctpn_ctx* c, const uint8_t* pixels_dev, int n, int h, int w, int quality, JpegGeom& g) {
+// device half in the ctx's copy queue: pixels (device, n x h x w x 3) -> coefficients, in the page-locked block too unless the device codes
+// them as well (device_entropy); no host wait
+static int enc_enqueue(ctpn_ctx* c, const uint8_t* pixels_dev, int n, int h, int w, int quality, JpegGeom& g, bool device_entropy) {
   jpeg_enc_geom(h, w, g);
   int rc = enc_reserve(c, (size_t)n * (size_t)g.coef_per_img, quality);
   if (rc) return rc;
   auto& E = c->enc;
   if ((rc = launch_jpeg_fdct(pixels_dev, E.coef_dev, (const JencQ*)E.qtab_dev, g, n, c->stream_c))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host, E.coef_dev, (size_t)n * (size_t)g.coef_per_img * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
+  if (!device_entropy) CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host, E.coef_dev, (size_t)n * (size_t)g.coef_per_img * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
   CTPN_HIP_TRY(hipEventRecord(E.ev_done, c->stream_c));
   return CTPN_OK;
 }
 
-// host half on the ctx's pool, one image per worker: into the caller's buffers (out), or into files (paths)
-static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths) {
+// one image's file into the caller's buffer (out, bytes_out) or into a file of its own (path); code(buffer, capacity, &bytes) writes the
+// file's bytes and returns their status. Runs on a worker thread: nothing may leave it
+template <class Code>
+static void enc_deliver(size_t bound, uint8_t* out, size_t capacity, size_t* bytes_out, const char* path, int& st, std::string& msg, const Code& code) {
+  try {
+    size_t bytes = 0;
+    if (path) {
+      static thread_local std::vector<uint8_t> filebuf;      // one per worker thread, reused from batch to batch
+      if (filebuf.size() < bound) filebuf.resize(bound);
+      st = code(filebuf.data(), filebuf.size(), &bytes);
+      if (st) { msg = ctpn_last_error(); return; }
+      std::FILE* f = std::fopen(path, "wb");
+      if (!f) { st = CTPN_ERR_ARG; msg = std::string("cannot open ") + path; return; }
+      const bool ok = std::fwrite(filebuf.data(), 1, bytes, f) == bytes;
+      if (std::fclose(f) != 0 || !ok) { st = CTPN_ERR_ARG; msg = std::string("write failed: ") + path; }
+      if (filebuf.capacity() > ((size_t)64 << 20)) std::vector<uint8_t>().swap(filebuf);
+    } else {
+      st = code(out, capacity, &bytes);
+      *bytes_out = bytes;
+      if (st) msg = ctpn_last_error();
+    }
+  } catch (const std::exception& e) { st = CTPN_ERR_CAPACITY; msg = e.what(); }
+}
+
+// ---- the device-entropy form ---------------------------------------------------------------------------------------------------------
+struct EncJob {                       // one image of a device-entropy call
+  int h, w, hs, vs; const uint16_t* qt;      // the file's frame
+  long long coef_off;                 // its coefficients in E.coef_dev, int16 elements
+  const int16_t* coef_host;           // the same on the host in natural order (the test seam), or null: zig-zag, copied from the device if the host half needs them
+  uint8_t* out; size_t capacity; size_t* bytes_out; const char* path;
+  bool on_host = false;               // the host half codes it
+  const uint8_t* scan = nullptr; size_t scan_have = 0, scan_bytes = 0;      // else: the stuffed scan body (page-locked), the bytes of it that were copied, its size
+  int st = CTPN_OK; std::string msg;
+  uint32_t mcux() const { return (uint32_t)((w + 8 * hs - 1) / (8 * hs)); }
+  uint32_t mcus() const { return mcux() * (uint32_t)((h + 8 * vs - 1) / (8 * vs)); }
+  uint64_t blocks() const { return (uint64_t)mcus() * (uint32_t)(hs * vs + 2); }
+};
+
+static int grow_host(uint8_t** p, size_t& have, size_t need) {
+  if (need <= have) return CTPN_OK;
+  if (*p) CTPN_HIP_TRY(hipHostFree(*p));
+  *p = nullptr; have = 0;
+  CTPN_HIP_TRY(hipHostMalloc((void**)p, need));
+  have = need;
+  return CTPN_OK;
+}
+
+// one launch group (at most JHE_MAX_BLOCKS blocks): the kernels, then the result words -- the wait of the host form on its coefficients --,
+// then exactly the bytes the sizes say: scan bodies, or the coefficients of an image whose flag is raised
+static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vector<int>& use, bool zigzag) {
   auto& E = c->enc;
+  hipStream_t qs = c->stream_c;
+  const size_t m = use.size();
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  int rc;
+  if ((rc = grow_host(&E.huff_host, E.huff_host_bytes, m * (sizeof(JheImg) + sizeof(JheRes))))) return rc;
+  JheImg* imgs = (JheImg*)E.huff_host;
+  JheRes* res = (JheRes*)(E.huff_host + m * sizeof(JheImg));
+  uint32_t blk = 0, words = 0, chunks = 0, outb = 0, max_blocks = 0, max_chunks = 0;
+  for (size_t k = 0; k < m; ++k) {
+    const EncJob& J = jobs[use[k]];
+    JheImg& I = imgs[k];
+    I.coef_off = J.coef_off; I.mcux = J.mcux(); I.nmcu = J.mcus(); I.hs = (uint32_t)J.hs; I.vs = (uint32_t)J.vs;
+    I.nblk = (uint32_t)J.blocks(); I.blk0 = blk;
+    I.word0 = words; I.nwords = I.nblk * (JHE_BLOCK_BYTES / 4);
+    I.chunk0 = chunks; I.nchunk = (I.nblk * JHE_BLOCK_BYTES + JHE_CHUNK - 1) / JHE_CHUNK;
+    I.out0 = outb; I.out_cap = I.nblk * 2 * JHE_BLOCK_BYTES;
+    blk += I.nblk; words += I.nwords; chunks += I.nchunk; outb += I.out_cap;
+    max_blocks = std::max(max_blocks, I.nblk); max_chunks = std::max(max_chunks, I.nchunk);
+  }
+  const size_t o_img = 0, o_res = up(o_img + m * sizeof(JheImg)), o_len = up(o_res + m * sizeof(JheRes)), o_cnt = up(o_len + (size_t)blk * 4),
+               o_uns = up(o_cnt + (size_t)chunks * 4), o_out = up(o_uns + (size_t)words * 4), total = o_out + outb;
+  if ((rc = grow_dev((void**)&E.huff_dev, E.huff_bytes, total))) return rc;
+  if (!E.huff_tab_dev) {
+    static const JheTables T = [] { JheTables t; jhe_build_tables(t); return t; }();
+    CTPN_HIP_TRY(hipMalloc(&E.huff_tab_dev, sizeof(JheTables)));
+    CTPN_HIP_TRY(hipMemcpy(E.huff_tab_dev, &T, sizeof(JheTables), hipMemcpyHostToDevice));
+  }
+  JheBatchDev B;
+  B.imgs = (const JheImg*)(E.huff_dev + o_img); B.res = (JheRes*)(E.huff_dev + o_res); B.len = (uint32_t*)(E.huff_dev + o_len); B.cnt = (uint32_t*)(E.huff_dev + o_cnt);
+  B.uns = (uint32_t*)(E.huff_dev + o_uns); B.out = E.huff_dev + o_out; B.coef = E.coef_dev; B.tables = (const JheTables*)E.huff_tab_dev;
+  B.n = (int)m; B.max_blocks = max_blocks; B.max_chunks = max_chunks;
+  CTPN_HIP_TRY(hipMemcpyAsync(E.huff_dev + o_img, imgs, m * sizeof(JheImg), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_res, 0, m * sizeof(JheRes), qs));
+  CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_uns, 0, (size_t)words * 4, qs));      // the write pass ORs shared words into it
+  if ((rc = launch_jpeg_huff_enc(B, zigzag, qs))) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(res, E.huff_dev + o_res, m * sizeof(JheRes), hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipEventRecord(E.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
+  c->jhe_stats[3] += (long long)(m * sizeof(JheRes));
+  size_t scan_total = 0;
+  for (size_t k = 0; k < m; ++k) {
+    EncJob& J = jobs[use[k]];
+    if (res[k].flag || res[k].bytes > imgs[k].out_cap) { J.on_host = true; continue; }
+    J.scan_bytes = res[k].bytes;
+    J.scan_have = J.path ? J.scan_bytes : (J.out ? std::min(J.scan_bytes, J.capacity) : 0);
+    scan_total += up(J.scan_have);
+  }
+  if ((rc = grow_host(&E.scan_host, E.scan_host_bytes, scan_total))) return rc;
+  size_t at = 0;
+  bool copies = false;
+  for (size_t k = 0; k < m; ++k) {
+    EncJob& J = jobs[use[k]];
+    if (J.on_host) {
+      ++c->jhe_stats[1];
+      if (J.coef_host) continue;
+      const size_t bytes = (size_t)imgs[k].nblk * 64 * sizeof(int16_t);
+      CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + J.coef_off, E.coef_dev + J.coef_off, bytes, hipMemcpyDeviceToHost, qs));
+      c->jhe_stats[3] += (long long)bytes; copies = true;
+      continue;
+    }
+    ++c->jhe_stats[0]; c->jhe_stats[2] += imgs[k].nblk;
+    J.scan = E.scan_host + at;
+    if (J.scan_have) {
+      CTPN_HIP_TRY(hipMemcpyAsync(E.scan_host + at, E.huff_dev + o_out + imgs[k].out0, J.scan_have, hipMemcpyDeviceToHost, qs));
+      c->jhe_stats[3] += (long long)J.scan_have; copies = true;
+    }
+    at += up(J.scan_have);
+  }
+  if (copies) {
+    CTPN_HIP_TRY(hipEventRecord(E.ev_done, qs));
+    CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
+  }
+  return CTPN_OK;
+}
+
+// device entropy coding of the jobs' coefficients (in E.coef_dev, all zig-zag or all natural) and delivery of the files, group by group;
+// the per-file outcomes are in the jobs
+static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
+  auto& E = c->enc;
+  if (!E.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&E.ev_done, hipEventDisableTiming));
+  c->jhe_stats[0] = c->jhe_stats[1] = c->jhe_stats[2] = c->jhe_stats[3] = 0;
+  const int n = (int)jobs.size();
+  for (int i0 = 0; i0 < n;) {
+    std::vector<int> use;
+    uint64_t tot = 0;
+    int i1 = i0;
+    for (; i1 < n; ++i1) {
+      const uint64_t nb = jobs[i1].blocks();
+      if (nb > (uint64_t)JHE_MAX_BLOCKS) {      // offsets of 32 bits do not hold it: the host half's
+        jobs[i1].on_host = true; ++c->jhe_stats[1];
+        if (!jobs[i1].coef_host) {
+          CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + jobs[i1].coef_off, E.coef_dev + jobs[i1].coef_off, (size_t)nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
+          CTPN_HIP_TRY(hipEventRecord(E.ev_done, c->stream_c));
+          CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
+          c->jhe_stats[3] += (long long)((size_t)nb * 64 * sizeof(int16_t));
+        }
+        continue;
+      }
+      if (tot + nb > (uint64_t)JHE_MAX_BLOCKS || use.size() == 65535) break;
+      use.push_back(i1); tot += nb;
+    }
+    int rc;
+    if (!use.empty() && (rc = enc_huff_group(c, jobs, use, zigzag))) return rc;
+    c->pool->run(i1 - i0, [&](int k) {
+      EncJob& J = jobs[(size_t)i0 + k];
+      const size_t bound = J.on_host ? jpeg_encode_capacity(J.h, J.w) : J.scan_bytes + 1024;
+      if (J.on_host) {
+        const int16_t* coef = J.coef_host ? J.coef_host : E.coef_host + J.coef_off;
+        const bool zz = !J.coef_host;
+        enc_deliver(bound, J.out, J.capacity, J.bytes_out, J.path, J.st, J.msg, [&](uint8_t* buf, size_t cap, size_t* bytes) {
+          return jpeg_entropy_encode(coef, zz, J.h, J.w, J.hs, J.vs, J.qt, buf, cap, bytes); });
+      } else {
+        enc_deliver(bound, J.out, J.capacity, J.bytes_out, J.path, J.st, J.msg, [&](uint8_t* buf, size_t cap, size_t* bytes) {
+          return jpeg_enc_assemble(J.h, J.w, J.hs, J.vs, J.qt, J.scan, J.scan_have, J.scan_bytes, buf, cap, bytes); });
+      }
+    });
+    i0 = i1;
+  }
+  return CTPN_OK;
+}
+
+// second half of both forms: into the caller's buffers (out), or into files (paths). Host entropy: the coefficients are awaited and coded
+// on the ctx's pool, one image per worker. Device entropy: the kernels of jpeg_huff_enc.hip code them; the pool adds header and EOI
+static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths,
+                      bool device_entropy) {
+  auto& E = c->enc;
   uint16_t qt[192];
   jpeg_enc_qtables(quality, qt, nullptr);
   std::vector<int> st((size_t)n, CTPN_OK);
   std::vector<std::string> msg((size_t)n);
-  const size_t bound = jpeg_encode_capacity(g.h, g.w);
-  c->pool->run(n, [&](int i) {
-    try {
+  if (device_entropy) {
+    std::vector<EncJob> jobs((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      EncJob& J = jobs[i];
+      J.h = g.h; J.w = g.w; J.hs = 2; J.vs = 2; J.qt = qt; J.coef_off = (long long)i * g.coef_per_img; J.coef_host = nullptr;
+      J.out = paths ? nullptr : out[i]; J.capacity = paths ? 0 : capacities[i]; J.bytes_out = paths ? nullptr : bytes_out + i; J.path = paths ? paths[i] : nullptr;
+    }
+    const int rc = enc_huff(c, jobs, true);
+    if (rc) return rc;
+    for (int i = 0; i < n; ++i) { st[i] = jobs[i].st; msg[i] = jobs[i].msg; }
+  } else {
+    CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
+    const size_t bound = jpeg_encode_capacity(g.h, g.w);
+    c->pool->run(n, [&](int i) {
       const int16_t* coef = E.coef_host + (size_t)i * (size_t)g.coef_per_img;
-      size_t bytes = 0;
-      if (paths) {
-        static thread_local std::vector<uint8_t> filebuf;      // one per worker thread, reused from batch to batch
-        if (filebuf.size() < bound) filebuf.resize(bound);
-        st[i] = jpeg_entropy_encode(coef, true, g.h, g.w, 2, 2, qt, filebuf.data(), filebuf.size(), &bytes);
-        if (st[i]) { msg[i] = ctpn_last_error(); return; }
-        std::FILE* f = std::fopen(paths[i], "wb");
-        if (!f) { st[i] = CTPN_ERR_ARG; msg[i] = std::string("cannot open ") + paths[i]; return; }
-        const bool ok = std::fwrite(filebuf.data(), 1, bytes, f) == bytes;
-        if (std::fclose(f) != 0 || !ok) { st[i] = CTPN_ERR_ARG; msg[i] = std::string("write failed: ") + paths[i]; }
-        if (filebuf.capacity() > ((size_t)64 << 20)) std::vector<uint8_t>().swap(filebuf);
-      } else {
-        st[i] = jpeg_entropy_encode(coef, true, g.h, g.w, 2, 2, qt, out[i], capacities[i], &bytes);
-        bytes_out[i] = bytes;
-        if (st[i]) msg[i] = ctpn_last_error();
-      }
-    } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }      // nothing may leave a worker thread
-  });
+      enc_deliver(bound, paths ? nullptr : out[i], paths ? 0 : capacities[i], paths ? nullptr : bytes_out + i, paths ? paths[i] : nullptr, st[i], msg[i],
+                  [&](uint8_t* buf, size_t cap, size_t* bytes) { return jpeg_entropy_encode(coef, true, g.h, g.w, 2, 2, qt, buf, cap, bytes); });
+    });
+  }
   for (int i = 0; i < n; ++i) if (st[i]) return fail(st[i], std::string(who) + ": image " + std::to_string(i) + ": " + msg[i]);
   return CTPN_OK;
 }
 
-}  // namespace ctpn
-
-extern "C" {
-
-size_t ctpn_jpeg_encode_capacity(int h, int w) { return (h > 0 && w > 0 && h <= 65535 && w <= 65535) ? jpeg_encode_capacity(h, w) : 0; }
-
-int ctpn_jpeg_entropy_encode(const int16_t* coef, const int* layout8, const uint16_t* qt, uint8_t* out, size_t capacity, size_t* bytes_out) {
-  if (!coef || !layout8 || !qt || !bytes_out || (!out && capacity)) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode: null pointer");
-  const int h = layout8[0], w = layout8[1], nc = layout8[2], hs = layout8[3] & 0xff, orient = (layout8[3] >> 8) + 1;
+// size and sampling out of the eight layout ints ctpn_jpeg_entropy_decode returns
+static int enc_layout(const int* layout8, int& h, int& w, int& hs, int& vs) {
+  h = layout8[0]; w = layout8[1]; hs = layout8[3] & 0xff; vs = 0;
+  const int nc = layout8[2], orient = (layout8[3] >> 8) + 1;
   if (nc != 3 || orient != 1) return fail(CTPN_ERR_UNSUPPORTED, "ctpn_jpeg_entropy_encode: three components (YCbCr) and EXIF orientation 1 only");
   if (h <= 0 || w <= 0 || layout8[5] <= 0 || layout8[7] <= 0 || (hs != 1 && hs != 2)) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode: bad layout");
-  const int vs = layout8[6] / layout8[7];
+  vs = layout8[6] / layout8[7];
   if ((vs != 1 && vs != 2) || layout8[4] != layout8[5] * hs || layout8[6] != layout8[7] * vs || layout8[5] != (w + 8 * hs - 1) / (8 * hs) || layout8[7] != (h + 8 * vs - 1) / (8 * vs))
     return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode: the block counts do not belong to the size and sampling");
-  return jpeg_entropy_encode(coef, false, h, w, hs, vs, qt, out, capacity, bytes_out);
+  return CTPN_OK;
 }
 
-int ctpn_encode_jpeg_batch(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
-                           const size_t* capacities, size_t* bytes_out) {
-  if (!c || !images || !out || !capacities || !bytes_out) return fail(CTPN_ERR_ARG, "ctpn_encode_jpeg_batch: null pointer");
-  if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535) return fail(CTPN_ERR_ARG, "ctpn_encode_jpeg_batch: empty batch / bad size");
-  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, "ctpn_encode_jpeg_batch: quality must be 1 .. 100");
-  for (int i = 0; i < n; ++i) if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, "ctpn_encode_jpeg_batch: null output pointer");
-  if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_encode_jpeg_batch: post-processing-only ctx");
+// ctpn_encode_jpeg_batch / ctpn_encode_jpeg_batch_device
+static int encode_batch_impl(ctpn_ctx* c, const char* who_, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
+                             const size_t* capacities, size_t* bytes_out, bool device_entropy) {
+  const std::string who(who_);
+  if (!c || !images || !out || !capacities || !bytes_out) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size");
+  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
+  for (int i = 0; i < n; ++i) if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, who + ": null output pointer");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   auto& E = c->enc;
   const uint8_t* px = images;
@@ -113,25 +291,27 @@ int ctpn_encode_jpeg_batch(ctpn_ctx* c, const uint8_t* images, int images_on_dev
     for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(c->stream_c, J.ev_ready, 0));
   }
   JpegGeom g;
-  if ((rc = enc_enqueue(c, px, n, h, w, quality, g))) return rc;
-  return enc_finish(c, "ctpn_encode_jpeg_batch", g, n, quality, out, capacities, bytes_out, nullptr);
+  if ((rc = enc_enqueue(c, px, n, h, w, quality, g, device_entropy))) return rc;
+  return enc_finish(c, who_, g, n, quality, out, capacities, bytes_out, nullptr, device_entropy);
 }
 
-int ctpn_write_annotated_files(ctpn_ctx* c, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
-                               double scale, const char* const* paths, int quality) {
-  if (!c || !images_dev || !line_counts || !paths) return fail(CTPN_ERR_ARG, "ctpn_write_annotated_files: null pointer");
-  if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || line_capacity < 0 || !(scale > 0.0)) return fail(CTPN_ERR_ARG, "ctpn_write_annotated_files: empty batch / bad size / bad scale");
-  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, "ctpn_write_annotated_files: quality must be 1 .. 100");
+// ctpn_write_annotated_files / ctpn_write_annotated_files_device
+static int write_annotated_impl(ctpn_ctx* c, const char* who_, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
+                                double scale, const char* const* paths, int quality, bool device_entropy) {
+  const std::string who(who_);
+  if (!c || !images_dev || !line_counts || !paths) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || line_capacity < 0 || !(scale > 0.0)) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size / bad scale");
+  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
   for (int i = 0; i < n; ++i) {
-    if (!paths[i]) return fail(CTPN_ERR_ARG, "ctpn_write_annotated_files: null path");
-    if (line_counts[i] < 0 || line_counts[i] > line_capacity || (line_counts[i] > 0 && !recs)) return fail(CTPN_ERR_ARG, "ctpn_write_annotated_files: line count out of range");
+    if (!paths[i]) return fail(CTPN_ERR_ARG, who + ": null path");
+    if (line_counts[i] < 0 || line_counts[i] > line_capacity || (line_counts[i] > 0 && !recs)) return fail(CTPN_ERR_ARG, who + ": line count out of range");
   }
-  if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_write_annotated_files: post-processing-only ctx");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   // demo.py:51: cv2.resize(img, None, None, fx = 1 / scale, fy = 1 / scale); the identity (scale 1) is a copy there and no launch here
   const double f = 1.0 / scale;
   int dh = h, dw = w;
   if (f != 1.0) { dh = resize_out_dim(h, f); dw = resize_out_dim(w, f); }
-  if (dh <= 0 || dw <= 0 || dh > 65535 || dw > 65535) return fail(CTPN_ERR_ARG, "ctpn_write_annotated_files: the resized image is empty or too large for a JPEG file");
+  if (dh <= 0 || dw <= 0 || dh > 65535 || dw > 65535) return fail(CTPN_ERR_ARG, who + ": the resized image is empty or too large for a JPEG file");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   auto& E = c->enc;
   hipStream_t qs = c->stream_c;
@@ -156,8 +336,82 @@ int ctpn_write_annotated_files(ctpn_ctx* c, const uint8_t* images_dev, int n, in
     px = E.rs_dev;
   }
   JpegGeom g;
-  if ((rc = enc_enqueue(c, px, n, dh, dw, quality, g))) return rc;
-  return enc_finish(c, "ctpn_write_annotated_files", g, n, quality, nullptr, nullptr, nullptr, paths);
+  if ((rc = enc_enqueue(c, px, n, dh, dw, quality, g, device_entropy))) return rc;
+  return enc_finish(c, who_, g, n, quality, nullptr, nullptr, nullptr, paths, device_entropy);
+}
+
+}  // namespace ctpn
+
+extern "C" {
+
+size_t ctpn_jpeg_encode_capacity(int h, int w) { return (h > 0 && w > 0 && h <= 65535 && w <= 65535) ? jpeg_encode_capacity(h, w) : 0; }
+
+int ctpn_jpeg_entropy_encode(const int16_t* coef, const int* layout8, const uint16_t* qt, uint8_t* out, size_t capacity, size_t* bytes_out) {
+  if (!coef || !layout8 || !qt || !bytes_out || (!out && capacity)) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode: null pointer");
+  int h, w, hs, vs;
+  const int rc = enc_layout(layout8, h, w, hs, vs);
+  if (rc) return rc;
+  return jpeg_entropy_encode(coef, false, h, w, hs, vs, qt, out, capacity, bytes_out);
+}
+
+int ctpn_jpeg_entropy_encode_device(ctpn_ctx* c, const int16_t* const* coef, const int* layout8, const uint16_t* qt, int n, uint8_t* const* out, const size_t* capacities,
+                                    size_t* bytes_out, int* status_out) {
+  if (!c || !coef || !layout8 || !qt || !out || !capacities || !bytes_out || !status_out || n <= 0) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode_device: null pointer / empty batch");
+  for (int i = 0; i < n; ++i) if (!coef[i] || (!out[i] && capacities[i])) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode_device: null coefficient / output pointer");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_jpeg_entropy_encode_device: post-processing-only ctx");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  // what the host half refuses before it codes anything is refused here in its words; the rest is staged
+  std::vector<EncJob> jobs;
+  std::vector<int> owner;
+  size_t elems = 0;
+  for (int i = 0; i < n; ++i) {
+    EncJob J;
+    status_out[i] = enc_layout(layout8 + 8 * (size_t)i, J.h, J.w, J.hs, J.vs);
+    if (!status_out[i]) status_out[i] = jpeg_enc_check(J.h, J.w, J.hs, J.vs, qt + 192 * (size_t)i);
+    if (status_out[i]) continue;
+    J.qt = qt + 192 * (size_t)i; J.coef_off = (long long)elems; J.coef_host = coef[i];
+    J.out = out[i]; J.capacity = capacities[i]; J.bytes_out = bytes_out + i; J.path = nullptr;
+    elems += (size_t)J.blocks() * 64;
+    jobs.push_back(J); owner.push_back(i);
+  }
+  c->jhe_stats[0] = c->jhe_stats[1] = c->jhe_stats[2] = c->jhe_stats[3] = 0;
+  if (jobs.empty()) return CTPN_OK;
+  int rc = enc_reserve_coef(c, elems);
+  if (rc) return rc;
+  for (const EncJob& J : jobs)
+    CTPN_HIP_TRY(hipMemcpyAsync(c->enc.coef_dev + J.coef_off, J.coef_host, (size_t)J.blocks() * 64 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream_c));
+  if ((rc = enc_huff(c, jobs, false))) return rc;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    status_out[owner[k]] = jobs[k].st;
+    if (jobs[k].st) set_error(jobs[k].msg);      // (the worker thread's message)
+  }
+  return CTPN_OK;
+}
+
+int ctpn_jpeg_entropy_encode_device_stats(ctpn_ctx* c, long long* out4) {
+  if (!c || !out4) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_encode_device_stats: null pointer");
+  std::memcpy(out4, c->jhe_stats, sizeof(c->jhe_stats));
+  return CTPN_OK;
+}
+
+int ctpn_encode_jpeg_batch(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
+                           const size_t* capacities, size_t* bytes_out) {
+  return encode_batch_impl(c, "ctpn_encode_jpeg_batch", images, images_on_device, n, h, w, quality, out, capacities, bytes_out, false);
+}
+
+int ctpn_encode_jpeg_batch_device(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
+                                  const size_t* capacities, size_t* bytes_out) {
+  return encode_batch_impl(c, "ctpn_encode_jpeg_batch_device", images, images_on_device, n, h, w, quality, out, capacities, bytes_out, true);
+}
+
+int ctpn_write_annotated_files(ctpn_ctx* c, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
+                               double scale, const char* const* paths, int quality) {
+  return write_annotated_impl(c, "ctpn_write_annotated_files", images_dev, n, h, w, recs, line_capacity, line_counts, scale, paths, quality, false);
+}
+
+int ctpn_write_annotated_files_device(ctpn_ctx* c, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
+                                      double scale, const char* const* paths, int quality) {
+  return write_annotated_impl(c, "ctpn_write_annotated_files_device", images_dev, n, h, w, recs, line_capacity, line_counts, scale, paths, quality, true);
 }
 
 }  // extern "C"

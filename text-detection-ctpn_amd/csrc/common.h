@@ -355,6 +355,18 @@ void jpeg_enc_qtables(int quality, uint16_t* qt3x64, JencQ* q2x64);
 size_t jpeg_encode_capacity(int h, int w);
 int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, int vs, const uint16_t* qt3x64, uint8_t* out, size_t capacity, size_t* bytes_out);
 int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JpegGeom& g, int n, hipStream_t s);
+int jpeg_enc_check(int h, int w, int hs, int vs, const uint16_t* qt3x64);
+int jpeg_enc_assemble(int h, int w, int hs, int vs, const uint16_t* qt3x64, const uint8_t* scan, size_t have, size_t scan_bytes, uint8_t* out, size_t capacity, size_t* bytes_out);
+
+// jpeg_huff_enc.hip: the Huffman coding itself on the device (per-thread source and the structures: jpeg_huff_enc_dev.h). One launch group:
+// n images' descriptors, the batch's coefficients, and the group's per-block, per-chunk, unstuffed (cleared by the caller) and stuffed parts
+struct JheImg; struct JheTables; struct JheRes;
+struct JheBatchDev {
+  const JheImg* imgs; const int16_t* coef; const JheTables* tables;
+  uint32_t* len; uint32_t* cnt; uint32_t* uns; uint8_t* out; JheRes* res;
+  int n; uint32_t max_blocks, max_chunks;      // the largest image's
+};
+int launch_jpeg_huff_enc(const JheBatchDev& B, bool zigzag, hipStream_t s);
 int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* counts_dev, int line_capacity, int n, int h, int w, hipStream_t s);
 
 // crop.hip: rectified crops of text lines out of device images (arithmetic: crop_pixel.h). The host fills one descriptor per line

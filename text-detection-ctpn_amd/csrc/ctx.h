@@ -196,7 +196,14 @@ struct ctpn_ctx {
     double* recs_dev = nullptr; size_t recs_bytes = 0; int* cnt_dev = nullptr; size_t cnt_n = 0;
     void* qtab_dev = nullptr; void* qtab_host = nullptr; int qtab_quality = 0;               // JencQ[2][64] of the quality last used
     hipEvent_t ev_done = nullptr;
+    // the device-entropy form (jpeg_huff_enc.hip; ctpn_encode_jpeg_batch_device, ...): one device block for a launch group's descriptors,
+    // result words, lengths, counts, unstuffed and stuffed streams; the code tables; page-locked: descriptors + result words, scan bytes
+    uint8_t* huff_dev = nullptr; size_t huff_bytes = 0;
+    void* huff_tab_dev = nullptr;
+    uint8_t* huff_host = nullptr; size_t huff_host_bytes = 0;
+    uint8_t* scan_host = nullptr; size_t scan_host_bytes = 0;
   } enc;
+  long long jhe_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_encode_device_stats
   // ctpn_crop_lines (api_crops.hip): ONE set of buffers, for the reason the writer's set is one (the call returns when its crops are
   // complete), allocated on first use and grown to the largest call seen
   struct CropBufs {

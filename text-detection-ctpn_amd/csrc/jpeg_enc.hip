@@ -4,6 +4,7 @@
 //            planes live in LDS only), int16 coefficients in zig-zag order, [block rows][block columns][64] per component over the MCU grid
 //            (JpegGeom, as the decoder); draw_boxes_kernel, ctpn_draw_boxes on device images;
 //   host   : baseline Huffman coding with the standard tables K.3 - K.6 and the header (one image per worker thread of the ctx's pool).
+//            (The opt-in second form codes on the device too: jpeg_huff_enc.hip; the host then adds header and EOI, jpeg_enc_assemble.)
 // cv2.imwrite's defaults are libjpeg at quality 95, 4:2:0, islow DCT, standard Huffman tables, no optimisation; Pillow's
 // save(quality = 95, subsampling = 2) is the same encoder family (libjpeg-turbo) with the same settings, and the files written here are
 // byte-equal to Pillow's (tests/test_jpeg_encode.py on the CPU from the kernels' own source text, tests/test_gpu_jpeg_encode.py through the
@@ -15,6 +16,7 @@
 
 #include "common.h"
 #include "jpeg_enc_pixel.h"
+#include "jpeg_enc_tables.h"
 
 namespace ctpn {
 
@@ -28,21 +30,6 @@ static const uint8_t kLumaQ[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 1
                                    18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
 static const uint8_t kChromaQ[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
                                      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-static const uint8_t kBitsDc[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-static const uint8_t kValsDc[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-static const uint8_t kBitsAc[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
-static const uint8_t kValsAc[2][162] = {
-    {1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6, 19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240, 36, 51, 98, 114, 130, 9, 10, 22, 23,
-     24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106,
-     115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169,
-     170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 225, 226, 227, 228, 229,
-     230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250},
-    {0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65, 81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240, 21, 98, 114, 209, 10, 22, 36, 52, 225, 37,
-     241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106,
-     115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168,
-     169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 226, 227, 228, 229,
-     230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250}};
-
 // jcparam.c: jpeg_quality_scaling + jpeg_add_quant_table with force_baseline (1 .. 255). qt: 3 x 64, natural order (component 2 = component 1's)
 void jpeg_enc_qtables(int quality, uint16_t* qt3x64, JencQ* q2x64) {
   const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
@@ -146,15 +133,16 @@ static inline bool jenc_block(JencSink& s, const int16_t* blk, int& pred, const 
   return true;
 }
 
-// coef: [component][block rows][block columns][64] over the MCU grid, zig-zag (zigzag = true: what jpeg_fdct_kernel writes) or natural
-// order (what ctpn_jpeg_entropy_decode returns); three components, luma sampling hs x vs, chroma 1 x 1; qt: 3 x 64, natural order.
-// *bytes_out = the size of the file, also when it does not fit (CTPN_ERR_CAPACITY)
-int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, int vs, const uint16_t* qt3x64, uint8_t* out, size_t capacity, size_t* bytes_out) {
+// what both entropy forms ask of a file's frame before a byte is written
+static int jenc_check(int h, int w, int hs, int vs, const uint16_t* qt3x64) {
   if (h <= 0 || w <= 0 || h > 65535 || w > 65535 || (hs != 1 && hs != 2) || (vs != 1 && vs != 2)) return fail(CTPN_ERR_ARG, "jpeg encode: bad size / sampling");
   for (int k = 0; k < 192; ++k) if (qt3x64[k] < 1 || qt3x64[k] > 255) return fail(CTPN_ERR_UNSUPPORTED, "jpeg encode: baseline files hold 8-bit quantisation values (1 .. 255)");
   if (std::memcmp(qt3x64 + 64, qt3x64 + 128, 64 * sizeof(uint16_t)) != 0) return fail(CTPN_ERR_UNSUPPORTED, "jpeg encode: the two chroma components share one quantisation table");
-  const JencTables& T = jenc_tables();
-  JencSink s{out, out ? capacity : 0};
+  return CTPN_OK;
+}
+
+// SOI .. SOS: kHeaderBytes bytes
+static void jenc_header(JencSink& s, int h, int w, int hs, int vs, const uint16_t* qt3x64) {
   static const uint8_t kHead[20] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
   s.raw(kHead, 20);
   for (int t = 0; t < 2; ++t) {
@@ -169,6 +157,41 @@ int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, 
   }
   static const uint8_t kSos[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
   s.raw(kSos, 14);
+}
+
+// EOI, the file's size, and the verdict on the buffer
+static int jenc_close(JencSink& s, size_t* bytes_out) {
+  s.byte(0xFF); s.byte(0xD9);
+  if (bytes_out) *bytes_out = s.n;
+  if (s.n > s.cap) return fail(CTPN_ERR_CAPACITY, "jpeg encode: output buffer too small (" + std::to_string(s.n) + " bytes needed)");
+  return CTPN_OK;
+}
+
+int jpeg_enc_check(int h, int w, int hs, int vs, const uint16_t* qt3x64) { return jenc_check(h, w, hs, vs, qt3x64); }
+
+// the file around a scan body that is already coded and stuffed (the device-entropy form, jpeg_huff_enc.hip): of its scan_bytes bytes the
+// first `have` are at `scan` -- all of them, or as many as the buffer can still take behind the header
+int jpeg_enc_assemble(int h, int w, int hs, int vs, const uint16_t* qt3x64, const uint8_t* scan, size_t have, size_t scan_bytes, uint8_t* out, size_t capacity, size_t* bytes_out) {
+  const int rc = jenc_check(h, w, hs, vs, qt3x64);
+  if (rc) return rc;
+  JencSink s{out, out ? capacity : 0};
+  jenc_header(s, h, w, hs, vs, qt3x64);
+  have = have < scan_bytes ? have : scan_bytes;
+  const size_t room = s.cap > s.n ? s.cap - s.n : 0, put = have < room ? have : room;
+  if (put) std::memcpy(s.out + s.n, scan, put);
+  s.n += scan_bytes;
+  return jenc_close(s, bytes_out);
+}
+
+// coef: [component][block rows][block columns][64] over the MCU grid, zig-zag (zigzag = true: what jpeg_fdct_kernel writes) or natural
+// order (what ctpn_jpeg_entropy_decode returns); three components, luma sampling hs x vs, chroma 1 x 1; qt: 3 x 64, natural order.
+// *bytes_out = the size of the file, also when it does not fit (CTPN_ERR_CAPACITY)
+int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, int vs, const uint16_t* qt3x64, uint8_t* out, size_t capacity, size_t* bytes_out) {
+  const int rc = jenc_check(h, w, hs, vs, qt3x64);
+  if (rc) return rc;
+  const JencTables& T = jenc_tables();
+  JencSink s{out, out ? capacity : 0};
+  jenc_header(s, h, w, hs, vs, qt3x64);
   const int mcux = (w + 8 * hs - 1) / (8 * hs), mcuy = (h + 8 * vs - 1) / (8 * vs);
   const int16_t* base[3]; int bw[3], ch[3], cv[3];
   {
@@ -187,10 +210,7 @@ int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, 
           }
   if (!ok) return fail(CTPN_ERR_ARG, "jpeg encode: a coefficient is outside what 8-bit baseline JPEG codes (DC difference 11 bits, AC 10 bits)");
   s.flush();
-  s.byte(0xFF); s.byte(0xD9);
-  if (bytes_out) *bytes_out = s.n;
-  if (s.n > s.cap) return fail(CTPN_ERR_CAPACITY, "jpeg encode: output buffer too small (" + std::to_string(s.n) + " bytes needed)");
-  return CTPN_OK;
+  return jenc_close(s, bytes_out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -212,7 +212,8 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
     return k
 
 
-def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host"):
+def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
+             encode_entropy="host"):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -227,7 +228,9 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     batches of the host decoders and the single images keep Pillow's writer; the files are byte-identical either way.
     entropy='device' (--decode gpu-entropy): the Huffman decode of the JPEG batches runs on the device too (ctpn_decode_jpeg_files_device);
     a batch that call refuses -- one with a progressive file in it -- takes the host-entropy call, and what that refuses goes to Pillow, as
-    with decode='gpu'."""
+    with decode='gpu'.
+    encode_entropy='device' (--encode gpu-entropy): encode='gpu' with the Huffman CODING on the device too (ctpn_write_annotated_files_device):
+    only the files' own bytes cross to the host. The files are byte-identical."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -302,7 +305,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         if slot in dev_batches:                        # draw + resize + JPEG of the whole batch behind the C ABI; emit() writes the text files
             ptr, shape, scale = dev_batches.pop(slot)
             net.ctx.write_annotated_files(ptr, shape, [results[nm] for nm in members], scale,
-                                          [os.path.join(out_dir, os.path.basename(nm)) for nm in members])
+                                          [os.path.join(out_dir, os.path.basename(nm)) for nm in members], entropy=encode_entropy)
             stats["enc_gpu"] += len(members)
         if slot in crop_src:                           # (a device batch is live until the second-next decode: this is one decode from its own)
             ptr, shape, imgs = crop_src.pop(slot)
@@ -385,7 +388,8 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
-    (ctpn_write_annotated_files); 'host' (default): every image through Pillow, as before.
+    (ctpn_write_annotated_files); 'gpu-entropy': the same with the Huffman coding on the device too (ctpn_write_annotated_files_device,
+    byte-identical files); 'host' (default): every image through Pillow, as before.
     crops_dir (needs decode='gpu'): every detected line also as a rectified crop of height crop_h, <stem>_<k>.jpg in that directory, cut out
     on the device at collect time (write_crops); None (default): nothing changes.
     params: {name: value} of the detection tail (ctpn_set_param: RPN_* and the connector's names) for the ctx of this run; the connector's
@@ -394,8 +398,11 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     _check_uint8_feed_config(params)
     if params:
         parse_connector_args(["%s=%r" % (k, float(v)) for k, v in params.items() if k not in RPN_PARAM_NAMES])      # unknown names: an error before any work
-    if encode not in ("host", "gpu"):
-        raise ValueError("encode must be 'host' or 'gpu'")
+    if encode not in ("host", "gpu", "gpu-entropy"):
+        raise ValueError("encode must be 'host', 'gpu' or 'gpu-entropy'")
+    encode_entropy = "device" if encode == "gpu-entropy" else "host"      # gpu-entropy: encode='gpu' with the Huffman coding on the device too
+    if encode == "gpu-entropy":
+        encode = "gpu"
     entropy = "device" if decode == "gpu-entropy" else "host"      # gpu-entropy: decode='gpu' with the Huffman decode on the device too
     if decode == "gpu-entropy":
         decode = "gpu"
@@ -407,7 +414,7 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
-                        entropy=entropy)
+                        entropy=entropy, encode_entropy=encode_entropy)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -547,8 +554,9 @@ def build_parser():
     ap.add_argument('--decode', default='host', choices=['host', 'gpu', 'gpu-entropy'],
                     help="gpu: JPEG decode + resize_im on the device (ctpn_decode_jpeg_batch); gpu-entropy: the same with the Huffman decode on the device too "
                          "(ctpn_decode_jpeg_files_device; progressive files keep the host-entropy call)")
-    ap.add_argument('--encode', default='host', choices=['host', 'gpu'],
-                    help="gpu (with --decode gpu): annotated JPEG images drawn, resized and coded by the library (ctpn_write_annotated_files)")
+    ap.add_argument('--encode', default='host', choices=['host', 'gpu', 'gpu-entropy'],
+                    help="gpu (with --decode gpu): annotated JPEG images drawn, resized and coded by the library (ctpn_write_annotated_files); "
+                         "gpu-entropy: the same with the Huffman coding on the device too (ctpn_write_annotated_files_device)")
     ap.add_argument('--crops', default=None, metavar='DIR',
                     help="(with --decode gpu) also write every detected line as a rectified crop <stem>_<k>.jpg of height --crop-height into DIR (ctpn_crop_lines)")
     ap.add_argument('--crop-height', type=int, default=32)

@@ -78,17 +78,17 @@ def imwrite(path, bgr):
         im.save(path)
 
 
-def imencode_jpeg_batch(ctx, images, quality=95, device_ptr=None, shape=None):
+def imencode_jpeg_batch(ctx, images, quality=95, device_ptr=None, shape=None, entropy="host"):
     """cv2.imencode('.jpg', img, [IMWRITE_JPEG_QUALITY, quality]) for a batch of BGR uint8 images of one size, on the GPU
     (ctpn_encode_jpeg_batch): (n, h, w, 3) on the host, or device_ptr + shape -> list of n bytes objects, byte-equal to what imwrite above
-    puts into a .jpg file at the same quality."""
-    return ctx.encode_jpeg_batch(images, quality=quality, device_ptr=device_ptr, shape=shape)
+    puts into a .jpg file at the same quality. entropy="device": the Huffman coding on the device too (ctpn_encode_jpeg_batch_device)."""
+    return ctx.encode_jpeg_batch(images, quality=quality, device_ptr=device_ptr, shape=shape, entropy=entropy)
 
 
-def imwrite_jpeg_batch(ctx, paths, images, quality=95, device_ptr=None, shape=None):
+def imwrite_jpeg_batch(ctx, paths, images, quality=95, device_ptr=None, shape=None, entropy="host"):
     """imwrite for a batch of JPEG files: encoded by imencode_jpeg_batch, one file per image."""
     paths = list(paths)
-    files = imencode_jpeg_batch(ctx, images, quality=quality, device_ptr=device_ptr, shape=shape)
+    files = imencode_jpeg_batch(ctx, images, quality=quality, device_ptr=device_ptr, shape=shape, entropy=entropy)
     assert len(files) == len(paths)
     for path, data in zip(paths, files):
         with open(path, "wb") as f:

@@ -532,7 +532,7 @@ int    ctpn_crop_lines(ctpn_ctx* ctx, const uint8_t* images, int images_on_devic
                        const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device,
                        size_t capacity_bytes, int* widths_out, int* total_out);
 
-/* ---- cv2.imread for PNG files (reference ctpn/demo.py:59; data/demo holds .jpg and .png). HOST ONLY, by the nature of the format: one
+/* ---- cv2.imread for PNG files (reference ctpn/demo.py:59; data/demo holds .jpg and .png). HOST ONLY, by the nature of READING the format: one
  * DEFLATE stream (zlib's inflate, the library libpng itself sits on) and row filters that chain from row to row -- nothing a GPU is for. One
  * file per host thread, straight into the caller's batch buffer, which ctpn_detect_submit / ctpn_forward take as host images (one
  * host-to-device copy per batch). libpng's IMREAD_COLOR transforms restated: RGB / RGBA -> BGR with the alpha dropped, gray 1 / 2 / 4 / 8
@@ -551,6 +551,41 @@ int    ctpn_png_probe(const uint8_t* data, size_t len, int* h, int* w, int* colo
 int    ctpn_png_decode(const uint8_t* data, size_t len, uint8_t* bgr_out, size_t capacity);
 int    ctpn_png_probe_files(const char* const* paths, int n, int* info4, int threads);
 int    ctpn_decode_png_files(const char* const* paths, int n, int h, int w, uint8_t* bgr_out, int threads);
+
+/* ---- cv2.imwrite for PNG-named result images (reference ctpn/demo.py:28-52: draw_boxes, cv2.resize by 1 / scale, cv2.imwrite under the
+ * input's own name, and data/demo holds .png files). Additive to ABI 10, no option and no default changes. "Host work by nature" holds for
+ * READING a PNG file; writing one parallelises: the Sub filter reads raw pixels only, and a DEFLATE stream may be tokenised in independent
+ * pieces. The file, defined exactly (docs/decode_pipeline.md, "PNG out"): signature, IHDR (8-bit RGB), ONE IDAT, IEND; zlib stream 78 01,
+ * one dynamic-Huffman block, Adler-32; every row filtered with Sub; the filtered stream cut into pieces of 256 bytes, each tokenised on its
+ * own, greedily, with two candidate matches per position -- a run of the byte before (distance 1) and a repeat of the row above (distance
+ * 1 + 3 w, where that is within 32768) --, the longer taken from 3 bytes on (distance 1 on a tie); a literal/length code built from the
+ * image's own histogram, limited to 15 bits; a fixed two-symbol distance code. cv2's own writer uses the Sub filter and a run-length match
+ * strategy too; the BYTES are not pinned against it or Pillow (other match finders), parity is defined on the decoded pixels, which are
+ * exact: zlib, Pillow and ctpn_png_decode return the input from every file. The device form's files equal the host form's byte for byte.
+ *   ctpn_png_encode_capacity        upper bound of one h x w file (0 for a bad size): a token codes at least one stream byte in at most 15
+ *                                   bits (a literal: one code; a match: 15 + 5 + 1 + 13 bits for three bytes or more), so the block is below
+ *                                   2 bytes per stream byte + 171 (header of 1338 bits, EOB, padding); the frame adds 63
+ *   ctpn_png_encode                 the host form (needs no device): h x w x 3 BGR uint8, any size up to 65535 x 65535. *bytes_out is the file
+ *                                   size, also when it exceeds capacity (CTPN_ERR_CAPACITY; out == NULL with capacity 0 sizes the file)
+ *   ctpn_encode_png_batch           the contract of ctpn_encode_jpeg_batch without `quality`: histogram, length, prefix-sum and write passes
+ *                                   on the device (png_enc.hip), the code tables and the framing on the ctx's worker pool
+ *   ctpn_write_annotated_png_files  the contract of ctpn_write_annotated_files: outlines on a ctx-owned copy, cv2.resize by 1 / scale, then the
+ *                                   PNG passes. Takes host images too (images_on_device = 0: PNG batches are decoded on the host; they are
+ *                                   copied in the ctx's copy queue)
+ *   ctpn_png_encode_device_stats    of the ctx's last PNG call: out4 = {files coded on the device, files handed to the host form, pieces coded
+ *                                   on the device, bytes copied device to host}
+ * Both ctx calls run in the ctx's copy queue (a live batch of ctpn_decode_jpeg_batch is waited for there), return when the files are coded,
+ * and keep buffers that grow to the largest call seen. Only the histograms (1144 bytes per image), one result record (16 bytes) and the
+ * files' own bytes cross to the host. An image whose flag is raised is coded by the host form alone. CTPN_ERR_ARG, before any allocation
+ * or launch, when h (1 + 3 w) > 2^27 (bit offsets stay below 2^31; the host form takes such images); CTPN_ERR_STATE on a
+ * post-processing-only ctx; CTPN_ERR_ARG with the path in ctpn_last_error() for a file that cannot be written. */
+size_t ctpn_png_encode_capacity(int h, int w);
+int    ctpn_png_encode(const uint8_t* bgr, int h, int w, uint8_t* out, size_t capacity, size_t* bytes_out);
+int    ctpn_encode_png_batch(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, uint8_t* const* out,
+                             const size_t* capacities, size_t* bytes_out);
+int    ctpn_write_annotated_png_files(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs,
+                                      int line_capacity, const int* line_counts, double scale, const char* const* paths);
+int    ctpn_png_encode_device_stats(ctpn_ctx* ctx, long long* out4);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,11 @@ def _declare(lib):
         "ctpn_debug_png_backend": (C.c_int, [C.c_int]),
         "ctpn_png_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_png_decode": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t]),
+        "ctpn_png_encode_capacity": (C.c_size_t, [C.c_int, C.c_int]),
+        "ctpn_png_encode": (C.c_int, [u8p, C.c_int, C.c_int, u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "ctpn_encode_png_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "ctpn_write_annotated_png_files": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_double, C.POINTER(C.c_char_p)]),
+        "ctpn_png_encode_device_stats": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
         "ctpn_png_probe_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, i32p, C.c_int]),
         "ctpn_decode_png_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
         "ctpn_profile_enable": (C.c_int, [vp, C.c_int]),
@@ -313,13 +318,35 @@ def png_backend(zlib_only=-1):
 
 
 def png_decode(data):
-    """cv2.imread(IMREAD_COLOR) of one PNG file's bytes: (h, w, 3) BGR uint8 (ctpn_png_decode; host only by the nature of the format)."""
+    """cv2.imread(IMREAD_COLOR) of one PNG file's bytes: (h, w, 3) BGR uint8 (ctpn_png_decode; reading is host work by the nature of the format)."""
     lib = load_library()
     h, w, _, _ = png_probe(data)
     keep, ptr, n = _bytes_ptr(data)
     out = np.zeros((h, w, 3), np.uint8)
     _check(lib.ctpn_png_decode(ptr, n, _ptr(out, C.c_uint8), out.size))
     return out
+
+
+def png_encode_capacity(h, w):
+    """Upper bound of the bytes one h x w PNG file written by this library can need (ctpn_png_encode_capacity)."""
+    return int(load_library().ctpn_png_encode_capacity(int(h), int(w)))
+
+
+def png_encode(bgr):
+    """One (h, w, 3) BGR uint8 image as a PNG file's bytes, on the host (ctpn_png_encode: Sub filter, one dynamic-Huffman DEFLATE block,
+    run-length and row-above matches): lossless; byte-equal to what Context.encode_png_batch writes on the device."""
+    lib = load_library()
+    bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+    if bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError("png_encode wants (h,w,3) uint8")
+    h, w = int(bgr.shape[0]), int(bgr.shape[1])
+    size = C.c_size_t(0)
+    rc = lib.ctpn_png_encode(_ptr(bgr, C.c_uint8), h, w, None, 0, C.byref(size))
+    if rc != CTPN_ERR_CAPACITY:
+        _check(rc)
+    out = np.empty((size.value,), np.uint8)
+    _check(lib.ctpn_png_encode(_ptr(bgr, C.c_uint8), h, w, _ptr(out, C.c_uint8), out.size, C.byref(size)))
+    return out[: size.value].tobytes()
 
 
 def png_probe_files(paths, threads=0):
@@ -945,6 +972,58 @@ class Context:
         keep, arr = _path_array(list(paths))
         _check(fn(self._h, C.c_void_p(int(device_ptr)), n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
                                                     float(scale), arr, int(quality)))
+
+    def png_encode_device_stats(self):
+        """Of the last PNG call of this ctx (ctpn_png_encode_device_stats): dict(device=files coded on the device, host=files handed to the
+        host form, pieces=256-byte pieces coded on the device, d2h_bytes=bytes copied device to host)."""
+        out = (C.c_longlong * 4)()
+        _check(self._lib.ctpn_png_encode_device_stats(self._h, out))
+        return {"device": int(out[0]), "host": int(out[1]), "pieces": int(out[2]), "d2h_bytes": int(out[3])}
+
+    @staticmethod
+    def _image_source(images, device_ptr, shape, who):
+        if device_ptr is None:
+            images = np.ascontiguousarray(images, dtype=np.uint8)
+            if images.ndim != 4 or images.shape[3] != 3:
+                raise ValueError(who + " wants (n,h,w,3) uint8")
+            return images, images.shape, images.ctypes.data_as(C.c_void_p), 0
+        return None, shape, C.c_void_p(int(device_ptr)), 1
+
+    def encode_png_batch(self, images=None, device_ptr=None, shape=None):
+        """cv2.imwrite's PNG files of n BGR uint8 images of one size, coded on the device (ctpn_encode_png_batch): Sub filter, histogram,
+        length, prefix-sum and write passes over 256-byte pieces of the filtered stream; the code tables and the framing on the ctx's host
+        pool. images: (n, h, w, 3) on the host, or device_ptr + shape. -> list of n bytes objects; lossless, byte-equal to png_encode."""
+        keep, shape, src, on_dev = self._image_source(images, device_ptr, shape, "encode_png_batch")
+        n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+        bound = png_encode_capacity(h, w)
+        sizes = (C.c_size_t * n)()
+        for cap in (min(bound, h * w * 3 + 4096), bound):      # the raw size holds anything but noise; the proven bound is twice it
+            bufs = np.empty((n, cap), np.uint8)
+            ptrs = (C.c_void_p * n)(*[bufs[i].ctypes.data for i in range(n)])
+            caps = (C.c_size_t * n)(*([cap] * n))
+            rc = self._lib.ctpn_encode_png_batch(self._h, src, on_dev, n, h, w, ptrs, caps, sizes)
+            if rc != CTPN_ERR_CAPACITY or cap == bound:
+                break
+        _check(rc)
+        return [bufs[i, : sizes[i]].tobytes() for i in range(n)]
+
+    def write_annotated_png_files(self, images=None, device_ptr=None, shape=None, recs=(), scale=1.0, paths=()):
+        """draw_boxes + cv2.resize(1 / scale) + cv2.imwrite (reference ctpn/demo.py:28-52) into PNG files, all on the device
+        (ctpn_write_annotated_png_files). images: (n, h, w, 3) on the host (a PNG batch is decoded there), or device_ptr + shape (a live batch
+        of decode_jpeg_batch); recs = one (M_i, 9) array per image, paths = one file name per image. The batch is not modified."""
+        keep, shape, src, on_dev = self._image_source(images, device_ptr, shape, "write_annotated_png_files")
+        n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+        recs = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 9) for r in recs]
+        assert len(recs) == n and len(paths) == n
+        cap = max([r.shape[0] for r in recs] + [1])
+        packed = np.zeros((n, cap, 9), np.float64)
+        counts = np.zeros((n,), np.int32)
+        for i, r in enumerate(recs):
+            packed[i, : r.shape[0]] = r
+            counts[i] = r.shape[0]
+        keep_paths, arr = _path_array(list(paths))
+        _check(self._lib.ctpn_write_annotated_png_files(self._h, src, on_dev, n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
+                                                        float(scale), arr))
 
     def crop_lines(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None,
                    out_device_ptr=None, out_capacity=0):

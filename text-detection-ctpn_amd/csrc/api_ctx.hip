@@ -385,6 +385,9 @@ int ctpn_destroy(ctpn_ctx* c) {
   for (void* p : {(void*)c->enc.img_dev, (void*)c->enc.rs_dev, (void*)c->enc.coef_dev, (void*)c->enc.recs_dev, (void*)c->enc.cnt_dev, c->enc.qtab_dev, (void*)c->enc.huff_dev, c->enc.huff_tab_dev}) if (p) (void)hipFree(p);
   for (void* p : {(void*)c->enc.coef_host, c->enc.qtab_host, (void*)c->enc.huff_host, (void*)c->enc.scan_host}) if (p) (void)hipHostFree(p);
   if (c->enc.ev_done) (void)hipEventDestroy(c->enc.ev_done);
+  if (c->pnge.dev) (void)hipFree(c->pnge.dev);
+  for (void* p : {(void*)c->pnge.host, (void*)c->pnge.file_host}) if (p) (void)hipHostFree(p);
+  if (c->pnge.ev_done) (void)hipEventDestroy(c->pnge.ev_done);
   for (void* p : {(void*)c->crop.img_dev, (void*)c->crop.out_dev, c->crop.desc_dev}) if (p) (void)hipFree(p);
   if (c->crop.desc_host) (void)hipHostFree(c->crop.desc_host);
   if (c->crop.ev_done) (void)hipEventDestroy(c->crop.ev_done);

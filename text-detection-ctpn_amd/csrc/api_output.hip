@@ -91,15 +91,6 @@ struct EncJob {                       // one image of a device-entropy call
   uint64_t blocks() const { return (uint64_t)mcus() * (uint32_t)(hs * vs + 2); }
 };
 
-static int grow_host(uint8_t** p, size_t& have, size_t need) {
-  if (need <= have) return CTPN_OK;
-  if (*p) CTPN_HIP_TRY(hipHostFree(*p));
-  *p = nullptr; have = 0;
-  CTPN_HIP_TRY(hipHostMalloc((void**)p, need));
-  have = need;
-  return CTPN_OK;
-}
-
 // one launch group (at most JHE_MAX_BLOCKS blocks): the kernels, then the result words -- the wait of the host form on its coefficients --,
 // then exactly the bytes the sizes say: scan bodies, or the coefficients of an image whose flag is raised
 static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vector<int>& use, bool zigzag) {

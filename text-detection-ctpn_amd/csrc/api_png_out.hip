@@ -1,0 +1,211 @@
+// C ABI of libctpn_hip.so, PNG output unit: the PNG-named result images of ctpn/demo.py:28-52 -- outlines (draw_boxes_kernel), cv2.resize by
+// 1 / scale (preprocess.hip), cv2.imwrite -- for a batch on the device (kernels: png_enc.hip), and the host form of the same file
+// (png_enc_dev.h: one text for both, so the two forms cannot disagree about a file).
+#include "ctx.h"
+#include "png_enc_dev.h"
+
+namespace ctpn {
+
+// a finished file to the caller's buffer or to a file of its own. Runs on a worker thread: nothing may leave it
+static void png_deliver(const uint8_t* file, size_t bytes, uint8_t* out, size_t capacity, size_t* bytes_out, const char* path, int& st, std::string& msg) {
+  if (path) {
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f) { st = CTPN_ERR_ARG; msg = std::string("cannot open ") + path; return; }
+    const bool ok = std::fwrite(file, 1, bytes, f) == bytes;
+    if (std::fclose(f) != 0 || !ok) { st = CTPN_ERR_ARG; msg = std::string("write failed: ") + path; }
+  } else {
+    *bytes_out = bytes;
+    if (bytes > capacity) { st = CTPN_ERR_CAPACITY; msg = "the file needs " + std::to_string(bytes) + " bytes, the buffer holds " + std::to_string(capacity); return; }
+    std::memcpy(out, file, bytes);
+  }
+}
+
+static bool png_size_ok(int h, int w) { return h > 0 && w > 0 && h <= 65535 && w <= 65535; }
+static bool png_device_size_ok(int h, int w) { return (uint64_t)h * (1u + 3u * (uint64_t)w) <= PNGE_MAX_STREAM; }
+
+// n images of h x w x 3 at px (device, complete in the ctx's copy queue) -> n files, in the caller's buffers (out) or in files (paths)
+static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int h, int w, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths) {
+  auto& P = c->pnge;
+  hipStream_t qs = c->stream_c;
+  if (!P.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&P.ev_done, hipEventDisableTiming));
+  c->pnge_stats[0] = c->pnge_stats[1] = c->pnge_stats[2] = c->pnge_stats[3] = 0;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  PngeImg d0;
+  pnge_describe(d0, h, w);
+  const size_t nw = (size_t)pnge_words(d0), per_px = (size_t)h * w * 3;
+  if ((uint64_t)n * d0.npieces > 0xffffffffull || n > 65535) return fail(CTPN_ERR_ARG, std::string(who) + ": more than 65535 images or 2^32 pieces in one call");
+  const size_t o_img = 0, o_hist = up(o_img + (size_t)n * sizeof(PngeImg)), o_res = o_hist + (size_t)n * PNGE_NSYM * 4, o_codes = up(o_res + (size_t)n * sizeof(PngeRes)),
+               host_total = o_codes + (size_t)n * sizeof(PngeCodes), o_len = up(host_total), o_words = up(o_len + (size_t)n * d0.npieces * sizeof(PngeLen)),
+               dev_total = o_words + (size_t)n * nw * 4;
+  int rc;
+  if ((rc = grow_host(&P.host, P.host_bytes, host_total))) return rc;
+  if ((rc = grow_dev((void**)&P.dev, P.dev_bytes, dev_total))) return rc;
+  PngeImg* imgs = (PngeImg*)(P.host + o_img);
+  uint32_t* hist = (uint32_t*)(P.host + o_hist);
+  PngeRes* res = (PngeRes*)(P.host + o_res);
+  PngeCodes* codes = (PngeCodes*)(P.host + o_codes);
+  for (int i = 0; i < n; ++i) {
+    imgs[i] = d0;
+    imgs[i].pix_off = (uint64_t)i * per_px; imgs[i].piece0 = (uint32_t)i * d0.npieces; imgs[i].word0 = (uint64_t)i * nw; imgs[i].nwords = nw;
+  }
+  // histograms -> the host, which builds every image's code and block header; one copy brings them back
+  CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_img, imgs, (size_t)n * sizeof(PngeImg), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_hist, 0, (size_t)n * (PNGE_NSYM * 4 + sizeof(PngeRes)), qs));      // counters and result records
+  if ((rc = launch_png_hist((const PngeImg*)(P.dev + o_img), px, (uint32_t*)(P.dev + o_hist), n, d0.npieces, qs))) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(hist, P.dev + o_hist, (size_t)n * PNGE_NSYM * 4, hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
+  CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
+  c->pnge_stats[3] += (long long)n * PNGE_NSYM * 4;
+  c->pool->run(n, [&](int i) { pnge_build_codes(imgs[i], hist + (size_t)i * PNGE_NSYM, codes[i]); });
+  CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_codes, codes, (size_t)n * sizeof(PngeCodes), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_words, 0, (size_t)n * nw * 4, qs));      // the write pass ORs shared words into it
+  if ((rc = launch_png_code((const PngeImg*)(P.dev + o_img), px, (const PngeCodes*)(P.dev + o_codes), (PngeLen*)(P.dev + o_len), (uint32_t*)(P.dev + o_words),
+                            (PngeRes*)(P.dev + o_res), n, d0.npieces, qs))) return rc;
+  // the result records first, then exactly the bytes they name
+  CTPN_HIP_TRY(hipMemcpyAsync(res, P.dev + o_res, (size_t)n * sizeof(PngeRes), hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
+  CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
+  c->pnge_stats[3] += (long long)n * (long long)sizeof(PngeRes);
+  std::vector<size_t> at((size_t)n, 0);
+  std::vector<char> on_host((size_t)n, 0);
+  size_t file_total = 0, back_total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (res[i].flag || (size_t)res[i].bytes > nw * 4) { on_host[i] = 1; back_total += per_px; continue; }
+    at[i] = file_total;
+    file_total += up((size_t)PNGE_FRAME_BYTES + res[i].bytes);
+  }
+  if ((rc = grow_host(&P.file_host, P.file_host_bytes, file_total))) return rc;
+  std::vector<uint8_t> back;      // the pixels of the images the host form codes (none, unless a flag is raised)
+  try { back.resize(back_total); } catch (const std::exception& e) { return fail(CTPN_ERR_CAPACITY, std::string(who) + ": " + e.what()); }
+  size_t bat = 0;
+  std::vector<size_t> back_at((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    if (on_host[i]) {
+      ++c->pnge_stats[1];
+      back_at[i] = bat;
+      CTPN_HIP_TRY(hipMemcpyAsync(back.data() + bat, px + (size_t)i * per_px, per_px, hipMemcpyDeviceToHost, qs));
+      bat += per_px; c->pnge_stats[3] += (long long)per_px;
+      continue;
+    }
+    ++c->pnge_stats[0]; c->pnge_stats[2] += d0.npieces;
+    CTPN_HIP_TRY(hipMemcpyAsync(P.file_host + at[i] + PNGE_FRAME_FRONT, P.dev + o_words + (size_t)i * nw * 4, res[i].bytes, hipMemcpyDeviceToHost, qs));
+    c->pnge_stats[3] += (long long)res[i].bytes;
+  }
+  CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
+  CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
+  std::vector<int> st((size_t)n, CTPN_OK);
+  std::vector<std::string> msg((size_t)n);
+  c->pool->run(n, [&](int i) {
+    uint8_t* o = paths ? nullptr : out[i];
+    const size_t cap = paths ? 0 : capacities[i];
+    size_t* bo = paths ? nullptr : bytes_out + i;
+    const char* path = paths ? paths[i] : nullptr;
+    try {
+      if (on_host[i]) {
+        size_t need = 0;
+        (void)pnge_encode_host(back.data() + back_at[i], h, w, nullptr, 0, &need, png_crc32);
+        std::vector<uint8_t> file(need);
+        (void)pnge_encode_host(back.data() + back_at[i], h, w, file.data(), need, &need, png_crc32);
+        png_deliver(file.data(), need, o, cap, bo, path, st[i], msg[i]);
+      } else {
+        uint8_t* file = P.file_host + at[i];
+        pnge_frame(file, h, w, res[i].bytes, res[i].adler, png_crc32);
+        png_deliver(file, (size_t)PNGE_FRAME_BYTES + res[i].bytes, o, cap, bo, path, st[i], msg[i]);
+      }
+    } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }
+  });
+  for (int i = 0; i < n; ++i) if (st[i]) return fail(st[i], std::string(who) + ": image " + std::to_string(i) + ": " + msg[i]);
+  return CTPN_OK;
+}
+
+}  // namespace ctpn
+
+extern "C" {
+
+size_t ctpn_png_encode_capacity(int h, int w) { return png_size_ok(h, w) ? pnge_capacity(h, w) : 0; }
+
+int ctpn_png_encode(const uint8_t* bgr, int h, int w, uint8_t* out, size_t capacity, size_t* bytes_out) {
+  if (!bgr || !bytes_out || (!out && capacity)) return fail(CTPN_ERR_ARG, "ctpn_png_encode: null pointer");
+  if (!png_size_ok(h, w)) return fail(CTPN_ERR_ARG, "ctpn_png_encode: bad size");
+  try {
+    if (!pnge_encode_host(bgr, h, w, out, out ? capacity : 0, bytes_out, png_crc32))
+      return fail(CTPN_ERR_CAPACITY, "ctpn_png_encode: the file needs " + std::to_string(*bytes_out) + " bytes, the buffer holds " + std::to_string(capacity));
+  } catch (const std::exception& e) { return fail(CTPN_ERR_CAPACITY, std::string("ctpn_png_encode: ") + e.what()); }
+  return CTPN_OK;
+}
+
+int ctpn_encode_png_batch(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, uint8_t* const* out, const size_t* capacities, size_t* bytes_out) {
+  const std::string who("ctpn_encode_png_batch");
+  if (!c || !images || !out || !capacities || !bytes_out) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0 || !png_size_ok(h, w)) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size");
+  if (!png_device_size_ok(h, w)) return fail(CTPN_ERR_ARG, who + ": h (1 + 3 w) above 2^27: ctpn_png_encode takes such images");
+  for (int i = 0; i < n; ++i) if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, who + ": null output pointer");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  auto& E = c->enc;
+  const uint8_t* px = images;
+  if (!images_on_device) {
+    const size_t bytes = (size_t)n * h * w * 3;
+    const int rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256);
+    if (rc) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyHostToDevice, c->stream_c));
+    px = E.img_dev;
+  } else {
+    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(c->stream_c, J.ev_ready, 0));
+  }
+  return png_code(c, "ctpn_encode_png_batch", px, n, h, w, out, capacities, bytes_out, nullptr);
+}
+
+int ctpn_write_annotated_png_files(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
+                                   const int* line_counts, double scale, const char* const* paths) {
+  const std::string who("ctpn_write_annotated_png_files");
+  if (!c || !images || !line_counts || !paths) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0 || !png_size_ok(h, w) || line_capacity < 0 || !(scale > 0.0)) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size / bad scale");
+  for (int i = 0; i < n; ++i) {
+    if (!paths[i]) return fail(CTPN_ERR_ARG, who + ": null path");
+    if (line_counts[i] < 0 || line_counts[i] > line_capacity || (line_counts[i] > 0 && !recs)) return fail(CTPN_ERR_ARG, who + ": line count out of range");
+  }
+  // demo.py:51: cv2.resize(img, None, None, fx = 1 / scale, fy = 1 / scale); the identity (scale 1) is a copy there and no launch here
+  const double f = 1.0 / scale;
+  int dh = h, dw = w;
+  if (f != 1.0) { dh = resize_out_dim(h, f); dw = resize_out_dim(w, f); }
+  if (!png_size_ok(dh, dw)) return fail(CTPN_ERR_ARG, who + ": the resized image is empty or too large for a PNG file");
+  if (!png_device_size_ok(h, w) || !png_device_size_ok(dh, dw)) return fail(CTPN_ERR_ARG, who + ": h (1 + 3 w) above 2^27: ctpn_png_encode takes such images");
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  auto& E = c->enc;
+  hipStream_t qs = c->stream_c;
+  const size_t bytes = (size_t)n * h * w * 3;
+  int rc;
+  if ((rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
+  if (f != 1.0 && (rc = grow_dev((void**)&E.rs_dev, E.rs_bytes, (size_t)n * dh * dw * 3 + 256))) return rc;
+  const size_t rbytes = std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64);
+  if ((rc = grow_dev((void**)&E.recs_dev, E.recs_bytes, rbytes))) return rc;
+  size_t cnt_bytes = E.cnt_n * sizeof(int);
+  if ((rc = grow_dev((void**)&E.cnt_dev, cnt_bytes, (size_t)n * sizeof(int)))) return rc;
+  E.cnt_n = cnt_bytes / sizeof(int);
+  // the outlines go onto a copy owned by the ctx: a live batch of ctpn_decode_jpeg_batch (produced in this queue) may still feed a forward
+  if (images_on_device) {
+    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
+    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyDeviceToDevice, qs));
+  } else {
+    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyHostToDevice, qs));
+  }
+  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(E.recs_dev, recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(E.cnt_dev, line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
+  if ((rc = launch_draw_boxes(E.img_dev, E.recs_dev, E.cnt_dev, line_capacity, n, h, w, qs))) return rc;
+  const uint8_t* px = E.img_dev;
+  if (f != 1.0) {
+    if ((rc = launch_resize_linear(E.img_dev, E.rs_dev, 0, n, h, w, dh, dw, f, f, qs))) return rc;
+    px = E.rs_dev;
+  }
+  return png_code(c, "ctpn_write_annotated_png_files", px, n, dh, dw, nullptr, nullptr, nullptr, paths);
+}
+
+int ctpn_png_encode_device_stats(ctpn_ctx* c, long long* out4) {
+  if (!c || !out4) return fail(CTPN_ERR_ARG, "ctpn_png_encode_device_stats: null pointer");
+  std::memcpy(out4, c->pnge_stats, sizeof(c->pnge_stats));
+  return CTPN_OK;
+}
+
+}  // extern "C"

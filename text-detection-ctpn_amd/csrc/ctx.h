@@ -204,6 +204,15 @@ struct ctpn_ctx {
     uint8_t* scan_host = nullptr; size_t scan_host_bytes = 0;
   } enc;
   long long jhe_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_encode_device_stats
+  // ctpn_encode_png_batch / ctpn_write_annotated_png_files (api_png_out.hip): ONE set of buffers, for the reason the JPEG writer's set is one,
+  // allocated on first use and grown to the largest call seen. The pixels, the outlines' records and the resized copy use `enc`'s
+  struct PngEncBufs {
+    uint8_t* dev = nullptr; size_t dev_bytes = 0;              // descriptors, histograms, codes, result records, per-piece array, DEFLATE words
+    uint8_t* host = nullptr; size_t host_bytes = 0;            // page-locked: descriptors, histograms, codes, result records
+    uint8_t* file_host = nullptr; size_t file_host_bytes = 0;  // page-locked: the DEFLATE blocks, each behind room for its file's front
+    hipEvent_t ev_done = nullptr;
+  } pnge;
+  long long pnge_stats[4] = {0, 0, 0, 0};      // ctpn_png_encode_device_stats
   // ctpn_crop_lines (api_crops.hip): ONE set of buffers, for the reason the writer's set is one (the call returns when its crops are
   // complete), allocated on first use and grown to the largest call seen
   struct CropBufs {
@@ -356,6 +365,16 @@ static inline int grow_dev(void** p, size_t& have, size_t need) {
   if (*p) CTPN_HIP_TRY(hipFree(*p));
   *p = nullptr; have = 0;
   CTPN_HIP_TRY(hipMalloc(p, need));
+  have = need;
+  return CTPN_OK;
+}
+
+// ... and a page-locked host block of the same kind
+static inline int grow_host(uint8_t** p, size_t& have, size_t need) {
+  if (need <= have) return CTPN_OK;
+  if (*p) CTPN_HIP_TRY(hipHostFree(*p));
+  *p = nullptr; have = 0;
+  CTPN_HIP_TRY(hipHostMalloc((void**)p, need));
   have = need;
   return CTPN_OK;
 }

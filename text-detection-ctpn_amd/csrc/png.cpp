@@ -347,6 +347,17 @@ class PngPool {
 
 }  // namespace ctpn
 
+// for the PNG writer (api_png_out.hip): the loaded library's CRC-32, or the bitwise form where there is none (writing needs no inflate)
+uint32_t ctpn::png_crc32(const uint8_t* p, size_t n) {
+  if (have_deflate() && n <= 0xffffffffu) return png_crc(p, n);
+  uint32_t c = 0xffffffffu;
+  for (size_t i = 0; i < n; ++i) {
+    c ^= p[i];
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1u)));
+  }
+  return ~c;
+}
+
 using namespace ctpn;
 
 extern "C" {

@@ -193,6 +193,10 @@ def _is_jpeg(name):
     return name.lower().endswith((".jpg", ".jpeg"))
 
 
+def _is_png(name):
+    return name.lower().endswith(".png")
+
+
 def _read(name):
     with open(name, "rb") as f:
         return f.read()
@@ -213,7 +217,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
 
 
 def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
-             encode_entropy="host"):
+             encode_entropy="host", png_encode="host"):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -224,13 +228,18 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     (lib/utils/image.py), batched the same way; the result files are the same whichever decoder a file went through.
     encode='gpu' (with write_images): the annotated images of device-decoded batches whose output name is a JPEG's are drawn, resized by
     1 / scale and JPEG-coded by the library at collect time (ctpn_write_annotated_files: kernels in the ctx's copy queue, Huffman coding and
-    file writing on its C++ pool) -- those pixels never reach the host. PNG-named outputs (a lossless DEFLATE stream: host work by nature),
+    file writing on its C++ pool) -- those pixels never reach the host. PNG-named outputs (unless png_encode='gpu'),
     batches of the host decoders and the single images keep Pillow's writer; the files are byte-identical either way.
     entropy='device' (--decode gpu-entropy): the Huffman decode of the JPEG batches runs on the device too (ctpn_decode_jpeg_files_device);
     a batch that call refuses -- one with a progressive file in it -- takes the host-entropy call, and what that refuses goes to Pillow, as
     with decode='gpu'.
     encode_entropy='device' (--encode gpu-entropy): encode='gpu' with the Huffman CODING on the device too (ctpn_write_annotated_files_device):
-    only the files' own bytes cross to the host. The files are byte-identical."""
+    only the files' own bytes cross to the host. The files are byte-identical.
+    png_encode='gpu' (--png-encode gpu, with write_images): the PNG-named outputs of library-decoded batches -- PNG batches, which reach the
+    device as host images, and device JPEG batches whose names end in .png -- are drawn, resized by 1 / scale and PNG-coded by the library
+    at collect time (ctpn_write_annotated_png_files). "Host work by nature" holds for READING a PNG file (inflate is serial, un-filtering
+    chains from row to row); writing one parallelises. The files are the library's own (Sub filter, one dynamic-Huffman block): they decode
+    to the pixels Pillow's files decode to, but are not byte-equal to them. Default 'host': Pillow, as before."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -261,7 +270,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
         _set_tail_params(net, params)
-    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_host": 0, "crops": 0}
+    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_png": 0, "enc_host": 0, "crops": 0}
+    png_batches = {}                                   # slot -> (device pointer or None, host images or None, shape, scale) of a batch whose PNG files the library writes
     dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
     crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images
     # PNG batches are decoded ONE JOB AHEAD on a helper thread (the C++ decode threads hang off that call; ctypes releases the GIL), so that
@@ -307,6 +317,12 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.write_annotated_files(ptr, shape, [results[nm] for nm in members], scale,
                                           [os.path.join(out_dir, os.path.basename(nm)) for nm in members], entropy=encode_entropy)
             stats["enc_gpu"] += len(members)
+        if slot in png_batches:                        # the same into PNG files (ctpn_write_annotated_png_files)
+            ptr, host_imgs, shape, scale = png_batches.pop(slot)
+            net.ctx.write_annotated_png_files(images=host_imgs, device_ptr=ptr, shape=shape, recs=[results[nm] for nm in members], scale=scale,
+                                              paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members])
+            stats["enc_gpu"] += len(members)
+            stats["enc_png"] += len(members)
         if slot in crop_src:                           # (a device batch is live until the second-next decode: this is one decode from its own)
             ptr, shape, imgs = crop_src.pop(slot)
             stats["crops"] += write_crops(net.ctx, crops_dir, members, [results[nm] for nm in members], crop_h, images=imgs, device_ptr=ptr, shape=shape)
@@ -333,6 +349,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                 stats["gpu"] += len(members)
                 if write_images and encode == "gpu" and all(_is_jpeg(nm) for nm in members):      # (the output's format follows its NAME)
                     dev_batches[k & 1] = (ptr, shape, f)      # (live until the second-next decode: collected one decode from now)
+                elif write_images and png_encode == "gpu" and all(_is_png(nm) for nm in members):
+                    png_batches[k & 1] = (ptr, None, shape, f)
                 elif write_images:
                     imgs = net.ctx.jpeg_batch_fetch(ptr, shape)
             except B.CtpnError as e:                                       # e.g. damaged entropy data: the host decoder's call
@@ -340,11 +358,14 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                     raise
                 kind = "host"
                 dev_batches.pop(k & 1, None)
+                png_batches.pop(k & 1, None)
         elif kind == "png":
             try:
                 imgs = png_ahead.pop(k).result()
                 net.ctx.detect_submit(images=imgs, slot=k & 1)
                 stats["png"] += len(members)
+                if write_images and png_encode == "gpu" and all(_is_png(nm) for nm in members):
+                    png_batches[k & 1] = (None, imgs, imgs.shape, f)      # (its ring buffer is not rewritten before the second-next decode)
             except B.CtpnError as e:
                 if e.code not in (B.CTPN_ERR_UNSUPPORTED, -1):
                     raise
@@ -354,7 +375,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.detect_submit(images=imgs, slot=k & 1)
             stats["host"] += len(members)
         for i, nm in enumerate(members):
-            meta[nm] = (imgs[i] if imgs is not None and write_images else None, f)
+            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches else None, f)
         if pending is not None:
             collect(pending)
         if crops_dir:
@@ -378,18 +399,22 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     if write_images:
         log('Annotated images: {:d} drawn, resized and JPEG-coded by the library (device + C++ pool), {:d} by the host writer (Pillow)'.format(
             stats["enc_gpu"], stats["enc_host"]))
+        if stats["enc_png"]:
+            log('... of the library\'s, {:d} are PNG files, coded on the device'.format(stats["enc_png"]))
     if crops_dir:
         log('Text-line crops: {:d} of height {:d} cut out on the device'.format(stats["crops"], crop_h))
     return results
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host", crops_dir=None, crop_h=32, params=None):
+        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host"):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
     (ctpn_write_annotated_files); 'gpu-entropy': the same with the Huffman coding on the device too (ctpn_write_annotated_files_device,
     byte-identical files); 'host' (default): every image through Pillow, as before.
+    png_encode='gpu' (needs decode='gpu'): the PNG-named outputs of library-decoded batches are written by the library too
+    (ctpn_write_annotated_png_files: PNG coding on the device); 'host' (default): Pillow, as before.
     crops_dir (needs decode='gpu'): every detected line also as a rectified crop of height crop_h, <stem>_<k>.jpg in that directory, cut out
     on the device at collect time (write_crops); None (default): nothing changes.
     params: {name: value} of the detection tail (ctpn_set_param: RPN_* and the connector's names) for the ctx of this run; the connector's
@@ -408,13 +433,17 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         decode = "gpu"
     if encode == "gpu" and decode != "gpu":
         raise ValueError("encode='gpu' writes the images of device-decoded batches: it needs decode='gpu'")
+    if png_encode not in ("host", "gpu"):
+        raise ValueError("png_encode must be 'host' or 'gpu'")
+    if png_encode == "gpu" and decode != "gpu":
+        raise ValueError("png_encode='gpu' writes the images of library-decoded batches: it needs decode='gpu'")
     if crops_dir is not None and decode != "gpu":
         raise ValueError("crops_dir cuts the lines out of the batches of the device path: it needs decode='gpu'")
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
-                        entropy=entropy, encode_entropy=encode_entropy)
+                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -557,6 +586,9 @@ def build_parser():
     ap.add_argument('--encode', default='host', choices=['host', 'gpu', 'gpu-entropy'],
                     help="gpu (with --decode gpu): annotated JPEG images drawn, resized and coded by the library (ctpn_write_annotated_files); "
                          "gpu-entropy: the same with the Huffman coding on the device too (ctpn_write_annotated_files_device)")
+    ap.add_argument('--png-encode', default='host', choices=['host', 'gpu'],
+                    help="gpu (with --decode gpu): the PNG-named annotated images of library-decoded batches drawn, resized and PNG-coded on the "
+                         "device (ctpn_write_annotated_png_files); host: Pillow")
     ap.add_argument('--crops', default=None, metavar='DIR',
                     help="(with --decode gpu) also write every detected line as a rectified crop <stem>_<k>.jpg of height --crop-height into DIR (ctpn_crop_lines)")
     ap.add_argument('--crop-height', type=int, default=32)
@@ -589,7 +621,7 @@ def main(argv=None):
     if not names:
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
-        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, crops_dir=args.crops, crop_h=args.crop_height,
+        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height,
         params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)))
     net.close()
 

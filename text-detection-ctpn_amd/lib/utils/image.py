@@ -50,7 +50,7 @@ def image_size(path):
 
 
 def imread(path):
-    """BGR uint8 HWC like cv2.imread(path). PNG files go through the library's decoder (ctpn_png_decode: host code by the nature of the format,
+    """BGR uint8 HWC like cv2.imread(path). PNG files go through the library's decoder (ctpn_png_decode: reading is host work by the nature of the format,
     libdeflate + row filters, byte-equal to Pillow's result at half its time); what it does not take (16-bit PNG) and every other format
     through Pillow."""
     if str(path).lower().endswith(".png"):
@@ -89,6 +89,23 @@ def imwrite_jpeg_batch(ctx, paths, images, quality=95, device_ptr=None, shape=No
     """imwrite for a batch of JPEG files: encoded by imencode_jpeg_batch, one file per image."""
     paths = list(paths)
     files = imencode_jpeg_batch(ctx, images, quality=quality, device_ptr=device_ptr, shape=shape, entropy=entropy)
+    assert len(files) == len(paths)
+    for path, data in zip(paths, files):
+        with open(path, "wb") as f:
+            f.write(data)
+
+
+def imencode_png_batch(ctx, images, device_ptr=None, shape=None):
+    """cv2.imencode('.png', img) for a batch of BGR uint8 images of one size, on the GPU (ctpn_encode_png_batch): (n, h, w, 3) on the host,
+    or device_ptr + shape -> list of n bytes objects. Lossless: every decoder returns the pixels; the bytes are this library's own (Sub
+    filter, run-length and row-above matches, one dynamic-Huffman block), not Pillow's or cv2's."""
+    return ctx.encode_png_batch(images, device_ptr=device_ptr, shape=shape)
+
+
+def imwrite_png_batch(ctx, paths, images, device_ptr=None, shape=None):
+    """imwrite for a batch of PNG files: encoded by imencode_png_batch, one file per image."""
+    paths = list(paths)
+    files = imencode_png_batch(ctx, images, device_ptr=device_ptr, shape=shape)
     assert len(files) == len(paths)
     for path, data in zip(paths, files):
         with open(path, "wb") as f:

@@ -203,6 +203,31 @@ int ctpn_forward(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int
  * mean of each other at 600x900 (tests/test_gpu_round3.py::test_float_blob_feed_tracks_uint8_feed_in_bf16_mode). In bf16 mode the
  * BiLSTM gates use v_exp_f32 / v_rcp_f32 (|diff| < 2e-5 on lstm_out against the exact path, same file). */
 int ctpn_forward_blob(ctpn_ctx* ctx, const float* blob, int blob_on_device, int n, int h, int w);
+/* ---- ragged batches: images of one WIDTH and different heights in one call --------------------
+ * (The reference's notion of such a batch is lib/utils/blob.py im_list_to_blob, which zero-pads a list of images to the largest shape; it
+ * asserts batch size 1 in front of it, lib/rpn_msr/proposal_layer_tf.py:51-52.)
+ * A ragged batch is a canvas n x hc x w x 3 (BGR uint8) plus heights[n], 16 <= heights[i] <= hc. Image i is rows [0, heights[i]) of slot i;
+ * the rows below it may hold anything and are never read as pixels. Its valid rows at pooling level L are heights[i] >> L (every VALID
+ * pool drops an odd last row): ctpn_ragged_valid_rows, a pure function (no ctx, no device; -1 for height < 0 or a level outside 0 .. 4).
+ * The forward runs the uniform forward's kernels on the canvas geometry (n, hc, w) and clears rows >= heights[i] >> L of every STORED
+ * activation of image i before the next layer reads it -- the input, every stored conv output, every stored pool output, rpn_conv/3x3 -- so
+ * that to the image above them those rows are the zero padding it would have had alone. The result is defined as, and tested to be, bit
+ * for bit what ctpn_forward / ctpn_detect give for image i alone (an n x heights[i] x w call of one image).
+ *  - conv1_1 is computed stand-alone from the q-image (the form option conv1_fuse = 0 selects: the same bytes); CTPN_PREC_FP32, CTPN_PREC_SPLIT
+ *    and conv1_kernel < 2 go through a ctx-owned float feed (pixel - PIXEL_MEANS inside an image, 0.0f below it; n * hc * w * 12 bytes,
+ *    allocated on the first ragged call and grown on demand).
+ *  - The BiLSTM, its projection and the heads run on all n * (hc >> 4) feature rows; the proposal layer gives the cells below an image no
+ *    candidates. Anchor indices (y * wf + x) * 10 + a are the lone image's, since wf is shared.
+ *  - im_info row i is [heights[i], w, scales[i]] in the detect forms. ctpn_proposals after a ragged forward uses that forward's valid rows
+ *    (its im_info is the caller's, as always); a uniform ctpn_forward forgets them.
+ *  - ctpn_get_tensor after a ragged forward returns canvas-shaped tensors (n, hc >> L, w >> L, C): conv and pool maps are zero below an
+ *    image, lstm_*, heads and rpn_* are undefined there.
+ *  - A call whose heights all equal hc IS the uniform call and takes its path (fused conv1_1, no clearing).
+ *  - A caller's device canvas is not modified. Mixed widths are not supported: group by width first.
+ * Errors: CTPN_ERR_ARG for a null pointer or a height outside 16 .. hc; CTPN_ERR_CAPACITY for the canvas as ctpn_forward; CTPN_ERR_STATE
+ * on a post-processing-only ctx or without weights. Asynchronous like ctpn_forward. */
+int ctpn_ragged_valid_rows(int height, int level);
+int ctpn_forward_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights);
 /* feature-map geometry of the last forward: hf = h/16 (VALID pools), wf = w/16 */
 int ctpn_feat_shape(ctpn_ctx* ctx, int* n, int* hf, int* wf);
 /* copy a named activation of the last forward to the host as dense fp32 NHWC (layer-wise parity).
@@ -312,6 +337,14 @@ int ctpn_detect_submit(ctpn_ctx* ctx, const uint8_t* images, int images_on_devic
                        const float* scales, int slot);
 int ctpn_detect_collect(ctpn_ctx* ctx, int slot, int mode, double* recs_out, int line_capacity, int* line_counts,
                         float* rois_out, int* roi_counts);
+
+/* ctpn_detect / ctpn_detect_submit for a ragged batch (see ctpn_forward_ragged): per image the rois, roi counts, anchors, lines and line
+ * counts of that image through ctpn_detect alone. Slots, outputs and ctpn_detect_collect as for the uniform forms. */
+int ctpn_detect_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                       const float* scales, int mode, double* recs_out, int line_capacity, int* line_counts,
+                       float* rois_out, int* roi_counts);
+int ctpn_detect_submit_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                              const float* scales, int slot);
 
 /* ---- measurement --------------------------------------------------------------------------
  * When enabled, every kernel launch on the ctx stream is bracketed by hipEvents; ctpn_profile_read

@@ -84,6 +84,10 @@ def _declare(lib):
         "ctpn_broadcast_weights_rank": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int, C.c_int]),
         "ctpn_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
         "ctpn_forward_blob": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "ctpn_ragged_valid_rows": (C.c_int, [C.c_int, C.c_int]),
+        "ctpn_forward_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p]),
+        "ctpn_detect_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f32p, C.c_int, f64p, C.c_int, i32p, f32p, i32p]),
+        "ctpn_detect_submit_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f32p, C.c_int]),
         "ctpn_feat_shape": (C.c_int, [vp, i32p, i32p, i32p]),
         "ctpn_get_tensor": (C.c_int, [vp, C.c_char_p, f32p, C.c_size_t, i32p]),
         "ctpn_proposals": (C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_float, C.c_float, f32p, i32p]),
@@ -613,6 +617,14 @@ def broadcast_weights(contexts):
     _check(load_library().ctpn_broadcast_weights(arr, len(contexts)))
 
 
+def ragged_valid_rows(height, level):
+    """Valid rows of an image of `height` pixel rows at pooling level 0 .. 4 (ctpn_ragged_valid_rows; needs no device)."""
+    r = load_library().ctpn_ragged_valid_rows(int(height), int(level))
+    if r < 0:
+        raise ValueError("ragged_valid_rows: height >= 0 and 0 <= level <= 4 required")
+    return r
+
+
 def host_thread_budget(cpu_count, local_world_size=1, requested=0):
     """ctpn_host_thread_budget: host workers per ctx (pure function of its arguments, no GPU needed)."""
     return int(load_library().ctpn_host_thread_budget(int(cpu_count), int(local_world_size), int(requested)))
@@ -744,6 +756,30 @@ class Context:
         self._keepalive = im
         _check(self._lib.ctpn_forward(self._h, im.ctypes.data_as(C.c_void_p), 0, n, h, w))
 
+    @staticmethod
+    def _canvas(canvas, heights, device_ptr, shape):
+        """-> (pointer, on_device, n, hc, w, heights int32, keepalive) of a ragged batch (ctpn_hip.h, ctpn_forward_ragged)."""
+        if device_ptr is not None:
+            n, hc, w = shape
+            ptr, on_dev, keep = C.c_void_p(int(device_ptr)), 1, None
+        else:
+            keep = np.ascontiguousarray(canvas, dtype=np.uint8)
+            if keep.ndim != 4 or keep.shape[3] != 3:
+                raise ValueError("canvas must be (n, hc, w, 3) uint8")
+            n, hc, w, _ = keep.shape
+            ptr, on_dev = keep.ctypes.data_as(C.c_void_p), 0
+        hts = np.ascontiguousarray(heights, dtype=np.int32).reshape(-1)
+        if hts.shape[0] != n:
+            raise ValueError("one height per image")
+        return ptr, on_dev, int(n), int(hc), int(w), hts, keep
+
+    def forward_ragged(self, canvas, heights, device_ptr=None, shape=None):
+        """Images of one width and different heights in one forward (ctpn_forward_ragged): canvas (n,hc,w,3) uint8 BGR, image i in rows
+        [0, heights[i]) of slot i (lib/utils/blob.py im_list_to_canvas builds one). Tensors come back canvas-shaped."""
+        ptr, on_dev, n, hc, w, hts, keep = self._canvas(canvas, heights, device_ptr, shape)
+        self._keepalive = (keep, hts)
+        _check(self._lib.ctpn_forward_ragged(self._h, ptr, on_dev, n, hc, w, _ptr(hts, C.c_int)))
+
     def forward_blob(self, blob, device_ptr=None, shape=None):
         """blob: (n,h,w,3) float32 BGR with PIXEL_MEANS already subtracted (the reference's net.data feed)."""
         if device_ptr is not None:
@@ -839,6 +875,24 @@ class Context:
                                      _ptr(recs, C.c_double), int(line_capacity), _ptr(lcnt, C.c_int),
                                      _ptr(rois, C.c_float) if want_rois else None,
                                      _ptr(rcnt, C.c_int) if want_rois else None))
+        lines = [recs[i, : lcnt[i]].copy() for i in range(n)]
+        if want_rois:
+            return lines, [rois[i, : rcnt[i]].copy() for i in range(n)]
+        return lines
+
+    def detect_ragged(self, canvas=None, heights=None, scales=None, mode="H", line_capacity=512, device_ptr=None, shape=None, want_rois=False):
+        """detect() for a ragged batch (ctpn_detect_ragged): per image what detect() returns for that image alone."""
+        ptr, on_dev, n, hc, w, hts, keep = self._canvas(canvas, heights, device_ptr, shape)
+        self._keepalive = (keep, hts)
+        sc = _f32(scales if scales is not None else np.ones((n,), np.float32)).reshape(-1)
+        recs = np.zeros((n, line_capacity, 9), np.float64)
+        lcnt = np.zeros((n,), np.int32)
+        rois = np.zeros((n, 1000, 5), np.float32) if want_rois else None
+        rcnt = np.zeros((n,), np.int32) if want_rois else None
+        m = MODE_O if str(mode).upper().startswith("O") else MODE_H
+        _check(self._lib.ctpn_detect_ragged(self._h, ptr, on_dev, n, hc, w, _ptr(hts, C.c_int), _ptr(sc, C.c_float), m,
+                                            _ptr(recs, C.c_double), int(line_capacity), _ptr(lcnt, C.c_int),
+                                            _ptr(rois, C.c_float) if want_rois else None, _ptr(rcnt, C.c_int) if want_rois else None))
         lines = [recs[i, : lcnt[i]].copy() for i in range(n)]
         if want_rois:
             return lines, [rois[i, : rcnt[i]].copy() for i in range(n)]
@@ -1058,8 +1112,18 @@ class Context:
             call(crops.ctypes.data_as(C.c_void_p), 0, crops.size)
         return crops, widths[: total.value].copy()
 
-    def detect_submit(self, images=None, slot=0, scales=None, device_ptr=None, shape=None):
-        """Asynchronous detect, part 1 (ctpn_detect_submit). Returns immediately."""
+    def detect_submit(self, images=None, slot=0, scales=None, device_ptr=None, shape=None, heights=None):
+        """Asynchronous detect, part 1 (ctpn_detect_submit). Returns immediately. heights: the batch is ragged -- images is a canvas
+        (ctpn_detect_submit_ragged; see forward_ragged)."""
+        if heights is not None:
+            ptr, on_dev, n, hc, w, hts, keep = self._canvas(images, heights, device_ptr, shape)
+            self._keep_slot = getattr(self, "_keep_slot", {})
+            self._keep_slot[slot] = (keep, hts)
+            sc = _f32(scales if scales is not None else np.ones((n,), np.float32)).reshape(-1)
+            _check(self._lib.ctpn_detect_submit_ragged(self._h, ptr, on_dev, n, hc, w, _ptr(hts, C.c_int), _ptr(sc, C.c_float), int(slot)))
+            self._slot_n = getattr(self, "_slot_n", {})
+            self._slot_n[slot] = n
+            return
         if device_ptr is not None:
             n, h, w = shape
             ptr, on_dev = C.c_void_p(int(device_ptr)), 1
@@ -1090,6 +1154,8 @@ class Context:
         if want_rois:
             return lines, [rois[i, : rcnt[i]].copy() for i in range(n)]
         return lines
+
+    ragged_valid_rows = staticmethod(ragged_valid_rows)
 
     # ---- measurement
     def profile_enable(self, on=True):

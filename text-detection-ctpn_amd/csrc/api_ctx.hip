@@ -372,6 +372,8 @@ int ctpn_destroy(ctpn_ctx* c) {
     for (hipEvent_t e : {sl.ev_heads, sl.ev_decoded, sl.ev_done}) if (e) (void)hipEventDestroy(e);
   }
   for (hipEvent_t e : {c->ev_conv, c->ev_tail}) if (e) (void)hipEventDestroy(e);
+  for (auto& r : c->ragged) { if (r.host) (void)hipHostFree(r.host); if (r.dev) (void)hipFree(r.dev); if (r.ev_copied) (void)hipEventDestroy(r.ev_copied); }
+  if (c->ragged_blob) (void)hipFree(c->ragged_blob);
   for (auto& j : c->jpeg) {
     if (j.coef_host) (void)hipHostFree(j.coef_host);
     if (j.qt_host) (void)hipHostFree(j.qt_host);

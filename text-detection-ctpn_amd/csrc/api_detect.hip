@@ -42,12 +42,14 @@ static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hip
 // lone: a synchronous ctpn_detect with nothing else in flight on this ctx -- the proposal layer and the connector front end then follow the
 // forward on ITS stream instead of hopping to the proposal stream (an event record + a cross-queue wait: ~12 us of a lone image's millisecond;
 // the second stream exists to run the tail under the NEXT batch's convolutions, and there is no next batch here)
-static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone) {
+// heights (nullable): a ragged batch in a canvas of height h (ctpn_detect_submit_ragged)
+static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone,
+                              const int* heights) {
   if (!c) return fail(CTPN_ERR_ARG, "ctpn_detect_submit: null ctx");
   if (slot < 0 || slot > 1) return fail(CTPN_ERR_ARG, "ctpn_detect_submit: slot must be 0 or 1");
   ctpn_ctx::Slot& sl = c->slot[slot];
   if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_detect_submit: slot still holds an uncollected batch");
-  int rc = forward_impl(c, images, 0, images_on_device, n, h, w, c->tail_overlap != 0);
+  int rc = forward_impl(c, images, 0, images_on_device, n, h, w, c->tail_overlap != 0, heights, slot);
   if (rc) {
     // a forward that failed midway may have consumed the cross-stream hand-over state (tail_pending is cleared when the wait is ENQUEUED,
     // the events are recorded later): drain both streams so that a retry starts from a quiet ctx, keeping the first error text
@@ -56,14 +58,18 @@ static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_
     c->tail_pending = false; c->ev_last_decoded = nullptr; c->ev_last_done = nullptr;
     return fail(rc, first);
   }
-  for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)h; sl.im_info[3 * i + 1] = (float)w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
+  // im_info row i = [the image's own height, w, scale]: what the proposal layer clips to, and lines_prep, the connector's NMS and connect_kernel read
+  sl.hts.assign(n, h);
+  if (heights) sl.hts.assign(heights, heights + n);
+  for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)sl.hts[i]; sl.im_info[3 * i + 1] = (float)w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
   hipStream_t p = lone ? c->stream : c->stream_p;
   if (!lone) {
     CTPN_HIP_TRY(hipEventRecord(sl.ev_heads, c->stream));
     CTPN_HIP_TRY(hipStreamWaitEvent(p, sl.ev_heads, 0));
   }
   // cfg.TEST.RPN_* (reference lib/fast_rcnn/config.py:175-183): the ctx's parameters, those defaults unless ctpn_set_param changed them
-  rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded);
+  rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded,
+                         c->fwd_ragged >= 0 ? c->ragged[c->fwd_ragged].dev + n : nullptr);
   if (rc) return rc;
   c->ev_last_decoded = sl.ev_decoded;
   if ((rc = enqueue_text_lines(c, sl, n, w, p))) return rc;
@@ -73,15 +79,17 @@ static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_
   sl.n = n; sl.h = h; sl.w = w; sl.busy = true;
   return CTPN_OK;
 }
-static int detect_submit_impl(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone) {
-  const int rc = detect_submit_body(c, images, images_on_device, n, h, w, scales, slot, lone);
+static int detect_submit_impl(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone,
+                              const int* heights = nullptr) {
+  const int rc = detect_submit_body(c, images, images_on_device, n, h, w, scales, slot, lone, heights);
   if (rc != CTPN_OK && c) c->nms_mw_dirty = true;        // an error anywhere in a submit (the connector NMS's launch included): see common.h, NMS_MW_OVERFLOW_OFF
   return rc;
 }
 
 // the lines of a batch whose tail has finished, from what it left in the slot's page-locked buffers: the device connector's records (option
 // connect_device), or connect_lines on the host workers over the connector NMS's survivors. ctpn_detect_collect and ctpn_debug_text_lines.
-static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int h, int w, int mode, double* recs_out, int line_capacity, int* line_counts) {
+// sl.hts: the images' heights (one value unless the batch was ragged).
+static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, int mode, double* recs_out, int line_capacity, int* line_counts) {
   const int post = c->rpn_post;
   const ConnectorCfg cfg = c->conn;      // the workers' copy
   if (c->connect_device) {
@@ -105,7 +113,7 @@ static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int h, int w, i
       ks[j] = sl.tls[(size_t)i * post + src];
     }
     std::vector<double> recs;
-    int st = connect_lines(kb.data(), ks.data(), nk, h, w, mode, cfg, recs);
+    int st = connect_lines(kb.data(), ks.data(), nk, sl.hts[i], w, mode, cfg, recs);
     if (st) { status[i] = st; errs[i] = ctpn_last_error(); return; }
     const int cnt = (int)(recs.size() / 9);
     line_counts[i] = cnt;
@@ -135,6 +143,7 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
   ctpn_ctx::Slot& sl = c->slot[0];
   hipStream_t p = c->stream_p;
+  sl.hts.assign(n, im_h);
   for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)im_h; sl.im_info[3 * i + 1] = (float)im_w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
   if (c->nms_mw_scratch && c->nms_mw_dirty) {       // as enqueue_proposals does in front of a submit's tail
     CTPN_HIP_TRY(hipMemsetAsync(c->nms_mw_scratch, 0, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, p));
@@ -155,7 +164,7 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
   // option nms_check, as in the proposal layer: the generic kernel on the same prepared boxes must keep the same rows
   if (c->nms_check && form != 0 &&
       (rc = nms_check_generic(c, c->tl_boxes, c->tl_scores, c->tl_counts, post, c->conn.nms_thresh, post, sl.keep, post, sl.kcnt, n, form == 2, p, "connector NMS"))) return rc;
-  return lines_of_slot(c, sl, n, im_h, im_w, mode, recs_out, line_capacity, line_counts);
+  return lines_of_slot(c, sl, n, im_w, mode, recs_out, line_capacity, line_counts);
 }
 
 }  // namespace ctpn
@@ -199,11 +208,11 @@ int ctpn_detect_collect(ctpn_ctx* c, int slot, int mode, double* recs_out, int l
   if (!sl.busy) return fail(CTPN_ERR_STATE, "ctpn_detect_collect: nothing was submitted to this slot");
   CTPN_HIP_TRY(hipEventSynchronize(sl.ev_done));
   sl.busy = false;
-  const int n = sl.n, h = sl.h, w = sl.w, post = c->rpn_post, post_max = c->post_max;
+  const int n = sl.n, w = sl.w, post = c->rpn_post, post_max = c->post_max;
   // rois_out keeps post_max (1000) rows per image whatever RPN_POST_NMS_TOP_N is; the slot holds them packed
   if (rois_out) for (int i = 0; i < n; ++i) std::memcpy(rois_out + (size_t)i * post_max * 5, sl.rois + (size_t)i * post * 5, (size_t)post * 5 * sizeof(float));
   if (roi_counts) std::memcpy(roi_counts, sl.rcnt, (size_t)n * sizeof(int));
-  return lines_of_slot(c, sl, n, h, w, mode, recs_out, line_capacity, line_counts);
+  return lines_of_slot(c, sl, n, w, mode, recs_out, line_capacity, line_counts);
 }
 
 int ctpn_detect(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int mode,
@@ -213,6 +222,22 @@ int ctpn_detect(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n,
   int slot = c->slot[0].busy ? 1 : 0;
   const bool lone = !c->slot[0].busy && !c->slot[1].busy && c->tail_overlap == 0;
   int rc = detect_submit_impl(c, images, images_on_device, n, h, w, scales, slot, lone);
+  if (rc) return rc;
+  return ctpn_detect_collect(c, slot, mode, recs_out, line_capacity, line_counts, rois_out, roi_counts);
+}
+
+int ctpn_detect_submit_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const float* scales, int slot) {
+  if (!c || !heights) return fail(CTPN_ERR_ARG, "ctpn_detect_submit_ragged: null pointer");
+  return detect_submit_impl(c, canvas, canvas_on_device, n, hc, w, scales, slot, false, heights);
+}
+
+int ctpn_detect_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const float* scales, int mode,
+                       double* recs_out, int line_capacity, int* line_counts, float* rois_out, int* roi_counts) {
+  if (!c || !heights || !recs_out || !line_counts) return fail(CTPN_ERR_ARG, "ctpn_detect_ragged: null pointer");
+  if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "ctpn_detect_ragged: mode must be H(0) or O(1)");
+  int slot = c->slot[0].busy ? 1 : 0;
+  const bool lone = !c->slot[0].busy && !c->slot[1].busy && c->tail_overlap == 0;
+  int rc = detect_submit_impl(c, canvas, canvas_on_device, n, hc, w, scales, slot, lone, heights);
   if (rc) return rc;
   return ctpn_detect_collect(c, slot, mode, recs_out, line_capacity, line_counts, rois_out, roi_counts);
 }

@@ -15,12 +15,47 @@ static void parallel_memcpy(HostPool* pool, void* dst, const void* src, size_t b
   }, 8);
 }
 
-int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p) {
+// a ragged batch's heights on their way to the device: [heights(n) | feature rows(n)] through the set's page-locked array, copied on s
+static int ragged_upload(ctpn_ctx* c, ctpn_ctx::RaggedSet& r, const int* heights, int n, hipStream_t s) {
+  if (!r.host) {
+    CTPN_HIP_TRY(hipHostMalloc((void**)&r.host, (size_t)c->max_batch * 2 * sizeof(int)));
+    CTPN_HIP_TRY(hipMalloc((void**)&r.dev, (size_t)c->max_batch * 2 * sizeof(int)));
+    CTPN_HIP_TRY(hipEventCreateWithFlags(&r.ev_copied, hipEventDisableTiming));
+  }
+  if (r.copied_valid) CTPN_HIP_TRY(hipEventSynchronize(r.ev_copied));      // the copy that last read the page-locked array (long done)
+  for (int i = 0; i < n; ++i) { r.host[i] = heights[i]; r.host[n + i] = ragged_valid_rows(heights[i], 4); }
+  CTPN_HIP_TRY(hipMemcpyAsync(r.dev, r.host, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+  CTPN_HIP_TRY(hipEventRecord(r.ev_copied, s));
+  r.copied_valid = true;
+  return CTPN_OK;
+}
+
+// the mask launch behind one stored map of a ragged batch (canvas n x hc x w): a bordered activation buffer at pooling level `level`
+static int ragged_mask_act(void* buf, size_t pix_bytes, int level, const int* heights, const int* heights_dev, int n, int hc, int w, hipStream_t s) {
+  const int hl = lvl(hc, level), wl = lvl(w, level);
+  RaggedMap m;
+  m.row_bytes = (long long)(wl + 2) * (long long)pix_bytes; m.img_bytes = (long long)(hl + 2) * m.row_bytes;
+  m.top = 1; m.left_bytes = (int)pix_bytes; m.span_bytes = (int)(wl * pix_bytes); m.rows = hl; m.level = level;
+  int pad = 0;
+  for (int i = 0; i < n; ++i) pad = std::max(pad, hl - ragged_valid_rows(heights[i], level));
+  return launch_ragged_mask(buf, m, heights_dev, n, pad, s);
+}
+
+int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p, const int* heights, int rset) {
   if (!c || !images) return fail(CTPN_ERR_ARG, "null pointer");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_forward: post-processing-only ctx (ctpn_create_postproc) has no network");
   if (!c->weights_loaded) return fail(CTPN_ERR_STATE, "ctpn_forward: weights not loaded");
   if (n <= 0 || n > c->max_batch || h < 16 || w < 16 || h > c->max_h || w > c->max_w)
     return fail(CTPN_ERR_CAPACITY, "ctpn_forward: batch/size outside what the ctx was created for (h, w >= 16)");
+  // a ragged batch (h is the canvas height). One whose heights all equal h IS the uniform batch and takes the uniform path
+  bool ragged = false;
+  if (heights) {
+    if (is_f32 || rset < 0 || rset > 2) return fail(CTPN_ERR_ARG, "ragged forward: uint8 canvas only");
+    for (int i = 0; i < n; ++i) {
+      if (heights[i] < 16 || heights[i] > h) return fail(CTPN_ERR_ARG, "ragged forward: every height must lie in 16 .. the canvas height");
+      ragged = ragged || heights[i] != h;
+    }
+  }
   CTPN_HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
   int rc;
@@ -80,6 +115,12 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
     img = c->img_dev_b[staged];
   }
   c->n = n; c->h = h; c->w = w;
+  c->fwd_ragged = ragged ? rset : -1;
+  const int* hts_dev = nullptr;
+  if (ragged) {
+    if ((rc = ragged_upload(c, c->ragged[rset], heights, n, s))) return rc;
+    hts_dev = c->ragged[rset].dev;
+  }
   int jpeg_src = -1;
   if (images_on_device && c->jpeg_ready)
     for (int b = 0; b < 2; ++b)
@@ -96,12 +137,34 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
     // uint8 feed of the 16-bit modes ("conv1_kernel" = 2): bytes -> q-image; conv1_1 then runs inside conv1_2's window stage (the production
     // path: its 69 MB per image are never stored) or, with keep_acts / "conv1_fuse" = 0, stand-alone from the q-image: the same bytes
     via_q = !is_f32 && dtype_is_half(c->prec) && c->conv1_mfma >= 2 && c->q_img != nullptr;
-    fuse1 = via_q && c->conv1_fuse && !c->keep_acts && conv1_fusable(c->prec, n, h, w, 64, 64, true, false);
+    // a ragged batch takes the stand-alone form: the fused one never stores conv1_1, so nothing could be cleared below an image, where it
+    // yields ReLU(bias) and not 0 (the two forms store the same bytes: option conv1_fuse)
+    fuse1 = via_q && c->conv1_fuse && !c->keep_acts && !ragged && conv1_fusable(c->prec, n, h, w, 64, 64, true, false);
     if (via_q) {
       if ((rc = launch_image_to_q((const uint8_t*)img, c->q_img, c->prec, n, h, w, s))) return rc;
+      if (ragged) {      // the q-image's rows below an image: all four channels, the 1.0 that says "inside the image" included
+        RaggedMap m;
+        m.row_bytes = (long long)conv1_q_w(w) * 8; m.img_bytes = (long long)conv1_q_h(h) * m.row_bytes;
+        m.top = 2; m.left_bytes = 16; m.span_bytes = w * 8; m.rows = h; m.level = 0;
+        int pad = 0;
+        for (int i = 0; i < n; ++i) pad = std::max(pad, h - heights[i]);
+        if ((rc = launch_ragged_mask(c->q_img, m, hts_dev, n, pad, s))) return rc;
+      }
       if (!fuse1 && (rc = launch_conv_first_from_q(c->q_img, conv1_p_frags(c->w_first_frags, c->prec), c->act_conv[0], c->prec, n, h, w, 0, w, s))) return rc;
+    } else if (ragged) {
+      // the kernels that read raw pixels (fp32, split precision; the 16-bit modes with conv1_kernel < 2) take the float feed instead, which they
+      // compute identically (ctpn_forward_blob): p - mean inside an image, 0.0f below it
+      const size_t need = (size_t)n * h * w * 3 * sizeof(float);
+      if (need > c->ragged_blob_bytes) {
+        CTPN_HIP_TRY(hipStreamSynchronize(s));      // an earlier ragged forward may still read the block that goes
+        if ((rc = grow_dev((void**)&c->ragged_blob, c->ragged_blob_bytes, need))) return rc;
+      }
+      if ((rc = launch_ragged_blob((const uint8_t*)img, c->ragged_blob, hts_dev, n, h, w, s))) return rc;
+      if ((rc = launch_conv_first(c->ragged_blob, 1, c->w_first, c->b_conv[0], c->act_conv[0], c->prec, n, h, w, s,
+                                  frags ? c->w_first_frags : nullptr))) return rc;
     } else if ((rc = launch_conv_first(img, is_f32, c->w_first, c->b_conv[0], c->act_conv[0], c->prec, n, h, w, s,
                                        frags ? c->w_first_frags : nullptr))) return rc;
+    if (ragged && (rc = ragged_mask_act(c->act_conv[0], (size_t)64 * c->es, 0, heights, hts_dev, n, h, w, s))) return rc;
   }
   c->act_valid[0] = !fuse1;      // fused: conv1_1's map exists only inside conv1_2's LDS windows
   if (jpeg_src >= 0) {           // the images came from ctpn_decode_jpeg_batch: its buffer may be rewritten once the first layer has read it
@@ -141,6 +204,11 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
                                f1 ? c->q_img : nullptr, f1 ? conv1_p_frags(c->w_first_frags, c->prec) : nullptr, (c->conv_p64 ? 1 : 0) | (c->split_edge ? 2 : 0)))) return rc;
     }
     c->act_valid[i] = full != nullptr;
+    if (ragged) {      // every stored output, before the next layer reads it
+      const size_t pix = (size_t)kConvs[i].co * ((c->prec == DType::SPLIT && i == 13) ? 6 : c->es);
+      if (full && (rc = ragged_mask_act(full, pix, kConvs[i].level, heights, hts_dev, n, h, w, s))) return rc;
+      if (fuse && (rc = ragged_mask_act(c->act_pool[pool_i], (size_t)kConvs[i].co * c->es, kConvs[i].level + 1, heights, hts_dev, n, h, w, s))) return rc;
+    }
     cur = fuse ? c->act_pool[pool_i] : c->act_conv[i];
     if (fuse) ++pool_i;
   }
@@ -218,6 +286,11 @@ int ctpn_forward(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n
 }
 int ctpn_forward_blob(ctpn_ctx* c, const float* blob, int blob_on_device, int n, int h, int w) {
   return forward_impl(c, blob, 1, blob_on_device, n, h, w);
+}
+
+int ctpn_forward_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights) {
+  if (!c || !canvas || !heights) return fail(CTPN_ERR_ARG, "ctpn_forward_ragged: null pointer");
+  return forward_impl(c, canvas, 0, canvas_on_device, n, hc, w, false, heights, 2);
 }
 
 int ctpn_feat_shape(ctpn_ctx* c, int* n, int* hf, int* wf) {

@@ -36,7 +36,8 @@ int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, cons
 }
 
 static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
-                                  int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s, hipEvent_t ev_decoded) {
+                                  int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s, hipEvent_t ev_decoded,
+                                  const int* valid_rows_dev) {
   if (!s) s = c->stream;
   if (!im_info) return fail(CTPN_ERR_ARG, "proposals: null pointer");
   if (pre_nms_topn <= 0 || pre_nms_topn > c->topn_max) return fail(CTPN_ERR_CAPACITY, "proposals: pre_nms_topn must be in 1..12000");
@@ -58,7 +59,7 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
   {
     Timed t(c, CTPN_KIND_DECODE, nanch * (60.0 * 4 / 10 + 8 + 16), s);
     if ((rc = launch_decode(heads, 64, heads_are_probs, c->cls_in, c->bbox_in, c->im_info_dev, heads_are_probs ? nullptr : c->cls_prob,
-                            heads_are_probs ? nullptr : c->bbox_pred, c->keys, c->boxes4, pc, npad, s, seg_sort && sort_is_segmented(n, per_img), n <= 4 ? im_info : nullptr))) return rc;
+                            heads_are_probs ? nullptr : c->bbox_pred, c->keys, c->boxes4, pc, npad, s, seg_sort && sort_is_segmented(n, per_img), n <= 4 ? im_info : nullptr, valid_rows_dev))) return rc;
   }
   if (ev_decoded) CTPN_HIP_TRY(hipEventRecord(ev_decoded, s));
   {
@@ -107,17 +108,18 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
 }
 int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
                       int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s,
-                      hipEvent_t ev_decoded) {
-  const int rc = enqueue_proposals_impl(c, heads, heads_are_probs, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size, s, ev_decoded);
+                      hipEvent_t ev_decoded, const int* valid_rows_dev) {
+  const int rc = enqueue_proposals_impl(c, heads, heads_are_probs, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size, s, ev_decoded, valid_rows_dev);
   if (rc != CTPN_OK) c->nms_mw_dirty = true;       // whatever failed, nobody vouches for the multi-workgroup NMS's scratch any more (common.h)
   return rc;
 }
 
 static int run_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
-                         int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* rois_out, int* counts_out) {
+                         int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* rois_out, int* counts_out,
+                         const int* valid_rows_dev = nullptr) {
   if (!rois_out || !counts_out) return fail(CTPN_ERR_ARG, "proposals: null pointer");
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));   // the asynchronous detect path shares the proposal buffers
-  int rc = enqueue_proposals(c, heads, heads_are_probs, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size);
+  int rc = enqueue_proposals(c, heads, heads_are_probs, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size, nullptr, nullptr, valid_rows_dev);
   if (rc) return rc;
   hipStream_t s = c->stream;
   CTPN_HIP_TRY(hipMemcpyAsync(counts_out, c->keep_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -146,8 +148,10 @@ int ctpn_proposals(ctpn_ctx* c, const float* im_info, int pre_nms_topn, int post
   if (!c) return fail(CTPN_ERR_ARG, "null ctx");
   if (!c->forward_done) return fail(CTPN_ERR_STATE, "ctpn_proposals: no forward yet");
   CTPN_HIP_TRY(hipSetDevice(c->device));
+  // after a ragged forward: that forward's feature rows per image (its set's second half), which a uniform forward forgets
+  const int* valid = c->fwd_ragged >= 0 ? c->ragged[c->fwd_ragged].dev + c->n : nullptr;
   return run_proposals(c, c->heads, 0, c->n, lvl(c->h, 4), lvl(c->w, 4), im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size,
-                       rois_out, counts_out);
+                       rois_out, counts_out, valid);
 }
 
 int ctpn_proposals_from_host(ctpn_ctx* c, const float* cls_prob, const float* bbox_pred, int n, int hf, int wf, const float* im_info,

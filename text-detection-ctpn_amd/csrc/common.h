@@ -10,6 +10,7 @@
 #include "../../include/ctpn_hip.h"
 #include "jpeg_pixel.h"
 #include "jpeg_huff_dev.h"
+#include "ragged_dev.h"
 
 namespace ctpn {
 
@@ -234,7 +235,8 @@ int launch_decode(const float* heads, int head_ld, int heads_are_probs, const fl
                   const float* bbox_in, const float* im_info_dev, float* cls_prob_out, float* bbox_out,
                   unsigned long long* keys, float* boxes4, const ProposalCfg& c, int npad, hipStream_t s,
                   bool skip_fill = false /* the keys behind the image's anchors are not read (launch_sort_keys' segmented form) */,
-                  const float* im_info_host = nullptr /* n <= 4: the rows travel in the kernel arguments and decode_kernel writes im_info_dev itself */);
+                  const float* im_info_host = nullptr /* n <= 4: the rows travel in the kernel arguments and decode_kernel writes im_info_dev itself */,
+                  const int* valid_rows_dev = nullptr /* ragged batch: feature rows of every image; cells below them get KEY_INVALID */);
 bool sort_is_segmented(int n_img, int per_img);      // will launch_sort_keys(..., in_tmp != nullptr) take the segmented form?
 // stable radix sort of the first per_img keys of every npad-strided segment (tmp: same size as keys)
 // in_tmp != nullptr allows the segmented form for small batches; *in_tmp says which buffer holds the sorted keys afterwards
@@ -383,6 +385,11 @@ int launch_png_hist(const PngeImg* imgs, const uint8_t* px, uint32_t* hist, int 
 int launch_png_code(const PngeImg* imgs, const uint8_t* px, const PngeCodes* codes, PngeLen* len, uint32_t* words, PngeRes* res, int n, uint32_t max_pieces, hipStream_t s);
 // png.cpp: CRC-32 of the PNG chunks (the DEFLATE library's where one is loaded)
 uint32_t png_crc32(const uint8_t* p, size_t n);
+
+// ragged.hip: a canvas batch of images of one width and different heights (RaggedMap and the per-thread bodies: ragged_dev.h).
+// heights_dev: the batch's pixel heights; max_pad_rows: the most rows any image lacks at the map's level (0: no launch)
+int launch_ragged_mask(void* base, const RaggedMap& m, const int* heights_dev, int n, int max_pad_rows, hipStream_t s);
+int launch_ragged_blob(const uint8_t* canvas, float* blob, const int* heights_dev, int n, int hc, int w, hipStream_t s);
 
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 

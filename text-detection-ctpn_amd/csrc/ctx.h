@@ -135,6 +135,7 @@ struct ctpn_ctx {
     double* crecs = nullptr; int* ccnt = nullptr;      // device connector results: [n][2 modes][CONN_CAP][9], [n][3]
     hipEvent_t ev_heads = nullptr, ev_decoded = nullptr, ev_done = nullptr;
     int n = 0, h = 0, w = 0; bool busy = false;
+    std::vector<int> hts;      // pixel height of every image of the batch (a ragged submit: the caller's heights; else h): what the host connector clips to
   } slot[2];
   hipEvent_t ev_last_decoded = nullptr;  // decode of the most recent submit (it reads `heads`, which the next forward rewrites)
   hipEvent_t ev_last_done = nullptr;     // the whole proposal tail (stream_p) of the most recent submit
@@ -322,6 +323,16 @@ struct ctpn_ctx {
   float* cls_in = nullptr;  // staging for proposals_from_host
   float* bbox_in = nullptr;
 
+  // ragged batches (ctpn_forward_ragged, ctpn_detect_submit_ragged; ragged.hip): a batch's heights reach the device once per call, through a small
+  // page-locked array, as [heights(n) | feature rows(n)]. One set per detect slot and one for ctpn_forward_ragged (index 2): a slot's
+  // decode kernel reads its set on stream_p while the next submit's forward already copies the other slot's. Allocated on the first ragged call.
+  struct RaggedSet {
+    int* host = nullptr; int* dev = nullptr;
+    hipEvent_t ev_copied = nullptr; bool copied_valid = false;      // the copy that last read `host`
+  } ragged[3];
+  float* ragged_blob = nullptr; size_t ragged_blob_bytes = 0;       // fp32 / split precision: the canvas as a float feed, 0.0f below the images
+  int fwd_ragged = -1;               // the last forward was ragged: index of its set (ctpn_proposals hands its feature rows to decode_kernel), else -1
+
   // last forward geometry
   int n = 0, h = 0, w = 0;
   int gn = -1, gh = -1, gw = -1;  // geometry the borders are currently zeroed for
@@ -408,11 +419,14 @@ struct Timed {
 };
 
 // the network forward (api_forward.hip); tail_on_p: the recurrent tail runs on stream_p (option tail_overlap)
-int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p = false);
+// heights (nullable): a ragged batch -- h is the canvas height, image i is rows [0, heights[i]) of its slot; rset: which of the ctx's RaggedSets
+// carries them to the device. Heights that all equal h take the uniform path.
+int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p = false,
+                 const int* heights = nullptr, int rset = 2);
 // the proposal layer in stream order on s (api_proposals.hip; null: the forward's stream); ev_decoded is recorded behind the decode kernel
 int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
                       int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s = nullptr,
-                      hipEvent_t ev_decoded = nullptr);
+                      hipEvent_t ev_decoded = nullptr, const int* valid_rows_dev = nullptr /* ragged batch: feature rows per image */);
 // option nms_check behind a column-decomposed NMS launch on s (api_proposals.hip): the generic kernel on the same candidates must give keep1 / cnt1
 int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, const int* counts, int stride, float thresh, int post_topn,
                       const int* keep1, int keep_stride, const int* cnt1, int n, bool mw, hipStream_t s, const char* what);

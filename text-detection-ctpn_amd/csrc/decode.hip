@@ -33,7 +33,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
                                                      const float* __restrict__ im_info, float* __restrict__ cls_prob_out,
                                                      float* __restrict__ bbox_out, unsigned long long* __restrict__ keys,
                                                      float* __restrict__ boxes4, int n_img, int hf, int wf, float min_size,
-                                                     int npad, ImInfoSmall small, float* __restrict__ im_info_pub) {
+                                                     int npad, ImInfoSmall small, float* __restrict__ im_info_pub,
+                                                     const int* __restrict__ valid_rows) {
   const int per_img = hf * wf * 10;
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   // small batches: im_info arrives in the kernel arguments (no 12-byte host-to-device copy in front of this kernel: ~5 us of a lone image's
@@ -98,7 +99,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
   // _filter_boxes
   const float ms = min_size * imS;
   const float ws = x2 - x1 + 1.0f, hs = y2 - y1 + 1.0f;
-  const bool keep = (ws >= ms) && (hs >= ms);
+  // ragged batch (valid_rows: feature rows of every image, else null): the cells below an image are not the image's
+  const bool keep = (ws >= ms) && (hs >= ms) && (!valid_rows || y < valid_rows[img]);
 
   *(float4*)(boxes4 + ((long long)img * per_img + idx) * 4) = make_float4(x1, y1, x2, y2);
   // High word = ~(order-preserving image of the score): ascending key = descending score for EVERY finite score (also 0.0
@@ -122,7 +124,8 @@ __global__ void fill_keys_kernel(unsigned long long* keys, int n_img, int npad, 
 
 int launch_decode(const float* heads, int head_ld, int heads_are_probs, const float* cls_prob_in, const float* bbox_in,
                   const float* im_info_dev, float* cls_prob_out, float* bbox_out, unsigned long long* keys, float* boxes4,
-                  const ProposalCfg& c, int npad, hipStream_t s, bool skip_fill, const float* im_info_host) {
+                  const ProposalCfg& c, int npad, hipStream_t s, bool skip_fill, const float* im_info_host,
+                  const int* valid_rows_dev) {
   const int per_img = c.hf * c.wf * 10;
   const long long total = (long long)c.n * per_img;
   if (npad > per_img && !skip_fill) {      // (the segmented sort of small batches never reads behind the image's keys and pads its merged buffer itself)
@@ -133,7 +136,7 @@ int launch_decode(const float* heads, int head_ld, int heads_are_probs, const fl
   if (im_info_host && c.n <= 4) for (int i = 0; i < 3 * c.n; ++i) small.v[i] = im_info_host[i];
   hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
                      heads_are_probs ? nullptr : heads, head_ld, cls_prob_in, bbox_in, im_info_dev, cls_prob_out, bbox_out,
-                     keys, boxes4, c.n, c.hf, c.wf, c.min_size, npad, small, im_info_host && c.n <= 4 ? (float*)im_info_dev : nullptr);
+                     keys, boxes4, c.n, c.hf, c.wf, c.min_size, npad, small, im_info_host && c.n <= 4 ? (float*)im_info_dev : nullptr, valid_rows_dev);
   return launch_status("decode");
 }
 

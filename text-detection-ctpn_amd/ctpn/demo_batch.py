@@ -41,6 +41,7 @@ from ctpn_amd.lib.networks.factory import get_network  # noqa: E402
 from ctpn_amd.lib.fast_rcnn.config import cfg, cfg_from_file  # noqa: E402
 from ctpn_amd.lib.fast_rcnn.test import _scale_for  # noqa: E402
 from ctpn_amd.lib.utils import image as imutil  # noqa: E402
+from ctpn_amd.lib.utils.blob import im_list_to_canvas  # noqa: E402
 from ctpn_amd.lib.text_connector.text_connect_cfg import Config as TextLineCfg  # noqa: E402
 
 
@@ -78,6 +79,43 @@ def plan(names, batch):
         for i in range(0, len(members), batch):
             jobs.append((shape, members[i:i + batch]))
     return jobs, singles, shapes
+
+
+RAGGED_WASTE = 0.25      # plan_ragged_batches' default: see there
+
+
+def plan_ragged_batches(shapes, max_batch, waste=RAGGED_WASTE):
+    """Ragged batches (Context.detect_submit(..., heights=): images of one width and different heights in one call) for images of the
+    given (h, w) shapes. -> (batches, alone): batches = [((hc, w), [indices into shapes])] with at least two members each, alone = the
+    indices that ended without company (they go through the uniform path). A pure function.
+    Per width: the images sorted by height, tallest first; the tallest remaining one opens a batch and sets its canvas height hc; the
+    next joins while the batch is below max_batch and the padded rows, sum(hc - h_i), stay within waste * n * hc. Equal heights therefore
+    form the plain batches they always did, whatever waste is.
+    waste: a padded row costs about what a valid one does (the masks only clear it), and a lone 600 x 900 bf16 image costs about 2.4 x a
+    batched one (README), so padding pays up to roughly 1 - 1 / 2.4 = 0.58 of a batch; 0.25 keeps well inside that and still joins the
+    usual portrait pages at width 600 (letter 776, 3:4 800, A4 849, 9:16 1067 rows: one of each pads 18 % of the batch). It is a first
+    value: tools/ragged_throughput.py measures the three forms it decides between."""
+    if max_batch < 1 or not 0.0 <= waste < 1.0:
+        raise ValueError("plan_ragged_batches: max_batch >= 1 and 0 <= waste < 1 required")
+    by_w = {}
+    for i, (h, w) in enumerate(shapes):
+        by_w.setdefault(int(w), []).append((int(h), i))
+    batches, alone = [], []
+    for w in sorted(by_w):
+        rest = sorted(by_w[w], key=lambda t: (-t[0], t[1]))
+        while rest:
+            hc, members, rows = rest[0][0], [rest[0][1]], rest[0][0]
+            k = 1
+            while k < len(rest) and len(members) < max_batch and (len(members) + 1) * hc - (rows + rest[k][0]) <= waste * (len(members) + 1) * hc:
+                members.append(rest[k][1])
+                rows += rest[k][0]
+                k += 1
+            rest = rest[k:]
+            if len(members) > 1:
+                batches.append(((hc, w), members))
+            else:
+                alone.append(members[0])
+    return batches, alone
 
 
 RPN_PARAM_NAMES = ("RPN_PRE_NMS_TOP_N", "RPN_POST_NMS_TOP_N", "RPN_NMS_THRESH", "RPN_MIN_SIZE")
@@ -407,7 +445,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host"):
+        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
@@ -418,7 +456,10 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     crops_dir (needs decode='gpu'): every detected line also as a rectified crop of height crop_h, <stem>_<k>.jpg in that directory, cut out
     on the device at collect time (write_crops); None (default): nothing changes.
     params: {name: value} of the detection tail (ctpn_set_param: RPN_* and the connector's names) for the ctx of this run; the connector's
-    also reach the images that take the single-image path. None: the defaults."""
+    also reach the images that take the single-image path. None: the defaults.
+    ragged (host decode on the thread pool only; off by default): images of one resized width and different heights share batches
+    (plan_ragged_batches with ragged_waste; Context.detect_submit(..., heights=)) instead of one batch per resized shape. Same result
+    files. The device JPEG path decodes one size per call and stays size-grouped, as do its PNG batches and the process-pool decoder."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config(params)
     if params:
@@ -439,6 +480,8 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         raise ValueError("png_encode='gpu' writes the images of library-decoded batches: it needs decode='gpu'")
     if crops_dir is not None and decode != "gpu":
         raise ValueError("crops_dir cuts the lines out of the batches of the device path: it needs decode='gpu'")
+    if ragged and (decode == "gpu" or decode_procs > 0 or decode_pool is not None):
+        raise ValueError("ragged batches are built from resized images held on the host: decode='host' on the thread pool")
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
@@ -448,7 +491,11 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
-    jobs, singles, _ = plan(names, batch)
+    jobs, singles, shapes = plan(names, batch)
+    if ragged:      # the same images, re-batched across heights; what ends alone stays a uniform batch of one
+        pooled = [nm for _, members in jobs for nm in members]
+        batches, alone = plan_ragged_batches([shapes[nm] for nm in pooled], batch, ragged_waste)
+        jobs = [(shape, [pooled[i] for i in members]) for shape, members in batches] + [(shapes[pooled[i]], [pooled[i]]) for i in alone]
     if jobs:      # one ctx for the whole run: largest batch x largest shape
         net.ensure_capacity(max(len(m) for _, m in jobs), max(s[0] for s, _ in jobs), max(s[1] for s, _ in jobs))
         _set_tail_params(net, params)
@@ -470,9 +517,13 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
             loaded = [f.result() for f in ahead]
             ahead = decode(jobs[k + 1][1]) if k + 1 < len(jobs) else []      # next batch decodes while this one is on the GPU
             for nm, (img, scale) in zip(members, loaded):
-                assert img.shape[:2] == tuple(shape), (nm, img.shape, shape)
+                assert img.shape[:2] == tuple(shapes[nm]) and img.shape[0] <= shape[0] and img.shape[1] == shape[1], (nm, img.shape, shape)
                 meta[nm] = (img, scale)
-            net.ctx.detect_submit(images=np.stack([img for img, _ in loaded]), slot=k & 1)
+            if all(img.shape[0] == shape[0] for img, _ in loaded):
+                net.ctx.detect_submit(images=np.stack([img for img, _ in loaded]), slot=k & 1)
+            else:
+                canvas, heights = im_list_to_canvas([img for img, _ in loaded])
+                net.ctx.detect_submit(images=canvas, heights=heights, slot=k & 1)
             if pending is not None:
                 collect(pending)
             pending = (k & 1, members)
@@ -592,6 +643,9 @@ def build_parser():
     ap.add_argument('--crops', default=None, metavar='DIR',
                     help="(with --decode gpu) also write every detected line as a rectified crop <stem>_<k>.jpg of height --crop-height into DIR (ctpn_crop_lines)")
     ap.add_argument('--crop-height', type=int, default=32)
+    ap.add_argument('--ragged', action='store_true',
+                    help="batch images of one resized width across heights (host decode only; same result files)")
+    ap.add_argument('--ragged-waste', type=float, default=RAGGED_WASTE, help="padded share of a ragged batch's rows at most")
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
                          "throughput choice (3.2 x split's rate, outside the 1e-3 / 1 px bar)")
@@ -622,7 +676,7 @@ def main(argv=None):
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
         decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height,
-        params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)))
+        params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)), ragged=args.ragged, ragged_waste=args.ragged_waste)
     net.close()
 
 

@@ -12,10 +12,8 @@
 #define __host__
 #define __device__
 #define __forceinline__ inline
-#define JHE_ATOMIC_OR(p, v) (*(p) |= (v))
 #include "../text-detection-ctpn_amd/csrc/jpeg_huff_enc_dev.h"
 
-#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -45,20 +43,17 @@ static int run_group(const std::vector<Case>& cases, const JheTables& T, bool zi
   std::vector<JheImg> imgs(m);
   std::vector<JheRes> res(m);
   std::memset(res.data(), 0, m * sizeof(JheRes));
-  uint32_t blk = 0, words = 0, chunks = 0, outb = 0;
   long long elems = 0;
-  for (size_t k = 0; k < m; ++k) {      // enc_huff_group (api_output.hip)
+  for (size_t k = 0; k < m; ++k) {      // enc_huff_group (api_jpeg_out.hip)
     const Case& c = cases[k];
     JheImg& I = imgs[k];
-    I.coef_off = elems; I.mcux = (uint32_t)((c.w + 8 * c.hs - 1) / (8 * c.hs)); I.nmcu = I.mcux * (uint32_t)((c.h + 8 * c.vs - 1) / (8 * c.vs));
-    I.hs = (uint32_t)c.hs; I.vs = (uint32_t)c.vs; I.nblk = I.nmcu * (uint32_t)(c.hs * c.vs + 2); I.blk0 = blk;
-    I.word0 = words; I.nwords = I.nblk * (JHE_BLOCK_BYTES / 4);
-    I.chunk0 = chunks; I.nchunk = (I.nblk * JHE_BLOCK_BYTES + JHE_CHUNK - 1) / JHE_CHUNK;
-    I.out0 = outb; I.out_cap = I.nblk * 2 * JHE_BLOCK_BYTES;
-    blk += I.nblk; words += I.nwords; chunks += I.nchunk; outb += I.out_cap;
+    jhe_describe(I, c.h, c.w, c.hs, c.vs);
+    I.coef_off = elems;
     if (c.coef.size() != (size_t)I.nblk * 64) { std::printf("FAIL case %zu: %zu coefficients for %u blocks\n", k, c.coef.size(), I.nblk); return (int)m; }
     elems += (long long)I.nblk * 64;
   }
+  JheTotals t;
+  jhe_layout(imgs.data(), m, t);
   // the batch's coefficients in a block of exactly their size, 16-byte aligned like the library's (a block is then 128-byte aligned)
   std::vector<int16_t> coef((size_t)elems);
   for (size_t k = 0; k < m; ++k) {
@@ -67,8 +62,8 @@ static int run_group(const std::vector<Case>& cases, const JheTables& T, bool zi
     for (size_t b = 0; b < (size_t)imgs[k].nblk; ++b)
       for (int q = 0; q < 64; ++q) dst[b * 64 + q] = zigzag ? src[b * 64 + T.nat[q]] : src[b * 64 + q];
   }
-  std::vector<uint32_t> len(blk), cnt(chunks), uns(words, 0u);
-  std::vector<uint8_t> out(outb);
+  std::vector<uint32_t> len(t.blk), cnt(t.chunks), uns(t.words, 0u);
+  std::vector<uint8_t> out(t.outb);
   auto threads = [](uint32_t n) { return (n + 255u) / 256u * 256u; };
   for (size_t k = 0; k < m; ++k)      // jhe_length_kernel
     for (uint32_t s = 0; s < threads(imgs[k].nblk); ++s) {
@@ -78,7 +73,7 @@ static int run_group(const std::vector<Case>& cases, const JheTables& T, bool zi
   for (size_t k = 0; k < m; ++k) {      // jhe_scan_kernel<false>
     uint32_t carry = 0;
     for (uint32_t s = 0; s < imgs[k].nblk; ++s) { const uint32_t v = len[imgs[k].blk0 + s]; len[imgs[k].blk0 + s] = carry; carry += v; }
-    res[k].bits = carry;
+    jhe_scan_finish<false>(imgs[k], 0u, carry, res[k]);
   }
   for (size_t k = 0; k < m; ++k)      // jhe_write_kernel
     for (uint32_t i = 0; i < threads(imgs[k].nblk); ++i) {
@@ -89,12 +84,10 @@ static int run_group(const std::vector<Case>& cases, const JheTables& T, bool zi
   for (size_t k = 0; k < m; ++k)      // jhe_count_kernel
     for (uint32_t q = 0; q < threads(imgs[k].nchunk); ++q) jhe_count_thread(imgs[k], q, res[k].bits, uns.data(), cnt.data());
   for (size_t k = 0; k < m; ++k) {      // jhe_scan_kernel<true>
-    const uint32_t nbytes = jhe_unstuffed_bytes(res[k].bits);
-    const uint32_t count = std::min((nbytes + JHE_CHUNK - 1) / JHE_CHUNK, imgs[k].nchunk);
+    const uint32_t count = jhe_chunk_count(res[k].bits, imgs[k]);
     uint32_t carry = 0;
     for (uint32_t q = 0; q < count; ++q) { const uint32_t v = cnt[imgs[k].chunk0 + q]; cnt[imgs[k].chunk0 + q] = carry; carry += v; }
-    res[k].bytes = nbytes + carry;
-    if (nbytes > imgs[k].nwords * 4u || nbytes + carry > imgs[k].out_cap) res[k].flag |= JHE_FLAG_SIZE;
+    jhe_scan_finish<true>(imgs[k], res[k].bits, carry, res[k]);
   }
   for (size_t k = 0; k < m; ++k)      // jhe_stuff_kernel
     for (uint32_t q = 0; q < threads(imgs[k].nchunk); ++q) jhe_stuff_thread(imgs[k], q, res[k].bits, uns.data(), cnt.data(), out.data(), &res[k].flag);

@@ -89,18 +89,16 @@ static bool run_batch(const std::vector<Case>& cases, bool descending, std::vect
   std::vector<PngeRes> res(m);
   std::vector<PngeCodes> codes(m);
   std::memset(res.data(), 0, m * sizeof(PngeRes));
-  uint64_t pix = 0, words = 0;
-  uint32_t pieces = 0;
   for (size_t k = 0; k < m; ++k) {      // png_code (api_png_out.hip), with images of any size
     pnge_describe(imgs[k], cases[k].h, cases[k].w);
     if (cases[k].flags & 1) imgs[k].far_ok = 0;
-    imgs[k].pix_off = pix; imgs[k].piece0 = pieces; imgs[k].word0 = words; imgs[k].nwords = pnge_words(imgs[k]);
-    pix += cases[k].px.size(); pieces += imgs[k].npieces; words += imgs[k].nwords;
   }
-  std::vector<uint8_t> px((size_t)pix);      // the batch's pixels in a block of exactly their size
+  PngeTotals t;
+  pnge_layout(imgs.data(), m, t);
+  std::vector<uint8_t> px((size_t)t.pix);      // the batch's pixels in a block of exactly their size
   for (size_t k = 0; k < m; ++k) std::memcpy(px.data() + imgs[k].pix_off, cases[k].px.data(), cases[k].px.size());
-  std::vector<uint32_t> hist(m * PNGE_NSYM, 0u), wd((size_t)words, 0u);
-  std::vector<PngeLen> len(pieces);
+  std::vector<uint32_t> hist(m * PNGE_NSYM, 0u), wd((size_t)t.words, 0u);
+  std::vector<PngeLen> len((size_t)t.pieces);
   auto threads = [](uint32_t n) { return (n + 255u) / 256u * 256u; };
   for (size_t k = 0; k < m; ++k) {      // pnge_hist_kernel: a workgroup's counters, then the image's
     for (uint32_t g = 0; g < threads(imgs[k].npieces); g += 256) {
@@ -120,8 +118,7 @@ static bool run_batch(const std::vector<Case>& cases, bool descending, std::vect
       pnge_adler_term(imgs[k].n, pnge_piece_end(imgs[k], s), r.a, r.b, sa, ss);
       const uint32_t v = r.bits; r.bits = carry; carry += v;
     }
-    res[k].bits = carry; res[k].bytes = (carry + 7u) / 8u; res[k].adler = pnge_adler_final(imgs[k].n, sa, ss);
-    if ((uint64_t)res[k].bytes > imgs[k].nwords * 4u) res[k].flag |= PNGE_FLAG_SIZE;
+    pnge_scan_finish(imgs[k], carry, sa, ss, res[k]);
   }
   for (size_t k = 0; k < m; ++k)      // pnge_write_kernel
     for (uint32_t i = 0; i < threads(imgs[k].npieces); ++i) {

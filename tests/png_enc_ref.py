@@ -126,6 +126,8 @@ def images():
     s["2x10923"] = np.repeat(few(1, 10923), 2, axis=0)                    # stride 32770: distance 1 only, S = the dummy
     s.update(_demo_crops())
     s["page-300x450"] = document_page()
+    for h in (1023, 1024, 1025):                                          # one piece per row: the scan kernel's step of 1024 pieces, one off either side
+        s["scan-%dx85" % h] = few(h, 85)
     return s
 
 

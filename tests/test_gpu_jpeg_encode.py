@@ -1,4 +1,4 @@
-"""GPU: the JPEG writer behind the C ABI (csrc/jpeg_enc.hip, api_output.hip) against Pillow's files, byte for byte: ctpn_encode_jpeg_batch on
+"""GPU: the JPEG writer behind the C ABI (csrc/jpeg_enc.hip, api_jpeg_out.hip, api_out_stage.hip) against Pillow's files, byte for byte: ctpn_encode_jpeg_batch on
 host and device pixels, draw_boxes_kernel against ctpn_draw_boxes through ctpn_write_annotated_files, demo_batch's encode='gpu' against its
 default writer, batches in flight, buffer growth. (The arithmetic itself is pinned on the CPU from the kernels' source text:
 tests/test_jpeg_encode.py.)"""

@@ -1,6 +1,6 @@
 // C ABI of libctpn_hip.so, crop unit: the detected text lines of a batch cut out of its images ON THE DEVICE, one rectified image of fixed
 // height per line -- what a recogniser behind the detector reads (kernel and descriptor: crop.hip, arithmetic: crop_pixel.h). An output
-// stage in the ctx's copy queue like the annotated writer (api_output.hip): behind the decode that produced the batch, in front of the next.
+// stage in the ctx's copy queue like the annotated writer (api_out_stage.hip): behind the decode that produced the batch, in front of the next.
 #include <climits>
 #include <cmath>
 
@@ -84,16 +84,8 @@ int ctpn_crop_lines(ctpn_ctx* c, const uint8_t* images, int images_on_device, in
     for (int j = 0; j < line_counts[i]; ++j, ++k)
       crop_fill_desc(recs + ((size_t)i * line_capacity + j) * 9, i, widths[k], (size_t)k * line_bytes, (char*)K.desc_host + (size_t)k * CROP_DESC_BYTES);
   CTPN_HIP_TRY(hipMemcpyAsync(K.desc_dev, K.desc_host, (size_t)total * CROP_DESC_BYTES, hipMemcpyHostToDevice, qs));
-  const uint8_t* px = images;
-  if (!images_on_device) {
-    const size_t bytes = (size_t)n * h * w * 3;
-    if ((rc = grow_dev((void**)&K.img_dev, K.img_bytes, bytes))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(K.img_dev, images, bytes, hipMemcpyHostToDevice, qs));
-    px = K.img_dev;
-  } else {
-    // a live batch of ctpn_decode_jpeg_batch was produced in this queue; it is only read here (a forward may read it at the same time)
-    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
-  }
+  const uint8_t* px;
+  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 0, K.img_dev, K.img_bytes, qs, px))) return rc;
   uint8_t* out = crops_out;
   if (!crops_on_device) {
     if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, need))) return rc;

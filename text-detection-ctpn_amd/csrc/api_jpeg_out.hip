@@ -1,5 +1,5 @@
-// C ABI of libctpn_hip.so, output unit: JPEG writing (kernels and the entropy coder: jpeg_enc.hip) and the annotated result images of
-// ctpn/demo.py:28-52 -- outlines (draw_boxes_kernel), cv2.resize by 1 / scale (preprocess.hip), cv2.imwrite -- for a batch on the device.
+// C ABI of libctpn_hip.so, JPEG output unit: JPEG writing (kernels and the entropy coder: jpeg_enc.hip) of a batch on the device, and
+// the cv2.imwrite end of the annotated result images of ctpn/demo.py:28-52 (outlines and resize: api_out_stage.hip).
 // Two entropy forms behind one enc_enqueue / enc_finish: host (the default entry points) and device (the *_device entry points: jpeg_huff_enc.hip).
 #include "ctx.h"
 #include "jpeg_enc_pixel.h"
@@ -64,10 +64,7 @@ static void enc_deliver(size_t bound, uint8_t* out, size_t capacity, size_t* byt
       if (filebuf.size() < bound) filebuf.resize(bound);
       st = code(filebuf.data(), filebuf.size(), &bytes);
       if (st) { msg = ctpn_last_error(); return; }
-      std::FILE* f = std::fopen(path, "wb");
-      if (!f) { st = CTPN_ERR_ARG; msg = std::string("cannot open ") + path; return; }
-      const bool ok = std::fwrite(filebuf.data(), 1, bytes, f) == bytes;
-      if (std::fclose(f) != 0 || !ok) { st = CTPN_ERR_ARG; msg = std::string("write failed: ") + path; }
+      write_file(path, filebuf.data(), bytes, st, msg);
       if (filebuf.capacity() > ((size_t)64 << 20)) std::vector<uint8_t>().swap(filebuf);
     } else {
       st = code(out, capacity, &bytes);
@@ -80,15 +77,13 @@ static void enc_deliver(size_t bound, uint8_t* out, size_t capacity, size_t* byt
 // ---- the device-entropy form ---------------------------------------------------------------------------------------------------------
 struct EncJob {                       // one image of a device-entropy call
   int h, w, hs, vs; const uint16_t* qt;      // the file's frame
-  long long coef_off;                 // its coefficients in E.coef_dev, int16 elements
-  const int16_t* coef_host;           // the same on the host in natural order (the test seam), or null: zig-zag, copied from the device if the host half needs them
+  JheImg img;                         // ... described (jhe_describe); coef_off: its coefficients in E.coef_dev, int16 elements
+  const int16_t* coef_host;          // the same on the host in natural order (the test seam), or null: zig-zag, copied from the device if the host half needs them
   uint8_t* out; size_t capacity; size_t* bytes_out; const char* path;
   bool on_host = false;               // the host half codes it
   const uint8_t* scan = nullptr; size_t scan_have = 0, scan_bytes = 0;      // else: the stuffed scan body (page-locked), the bytes of it that were copied, its size
   int st = CTPN_OK; std::string msg;
-  uint32_t mcux() const { return (uint32_t)((w + 8 * hs - 1) / (8 * hs)); }
-  uint32_t mcus() const { return mcux() * (uint32_t)((h + 8 * vs - 1) / (8 * vs)); }
-  uint64_t blocks() const { return (uint64_t)mcus() * (uint32_t)(hs * vs + 2); }
+  void describe(long long coef_off) { jhe_describe(img, h, w, hs, vs); img.coef_off = coef_off; }
 };
 
 // one launch group (at most JHE_MAX_BLOCKS blocks): the kernels, then the result words -- the wait of the host form on its coefficients --,
@@ -102,20 +97,11 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
   if ((rc = grow_host(&E.huff_host, E.huff_host_bytes, m * (sizeof(JheImg) + sizeof(JheRes))))) return rc;
   JheImg* imgs = (JheImg*)E.huff_host;
   JheRes* res = (JheRes*)(E.huff_host + m * sizeof(JheImg));
-  uint32_t blk = 0, words = 0, chunks = 0, outb = 0, max_blocks = 0, max_chunks = 0;
-  for (size_t k = 0; k < m; ++k) {
-    const EncJob& J = jobs[use[k]];
-    JheImg& I = imgs[k];
-    I.coef_off = J.coef_off; I.mcux = J.mcux(); I.nmcu = J.mcus(); I.hs = (uint32_t)J.hs; I.vs = (uint32_t)J.vs;
-    I.nblk = (uint32_t)J.blocks(); I.blk0 = blk;
-    I.word0 = words; I.nwords = I.nblk * (JHE_BLOCK_BYTES / 4);
-    I.chunk0 = chunks; I.nchunk = (I.nblk * JHE_BLOCK_BYTES + JHE_CHUNK - 1) / JHE_CHUNK;
-    I.out0 = outb; I.out_cap = I.nblk * 2 * JHE_BLOCK_BYTES;
-    blk += I.nblk; words += I.nwords; chunks += I.nchunk; outb += I.out_cap;
-    max_blocks = std::max(max_blocks, I.nblk); max_chunks = std::max(max_chunks, I.nchunk);
-  }
-  const size_t o_img = 0, o_res = up(o_img + m * sizeof(JheImg)), o_len = up(o_res + m * sizeof(JheRes)), o_cnt = up(o_len + (size_t)blk * 4),
-               o_uns = up(o_cnt + (size_t)chunks * 4), o_out = up(o_uns + (size_t)words * 4), total = o_out + outb;
+  for (size_t k = 0; k < m; ++k) imgs[k] = jobs[use[k]].img;
+  JheTotals t;
+  jhe_layout(imgs, m, t);
+  const size_t o_img = 0, o_res = up(o_img + m * sizeof(JheImg)), o_len = up(o_res + m * sizeof(JheRes)), o_cnt = up(o_len + (size_t)t.blk * 4),
+               o_uns = up(o_cnt + (size_t)t.chunks * 4), o_out = up(o_uns + (size_t)t.words * 4), total = o_out + t.outb;
   if ((rc = grow_dev((void**)&E.huff_dev, E.huff_bytes, total))) return rc;
   if (!E.huff_tab_dev) {
     static const JheTables T = [] { JheTables t; jhe_build_tables(t); return t; }();
@@ -125,10 +111,10 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
   JheBatchDev B;
   B.imgs = (const JheImg*)(E.huff_dev + o_img); B.res = (JheRes*)(E.huff_dev + o_res); B.len = (uint32_t*)(E.huff_dev + o_len); B.cnt = (uint32_t*)(E.huff_dev + o_cnt);
   B.uns = (uint32_t*)(E.huff_dev + o_uns); B.out = E.huff_dev + o_out; B.coef = E.coef_dev; B.tables = (const JheTables*)E.huff_tab_dev;
-  B.n = (int)m; B.max_blocks = max_blocks; B.max_chunks = max_chunks;
+  B.n = (int)m; B.max_blocks = t.max_blocks; B.max_chunks = t.max_chunks;
   CTPN_HIP_TRY(hipMemcpyAsync(E.huff_dev + o_img, imgs, m * sizeof(JheImg), hipMemcpyHostToDevice, qs));
   CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_res, 0, m * sizeof(JheRes), qs));
-  CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_uns, 0, (size_t)words * 4, qs));      // the write pass ORs shared words into it
+  CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_uns, 0, (size_t)t.words * 4, qs));      // the write pass ORs shared words into it
   if ((rc = launch_jpeg_huff_enc(B, zigzag, qs))) return rc;
   CTPN_HIP_TRY(hipMemcpyAsync(res, E.huff_dev + o_res, m * sizeof(JheRes), hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(E.ev_done, qs));
@@ -151,7 +137,7 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
       ++c->jhe_stats[1];
       if (J.coef_host) continue;
       const size_t bytes = (size_t)imgs[k].nblk * 64 * sizeof(int16_t);
-      CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + J.coef_off, E.coef_dev + J.coef_off, bytes, hipMemcpyDeviceToHost, qs));
+      CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + J.img.coef_off, E.coef_dev + J.img.coef_off, bytes, hipMemcpyDeviceToHost, qs));
       c->jhe_stats[3] += (long long)bytes; copies = true;
       continue;
     }
@@ -182,11 +168,11 @@ static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
     uint64_t tot = 0;
     int i1 = i0;
     for (; i1 < n; ++i1) {
-      const uint64_t nb = jobs[i1].blocks();
+      const uint64_t nb = jobs[i1].img.nblk;      // (below 2^28 at 65535 x 65535)
       if (nb > (uint64_t)JHE_MAX_BLOCKS) {      // offsets of 32 bits do not hold it: the host half's
         jobs[i1].on_host = true; ++c->jhe_stats[1];
         if (!jobs[i1].coef_host) {
-          CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + jobs[i1].coef_off, E.coef_dev + jobs[i1].coef_off, (size_t)nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
+          CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + jobs[i1].img.coef_off, E.coef_dev + jobs[i1].img.coef_off, (size_t)nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
           CTPN_HIP_TRY(hipEventRecord(E.ev_done, c->stream_c));
           CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
           c->jhe_stats[3] += (long long)((size_t)nb * 64 * sizeof(int16_t));
@@ -202,7 +188,7 @@ static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
       EncJob& J = jobs[(size_t)i0 + k];
       const size_t bound = J.on_host ? jpeg_encode_capacity(J.h, J.w) : J.scan_bytes + 1024;
       if (J.on_host) {
-        const int16_t* coef = J.coef_host ? J.coef_host : E.coef_host + J.coef_off;
+        const int16_t* coef = J.coef_host ? J.coef_host : E.coef_host + J.img.coef_off;
         const bool zz = !J.coef_host;
         enc_deliver(bound, J.out, J.capacity, J.bytes_out, J.path, J.st, J.msg, [&](uint8_t* buf, size_t cap, size_t* bytes) {
           return jpeg_entropy_encode(coef, zz, J.h, J.w, J.hs, J.vs, J.qt, buf, cap, bytes); });
@@ -229,7 +215,7 @@ static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, in
     std::vector<EncJob> jobs((size_t)n);
     for (int i = 0; i < n; ++i) {
       EncJob& J = jobs[i];
-      J.h = g.h; J.w = g.w; J.hs = 2; J.vs = 2; J.qt = qt; J.coef_off = (long long)i * g.coef_per_img; J.coef_host = nullptr;
+      J.h = g.h; J.w = g.w; J.hs = 2; J.vs = 2; J.qt = qt; J.describe((long long)i * g.coef_per_img); J.coef_host = nullptr;
       J.out = paths ? nullptr : out[i]; J.capacity = paths ? 0 : capacities[i]; J.bytes_out = paths ? nullptr : bytes_out + i; J.path = paths ? paths[i] : nullptr;
     }
     const int rc = enc_huff(c, jobs, true);
@@ -244,8 +230,7 @@ static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, in
                   [&](uint8_t* buf, size_t cap, size_t* bytes) { return jpeg_entropy_encode(coef, true, g.h, g.w, 2, 2, qt, buf, cap, bytes); });
     });
   }
-  for (int i = 0; i < n; ++i) if (st[i]) return fail(st[i], std::string(who) + ": image " + std::to_string(i) + ": " + msg[i]);
-  return CTPN_OK;
+  return first_failure(who, st, msg);
 }
 
 // size and sampling out of the eight layout ints ctpn_jpeg_entropy_decode returns
@@ -270,17 +255,9 @@ static int encode_batch_impl(ctpn_ctx* c, const char* who_, const uint8_t* image
   for (int i = 0; i < n; ++i) if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, who + ": null output pointer");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
-  auto& E = c->enc;
-  const uint8_t* px = images;
+  const uint8_t* px;
   int rc;
-  if (!images_on_device) {
-    const size_t bytes = (size_t)n * h * w * 3;
-    if ((rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyHostToDevice, c->stream_c));
-    px = E.img_dev;
-  } else {
-    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(c->stream_c, J.ev_ready, 0));
-  }
+  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
   JpegGeom g;
   if ((rc = enc_enqueue(c, px, n, h, w, quality, g, device_entropy))) return rc;
   return enc_finish(c, who_, g, n, quality, out, capacities, bytes_out, nullptr, device_entropy);
@@ -289,43 +266,10 @@ static int encode_batch_impl(ctpn_ctx* c, const char* who_, const uint8_t* image
 // ctpn_write_annotated_files / ctpn_write_annotated_files_device
 static int write_annotated_impl(ctpn_ctx* c, const char* who_, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
                                 double scale, const char* const* paths, int quality, bool device_entropy) {
-  const std::string who(who_);
-  if (!c || !images_dev || !line_counts || !paths) return fail(CTPN_ERR_ARG, who + ": null pointer");
-  if (n <= 0 || h <= 0 || w <= 0 || h > 65535 || w > 65535 || line_capacity < 0 || !(scale > 0.0)) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size / bad scale");
-  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
-  for (int i = 0; i < n; ++i) {
-    if (!paths[i]) return fail(CTPN_ERR_ARG, who + ": null path");
-    if (line_counts[i] < 0 || line_counts[i] > line_capacity || (line_counts[i] > 0 && !recs)) return fail(CTPN_ERR_ARG, who + ": line count out of range");
-  }
-  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
-  // demo.py:51: cv2.resize(img, None, None, fx = 1 / scale, fy = 1 / scale); the identity (scale 1) is a copy there and no launch here
-  const double f = 1.0 / scale;
-  int dh = h, dw = w;
-  if (f != 1.0) { dh = resize_out_dim(h, f); dw = resize_out_dim(w, f); }
-  if (dh <= 0 || dw <= 0 || dh > 65535 || dw > 65535) return fail(CTPN_ERR_ARG, who + ": the resized image is empty or too large for a JPEG file");
-  CTPN_HIP_TRY(hipSetDevice(c->device));
-  auto& E = c->enc;
-  hipStream_t qs = c->stream_c;
-  const size_t bytes = (size_t)n * h * w * 3;
-  int rc;
-  if ((rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
-  if (f != 1.0 && (rc = grow_dev((void**)&E.rs_dev, E.rs_bytes, (size_t)n * dh * dw * 3 + 256))) return rc;
-  const size_t rbytes = std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64);
-  if ((rc = grow_dev((void**)&E.recs_dev, E.recs_bytes, rbytes))) return rc;
-  size_t cnt_bytes = E.cnt_n * sizeof(int);
-  if ((rc = grow_dev((void**)&E.cnt_dev, cnt_bytes, (size_t)n * sizeof(int)))) return rc;
-  E.cnt_n = cnt_bytes / sizeof(int);
-  // a live batch of ctpn_decode_jpeg_batch was produced in this queue; its buffer is not drawn on (a forward may still read it): a copy is
-  for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images_dev) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
-  CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images_dev, bytes, hipMemcpyDeviceToDevice, qs));
-  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(E.recs_dev, recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemcpyAsync(E.cnt_dev, line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
-  if ((rc = launch_draw_boxes(E.img_dev, E.recs_dev, E.cnt_dev, line_capacity, n, h, w, qs))) return rc;
-  const uint8_t* px = E.img_dev;
-  if (f != 1.0) {
-    if ((rc = launch_resize_linear(E.img_dev, E.rs_dev, 0, n, h, w, dh, dw, f, f, qs))) return rc;
-    px = E.rs_dev;
-  }
+  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, std::string(who_) + ": quality must be 1 .. 100");
+  const uint8_t* px;
+  int dh, dw, rc;
+  if ((rc = annotate_batch(c, who_, "JPEG", nullptr, images_dev, 1, n, h, w, recs, line_capacity, line_counts, scale, paths, px, dh, dw))) return rc;
   JpegGeom g;
   if ((rc = enc_enqueue(c, px, n, dh, dw, quality, g, device_entropy))) return rc;
   return enc_finish(c, who_, g, n, quality, nullptr, nullptr, nullptr, paths, device_entropy);
@@ -360,9 +304,9 @@ int ctpn_jpeg_entropy_encode_device(ctpn_ctx* c, const int16_t* const* coef, con
     status_out[i] = enc_layout(layout8 + 8 * (size_t)i, J.h, J.w, J.hs, J.vs);
     if (!status_out[i]) status_out[i] = jpeg_enc_check(J.h, J.w, J.hs, J.vs, qt + 192 * (size_t)i);
     if (status_out[i]) continue;
-    J.qt = qt + 192 * (size_t)i; J.coef_off = (long long)elems; J.coef_host = coef[i];
+    J.qt = qt + 192 * (size_t)i; J.describe((long long)elems); J.coef_host = coef[i];
     J.out = out[i]; J.capacity = capacities[i]; J.bytes_out = bytes_out + i; J.path = nullptr;
-    elems += (size_t)J.blocks() * 64;
+    elems += (size_t)J.img.nblk * 64;
     jobs.push_back(J); owner.push_back(i);
   }
   c->jhe_stats[0] = c->jhe_stats[1] = c->jhe_stats[2] = c->jhe_stats[3] = 0;
@@ -370,7 +314,7 @@ int ctpn_jpeg_entropy_encode_device(ctpn_ctx* c, const int16_t* const* coef, con
   int rc = enc_reserve_coef(c, elems);
   if (rc) return rc;
   for (const EncJob& J : jobs)
-    CTPN_HIP_TRY(hipMemcpyAsync(c->enc.coef_dev + J.coef_off, J.coef_host, (size_t)J.blocks() * 64 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream_c));
+    CTPN_HIP_TRY(hipMemcpyAsync(c->enc.coef_dev + J.img.coef_off, J.coef_host, (size_t)J.img.nblk * 64 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream_c));
   if ((rc = enc_huff(c, jobs, false))) return rc;
   for (size_t k = 0; k < jobs.size(); ++k) {
     status_out[owner[k]] = jobs[k].st;

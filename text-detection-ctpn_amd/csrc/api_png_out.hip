@@ -1,5 +1,5 @@
-// C ABI of libctpn_hip.so, PNG output unit: the PNG-named result images of ctpn/demo.py:28-52 -- outlines (draw_boxes_kernel), cv2.resize by
-// 1 / scale (preprocess.hip), cv2.imwrite -- for a batch on the device (kernels: png_enc.hip), and the host form of the same file
+// C ABI of libctpn_hip.so, PNG output unit: PNG writing of a batch on the device (kernels: png_enc.hip) -- the cv2.imwrite end of the
+// PNG-named result images of ctpn/demo.py:28-52 (outlines and resize: api_out_stage.hip) --, and the host form of the same file
 // (png_enc_dev.h: one text for both, so the two forms cannot disagree about a file).
 #include "ctx.h"
 #include "png_enc_dev.h"
@@ -9,10 +9,7 @@ namespace ctpn {
 // a finished file to the caller's buffer or to a file of its own. Runs on a worker thread: nothing may leave it
 static void png_deliver(const uint8_t* file, size_t bytes, uint8_t* out, size_t capacity, size_t* bytes_out, const char* path, int& st, std::string& msg) {
   if (path) {
-    std::FILE* f = std::fopen(path, "wb");
-    if (!f) { st = CTPN_ERR_ARG; msg = std::string("cannot open ") + path; return; }
-    const bool ok = std::fwrite(file, 1, bytes, f) == bytes;
-    if (std::fclose(f) != 0 || !ok) { st = CTPN_ERR_ARG; msg = std::string("write failed: ") + path; }
+    write_file(path, file, bytes, st, msg);
   } else {
     *bytes_out = bytes;
     if (bytes > capacity) { st = CTPN_ERR_CAPACITY; msg = "the file needs " + std::to_string(bytes) + " bytes, the buffer holds " + std::to_string(capacity); return; }
@@ -21,7 +18,9 @@ static void png_deliver(const uint8_t* file, size_t bytes, uint8_t* out, size_t 
 }
 
 static bool png_size_ok(int h, int w) { return h > 0 && w > 0 && h <= 65535 && w <= 65535; }
-static bool png_device_size_ok(int h, int w) { return (uint64_t)h * (1u + 3u * (uint64_t)w) <= PNGE_MAX_STREAM; }
+static int png_device_size_check(const std::string& who, int h, int w) {      // the device form's bound on an image
+  return (uint64_t)h * (1u + 3u * (uint64_t)w) <= PNGE_MAX_STREAM ? CTPN_OK : fail(CTPN_ERR_ARG, who + ": h (1 + 3 w) above 2^27: ctpn_png_encode takes such images");
+}
 
 // n images of h x w x 3 at px (device, complete in the ctx's copy queue) -> n files, in the caller's buffers (out) or in files (paths)
 static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int h, int w, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths) {
@@ -44,10 +43,9 @@ static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int 
   uint32_t* hist = (uint32_t*)(P.host + o_hist);
   PngeRes* res = (PngeRes*)(P.host + o_res);
   PngeCodes* codes = (PngeCodes*)(P.host + o_codes);
-  for (int i = 0; i < n; ++i) {
-    imgs[i] = d0;
-    imgs[i].pix_off = (uint64_t)i * per_px; imgs[i].piece0 = (uint32_t)i * d0.npieces; imgs[i].word0 = (uint64_t)i * nw; imgs[i].nwords = nw;
-  }
+  for (int i = 0; i < n; ++i) imgs[i] = d0;
+  PngeTotals t;
+  pnge_layout(imgs, (size_t)n, t);      // (one size: image i's parts are the i-th of n equal ones)
   // histograms -> the host, which builds every image's code and block header; one copy brings them back
   CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_img, imgs, (size_t)n * sizeof(PngeImg), hipMemcpyHostToDevice, qs));
   CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_hist, 0, (size_t)n * (PNGE_NSYM * 4 + sizeof(PngeRes)), qs));      // counters and result records
@@ -114,8 +112,7 @@ static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int 
       }
     } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }
   });
-  for (int i = 0; i < n; ++i) if (st[i]) return fail(st[i], std::string(who) + ": image " + std::to_string(i) + ": " + msg[i]);
-  return CTPN_OK;
+  return first_failure(who, st, msg);
 }
 
 }  // namespace ctpn
@@ -138,67 +135,21 @@ int ctpn_encode_png_batch(ctpn_ctx* c, const uint8_t* images, int images_on_devi
   const std::string who("ctpn_encode_png_batch");
   if (!c || !images || !out || !capacities || !bytes_out) return fail(CTPN_ERR_ARG, who + ": null pointer");
   if (n <= 0 || !png_size_ok(h, w)) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size");
-  if (!png_device_size_ok(h, w)) return fail(CTPN_ERR_ARG, who + ": h (1 + 3 w) above 2^27: ctpn_png_encode takes such images");
+  int rc;
+  if ((rc = png_device_size_check(who, h, w))) return rc;
   for (int i = 0; i < n; ++i) if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, who + ": null output pointer");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
-  auto& E = c->enc;
-  const uint8_t* px = images;
-  if (!images_on_device) {
-    const size_t bytes = (size_t)n * h * w * 3;
-    const int rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256);
-    if (rc) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyHostToDevice, c->stream_c));
-    px = E.img_dev;
-  } else {
-    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(c->stream_c, J.ev_ready, 0));
-  }
+  const uint8_t* px;
+  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
   return png_code(c, "ctpn_encode_png_batch", px, n, h, w, out, capacities, bytes_out, nullptr);
 }
 
 int ctpn_write_annotated_png_files(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
                                    const int* line_counts, double scale, const char* const* paths) {
-  const std::string who("ctpn_write_annotated_png_files");
-  if (!c || !images || !line_counts || !paths) return fail(CTPN_ERR_ARG, who + ": null pointer");
-  if (n <= 0 || !png_size_ok(h, w) || line_capacity < 0 || !(scale > 0.0)) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size / bad scale");
-  for (int i = 0; i < n; ++i) {
-    if (!paths[i]) return fail(CTPN_ERR_ARG, who + ": null path");
-    if (line_counts[i] < 0 || line_counts[i] > line_capacity || (line_counts[i] > 0 && !recs)) return fail(CTPN_ERR_ARG, who + ": line count out of range");
-  }
-  // demo.py:51: cv2.resize(img, None, None, fx = 1 / scale, fy = 1 / scale); the identity (scale 1) is a copy there and no launch here
-  const double f = 1.0 / scale;
-  int dh = h, dw = w;
-  if (f != 1.0) { dh = resize_out_dim(h, f); dw = resize_out_dim(w, f); }
-  if (!png_size_ok(dh, dw)) return fail(CTPN_ERR_ARG, who + ": the resized image is empty or too large for a PNG file");
-  if (!png_device_size_ok(h, w) || !png_device_size_ok(dh, dw)) return fail(CTPN_ERR_ARG, who + ": h (1 + 3 w) above 2^27: ctpn_png_encode takes such images");
-  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
-  CTPN_HIP_TRY(hipSetDevice(c->device));
-  auto& E = c->enc;
-  hipStream_t qs = c->stream_c;
-  const size_t bytes = (size_t)n * h * w * 3;
-  int rc;
-  if ((rc = grow_dev((void**)&E.img_dev, E.img_bytes, bytes + 256))) return rc;
-  if (f != 1.0 && (rc = grow_dev((void**)&E.rs_dev, E.rs_bytes, (size_t)n * dh * dw * 3 + 256))) return rc;
-  const size_t rbytes = std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64);
-  if ((rc = grow_dev((void**)&E.recs_dev, E.recs_bytes, rbytes))) return rc;
-  size_t cnt_bytes = E.cnt_n * sizeof(int);
-  if ((rc = grow_dev((void**)&E.cnt_dev, cnt_bytes, (size_t)n * sizeof(int)))) return rc;
-  E.cnt_n = cnt_bytes / sizeof(int);
-  // the outlines go onto a copy owned by the ctx: a live batch of ctpn_decode_jpeg_batch (produced in this queue) may still feed a forward
-  if (images_on_device) {
-    for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
-    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyDeviceToDevice, qs));
-  } else {
-    CTPN_HIP_TRY(hipMemcpyAsync(E.img_dev, images, bytes, hipMemcpyHostToDevice, qs));
-  }
-  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(E.recs_dev, recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemcpyAsync(E.cnt_dev, line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
-  if ((rc = launch_draw_boxes(E.img_dev, E.recs_dev, E.cnt_dev, line_capacity, n, h, w, qs))) return rc;
-  const uint8_t* px = E.img_dev;
-  if (f != 1.0) {
-    if ((rc = launch_resize_linear(E.img_dev, E.rs_dev, 0, n, h, w, dh, dw, f, f, qs))) return rc;
-    px = E.rs_dev;
-  }
+  const uint8_t* px;
+  int dh, dw;
+  if (int rc = annotate_batch(c, "ctpn_write_annotated_png_files", "PNG", png_device_size_check, images, images_on_device, n, h, w, recs, line_capacity, line_counts, scale, paths, px, dh, dw)) return rc;
   return png_code(c, "ctpn_write_annotated_png_files", px, n, dh, dw, nullptr, nullptr, nullptr, paths);
 }
 

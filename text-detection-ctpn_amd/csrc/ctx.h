@@ -188,13 +188,16 @@ struct ctpn_ctx {
     uint32_t* res_host = nullptr; size_t res_words = 0;                                      // page-locked: what comes back (2 words per file)
   } jh;
   long long jh_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_device_stats
-  // ctpn_encode_jpeg_batch / ctpn_write_annotated_files (api_output.hip): ONE set of buffers -- both calls return when their files are coded,
-  // so nothing of a call is in flight when the next one starts -- allocated on first use and grown to the largest batch seen
-  struct EncBufs {
+  // the output stage both writers share (api_out_stage.hip): ONE set of buffers -- every writer call returns when its files are coded, so
+  // nothing of a call is in flight when the next one starts -- allocated on first use and grown to the largest batch seen
+  struct StageBufs {
     uint8_t* img_dev = nullptr; size_t img_bytes = 0;          // the batch's pixels: staged host images, or the copy the outlines are drawn on
     uint8_t* rs_dev = nullptr; size_t rs_bytes = 0;            // ... resized by 1 / scale
+    double* recs_dev = nullptr; size_t recs_bytes = 0; int* cnt_dev = nullptr; size_t cnt_bytes = 0;      // the outlines' records and counts
+  } stage;
+  // ctpn_encode_jpeg_batch / ctpn_write_annotated_files (api_jpeg_out.hip): ONE set of buffers, for the reason the stage's set is one
+  struct EncBufs {
     int16_t* coef_dev = nullptr; int16_t* coef_host = nullptr; size_t coef_elems = 0;      // quantised coefficients; the host side is page-locked
-    double* recs_dev = nullptr; size_t recs_bytes = 0; int* cnt_dev = nullptr; size_t cnt_n = 0;
     void* qtab_dev = nullptr; void* qtab_host = nullptr; int qtab_quality = 0;               // JencQ[2][64] of the quality last used
     hipEvent_t ev_done = nullptr;
     // the device-entropy form (jpeg_huff_enc.hip; ctpn_encode_jpeg_batch_device, ...): one device block for a launch group's descriptors,
@@ -205,8 +208,7 @@ struct ctpn_ctx {
     uint8_t* scan_host = nullptr; size_t scan_host_bytes = 0;
   } enc;
   long long jhe_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_encode_device_stats
-  // ctpn_encode_png_batch / ctpn_write_annotated_png_files (api_png_out.hip): ONE set of buffers, for the reason the JPEG writer's set is one,
-  // allocated on first use and grown to the largest call seen. The pixels, the outlines' records and the resized copy use `enc`'s
+  // ctpn_encode_png_batch / ctpn_write_annotated_png_files (api_png_out.hip): ONE set of buffers, for the same reason, grown likewise
   struct PngEncBufs {
     uint8_t* dev = nullptr; size_t dev_bytes = 0;              // descriptors, histograms, codes, result records, per-piece array, DEFLATE words
     uint8_t* host = nullptr; size_t host_bytes = 0;            // page-locked: descriptors, histograms, codes, result records
@@ -369,7 +371,7 @@ static inline bool nms_multi_wg(const ctpn_ctx* c, int n, int hf) {
   return c->nms_mw_scratch && hf * 10 <= 1024 && ((c->nms_columns == 3 && n <= NMS_MW_CAP_BATCH) || (c->nms_columns == 1 && n <= NMS_MW_MAX_BATCH));
 }
 
-// a ctx-owned device buffer that grows to the largest size asked for (the output stages: api_output.hip, api_crops.hip). Their calls return
+// a ctx-owned device buffer that grows to the largest size asked for (the output stages: api_out_stage.hip, the writers, api_crops.hip). Their calls return
 // when their results are complete, so nothing reads the old block any more when one grows
 static inline int grow_dev(void** p, size_t& have, size_t need) {
   if (need <= have) return CTPN_OK;
@@ -430,5 +432,16 @@ int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int 
 // option nms_check behind a column-decomposed NMS launch on s (api_proposals.hip): the generic kernel on the same candidates must give keep1 / cnt1
 int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, const int* counts, int stride, float thresh, int post_topn,
                       const int* keep1, int keep_stride, const int* cnt1, int n, bool mw, hipStream_t s, const char* what);
+// the output stage of the writers and the crops (api_out_stage.hip). stage_pixels: a call's pixels where its kernels on qs may read them --
+// host images copied into buf (ctx-owned, grown to bytes + slack), device images in place, behind a live ctpn_decode_jpeg_batch batch's event
+int stage_pixels(ctpn_ctx* c, const uint8_t* images, int on_device, size_t bytes, size_t slack, uint8_t*& buf, size_t& buf_bytes, hipStream_t qs, const uint8_t*& px);
+// the ctpn_write_annotated_* entry points up to the file format: their argument checks (format: "JPEG" or "PNG", for the message; size_check,
+// nullable: the format's own check of both sizes), then the ctx's copy of the images, outlines drawn, resized by 1 / scale, at px (dh x dw)
+typedef int (*StageSizeCheck)(const std::string& who, int h, int w);
+int annotate_batch(ctpn_ctx* c, const std::string& who, const char* format, StageSizeCheck size_check, const uint8_t* images, int on_device, int n, int h, int w, const double* recs,
+                   int line_capacity, const int* line_counts, double scale, const char* const* paths, const uint8_t*& px, int& dh, int& dw);
+// a finished file onto the disk (on worker threads: nothing may leave it; st, msg: why it failed); the report of a call's first failed image
+void write_file(const char* path, const uint8_t* data, size_t bytes, int& st, std::string& msg);
+int first_failure(const char* who, const std::vector<int>& st, const std::vector<std::string>& msg);
 
 }  // namespace ctpn

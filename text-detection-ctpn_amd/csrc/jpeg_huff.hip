@@ -6,6 +6,7 @@
 // What bounds the kernels: the decode is a chain of dependent LDS lookups and shifts per code with every lane of a wave at its own place in
 // its own loop -- latency- and divergence-bound, not bandwidth-bound; the rate comes from the number of subsequences in flight.
 #include "common.h"
+#include "wg_scan.h"
 
 namespace ctpn {
 
@@ -83,34 +84,22 @@ __global__ __launch_bounds__(JH_WG) void jh_sync_kernel(JhBatchDev B, int round)
   if (round > 0 && !jh_same(x, prev[g])) B.changed[fi] = (uint32_t)round;      // every writer of a round stores the same value
 }
 
-// inclusive scan of one value per thread across the workgroup (wave64 shuffles, then the four wave totals through LDS)
-static __device__ __forceinline__ int jh_block_scan(int v, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d, 64); if (lane >= d) v += t; }
-  __syncthreads();                                      // (the previous call's readers are done with wsum)
-  if (lane == 63) wsum[w] = v;
-  __syncthreads();
-  int add = 0; total = 0;
-#pragma unroll
-  for (int q = 0; q < JH_WG / 64; ++q) { if (q < w) add += wsum[q]; total += wsum[q]; }
-  return v + add;
-}
+static_assert(JH_WG == 256, "wg_scan256 scans a workgroup of 256");
 
 // one workgroup per segment: exclusive scan of the blocks begun per subsequence, JH_WG at a time with a carry; then the segment's checks
 __global__ __launch_bounds__(JH_WG) void jh_scan_kernel(JhBatchDev B, int fin) {
-  __shared__ int wsum[JH_WG / 64];
   const JhSeg seg = B.segs[blockIdx.x];
   if (seg.file >= B.nfiles) return;
   uint32_t carry = 0;
   for (uint32_t base = 0; base < seg.nsub; base += JH_WG) {
     const uint32_t i = base + threadIdx.x;
     const bool in = i < seg.nsub && seg.sub0 + i < B.nsub;
-    const int v = in ? (int)B.begun[seg.sub0 + i] : 0;
-    int total;
-    const int incl = jh_block_scan(v, wsum, total);
-    if (in) B.prefix[seg.sub0 + i] = carry + (uint32_t)(incl - v);
-    carry += (uint32_t)total;
+    const uint32_t v = in ? B.begun[seg.sub0 + i] : 0u;
+    uint32_t total;
+    const uint32_t incl = wg_scan256(v, total);
+    if (in) B.prefix[seg.sub0 + i] = carry + (incl - v);
+    carry += total;
+    __syncthreads();      // wg_scan256's second barrier
   }
   if (threadIdx.x == 0 && seg.nsub > 0 && seg.sub0 + seg.nsub <= B.nsub) {
     const uint64_t need = (uint64_t)seg.nmcu * (uint32_t)B.files[seg.file].bpm;
@@ -146,7 +135,6 @@ __global__ __launch_bounds__(JH_WG) void jh_write_kernel(JhBatchDev B, int fin) 
 // one workgroup per (segment, component): the DC differences of the component's blocks, in scan order, summed in 32 bits and truncated to
 // int16 at the store, as pred[c] is on the host; JH_WG blocks at a time with a carry
 __global__ __launch_bounds__(JH_WG) void jh_dc_kernel(JhBatchDev B) {
-  __shared__ int wsum[JH_WG / 64];
   const JhSeg seg = B.segs[blockIdx.x / 3];
   const int c = blockIdx.x % 3;
   if (seg.file >= B.nfiles) return;
@@ -169,10 +157,11 @@ __global__ __launch_bounds__(JH_WG) void jh_dc_kernel(JhBatchDev B) {
       }
     }
     const int v = blk ? (int)blk[0] : 0;
-    int total;
-    const int incl = jh_block_scan(v, wsum, total);
+    uint32_t total;      // (two's complement: the unsigned scan is exact for the differences)
+    const int incl = (int)wg_scan256((uint32_t)v, total);
     if (blk) blk[0] = (int16_t)(carry + incl);
-    carry += total;
+    carry += (int)total;
+    __syncthreads();      // wg_scan256's second barrier
   }
 }
 

@@ -5,6 +5,7 @@
 // workgroup per image for the two prefix sums; grid y = the image. No workgroup waits on another.
 #include "common.h"
 #include "jpeg_huff_enc_dev.h"
+#include "wg_scan.h"
 
 namespace ctpn {
 
@@ -38,13 +39,11 @@ __global__ __launch_bounds__(256) void jhe_stuff_kernel(const JheImg* __restrict
 // chunks the unstuffed bytes fill -> stuffing offsets, unstuffed bytes + total to res.bytes
 template <bool CHUNKS>
 __global__ __launch_bounds__(256) void jhe_scan_kernel(const JheImg* __restrict__ imgs, uint32_t* __restrict__ items, JheRes* __restrict__ res) {
-  __shared__ uint32_t wsum[4];
   const JheImg im = imgs[blockIdx.x];
-  const uint32_t nbytes = CHUNKS ? jhe_unstuffed_bytes(res[blockIdx.x].bits) : 0u;
-  uint32_t count = im.nblk;
-  if (CHUNKS) { count = (nbytes + JHE_CHUNK - 1) / JHE_CHUNK; count = count < im.nchunk ? count : im.nchunk; }
+  const uint32_t bits = CHUNKS ? res[blockIdx.x].bits : 0u;
+  const uint32_t count = CHUNKS ? jhe_chunk_count(bits, im) : im.nblk;
   uint32_t* it = items + (CHUNKS ? im.chunk0 : im.blk0);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t tid = threadIdx.x;
   const uint32_t steps = (count + JHE_SCAN_ITEMS - 1) / JHE_SCAN_ITEMS;
   uint32_t carry = 0;
   for (uint32_t st = 0; st < steps; ++st) {
@@ -53,34 +52,17 @@ __global__ __launch_bounds__(256) void jhe_scan_kernel(const JheImg* __restrict_
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = base + k < count ? it[base + k] : 0u;
     const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(inc, d, 64);
-      if (lane >= (uint32_t)d) inc += up;
-    }
-    if (lane == 63u) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) { before += k < wave ? wsum[k] : 0u; total += wsum[k]; }
-    uint32_t ex = carry + before + inc - mine;
+    uint32_t total;
+    uint32_t ex = carry + wg_scan256(mine, total) - mine;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (base + k < count) it[base + k] = ex;
       ex += v[k];
     }
     carry += total;
-    __syncthreads();      // wsum is rewritten in the next step
+    __syncthreads();      // wg_scan256's second barrier: the wave totals are rewritten in the next step
   }
-  if (tid == 0) {
-    if (CHUNKS) {
-      res[blockIdx.x].bytes = nbytes + carry;
-      if (nbytes > im.nwords * 4u || nbytes + carry > im.out_cap) atomicOr(&res[blockIdx.x].flag, (uint32_t)JHE_FLAG_SIZE);
-    } else {
-      res[blockIdx.x].bits = carry;
-    }
-  }
+  if (tid == 0) jhe_scan_finish<CHUNKS>(im, bits, carry, res[blockIdx.x]);
 }
 
 // the passes of one launch group in queue s; B: the group's buffers (every part sized by the caller from the images' block counts)

@@ -17,22 +17,16 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "bits_dev.h"
 #include "jpeg_enc_tables.h"
 
-#ifndef JHE_HD
-#define JHE_HD __host__ __device__ __forceinline__
-#endif
-// an OR into a word other threads may OR into at the same time (the host program runs its threads one after the other and defines a plain |=)
-#ifndef JHE_ATOMIC_OR
-#define JHE_ATOMIC_OR(p, v) atomicOr((p), (v))
-#endif
+#define JHE_HD BITS_HD
 
 namespace ctpn {
 
 enum : uint32_t {
   JHE_FLAG_RANGE = 1,       // a DC difference above 11 bits or an AC coefficient above 10: the host half says so in its own words
-  JHE_FLAG_STORE = 2,       // a store outside the image's part of a buffer was asked for (and not made): a count did not come out
-  JHE_FLAG_SIZE = 4         // the totals do not fit the image's parts
+  JHE_FLAG_STORE = BITS_FLAG_STORE, JHE_FLAG_SIZE = BITS_FLAG_SIZE
 };
 
 enum {
@@ -161,36 +155,19 @@ struct JheCount {
   JHE_HD void put(uint32_t, int len) { bits += (uint32_t)len; }
 };
 
-// bits -> the image's unstuffed words. A word's first stream byte is its lowest byte, a byte's first stream bit its highest. The first
-// word a block touches and its last, partial one may hold a neighbour's bits too: those are ORed in; the words between are the block's
-// alone and stored whole
-struct JheWrite {
-  uint32_t* words;          // the image's part
-  uint32_t nwords;
-  uint32_t w;               // the word the pending bits belong to
-  uint64_t acc;             // its pending bits are acc's lowest nb
+// bits -> the image's unstuffed words (WordSink, bits_dev.h), MSB first. A word's first stream byte is its lowest, a byte's first stream bit
+// its highest: a full word is byte-swapped on its way out
+struct JheWrite : WordSink<uint32_t> {
+  uint64_t acc;             // the pending bits of word w are acc's lowest nb
   int nb;                   // < 32 between two puts
-  bool shared;              // nothing emitted yet: the next word may hold the previous block's bits
-  uint32_t bad;
-  JHE_HD void start(uint32_t* p, uint32_t n, uint32_t bit0) { words = p; nwords = n; w = bit0 >> 5; acc = 0; nb = (int)(bit0 & 31u); shared = true; bad = 0; }
-  JHE_HD void emit(uint32_t v, bool whole) {
-    v = __builtin_bswap32(v);
-    if (w < nwords) {
-      if (whole && !shared) words[w] = v;
-      else JHE_ATOMIC_OR(words + w, v);
-    } else {
-      bad = JHE_FLAG_STORE;
-    }
-    ++w;
-    shared = false;
-  }
+  JHE_HD void start(uint32_t* p, uint32_t n, uint32_t bit0) { WordSink<uint32_t>::start(p, n, bit0); acc = 0; nb = (int)(bit0 & 31u); }
   JHE_HD void put(uint32_t code, int len) {      // len <= 16
     acc = (acc << len) | code;
     nb += len;
-    if (nb >= 32) { emit((uint32_t)(acc >> (nb - 32)), true); nb -= 32; }
+    if (nb >= 32) { emit(__builtin_bswap32((uint32_t)(acc >> (nb - 32))), true); nb -= 32; }
   }
-  JHE_HD uint32_t position() const { return w * 32u + (uint32_t)nb; }
-  JHE_HD void finish() { if (nb) { emit((uint32_t)(acc << (32 - nb)), false); nb = 0; } }
+  JHE_HD uint32_t position() const { return WordSink<uint32_t>::position() + (uint32_t)nb; }
+  JHE_HD void finish() { if (nb) { emit(__builtin_bswap32((uint32_t)(acc << (32 - nb))), false); nb = 0; } }
 };
 
 // ---- the passes, one call per thread -----------------------------------------------------------------------------------------------
@@ -207,7 +184,7 @@ JHE_HD void jhe_length_thread(const JheImg& im, uint32_t s, const int16_t* coef,
   const int pred = prev < 0 ? 0 : (int)coef[jhe_locate(im, (uint32_t)prev, ptc, pp)];
   JheCount c;
   c.bits = 0;
-  if (!jhe_block<ZZ>(c, blk, pred, T, tc)) JHE_ATOMIC_OR(flag, (uint32_t)JHE_FLAG_RANGE);
+  if (!jhe_block<ZZ>(c, blk, pred, T, tc)) BITS_ATOMIC_OR(flag, (uint32_t)JHE_FLAG_RANGE);
   len[im.blk0 + s] = c.bits;
 }
 
@@ -229,7 +206,7 @@ JHE_HD void jhe_write_thread(const JheImg& im, uint32_t s, const int16_t* coef, 
     if (pad) wr.put((1u << pad) - 1u, pad);
   }
   wr.finish();
-  if (wr.bad) JHE_ATOMIC_OR(flag, wr.bad);
+  if (wr.bad) BITS_ATOMIC_OR(flag, wr.bad);
 }
 
 // the unstuffed bytes of an image whose length pass counted `bits`
@@ -271,7 +248,42 @@ JHE_HD void jhe_stuff_thread(const JheImg& im, uint32_t q, uint32_t bits, const 
       }
     }
   }
-  if (bad) JHE_ATOMIC_OR(flag, bad);
+  if (bad) BITS_ATOMIC_OR(flag, bad);
+}
+
+// the chunks the second scan sums: those the unstuffed bytes of `bits` fill
+JHE_HD uint32_t jhe_chunk_count(uint32_t bits, const JheImg& im) {
+  const uint32_t count = (jhe_unstuffed_bytes(bits) + JHE_CHUNK - 1) / JHE_CHUNK; return count < im.nchunk ? count : im.nchunk;
+}
+// what a scan leaves in the image's result record; carry: its total. CHUNKS = false: the blocks' bits. CHUNKS = true: the 0xFF bytes of
+// the chunks of an unstuffed stream of `bits` -> the stuffed size, and whether both streams fit the image's parts
+template <bool CHUNKS>
+JHE_HD void jhe_scan_finish(const JheImg& im, uint32_t bits, uint32_t carry, JheRes& r) {
+  if (!CHUNKS) { r.bits = carry; return; }
+  const uint32_t nbytes = jhe_unstuffed_bytes(bits);
+  r.bytes = nbytes + carry;
+  if (nbytes > im.nwords * 4u || nbytes + carry > im.out_cap) BITS_ATOMIC_OR(&r.flag, (uint32_t)JHE_FLAG_SIZE);
+}
+
+// ---- host only: ONE copy for the library (api_jpeg_out.hip) and the test program --------------------------------------------------------
+// the descriptor of an h x w image with hs x vs luma sampling (coef_off: the caller's; its parts: jhe_layout)
+inline void jhe_describe(JheImg& I, int h, int w, int hs, int vs) {
+  I = JheImg();
+  I.hs = (uint32_t)hs; I.vs = (uint32_t)vs; I.mcux = (uint32_t)((w + 8 * hs - 1) / (8 * hs));
+  I.nmcu = I.mcux * (uint32_t)((h + 8 * vs - 1) / (8 * vs)); I.nblk = I.nmcu * (uint32_t)(hs * vs + 2);
+}
+struct JheTotals { uint32_t blk, words, chunks, outb, max_blocks, max_chunks; };
+// every image's part of every buffer of a launch group (the images described, JHE_MAX_BLOCKS blocks in all at most), and the buffers' sizes
+inline void jhe_layout(JheImg* imgs, size_t m, JheTotals& t) {
+  t = JheTotals();
+  for (size_t k = 0; k < m; ++k) {
+    JheImg& I = imgs[k];
+    I.blk0 = t.blk; I.word0 = t.words; I.nwords = I.nblk * (JHE_BLOCK_BYTES / 4);
+    I.chunk0 = t.chunks; I.nchunk = (I.nblk * JHE_BLOCK_BYTES + JHE_CHUNK - 1) / JHE_CHUNK;
+    I.out0 = t.outb; I.out_cap = I.nblk * 2 * JHE_BLOCK_BYTES;
+    t.blk += I.nblk; t.words += I.nwords; t.chunks += I.nchunk; t.outb += I.out_cap;
+    t.max_blocks = I.nblk > t.max_blocks ? I.nblk : t.max_blocks; t.max_chunks = I.nchunk > t.max_chunks ? I.nchunk : t.max_chunks;
+  }
 }
 
 }  // namespace ctpn

@@ -7,6 +7,7 @@
 // No workgroup waits on another: order comes from the kernel boundaries.
 #include "common.h"
 #include "png_enc_dev.h"
+#include "wg_scan.h"
 
 namespace ctpn {
 
@@ -41,10 +42,9 @@ __global__ __launch_bounds__(256) void pnge_write_kernel(const PngeImg* __restri
 }
 
 // exclusive prefix sum, in place, of one image's piece lengths behind the header's bits, and the Adler-32 out of the pieces' partials: one
-// workgroup per image, PNGE_SCAN_ITEMS pieces per step, the running total in a register of every thread (the form of jhe_scan_kernel,
-// whose item is one word and whose result record is the JPEG coder's: this one carries the two Adler sums along)
+// workgroup per image, PNGE_SCAN_ITEMS pieces per step, the running total in a register of every thread (jhe_scan_kernel's form, with
+// the two Adler sums carried along)
 __global__ __launch_bounds__(256) void pnge_scan_kernel(const PngeImg* __restrict__ imgs, const PngeCodes* __restrict__ codes, PngeLen* __restrict__ items, PngeRes* __restrict__ res) {
-  __shared__ uint32_t wsum[4];
   __shared__ unsigned long long wad[4][2];
   const PngeImg im = imgs[blockIdx.x];
   PngeLen* it = items + im.piece0;
@@ -66,25 +66,15 @@ __global__ __launch_bounds__(256) void pnge_scan_kernel(const PngeImg* __restric
       }
     }
     const uint32_t mine = v[0] + v[1] + v[2] + v[3];
-    uint32_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t up = __shfl_up(inc, d, 64);
-      if (lane >= (uint32_t)d) inc += up;
-    }
-    if (lane == 63u) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4; ++k) { before += k < wave ? wsum[k] : 0u; total += wsum[k]; }
-    uint32_t ex = carry + before + inc - mine;
+    uint32_t total;
+    uint32_t ex = carry + wg_scan256(mine, total) - mine;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (base + k < count) it[base + k].bits = ex;
       ex += v[k];
     }
     carry += total;
-    __syncthreads();      // wsum is rewritten in the next step
+    __syncthreads();      // wg_scan256's second barrier: the wave totals are rewritten in the next step
   }
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) { sa += __shfl_down(sa, d, 64); ss += __shfl_down(ss, d, 64); }
@@ -93,11 +83,7 @@ __global__ __launch_bounds__(256) void pnge_scan_kernel(const PngeImg* __restric
   if (tid == 0) {
     sa = wad[0][0] + wad[1][0] + wad[2][0] + wad[3][0];
     ss = wad[0][1] + wad[1][1] + wad[2][1] + wad[3][1];
-    const uint32_t bytes = (carry >> 3) + ((carry & 7u) ? 1u : 0u);
-    res[blockIdx.x].bits = carry;
-    res[blockIdx.x].bytes = bytes;
-    res[blockIdx.x].adler = pnge_adler_final(im.n, sa, ss);
-    if ((uint64_t)bytes > im.nwords * 4u) atomicOr(&res[blockIdx.x].flag, (uint32_t)PNGE_FLAG_SIZE);
+    pnge_scan_finish(im, carry, sa, ss, res[blockIdx.x]);
   }
 }
 

@@ -23,25 +23,13 @@
 #include <cstring>
 #include <vector>
 
-#ifndef PNGE_HD
-#define PNGE_HD __host__ __device__ __forceinline__
-#endif
-// an OR into a word / an add to a counter other threads may touch at the same time. The host forms (the library's ctpn_png_encode, one
-// image per thread, and the test program) run an image's threads one after the other: plain ones
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PNGE_ATOMIC_OR(p, v) atomicOr((p), (v))
-#define PNGE_ATOMIC_ADD(p, v) atomicAdd((p), (v))
-#else
-#define PNGE_ATOMIC_OR(p, v) (*(p) |= (v))
-#define PNGE_ATOMIC_ADD(p, v) (*(p) += (v))
-#endif
+#include "bits_dev.h"
+
+#define PNGE_HD BITS_HD
 
 namespace ctpn {
 
-enum : uint32_t {
-  PNGE_FLAG_STORE = 2,      // a store outside the image's part of the buffer was asked for (and not made)
-  PNGE_FLAG_SIZE = 4        // the total does not fit the image's part
-};
+enum : uint32_t { PNGE_FLAG_STORE = BITS_FLAG_STORE, PNGE_FLAG_SIZE = BITS_FLAG_SIZE };
 
 enum {
   PNGE_P = 256,             // stream bytes per piece
@@ -153,8 +141,8 @@ PNGE_HD void pnge_piece(const PngeImg& im, const uint8_t* img, uint64_t p, Sink&
 struct PngeHist {
   uint32_t* cnt;            // 286 counters (the workgroup's, in LDS)
   static const bool BYTES = false;
-  PNGE_HD void lit(uint32_t v) { PNGE_ATOMIC_ADD(cnt + v, 1u); }
-  PNGE_HD void match(uint32_t L, bool) { uint32_t k, eb, ev; pnge_lsym(L, k, eb, ev); PNGE_ATOMIC_ADD(cnt + 257u + k, 1u); }
+  PNGE_HD void lit(uint32_t v) { BITS_ATOMIC_ADD(cnt + v, 1u); }
+  PNGE_HD void match(uint32_t L, bool) { uint32_t k, eb, ev; pnge_lsym(L, k, eb, ev); BITS_ATOMIC_ADD(cnt + 257u + k, 1u); }
   PNGE_HD void run(uint32_t, uint32_t) {}
   PNGE_HD void byte(uint32_t) {}
 };
@@ -170,32 +158,20 @@ struct PngeCount {
   PNGE_HD void match(uint32_t L, bool far) { uint32_t k, eb, ev; pnge_lsym(L, k, eb, ev); bits += (ll[257u + k] >> 16) + eb + (far ? far_len : 1u); }
 };
 
-// bits -> the image's words, LSB first (a word's first stream byte is its lowest: the words are the bytes on a little-endian machine).
-// The first word a piece touches and its last, partial one may hold other pieces' bits -- several WHOLE pieces where the paper is flat:
-// those are ORed in. A word flushed full behind the first is the piece's alone (the next piece starts behind it) and stored whole
-struct PngeWrite {
+// bits -> the image's words (WordSink, bits_dev.h), LSB first (a word's first stream byte is its lowest: the words are the bytes on a
+// little-endian machine). The words a piece shares may hold several WHOLE pieces where the paper is flat. The index is 64 bits wide: the
+// host form takes images beyond 2^32 bits
+struct PngeWrite : WordSink<uint64_t> {
   const uint32_t* ll;
   uint32_t far_bits, far_len;
-  uint32_t* words;          // the image's part
-  uint64_t nwords, w;       // w: the word the pending bits belong to
-  uint64_t acc;             // its pending bits are acc's lowest nb
+  uint64_t acc;             // the pending bits of word w are acc's lowest nb
   uint32_t nb;              // < 32 between two puts
-  bool shared;
-  uint32_t bad;
   static const bool BYTES = false;
   PNGE_HD void start(const uint32_t* ll_, uint32_t fb, uint32_t fl, uint32_t* p, uint64_t n, uint64_t bit0) {
-    ll = ll_; far_bits = fb; far_len = fl; words = p; nwords = n; w = bit0 >> 5; acc = 0; nb = (uint32_t)(bit0 & 31u); shared = true; bad = 0;
+    WordSink<uint64_t>::start(p, n, bit0);
+    ll = ll_; far_bits = fb; far_len = fl; acc = 0; nb = (uint32_t)(bit0 & 31u);
   }
-  PNGE_HD void emit(uint32_t v, bool whole) {
-    if (w < nwords) {
-      if (whole && !shared) words[w] = v;
-      else if (v) PNGE_ATOMIC_OR(words + w, v);
-    } else {
-      bad = PNGE_FLAG_STORE;
-    }
-    ++w;
-    shared = false;
-  }
+  PNGE_HD uint64_t position() const { return WordSink<uint64_t>::position() + nb; }
   PNGE_HD void put(uint32_t v, uint32_t len) {      // len <= 16; v below 2^len
     acc |= (uint64_t)v << nb;
     nb += len;
@@ -223,7 +199,7 @@ PNGE_HD void pnge_hist_thread(const PngeImg& im, uint32_t s, const uint8_t* px, 
   PngeHist hs;
   hs.cnt = cnt;
   pnge_piece(im, px + im.pix_off, s, hs);
-  if (s == im.npieces - 1u) PNGE_ATOMIC_ADD(cnt + PNGE_EOB, 1u);
+  if (s == im.npieces - 1u) BITS_ATOMIC_ADD(cnt + PNGE_EOB, 1u);
 }
 
 // length pass: thread s of image im. ll: the image's code; out: the per-piece array. The last piece carries EOB
@@ -243,7 +219,7 @@ PNGE_HD void pnge_length_thread(const PngeImg& im, uint32_t s, const uint8_t* px
 PNGE_HD void pnge_write_thread(const PngeImg& im, uint32_t s, const uint8_t* px, const uint32_t* ll, const uint32_t* hdr, const PngeLen* off, uint32_t* words, uint32_t* flag) {
   uint32_t bad = 0;
   if (s < (uint32_t)PNGE_HDR_WORDS && hdr[s]) {
-    if ((uint64_t)s < im.nwords) PNGE_ATOMIC_OR(words + im.word0 + s, hdr[s]); else bad = PNGE_FLAG_STORE;
+    if ((uint64_t)s < im.nwords) BITS_ATOMIC_OR(words + im.word0 + s, hdr[s]); else bad = PNGE_FLAG_STORE;
   }
   if (s < im.npieces && !*flag) {
     PngeWrite wr;
@@ -253,7 +229,7 @@ PNGE_HD void pnge_write_thread(const PngeImg& im, uint32_t s, const uint8_t* px,
     wr.finish();
     bad |= wr.bad;
   }
-  if (bad) PNGE_ATOMIC_OR(flag, bad);
+  if (bad) BITS_ATOMIC_OR(flag, bad);
 }
 
 // Adler-32 of the stream from the pieces' partials: s1 = 1 + sum A_p, s2 = n + sum_p [(n - end_p) A_p + B_p], mod 65521. One piece's
@@ -268,10 +244,17 @@ PNGE_HD uint32_t pnge_adler_final(uint64_t n, uint64_t sa, uint64_t ss) {
 }
 // the end of piece s in the stream
 PNGE_HD uint64_t pnge_piece_end(const PngeImg& im, uint32_t s) { const uint64_t e = ((uint64_t)s + 1u) * PNGE_P; return e < im.n ? e : im.n; }
+// what the scan leaves in the image's result record; carry: the block's bits, header included; sa, ss: the pieces' Adler terms
+PNGE_HD void pnge_scan_finish(const PngeImg& im, uint32_t carry, uint64_t sa, uint64_t ss, PngeRes& r) {
+  r.bits = carry;
+  r.bytes = (carry >> 3) + ((carry & 7u) ? 1u : 0u);
+  r.adler = pnge_adler_final(im.n, sa, ss);
+  if ((uint64_t)r.bytes > im.nwords * 4u) BITS_ATOMIC_OR(&r.flag, (uint32_t)PNGE_FLAG_SIZE);
+}
 
 // ---- host only: ONE copy for the library's host form, the device form's host half and the test program ------------------------------
 
-// the descriptor of an h x w image (pix_off, word0, nwords, piece0: the caller's)
+// the descriptor of an h x w image (pix_off, word0, nwords, piece0: pnge_layout)
 inline void pnge_describe(PngeImg& I, int h, int w) {
   static const uint32_t dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
   I = PngeImg();
@@ -289,6 +272,17 @@ inline void pnge_describe(PngeImg& I, int h, int w) {
 // words of an image's part of the buffer: header, 15 bits per stream byte at most (a literal is one code; a match covers three bytes with
 // 15 + 5 + 1 + 13 bits), EOB, and the last word
 inline uint64_t pnge_words(const PngeImg& I) { return (1338u + 15u * I.n + 15u + 31u) / 32u + 1u; }
+
+struct PngeTotals { uint64_t pix, pieces, words; };
+// every image's part of every buffer of a call (the images described, of any sizes; the caller keeps `pieces` below 2^32), and their sizes
+inline void pnge_layout(PngeImg* imgs, size_t m, PngeTotals& t) {
+  t = PngeTotals();
+  for (size_t k = 0; k < m; ++k) {
+    PngeImg& I = imgs[k];
+    I.pix_off = t.pix; I.piece0 = (uint32_t)t.pieces; I.word0 = t.words; I.nwords = pnge_words(I);
+    t.pix += (uint64_t)I.h * I.w * 3u; t.pieces += I.npieces; t.words += I.nwords;
+  }
+}
 
 // code lengths of at most `limit` bits for the symbols with cnt > 0 (0 for the others): Huffman's lengths, and where they exceed the limit
 // the Kraft sum is repaired -- clipped codes overdraw it; the deepest codes below the limit are lengthened until it holds, then codes are
@@ -417,7 +411,7 @@ inline bool pnge_encode_host(const uint8_t* bgr, int h, int w, uint8_t* out, siz
     wr.start(C.ll, I.far_bits, I.far_len, words.data(), words.size(), at);
     pnge_piece(I, bgr, p, wr);
     if (p == I.npieces - 1u) wr.sym(C.ll[PNGE_EOB]);
-    at = wr.w * 32u + wr.nb;
+    at = wr.position();
     wr.finish();
   }
   std::memcpy(out + PNGE_FRAME_FRONT, words.data(), bytes);

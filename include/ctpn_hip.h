@@ -475,6 +475,33 @@ int    ctpn_jpeg_entropy_decode_device(ctpn_ctx* ctx, const uint8_t* const* file
                                        size_t coef_capacity_per_file, uint16_t* qt_out, int* layout8_out, int* status_out);
 int    ctpn_jpeg_entropy_device_stats(ctpn_ctx* ctx, long long* out4);
 
+/* ---- JPEG files of MIXED sizes into one ragged device batch (jpeg_ragged.hip): additive to ABI 10, no option and no default changes. The
+ * calls above take n files of one size, one layout and one orientation; a folder of photographs and scans has many file sizes that resize_im
+ * maps to one or two widths, and ctpn_forward_ragged / ctpn_detect_submit_ragged batch images of one width and different heights. These two
+ * calls join them: the files of one call may differ in size, component layout (gray, 4:4:4, 4:4:0, 4:2:2, 4:2:0), EXIF orientation and
+ * restart interval.
+ *   ctpn_decode_jpeg_batch_ragged   file_h[i] x file_w[i]: file i's size as ctpn_jpeg_probe reports it (turned), checked after the parse;
+ *                                   factors[i]: its resize_im factor, used as fx = fy (<= 0 or 1: no resize). Every file's width must map to
+ *                                   the canvas's -- round-half-even(file_w[i] * factors[i]) == wc -- and its height to 16 .. hc; otherwise
+ *                                   CTPN_ERR_ARG naming the file, before any work. Result: a canvas n x hc x wc x 3 BGR uint8 in device memory
+ *                                   owned by the ctx; slot i holds cv2.resize(cv2.imread(file i), factors[i]) in rows [0, heights_out[i]) and
+ *                                   ZEROS below (lib/utils/blob.py im_list_to_canvas's canvas, byte for byte: image i's rows are what
+ *                                   ctpn_decode_jpeg_batch(n = 1, fx = fy = factors[i]) returns for it). entropy_on_device: 0 = Huffman
+ *                                   decoding on the ctx's host pool (progressive files included), 1 = on the device (a progressive file is
+ *                                   CTPN_ERR_UNSUPPORTED; a raised flag word sends that file alone to the host half). Per-file errors carry
+ *                                   the file's index. Buffers and events are ctpn_decode_jpeg_batch's -- the same two sets, in turn with
+ *                                   that call: *canvas_dev_out is valid for ctpn_forward_ragged / ctpn_detect_submit_ragged(canvas_on_device
+ *                                   = 1) and ctpn_jpeg_batch_fetch (n x hc x wc x 3 bytes) until the second-next decode call of either
+ *                                   kind. Coefficients and planes are packed per file (each file's own ctpn_jpeg_coef_capacity at a
+ *                                   prefix-summed base), not n x the largest. The file-size BGR image is never stored: colour conversion
+ *                                   and resize are one kernel over the canvas.
+ *   ctpn_decode_jpeg_files_ragged   the same from n PATHS.
+ * A post-processing-only ctx is CTPN_ERR_STATE. */
+int    ctpn_decode_jpeg_batch_ragged(ctpn_ctx* ctx, const uint8_t* const* files, const size_t* sizes, int n, const int* file_h, const int* file_w,
+                                     const double* factors, int hc, int wc, int entropy_on_device, const uint8_t** canvas_dev_out, int* heights_out);
+int    ctpn_decode_jpeg_files_ragged(ctpn_ctx* ctx, const char* const* paths, int n, const int* file_h, const int* file_w, const double* factors,
+                                     int hc, int wc, int entropy_on_device, const uint8_t** canvas_dev_out, int* heights_out);
+
 /* ---- cv2.imwrite for the annotated result images (reference ctpn/demo.py:28-52: draw_boxes, cv2.resize by 1 / scale, cv2.imwrite), the mirror
  * image of the JPEG reader above, split where the work splits: BGR -> YCbCr, 2 x 2 chroma downsampling, the 8 x 8 forward DCT and the
  * quantiser on the device (one launch; the outlines and the resize before it, so annotated pixels never visit the host), baseline Huffman

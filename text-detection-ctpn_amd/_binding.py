@@ -125,6 +125,9 @@ def _declare(lib):
         "ctpn_jpeg_entropy_decode_device": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_size_t,
                                                       C.POINTER(C.c_uint16), i32p, i32p]),
         "ctpn_jpeg_entropy_device_stats": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
+        "ctpn_decode_jpeg_batch_ragged": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(C.c_size_t), C.c_int, i32p, i32p, f64p, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(vp), i32p]),
+        "ctpn_decode_jpeg_files_ragged": (C.c_int, [vp, C.POINTER(C.c_char_p), C.c_int, i32p, i32p, f64p, C.c_int, C.c_int, C.c_int, C.POINTER(vp), i32p]),
         "ctpn_jpeg_encode_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_encode": (C.c_int, [C.POINTER(C.c_int16), i32p, C.POINTER(C.c_uint16), u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "ctpn_encode_jpeg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
@@ -968,6 +971,35 @@ class Context:
         out, oh, ow = C.c_void_p(0), C.c_int(0), C.c_int(0)
         _check(fn(self._h, arr, len(paths), int(h), int(w), float(fx), float(fy), C.byref(out), C.byref(oh), C.byref(ow)))
         return out.value, (len(paths), oh.value, ow.value)
+
+    def decode_jpeg_ragged(self, files_or_paths, sizes, factors, hc, wc, entropy="host"):
+        """JPEG files of mixed sizes, layouts and orientations into one ragged canvas on the device (ctpn_decode_jpeg_batch_ragged /
+        ctpn_decode_jpeg_files_ragged). files_or_paths: every item the bytes of a file, or every item a path (str / os.PathLike); sizes: one
+        (h, w) per file as jpeg_probe reports it; factors: one resize_im factor per file (<= 0 or 1: no resize); every width must map to wc
+        and every height to 16 .. hc. -> ((device pointer, (n, hc, wc)), heights int32): the canvas handle goes to detect_submit(device_ptr=,
+        shape=, heights=) / forward_ragged / detect_ragged and to jpeg_batch_fetch; it stays valid until the second-next decode call."""
+        on_dev = 1 if self._entropy_form(entropy) else 0
+        items = list(files_or_paths)
+        n = len(items)
+        hw = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
+        fh, fw = np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+        fac = np.ascontiguousarray(np.asarray(factors, np.float64).reshape(n))
+        hts = np.zeros((n,), np.int32)
+        out = C.c_void_p(0)
+        as_paths = [isinstance(it, (str, os.PathLike)) for it in items]
+        if n and all(as_paths):
+            keep, arr = _path_array(items)
+            _check(self._lib.ctpn_decode_jpeg_files_ragged(self._h, arr, n, _ptr(fh, C.c_int), _ptr(fw, C.c_int), _ptr(fac, C.c_double), int(hc), int(wc), on_dev,
+                                                           C.byref(out), _ptr(hts, C.c_int)))
+        else:
+            if any(as_paths):
+                raise ValueError("decode_jpeg_ragged wants all files as bytes or all as paths")
+            keeps = [_bytes_ptr(f) for f in items]
+            ptrs = (C.POINTER(C.c_uint8) * n)(*[k[1] for k in keeps])
+            lens = (C.c_size_t * n)(*[k[2] for k in keeps])
+            _check(self._lib.ctpn_decode_jpeg_batch_ragged(self._h, ptrs, lens, n, _ptr(fh, C.c_int), _ptr(fw, C.c_int), _ptr(fac, C.c_double), int(hc), int(wc),
+                                                           on_dev, C.byref(out), _ptr(hts, C.c_int)))
+        return (out.value, (n, int(hc), int(wc))), hts
 
     def jpeg_batch_fetch(self, device_ptr, shape):
         """The decoded batch as an (n, h, w, 3) uint8 array on the host (ctpn_jpeg_batch_fetch)."""

@@ -377,7 +377,8 @@ int ctpn_destroy(ctpn_ctx* c) {
   for (auto& j : c->jpeg) {
     if (j.coef_host) (void)hipHostFree(j.coef_host);
     if (j.qt_host) (void)hipHostFree(j.qt_host);
-    for (void* p : {(void*)j.coef_dev, (void*)j.qt_dev, (void*)j.out_dev}) if (p) (void)hipFree(p);
+    if (j.tab_host) (void)hipHostFree(j.tab_host);
+    for (void* p : {(void*)j.coef_dev, (void*)j.qt_dev, (void*)j.out_dev, (void*)j.tab_dev}) if (p) (void)hipFree(p);
     for (hipEvent_t e : {j.ev_h2d, j.ev_ready, j.ev_consumed}) if (e) (void)hipEventDestroy(e);
   }
   for (void* p : {(void*)c->jpeg_planes, (void*)c->jpeg_raw}) if (p) (void)hipFree(p);

@@ -1,5 +1,6 @@
 // C ABI of libctpn_hip.so, input unit: JPEG probe / entropy decode / batched decode to device images (kernels: jpeg.hip), resize (preprocess.hip).
 #include "ctx.h"
+#include "jpeg_ragged_dev.h"      // JrImage: the ragged decode's per-image descriptor
 
 namespace ctpn {
 
@@ -13,21 +14,32 @@ static int jpeg_grow_dev(ctpn_ctx* c, void** p, size_t& have, size_t need) {
   return CTPN_OK;
 }
 
-static int jpeg_reserve(ctpn_ctx* c, ctpn_ctx::JpegBufs& J, size_t n, size_t cap, size_t raw_bytes, size_t out_bytes) {
+// coef_total: int16 elements of the call's coefficient blocks (n x one capacity, or the sum of the files' own); tab: the ragged call's
+// descriptor table too
+static int jpeg_reserve(ctpn_ctx* c, ctpn_ctx::JpegBufs& J, size_t n, size_t coef_total, size_t raw_bytes, size_t out_bytes, bool tab = false) {
   if (!c->jpeg_ready) {
     for (auto& j : c->jpeg)
       for (hipEvent_t* e : {&j.ev_h2d, &j.ev_ready, &j.ev_consumed}) CTPN_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
     c->jpeg_ready = true;
   }
   int rc;
-  if (n * cap > J.coef_elems) {        // (the copy that last read the page-locked block has been waited for by the caller)
+  if (coef_total > J.coef_elems) {     // (the copy that last read the page-locked block has been waited for by the caller)
     if (J.coef_host) CTPN_HIP_TRY(hipHostFree(J.coef_host));
     J.coef_host = nullptr;
     J.coef_elems = 0;                  // (a failed allocation below must not leave the old size standing next to a null block)
-    CTPN_HIP_TRY(hipHostMalloc((void**)&J.coef_host, n * cap * sizeof(int16_t)));
+    CTPN_HIP_TRY(hipHostMalloc((void**)&J.coef_host, coef_total * sizeof(int16_t)));
     size_t have = J.coef_elems * sizeof(int16_t);
-    if ((rc = jpeg_grow_dev(c, (void**)&J.coef_dev, have, n * cap * sizeof(int16_t)))) return rc;
-    J.coef_elems = n * cap;
+    if ((rc = jpeg_grow_dev(c, (void**)&J.coef_dev, have, coef_total * sizeof(int16_t)))) return rc;
+    J.coef_elems = coef_total;
+  }
+  if (tab && n > J.tab_imgs) {
+    if (J.tab_host) CTPN_HIP_TRY(hipHostFree(J.tab_host));
+    J.tab_host = nullptr;
+    J.tab_imgs = 0;
+    CTPN_HIP_TRY(hipHostMalloc((void**)&J.tab_host, n * sizeof(JrImage)));
+    size_t have = 0;
+    if ((rc = jpeg_grow_dev(c, (void**)&J.tab_dev, have, n * sizeof(JrImage)))) return rc;
+    J.tab_imgs = n;
   }
   if (n > J.qt_imgs) {
     if (J.qt_host) CTPN_HIP_TRY(hipHostFree(J.qt_host));
@@ -39,7 +51,7 @@ static int jpeg_reserve(ctpn_ctx* c, ctpn_ctx::JpegBufs& J, size_t n, size_t cap
     J.qt_imgs = n;
   }
   if ((rc = jpeg_grow_dev(c, (void**)&J.out_dev, J.out_bytes, out_bytes + 256))) return rc;
-  if ((rc = jpeg_grow_dev(c, (void**)&c->jpeg_planes, c->jpeg_planes_bytes, n * cap))) return rc;      // one byte per coefficient
+  if ((rc = jpeg_grow_dev(c, (void**)&c->jpeg_planes, c->jpeg_planes_bytes, coef_total))) return rc;      // one byte per coefficient
   if (raw_bytes && (rc = jpeg_grow_dev(c, (void**)&c->jpeg_raw, c->jpeg_raw_bytes, raw_bytes + 256))) return rc;
   return CTPN_OK;
 }
@@ -227,7 +239,7 @@ static int jpeg_decode_impl(ctpn_ctx* c, const JpegSource& src, int n, int h, in
   // the page-locked coefficient block was last read by the copy of two calls ago
   if (J.h2d_valid) CTPN_HIP_TRY(hipEventSynchronize(J.ev_h2d));
   const size_t cap = jpeg_coef_capacity(h, w);
-  int rc = jpeg_reserve(c, J, (size_t)n, cap, resize ? (size_t)n * h * w * 3 : 0, (size_t)n * dh * dw * 3);
+  int rc = jpeg_reserve(c, J, (size_t)n, (size_t)n * cap, resize ? (size_t)n * h * w * 3 : 0, (size_t)n * dh * dw * 3);
   if (rc) return rc;
   // host half: one image per worker thread
   std::vector<JpegGeom> geo((size_t)n);
@@ -303,6 +315,122 @@ static int jpeg_decode_impl(ctpn_ctx* c, const JpegSource& src, int n, int h, in
   *images_dev_out = J.out_dev;
   if (out_h) *out_h = dh;
   if (out_w) *out_w = dw;
+  return CTPN_OK;
+}
+
+// ctpn_decode_jpeg_batch_ragged / ctpn_decode_jpeg_files_ragged: files of mixed sizes, layouts and orientations into one ragged canvas. The
+// two buffer sets, the flip and the three events are jpeg_decode_impl's; what differs is per file: its own coefficient capacity at a
+// prefix-summed base (coefficients and planes alike), its own geometry and factor in a descriptor table, one pixel launch pair over the table
+static int jpeg_decode_ragged_impl(ctpn_ctx* c, const JpegSource& src, int n, const int* file_h, const int* file_w, const double* factors, int hc, int wc,
+                                   bool dev_entropy, const uint8_t** canvas_dev_out, int* heights_out) {
+  const std::string who = "ctpn_decode_jpeg_batch_ragged: ";
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + "post-processing-only ctx");
+  if (n <= 0 || hc < 16 || wc <= 0 || hc > 65535 || wc > 65535) return fail(CTPN_ERR_ARG, who + "empty batch / bad canvas size (hc >= 16)");
+  std::vector<double> fac((size_t)n);
+  std::vector<int> hts((size_t)n);
+  std::vector<size_t> cap((size_t)n), base((size_t)n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    const int h = file_h[i], w = file_w[i];
+    const std::string file = "file " + std::to_string(i);
+    if (h <= 0 || w <= 0 || h > 65535 || w > 65535) return fail(CTPN_ERR_ARG, who + file + ": bad size");
+    const double f = factors[i] > 0.0 ? factors[i] : 1.0;
+    const int dh = f == 1.0 ? h : resize_out_dim(h, f), dw = f == 1.0 ? w : resize_out_dim(w, f);
+    if (dw != wc) return fail(CTPN_ERR_ARG, who + file + ": width " + std::to_string(w) + " maps to " + std::to_string(dw) + ", not to the canvas's " + std::to_string(wc));
+    if (dh < 16 || dh > hc) return fail(CTPN_ERR_ARG, who + file + ": height " + std::to_string(h) + " maps to " + std::to_string(dh) + ", outside 16 .. " + std::to_string(hc));
+    fac[i] = f; hts[i] = dh;
+    cap[i] = jpeg_coef_capacity(h, w);
+    base[i + 1] = base[i] + cap[i];
+  }
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  const int b = c->jpeg_flip;
+  auto& J = c->jpeg[b];
+  // the page-locked blocks (coefficients, tables, descriptors) were last read by the copies of two calls ago
+  if (J.h2d_valid) CTPN_HIP_TRY(hipEventSynchronize(J.ev_h2d));
+  int rc = jpeg_reserve(c, J, (size_t)n, base[n], 0, (size_t)n * hc * wc * 3, true);
+  if (rc) return rc;
+  std::vector<JpegGeom> geo((size_t)n);
+  std::vector<int> st((size_t)n, CTPN_OK);
+  std::vector<std::string> msg((size_t)n);
+  std::vector<JhPrep> prep(dev_entropy ? (size_t)n : 0);
+  std::vector<std::vector<uint8_t>> held(dev_entropy && src.paths ? (size_t)n : 0);
+  std::vector<const uint8_t*> dptr((size_t)n, nullptr);
+  std::vector<size_t> dlen((size_t)n, 0);
+  if (dev_entropy) c->pool->run(n, [&](int i) {
+    try {
+      if (src.paths) {
+        if (!jpeg_read_file(src.paths[i], held[i])) { st[i] = CTPN_ERR_ARG; msg[i] = std::string("cannot read ") + src.paths[i]; return; }
+        dptr[i] = held[i].data(); dlen[i] = held[i].size();
+      } else { dptr[i] = src.mem[i]; dlen[i] = src.sizes[i]; }
+      st[i] = jpeg_huff_prepare(dptr[i], dlen[i], &prep[i]);
+      if (!st[i] && prep[i].coef_count > cap[i]) st[i] = fail(CTPN_ERR_ARG, "jpeg: the file is larger than the size given for it");
+      if (st[i]) msg[i] = ctpn_last_error();
+      else geo[i] = prep[i].g;
+    } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }
+  });
+  else c->pool->run(n, [&](int i) {
+    const uint8_t* data = nullptr; size_t len = 0;
+    static thread_local std::vector<uint8_t> filebuf;      // one per worker thread, reused from batch to batch
+    try {
+      if (src.paths) {
+        if (!jpeg_read_file(src.paths[i], filebuf)) { st[i] = CTPN_ERR_ARG; msg[i] = std::string("cannot read ") + src.paths[i]; return; }
+        data = filebuf.data(); len = filebuf.size();
+      } else { data = src.mem[i]; len = src.sizes[i]; }
+      st[i] = jpeg_entropy_decode(data, len, J.coef_host + base[i], cap[i], J.qt_host + (size_t)i * 192, &geo[i]);
+      if (st[i] == CTPN_ERR_CAPACITY) st[i] = CTPN_ERR_ARG;      // (only a file that is not file_h x file_w overruns its own capacity)
+      if (st[i]) msg[i] = ctpn_last_error();
+      if (filebuf.capacity() > ((size_t)8 << 20)) std::vector<uint8_t>().swap(filebuf);
+    } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }      // nothing may leave a worker thread
+  });
+  for (int i = 0; i < n; ++i) if (st[i]) return fail(st[i], who + "file " + std::to_string(i) + ": " + msg[i]);
+  for (int i = 0; i < n; ++i)
+    if (geo[i].oh != file_h[i] || geo[i].ow != file_w[i])
+      return fail(CTPN_ERR_ARG, who + "file " + std::to_string(i) + " is not " + std::to_string(file_h[i]) + " x " + std::to_string(file_w[i]) + " (as cv2.imread returns it: EXIF orientation applied)");
+  // the descriptor table
+  JrImage* tab = (JrImage*)J.tab_host;
+  long long blocks = 0;
+  for (int i = 0; i < n; ++i) {
+    JrImage& d = tab[i];
+    std::memset(&d, 0, sizeof(d));
+    d.g = geo[i];
+    d.coef_base = d.plane_base = (long long)base[i];
+    d.block0 = blocks;
+    d.inv_f = 1.0 / fac[i];
+    d.resize = fac[i] != 1.0;
+    d.height = hts[i];
+    blocks += geo[i].blocks_per_img;
+  }
+  hipStream_t qs = c->stream_c;
+  // the device buffers of this set: the forward that read out_dev two calls ago has passed its first layer
+  if (J.consumed_valid) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_consumed, 0));
+  if (dev_entropy) {
+    std::vector<long long> coef_base((size_t)n);
+    std::vector<int> use((size_t)n);
+    std::vector<uint32_t> flags((size_t)n, 0u);
+    for (int i = 0; i < n; ++i) { coef_base[i] = (long long)base[i]; use[i] = i; std::memcpy(J.qt_host + (size_t)i * 192, prep[i].qt, sizeof(prep[i].qt)); }
+    if ((rc = jh_decode(c, dptr.data(), dlen.data(), prep, use, JH_SUBSEQ_DEFAULT, J.coef_dev, coef_base, base[n], qs, flags))) return rc;
+    // a file with a raised flag is the host half's, alone: its status and message are the host's, its coefficients replace the device's
+    for (int i = 0; i < n; ++i) {
+      if (!flags[i]) continue;
+      JpegGeom g2;
+      if ((rc = jpeg_entropy_decode(dptr[i], dlen[i], J.coef_host + base[i], cap[i], J.qt_host + (size_t)i * 192, &g2)))
+        return fail(rc, who + "file " + std::to_string(i) + ": " + ctpn_last_error());
+      CTPN_HIP_TRY(hipMemcpyAsync(J.coef_dev + base[i], J.coef_host + base[i], (size_t)geo[i].coef_per_img * sizeof(int16_t), hipMemcpyHostToDevice, qs));
+    }
+  } else
+    for (int i = 0; i < n; ++i)      // every file's own coefficients (its capacity is the largest any layout of its size needs: up to twice as many)
+      CTPN_HIP_TRY(hipMemcpyAsync(J.coef_dev + base[i], J.coef_host + base[i], (size_t)geo[i].coef_per_img * sizeof(int16_t), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(J.qt_dev, J.qt_host, (size_t)n * 192 * sizeof(uint16_t), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(J.tab_dev, J.tab_host, (size_t)n * sizeof(JrImage), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipEventRecord(J.ev_h2d, qs));
+  J.h2d_valid = true;
+  if ((rc = launch_jpeg_pixels_ragged(J.coef_dev, J.qt_dev, c->jpeg_planes, J.out_dev, (const JrImage*)J.tab_dev, n, blocks, hc, wc, qs))) return rc;
+  CTPN_HIP_TRY(hipEventRecord(J.ev_ready, qs));
+  J.ready_valid = true;
+  J.consumed_valid = false;      // until a forward reads this buffer
+  J.out_n = n; J.out_h = hc; J.out_w = wc;
+  c->jpeg_flip ^= 1;
+  *canvas_dev_out = J.out_dev;
+  for (int i = 0; i < n; ++i) heights_out[i] = hts[i];
   return CTPN_OK;
 }
 
@@ -385,7 +513,24 @@ int ctpn_decode_jpeg_files_device(ctpn_ctx* c, const char* const* paths, int n, 
   return jpeg_decode_impl(c, src, n, h, w, fx, fy, images_dev_out, out_h, out_w, true);
 }
 
-int ctpn_jpeg_entropy_decode_device(ctpn_ctx* c, const uint8_t* const* files, const size_t* sizes, int n, int subseq_bits, int16_t* coef_out,
+// ---- files of mixed sizes into one ragged canvas (jpeg_ragged.hip) ----
+int ctpn_decode_jpeg_batch_ragged(ctpn_ctx* c, const uint8_t* const* files, const size_t* sizes, int n, const int* file_h, const int* file_w, const double* factors,
+                                  int hc, int wc, int entropy_on_device, const uint8_t** canvas_dev_out, int* heights_out) {
+  if (!c || !files || !sizes || !file_h || !file_w || !factors || !canvas_dev_out || !heights_out) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_batch_ragged: null pointer");
+  for (int i = 0; i < n; ++i) if (!files[i]) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_batch_ragged: null file pointer");
+  JpegSource src; src.mem = files; src.sizes = sizes;
+  return jpeg_decode_ragged_impl(c, src, n, file_h, file_w, factors, hc, wc, entropy_on_device != 0, canvas_dev_out, heights_out);
+}
+
+int ctpn_decode_jpeg_files_ragged(ctpn_ctx* c, const char* const* paths, int n, const int* file_h, const int* file_w, const double* factors, int hc, int wc,
+                                  int entropy_on_device, const uint8_t** canvas_dev_out, int* heights_out) {
+  if (!c || !paths || !file_h || !file_w || !factors || !canvas_dev_out || !heights_out) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_files_ragged: null pointer");
+  for (int i = 0; i < n; ++i) if (!paths[i]) return fail(CTPN_ERR_ARG, "ctpn_decode_jpeg_files_ragged: null path");
+  JpegSource src; src.paths = paths;
+  return jpeg_decode_ragged_impl(c, src, n, file_h, file_w, factors, hc, wc, entropy_on_device != 0, canvas_dev_out, heights_out);
+}
+
+int ctpn_jpeg_entropy_decode_device(ctpn_ctx* c,const uint8_t* const* files, const size_t* sizes, int n, int subseq_bits, int16_t* coef_out,
                                     size_t coef_capacity_per_file, uint16_t* qt_out, int* layout8_out, int* status_out) {
   if (!c || !files || !sizes || !coef_out || !qt_out || !layout8_out || !status_out || n <= 0) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_decode_device: null pointer / empty batch");
   for (int i = 0; i < n; ++i) if (!files[i]) return fail(CTPN_ERR_ARG, "ctpn_jpeg_entropy_decode_device: null file pointer");

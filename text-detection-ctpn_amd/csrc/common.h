@@ -324,6 +324,10 @@ int jpeg_entropy_decode(const uint8_t* data, size_t len, int16_t* coef, size_t c
 int launch_jpeg_pixels(const int16_t* coef_dev, const uint16_t* qt_dev, uint8_t* planes_dev, uint8_t* out_dev, const JpegGeom& g, int n, hipStream_t s);
 int jpeg_probe(const uint8_t* data, size_t len, int* h, int* w, int* ncomp, int* luma_sampling);
 size_t jpeg_coef_capacity(int h, int w);
+// jpeg_ragged.hip: the pixel half for files of mixed sizes, into one ragged canvas (JrImage, the per-image descriptor: jpeg_ragged_dev.h)
+struct JrImage;
+int launch_jpeg_pixels_ragged(const int16_t* coef_dev, const uint16_t* qt_dev, uint8_t* planes_dev, uint8_t* canvas_dev, const JrImage* tab_dev, int n,
+                              long long total_blocks, int hc, int wc, hipStream_t s);
 
 // jpeg_huff.hip: the Huffman decode itself on the device (sequential files; per-thread source: jpeg_huff_dev.h). jpeg.hip prepares a file
 // for it without decoding a code: jparse + one linear pass over the scan's bytes

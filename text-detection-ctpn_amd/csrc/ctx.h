@@ -170,6 +170,7 @@ struct ctpn_ctx {
     int16_t* coef_host = nullptr; uint16_t* qt_host = nullptr;      // page-locked: what the entropy decoders write
     int16_t* coef_dev = nullptr; uint16_t* qt_dev = nullptr; uint8_t* out_dev = nullptr;
     size_t coef_elems = 0, qt_imgs = 0, out_bytes = 0;              // capacities
+    uint8_t* tab_host = nullptr; uint8_t* tab_dev = nullptr; size_t tab_imgs = 0;      // ctpn_decode_jpeg_batch_ragged: per-image descriptors (page-locked / device)
     int out_n = 0, out_h = 0, out_w = 0;                            // what out_dev holds
     hipEvent_t ev_h2d = nullptr, ev_ready = nullptr, ev_consumed = nullptr;
     bool h2d_valid = false, consumed_valid = false, ready_valid = false;

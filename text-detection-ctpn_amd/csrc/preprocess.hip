@@ -11,23 +11,9 @@
 #include <cmath>
 
 #include "common.h"
+#include "resize_pixel.h"      // rs_coord, rs_short, rs_weights, rs_u8: the per-sample arithmetic (shared with jpeg_ragged.hip)
 
 namespace ctpn {
-
-__device__ __forceinline__ void rs_coord(int d, double inv_f, int n, int clamp_w, int& s, float& f) {
-  f = (float)(((double)d + 0.5) * inv_f - 0.5);
-  s = (int)floorf(f);
-  f -= (float)s;
-  if (clamp_w) {
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= n - 1) { s = n - 1; f = 0.f; }
-  }
-}
-
-__device__ __forceinline__ int rs_short(float v) {   // saturate_cast<short>(float): round half to even, saturate
-  const int r = (int)rintf(v);
-  return r < -32768 ? -32768 : (r > 32767 ? 32767 : r);
-}
 
 template <typename T>
 __global__ void resize_linear_kernel(const T* __restrict__ src, T* __restrict__ dst, int n, int h, int w, int dh, int dw, double inv_fx,
@@ -48,15 +34,12 @@ __global__ void resize_linear_kernel(const T* __restrict__ src, T* __restrict__ 
     const T* r1 = src + ((long long)img * h + y1) * w * 3;
     T* o = dst + p * 3;
     if constexpr (sizeof(T) == 1) {
-      const int a0 = rs_short((1.f - fx) * 2048.f), a1 = rs_short(fx * 2048.f);
-      const int b0 = rs_short((1.f - fy) * 2048.f), b1 = rs_short(fy * 2048.f);
+      int a0, a1, b0, b1;
+      rs_weights(fx, a0, a1);
+      rs_weights(fy, b0, b1);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int S0 = (int)r0[sx * 3 + c] * a0 + (int)r0[x1 * 3 + c] * a1;
-        const int S1 = (int)r1[sx * 3 + c] * a0 + (int)r1[x1 * 3 + c] * a1;
-        const int v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-        o[c] = (T)(v < 0 ? 0 : (v > 255 ? 255 : v));
-      }
+      for (int c = 0; c < 3; ++c)
+        o[c] = (T)rs_u8((int)r0[sx * 3 + c], (int)r0[x1 * 3 + c], (int)r1[sx * 3 + c], (int)r1[x1 * 3 + c], a0, a1, b0, b1);
     } else {
       const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
 #pragma unroll

@@ -10,6 +10,10 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
     lib/rpn_msr/proposal_layer_tf.py:51), software-pipelined over the ctx's two slots; the ctx is sized ONCE for the largest
     batch / shape of the run (growing it mid-run would destroy the slot that still holds an uncollected batch).
 
+  * with --ragged images of one resized width and different heights share batches (ctpn_detect_submit_ragged); together with --decode gpu /
+    gpu-entropy the JPEG files are grouped by their RESIZED shapes, whatever their file sizes, layouts and orientations, and decoded into
+    the batch's canvas on the device (ctpn_decode_jpeg_files_ragged). Same result files.
+
   * with --crops DIR every detected line is also cut out as a rectified image of fixed height, `<stem>_<k>.jpg`, for a recogniser behind
     the detector (ctpn_crop_lines: on the device; batches decoded there are cropped where they lie, without fetching them).
 
@@ -116,6 +120,51 @@ def plan_ragged_batches(shapes, max_batch, waste=RAGGED_WASTE):
             else:
                 alone.append(members[0])
     return batches, alone
+
+
+PNG_LAYOUT, OTHER_LAYOUT = (-1, 0), (0, 0)      # plan_device_jobs: layouts of the files the JPEG decoder does not take
+
+
+def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE):
+    """The batches of the device path (_run_gpu). entries: [(name, file (h, w), layout, resize_im factor, resized (h, w))] of the images that
+    take the batched path; layout = (components, sampling | orientation) of a JPEG file the library takes, PNG_LAYOUT, or OTHER_LAYOUT
+    (Pillow). -> jobs = [(size, kind, f, rs, names)]. A pure function.
+    kind 'jpg' / 'png' / 'host': files of one FILE size (and, for JPEG, one layout and orientation), size = that (h, w), f = their factor,
+    rs = their resized shape -- one decode call each takes.
+    ragged: the JPEG files the library takes are planned with plan_ragged_batches on their RESIZED shapes first, whatever their file size,
+    layout and orientation: kind 'ragged', size = rs = the canvas (hc, wc), f = [(file h, file w, factor)] per name
+    (Context.decode_jpeg_ragged). What ends alone there, and every PNG and Pillow file, is size-grouped as without it."""
+    entries = list(entries)
+    jobs = []
+    if ragged:
+        jpegs = [e for e in entries if e[2][0] > 0 and e[4][0] >= 16]      # (a ragged image has at least one feature row)
+        batches, _ = plan_ragged_batches([e[4] for e in jpegs], batch, waste)
+        for (hc, wc), members in batches:
+            jobs.append(((hc, wc), "ragged", [(jpegs[i][1][0], jpegs[i][1][1], jpegs[i][3]) for i in members], (hc, wc), [jpegs[i][0] for i in members]))
+        batched = {jpegs[i][0] for _, members in batches for i in members}
+        entries = [e for e in entries if e[0] not in batched]
+    groups = {}
+    for name, (h, w), layout, f, rs in entries:
+        groups.setdefault((h, w, tuple(layout)), (f, rs, []))[2].append(name)
+    for (h, w, layout), (f, rs, members) in sorted(groups.items()):
+        for i in range(0, len(members), batch):
+            jobs.append(((h, w), "jpg" if layout[0] > 0 else ("png" if layout == PNG_LAYOUT else "host"), f, rs, members[i:i + batch]))
+    return jobs
+
+
+def check_ragged_options(decode="host", encode="host", png_encode="host", crops_dir=None, decode_procs=0, decode_pool=None):
+    """run(..., ragged=True) with these options: ValueError for the combinations that stay uniform. The process-pool decoder fills
+    shared-memory batches of one shape; the library's writers (encode / png_encode = 'gpu') and the crops take uniform device batches."""
+    if decode_procs > 0 or decode_pool is not None:
+        raise ValueError("ragged batches are built by the thread-pool decoder (decode='host') or on the device (decode='gpu' / 'gpu-entropy'): "
+                         "the process-pool decoder stays size-grouped")
+    if decode in ("gpu", "gpu-entropy"):
+        if encode != "host":
+            raise ValueError("ragged device decode does not combine with encode='gpu' / 'gpu-entropy': ctpn_write_annotated_files takes uniform batches")
+        if png_encode != "host":
+            raise ValueError("ragged device decode does not combine with png_encode='gpu': ctpn_write_annotated_png_files takes uniform batches")
+        if crops_dir is not None:
+            raise ValueError("ragged device decode does not combine with crops_dir: ctpn_crop_lines takes uniform batches")
 
 
 RPN_PARAM_NAMES = ("RPN_PRE_NMS_TOP_N", "RPN_POST_NMS_TOP_N", "RPN_NMS_THRESH", "RPN_MIN_SIZE")
@@ -255,7 +304,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
 
 
 def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
-             encode_entropy="host", png_encode="host"):
+             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -277,34 +326,35 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     device as host images, and device JPEG batches whose names end in .png -- are drawn, resized by 1 / scale and PNG-coded by the library
     at collect time (ctpn_write_annotated_png_files). "Host work by nature" holds for READING a PNG file (inflate is serial, un-filtering
     chains from row to row); writing one parallelises. The files are the library's own (Sub filter, one dynamic-Huffman block): they decode
-    to the pixels Pillow's files decode to, but are not byte-equal to them. Default 'host': Pillow, as before."""
+    to the pixels Pillow's files decode to, but are not byte-equal to them. Default 'host': Pillow, as before.
+    ragged (--ragged): the JPEG files the library takes are batched by their RESIZED shapes -- one width, different heights, whatever their file
+    sizes, layouts and orientations (plan_device_jobs) -- decoded into one canvas on the device (ctpn_decode_jpeg_files_ragged) and detected
+    from it (ctpn_detect_submit_ragged); annotated images are cut from the fetched canvas for the host writer. What ends alone, PNG batches
+    and Pillow's files stay size-grouped. The result files are the same."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
-    groups, singles = {}, []
+    singles = []
     t_plan = time.time()
     probed = B.jpeg_probe_files(names, read_threads)                          # the header scan: one call, C++ threads
     pngs = [i for i, nm in enumerate(names) if probed[i, 0] == 0 and nm.lower().endswith(".png")]
     png_info = dict(zip(pngs, B.png_probe_files([names[i] for i in pngs], read_threads).tolist())) if pngs else {}
-    PNG, OTHER = (-1, 0), (0, 0)                                              # layouts of the files the JPEG decoder does not take
+    entries = []
     for i, (name, pr) in enumerate(zip(names, probed.tolist())):
         if pr[0] > 0:
             (h, w), layout = (pr[0], pr[1]), (pr[2], pr[3])
         elif png_info.get(i, [0])[0] > 0:
-            (h, w), layout = tuple(png_info[i][:2]), PNG
+            (h, w), layout = tuple(png_info[i][:2]), PNG_LAYOUT
         else:
-            (h, w), layout = image_size(name), OTHER
+            (h, w), layout = image_size(name), OTHER_LAYOUT
         f = D.resize_factor((h, w), TextLineCfg.SCALE, TextLineCfg.MAX_SCALE)
         rs = (h, w) if f == 1.0 else resize_dims(h, w, f, f)
         s2 = _scale_for(rs)
         if int(round(rs[0] * s2)) == rs[0] and int(round(rs[1] * s2)) == rs[1]:
-            groups.setdefault((h, w, layout), (f, rs, []))[2].append(name)
+            entries.append((name, (h, w), layout, f, rs))
         else:
             singles.append(name)
-    jobs = []
-    for (h, w, layout), (f, rs, members) in sorted(groups.items()):
-        for i in range(0, len(members), batch):
-            jobs.append(((h, w), "jpg" if layout[0] > 0 else ("png" if layout == PNG else "host"), f, rs, members[i:i + batch]))
+    jobs = plan_device_jobs(entries, batch, ragged, ragged_waste)
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
         _set_tail_params(net, params)
@@ -371,6 +421,32 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     for k, ((h, w), kind, f, rs, members) in enumerate(jobs):
         png_prefetch(k + 1)
         imgs = None
+        scales = [f] * len(members)
+        if kind == "ragged":                           # f: (file h, file w, factor) per member; (h, w) and rs: the canvas
+            sizes, scales = [t[:2] for t in f], [t[2] for t in f]
+            try:
+                handle = None
+                if entropy == "device":
+                    try:
+                        handle = net.ctx.decode_jpeg_ragged(members, sizes, scales, h, w, entropy="device")
+                    except B.CtpnError as e:
+                        if e.code != B.CTPN_ERR_UNSUPPORTED:                   # (a progressive file in the batch: the host half's)
+                            raise
+                if handle is None:
+                    handle = net.ctx.decode_jpeg_ragged(members, sizes, scales, h, w)
+                (ptr, shape), heights = handle
+                net.ctx.detect_submit(device_ptr=ptr, shape=shape, heights=heights, slot=k & 1)
+                stats["gpu"] += len(members)
+                if write_images:
+                    canvas = net.ctx.jpeg_batch_fetch(ptr, shape)
+                    imgs = [canvas[i, :heights[i]] for i in range(len(members))]
+            except B.CtpnError as e:                                       # e.g. damaged entropy data: the same canvas from the host decoder
+                if e.code not in (B.CTPN_ERR_UNSUPPORTED, -1):
+                    raise
+                imgs = [_load(nm)[0] for nm in members]
+                canvas, heights = im_list_to_canvas(imgs)
+                net.ctx.detect_submit(images=canvas, heights=heights, slot=k & 1)
+                stats["host"] += len(members)
         if kind == "jpg":
             try:
                 ptr = None
@@ -413,7 +489,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.detect_submit(images=imgs, slot=k & 1)
             stats["host"] += len(members)
         for i, nm in enumerate(members):
-            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches else None, f)
+            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches else None, scales[i])
         if pending is not None:
             collect(pending)
         if crops_dir:
@@ -457,9 +533,12 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     on the device at collect time (write_crops); None (default): nothing changes.
     params: {name: value} of the detection tail (ctpn_set_param: RPN_* and the connector's names) for the ctx of this run; the connector's
     also reach the images that take the single-image path. None: the defaults.
-    ragged (host decode on the thread pool only; off by default): images of one resized width and different heights share batches
-    (plan_ragged_batches with ragged_waste; Context.detect_submit(..., heights=)) instead of one batch per resized shape. Same result
-    files. The device JPEG path decodes one size per call and stays size-grouped, as do its PNG batches and the process-pool decoder."""
+    ragged (off by default): images of one resized width and different heights share batches (plan_ragged_batches with ragged_waste;
+    Context.detect_submit(..., heights=)) instead of one batch per resized shape. Same result files. decode='host': from resized images
+    on the thread pool. decode='gpu' / 'gpu-entropy': the JPEG files the library takes are decoded into ragged canvases on the device
+    whatever their file sizes, layouts and orientations (Context.decode_jpeg_ragged; see _run_gpu); PNG batches, Pillow's files and what
+    ends alone stay size-grouped. Not with the process-pool decoder, and on the device path not with encode='gpu' / 'gpu-entropy',
+    png_encode='gpu' or crops_dir, which take uniform batches (check_ragged_options: ValueError)."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config(params)
     if params:
@@ -480,13 +559,13 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         raise ValueError("png_encode='gpu' writes the images of library-decoded batches: it needs decode='gpu'")
     if crops_dir is not None and decode != "gpu":
         raise ValueError("crops_dir cuts the lines out of the batches of the device path: it needs decode='gpu'")
-    if ragged and (decode == "gpu" or decode_procs > 0 or decode_pool is not None):
-        raise ValueError("ragged batches are built from resized images held on the host: decode='host' on the thread pool")
+    if ragged:
+        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool)
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
-                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode)
+                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -644,7 +723,8 @@ def build_parser():
                     help="(with --decode gpu) also write every detected line as a rectified crop <stem>_<k>.jpg of height --crop-height into DIR (ctpn_crop_lines)")
     ap.add_argument('--crop-height', type=int, default=32)
     ap.add_argument('--ragged', action='store_true',
-                    help="batch images of one resized width across heights (host decode only; same result files)")
+                    help="batch images of one resized width across heights (same result files); with --decode gpu / gpu-entropy the JPEG files "
+                         "are decoded into ragged canvases on the device whatever their file sizes (not with --encode gpu, --png-encode gpu, --crops)")
     ap.add_argument('--ragged-waste', type=float, default=RAGGED_WASTE, help="padded share of a ragged batch's rows at most")
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "

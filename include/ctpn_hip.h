@@ -382,6 +382,26 @@ int ctpn_debug_cvt_bf16(int device_id, const float* in, uint16_t* out, int n, in
 int ctpn_debug_lds_dma(int device_id, const uint8_t* src, size_t bytes, uint8_t* out_clobber, uint8_t* out_keep);
 int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio, const float* bias, int n, int h, int w,
                        int ci, int co, int precision, int impl, int fuse_pool, float* out_full, float* out_pool);
+/* impl 3 (split precision, no pool, out_full given): impl 1 with the dup_hi layout of the layer that feeds the LSTM projection -- the stored
+ * pixel is [hi | lo | hi]; out_full is hi + lo as always, and a third plane that is not bit-equal to the hi plane is CTPN_ERR_STATE.
+ *
+ * Which kernels one conv3x3 layer runs -- the plan launch_conv3x3 computes from the layer's shape and then follows (csrc/conv3x3_plan.h), so
+ * what this reports is what ctpn_debug_conv3x3 and the forward launch for that shape. Pure host arithmetic: no device is touched when
+ * cu_count > 0; cu_count 0 = the current device's CU count (CTPN_ERR_NODEVICE without one). One call covers the widths w_first ..
+ * w_first + w_count - 1 of an n x h x w map with ci -> co channels (the layer's channel counts in every precision): fuse_pool / keep_full as
+ * ctpn_debug_conv3x3's fuse_pool / out_full != NULL (without a pool the full map is always kept), dup_hi as the forward passes it for
+ * rpn_conv in split precision, conv_p64 / split_edge the ctx options of those names (split precision only; defaults 1, 1). Bias and ReLU are
+ * taken as present, as on every layer of the network. plans: w_count x CTPN_CONV_PLAN_INTS ints per width:
+ *   [0] main form   0 wr  1 p64  2 t64  3 p_flat  4 p_flat64  5 p_16x16  6 p_8x32  7 p_8x32_half  8 t_flat  9 t_16x16  10 t_8x32
+ *   [1] strip kind  0 none  1 edge  2 edge_pool  3 im2col     (the ragged right-hand columns of a 2D tiling)
+ *   [2] strip columns (0 without a strip)     [3] w_cover: columns [0, w_cover) are the main launch's, 0 = all
+ *   [4] 1 = edge strip in its deep form in the layer's own stream, 0 = forked onto the helper stream (the im2col strip always is)
+ *   [5] K split of an edge strip in waves (split precision: 3 or 6 by Ci; the 16-bit modes: 1); 0 without an edge strip
+ * ctpn_debug_conv3x3_form_name(kind, id): the short name above of main form (kind 0) / strip kind (kind 1) id, NULL out of range. */
+#define CTPN_CONV_PLAN_INTS 6
+int ctpn_debug_conv3x3_plan(int precision, int n, int h, int w_first, int w_count, int ci, int co, int fuse_pool, int keep_full, int dup_hi,
+                            int conv_p64, int split_edge, int cu_count, int* plans);
+const char* ctpn_debug_conv3x3_form_name(int kind, int id);
 /* TextDetector.detect (lib/text_connector/detectors.py:19-49) for ONE image with every step on the device -- score > 0.7 prefix and
  * boxes / scale (lines_prep_kernel), NMS 0.2 (nms_kernel), graph build / chains / line fit / filter_boxes (connect_kernel) -- i.e.
  * the device-connector form of the asynchronous detect path (option connect_device = 1). rois: r x 5 fp32 [score,x1,y1,x2,y2] in

@@ -31,24 +31,27 @@ def rel_err(got, ref):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# single layers through ctpn_debug_conv3x3: every kernel family of the split mode (Co = 64 non-persistent, 8 x 32 / 16 x 16 patches with and
-# without the fused pool, flat windows, stacked tile rows, half-tile tails), against the fp32 oracle op
+# single layers through ctpn_debug_conv3x3 in the split mode, against the fp32 oracle op. Which kernels a row runs is not a comment but the
+# library's own plan (ctpn_debug_conv3x3_plan) on 256 CUs, asserted: (main form, strip kind) of the launch that keeps the full map. These eight shapes cross the
+# Co = 64 persistent form, flat 64-pixel items and 8 x 32 patches with the half-tile tail, pooled and not, and no strip; every other form
+# of the mode, the edge kernels and their K split included, has its own case in tests/test_gpu_conv_forms.py
 # ---------------------------------------------------------------------------------------------------------------
-SPLIT_LAYERS = [
-    # n, h, w, ci, co, pool
-    (1, 20, 70, 64, 64, True),        # conv1_2's shape class: Co = 64, three K chunks over two input chunks
-    (2, 33, 45, 64, 64, False),
-    (2, 24, 66, 64, 128, False),      # conv2_1: 8 x 32 patches, ragged last column computed in the padded tile column
-    (1, 40, 50, 128, 128, True),      # conv2_2: pooled, 16 x 16 or 8 x 32 whichever tiles better
-    (2, 37, 56, 128, 256, False),     # flat windows
-    (3, 21, 23, 256, 256, False),     # stacked tile rows over the batch
-    (1, 18, 113, 256, 512, True),     # 16 x 16 patches, pooled, odd width
-    (2, 9, 14, 512, 512, False),      # tiny map: one flat tile, half-tile tail
-]
+SPLIT_LAYERS = {
+    # (n, h, w, ci, co, pool): (main form, strip kind)
+    (1, 20, 70, 64, 64, True): ("p64", "none"),               # conv1_2's shape class: Co = 64, three K chunks over two input chunks
+    (2, 33, 45, 64, 64, False): ("p64", "none"),
+    (2, 24, 66, 64, 128, False): ("p_flat64", "none"),        # conv2_1's channels; 66 + 2 <= 114 columns: flat, so no strip
+    (1, 40, 50, 128, 128, True): ("p_8x32_half", "none"),     # conv2_2: pooled
+    (2, 37, 56, 128, 256, False): ("p_flat64", "none"),
+    (3, 21, 23, 256, 256, False): ("p_flat64", "none"),
+    (1, 18, 113, 256, 512, True): ("p_8x32_half", "none"),    # pooled, odd width (a pooled layer takes no edge1 strip)
+    (2, 9, 14, 512, 512, False): ("p_flat64", "none"),        # tiny map
+}
 
 
-@pytest.mark.parametrize("n,h,w,ci,co,pool", SPLIT_LAYERS)
+@pytest.mark.parametrize("n,h,w,ci,co,pool", list(SPLIT_LAYERS))
 def test_split_conv_layer_is_fp32_class(n, h, w, ci, co, pool):
+    assert tuple(B.conv3x3_plan("split", n, h, w, ci, co, pool, True, cu_count=256)[:2]) == SPLIT_LAYERS[n, h, w, ci, co, pool]
     rng = np.random.default_rng(ci * 1000 + co + h)
     x = np.maximum(rng.standard_normal((n, h, w, ci)).astype(np.float32), 0) * 3.0
     wt = (rng.standard_normal((3, 3, ci, co)) * np.sqrt(2.0 / (9 * ci))).astype(np.float32)
@@ -67,10 +70,17 @@ def test_split_conv_layer_is_fp32_class(n, h, w, ci, co, pool):
     assert rel_err(full, f32.astype(np.float64)) < 2e-5
 
 
-@pytest.mark.parametrize("n,h,w,ci,co,pool", [(2, 24, 66, 64, 128, False), (1, 20, 70, 64, 64, True), (1, 18, 113, 256, 512, True), (2, 37, 56, 128, 256, False)])
+# (main form, strip kind) of the library's plan on 256 CUs, asserted
+FP16_LAYERS = {(2, 24, 66, 64, 128, False): ("wr", "none"), (1, 20, 70, 64, 64, True): ("wr", "none"), (1, 18, 113, 256, 512, True): ("p_8x32_half", "none"),
+               (2, 37, 56, 128, 256, False): ("p_flat64", "none")}
+
+
+@pytest.mark.parametrize("n,h,w,ci,co,pool", list(FP16_LAYERS))
 def test_fp16_conv_layer_tracks_oracle(n, h, w, ci, co, pool):
-    """The 16-bit kernels instantiated for fp16 (weights-in-registers, persistent, edge): 11 mantissa bits per operand and on the stored
-    result -- 2^-11 relative on the output rounding, well inside 2e-3 (bf16 holds 8e-3 on the same layers)."""
+    """The 16-bit kernels instantiated for fp16 (weights-in-registers, persistent; the edge kernels and every other form:
+    tests/test_gpu_conv_forms.py): 11 mantissa bits per operand and on the stored result -- 2^-11 relative on the output rounding, well
+    inside 2e-3 (bf16 holds 8e-3 on the same layers)."""
+    assert tuple(B.conv3x3_plan("fp16", n, h, w, ci, co, pool, True, cu_count=256)[:2]) == FP16_LAYERS[n, h, w, ci, co, pool]
     rng = np.random.default_rng(ci + co + w)
     x = np.maximum(rng.standard_normal((n, h, w, ci)).astype(np.float32), 0) * 3.0
     wt = (rng.standard_normal((3, 3, ci, co)) * np.sqrt(2.0 / (9 * ci))).astype(np.float32)

@@ -3,8 +3,8 @@ The result is DEFINED as what the image gives alone, so everything here is an eq
 rows, rois, roi counts, anchors, lines and line counts, in all four precisions.
 
 Shapes: w = 82 (W mod 16 = 2: the edge-column kernels) with heights 96, 80, 49, 16, 33 in a canvas of 96, and w = 144 with heights 96 and
-49, where the pooled conv2_2 takes the 16 x 16-patch form for the canvas and the 8 x 32 form for the 49-row image alone (c3_tiles2d,
-restated below). Random bytes below every image. Weights: tests/util.py's "biased" arena, on which every one of these images yields
+49, where the pooled conv2_2 takes the 16 x 16-patch form for the canvas and the 8 x 32 form for the 49-row image alone (asserted
+below through the library's plan function). Random bytes below every image. Weights: tests/util.py's "biased" arena, on which every one of these images yields
 proposals and text lines (asserted)."""
 import ctypes as C
 
@@ -54,11 +54,13 @@ def _tensors(ctx, names, info):
 
 
 def test_the_two_heights_of_w144_take_different_conv_forms():
-    """c3_tiles2d (csrc/conv3x3_base.h) restated: tiles of tw x 256 / tw pixels over the pooled conv2_2's 72-wide map"""
-    def tiles(h, w, tw):
-        return -(-w // tw) * -(-(h & ~1) // (256 // tw))
-    assert tiles(96 >> 1, 144 >> 1, 16) < tiles(96 >> 1, 144 >> 1, 32)            # the canvas: 16 x 16 patches
-    assert not tiles(49 >> 1, 144 >> 1, 16) < tiles(49 >> 1, 144 >> 1, 32)        # the 49-row image alone: 8 x 32
+    """the library's own plan (ctpn_debug_conv3x3_plan) of the pooled conv2_2 over the 72-wide map, kept and production form, on this device"""
+    for prec in PRECS:
+        for keep in (False, True):
+            canvas = B.conv3x3_plan(prec, 2, 96 >> 1, 144 >> 1, 128, 128, True, keep)
+            alone = B.conv3x3_plan(prec, 1, 49 >> 1, 144 >> 1, 128, 128, True, keep)
+            assert canvas.main == "p_16x16" and canvas.strip == "none", (prec, keep, canvas)      # the canvas: 16 x 16 patches
+            assert alone.main in ("p_8x32", "p_8x32_half") and alone.strip == "none", (prec, keep, alone)      # the 49-row image alone: 8 x 32
 
 
 @pytest.mark.parametrize("which", sorted(SETS))

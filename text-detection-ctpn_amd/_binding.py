@@ -4,6 +4,7 @@
 binding uses `ctypes`; the declarations below are a 1:1 transcription of the header and
 tests/test_abi.py checks that every symbol the header declares is exported.
 """
+import collections
 import ctypes as C
 import os
 import sys
@@ -111,6 +112,8 @@ def _declare(lib):
         "ctpn_debug_lds_dma": (C.c_int, [C.c_int, u8p, C.c_size_t, u8p, u8p]),
         "ctpn_debug_conv3x3": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, f32p, f32p]),
+        "ctpn_debug_conv3x3_plan": (C.c_int, [C.c_int] * 13 + [i32p]),
+        "ctpn_debug_conv3x3_form_name": (C.c_char_p, [C.c_int, C.c_int]),
         "ctpn_jpeg_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_jpeg_coef_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_decode": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint16), i32p]),
@@ -650,7 +653,7 @@ def debug_lds_dma(src, device_id=0):
     return a, b
 
 
-def debug_conv3x3(x, w_hwio, bias, precision="fp32", impl=1, fuse_pool=False, want_full=True, device_id=0):
+def debug_conv3x3(x, w_hwio, bias, precision="fp32", impl=1, fuse_pool=False, want_full=True, device_id=0, dup_hi=False):
     """Unit-test hook (ctpn_debug_conv3x3): returns (full or None, pooled or None) as dense fp32 NHWC."""
     lib = load_library()
     x = _f32(x); w_hwio = _f32(w_hwio); bias = _f32(bias)
@@ -659,10 +662,50 @@ def debug_conv3x3(x, w_hwio, bias, precision="fp32", impl=1, fuse_pool=False, wa
     full = np.zeros((n, h, w, co), np.float32) if want_full else None
     pooled = np.zeros((n, h // 2, w // 2, co), np.float32) if fuse_pool else None
     prec = precision_code(precision)
+    if dup_hi:      # impl 3: impl 1 with the [hi | lo | hi] pixel of the layer that feeds the LSTM projection (the library compares the planes)
+        assert impl == 1
+        impl = 3
     _check(lib.ctpn_debug_conv3x3(int(device_id), _ptr(x, C.c_float), _ptr(w_hwio, C.c_float), _ptr(bias, C.c_float), n, h, w, ci,
                                   co, prec, int(impl), 1 if fuse_pool else 0,
                                   _ptr(full, C.c_float) if want_full else None, _ptr(pooled, C.c_float) if fuse_pool else None))
     return full, pooled
+
+
+CONV_PLAN_INTS = 6      # CTPN_CONV_PLAN_INTS
+ConvPlan = collections.namedtuple("ConvPlan", "main strip cols w_cover deep ks")
+
+
+def conv3x3_form_names():
+    """(main form names, strip kind names) by id, as ctpn_debug_conv3x3_form_name gives them."""
+    lib = load_library()
+    out = []
+    for kind in (0, 1):
+        names, i = [], 0
+        while True:
+            s = lib.ctpn_debug_conv3x3_form_name(kind, i)
+            if s is None:
+                break
+            names.append(s.decode())
+            i += 1
+        out.append(names)
+    return tuple(out)
+
+
+def conv3x3_plan_sweep(precision, n, h, w_first, w_count, ci, co, pool, keep_full=True, dup_hi=False, conv_p64=1, split_edge=1, cu_count=0):
+    """ctpn_debug_conv3x3_plan: int32 array [w_count, CONV_PLAN_INTS] -- the plans of the widths w_first .. w_first + w_count - 1 (ids, see
+    conv3x3_form_names). cu_count 0 asks the current device; any other value needs no device."""
+    lib = load_library()
+    out = np.zeros((int(w_count), CONV_PLAN_INTS), np.int32)
+    _check(lib.ctpn_debug_conv3x3_plan(precision_code(precision), int(n), int(h), int(w_first), int(w_count), int(ci), int(co), 1 if pool else 0,
+                                       1 if keep_full else 0, 1 if dup_hi else 0, int(conv_p64), int(split_edge), int(cu_count), _ptr(out, C.c_int)))
+    return out
+
+
+def conv3x3_plan(precision, n, h, w, ci, co, pool, keep_full=True, dup_hi=False, conv_p64=1, split_edge=1, cu_count=0):
+    """The plan of one layer shape as a ConvPlan of names and numbers: (main, strip, cols, w_cover, deep, ks)."""
+    mains, strips = conv3x3_form_names()
+    p = [int(v) for v in conv3x3_plan_sweep(precision, n, h, w, 1, ci, co, pool, keep_full, dup_hi, conv_p64, split_edge, cu_count)[0]]
+    return ConvPlan(mains[p[0]], strips[p[1]], p[2], p[3], p[4], p[5])
 
 
 class Context:

@@ -1,6 +1,7 @@
 // C ABI of libctpn_hip.so, test hooks: ctpn_debug_* entry points that run one kernel on caller-supplied data, everything on the null stream.
 // Not on the product path.
 #include "ctx.h"
+#include "conv3x3_plan.h"
 
 extern "C" {
 
@@ -52,12 +53,17 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
   CTPN_HIP_TRY(hipSetDevice(device_id));
   const DType t = prec_dtype(precision);
   const bool split = t == DType::SPLIT;
-  if (impl != 0 && impl != 1) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: impl is 0 (im2col GEMM) or 1 (the product kernels)");
-  if (split && impl != 1) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: split precision exists in the tap-reuse kernels only (impl 1)");
+  if (impl != 0 && impl != 1 && impl != 3) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: impl is 0 (im2col GEMM), 1 (the product kernels) or 3 (1 with the dup_hi layout)");
+  if (split && impl == 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: split precision exists in the tap-reuse kernels only (impl 1, 3)");
+  if (impl == 3 && !split) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: dup_hi (impl 3) is a split-precision layout");
+  // impl 3: the full-resolution pixel is [hi | lo | hi] (what rpn_conv stores for the LSTM projection); the third plane must equal the first
+  const int dup = impl == 3 ? 1 : 0;
+  if (dup && (fuse_pool || !out_full)) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: impl 3 stores the full-resolution map only");
+  if (dup) impl = 1;
   const int es = split ? 2 : dtype_bytes(t);                 // bytes per stored scalar
   const int cin_p = split ? 2 * ci : ci, cout_p = split ? 2 * co : co;      // scalars per pixel: split precision stores [hi | lo] planes
   const int Hp = h + 2, Wp = w + 2, ho = h / 2, wo = w / 2;
-  const size_t in_elems = ((size_t)n * Hp * Wp + act_slack_pixels(w)) * cin_p, out_elems = (size_t)n * Hp * Wp * cout_p, pool_elems = (size_t)n * (ho + 2) * (wo + 2) * cout_p;
+  const size_t in_elems = ((size_t)n * Hp * Wp + act_slack_pixels(w)) * cin_p, out_elems = (size_t)n * Hp * Wp * (cout_p + (dup ? co : 0)), pool_elems = (size_t)n * (ho + 2) * (wo + 2) * cout_p;
   const int co_pad = (co + 127) / 128 * 128;
   std::vector<char> hin(in_elems * es, 0);
   for (int in = 0; in < n; ++in) for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) for (int c = 0; c < ci; ++c) {
@@ -97,7 +103,7 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
   bool host_pool = false;
   if (!rc) {
     if (impl == 1) {
-      rc = launch_conv3x3(d_in, d_wt, d_b, (out_full || !fuse_pool) ? d_out : nullptr, fuse_pool ? d_pool : nullptr, t, n, h, w, ci, co, 1, s, 0);
+      rc = launch_conv3x3(d_in, d_wt, d_b, (out_full || !fuse_pool) ? d_out : nullptr, fuse_pool ? d_pool : nullptr, t, n, h, w, ci, co, 1, s, dup);
     } else {
       // impl 0: the im2col GEMM (igemm.hip) as an independent reference of the same layer; its pool is taken on the host from the stored map
       IGemm g{};
@@ -108,12 +114,13 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
     }
   }
   if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_debug_conv3x3: kernel failed");
-  auto fetch = [&](void* dsrc, int H2, int W2, float* dst) -> int {
-    const size_t elems = (size_t)n * (H2 + 2) * (W2 + 2) * cout_p;
+  auto fetch = [&](void* dsrc, int H2, int W2, float* dst, int dup_plane) -> int {
+    const int pitch = cout_p + (dup_plane ? co : 0);
+    const size_t elems = (size_t)n * (H2 + 2) * (W2 + 2) * pitch;
     std::vector<char> tmp(elems * es);
     CTPN_HIP_TRY(hipMemcpy(tmp.data(), dsrc, elems * es, hipMemcpyDeviceToHost));
     for (int in = 0; in < n; ++in) for (int y = 0; y < H2; ++y) for (int x = 0; x < W2; ++x) for (int c = 0; c < co; ++c) {
-      const size_t o = (((size_t)in * (H2 + 2) + y + 1) * (W2 + 2) + x + 1) * cout_p + c;
+      const size_t o = (((size_t)in * (H2 + 2) + y + 1) * (W2 + 2) + x + 1) * pitch + c;
       float v;
       if (t == DType::F32) std::memcpy(&v, &tmp[o * 4], 4);
       else {
@@ -122,6 +129,7 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
         else {
           v = host_bf16_to_f32(b);
           if (split) { uint16_t l; std::memcpy(&l, &tmp[(o + co) * 2], 2); v += host_bf16_to_f32(l); }
+          if (dup_plane && std::memcmp(&tmp[(o + 2 * co) * 2], &b, 2) != 0) return fail(CTPN_ERR_STATE, "ctpn_debug_conv3x3: the dup_hi plane differs from the hi plane");
         }
       }
       dst[(((size_t)in * H2 + y) * W2 + x) * co + c] = v;
@@ -132,15 +140,42 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
     std::vector<float> full_tmp;
     float* fdst = out_full;
     if (!fdst) { full_tmp.resize((size_t)n * h * w * co); fdst = full_tmp.data(); }
-    rc = fetch(d_out, h, w, fdst);
+    rc = fetch(d_out, h, w, fdst, dup);
     if (!rc && host_pool && out_pool)
       for (int in = 0; in < n; ++in) for (int y = 0; y < ho; ++y) for (int x = 0; x < wo; ++x) for (int c = 0; c < co; ++c) {
         auto at = [&](int yy, int xx) { return fdst[(((size_t)in * h + yy) * w + xx) * co + c]; };
         out_pool[(((size_t)in * ho + y) * wo + x) * co + c] = std::max(std::max(at(2 * y, 2 * x), at(2 * y, 2 * x + 1)), std::max(at(2 * y + 1, 2 * x), at(2 * y + 1, 2 * x + 1)));
       }
   }
-  if (!rc && out_pool && fuse_pool && !host_pool) rc = fetch(d_pool, ho, wo, out_pool);
+  if (!rc && out_pool && fuse_pool && !host_pool) rc = fetch(d_pool, ho, wo, out_pool, 0);
   return rc;
 }
+
+// The plan of launch_conv3x3 (conv3x3_plan.h) for the widths w_first .. w_first + w_count - 1 of one layer: what ctpn_debug_conv3x3 and the
+// forward would launch for that shape. Host arithmetic only; a device is asked for its CU count when cu_count is 0.
+int ctpn_debug_conv3x3_plan(int precision, int n, int h, int w_first, int w_count, int ci, int co, int fuse_pool, int keep_full, int dup_hi,
+                            int conv_p64, int split_edge, int cu_count, int* plans) {
+  if (!plans || w_count <= 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_plan: no output");
+  if (precision < CTPN_PREC_FP32 || precision > CTPN_PREC_SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_plan: unknown precision");
+  const DType t = prec_dtype(precision);
+  if (n <= 0 || h <= 0 || w_first <= 0 || w_first > 0x7fffffff - w_count || ci <= 0 || ci % (t == DType::F32 ? 32 : 64) != 0 || co <= 0 || co % (t == DType::F32 ? 4 : 8) != 0)
+    return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_plan: shape out of range (Ci a multiple of 32 / 64, Co of 4 / 8)");
+  if (dup_hi && t != DType::SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_plan: dup_hi is a split-precision layout");
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_plan: cu_count is a CU count, or 0 for the current device's");
+  if (cu_count == 0) {
+    if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_conv3x3_plan: cu_count 0 asks the current device, and no HIP device is visible");
+    int dev = 0, rc;
+    if ((rc = current_device(dev)) || (rc = device_cu_count(dev, cu_count))) return rc;
+  }
+  for (int i = 0; i < w_count; ++i) {
+    const C3Plan p = c3_plan(t, n, h, w_first + i, ci, co, fuse_pool != 0, keep_full != 0 || !fuse_pool, dup_hi, true, true, (conv_p64 ? 1 : 0) | (split_edge ? 2 : 0), cu_count);
+    if (p.main_form == C3M_NONE) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_plan: no kernel for this shape (split precision: Co <= 64 or a multiple of 128)");
+    int* o = plans + (size_t)i * CTPN_CONV_PLAN_INTS;
+    o[0] = p.main_form; o[1] = p.strip; o[2] = p.strip_cols; o[3] = p.w_cover; o[4] = p.deep; o[5] = p.edge_ks;
+  }
+  return CTPN_OK;
+}
+
+const char* ctpn_debug_conv3x3_form_name(int kind, int id) { return kind == 0 ? c3_main_name(id) : (kind == 1 ? c3_strip_name(id) : nullptr); }
 
 }  // extern "C"

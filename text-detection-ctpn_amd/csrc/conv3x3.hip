@@ -76,79 +76,49 @@ bool conv1_fusable(DType t, int n, int h, int w, int ci, int co, bool pool, bool
 // batch's q-image (conv3x3_wr_kernel FUSE); `in` (conv1_1's map) is not touched
 int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out, void* pool_out, DType t, int n, int h, int w,
                    int ci, int co, int relu, hipStream_t s, int dup_hi, const void* q1, const void* q1_frags, int split_opts) {
-  const int p64 = split_opts & 1;
   const int bke = (t == DType::F32) ? 32 : 64;
   if (ci <= 0 || ci % bke != 0) return fail(CTPN_ERR_ARG, "conv3x3: Ci must be a multiple of the 128-byte strip");
   const int epc = (t == DType::F32) ? 4 : 8;
   if (co % epc != 0) return fail(CTPN_ERR_ARG, "conv3x3: Co must be a multiple of a 16-byte chunk");
   if (!out && !pool_out) return fail(CTPN_ERR_ARG, "conv3x3: no output");
   if (dup_hi && t != DType::SPLIT) return fail(CTPN_ERR_ARG, "conv3x3: dup_hi is a split-precision layout");
-  const bool half = dtype_is_half(t);
   Conv3 g{};
   g.in = in; g.wt = wt; g.bias = bias; g.out = out; g.pool_out = pool_out;
   g.N = n; g.H = h; g.W = w; g.Ci = ci; g.Co = co; g.relu = relu;
-  g.in_pitch = ci; g.out_pitch = co; g.a_wrap = 0; g.dup_hi = 0; g.opt_p64 = p64; g.opt_small = 1;
+  g.in_pitch = ci; g.out_pitch = co; g.a_wrap = 0; g.dup_hi = 0;
   if (t == DType::SPLIT) {
     if (!bias) return fail(CTPN_ERR_ARG, "conv3x3 (split precision): bias required");
     g.Ci = 3 * ci; g.in_pitch = 2 * ci; g.a_wrap = 2 * ci / 64; g.out_pitch = (dup_hi ? 3 : 2) * co; g.dup_hi = dup_hi ? 1 : 0;
   }
   const bool pool = pool_out != nullptr;
-  // Ragged last tile column (W = 225 = 7 * 32 + 1 wastes an eighth of the tiles on one pixel column): the 2D launch covers
-  // the multiple of 32 and the few remaining columns go through the im2col kernel (igemm.hip) as a [N*H*r] x Co GEMM (fp32).
-  // 16-bit modes: one or two columns beyond a multiple of 16 go through conv3x3_edge_kernel, which shares the CUs with the main
-  // launch (W = 113 then tiles as 7 x 16 instead of 8 x 16); otherwise up to 8 columns beyond a multiple of 32 go through igemm.
-  // Split precision (round 6): the same edge kernel over [hi | lo] planes (three K blocks per tap); no igemm strip there.
+  // Everything that depends on the layer's shape -- the main kernel, which ragged columns go to a strip and through which kernel, in the
+  // layer's stream or forked, the edge kernel's K split -- is the plan's (conv3x3_plan.h; ctpn_debug_conv3x3_plan reports the same struct)
   const bool split = t == DType::SPLIT;
-  const bool half_or_split = half || (split && (split_opts & 2) != 0);
-  const bool can_strip = !pool && !c3_flat_ok(g, pool) && w > 32 && out;
-  const bool edge = can_strip && half_or_split && bias && co % 64 == 0 && w % 16 >= 1 && w % 16 <= 2;
-  // 16-bit layers with a fused pool and no full-resolution output (conv1_2: W = 900 = 28 * 32 + 4; conv2_2: 450 = 28 * 16 + 2): two or
-  // four columns beyond the main launch's tile width go through the pooled form of the edge kernel (whole pooled pixels lie inside them)
-  const bool wr_layer = half && ci == 64 && (co == 64 || co == 128) && bias && relu;
-  const int rp = w % (wr_layer ? 32 : 16);
-  // (when the full-resolution map is kept as well -- keep_acts -- the same columns also go through the plain edge kernel: both
-  // forms accumulate in the same order, so the stored pool stays the exact max of the stored map and equal to the production path's)
-  // NOT for conv1_2 (Ci = Co = 64 with the pool): since conv1_1 is computed inside its window stage the persistent workgroups fill 456 of a
-  // SIMD's 512 registers, ONE edge wave fits next to them instead of three, and the strip -- which also needs conv1_1 for its own columns
-  // first -- ended 15 us AFTER the main launch instead of inside it, its one-wave workgroups crowding onto the CUs of the previous batch's NMS
-  // (1.3 ms instead of 0.54). The padded 29th tile column costs the main launch 3.5 %; the decision depends on the layer's shape only, so the
-  // stored (keep_acts) form takes the same columns through the same kernel family.
-  const bool conv1_2_like = wr_layer && co == 64 && pool;
-  const bool edge_pool = !conv1_2_like && pool && half_or_split && bias && co % 64 == 0 && w > 64 && h >= 2 && (w & 1) == 0 && (rp == 2 || rp == 4);
-  const int r = edge_pool ? rp : (edge ? w % 16 : w % 32);
-  // (which columns go to a strip depends on the layer's shape only, never on the batch: the edge kernel and the main kernels sum K in
-  // different orders, and a batch must reproduce its images run alone bit for bit)
-  bool strip = edge_pool || (can_strip && (edge || (!split && r >= 1 && r <= 8)));
-  if (strip) g.w_cover = w - r;
+  int dev = 0, ncu = 0, rc;
+  if ((rc = current_device(dev)) || (rc = device_cu_count(dev, ncu))) return rc;
+  const C3Plan plan = c3_plan(t, n, h, w, ci, co, pool, out != nullptr, dup_hi, relu != 0, bias != nullptr, split_opts, ncu);
+  if (plan.main_form == C3M_NONE) return fail(CTPN_ERR_ARG, "conv3x3 (split precision): Co must be <= 64 or a multiple of 128, with ReLU");
+  const bool strip = plan.strip != C3S_NONE, edge = plan.strip == C3S_EDGE, edge_pool = plan.strip == C3S_EDGE_POOL;
+  const int r = plan.strip_cols;
+  g.w_cover = plan.w_cover;
   if (q1) {
     if (!conv1_fusable(t, n, h, w, ci, co, pool, out != nullptr) || !q1_frags || strip) return fail(CTPN_ERR_ARG, "conv3x3: the fused conv1_1 form is conv1_2's pooled 16-bit launch");
     g.q1 = q1; g.q1_frags = q1_frags;
   }
-  int rc;
   // The strip (a few dozen workgroups) runs on its own stream, forked after the previous layer and joined before the next,
   // so it shares the machine with the main launch instead of adding 35-50 us of a nearly empty GPU per layer.
   static hipStream_t sstream[16] = {nullptr};
   static hipEvent_t ev_fork[16] = {nullptr}, ev_join[16] = {nullptr};
   static std::mutex strip_mu[16];     // the helper stream and its two events are per device, shared by every ctx on it
-  int dev = 0;
   std::unique_lock<std::mutex> strip_lock;
-  // One or two images: the edge kernel runs in the layer's own stream, behind the main launch, in its DEEP form (conv3x3_edge.h) -- no fork,
-  // no join. WHICH columns it takes is still a function of the layer's shape alone, and the deep form issues the same MFMAs in the same
-  // order, so a batch and its images run alone still agree bit for bit.
-  // Split precision, any batch: in the stream as well. Beside the main launch (forked, in front of it or behind it) the one-wave workgroups
-  // run for as long as the main launch does -- its two waves per SIMD hold 2 x 183 .. 246 of the 512 registers, the edge waves take the places
-  // of main workgroups that then start late -- and end 60 .. 270 us after it: -3 % images/s against a padded tile column. Behind the main
-  // launch on an empty machine the deep form takes 30 .. 60 us per layer: +1.8 % (tools/r6_split_edge_ab.sh, one context per process).
-  const bool instream = strip && (edge || edge_pool) && (n <= 2 || split);
+  const bool instream = strip && plan.deep != 0;      // the edge kernels' deep form, behind the main launch: no fork, no join
   auto run_edge = [&](void* dst, bool pooled) -> int {
     hipStream_t es = instream ? s : sstream[dev];
-    if (split) return c3_edge_split(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, true, dup_hi);      // always the deep form
+    if (split) return c3_edge_split(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, true, dup_hi, plan.edge_ks);      // always the deep form
     return t == DType::F16 ? c3_edge_f16(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, instream)
                            : c3_edge_bf16(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, instream);
   };
   if (strip && !instream) {
-    CTPN_HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) return fail(CTPN_ERR_ARG, "conv3x3: device index out of range");
     strip_lock = std::unique_lock<std::mutex>(strip_mu[dev]);   // held until the join is enqueued (event waits capture the record made before them)
     if (!sstream[dev]) {
       CTPN_HIP_TRY(hipStreamCreateWithFlags(&sstream[dev], hipStreamNonBlocking));
@@ -172,10 +142,10 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
     CTPN_HIP_TRY(hipEventRecord(ev_join[dev], sstream[dev]));
   }
   switch (t) {
-    case DType::F32: rc = c3_run_f32(g, pool, s); break;
-    case DType::BF16: rc = c3_run_bf16(g, pool, wr_layer, s); break;
-    case DType::F16: rc = c3_run_f16(g, pool, wr_layer, s); break;
-    default: rc = c3_run_split(g, pool, s); break;
+    case DType::F32: rc = c3_run_f32(g, pool, plan.main_form, s); break;
+    case DType::BF16: rc = c3_run_bf16(g, pool, plan.main_form, s); break;
+    case DType::F16: rc = c3_run_f16(g, pool, plan.main_form, s); break;
+    default: rc = c3_run_split(g, pool, plan.main_form, s); break;
   }
   if (rc) return rc;
   if (instream) {

@@ -39,10 +39,9 @@
 #include <utility>
 
 #include "common.h"
+#include "conv3x3_plan.h"
 
 namespace ctpn {
-
-constexpr int C3_LDS_MAX = 160 * 1024;       // a CU's LDS: the budget of every launch here, and what raise_dynamic_lds (common.h) asks for per kernel
 
 typedef ctpn_f32x16 c3_f32x16;
 typedef __attribute__((ext_vector_type(4))) float c3_f32x4;
@@ -164,15 +163,12 @@ struct Conv3 {
   // input pixel (2 x), a_wrap = first 64-channel K chunk that re-reads the hi plane (chunk c -> pixel chunk c - a_wrap), out_pitch = bf16
   // elements per output pixel (2 Co, or 3 Co with dup_hi: [hi | lo | hi]). Non-split launches: in_pitch = Ci, out_pitch = Co.
   int in_pitch, a_wrap, out_pitch, dup_hi;
-  // tuning options (ctpn_set_option; same results either way): -1 = the kernel family's default
   int opt_ahead;              // unused since round 6 (every persistent form reads ahead); kept so that the kernel-argument layout does not move
-  int opt_small;              // flat windows at one image per call: 0 = half tiles of 128 pixels (round 3), else 64-pixel x 128-channel items (round 6)
-  int opt_p64;                // Co = 64 layers outside the weights-in-registers kernel: 0 = the non-persistent kernel, else conv3x3_p_kernel<.., BN_T = 64>
+  int unused_[2];             // two former tuning options; what they chose is the plan's now (conv3x3_plan.h, which the launchers follow: no kernel and no
+                              // launcher reads a choice from this struct). Kept, like opt_ahead, so that the kernel-argument layout does not move
   // conv1_2 with conv1_1 computed in its window stage (conv3x3_wr_kernel FUSE): the batch's q-image and conv1_1's fragments; `in` is unused
   const void* q1; const void* q1_frags;
 };
-
-constexpr int C3_BM = 256;
 
 // 16 x 16 patches: a 32-pixel MFMA tile is two patch rows of 16. Lanes 16..31 take the second row ROTATED by two columns
 // (lane 16 + k owns column (k + 14) & 15): with the 18-pixel LDS row pitch that makes the LDS row of lane l congruent to l
@@ -180,34 +176,17 @@ constexpr int C3_BM = 256;
 // busy cycles in SQ_LDS_BANK_CONFLICT on the conv4 layers).
 __device__ __forceinline__ int c3_tw16_col(int l31) { return (l31 & 16) ? ((l31 - 2) & 15) : l31; }
 
-// pixels the 2D tiling has to cover: a fused 2x2 VALID pool that does not keep the full-resolution map never reads an
-// odd last row / column (150 x 225 -> 75 x 112 uses 150 x 224), which for W = 225 = 7 * 32 + 1 removes a whole tile column
-static inline void c3_extent(const Conv3& g, bool pool, int& he, int& we) {
-  he = (pool && !g.out) ? (g.H & ~1) : g.H;
-  we = (pool && !g.out) ? (g.W & ~1) : g.W;
-  if (g.w_cover > 0 && g.w_cover < we) we = g.w_cover;
-}
-static inline long long c3_tiles2d(const Conv3& g, bool pool, int tw) {
-  int he, we;
-  c3_extent(g, pool, he, we);
-  const int th = C3_BM / tw;
-  return (long long)((we + tw - 1) / tw) * ((he + th - 1) / th);
-}
-
-// flat windows need 256 + 2(W+2) + 2 rows per buffer; they must fit LDS twice next to nb weight strips
-static inline bool c3_flat_ok(const Conv3& g, bool pool, int nb = 3) {
-  const int flat_rows = (C3_BM + 2 * (g.W + 2) + 2 + 7) & ~7;
-  const int bias_bytes = ((g.Co + 127) / 128) * 128 * 4;      // the persistent kernel keeps the bias vector in LDS as well
-  return !pool && (g.W + 2) <= 114 && (2 * flat_rows * 128 + nb * 128 * 128 + bias_bytes) <= C3_LDS_MAX;
-}
+// the tiling helpers of conv3x3_plan.h on a launch argument (the plan and the launchers count the same tiles)
+static inline void c3_extent(const Conv3& g, bool pool, int& he, int& we) { c3_extent_of(g.H, g.W, pool, g.out != nullptr, g.w_cover, he, we); }
 
 // ---- per-type entry points: one translation unit each (conv3x3_<type>.hip), called by launch_conv3x3 (conv3x3.hip) ----
-int c3_run_f32(const Conv3& g, bool pool, hipStream_t s);                    // exact-fp32 MFMA kernels
-int c3_run_bf16(const Conv3& g, bool pool, bool wr, hipStream_t s);          // wr: the weights-in-registers kernel (Ci = 64)
-int c3_run_f16(const Conv3& g, bool pool, bool wr, hipStream_t s);
-int c3_run_split(const Conv3& g, bool pool, hipStream_t s);                  // (hi, lo) bf16 planes, three MFMA terms
+// (form: the plan's main_form, C3Main; ks: the plan's edge_ks)
+int c3_run_f32(const Conv3& g, bool pool, int form, hipStream_t s);          // exact-fp32 MFMA kernels
+int c3_run_bf16(const Conv3& g, bool pool, int form, hipStream_t s);         // C3M_WR: the weights-in-registers kernel (Ci = 64)
+int c3_run_f16(const Conv3& g, bool pool, int form, hipStream_t s);
+int c3_run_split(const Conv3& g, bool pool, int form, hipStream_t s);        // (hi, lo) bf16 planes, three MFMA terms
 int c3_edge_bf16(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep);
 int c3_edge_f16(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep);
-int c3_edge_split(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep, int dup_hi);
+int c3_edge_split(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep, int dup_hi, int ks);
 
 }  // namespace ctpn

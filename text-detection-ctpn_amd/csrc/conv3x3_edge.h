@@ -212,7 +212,7 @@ __global__ __launch_bounds__(64 * KS, DEEP ? 2 : 6) void conv3x3_edge_kernel(Con
 // r edge columns [w - r, w) of an h x w layer; pooled: r even, w - r even, `out` is the pooled map ((h / 2 + 2) x (w / 2 + 2) bordered)
 template <typename H, bool SPLIT = false>
 static int c3_launch_edge(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r,
-                          bool pooled, hipStream_t s, bool deep, int dup_hi = 0) {
+                          bool pooled, hipStream_t s, bool deep, int dup_hi = 0, int ks = 1) {
   ConvEdge e{};
   e.in = in; e.wt = wt; e.bias = bias; e.out = out; e.H = h; e.W = w; e.Ci = ci; e.Co = co; e.rx0 = w - r; e.rw = r; e.relu = relu;
   e.in_pitch = SPLIT ? 2 * ci : ci; e.out_pitch = SPLIT ? (dup_hi ? 3 : 2) * co : co; e.dup_hi = SPLIT && dup_hi ? 1 : 0;
@@ -222,8 +222,8 @@ static int c3_launch_edge(const void* in, const void* wt, const float* bias, voi
   const long long nblk = ((e.M + per_wave - 1) / per_wave) * (co / 64);
   if (nblk <= 0 || nblk > 0x7fffffffLL || e.M > 0x7fffffffLL || !bias) return fail(CTPN_ERR_ARG, "conv3x3 edge: problem out of range");
   if constexpr (SPLIT) {
-    // K split over waves, by Ci alone: S = 27 Ci / 16 K steps = 108 / 216 / 432 for Ci = 64 / 128 / 256 -> 3 / 6 / 6 waves of 36 / 36 / 72 steps
-    const int S = 27 * (ci / 16), ks = S % 24 == 0 && S / 6 >= 36 ? 6 : (S % 12 == 0 && S / 3 >= 36 ? 3 : 1);
+    // K split over waves: ks = the plan's edge_ks (c3_plan: 3 or 6 by Ci alone)
+    if ((ks != 1 && ks != 3 && ks != 6) || (27 * (ci / 16)) % (4 * ks) != 0) return fail(CTPN_ERR_ARG, "conv3x3 edge: the K split is 1, 3 or 6 waves of whole rounds of four K steps");
     if (deep && ks > 1) {
       if (ks == 6) {
         if (pooled) hipLaunchKernelGGL((conv3x3_edge_kernel<H, true, true, true, 6>), dim3((unsigned)nblk), dim3(64 * 6), 0, s, e);

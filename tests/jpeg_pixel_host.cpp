@@ -32,15 +32,12 @@ extern "C" int jpeg_pixels_host(const int16_t* coef, const uint16_t* qt3x64, con
         const uint16_t* q = qt3x64 + 64 * c;
         int ws[8][8], x[8], o[8];
         for (int t = 0; t < 8; ++t) {                      // pass 1: thread t takes column t
-          for (int k = 0; k < 8; ++k) x[k] = (int)blk[8 * k + t] * (int)q[8 * k + t];
-          jidct_1d(x, o, 13 - 2);
+          jidct_pass1(blk, q, true, t, o);
           for (int k = 0; k < 8; ++k) ws[k][t] = o[k];
         }
         for (int t = 0; t < 8; ++t) {                      // pass 2: thread t takes row t
           for (int k = 0; k < 8; ++k) x[k] = ws[t][k];
-          jidct_1d(x, o, 13 + 2 + 3);
-          uint8_t* dst = planes.data() + g.plane_off[c] + ((long long)(by * 8 + t) * (g.bw[c] * 8) + bx * 8);
-          for (int k = 0; k < 8; ++k) { int v = o[k] + 128; dst[k] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+          jidct_pass2(planes.data() + g.plane_off[c] + ((long long)(by * 8 + t) * (g.bw[c] * 8) + bx * 8), true, x);
         }
       }
   for (int y = 0; y < g.oh; ++y)                           // the colour kernel: one turned-image pixel at a time (jpeg_orient: EXIF orientation)

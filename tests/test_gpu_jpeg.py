@@ -36,6 +36,22 @@ def test_device_decode_equals_pillow(ctx, case):
     assert d.size == 0, "%d bytes differ, first at %s: %d vs %d" % (len(d), d[0], got[tuple(d[0])], want[tuple(d[0])])
 
 
+@pytest.mark.parametrize("entropy", ["host", "device"])
+def test_idct_workgroups_with_dead_lanes_equal_pillow(ctx, entropy):
+    """The IDCT passes (csrc/jpeg_pixel.h) take a lane's liveness as an argument: a lone 8 x 8 single-component file is 1 live block and 31
+    dead ones in its workgroup; three 8 x 24 4:2:0 files are 3 x 12 blocks, a full workgroup and one of 4 live blocks whose first block
+    continues the third image. No other test decodes these shapes."""
+    lone = encode(scene(8, 8, 3, True), 90)
+    ptr, shape = ctx.decode_jpeg_batch([lone], entropy=entropy)
+    assert shape == (1, 8, 8) and np.array_equal(ctx.jpeg_batch_fetch(ptr, shape)[0], pillow_bgr(lone))
+    three = [encode(scene(8, 24, 4 + i), 90, 2) for i in range(3)]
+    ptr, shape = ctx.decode_jpeg_batch(three, 8, 24, entropy=entropy)
+    got = ctx.jpeg_batch_fetch(ptr, shape)
+    assert shape == (3, 8, 24)
+    for i, d in enumerate(three):
+        assert np.array_equal(got[i], pillow_bgr(d)), i
+
+
 def test_device_decode_equals_the_committed_vectors(ctx, golden_dir):
     """tests/golden/jpeg_cases.npz: files and libjpeg-turbo's pixels as committed (independent of the Pillow installed on this box)."""
     g = np.load(os.path.join(golden_dir, "jpeg_cases.npz"))

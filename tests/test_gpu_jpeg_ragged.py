@@ -80,6 +80,19 @@ def test_canvas_equals_the_uniform_call_on_every_file(ctx, lone, tmp_path, entro
             assert ctx.jpeg_entropy_device_stats()["device"] == 5
 
 
+@pytest.mark.parametrize("entropy", ["host", "device"])
+def test_one_workgroup_over_two_small_images_equals_pillow(ctx, entropy):
+    """16 x 16 gray (4 blocks) and 24 x 16 4:2:0 (8 + 2 + 2 blocks) at factor 1: the IDCT's one workgroup holds both images and 16 dead
+    lanes' blocks, which load and store nothing (csrc/jpeg_pixel.h). No other test decodes these shapes."""
+    from util_jpeg import pillow_bgr
+    files = [encode(scene(16, 16, 5, True), 90), encode(scene(24, 16, 6), 90, 2)]
+    (ptr, shape), heights = ctx.decode_jpeg_ragged(files, [(16, 16), (24, 16)], [1.0, 1.0], 24, 16, entropy=entropy)
+    assert shape == (2, 24, 16) and tuple(heights) == (16, 24)
+    got = ctx.jpeg_batch_fetch(ptr, shape)
+    assert np.array_equal(got[0, :16], pillow_bgr(files[0])) and not got[0, 16:].any()
+    assert np.array_equal(got[1], pillow_bgr(files[1]))
+
+
 @pytest.mark.parametrize("prec", ["bf16", "fp32"])
 def test_live_canvas_feeds_the_detector(weights, lone, prec):
     """detect_submit on the live device canvas against detect_ragged on the fetched host canvas: rois, anchors and lines in modes H and O, with

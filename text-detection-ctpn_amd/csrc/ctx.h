@@ -444,5 +444,7 @@ int annotate_batch(ctpn_ctx* c, const std::string& who, const char* format, Stag
 // a finished file onto the disk (on worker threads: nothing may leave it; st, msg: why it failed); the report of a call's first failed image
 void write_file(const char* path, const uint8_t* data, size_t bytes, int& st, std::string& msg);
 int first_failure(const char* who, const std::vector<int>& st, const std::vector<std::string>& msg);
+bool jpeg_read_file(const char* path, std::vector<uint8_t>& buf, size_t limit = 0);      // api_input.hip: a whole file (limit: its first bytes only); false if it cannot be read
+void jpeg_layout8(const JpegGeom& g, int* layout8);                                      // api_input.hip: the eight ints ctpn_jpeg_entropy_decode describes a file's layout with
 
 }  // namespace ctpn

@@ -518,27 +518,14 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
   const int by = (int)(b / g.bw[c]), bx = (int)(b - (long long)by * g.bw[c]);
   const int16_t* blk = coef + (long long)img * g.coef_per_img + g.coef_off[c] + b * 64;
   const uint16_t* q = qt + ((long long)img * 3 + c) * 64;
-  // pass 1: column t (elements t, t + 8, ...), dequantised
   int x[8], o[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) x[k] = live ? (int)blk[8 * k + t] * (int)q[8 * k + t] : 0;
-  jidct_1d(x, o, 13 - 2);
+  jidct_pass1(blk, q, live, t, o);
 #pragma unroll
   for (int k = 0; k < 8; ++k) ws[lb][k][t] = o[k];                      // ws[row][col]
   __syncthreads();
-  // pass 2: row t
 #pragma unroll
   for (int k = 0; k < 8; ++k) x[k] = ws[lb][t][k];
-  jidct_1d(x, o, 13 + 2 + 3);
-  if (!live) return;
-  uint32_t lo = 0, hi = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int v = o[k] + 128; v = v < 0 ? 0 : (v > 255 ? 255 : v); lo |= (uint32_t)v << (8 * k);
-    int u = o[k + 4] + 128; u = u < 0 ? 0 : (u > 255 ? 255 : u); hi |= (uint32_t)u << (8 * k);
-  }
-  uint8_t* dst = planes + (long long)img * g.plane_per_img + g.plane_off[c] + ((long long)(by * 8 + t) * (g.bw[c] * 8) + bx * 8);
-  *(uint2*)dst = make_uint2(lo, hi);
+  jidct_pass2(planes + (long long)img * g.plane_per_img + g.plane_off[c] + ((long long)(by * 8 + t) * (g.bw[c] * 8) + bx * 8), live, x);
 }
 
 // four consecutive pixels of the batch's linear pixel order per thread: 12 output bytes = three aligned dwords (the group may straddle a row
@@ -561,19 +548,11 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
     }
     if (++x == g.ow) { x = 0; if (++y == g.oh) { y = 0; ++img; } }
   }
-  uint32_t* o = (uint32_t*)(out + p0 * 3);
-  if (p0 + 4 <= total) {
-    o[0] = px[0] | (px[1] << 24);
-    o[1] = (px[1] >> 8) | (px[2] << 16);
-    o[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    uint8_t* ob = out + p0 * 3;
-    for (int k = 0; k < 4 && p0 + k < total; ++k) { ob[3 * k] = (uint8_t)px[k]; ob[3 * k + 1] = (uint8_t)(px[k] >> 8); ob[3 * k + 2] = (uint8_t)(px[k] >> 16); }
-  }
+  jpeg_store4(out, p0, total, px);
 }
 
 // ---------------------------------------------------------------------------------------------
-// entry points used by api_input.hip
+// entry points used by api_input.hip and api_jpeg_decode.hip
 // ---------------------------------------------------------------------------------------------
 int jpeg_probe(const uint8_t* data, size_t len, int* h, int* w, int* ncomp, int* luma_sampling) {
   JFrame f; std::string why;

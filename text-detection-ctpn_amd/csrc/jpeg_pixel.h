@@ -1,5 +1,5 @@
 // The per-sample arithmetic of the JPEG decoder's device half (jpeg.hip), in a header of its own so that ONE source serves two compilers:
-// hipcc compiles it into jpeg_idct_kernel / jpeg_color_kernel; tests/test_jpeg.py compiles the same text with g++ (the HIP qualifiers
+// hipcc compiles it into jpeg_idct_kernel / jpeg_color_kernel and their ragged forms (jpeg_ragged.hip); tests/test_jpeg.py compiles the same text with g++ (the HIP qualifiers
 // defined away) into a small checker library and compares it with Pillow's decode on the CPU -- a new layout's arithmetic is pinned before
 // it ever reaches a GPU. Nothing here is product host code: the library itself only ever calls these functions from its kernels.
 #pragma once
@@ -38,6 +38,49 @@ __host__ __device__ __forceinline__ void jidct_1d(const int (&x)[8], int (&o)[8]
   o[1] = (tmp11 + t2 + r) >> descale; o[6] = (tmp11 - t2 + r) >> descale;
   o[2] = (tmp12 + t1 + r) >> descale; o[5] = (tmp12 - t1 + r) >> descale;
   o[3] = (tmp13 + t0 + r) >> descale; o[4] = (tmp13 - t0 + r) >> descale;
+}
+
+// The two passes of one 8 x 8 block's IDCT as thread t of the block's eight runs them. The caller finds the block (blk: its 64 coefficients,
+// q: its component's table, dst: row t of the block in its plane, 8-byte aligned), keeps the transpose buffer and puts its barrier between
+// the passes. A lane that is not live computes on zeros and neither loads nor stores: its pointers are never dereferenced.
+// pass 1: column t (elements t, t + 8, ...), dequantised; o[k] goes to row k, column t of the transpose buffer
+__host__ __device__ __forceinline__ void jidct_pass1(const int16_t* __restrict__ blk, const uint16_t* __restrict__ q, bool live, int t, int (&o)[8]) {
+  int x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (live) {      // (one branch around the sixteen loads, not a select per element: a load cannot be hoisted out of a select)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = (int)blk[8 * k + t] * (int)q[8 * k + t];
+  }
+  jidct_1d(x, o, 13 - 2);
+}
+
+struct alignas(8) JpegVec8 { uint32_t lo, hi; };
+
+// pass 2: row t (x: that row of the transpose buffer); eight clamped samples as one 8-byte store
+__host__ __device__ __forceinline__ void jidct_pass2(uint8_t* __restrict__ dst, bool live, const int (&x)[8]) {
+  int o[8];
+  jidct_1d(x, o, 13 + 2 + 3);
+  if (!live) return;
+  uint32_t lo = 0, hi = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int v = o[k] + 128; v = v < 0 ? 0 : (v > 255 ? 255 : v); lo |= (uint32_t)v << (8 * k);
+    int u = o[k + 4] + 128; u = u < 0 ? 0 : (u > 255 ? 255 : u); hi |= (uint32_t)u << (8 * k);
+  }
+  *(JpegVec8*)dst = JpegVec8{lo, hi};
+}
+
+// the four pixels p0 .. p0 + 3 (B | G << 8 | R << 16 each; p0 a multiple of 4) of an image of `total` pixels at out: three aligned dwords,
+// or byte by byte where fewer than four are left. Nothing is written at or behind total x 3 bytes.
+__host__ __device__ __forceinline__ void jpeg_store4(uint8_t* __restrict__ out, long long p0, long long total, const uint32_t (&px)[4]) {
+  if (p0 + 4 <= total) {
+    uint32_t* o = (uint32_t*)(out + p0 * 3);
+    o[0] = px[0] | (px[1] << 24);
+    o[1] = (px[1] >> 8) | (px[2] << 16);
+    o[2] = (px[2] >> 16) | (px[3] << 8);
+  } else {
+    uint8_t* ob = out + p0 * 3;
+    for (int k = 0; k < 4 && p0 + k < total; ++k) { ob[3 * k] = (uint8_t)px[k]; ob[3 * k + 1] = (uint8_t)(px[k] >> 8); ob[3 * k + 2] = (uint8_t)(px[k] >> 16); }
+  }
 }
 
 // pixel (oy, ox) of the image as cv2.imread returns it -> the stored pixel it is (EXIF orientation, tag 0x0112: 2 mirrored left-right,

@@ -1,9 +1,9 @@
 // JPEG files of mixed sizes into one ragged canvas (include/ctpn_hip.h, ctpn_decode_jpeg_batch_ragged): the per-thread text of
 // jpeg_ragged.hip's two kernels as __host__ __device__ functions. The kernels call them with their thread indices;
 // tests/jpeg_ragged_host.cpp compiles this same text with g++ under ASan + UBSan and calls them from loops over those indices.
-//   IDCT            jpeg_idct_kernel's body (jpeg.hip: jidct_1d by column, transpose, jidct_1d by row, clamp, one 8-byte store) with the image
-//                   found per 8 x 8 block from a descriptor table instead of one JpegGeom for the batch. The two passes are two functions:
-//                   the kernel's barrier (the host's loop over a workgroup's threads) stands between them.
+//   IDCT            jpeg_idct_kernel's two passes (jpeg_pixel.h: jidct_pass1 by column, the caller's transpose, jidct_pass2 by row with the
+//                   clamp and one 8-byte store) with the image found per 8 x 8 block from a descriptor table instead of one JpegGeom for
+//                   the batch. The kernel's barrier (the host's loop over a workgroup's threads) stands between the passes.
 //   colour + resize jpeg_color_kernel followed by resize_linear_kernel (preprocess.hip) in one pass over the CANVAS: every canvas pixel is
 //                   zero below its image, jpeg_pixel at jpeg_orient of itself where the factor is 1, and otherwise the resize's uint8 formula
 //                   over four neighbours that are jpeg_pixel values -- the file-size BGR image the uniform path stores between its two
@@ -55,35 +55,19 @@ RS_HD JrBlockPos jr_block_locate(const JrImage* __restrict__ tab, int n, long lo
   return p;
 }
 
-// pass 1: thread t of the block takes column t (elements t, t + 8, ...), dequantised; o[k] goes to row k, column t of the transpose buffer
+// the two passes (jpeg_pixel.h) on the block jr_block_locate found. A padding lane reads no descriptor and hands the pass null pointers,
+// which a lane that is not live never dereferences
 RS_HD void jr_idct_pass1(const JrImage* __restrict__ tab, const int16_t* __restrict__ coef, const uint16_t* __restrict__ qt /* [n][3][64] */,
                          const JrBlockPos& p, int t, int (&o)[8]) {
-  int x[8];
-  if (p.live) {
-    const JrImage& d = tab[p.img];
-    const int16_t* blk = coef + d.coef_base + d.g.coef_off[p.c] + p.b * 64;
-    const uint16_t* q = qt + ((long long)p.img * 3 + p.c) * 64;
-    for (int k = 0; k < 8; ++k) x[k] = (int)blk[8 * k + t] * (int)q[8 * k + t];
-  } else
-    for (int k = 0; k < 8; ++k) x[k] = 0;
-  jidct_1d(x, o, 13 - 2);
+  const int16_t* blk = nullptr;
+  if (p.live) { const JrImage& d = tab[p.img]; blk = coef + d.coef_base + d.g.coef_off[p.c] + p.b * 64; }
+  jidct_pass1(blk, qt + ((long long)p.img * 3 + p.c) * 64, p.live != 0, t, o);
 }
 
-struct alignas(8) JrVec8 { uint32_t lo, hi; };
-
-// pass 2: thread t takes row t (x: that row of the transpose buffer); eight clamped samples as one 8-byte store into the image's plane
 RS_HD void jr_idct_pass2(const JrImage* __restrict__ tab, uint8_t* __restrict__ planes, const JrBlockPos& p, int t, const int (&x)[8]) {
-  int o[8];
-  jidct_1d(x, o, 13 + 2 + 3);
-  if (!p.live) return;
-  uint32_t lo = 0, hi = 0;
-  for (int k = 0; k < 4; ++k) {
-    int v = o[k] + 128; v = v < 0 ? 0 : (v > 255 ? 255 : v); lo |= (uint32_t)v << (8 * k);
-    int u = o[k + 4] + 128; u = u < 0 ? 0 : (u > 255 ? 255 : u); hi |= (uint32_t)u << (8 * k);
-  }
-  const JrImage& d = tab[p.img];
-  uint8_t* dst = planes + d.plane_base + d.g.plane_off[p.c] + ((long long)(p.by * 8 + t) * (d.g.bw[p.c] * 8) + p.bx * 8);
-  *(JrVec8*)dst = JrVec8{lo, hi};
+  uint8_t* dst = nullptr;
+  if (p.live) { const JrImage& d = tab[p.img]; dst = planes + d.plane_base + d.g.plane_off[p.c] + ((long long)(p.by * 8 + t) * (d.g.bw[p.c] * 8) + p.bx * 8); }
+  jidct_pass2(dst, p.live != 0, x);
 }
 
 // pixel (y, x) of the TURNED image (what cv2.imread returns): B | G << 8 | R << 16
@@ -158,15 +142,7 @@ RS_HD void jr_color_resize_thread(const uint8_t* __restrict__ planes, uint8_t* _
       if (++dy == hc) { dy = 0; if (img + 1 < n) ++img; }      // (behind the last image nothing more is computed: p0 + k >= total)
     }
   }
-  if (p0 + 4 <= total) {
-    uint32_t* o = (uint32_t*)(canvas + p0 * 3);
-    o[0] = px[0] | (px[1] << 24);
-    o[1] = (px[1] >> 8) | (px[2] << 16);
-    o[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    uint8_t* ob = canvas + p0 * 3;
-    for (int k = 0; k < 4 && p0 + k < total; ++k) { ob[3 * k] = (uint8_t)px[k]; ob[3 * k + 1] = (uint8_t)(px[k] >> 8); ob[3 * k + 2] = (uint8_t)(px[k] >> 16); }
-  }
+  jpeg_store4(canvas, p0, total, px);
 }
 
 }  // namespace ctpn

@@ -612,6 +612,51 @@ int    ctpn_crop_lines(ctpn_ctx* ctx, const uint8_t* images, int images_on_devic
                        const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device,
                        size_t capacity_bytes, int* widths_out, int* total_out);
 
+/* ---- JPEG files of images of MIXED sizes in one call, and the text-line crops written as files where they are cut: additive to ABI 10.
+ * The writer's pixel half over a table of images (jpeg_enc.hip, jpeg_fdct_mixed_kernel): one descriptor per image -- size, row pitch,
+ * place in the source, block grid, place of its coefficients -- and a one-dimensional grid over the call's work items (one MCU row by 8
+ * MCUs each), whose workgroups find their image by a binary search of the items' prefix sums. The arithmetic is the uniform kernel's own
+ * text, so every file is byte-equal to ctpn_encode_jpeg_batch's of that image alone (and to Pillow's). Always 4:2:0, standard tables.
+ * Both entropy forms: the plain names code on the ctx's host pool, the _device names on the device (an image whose flag is raised goes to
+ * the host half, as in ctpn_encode_jpeg_batch_device; ctpn_jpeg_entropy_encode_device_stats counts the call's files). Measured end to end only: docs/decode_pipeline.md, "Crops out".
+ *   ctpn_encode_jpeg_mixed         n BGR uint8 images in ONE source buffer: image i is heights[i] x widths[i] (1 .. 65535 each), its first
+ *   ctpn_encode_jpeg_mixed_device  pixel offsets[i] bytes into `source`, its rows pitches[i] >= 3 widths[i] bytes apart; the bytes between a
+ *                                  row's end and the next row never enter a file. source on the host: source_bytes is its size, every image
+ *                                  must lie inside it, and it is copied in the ctx's copy queue (with slack behind it). source in HBM
+ *                                  (source_on_device; source_bytes is not read): a live batch of ctpn_decode_jpeg_batch is waited for in
+ *                                  the queue, any other buffer must be complete. The pixel read takes whole aligned dwords: a device
+ *                                  source must be READABLE over the aligned dwords its pixels touch -- at most three bytes past an image's
+ *                                  last pixel and three in front of its first (nothing outside the pixels where rows start 4-byte
+ *                                  aligned). This is ctpn_encode_jpeg_batch's contract for device images too. out / capacities /
+ *                                  bytes_out: as in ctpn_encode_jpeg_batch -- out[i] holds capacities[i] bytes, bytes_out[i] receives the
+ *                                  size, also of a file that did not fit (CTPN_ERR_CAPACITY; out[i] == NULL with capacity 0 sizes it);
+ *                                  ctpn_jpeg_encode_capacity(heights[i], widths[i]) always fits. CTPN_ERR_ARG: n <= 0, a null pointer, a
+ *                                  size outside 1 .. 65535, a pitch below 3 widths[i], a pitch or offset of 2^40 bytes or more, an image outside
+ *                                  source_bytes (host source),
+ *                                  quality outside 1 .. 100, more than 2^31 - 1 work items; CTPN_ERR_STATE: a post-processing-only ctx
+ *   ctpn_write_line_crops          ctpn_crop_lines' arguments without the output buffer, plus quality and paths[total] (image 0's lines,
+ *   ctpn_write_line_crops_device   then image 1's, ...): the crops are cut into a buffer the ctx owns (the same kernel, the same pixels)
+ *                                  and coded there, crop k as a crop_h x Wc_k image at pitch 3 max_w -- the pad columns never enter a
+ *                                  file, no crop visits the host. The ctx's pool writes the files; the call returns when they are
+ *                                  written. widths_out (nullable): total ints; *total_out is always written. paths == NULL SIZES the
+ *                                  call: widths and total, no launch. No lines at all is CTPN_OK. A path that cannot be written (or is
+ *                                  NULL) is CTPN_ERR_ARG, its name in ctpn_last_error(); quality outside 1 .. 100 is CTPN_ERR_ARG; the
+ *                                  remaining errors are ctpn_crop_lines' and the writer's.
+ * All four run in the ctx's copy queue, behind the decode that produced the batch and in front of the next one; their buffers (the
+ * descriptor table and its page-locked copy among them) grow to the largest call seen and are then reused. */
+int    ctpn_encode_jpeg_mixed(ctpn_ctx* ctx, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights,
+                              const int* widths, const size_t* pitches, const size_t* offsets, int quality, uint8_t* const* out,
+                              const size_t* capacities, size_t* bytes_out);
+int    ctpn_encode_jpeg_mixed_device(ctpn_ctx* ctx, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights,
+                                     const int* widths, const size_t* pitches, const size_t* offsets, int quality, uint8_t* const* out,
+                                     const size_t* capacities, size_t* bytes_out);
+int    ctpn_write_line_crops(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
+                             const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths,
+                             int* widths_out, int* total_out);
+int    ctpn_write_line_crops_device(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs,
+                                    int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality,
+                                    const char* const* paths, int* widths_out, int* total_out);
+
 /* ---- cv2.imread for PNG files (reference ctpn/demo.py:59; data/demo holds .jpg and .png). HOST ONLY, by the nature of READING the format: one
  * DEFLATE stream (zlib's inflate, the library libpng itself sits on) and row filters that chain from row to row -- nothing a GPU is for. One
  * file per host thread, straight into the caller's batch buffer, which ctpn_detect_submit / ctpn_forward take as host images (one

@@ -145,6 +145,14 @@ def _declare(lib):
         "ctpn_line_crop_width": (C.c_int, [f64p, C.c_int, C.c_int, i32p]),
         "ctpn_crop_lines": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_size_t,
                                       i32p, i32p]),
+        "ctpn_encode_jpeg_mixed": (C.c_int, [vp, vp, C.c_int, C.c_size_t, C.c_int, i32p, i32p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int,
+                                             C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "ctpn_encode_jpeg_mixed_device": (C.c_int, [vp, vp, C.c_int, C.c_size_t, C.c_int, i32p, i32p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int,
+                                                    C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "ctpn_write_line_crops": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(C.c_char_p), i32p, i32p]),
+        "ctpn_write_line_crops_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_char_p), i32p, i32p]),
         "ctpn_debug_png_backend": (C.c_int, [C.c_int]),
         "ctpn_png_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_png_decode": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t]),
@@ -1186,6 +1194,82 @@ class Context:
         if total.value:
             call(crops.ctypes.data_as(C.c_void_p), 0, crops.size)
         return crops, widths[: total.value].copy()
+
+    def write_line_crops(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None, paths=None,
+                         quality=95, entropy="host"):
+        """crop_lines with the crops written as JPEG files where they are cut (ctpn_write_line_crops): crop k, crop_h x widths[k], goes to
+        paths[k] at `quality` -- image 0's lines first, then image 1's, ... --, byte-equal to Pillow's save(quality=quality, subsampling=2) of
+        crop_lines' crops[k, :, :widths[k]]. No crop visits the host. paths=None sizes the call. -> widths (int32, one per line).
+        entropy="device": ctpn_write_line_crops_device, the same files with the Huffman coding on the device."""
+        fn = self._lib.ctpn_write_line_crops_device if self._entropy_form(entropy) else self._lib.ctpn_write_line_crops
+        if device_ptr is None:
+            images = np.ascontiguousarray(images, dtype=np.uint8)
+            if images.ndim == 3:
+                images = images[None]
+            if images.ndim != 4 or images.shape[3] != 3:
+                raise ValueError("write_line_crops wants (n,h,w,3) uint8")
+            shape, src, on_dev = images.shape, images.ctypes.data_as(C.c_void_p), 0
+        else:
+            src, on_dev = C.c_void_p(int(device_ptr)), 1
+        n, h, w = int(shape[0]), int(shape[1]), int(shape[2])
+        packed, counts = _pack_lines(recs, line_counts, n)
+        lines = int(counts.sum())
+        widths = np.zeros((max(lines, 1),), np.int32)
+        total = C.c_int(0)
+        arr = None
+        if paths is not None:
+            paths = list(paths)
+            if len(paths) != lines:
+                raise ValueError("write_line_crops wants one path per line")
+            keep, arr = _path_array(paths)
+        _check(fn(self._h, src, on_dev, n, h, w, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h), int(max_w), int(pad_value),
+                  int(quality), arr, _ptr(widths, C.c_int), C.byref(total)))
+        return widths[: total.value].copy()
+
+    def encode_jpeg_mixed(self, images=None, quality=95, entropy="host", device_ptr=None, heights=None, widths=None, pitches=None, offsets=None):
+        """JPEG files of n BGR uint8 images of ANY mix of sizes in one call (ctpn_encode_jpeg_mixed). images: a list of (h_i, w_i, 3) arrays
+        (packed into one source buffer, rows 4-byte aligned), or device_ptr with the tables heights / widths / pitches (bytes, >= 3 w) /
+        offsets (bytes into the buffer). -> list of n bytes objects, each byte-equal to encode_jpeg_batch of that image alone and to
+        Pillow's save(quality=quality, subsampling=2). entropy="device": ctpn_encode_jpeg_mixed_device."""
+        fn = self._lib.ctpn_encode_jpeg_mixed_device if self._entropy_form(entropy) else self._lib.ctpn_encode_jpeg_mixed
+        if device_ptr is None:
+            images = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+            if any(im.ndim != 3 or im.shape[2] != 3 for im in images):
+                raise ValueError("encode_jpeg_mixed wants a list of (h,w,3) uint8 images")
+            heights = [im.shape[0] for im in images]
+            widths = [im.shape[1] for im in images]
+            pitches = [(3 * w + 3) & ~3 for w in widths]
+            offsets, at = [], 0
+            for h, p in zip(heights, pitches):
+                offsets.append(at)
+                at += h * p
+            source = np.zeros((max(at, 1),), np.uint8)
+            for im, p, o in zip(images, pitches, offsets):
+                h, w = im.shape[:2]
+                source[o: o + h * p].reshape(h, p)[:, : 3 * w] = im.reshape(h, 3 * w)
+            src, on_dev, nbytes = source.ctypes.data_as(C.c_void_p), 0, source.size
+        else:
+            src, on_dev, nbytes = C.c_void_p(int(device_ptr)), 1, 0
+        ht = np.ascontiguousarray(heights, dtype=np.int32).reshape(-1)
+        wd = np.ascontiguousarray(widths, dtype=np.int32).reshape(-1)
+        n = int(ht.shape[0])
+        if wd.shape[0] != n or len(pitches) != n or len(offsets) != n:
+            raise ValueError("encode_jpeg_mixed wants one height, width, pitch and offset per image")
+        pt = (C.c_size_t * max(n, 1))(*[int(v) for v in pitches])
+        of = (C.c_size_t * max(n, 1))(*[int(v) for v in offsets])
+        bounds = [jpeg_encode_capacity(int(h), int(w)) for h, w in zip(ht, wd)]
+        sizes = (C.c_size_t * max(n, 1))()
+        rc = CTPN_OK
+        for proven in (False, True):      # a byte per pixel holds any photograph; the proven bound is three times the raw image
+            want = [b if proven else min(b, int(h) * int(w) + 4096) for b, h, w in zip(bounds, ht, wd)]
+            bufs = [np.empty((cap,), np.uint8) for cap in want]
+            ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+            caps = (C.c_size_t * max(n, 1))(*want)
+            rc = fn(self._h, src, on_dev, nbytes, n, _ptr(ht, C.c_int), _ptr(wd, C.c_int), pt, of, int(quality), ptrs, caps, sizes)
+            if rc != CTPN_ERR_CAPACITY:
+                break
+        _check(rc)
+        return [bufs[i][: sizes[i]].tobytes() for i in range(n)]
 
     def detect_submit(self, images=None, slot=0, scales=None, device_ptr=None, shape=None, heights=None):
         """Asynchronous detect, part 1 (ctpn_detect_submit). Returns immediately. heights: the batch is ragged -- images is a canvas

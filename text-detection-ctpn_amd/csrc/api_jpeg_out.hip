@@ -1,7 +1,9 @@
 // C ABI of libctpn_hip.so, JPEG output unit: JPEG writing (kernels and the entropy coder: jpeg_enc.hip) of a batch on the device, and
 // the cv2.imwrite end of the annotated result images of ctpn/demo.py:28-52 (outlines and resize: api_out_stage.hip).
-// Two entropy forms behind one enc_enqueue / enc_finish: host (the default entry points) and device (the *_device entry points: jpeg_huff_enc.hip).
+// One enc_enqueue / enc_finish over a list of per-image geometries: n equal ones (the uniform calls, jpeg_fdct_kernel) or any mix of sizes
+// and pitches (ctpn_encode_jpeg_mixed, ctpn_write_line_crops: jpeg_fdct_mixed_kernel). Two entropy forms behind them: host (the default entry points) and device (the *_device entry points: jpeg_huff_enc.hip).
 #include "ctx.h"
+#include "jpeg_enc_mixed_dev.h"
 #include "jpeg_enc_pixel.h"
 #include "jpeg_huff_enc_dev.h"
 
@@ -40,15 +42,61 @@ static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
   return CTPN_OK;
 }
 
-// device half in the ctx's copy queue: pixels (device, n x h x w x 3) -> coefficients, in the page-locked block too unless the device codes
-// them as well (device_entropy); no host wait
-static int enc_enqueue(ctpn_ctx* c, const uint8_t* pixels_dev, int n, int h, int w, int quality, JpegGeom& g, bool device_entropy) {
-  jpeg_enc_geom(h, w, g);
-  int rc = enc_reserve(c, (size_t)n * (size_t)g.coef_per_img, quality);
+// the images of one call: every image's geometry (jpeg_enc_geom) and the int16 offset of its coefficients, packed at the prefix sums of the
+// images' own coef_per_img. The uniform calls hold n equal geometries
+struct EncPlan {
+  std::vector<JpegGeom> g;
+  std::vector<long long> coef0;
+  size_t coef_elems = 0;
+  void add(int h, int w) {
+    JpegGeom q;
+    jpeg_enc_geom(h, w, q);
+    g.push_back(q); coef0.push_back((long long)coef_elems);
+    coef_elems += (size_t)q.coef_per_img;
+  }
+  int n() const { return (int)g.size(); }
+};
+
+// where the images of a mixed call lie in their source buffer (bytes)
+struct EncSource { const size_t* pitches; const size_t* offsets; };
+
+// the descriptor table of a mixed call: built in the ctx's page-locked block, copied in the copy queue (the block is free again: every
+// call that used it waited for its coefficients or result words, which come behind the copy)
+static int enc_stage_table(ctpn_ctx* c, const EncPlan& P, const EncSource& src, long long& items) {
+  auto& E = c->enc;
+  const size_t bytes = (size_t)P.n() * sizeof(JemImage);
+  int rc;
+  if ((rc = grow_host(&E.mix_host, E.mix_host_bytes, bytes)) || (rc = grow_dev((void**)&E.mix_dev, E.mix_bytes, bytes))) return rc;
+  JemImage* tab = (JemImage*)E.mix_host;
+  for (int i = 0; i < P.n(); ++i) {
+    const JpegGeom& g = P.g[i];
+    jem_describe(tab[i], g.h, g.w, (long long)src.pitches[i], (long long)src.offsets[i]);
+    for (int k = 0; k < 3; ++k)
+      if (tab[i].bw[k] != g.bw[k] || tab[i].bh[k] != g.bh[k] || tab[i].coef_off[k] != g.coef_off[k]) return fail(CTPN_ERR_STATE, "jpeg encode: descriptor and geometry disagree");
+  }
+  long long coef_total = 0;
+  items = jem_prefix(tab, P.n(), &coef_total);
+  if (items < 0) return fail(CTPN_ERR_ARG, "jpeg encode: more than 2^31 - 1 work items in one call");
+  if ((size_t)coef_total != P.coef_elems) return fail(CTPN_ERR_STATE, "jpeg encode: descriptor and geometry disagree");
+  CTPN_HIP_TRY(hipMemcpyAsync(E.mix_dev, tab, bytes, hipMemcpyHostToDevice, c->stream_c));
+  return CTPN_OK;
+}
+
+// device half in the ctx's copy queue: pixels (device) -> coefficients, in the page-locked block too unless the device codes them as well
+// (device_entropy); no host wait. src == null: the plan's n equal images, tightly packed (n x h x w x 3); else images of any sizes at
+// their own pitches and offsets
+static int enc_enqueue(ctpn_ctx* c, const uint8_t* pixels_dev, const EncPlan& P, const EncSource* src, int quality, bool device_entropy) {
+  int rc = enc_reserve(c, P.coef_elems, quality);
   if (rc) return rc;
   auto& E = c->enc;
-  if ((rc = launch_jpeg_fdct(pixels_dev, E.coef_dev, (const JencQ*)E.qtab_dev, g, n, c->stream_c))) return rc;
-  if (!device_entropy) CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host, E.coef_dev, (size_t)n * (size_t)g.coef_per_img * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
+  if (!src) {
+    if ((rc = launch_jpeg_fdct(pixels_dev, E.coef_dev, (const JencQ*)E.qtab_dev, P.g[0], P.n(), c->stream_c))) return rc;
+  } else {
+    long long items = 0;
+    if ((rc = enc_stage_table(c, P, *src, items))) return rc;
+    if ((rc = launch_jpeg_fdct_mixed(pixels_dev, E.coef_dev, (const JencQ*)E.qtab_dev, (const JemImage*)E.mix_dev, P.n(), items, c->stream_c))) return rc;
+  }
+  if (!device_entropy) CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host, E.coef_dev, P.coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
   CTPN_HIP_TRY(hipEventRecord(E.ev_done, c->stream_c));
   return CTPN_OK;
 }
@@ -204,9 +252,10 @@ static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
 
 // second half of both forms: into the caller's buffers (out), or into files (paths). Host entropy: the coefficients are awaited and coded
 // on the ctx's pool, one image per worker. Device entropy: the kernels of jpeg_huff_enc.hip code them; the pool adds header and EOI
-static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths,
+static int enc_finish(ctpn_ctx* c, const char* who, const EncPlan& P, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths,
                       bool device_entropy) {
   auto& E = c->enc;
+  const int n = P.n();
   uint16_t qt[192];
   jpeg_enc_qtables(quality, qt, nullptr);
   std::vector<int> st((size_t)n, CTPN_OK);
@@ -215,7 +264,7 @@ static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, in
     std::vector<EncJob> jobs((size_t)n);
     for (int i = 0; i < n; ++i) {
       EncJob& J = jobs[i];
-      J.h = g.h; J.w = g.w; J.hs = 2; J.vs = 2; J.qt = qt; J.describe((long long)i * g.coef_per_img); J.coef_host = nullptr;
+      J.h = P.g[i].h; J.w = P.g[i].w; J.hs = 2; J.vs = 2; J.qt = qt; J.describe(P.coef0[i]); J.coef_host = nullptr;
       J.out = paths ? nullptr : out[i]; J.capacity = paths ? 0 : capacities[i]; J.bytes_out = paths ? nullptr : bytes_out + i; J.path = paths ? paths[i] : nullptr;
     }
     const int rc = enc_huff(c, jobs, true);
@@ -223,10 +272,10 @@ static int enc_finish(ctpn_ctx* c, const char* who, const JpegGeom& g, int n, in
     for (int i = 0; i < n; ++i) { st[i] = jobs[i].st; msg[i] = jobs[i].msg; }
   } else {
     CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
-    const size_t bound = jpeg_encode_capacity(g.h, g.w);
     c->pool->run(n, [&](int i) {
-      const int16_t* coef = E.coef_host + (size_t)i * (size_t)g.coef_per_img;
-      enc_deliver(bound, paths ? nullptr : out[i], paths ? 0 : capacities[i], paths ? nullptr : bytes_out + i, paths ? paths[i] : nullptr, st[i], msg[i],
+      const JpegGeom& g = P.g[i];
+      const int16_t* coef = E.coef_host + P.coef0[i];
+      enc_deliver(jpeg_encode_capacity(g.h, g.w), paths ? nullptr : out[i], paths ? 0 : capacities[i], paths ? nullptr : bytes_out + i, paths ? paths[i] : nullptr, st[i], msg[i],
                   [&](uint8_t* buf, size_t cap, size_t* bytes) { return jpeg_entropy_encode(coef, true, g.h, g.w, 2, 2, qt, buf, cap, bytes); });
     });
   }
@@ -258,9 +307,46 @@ static int encode_batch_impl(ctpn_ctx* c, const char* who_, const uint8_t* image
   const uint8_t* px;
   int rc;
   if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
-  JpegGeom g;
-  if ((rc = enc_enqueue(c, px, n, h, w, quality, g, device_entropy))) return rc;
-  return enc_finish(c, who_, g, n, quality, out, capacities, bytes_out, nullptr, device_entropy);
+  EncPlan P;
+  for (int i = 0; i < n; ++i) P.add(h, w);
+  if ((rc = enc_enqueue(c, px, P, nullptr, quality, device_entropy))) return rc;
+  return enc_finish(c, who_, P, quality, out, capacities, bytes_out, nullptr, device_entropy);
+}
+
+// the images of a mixed call as the writer takes them: sizes 1 .. 65535, pitches that hold a row; pitches and offsets below 2^40, so that
+// the kernel's signed 64-bit addresses (offset + row * pitch) cannot wrap
+static int mixed_check(const std::string& who, int n, const int* heights, const int* widths, const size_t* pitches, const size_t* offsets) {
+  const size_t limit = (size_t)1 << 40;
+  for (int i = 0; i < n; ++i) {
+    if (heights[i] < 1 || widths[i] < 1 || heights[i] > 65535 || widths[i] > 65535) return fail(CTPN_ERR_ARG, who + ": image " + std::to_string(i) + ": bad size");
+    if (pitches[i] < (size_t)widths[i] * 3) return fail(CTPN_ERR_ARG, who + ": image " + std::to_string(i) + ": the pitch is below 3 * width");
+    if (pitches[i] >= limit || offsets[i] >= limit) return fail(CTPN_ERR_ARG, who + ": image " + std::to_string(i) + ": pitch or offset of 2^40 bytes or more");
+  }
+  return CTPN_OK;
+}
+
+// ctpn_encode_jpeg_mixed / ctpn_encode_jpeg_mixed_device
+static int encode_mixed_impl(ctpn_ctx* c, const char* who_, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights, const int* widths,
+                             const size_t* pitches, const size_t* offsets, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, bool device_entropy) {
+  const std::string who(who_);
+  if (!c || !source || !heights || !widths || !pitches || !offsets || !out || !capacities || !bytes_out) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0) return fail(CTPN_ERR_ARG, who + ": empty batch");
+  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
+  int rc;
+  if ((rc = mixed_check(who, n, heights, widths, pitches, offsets))) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, who + ": null output pointer");
+    if (!source_on_device) {      // (sizes and pitches are bounded: the sum cannot wrap unless the offset does)
+      const size_t span = (size_t)(heights[i] - 1) * pitches[i] + (size_t)widths[i] * 3;
+      if (pitches[i] > source_bytes || offsets[i] > source_bytes || span > source_bytes - offsets[i])
+        return fail(CTPN_ERR_ARG, who + ": image " + std::to_string(i) + " does not lie inside source_bytes");
+    }
+  }
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  const uint8_t* px;
+  if ((rc = stage_pixels(c, source, source_on_device, source_bytes, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
+  return encode_mixed_dev(c, who_, px, n, heights, widths, pitches, offsets, quality, out, capacities, bytes_out, nullptr, device_entropy);
 }
 
 // ctpn_write_annotated_files / ctpn_write_annotated_files_device
@@ -270,9 +356,20 @@ static int write_annotated_impl(ctpn_ctx* c, const char* who_, const uint8_t* im
   const uint8_t* px;
   int dh, dw, rc;
   if ((rc = annotate_batch(c, who_, "JPEG", nullptr, images_dev, 1, n, h, w, recs, line_capacity, line_counts, scale, paths, px, dh, dw))) return rc;
-  JpegGeom g;
-  if ((rc = enc_enqueue(c, px, n, dh, dw, quality, g, device_entropy))) return rc;
-  return enc_finish(c, who_, g, n, quality, nullptr, nullptr, nullptr, paths, device_entropy);
+  EncPlan P;
+  for (int i = 0; i < n; ++i) P.add(dh, dw);
+  if ((rc = enc_enqueue(c, px, P, nullptr, quality, device_entropy))) return rc;
+  return enc_finish(c, who_, P, quality, nullptr, nullptr, nullptr, paths, device_entropy);
+}
+
+// (ctx.h) n checked images in device memory the copy queue may read -> files in caller memory (out) or on disk (paths)
+int encode_mixed_dev(ctpn_ctx* c, const char* who, const uint8_t* px_dev, int n, const int* heights, const int* widths, const size_t* pitches, const size_t* offsets,
+                     int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths, bool device_entropy) {
+  EncPlan P;
+  for (int i = 0; i < n; ++i) P.add(heights[i], widths[i]);
+  const EncSource src{pitches, offsets};
+  if (int rc = enc_enqueue(c, px_dev, P, &src, quality, device_entropy)) return rc;
+  return enc_finish(c, who, P, quality, out, capacities, bytes_out, paths, device_entropy);
 }
 
 }  // namespace ctpn
@@ -337,6 +434,16 @@ int ctpn_encode_jpeg_batch(ctpn_ctx* c, const uint8_t* images, int images_on_dev
 int ctpn_encode_jpeg_batch_device(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, int quality, uint8_t* const* out,
                                   const size_t* capacities, size_t* bytes_out) {
   return encode_batch_impl(c, "ctpn_encode_jpeg_batch_device", images, images_on_device, n, h, w, quality, out, capacities, bytes_out, true);
+}
+
+int ctpn_encode_jpeg_mixed(ctpn_ctx* c, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights, const int* widths, const size_t* pitches,
+                           const size_t* offsets, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out) {
+  return encode_mixed_impl(c, "ctpn_encode_jpeg_mixed", source, source_on_device, source_bytes, n, heights, widths, pitches, offsets, quality, out, capacities, bytes_out, false);
+}
+
+int ctpn_encode_jpeg_mixed_device(ctpn_ctx* c, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights, const int* widths, const size_t* pitches,
+                                  const size_t* offsets, int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out) {
+  return encode_mixed_impl(c, "ctpn_encode_jpeg_mixed_device", source, source_on_device, source_bytes, n, heights, widths, pitches, offsets, quality, out, capacities, bytes_out, true);
 }
 
 int ctpn_write_annotated_files(ctpn_ctx* c, const uint8_t* images_dev, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,

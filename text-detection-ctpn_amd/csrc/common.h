@@ -361,6 +361,9 @@ void jpeg_enc_qtables(int quality, uint16_t* qt3x64, JencQ* q2x64);
 size_t jpeg_encode_capacity(int h, int w);
 int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, int vs, const uint16_t* qt3x64, uint8_t* out, size_t capacity, size_t* bytes_out);
 int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JpegGeom& g, int n, hipStream_t s);
+// ... over a table of images of different sizes and pitches (JemImage, the table's prefix sums and the work items: jpeg_enc_mixed_dev.h)
+struct JemImage;
+int launch_jpeg_fdct_mixed(const uint8_t* src_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JemImage* tab_dev, int n, long long total_items, hipStream_t s);
 int jpeg_enc_check(int h, int w, int hs, int vs, const uint16_t* qt3x64);
 int jpeg_enc_assemble(int h, int w, int hs, int vs, const uint16_t* qt3x64, const uint8_t* scan, size_t have, size_t scan_bytes, uint8_t* out, size_t capacity, size_t* bytes_out);
 

@@ -207,6 +207,9 @@ struct ctpn_ctx {
     void* huff_tab_dev = nullptr;
     uint8_t* huff_host = nullptr; size_t huff_host_bytes = 0;
     uint8_t* scan_host = nullptr; size_t scan_host_bytes = 0;
+    // images of mixed sizes (ctpn_encode_jpeg_mixed, ctpn_write_line_crops): the descriptor table with its prefix sums, page-locked / device
+    uint8_t* mix_host = nullptr; size_t mix_host_bytes = 0;
+    uint8_t* mix_dev = nullptr; size_t mix_bytes = 0;
   } enc;
   long long jhe_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_encode_device_stats
   // ctpn_encode_png_batch / ctpn_write_annotated_png_files (api_png_out.hip): ONE set of buffers, for the same reason, grown likewise
@@ -444,6 +447,11 @@ int annotate_batch(ctpn_ctx* c, const std::string& who, const char* format, Stag
 // a finished file onto the disk (on worker threads: nothing may leave it; st, msg: why it failed); the report of a call's first failed image
 void write_file(const char* path, const uint8_t* data, size_t bytes, int& st, std::string& msg);
 int first_failure(const char* who, const std::vector<int>& st, const std::vector<std::string>& msg);
+// api_jpeg_out.hip: n BGR images of mixed sizes (each 1 .. 65535, pitches[i] >= 3 widths[i], both checked by the caller) at offsets[i] bytes of
+// px_dev, device memory the copy queue may read as it stands -> JPEG files at `quality`, in caller memory (out / capacities / bytes_out) or
+// on disk (paths); returns when they are written. The contract of ctpn_encode_jpeg_mixed behind its argument checks
+int encode_mixed_dev(ctpn_ctx* c, const char* who, const uint8_t* px_dev, int n, const int* heights, const int* widths, const size_t* pitches, const size_t* offsets,
+                     int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths, bool device_entropy);
 bool jpeg_read_file(const char* path, std::vector<uint8_t>& buf, size_t limit = 0);      // api_input.hip: a whole file (limit: its first bytes only); false if it cannot be read
 void jpeg_layout8(const JpegGeom& g, int* layout8);                                      // api_input.hip: the eight ints ctpn_jpeg_entropy_decode describes a file's layout with
 

@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "jpeg_enc_mixed_dev.h"
 #include "jpeg_enc_pixel.h"
 #include "jpeg_enc_tables.h"
 
@@ -224,53 +225,33 @@ int jpeg_entropy_encode(const int16_t* coef, bool zigzag, int h, int w, int hs, 
 // ---------------------------------------------------------------------------------------------
 __constant__ uint8_t d_jenc_zzpos[64] = CTPN_JENC_ZIGZAG_POS;
 
-// four pixels (B | G << 8 | R << 16) of one image row from column x0 on, the last column repeated behind the image
-__device__ __forceinline__ void jenc_load4(const uint8_t* __restrict__ row, int x0, int w, uint32_t (&px)[4]) {
-  if (x0 + 4 <= w) {
-    const uintptr_t a = (uintptr_t)(row + (long long)x0 * 3);
-    const uint32_t* p = (const uint32_t*)(a & ~(uintptr_t)3);
-    const int sh = (int)(a & 3) * 8;
-    uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-    if (sh) {      // (the fourth dword holds the run's last bytes: inside the image)
-      const uint32_t d3 = p[3];
-      d0 = (d0 >> sh) | (d1 << (32 - sh)); d1 = (d1 >> sh) | (d2 << (32 - sh)); d2 = (d2 >> sh) | (d3 << (32 - sh));
-    }
-    px[0] = d0 & 0xffffffu; px[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8); px[2] = (d1 >> 16) | ((d2 & 0xffu) << 16); px[3] = d2 >> 8;
-  } else {      // the run crosses the right edge: byte by byte
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      int x = x0 + k;
-      x = x < w ? x : w - 1;
-      const uint8_t* q = row + (long long)x * 3;
-      px[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restrict__ img, int16_t* __restrict__ coef, const JencQ* __restrict__ qtab /* [2][64] */, JpegGeom g) {
+// One work item (jpeg_enc_mixed_dev.h): 8 MCUs `tile` of MCU row `my` of ONE h x w image whose first pixel is at img, rows `pitch` bytes
+// apart; coef: the image's own coefficient block, bw / coef_off its components' block columns and offsets. The whole sequence -- load,
+// colour conversion, downsampling, both DCT passes, quantiser, dummy blocks, store -- of both kernels below; every thread of the workgroup
+// runs through all of its barriers.
+__device__ __forceinline__ void jenc_fdct_item(const uint8_t* __restrict__ img, long long pitch, int h, int w, int16_t* __restrict__ coef, const int* __restrict__ bw,
+                                               const long long* __restrict__ coef_off, const JencQ* __restrict__ qtab /* [2][64] */, int tile, int my) {
   __shared__ __attribute__((aligned(16))) uint8_t sY[16][128];
   __shared__ __attribute__((aligned(16))) uint8_t sC[2][8][64];
   __shared__ int ws[32][8][9];
   __shared__ __attribute__((aligned(16))) int16_t zq[32][64];
   __shared__ JencQ sq[2][64];
   const int tid = threadIdx.x;
-  const int tile = blockIdx.x, my = blockIdx.y, im = blockIdx.z;
   if (tid < 128) sq[tid >> 6][tid & 63] = qtab[tid];
   {
     const int gx = tid & 31, ry = tid >> 5;
     const int x0 = tile * 128 + gx * 4;
-    const uint8_t* base = img + (long long)im * g.h * g.w * 3;
     // below the image the LUMA rows repeat the last pixel row, the CHROMA rows the last DOWNSAMPLED row (jcprepct.c pads the colour-converted
     // rows to one row group only, then expand_bottom_edge works on every component's own, downsampled, rows)
-    const int cy = jenc_chroma_row(my * 8 + ry, g.h);
+    const int cy = jenc_chroma_row(my * 8 + ry, h);
     int cb[2][4], cr[2][4];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       int y = my * 16 + ry * 2 + r, yc = 2 * cy + r;
-      y = y < g.h ? y : g.h - 1;
-      yc = yc < g.h ? yc : g.h - 1;
+      y = y < h ? y : h - 1;
+      yc = yc < h ? yc : h - 1;
       uint32_t px[4];
-      jenc_load4(base + (long long)y * g.w * 3, x0, g.w, px);
+      jenc_load4(img, pitch, y, x0, w, px);
       uint32_t yy = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -280,7 +261,7 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restric
       }
       *(uint32_t*)&sY[ry * 2 + r][gx * 4] = yy;
       if (yc != y) {      // (the rows below the image only)
-        jenc_load4(base + (long long)yc * g.w * 3, x0, g.w, px);
+        jenc_load4(img, pitch, yc, x0, w, px);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { int Y; jenc_ycc((int)(px[k] & 0xff), (int)((px[k] >> 8) & 0xff), (int)(px[k] >> 16), Y, cb[r][k], cr[r][k]); }
       }
@@ -293,7 +274,7 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restric
   }
   __syncthreads();
   const int lb = tid >> 3, t = tid & 7;
-  const int real_bw0 = (g.w + 7) >> 3, real_bh0 = (g.h + 7) >> 3;
+  const int real_bw0 = (w + 7) >> 3, real_bh0 = (h + 7) >> 3;
 #pragma unroll 1
   for (int it = 0; it < 2; ++it) {
     const bool active = it == 0 || lb < 16;
@@ -319,7 +300,7 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restric
     __syncthreads();
     if (active) {
       const int bxg = (c == 0 ? tile * 16 : tile * 8) + bx, byg = (c == 0 ? my * 2 : my) + by;
-      if (bxg < g.bw[c]) {
+      if (bxg < bw[c]) {
         uint4 v = *(const uint4*)&zq[lb][t * 8];
         if (c == 0) {
           const int s = jenc_dummy_src(by, bx & 1, (bxg | 1) >= real_bw0, my * 2 + 1 >= real_bh0);
@@ -328,11 +309,26 @@ __global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restric
             if (t == 0) v.x = (uint32_t)(uint16_t)zq[(s >> 1) * 16 + (bx & ~1) + (s & 1)][0];
           }
         }
-        *(uint4*)(coef + (long long)im * g.coef_per_img + g.coef_off[c] + ((long long)byg * g.bw[c] + bxg) * 64 + t * 8) = v;
+        *(uint4*)(coef + coef_off[c] + ((long long)byg * bw[c] + bxg) * 64 + t * 8) = v;
       }
     }
     __syncthreads();
   }
+}
+
+// n images of one size, tightly packed: grid (tiles, MCU rows, n), one JpegGeom for the batch
+__global__ __launch_bounds__(256) void jpeg_fdct_kernel(const uint8_t* __restrict__ img, int16_t* __restrict__ coef, const JencQ* __restrict__ qtab /* [2][64] */, JpegGeom g) {
+  const int im = blockIdx.z;
+  jenc_fdct_item(img + (long long)im * g.h * g.w * 3, (long long)g.w * 3, g.h, g.w, coef + (long long)im * g.coef_per_img, g.bw, g.coef_off, qtab, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// n images of any mix of sizes and pitches in one source buffer: a one-dimensional grid over the table's work items, the image of a
+// workgroup found in the items' prefix (uniform over the workgroup: no thread leaves in front of a barrier)
+__global__ __launch_bounds__(256) void jpeg_fdct_mixed_kernel(const uint8_t* __restrict__ src, int16_t* __restrict__ coef, const JencQ* __restrict__ qtab /* [2][64] */,
+                                                              const JemImage* __restrict__ tab, int n) {
+  const JemItem p = jem_locate(tab, n, (long long)blockIdx.x);
+  const JemImage& d = tab[p.img];
+  jenc_fdct_item(src + d.src_off, d.pitch, d.h, d.w, coef + d.coef_base, d.bw, d.coef_off, qtab, p.tile, p.my);
 }
 
 // ctpn_draw_boxes (text_connector.cpp) on n device images: one workgroup per image; lines, and the four segments of a line, in the host
@@ -398,6 +394,13 @@ int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qta
   if (n <= 0 || n > 65535 || mcuy > 65535 || mcux <= 0) return fail(CTPN_ERR_ARG, "jpeg encode: grid out of range");
   hipLaunchKernelGGL(jpeg_fdct_kernel, dim3((unsigned)((mcux + 7) / 8), (unsigned)mcuy, (unsigned)n), dim3(256), 0, s, img_dev, coef_dev, qtab_dev, g);
   return launch_status("jpeg encode");
+}
+
+// tab_dev: n descriptors with their prefix sums (jem_prefix), total_items work items in all
+int launch_jpeg_fdct_mixed(const uint8_t* src_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JemImage* tab_dev, int n, long long total_items, hipStream_t s) {
+  if (n <= 0 || total_items < n || total_items > JEM_MAX_ITEMS) return fail(CTPN_ERR_ARG, "jpeg encode: grid out of range");
+  hipLaunchKernelGGL(jpeg_fdct_mixed_kernel, dim3((unsigned)total_items), dim3(256), 0, s, src_dev, coef_dev, qtab_dev, tab_dev, n);
+  return launch_status("jpeg encode (mixed sizes)");
 }
 
 int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* counts_dev, int line_capacity, int n, int h, int w, hipStream_t s) {

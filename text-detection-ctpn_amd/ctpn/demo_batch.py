@@ -16,6 +16,8 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
 
   * with --crops DIR every detected line is also cut out as a rectified image of fixed height, `<stem>_<k>.jpg`, for a recogniser behind
     the detector (ctpn_crop_lines: on the device; batches decoded there are cropped where they lie, without fetching them).
+    --crops-encode gpu | gpu-entropy: the crops are JPEG-coded and written by the library where they are cut (ctpn_write_line_crops),
+    the same files as Pillow's (the default, host).
 
   * cfg.TEST.RPN_* of the loaded text.yml go into the ctx's tail parameters (ctpn_set_param), so the batched path honours the file like
     the single-image path; --connector NAME=VALUE (repeatable; TextLineCfg's names, MIN_LINE_WIDTH for TEXT_PROPOSALS_WIDTH *
@@ -289,10 +291,19 @@ def _read(name):
         return f.read()
 
 
-def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None):
+def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None, encode="host"):
     """The text lines of one batch as rectified crops of height crop_h (ctpn_crop_lines: cut out on the device, from host images or from
     a batch that lies there), each written as <stem>_<k>.jpg -- k counts the image's lines as its res file lists them --, trimmed to its
-    width, by the host writer. A line longer than max_w columns at that height is squeezed to max_w. -> number of files"""
+    width, by the host writer. A line longer than max_w columns at that height is squeezed to max_w. -> number of files
+    encode='gpu': the library codes and writes the files where the crops are cut (ctpn_write_line_crops: no crop visits the host or Python);
+    'gpu-entropy': the same with the Huffman coding on the device too (ctpn_write_line_crops_device). Same names, same bytes."""
+    if encode not in ("host", "gpu", "gpu-entropy"):
+        raise ValueError("encode must be 'host', 'gpu' or 'gpu-entropy'")
+    if encode != "host":
+        paths = [os.path.join(crops_dir, '{}_{}.jpg'.format(os.path.basename(nm).split('.')[0], j)) for nm, rr in zip(names, recs) for j in range(len(rr))]
+        ctx.write_line_crops(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape, paths=paths, quality=95,
+                             entropy="device" if encode == "gpu-entropy" else "host")
+        return len(paths)
     crops, widths = ctx.crop_lines(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape)
     k = 0
     for nm, rr in zip(names, recs):
@@ -304,7 +315,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
 
 
 def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
-             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE):
+             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host"):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -330,7 +341,9 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     ragged (--ragged): the JPEG files the library takes are batched by their RESIZED shapes -- one width, different heights, whatever their file
     sizes, layouts and orientations (plan_device_jobs) -- decoded into one canvas on the device (ctpn_decode_jpeg_files_ragged) and detected
     from it (ctpn_detect_submit_ragged); annotated images are cut from the fetched canvas for the host writer. What ends alone, PNG batches
-    and Pillow's files stay size-grouped. The result files are the same."""
+    and Pillow's files stay size-grouped. The result files are the same.
+    crops_encode (--crops-encode, with crops_dir): 'gpu' / 'gpu-entropy' -- the crops are JPEG-coded and written by the library where they
+    are cut (write_crops); 'host' (default): fetched and written by Pillow, as before. Same names, same bytes."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -413,7 +426,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             stats["enc_png"] += len(members)
         if slot in crop_src:                           # (a device batch is live until the second-next decode: this is one decode from its own)
             ptr, shape, imgs = crop_src.pop(slot)
-            stats["crops"] += write_crops(net.ctx, crops_dir, members, [results[nm] for nm in members], crop_h, images=imgs, device_ptr=ptr, shape=shape)
+            stats["crops"] += write_crops(net.ctx, crops_dir, members, [results[nm] for nm in members], crop_h, images=imgs, device_ptr=ptr, shape=shape,
+                                          encode=crops_encode)
         for nm in members:
             emit(nm)
 
@@ -505,7 +519,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         results[nm] = _text_detector(params).detect(boxes, scores[:, np.newaxis], img.shape[:2])
         meta[nm] = (img, scale)
         if crops_dir:
-            stats["crops"] += write_crops(net.ctx, crops_dir, [nm], [results[nm]], crop_h, images=img[None])
+            stats["crops"] += write_crops(net.ctx, crops_dir, [nm], [results[nm]], crop_h, images=img[None], encode=crops_encode)
         emit(nm)
     dt = time.time() - t0
     log('Detection of {:d} images in {:d} batches took {:.3f}s, result files included, after a header scan of {:.3f}s ({:.1f} images/s; {:d} decoded on the device, {:d} PNG files by the library, {:d} on the host)'.format(
@@ -516,12 +530,13 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         if stats["enc_png"]:
             log('... of the library\'s, {:d} are PNG files, coded on the device'.format(stats["enc_png"]))
     if crops_dir:
-        log('Text-line crops: {:d} of height {:d} cut out on the device'.format(stats["crops"], crop_h))
+        log('Text-line crops: {:d} of height {:d} cut out on the device, written by {}'.format(
+            stats["crops"], crop_h, "the host writer (Pillow)" if crops_encode == "host" else "the library (device + C++ pool)"))
     return results
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE):
+        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host"):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
@@ -531,6 +546,8 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     (ctpn_write_annotated_png_files: PNG coding on the device); 'host' (default): Pillow, as before.
     crops_dir (needs decode='gpu'): every detected line also as a rectified crop of height crop_h, <stem>_<k>.jpg in that directory, cut out
     on the device at collect time (write_crops); None (default): nothing changes.
+    crops_encode (needs crops_dir and decode='gpu'): 'gpu' -- the crops are JPEG-coded and written by the library where they are cut
+    (ctpn_write_line_crops), 'gpu-entropy' -- with the Huffman coding on the device too; 'host' (default): Pillow, as before. Same files.
     params: {name: value} of the detection tail (ctpn_set_param: RPN_* and the connector's names) for the ctx of this run; the connector's
     also reach the images that take the single-image path. None: the defaults.
     ragged (off by default): images of one resized width and different heights share batches (plan_ragged_batches with ragged_waste;
@@ -559,13 +576,17 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         raise ValueError("png_encode='gpu' writes the images of library-decoded batches: it needs decode='gpu'")
     if crops_dir is not None and decode != "gpu":
         raise ValueError("crops_dir cuts the lines out of the batches of the device path: it needs decode='gpu'")
+    if crops_encode not in ("host", "gpu", "gpu-entropy"):
+        raise ValueError("crops_encode must be 'host', 'gpu' or 'gpu-entropy'")
+    if crops_encode != "host" and (crops_dir is None or decode != "gpu"):
+        raise ValueError("crops_encode='%s' writes the crops of crops_dir on the device: it needs crops_dir and decode='gpu'" % crops_encode)
     if ragged:
         check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool)
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
-                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste)
+                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste, crops_encode=crops_encode)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -722,6 +743,9 @@ def build_parser():
     ap.add_argument('--crops', default=None, metavar='DIR',
                     help="(with --decode gpu) also write every detected line as a rectified crop <stem>_<k>.jpg of height --crop-height into DIR (ctpn_crop_lines)")
     ap.add_argument('--crop-height', type=int, default=32)
+    ap.add_argument('--crops-encode', default='host', choices=['host', 'gpu', 'gpu-entropy'],
+                    help="with --crops: 'gpu' = the library JPEG-codes and writes the crops where they are cut (ctpn_write_line_crops); 'gpu-entropy' = with "
+                         "the Huffman coding on the device too; 'host' (default) = Pillow. Same files")
     ap.add_argument('--ragged', action='store_true',
                     help="batch images of one resized width across heights (same result files); with --decode gpu / gpu-entropy the JPEG files "
                          "are decoded into ragged canvases on the device whatever their file sizes (not with --encode gpu, --png-encode gpu, --crops)")
@@ -755,7 +779,7 @@ def main(argv=None):
     if not names:
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
-        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height,
+        decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height, crops_encode=args.crops_encode,
         params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)), ragged=args.ragged, ragged_waste=args.ragged_waste)
     net.close()
 

@@ -657,6 +657,48 @@ int    ctpn_write_line_crops_device(ctpn_ctx* ctx, const uint8_t* images, int im
                                     int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality,
                                     const char* const* paths, int* widths_out, int* total_out);
 
+/* ---- Ragged batches OUT: the annotated writer and the crops over a ragged canvas: additive to ABI 10, no option and no default changes.
+ * A ragged batch is what ctpn_forward_ragged defines: a canvas n x hc x w x 3 BGR uint8 plus heights[n], 16 <= heights[i] <= hc; image i
+ * is rows [0, heights[i]) of slot i; the rows below it may hold anything and are never read as pixels. Each call's result for image i
+ * is, byte for byte, what the uniform call of the same name gives for that image ALONE -- rows [0, heights[i]) of slot i passed as n = 1,
+ * h = heights[i], w, with that image's lines and (the annotated writer) that image's scale. Nothing about JPEG coding, drawing, resizing
+ * or crop arithmetic is redefined: one copy of each body serves both forms (draw_boxes_kernel's body, resize_pixel.h, crop_pixel.h,
+ * encode_mixed_dev).
+ *   ctpn_write_annotated_files_ragged          the outlines of recs drawn per slot, bounded by the image's own height; every image resized
+ *   ctpn_write_annotated_files_ragged_device   by its OWN 1 / scales[i] into an output of its own size (dh_i = round-half-even(heights[i] /
+ *                                              scales[i]), dw_i likewise from w), all images of the call in one launch over a descriptor
+ *                                              table (resize_mixed.hip: ctpn_resize's uint8 arithmetic); an image at scale 1 is coded where
+ *                                              it lies. Then paths[i] written at `quality` by the mixed-size encoder. scales: n doubles.
+ *                                              _device: the Huffman coding on the device too; the files are byte-equal.
+ *   ctpn_crop_lines_ragged                     ctpn_crop_lines / ctpn_write_line_crops[_device] with a line's image taken from slot
+ *   ctpn_write_line_crops_ragged               `img` of the canvas and the row axis clamped at heights[img] - 1: a line that hangs below
+ *   ctpn_write_line_crops_ragged_device        its image reads the image's last row, never a canvas row. Everything else -- layout of recs /
+ *                                              line_capacity / line_counts, lines in image order, the sizing forms (crops_out == NULL with
+ *                                              capacity 0; paths == NULL), *total_out always written, no lines at all is CTPN_OK, geometry
+ *                                              limits -- is the uniform call's.
+ * canvas: in HBM (canvas_on_device: a live canvas of ctpn_decode_jpeg_*_ragged is waited for in the copy queue; any other buffer must be
+ * complete) or on the host (copied into a ctx-owned buffer in the copy queue). A caller's canvas is never modified: the outlines go onto
+ * the ctx's copy. Everything runs in the ctx's copy queue, behind the decode that produced the canvas and in front of the next one; the
+ * calls return when their files are written or their output is complete; buffers grow to the largest call seen and are then reused.
+ * CTPN_ERR_ARG, before any device work and naming the image: a null pointer, n <= 0, a height outside 16 .. hc, a scale that is not finite
+ * and positive, a resized size outside 1 .. 65535, quality outside 1 .. 100; a path that cannot be written (its name in
+ * ctpn_last_error()). CTPN_ERR_STATE: a post-processing-only ctx. Measured end to end: docs/decode_pipeline.md, "Ragged batches out". */
+int    ctpn_write_annotated_files_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                                         const double* recs, int line_capacity, const int* line_counts, const double* scales,
+                                         const char* const* paths, int quality);
+int    ctpn_write_annotated_files_ragged_device(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                                                const double* recs, int line_capacity, const int* line_counts, const double* scales,
+                                                const char* const* paths, int quality);
+int    ctpn_crop_lines_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs,
+                              int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out,
+                              int crops_on_device, size_t capacity_bytes, int* widths_out, int* total_out);
+int    ctpn_write_line_crops_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                                    const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality,
+                                    const char* const* paths, int* widths_out, int* total_out);
+int    ctpn_write_line_crops_ragged_device(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                                           const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value,
+                                           int quality, const char* const* paths, int* widths_out, int* total_out);
+
 /* ---- cv2.imread for PNG files (reference ctpn/demo.py:59; data/demo holds .jpg and .png). HOST ONLY, by the nature of READING the format: one
  * DEFLATE stream (zlib's inflate, the library libpng itself sits on) and row filters that chain from row to row -- nothing a GPU is for. One
  * file per host thread, straight into the caller's batch buffer, which ctpn_detect_submit / ctpn_forward take as host images (one

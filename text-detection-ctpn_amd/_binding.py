@@ -153,6 +153,16 @@ def _declare(lib):
                                             C.POINTER(C.c_char_p), i32p, i32p]),
         "ctpn_write_line_crops_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                    C.POINTER(C.c_char_p), i32p, i32p]),
+        "ctpn_write_annotated_files_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, f64p, C.POINTER(C.c_char_p),
+                                                        C.c_int]),
+        "ctpn_write_annotated_files_ragged_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, f64p,
+                                                               C.POINTER(C.c_char_p), C.c_int]),
+        "ctpn_crop_lines_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, vp, C.c_int,
+                                             C.c_size_t, i32p, i32p]),
+        "ctpn_write_line_crops_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_char_p), i32p, i32p]),
+        "ctpn_write_line_crops_ragged_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                          C.POINTER(C.c_char_p), i32p, i32p]),
         "ctpn_debug_png_backend": (C.c_int, [C.c_int]),
         "ctpn_png_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_png_decode": (C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t]),
@@ -1110,6 +1120,25 @@ class Context:
         _check(fn(self._h, C.c_void_p(int(device_ptr)), n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
                                                     float(scale), arr, int(quality)))
 
+    def write_annotated_files_ragged(self, images=None, device_ptr=None, shape=None, heights=None, recs=(), scales=None, paths=(), quality=95, entropy="host"):
+        """write_annotated_files for a RAGGED batch (ctpn_write_annotated_files_ragged): images = the canvas (n, hc, w, 3) on the host, or
+        device_ptr + shape = (n, hc, w) -- a live canvas of decode_jpeg_ragged is written from where it lies; heights: image i is rows
+        [0, heights[i]) of slot i; recs = one (M_i, 9) array per image; scales: one per image -- image i is resized by 1 / scales[i] into a
+        file of its own size. File i is byte-equal to write_annotated_files of that image alone. The canvas is not modified.
+        entropy="device": ctpn_write_annotated_files_ragged_device."""
+        fn = self._lib.ctpn_write_annotated_files_ragged_device if self._entropy_form(entropy) else self._lib.ctpn_write_annotated_files_ragged
+        if heights is None or scales is None:
+            raise ValueError("write_annotated_files_ragged wants heights and scales")
+        ptr, on_dev, n, hc, w, hts, keep = self._canvas(images, heights, device_ptr, shape)
+        sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+        paths = list(paths)
+        if sc.shape[0] != n or len(paths) != n:
+            raise ValueError("write_annotated_files_ragged wants one scale and one path per image")
+        packed, counts = _pack_lines(recs, None, n)
+        keep_paths, arr = _path_array(paths)
+        _check(fn(self._h, ptr, on_dev, n, hc, w, _ptr(hts, C.c_int), _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), _ptr(sc, C.c_double),
+                  arr, int(quality)))
+
     def png_encode_device_stats(self):
         """Of the last PNG call of this ctx (ctpn_png_encode_device_stats): dict(device=files coded on the device, host=files handed to the
         host form, pieces=256-byte pieces coded on the device, d2h_bytes=bytes copied device to host)."""
@@ -1162,13 +1191,25 @@ class Context:
         _check(self._lib.ctpn_write_annotated_png_files(self._h, src, on_dev, n, h, w, _ptr(packed, C.c_double), cap, _ptr(counts, C.c_int),
                                                         float(scale), arr))
 
+    @staticmethod
+    def _ragged_heights(heights, n):
+        """heights= of crop_lines / write_line_crops -> the extra argument of the *_ragged call: () for a uniform batch"""
+        if heights is None:
+            return None, ()
+        hts = np.ascontiguousarray(heights, dtype=np.int32).reshape(-1)
+        if hts.shape[0] != n:
+            raise ValueError("one height per image")
+        return hts, (_ptr(hts, C.c_int),)
+
     def crop_lines(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None,
-                   out_device_ptr=None, out_capacity=0):
+                   out_device_ptr=None, out_capacity=0, heights=None):
         """One rectified crop of height crop_h per text line, cut out on the device (ctpn_crop_lines). images: (n, h, w, 3) uint8 on the host,
         or device_ptr + shape = (n, h, w) -- a live batch of decode_jpeg_batch is cropped where it lies, without a fetch. recs: one (M_i, 9)
         array per image as detect / detect_collect return them, or an (n, capacity, 9) array with line_counts. -> (crops, widths): crops
         (total, crop_h, max_w, 3) BGR uint8, lines in image order, columns >= widths[k] of crop k filled with pad_value (a longer line is
-        squeezed to max_w). With out_device_ptr (4-byte aligned, out_capacity bytes) the crops stay in device memory and crops is None."""
+        squeezed to max_w). With out_device_ptr (4-byte aligned, out_capacity bytes) the crops stay in device memory and crops is None.
+        heights: the batch is a ragged canvas (n, hc, w) -- image i is rows [0, heights[i]) of slot i (ctpn_crop_lines_ragged): the crops
+        are those of every image alone, and a line that hangs below its image reads the image's last row, never a canvas row."""
         if device_ptr is None:
             images = np.ascontiguousarray(images, dtype=np.uint8)
             if images.ndim == 3:
@@ -1182,10 +1223,12 @@ class Context:
         packed, counts = _pack_lines(recs, line_counts, n)
         widths = np.zeros((max(int(counts.sum()), 1),), np.int32)
         total = C.c_int(0)
+        hts, hts_arg = self._ragged_heights(heights, n)
+        fn = self._lib.ctpn_crop_lines if hts is None else self._lib.ctpn_crop_lines_ragged
 
         def call(out, out_on_dev, capacity):
-            _check(self._lib.ctpn_crop_lines(self._h, src, on_dev, n, h, w, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h),
-                                             int(max_w), int(pad_value), out, out_on_dev, capacity, _ptr(widths, C.c_int), C.byref(total)))
+            _check(fn(self._h, src, on_dev, n, h, w, *hts_arg, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h),
+                      int(max_w), int(pad_value), out, out_on_dev, capacity, _ptr(widths, C.c_int), C.byref(total)))
         if out_device_ptr is not None:
             call(C.c_void_p(int(out_device_ptr)), 1, int(out_capacity))
             return None, widths[: total.value].copy()
@@ -1196,12 +1239,17 @@ class Context:
         return crops, widths[: total.value].copy()
 
     def write_line_crops(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None, paths=None,
-                         quality=95, entropy="host"):
+                         quality=95, entropy="host", heights=None):
         """crop_lines with the crops written as JPEG files where they are cut (ctpn_write_line_crops): crop k, crop_h x widths[k], goes to
         paths[k] at `quality` -- image 0's lines first, then image 1's, ... --, byte-equal to Pillow's save(quality=quality, subsampling=2) of
         crop_lines' crops[k, :, :widths[k]]. No crop visits the host. paths=None sizes the call. -> widths (int32, one per line).
-        entropy="device": ctpn_write_line_crops_device, the same files with the Huffman coding on the device."""
-        fn = self._lib.ctpn_write_line_crops_device if self._entropy_form(entropy) else self._lib.ctpn_write_line_crops
+        entropy="device": ctpn_write_line_crops_device, the same files with the Huffman coding on the device.
+        heights: the batch is a ragged canvas, as in crop_lines (ctpn_write_line_crops_ragged / ctpn_write_line_crops_ragged_device)."""
+        dev = self._entropy_form(entropy)
+        if heights is None:
+            fn = self._lib.ctpn_write_line_crops_device if dev else self._lib.ctpn_write_line_crops
+        else:
+            fn = self._lib.ctpn_write_line_crops_ragged_device if dev else self._lib.ctpn_write_line_crops_ragged
         if device_ptr is None:
             images = np.ascontiguousarray(images, dtype=np.uint8)
             if images.ndim == 3:
@@ -1222,8 +1270,9 @@ class Context:
             if len(paths) != lines:
                 raise ValueError("write_line_crops wants one path per line")
             keep, arr = _path_array(paths)
-        _check(fn(self._h, src, on_dev, n, h, w, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h), int(max_w), int(pad_value),
-                  int(quality), arr, _ptr(widths, C.c_int), C.byref(total)))
+        hts, hts_arg = self._ragged_heights(heights, n)
+        _check(fn(self._h, src, on_dev, n, h, w, *hts_arg, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h), int(max_w),
+                  int(pad_value), int(quality), arr, _ptr(widths, C.c_int), C.byref(total)))
         return widths[: total.value].copy()
 
     def encode_jpeg_mixed(self, images=None, quality=95, entropy="host", device_ptr=None, heights=None, widths=None, pitches=None, offsets=None):

@@ -1,6 +1,8 @@
 // C ABI of libctpn_hip.so, crop unit: the detected text lines of a batch cut out of its images ON THE DEVICE, one rectified image of fixed
 // height per line -- what a recogniser behind the detector reads (kernel and descriptor: crop.hip, arithmetic: crop_pixel.h). An output
 // stage in the ctx's copy queue like the annotated writer (api_out_stage.hip): behind the decode that produced the batch, in front of the next.
+// The *_ragged entry points are the same calls over a ragged canvas: a table of heights rides with the descriptors, and the kernel takes a
+// line's image from its slot and clamps the row axis at the image's own last row.
 #include <climits>
 #include <cmath>
 
@@ -31,13 +33,17 @@ static int crop_reserve(ctpn_ctx* c, size_t desc_bytes) {
   return grow_dev(&K.desc_dev, K.desc_bytes, desc_bytes);
 }
 
-// the argument checks of ctpn_crop_lines and pass 1, host only: every line's width (what the sizing call is for)
-static int crop_plan(const char* who_, ctpn_ctx* c, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value,
-                     int* widths_out, int* total_out, std::vector<int>& widths) {
+// the argument checks of ctpn_crop_lines and pass 1, host only: every line's width (what the sizing call is for).
+// ragged: the batch is a canvas n x h x w x 3 and heights[i] (16 .. h) the rows of slot i that are image i (the *_ragged entry points)
+static int crop_plan(const char* who_, ctpn_ctx* c, int n, int h, int w, const int* heights, bool ragged, const double* recs, int line_capacity, const int* line_counts, int crop_h,
+                     int max_w, int pad_value, int* widths_out, int* total_out, std::vector<int>& widths) {
   const std::string who(who_);
   if (total_out) *total_out = 0;
-  if (!c || !line_counts || !total_out) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (!c || !line_counts || !total_out || (ragged && !heights)) return fail(CTPN_ERR_ARG, who + ": null pointer");
   if (n <= 0 || h <= 0 || w <= 0 || line_capacity < 0) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size");
+  for (int i = 0; ragged && i < n; ++i)
+    if (heights[i] < 16 || heights[i] > h)
+      return fail(CTPN_ERR_ARG, who + ": image " + std::to_string(i) + ": height " + std::to_string(heights[i]) + " outside 16 .. " + std::to_string(h));
   if (int rc = crop_check_geometry(who_, crop_h, max_w)) return rc;
   if (pad_value < 0 || pad_value > 255) return fail(CTPN_ERR_ARG, who + ": pad_value must be 0 .. 255");
   long long total = 0;
@@ -60,30 +66,34 @@ static int crop_plan(const char* who_, ctpn_ctx* c, int n, int h, int w, const d
 }
 
 // pass 2 in the ctx's copy queue: descriptors, the batch's pixels, the kernel into out_dev (total x crop_h x max_w x 3); no host wait
-static int crop_cut(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
-                    const std::vector<int>& widths, int crop_h, int max_w, int pad_value, uint8_t* out_dev) {
+// heights (nullable): a ragged canvas; the table rides behind the descriptors, in the same page-locked block and the same copy
+static int crop_cut(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const int* heights, const double* recs, int line_capacity,
+                    const int* line_counts, const std::vector<int>& widths, int crop_h, int max_w, int pad_value, uint8_t* out_dev) {
   auto& K = c->crop;
   hipStream_t qs = c->stream_c;
   const size_t total = widths.size(), line_bytes = (size_t)crop_h * max_w * 3;
   int rc;
-  if ((rc = crop_reserve(c, total * CROP_DESC_BYTES))) return rc;
+  const size_t desc_bytes = total * CROP_DESC_BYTES, table_bytes = desc_bytes + (heights ? (size_t)n * sizeof(int) : 0);
+  if ((rc = crop_reserve(c, table_bytes))) return rc;
   for (int i = 0, k = 0; i < n; ++i)
     for (int j = 0; j < line_counts[i]; ++j, ++k)
       crop_fill_desc(recs + ((size_t)i * line_capacity + j) * 9, i, widths[k], (size_t)k * line_bytes, (char*)K.desc_host + (size_t)k * CROP_DESC_BYTES);
-  CTPN_HIP_TRY(hipMemcpyAsync(K.desc_dev, K.desc_host, total * CROP_DESC_BYTES, hipMemcpyHostToDevice, qs));
+  if (heights) std::memcpy((char*)K.desc_host + desc_bytes, heights, (size_t)n * sizeof(int));
+  CTPN_HIP_TRY(hipMemcpyAsync(K.desc_dev, K.desc_host, table_bytes, hipMemcpyHostToDevice, qs));
+  const int* heights_dev = heights ? (const int*)((const char*)K.desc_dev + desc_bytes) : nullptr;
   const uint8_t* px;
   if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 0, K.img_dev, K.img_bytes, qs, px))) return rc;
-  return launch_crop_lines(px, K.desc_dev, (int)total, out_dev, h, w, crop_h, max_w, pad_value, qs);
+  return launch_crop_lines(px, K.desc_dev, (int)total, out_dev, h, w, heights_dev, crop_h, max_w, pad_value, qs);
 }
 
-// ctpn_write_line_crops / ctpn_write_line_crops_device
-static int write_line_crops_impl(ctpn_ctx* c, const char* who_, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
-                                 const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out,
-                                 bool device_entropy) {
+// ctpn_write_line_crops / ctpn_write_line_crops_device and their _ragged forms
+static int write_line_crops_impl(ctpn_ctx* c, const char* who_, const uint8_t* images, int images_on_device, int n, int h, int w, const int* heights, bool ragged,
+                                 const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths,
+                                 int* widths_out, int* total_out, bool device_entropy) {
   const std::string who(who_);
   std::vector<int> widths;
   int rc;
-  if ((rc = crop_plan(who_, c, n, h, w, recs, line_capacity, line_counts, crop_h, max_w, pad_value, widths_out, total_out, widths))) return rc;
+  if ((rc = crop_plan(who_, c, n, h, w, heights, ragged, recs, line_capacity, line_counts, crop_h, max_w, pad_value, widths_out, total_out, widths))) return rc;
   if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
   if (!paths) return CTPN_OK;      // the sizing call
   const size_t total = widths.size();
@@ -97,12 +107,42 @@ static int write_line_crops_impl(ctpn_ctx* c, const char* who_, const uint8_t* i
   // the encoder's aligned read (jenc_load4) stays inside a crop's pixels where its rows start 4-byte aligned: the buffer is a device
   // allocation, a crop's offset and the pitch are multiples of 12 (max_w % 4 == 0, crop_check_geometry)
   if (((uintptr_t)K.out_dev & 3) || (pitch & 3) || (line_bytes & 3)) return fail(CTPN_ERR_STATE, who + ": the crop rows are not 4-byte aligned");
-  if ((rc = crop_cut(c, images, images_on_device, n, h, w, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, K.out_dev))) return rc;
+  if ((rc = crop_cut(c, images, images_on_device, n, h, w, heights, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, K.out_dev))) return rc;
   // encoded where they lie, behind the kernel in the same queue: crop k is crop_h x widths[k] at pitch 3 max_w -- the pad columns never enter a file
-  std::vector<int> heights(total, crop_h);
+  std::vector<int> crop_heights(total, crop_h);
   std::vector<size_t> pitches(total, pitch), offsets(total);
   for (size_t k = 0; k < total; ++k) offsets[k] = k * line_bytes;
-  return encode_mixed_dev(c, who_, K.out_dev, (int)total, heights.data(), widths.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
+  return encode_mixed_dev(c, who_, K.out_dev, (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
+}
+
+// ctpn_crop_lines / ctpn_crop_lines_ragged
+static int crop_lines_impl(ctpn_ctx* c, const char* who_, const uint8_t* images, int images_on_device, int n, int h, int w, const int* heights, bool ragged, const double* recs,
+                           int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device, size_t capacity_bytes,
+                           int* widths_out, int* total_out) {
+  const std::string who(who_);
+  std::vector<int> widths;
+  if (int rc = crop_plan(who_, c, n, h, w, heights, ragged, recs, line_capacity, line_counts, crop_h, max_w, pad_value, widths_out, total_out, widths)) return rc;
+  const size_t total = widths.size(), line_bytes = (size_t)crop_h * max_w * 3;
+  if (!crops_out && capacity_bytes == 0) return CTPN_OK;      // the sizing call
+  if (total == 0) return CTPN_OK;
+  const size_t need = total * line_bytes;
+  if (capacity_bytes < need) return fail(CTPN_ERR_CAPACITY, who + ": the output holds " + std::to_string(capacity_bytes) + " bytes, the crops need " + std::to_string(need));
+  if (!crops_out || !images) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (crops_on_device && ((uintptr_t)crops_out & 3)) return fail(CTPN_ERR_ARG, who + ": a device output must be 4-byte aligned");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  auto& K = c->crop;
+  hipStream_t qs = c->stream_c;
+  int rc;
+  uint8_t* out = crops_out;
+  if (!crops_on_device) {
+    if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, need))) return rc;
+    out = K.out_dev;
+  }
+  if ((rc = crop_cut(c, images, images_on_device, n, h, w, heights, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, out))) return rc;
+  if (!crops_on_device) CTPN_HIP_TRY(hipMemcpyAsync(crops_out, K.out_dev, need, hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipEventRecord(K.ev_done, qs));
+  CTPN_HIP_TRY(hipEventSynchronize(K.ev_done));
+  return CTPN_OK;
 }
 
 }  // namespace ctpn
@@ -120,41 +160,40 @@ int ctpn_line_crop_width(const double* rec9, int crop_h, int max_w, int* width_o
 int ctpn_crop_lines(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,
                     const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device, size_t capacity_bytes,
                     int* widths_out, int* total_out) {
-  std::vector<int> widths;
-  if (int rc = crop_plan("ctpn_crop_lines", c, n, h, w, recs, line_capacity, line_counts, crop_h, max_w, pad_value, widths_out, total_out, widths)) return rc;
-  const size_t total = widths.size(), line_bytes = (size_t)crop_h * max_w * 3;
-  if (!crops_out && capacity_bytes == 0) return CTPN_OK;      // the sizing call
-  if (total == 0) return CTPN_OK;
-  const size_t need = total * line_bytes;
-  if (capacity_bytes < need) return fail(CTPN_ERR_CAPACITY, "ctpn_crop_lines: the output holds " + std::to_string(capacity_bytes) + " bytes, the crops need " + std::to_string(need));
-  if (!crops_out || !images) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: null pointer");
-  if (crops_on_device && ((uintptr_t)crops_out & 3)) return fail(CTPN_ERR_ARG, "ctpn_crop_lines: a device output must be 4-byte aligned");
-  CTPN_HIP_TRY(hipSetDevice(c->device));
-  auto& K = c->crop;
-  hipStream_t qs = c->stream_c;
-  int rc;
-  uint8_t* out = crops_out;
-  if (!crops_on_device) {
-    if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, need))) return rc;
-    out = K.out_dev;
-  }
-  if ((rc = crop_cut(c, images, images_on_device, n, h, w, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, out))) return rc;
-  if (!crops_on_device) CTPN_HIP_TRY(hipMemcpyAsync(crops_out, K.out_dev, need, hipMemcpyDeviceToHost, qs));
-  CTPN_HIP_TRY(hipEventRecord(K.ev_done, qs));
-  CTPN_HIP_TRY(hipEventSynchronize(K.ev_done));
-  return CTPN_OK;
+  return crop_lines_impl(c, "ctpn_crop_lines", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, crops_out,
+                         crops_on_device, capacity_bytes, widths_out, total_out);
+}
+
+int ctpn_crop_lines_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs, int line_capacity,
+                           const int* line_counts, int crop_h, int max_w, int pad_value, uint8_t* crops_out, int crops_on_device, size_t capacity_bytes,
+                           int* widths_out, int* total_out) {
+  return crop_lines_impl(c, "ctpn_crop_lines_ragged", canvas, canvas_on_device, n, hc, w, heights, true, recs, line_capacity, line_counts, crop_h, max_w, pad_value, crops_out,
+                         crops_on_device, capacity_bytes, widths_out, total_out);
 }
 
 int ctpn_write_line_crops(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
                           int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out) {
-  return write_line_crops_impl(c, "ctpn_write_line_crops", images, images_on_device, n, h, w, recs, line_capacity, line_counts, crop_h, max_w, pad_value, quality, paths,
+  return write_line_crops_impl(c, "ctpn_write_line_crops", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, quality, paths,
                                widths_out, total_out, false);
 }
 
 int ctpn_write_line_crops_device(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
                                  int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out) {
-  return write_line_crops_impl(c, "ctpn_write_line_crops_device", images, images_on_device, n, h, w, recs, line_capacity, line_counts, crop_h, max_w, pad_value, quality, paths,
+  return write_line_crops_impl(c, "ctpn_write_line_crops_device", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, quality, paths,
                                widths_out, total_out, true);
+}
+
+int ctpn_write_line_crops_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs, int line_capacity,
+                                 const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out) {
+  return write_line_crops_impl(c, "ctpn_write_line_crops_ragged", canvas, canvas_on_device, n, hc, w, heights, true, recs, line_capacity, line_counts, crop_h, max_w, pad_value,
+                               quality, paths, widths_out, total_out, false);
+}
+
+int ctpn_write_line_crops_ragged_device(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs,
+                                        int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths,
+                                        int* widths_out, int* total_out) {
+  return write_line_crops_impl(c, "ctpn_write_line_crops_ragged_device", canvas, canvas_on_device, n, hc, w, heights, true, recs, line_capacity, line_counts, crop_h, max_w,
+                               pad_value, quality, paths, widths_out, total_out, true);
 }
 
 }  // extern "C"

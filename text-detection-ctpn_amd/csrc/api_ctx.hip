@@ -385,7 +385,8 @@ int ctpn_destroy(ctpn_ctx* c) {
   for (void* p : {(void*)c->jh.stage_dev, (void*)c->jh.work_dev}) if (p) (void)hipFree(p);
   for (void* p : {(void*)c->jh.stage_host, (void*)c->jh.res_host}) if (p) (void)hipHostFree(p);
   for (void* p : c->jpeg_retired) (void)hipFree(p);
-  for (void* p : {(void*)c->stage.img_dev, (void*)c->stage.rs_dev, (void*)c->stage.recs_dev, (void*)c->stage.cnt_dev}) if (p) (void)hipFree(p);
+  for (void* p : {(void*)c->stage.img_dev, (void*)c->stage.rs_dev, (void*)c->stage.recs_dev, (void*)c->stage.cnt_dev, (void*)c->stage.rm_dev}) if (p) (void)hipFree(p);
+  if (c->stage.rm_host) (void)hipHostFree(c->stage.rm_host);
   for (void* p : {(void*)c->enc.coef_dev, c->enc.qtab_dev, (void*)c->enc.huff_dev, c->enc.huff_tab_dev, (void*)c->enc.mix_dev}) if (p) (void)hipFree(p);
   for (void* p : {(void*)c->enc.coef_host, c->enc.qtab_host, (void*)c->enc.huff_host, (void*)c->enc.scan_host, (void*)c->enc.mix_host}) if (p) (void)hipHostFree(p);
   if (c->enc.ev_done) (void)hipEventDestroy(c->enc.ev_done);

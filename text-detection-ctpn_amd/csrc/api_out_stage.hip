@@ -4,8 +4,8 @@
 
 namespace ctpn {
 
-// a live batch of ctpn_decode_jpeg_batch was produced in the ctx's copy queue: qs waits for it. It is only read (a forward may read it too)
-static int wait_live_batch(ctpn_ctx* c, const uint8_t* images_dev, hipStream_t qs) {
+// a live batch of ctpn_decode_jpeg_batch (or a live canvas of ctpn_decode_jpeg_*_ragged) was produced in the ctx's copy queue: qs waits for it. It is only read (a forward may read it too)
+int wait_live_batch(ctpn_ctx* c, const uint8_t* images_dev, hipStream_t qs) {
   for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images_dev) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
   return CTPN_OK;
 }

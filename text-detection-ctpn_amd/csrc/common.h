@@ -205,6 +205,15 @@ int launch_conv_first_from_q(const void* q, const void* frags, void* out, DType 
 // cv2.resize(INTER_LINEAR) restated (preprocess.hip); src / dst: n x h x w x 3 and n x dh x dw x 3, uint8 or float32, device pointers
 int resize_out_dim(int src, double f);
 int launch_resize_linear(const void* src, void* dst, int is_f32, int n, int h, int w, int dh, int dw, double fx, double fy, hipStream_t s);
+// resize_mixed.hip: the uint8 form over a TABLE of images of different sizes, each by its own factor (descriptor, work items, per-thread text:
+// resize_mixed_dev.h). resize_mixed_fill writes n descriptors of RM_DESC_BYTES each with their prefix sums and returns the work items (-1:
+// more than a grid holds); image i's destination rows are resize_mixed_pitch(dw[i]) bytes apart, its block dh[i] rows of them at dst_off[i]
+// (a multiple of 4); inv_f[i]: 1 / f as launch_resize_linear forms it
+constexpr size_t RM_DESC_BYTES = 64;
+size_t resize_mixed_pitch(int dw);
+long long resize_mixed_fill(void* table, int n, const int* h, const int* w, const int* dh, const int* dw, const long long* src_off, const long long* src_pitch,
+                            const long long* dst_off, const double* inv_f);
+int launch_resize_linear_mixed(const uint8_t* src_dev, uint8_t* dst_dev, const void* tab_dev, int n, long long total_items, hipStream_t s);
 int launch_cvt_bf16(const float* in, uint16_t* out, int n, int hw, hipStream_t s);
 // the two LDS-DMA helper forms of conv3x3_base.h on `tiles` 1-KiB tiles of src (conv3x3.hip; test hook behind ctpn_debug_lds_dma)
 int launch_lds_dma_check(const void* src, void* out_clobber, void* out_keep, int tiles, hipStream_t s);
@@ -377,13 +386,17 @@ struct JheBatchDev {
 };
 int launch_jpeg_huff_enc(const JheBatchDev& B, bool zigzag, hipStream_t s);
 int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* counts_dev, int line_capacity, int n, int h, int w, hipStream_t s);
+// ... on a ragged canvas n x hc x w x 3: image i is rows [0, heights_dev[i]) of slot i, and nothing is drawn below them
+int launch_draw_boxes_ragged(uint8_t* canvas_dev, const double* recs_dev, const int* counts_dev, const int* heights_dev, int line_capacity, int n, int hc, int w, hipStream_t s);
 
 // crop.hip: rectified crops of text lines out of device images (arithmetic: crop_pixel.h). The host fills one descriptor per line
 // (crop_fill_desc: coordinates, image, width, byte offset of its crop_h x max_w x 3 block); the kernel reads the table from device memory
 constexpr size_t CROP_DESC_BYTES = 80;
 int crop_line_width(const double* rec9, int crop_h, int max_w);
 void crop_fill_desc(const double* rec9, int img, int wc, size_t out_off, void* desc);
-int launch_crop_lines(const uint8_t* imgs_dev, const void* descs_dev, int total, uint8_t* out_dev, int h, int w, int crop_h, int max_w, int pad, hipStream_t s);
+// heights_dev (nullable): the images are the slots of a ragged canvas n x h x w x 3 -- a line's image is rows [0, heights_dev[img]) of slot img
+int launch_crop_lines(const uint8_t* imgs_dev, const void* descs_dev, int total, uint8_t* out_dev, int h, int w, const int* heights_dev, int crop_h, int max_w, int pad,
+                      hipStream_t s);
 
 // png_enc.hip: the DEFLATE block of PNG files on the device (per-piece source, the structures and the file's definition: png_enc_dev.h).
 // hist: the images' symbol counts (n x 286, cleared by the caller); code: lengths, prefix sum + Adler-32, write (words cleared by the caller)

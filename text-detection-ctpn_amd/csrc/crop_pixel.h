@@ -87,6 +87,14 @@ __host__ __device__ __forceinline__ void crop_sample(const uint8_t* img, int h, 
   }
 }
 
+// The image a line lies in: slot `img` of a batch whose slots are slot_h rows of w pixels. heights == null: a uniform batch, the image
+// fills its slot. Else a ragged canvas: the image is rows [0, heights[img]) of its slot -- h is what crop_sample clamps the row axis at,
+// so a line that hangs below its image reads the image's last row and never a canvas row under it.
+__host__ __device__ __forceinline__ const uint8_t* crop_image(const uint8_t* imgs, int img, int slot_h, int w, const int* heights, int& h) {
+  h = heights ? heights[img] : slot_h;
+  return imgs + (size_t)img * slot_h * w * 3;
+}
+
 // four consecutive output pixels of one row, columns u0 .. u0 + 3 (u0 % 4 == 0), as the three dwords they are stored in: columns from wc
 // on hold pad. cols: crop_column of the four (those from wc on are not read).
 __host__ __device__ __forceinline__ void crop_quad(const uint8_t* img, int h, int w, const CropColumn (&cols)[4], int u0, int wc, int v, int crop_h,

@@ -195,6 +195,8 @@ struct ctpn_ctx {
     uint8_t* img_dev = nullptr; size_t img_bytes = 0;          // the batch's pixels: staged host images, or the copy the outlines are drawn on
     uint8_t* rs_dev = nullptr; size_t rs_bytes = 0;            // ... resized by 1 / scale
     double* recs_dev = nullptr; size_t recs_bytes = 0; int* cnt_dev = nullptr; size_t cnt_bytes = 0;      // the outlines' records and counts
+    // ctpn_write_annotated_files_ragged (api_out_ragged.hip): [heights(n) | descriptors of the resized images], page-locked / device
+    uint8_t* rm_host = nullptr; size_t rm_host_bytes = 0; uint8_t* rm_dev = nullptr; size_t rm_bytes = 0;
   } stage;
   // ctpn_encode_jpeg_batch / ctpn_write_annotated_files (api_jpeg_out.hip): ONE set of buffers, for the reason the stage's set is one
   struct EncBufs {
@@ -438,6 +440,7 @@ int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, cons
                       const int* keep1, int keep_stride, const int* cnt1, int n, bool mw, hipStream_t s, const char* what);
 // the output stage of the writers and the crops (api_out_stage.hip). stage_pixels: a call's pixels where its kernels on qs may read them --
 // host images copied into buf (ctx-owned, grown to bytes + slack), device images in place, behind a live ctpn_decode_jpeg_batch batch's event
+int wait_live_batch(ctpn_ctx* c, const uint8_t* images_dev, hipStream_t qs);      // qs waits for the decode that produced images_dev, if it is a live batch or canvas
 int stage_pixels(ctpn_ctx* c, const uint8_t* images, int on_device, size_t bytes, size_t slack, uint8_t*& buf, size_t& buf_bytes, hipStream_t qs, const uint8_t*& px);
 // the ctpn_write_annotated_* entry points up to the file format: their argument checks (format: "JPEG" or "PNG", for the message; size_check,
 // nullable: the format's own check of both sizes), then the ctx's copy of the images, outlines drawn, resized by 1 / scale, at px (dh x dw)

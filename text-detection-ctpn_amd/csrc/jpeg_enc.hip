@@ -335,11 +335,8 @@ __global__ __launch_bounds__(256) void jpeg_fdct_mixed_kernel(const uint8_t* __r
 // function's order, the samples of a segment spread over the lanes. Later lines overwrite earlier ones, so a barrier stands wherever the
 // colour changes (segments of one colour write the same bytes, in whatever order). The sample positions are the host's doubles: this unit
 // is compiled without FMA contraction, like text_connector.cpp.
-__global__ __launch_bounds__(256) void draw_boxes_kernel(uint8_t* __restrict__ imgs, const double* __restrict__ recs, const int* __restrict__ counts, int line_capacity, int h, int w) {
-  uint8_t* img = imgs + (long long)blockIdx.x * h * w * 3;
-  const double* rr = recs + (long long)blockIdx.x * line_capacity * 9;
-  int n_lines = counts[blockIdx.x];
-  n_lines = n_lines < line_capacity ? n_lines : line_capacity;
+// The body, for ONE h x w image at img with its lines at rr: both kernels below run it, every thread of the workgroup through all of its barriers
+__device__ __forceinline__ void draw_boxes_image(uint8_t* __restrict__ img, const double* __restrict__ rr, int n_lines, int h, int w) {
   int last_green = -1;
   for (int li = 0; li < n_lines; ++li) {
     const double* b = rr + (long long)li * 9;
@@ -389,6 +386,21 @@ __global__ __launch_bounds__(256) void draw_boxes_kernel(uint8_t* __restrict__ i
   }
 }
 
+// n images of one size, tightly packed
+__global__ __launch_bounds__(256) void draw_boxes_kernel(uint8_t* __restrict__ imgs, const double* __restrict__ recs, const int* __restrict__ counts, int line_capacity, int h, int w) {
+  const int n_lines = counts[blockIdx.x];
+  draw_boxes_image(imgs + (long long)blockIdx.x * h * w * 3, recs + (long long)blockIdx.x * line_capacity * 9, n_lines < line_capacity ? n_lines : line_capacity, h, w);
+}
+
+// the slots of a ragged canvas n x hc x w x 3: image i is rows [0, heights[i]) of slot i. Row bounds and the clipping of the sample ranges
+// take the image's own height (clamped to the slot's), so nothing is drawn into the rows below an image
+__global__ __launch_bounds__(256) void draw_boxes_ragged_kernel(uint8_t* __restrict__ canvas, const double* __restrict__ recs, const int* __restrict__ counts,
+                                                                const int* __restrict__ heights, int line_capacity, int hc, int w) {
+  const int n_lines = counts[blockIdx.x], hi = heights[blockIdx.x];
+  const int h = hi < 0 ? 0 : (hi < hc ? hi : hc);
+  draw_boxes_image(canvas + (long long)blockIdx.x * hc * w * 3, recs + (long long)blockIdx.x * line_capacity * 9, n_lines < line_capacity ? n_lines : line_capacity, h, w);
+}
+
 int launch_jpeg_fdct(const uint8_t* img_dev, int16_t* coef_dev, const JencQ* qtab_dev, const JpegGeom& g, int n, hipStream_t s) {
   const int mcux = g.bw[1], mcuy = g.bh[1];
   if (n <= 0 || n > 65535 || mcuy > 65535 || mcux <= 0) return fail(CTPN_ERR_ARG, "jpeg encode: grid out of range");
@@ -407,6 +419,12 @@ int launch_draw_boxes(uint8_t* imgs_dev, const double* recs_dev, const int* coun
   if (n <= 0) return fail(CTPN_ERR_ARG, "draw_boxes: empty batch");
   hipLaunchKernelGGL(draw_boxes_kernel, dim3((unsigned)n), dim3(256), 0, s, imgs_dev, recs_dev, counts_dev, line_capacity, h, w);
   return launch_status("draw_boxes");
+}
+
+int launch_draw_boxes_ragged(uint8_t* canvas_dev, const double* recs_dev, const int* counts_dev, const int* heights_dev, int line_capacity, int n, int hc, int w, hipStream_t s) {
+  if (n <= 0 || hc <= 0 || w <= 0 || !heights_dev) return fail(CTPN_ERR_ARG, "draw_boxes: empty batch");
+  hipLaunchKernelGGL(draw_boxes_ragged_kernel, dim3((unsigned)n), dim3(256), 0, s, canvas_dev, recs_dev, counts_dev, heights_dev, line_capacity, hc, w);
+  return launch_status("draw_boxes (ragged)");
 }
 
 }  // namespace ctpn

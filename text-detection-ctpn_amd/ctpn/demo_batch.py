@@ -19,6 +19,11 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
     --crops-encode gpu | gpu-entropy: the crops are JPEG-coded and written by the library where they are cut (ctpn_write_line_crops),
     the same files as Pillow's (the default, host).
 
+  * with --ragged --ragged-outputs (and --decode gpu / gpu-entropy) the library's writers take the ragged batches too: --encode gpu /
+    gpu-entropy writes their annotated images from the canvas on the device, every image at its own size
+    (ctpn_write_annotated_files_ragged; the canvas is not fetched), and --crops cuts their lines from the canvas
+    (ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged). Same names, same bytes as without --ragged.
+
   * cfg.TEST.RPN_* of the loaded text.yml go into the ctx's tail parameters (ctpn_set_param), so the batched path honours the file like
     the single-image path; --connector NAME=VALUE (repeatable; TextLineCfg's names, MIN_LINE_WIDTH for TEXT_PROPOSALS_WIDTH *
     MIN_NUM_PROPOSALS) sets the connector's thresholds for the batches and for the images that take the single-image path.
@@ -154,18 +159,25 @@ def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE):
     return jobs
 
 
-def check_ragged_options(decode="host", encode="host", png_encode="host", crops_dir=None, decode_procs=0, decode_pool=None):
+def check_ragged_options(decode="host", encode="host", png_encode="host", crops_dir=None, decode_procs=0, decode_pool=None, ragged_outputs=False, ragged=True):
     """run(..., ragged=True) with these options: ValueError for the combinations that stay uniform. The process-pool decoder fills
-    shared-memory batches of one shape; the library's writers (encode / png_encode = 'gpu') and the crops take uniform device batches."""
+    shared-memory batches of one shape; the library's writers (encode / png_encode = 'gpu') and the crops take uniform device batches.
+    ragged_outputs: the JPEG writer and the crops take the ragged batches of the device path as well (ctpn_write_annotated_files_ragged,
+    ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged) -- it needs ragged and decode='gpu' / 'gpu-entropy'; encode and crops_dir then
+    pass, png_encode='gpu' stays refused (no PNG writer over a canvas)."""
+    if ragged_outputs and not ragged:
+        raise ValueError("ragged_outputs writes the outputs of ragged batches: it needs ragged=True")
+    if ragged_outputs and decode not in ("gpu", "gpu-entropy"):
+        raise ValueError("ragged_outputs writes the outputs of ragged device batches: it needs decode='gpu' or 'gpu-entropy'")
     if decode_procs > 0 or decode_pool is not None:
         raise ValueError("ragged batches are built by the thread-pool decoder (decode='host') or on the device (decode='gpu' / 'gpu-entropy'): "
                          "the process-pool decoder stays size-grouped")
     if decode in ("gpu", "gpu-entropy"):
-        if encode != "host":
+        if encode != "host" and not ragged_outputs:
             raise ValueError("ragged device decode does not combine with encode='gpu' / 'gpu-entropy': ctpn_write_annotated_files takes uniform batches")
         if png_encode != "host":
             raise ValueError("ragged device decode does not combine with png_encode='gpu': ctpn_write_annotated_png_files takes uniform batches")
-        if crops_dir is not None:
+        if crops_dir is not None and not ragged_outputs:
             raise ValueError("ragged device decode does not combine with crops_dir: ctpn_crop_lines takes uniform batches")
 
 
@@ -291,20 +303,21 @@ def _read(name):
         return f.read()
 
 
-def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None, encode="host"):
+def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None, encode="host", heights=None):
     """The text lines of one batch as rectified crops of height crop_h (ctpn_crop_lines: cut out on the device, from host images or from
     a batch that lies there), each written as <stem>_<k>.jpg -- k counts the image's lines as its res file lists them --, trimmed to its
     width, by the host writer. A line longer than max_w columns at that height is squeezed to max_w. -> number of files
     encode='gpu': the library codes and writes the files where the crops are cut (ctpn_write_line_crops: no crop visits the host or Python);
-    'gpu-entropy': the same with the Huffman coding on the device too (ctpn_write_line_crops_device). Same names, same bytes."""
+    'gpu-entropy': the same with the Huffman coding on the device too (ctpn_write_line_crops_device). Same names, same bytes.
+    heights: images / device_ptr is a ragged canvas, image i in rows [0, heights[i]) of slot i (the *_ragged calls). Same names, same bytes."""
     if encode not in ("host", "gpu", "gpu-entropy"):
         raise ValueError("encode must be 'host', 'gpu' or 'gpu-entropy'")
     if encode != "host":
         paths = [os.path.join(crops_dir, '{}_{}.jpg'.format(os.path.basename(nm).split('.')[0], j)) for nm, rr in zip(names, recs) for j in range(len(rr))]
         ctx.write_line_crops(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape, paths=paths, quality=95,
-                             entropy="device" if encode == "gpu-entropy" else "host")
+                             entropy="device" if encode == "gpu-entropy" else "host", heights=heights)
         return len(paths)
-    crops, widths = ctx.crop_lines(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape)
+    crops, widths = ctx.crop_lines(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape, heights=heights)
     k = 0
     for nm, rr in zip(names, recs):
         stem = os.path.basename(nm).split('.')[0]
@@ -315,7 +328,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
 
 
 def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
-             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host"):
+             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -343,7 +356,11 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     from it (ctpn_detect_submit_ragged); annotated images are cut from the fetched canvas for the host writer. What ends alone, PNG batches
     and Pillow's files stay size-grouped. The result files are the same.
     crops_encode (--crops-encode, with crops_dir): 'gpu' / 'gpu-entropy' -- the crops are JPEG-coded and written by the library where they
-    are cut (write_crops); 'host' (default): fetched and written by Pillow, as before. Same names, same bytes."""
+    are cut (write_crops); 'host' (default): fetched and written by Pillow, as before. Same names, same bytes.
+    ragged_outputs (--ragged-outputs, with ragged): encode='gpu' writes the annotated images of ragged batches too, from the canvas where it
+    lies, every image resized by its own 1 / scale (ctpn_write_annotated_files_ragged[_device]; the canvas is not fetched), and crops_dir
+    cuts their lines from the canvas (ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged[_device]). A ragged batch that fell back to
+    the host decoder hands its host canvas to the same calls. Same names, same bytes as without ragged."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -374,7 +391,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_png": 0, "enc_host": 0, "crops": 0}
     png_batches = {}                                   # slot -> (device pointer or None, host images or None, shape, scale) of a batch whose PNG files the library writes
     dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
-    crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images
+    crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images; heights of a ragged canvas
+    rag_batches = {}                                   # slot -> (device pointer or None, host canvas or None, shape, heights, scales) of a ragged batch whose images the library writes
     # PNG batches are decoded ONE JOB AHEAD on a helper thread (the C++ decode threads hang off that call; ctypes releases the GIL), so that
     # batch k + 1 inflates while batch k is submitted and batch k - 1 collected. Three batch buffers per shape in a ring: when batch k + 1
     # starts decoding, batch k sits decoded in its buffer and batch k - 1 may still be on its way to the device. THREE slots whatever the
@@ -424,10 +442,15 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                                               paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members])
             stats["enc_gpu"] += len(members)
             stats["enc_png"] += len(members)
+        if slot in rag_batches:                        # the same for a ragged canvas: every image at its own size (ctpn_write_annotated_files_ragged)
+            ptr, host_canvas, shape, hts, scs = rag_batches.pop(slot)
+            net.ctx.write_annotated_files_ragged(images=host_canvas, device_ptr=ptr, shape=shape, heights=hts, recs=[results[nm] for nm in members], scales=scs,
+                                                 paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members], entropy=encode_entropy)
+            stats["enc_gpu"] += len(members)
         if slot in crop_src:                           # (a device batch is live until the second-next decode: this is one decode from its own)
-            ptr, shape, imgs = crop_src.pop(slot)
+            ptr, shape, imgs, hts = crop_src.pop(slot)
             stats["crops"] += write_crops(net.ctx, crops_dir, members, [results[nm] for nm in members], crop_h, images=imgs, device_ptr=ptr, shape=shape,
-                                          encode=crops_encode)
+                                          encode=crops_encode, heights=hts)
         for nm in members:
             emit(nm)
 
@@ -436,6 +459,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         png_prefetch(k + 1)
         imgs = None
         scales = [f] * len(members)
+        rag_crops = None                               # a ragged batch's crop source (ragged_outputs)
         if kind == "ragged":                           # f: (file h, file w, factor) per member; (h, w) and rs: the canvas
             sizes, scales = [t[:2] for t in f], [t[2] for t in f]
             try:
@@ -451,16 +475,24 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                 (ptr, shape), heights = handle
                 net.ctx.detect_submit(device_ptr=ptr, shape=shape, heights=heights, slot=k & 1)
                 stats["gpu"] += len(members)
-                if write_images:
+                lib_writes = ragged_outputs and write_images and encode == "gpu" and all(_is_jpeg(nm) for nm in members)
+                if lib_writes:                         # (live until the second-next decode: collected one decode from now; not fetched)
+                    rag_batches[k & 1] = (ptr, None, shape, heights, scales)
+                elif write_images:
                     canvas = net.ctx.jpeg_batch_fetch(ptr, shape)
                     imgs = [canvas[i, :heights[i]] for i in range(len(members))]
+                rag_crops = (ptr, shape, None, heights)
             except B.CtpnError as e:                                       # e.g. damaged entropy data: the same canvas from the host decoder
                 if e.code not in (B.CTPN_ERR_UNSUPPORTED, -1):
                     raise
+                rag_batches.pop(k & 1, None)
                 imgs = [_load(nm)[0] for nm in members]
                 canvas, heights = im_list_to_canvas(imgs)
                 net.ctx.detect_submit(images=canvas, heights=heights, slot=k & 1)
                 stats["host"] += len(members)
+                if ragged_outputs and write_images and encode == "gpu" and all(_is_jpeg(nm) for nm in members):      # the host canvas through the same call
+                    rag_batches[k & 1] = (None, canvas, canvas.shape[:3], heights, scales)
+                rag_crops = (None, None, canvas, heights)
         if kind == "jpg":
             try:
                 ptr = None
@@ -503,11 +535,11 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.detect_submit(images=imgs, slot=k & 1)
             stats["host"] += len(members)
         for i, nm in enumerate(members):
-            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches else None, scales[i])
+            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches and (k & 1) not in rag_batches else None, scales[i])
         if pending is not None:
             collect(pending)
         if crops_dir:
-            crop_src[k & 1] = (ptr, shape, None) if kind == "jpg" else (None, None, imgs)
+            crop_src[k & 1] = rag_crops if rag_crops is not None else ((ptr, shape, None, None) if kind == "jpg" else (None, None, imgs, None))
         pending = (k & 1, members)
     if pending is not None:
         collect(pending)
@@ -536,7 +568,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host"):
+        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
@@ -555,7 +587,10 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     on the thread pool. decode='gpu' / 'gpu-entropy': the JPEG files the library takes are decoded into ragged canvases on the device
     whatever their file sizes, layouts and orientations (Context.decode_jpeg_ragged; see _run_gpu); PNG batches, Pillow's files and what
     ends alone stay size-grouped. Not with the process-pool decoder, and on the device path not with encode='gpu' / 'gpu-entropy',
-    png_encode='gpu' or crops_dir, which take uniform batches (check_ragged_options: ValueError)."""
+    png_encode='gpu' or crops_dir, which take uniform batches (check_ragged_options: ValueError).
+    ragged_outputs (off by default; needs ragged and decode='gpu' / 'gpu-entropy', else ValueError before any work): encode='gpu' /
+    'gpu-entropy' and crops_dir (with any crops_encode) then combine with ragged -- the library writes the annotated images and the crops
+    of ragged batches from their canvases (_run_gpu). png_encode='gpu' stays refused. Same names, same bytes as without ragged."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config(params)
     if params:
@@ -580,13 +615,14 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         raise ValueError("crops_encode must be 'host', 'gpu' or 'gpu-entropy'")
     if crops_encode != "host" and (crops_dir is None or decode != "gpu"):
         raise ValueError("crops_encode='%s' writes the crops of crops_dir on the device: it needs crops_dir and decode='gpu'" % crops_encode)
-    if ragged:
-        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool)
+    if ragged or ragged_outputs:
+        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool, ragged_outputs=ragged_outputs, ragged=ragged)
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
-                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste, crops_encode=crops_encode)
+                        entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste, crops_encode=crops_encode,
+                        ragged_outputs=ragged_outputs)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -749,6 +785,9 @@ def build_parser():
     ap.add_argument('--ragged', action='store_true',
                     help="batch images of one resized width across heights (same result files); with --decode gpu / gpu-entropy the JPEG files "
                          "are decoded into ragged canvases on the device whatever their file sizes (not with --encode gpu, --png-encode gpu, --crops)")
+    ap.add_argument('--ragged-outputs', action='store_true',
+                    help="with --ragged and --decode gpu / gpu-entropy: --encode gpu / gpu-entropy and --crops take the ragged batches too "
+                         "(ctpn_write_annotated_files_ragged, ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged); same files")
     ap.add_argument('--ragged-waste', type=float, default=RAGGED_WASTE, help="padded share of a ragged batch's rows at most")
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
@@ -780,7 +819,8 @@ def main(argv=None):
         raise SystemExit('no images under ' + args.input)
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
         decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height, crops_encode=args.crops_encode,
-        params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)), ragged=args.ragged, ragged_waste=args.ragged_waste)
+        params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)), ragged=args.ragged, ragged_waste=args.ragged_waste,
+        ragged_outputs=args.ragged_outputs)
     net.close()
 
 

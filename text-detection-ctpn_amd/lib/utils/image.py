@@ -112,6 +112,15 @@ def imwrite_png_batch(ctx, paths, images, device_ptr=None, shape=None):
             f.write(data)
 
 
+def imwrite_annotated_ragged(ctx, paths, canvas, heights, recs, scales, quality=95, device_ptr=None, shape=None, entropy="host"):
+    """draw_boxes + cv2.resize(1 / scale) + imwrite for a RAGGED batch, on the GPU (ctpn_write_annotated_files_ragged): canvas (n, hc, w, 3)
+    BGR uint8 on the host (lib/utils/blob.py im_list_to_canvas), or device_ptr + shape = (n, hc, w) for a canvas that is on the device
+    already; image i is rows [0, heights[i]) of slot i, resized by 1 / scales[i] and written to paths[i] at its own size, byte-equal to
+    the uniform batch writer's file of that image alone. entropy="device": the Huffman coding on the device too."""
+    ctx.write_annotated_files_ragged(images=canvas, device_ptr=device_ptr, shape=shape, heights=heights, recs=recs, scales=scales, paths=list(paths),
+                                     quality=quality, entropy=entropy)
+
+
 def crop_text_lines(ctx, images, recs, line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None):
     """The detected text lines of a batch as rectified images of height crop_h, one per line, for a recogniser -- cut out on the GPU
     (ctpn_crop_lines): the quadrilateral of every record mapped bilinearly onto crop_h x width pixels with cv2.resize's INTER_LINEAR uint8

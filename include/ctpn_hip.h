@@ -402,6 +402,31 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
 int ctpn_debug_conv3x3_plan(int precision, int n, int h, int w_first, int w_count, int ci, int co, int fuse_pool, int keep_full, int dup_hi,
                             int conv_p64, int split_edge, int cu_count, int* plans);
 const char* ctpn_debug_conv3x3_form_name(int kind, int id);
+/* The kernels behind the conv stack, one at a time on caller data (test hooks; null stream, buffers allocated and freed inside). Every output
+ * buffer is followed by 64 guard rows and pre-filled with one byte value; a guard byte that changed is CTPN_ERR_STATE.
+ *
+ * ctpn_debug_lstm_pre_plan: the launch shape launch_lstm_pre computes for `cells` feature-map cells and then follows (csrc/lstm_pre.hip). Pure
+ *   host arithmetic; cu_count 0 = the current device's CU count (CTPN_ERR_NODEVICE without one). plan_out[4]:
+ *   [0] form 0 small (one wave per 32 cells x four column tiles) / 1 resident (lstm_pre_kernel)   [1] waves per workgroup (small: 1)
+ *   [2] workgroups   [3] whole waves of the last workgroup that lie beyond the last cell
+ * ctpn_debug_lstm_pre: lstm_pre = x @ wx + bias of an n x hf x wf map. x [cells][512], wx [512][1024], bias [1024], out [cells][1024], gate columns
+ *   in TF's order (fw i | j | f | o, then bw) on both sides: the weights go through the chain ctpn_load_weights_* uses, the result's columns are
+ *   put back on the host. x is rounded to the mode's operand type and laid out as the bordered map the forward reads, the border filled with 3e4
+ *   instead of zeros. CTPN_PREC_BF16 / FP16: launch_lstm_pre with cu_count (0 = the device's; another value plans the launch for that many
+ *   CUs), fp16 results; CTPN_PREC_FP32 / SPLIT: the im2col GEMM as the forward sets it up, fp32 results.
+ * ctpn_debug_bilstm: the recurrence alone. pre [rows][T][1024] in TF's order (permuted inside; rounded to and stored as fp16 when pre_f16), wh
+ *   [2][128][512] = kernel[512:] of fw, bw; out [rows][T][256]. split / fast_gates / pre_f16 as the forward passes them; the two pairs it never
+ *   passes (no split: exact gates on fp16 pre, fast gates on fp32 pre) are CTPN_ERR_ARG. *form_out (nullable; set before a device is asked for):
+ *   the form launch_bilstm chooses: 0 exact, 1 exact with v_exp / v_rcp gates, 2 split-bf16 16 rows per workgroup, 3 split-bf16 4 rows.
+ * ctpn_debug_gemm: out[m][0 .. Co) = a[m] @ w + bias through launch_pack_transpose + launch_igemm (plain A, no ReLU, fp32 out). a [M][K] (rounded to
+ *   in_precision: CTPN_PREC_FP32 / BF16 / FP16), w [K][Co], out [M][ldc]: columns Co .. ldc - 1 come back holding the fill (bytes 0xC3), and a
+ *   pad column that changed is CTPN_ERR_STATE. K a multiple of 32 (fp32) / 64, Co and ldc of 4. */
+int ctpn_debug_lstm_pre_plan(long long cells, int cu_count, int* plan_out);
+int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const float* bias, int n, int hf, int wf, int precision, int cu_count,
+                        float* out);
+int ctpn_debug_bilstm(int device_id, const float* pre, const float* wh, int rows, int T, int split, int fast_gates, int pre_f16, float* out,
+                      int* form_out);
+int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* bias, int M, int K, int Co, int ldc, int in_precision, float* out);
 /* TextDetector.detect (lib/text_connector/detectors.py:19-49) for ONE image with every step on the device -- score > 0.7 prefix and
  * boxes / scale (lines_prep_kernel), NMS 0.2 (nms_kernel), graph build / chains / line fit / filter_boxes (connect_kernel) -- i.e.
  * the device-connector form of the asynchronous detect path (option connect_device = 1). rois: r x 5 fp32 [score,x1,y1,x2,y2] in

@@ -22,3 +22,17 @@ def test_no_lds_read_in_flight_across_a_barrier(root, src):
     assert len(p_rows) >= 10, rows
     assert r.returncode == 0, "\n".join(l for l in rows if "MUST BE CLEAN" in l)
     assert all(l.split()[-1] == "0" for l in p_rows), p_rows
+
+
+@pytest.mark.parametrize("src,kernel,count", [("lstm_pre.hip", "ctpn::lstm_pre_kernel<", 2), ("igemm.hip", "ctpn::igemm_kernel<", 18)])
+def test_the_tail_kernels_that_recycle_lds_behind_a_barrier_are_clean(root, src, kernel, count):
+    """lstm_pre_kernel hands the buffers of its 4-deep weight ring to the LDS-DMA of the next tile behind a raw s_barrier, igemm_kernel its two
+    stages behind __syncthreads(): both instantiations of the one (bf16, fp16) and all 18 of the other (6 type pairs x 3 tiles) are present
+    in the compiled unit and have no LDS read in flight across any barrier"""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc")
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "scan_barrier_reads.py"), src], capture_output=True, text=True, timeout=1200)
+    rows = [l for l in r.stdout.splitlines() if "barriers" in l and kernel in l]
+    assert len(rows) == count, r.stdout + r.stderr
+    assert r.returncode == 0, "\n".join(l for l in r.stdout.splitlines() if "MUST BE CLEAN" in l)
+    assert all(l.split()[-1] == "0" and int(l.split()[-7]) >= 2 for l in rows), rows

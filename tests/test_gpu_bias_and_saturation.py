@@ -129,11 +129,8 @@ def lstm_pre_form(prec, cells):
     (csrc/lstm_pre.hip), whose one-wave form reads the bias from global memory and whose resident-slice form reads it from LDS."""
     if prec in ("fp32", "split"):
         return "igemm"
-    import torch
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    groups = (cells + 31) // 32
-    waves = min(max((groups + ncu - 1) // ncu, 1), 12)
-    return "small" if (groups + waves - 1) // waves * 2 <= ncu else "lds"
+    from ctpn_amd import _binding as B
+    return B.lstm_pre_plan(cells, cu_count=0).form      # the plan launch_lstm_pre follows, on this device
 
 
 def recurrent_form(prec, lstm_split, rows):
@@ -433,9 +430,7 @@ def test_recurrence_shapes_reach_every_form():
     for p, s in REC_MODES:
         if s:
             assert {recurrent_form(p, s, sh[0] * (sh[1] // 16))[0] for sh in REC_SHAPES} == {"split_few", "split_16"}, p
-    src = open(os.path.join(ROOT, "text-detection-ctpn_amd", "csrc", "lstm_pre.hip")).read()
-    assert "if (cellblks * 2 <= ncu) {" in src and "groups = (g.M + 31) / 32;" in src, "launch_lstm_pre's selection rule changed: update lstm_pre_form"
-    for p in ("bf16", "fp16"):
+    for p in ("bf16", "fp16"):      # (lstm_pre_form asks the library's plan: no copy of launch_lstm_pre's rule here that could drift)
         assert {lstm_pre_form(p, sh[0] * (sh[1] // 16) * (sh[2] // 16)) for sh in REC_SHAPES} == {"small", "lds"}, p
 
 

@@ -114,6 +114,10 @@ def _declare(lib):
                                          C.c_int, f32p, f32p]),
         "ctpn_debug_conv3x3_plan": (C.c_int, [C.c_int] * 13 + [i32p]),
         "ctpn_debug_conv3x3_form_name": (C.c_char_p, [C.c_int, C.c_int]),
+        "ctpn_debug_lstm_pre_plan": (C.c_int, [C.c_longlong, C.c_int, i32p]),
+        "ctpn_debug_lstm_pre": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+        "ctpn_debug_bilstm": (C.c_int, [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, i32p]),
+        "ctpn_debug_gemm": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
         "ctpn_jpeg_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_jpeg_coef_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_decode": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint16), i32p]),
@@ -724,6 +728,54 @@ def conv3x3_plan(precision, n, h, w, ci, co, pool, keep_full=True, dup_hi=False,
     mains, strips = conv3x3_form_names()
     p = [int(v) for v in conv3x3_plan_sweep(precision, n, h, w, 1, ci, co, pool, keep_full, dup_hi, conv_p64, split_edge, cu_count)[0]]
     return ConvPlan(mains[p[0]], strips[p[1]], p[2], p[3], p[4], p[5])
+
+
+LstmPrePlan = collections.namedtuple("LstmPrePlan", "form waves workgroups idle_waves")
+LSTM_PRE_FORMS = ("small", "lds")
+BILSTM_FORMS = ("exact", "exact_fast_gates", "split_16", "split_few")
+
+
+def lstm_pre_plan(cells, cu_count=0):
+    """ctpn_debug_lstm_pre_plan: the launch shape of launch_lstm_pre for `cells` cells as (form name, waves per workgroup, workgroups, whole
+    idle waves of the last workgroup). cu_count 0 asks the current device; any other value needs no device."""
+    p = np.zeros(4, np.int32)
+    _check(load_library().ctpn_debug_lstm_pre_plan(int(cells), int(cu_count), _ptr(p, C.c_int)))
+    return LstmPrePlan(LSTM_PRE_FORMS[int(p[0])], int(p[1]), int(p[2]), int(p[3]))
+
+
+def debug_lstm_pre(x, wx, bias, precision="fp16", cu_count=0, device_id=0):
+    """ctpn_debug_lstm_pre: x (n, hf, wf, 512), wx (512, 1024), bias (1024,) in TF's gate order -> lstm_pre (n, hf, wf, 1024) fp32 values."""
+    x = _f32(x); wx = _f32(wx); bias = _f32(bias)
+    n, hf, wf, ci = x.shape
+    assert ci == 512 and wx.shape == (512, 1024) and bias.shape == (1024,)
+    out = np.zeros((n, hf, wf, 1024), np.float32)
+    _check(load_library().ctpn_debug_lstm_pre(int(device_id), _ptr(x, C.c_float), _ptr(wx, C.c_float), _ptr(bias, C.c_float), n, hf, wf,
+                                              precision_code(precision), int(cu_count), _ptr(out, C.c_float)))
+    return out
+
+
+def debug_bilstm(pre, wh, split=False, fast_gates=False, pre_f16=False, device_id=0):
+    """ctpn_debug_bilstm: pre (rows, T, 1024) in TF's gate order, wh (2, 128, 512) -> (lstm_out (rows, T, 256), the launcher's form name)."""
+    pre = _f32(pre); wh = _f32(wh)
+    rows, T, c = pre.shape
+    assert c == 1024 and wh.shape == (2, 128, 512)
+    out = np.zeros((rows, T, 256), np.float32)
+    form = C.c_int(-1)
+    _check(load_library().ctpn_debug_bilstm(int(device_id), _ptr(pre, C.c_float), _ptr(wh, C.c_float), rows, T, 1 if split else 0,
+                                            1 if fast_gates else 0, 1 if pre_f16 else 0, _ptr(out, C.c_float), C.byref(form)))
+    return out, BILSTM_FORMS[form.value]
+
+
+def debug_gemm(a, w, bias, ldc=None, precision="fp32", device_id=0):
+    """ctpn_debug_gemm: a (M, K) @ w (K, Co) + bias -> (M, ldc) fp32; columns Co .. ldc - 1 hold the hook's fill (bytes 0xC3)."""
+    a = _f32(a); w = _f32(w); bias = _f32(bias)
+    (M, K), Co = a.shape, w.shape[1]
+    assert w.shape[0] == K and bias.shape == (Co,)
+    ldc = Co if ldc is None else int(ldc)
+    out = np.zeros((M, ldc), np.float32)
+    _check(load_library().ctpn_debug_gemm(int(device_id), _ptr(a, C.c_float), _ptr(w, C.c_float), _ptr(bias, C.c_float), M, K, Co, ldc,
+                                          precision_code(precision), _ptr(out, C.c_float)))
+    return out
 
 
 class Context:

@@ -178,4 +178,198 @@ int ctpn_debug_conv3x3_plan(int precision, int n, int h, int w_first, int w_coun
 
 const char* ctpn_debug_conv3x3_form_name(int kind, int id) { return kind == 0 ? c3_main_name(id) : (kind == 1 ? c3_strip_name(id) : nullptr); }
 
+// ---- the recurrent tail's kernels alone ------------------------------------------------------------------------
+// Every output buffer below is followed by DBG_GUARD_ROWS guard rows and filled with DBG_FILL bytes before the launch: a kernel that stores
+// behind its last row, or into the pad columns of a row, changes a byte that the hook then finds changed (CTPN_ERR_STATE).
+}  // extern "C"
+namespace {
+constexpr int DBG_GUARD_ROWS = 64;
+constexpr int DBG_FILL = 0xC3;
+bool dbg_fill_intact(const char* p, size_t n) {
+  for (size_t i = 0; i < n; ++i) if ((unsigned char)p[i] != DBG_FILL) return false;
+  return true;
+}
+// one fp32 value as the 16-bit operand of mode t (split precision: the hi half)
+inline uint16_t dbg_to16(DType t, float v) { return t == DType::F16 ? host_f32_to_f16(v) : host_f32_to_bf16(v); }
+struct DevBufs {      // hipFree on every way out
+  std::vector<void*> p;
+  ~DevBufs() { for (void* q : p) if (q) (void)hipFree(q); }
+  int alloc(void** out, size_t bytes) {
+    CTPN_HIP_TRY(hipMalloc(out, bytes));
+    p.push_back(*out);
+    return CTPN_OK;
+  }
+};
+}  // namespace
+extern "C" {
+
+int ctpn_debug_lstm_pre_plan(long long cells, int cu_count, int* plan_out) {
+  if (!plan_out) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre_plan: no output");
+  if (cells <= 0 || cells > 0x7fffffffLL) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre_plan: cells out of range (1 .. 2^31 - 1)");
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre_plan: cu_count is a CU count, or 0 for the current device's");
+  if (cu_count == 0) {
+    if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_lstm_pre_plan: cu_count 0 asks the current device, and no HIP device is visible");
+    int dev = 0, rc;
+    if ((rc = current_device(dev)) || (rc = device_cu_count(dev, cu_count))) return rc;
+  }
+  const LstmPrePlan p = lstm_pre_plan(cells, cu_count);
+  plan_out[0] = p.small ? 0 : 1; plan_out[1] = p.waves; plan_out[2] = (int)p.workgroups; plan_out[3] = p.idle_waves;
+  return CTPN_OK;
+}
+
+int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const float* bias, int n, int hf, int wf, int precision, int cu_count, float* out) {
+  if (!x || !wx || !bias || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre: null pointer");
+  if (precision < CTPN_PREC_FP32 || precision > CTPN_PREC_SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre: unknown precision");
+  if (n <= 0 || hf <= 0 || wf <= 0 || (long long)n * hf * wf > (1 << 24)) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre: n, hf, wf positive, at most 2^24 cells");
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre: cu_count is a CU count, or 0 for the current device's");
+  if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_lstm_pre: no HIP device visible (no CPU fallback)");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  const DType t = prec_dtype(precision);
+  const bool split = t == DType::SPLIT, half = dtype_is_half(t);
+  const long long M = (long long)n * hf * wf;
+  const int Hp = hf + 2, Wp = wf + 2;
+  const int es = t == DType::F32 ? 4 : 2, pix = split ? 1536 : 512;      // bytes per stored scalar, scalars per pixel (split precision: [hi | lo | hi])
+  const int oes = half ? 2 : 4;                                           // lstm_pre is fp16 in the 16-bit modes, fp32 otherwise
+  // the bordered map, operands rounded to the mode's type; the border is POISON (the product's is zero): an index that strays into it shows
+  std::vector<char> hin((size_t)n * Hp * Wp * pix * es);
+  auto put = [&](size_t pixel, int c, float v) {
+    const size_t o = pixel * pix + c;
+    if (t == DType::F32) { std::memcpy(&hin[o * 4], &v, 4); return; }
+    const uint16_t b = dbg_to16(t, v);
+    std::memcpy(&hin[o * 2], &b, 2);
+    if (split) {
+      const uint16_t l = host_f32_to_bf16(v - host_bf16_to_f32(b));
+      std::memcpy(&hin[(o + 512) * 2], &l, 2);
+      std::memcpy(&hin[(o + 1024) * 2], &b, 2);
+    }
+  };
+  for (int in = 0; in < n; ++in) for (int y = 0; y < Hp; ++y) for (int xx = 0; xx < Wp; ++xx) {
+    const size_t pixel = ((size_t)in * Hp + y) * Wp + xx;
+    const bool inside = y >= 1 && y <= hf && xx >= 1 && xx <= wf;
+    const float* src = inside ? x + (((size_t)in * hf + (y - 1)) * wf + (xx - 1)) * 512 : nullptr;
+    for (int c = 0; c < 512; ++c) put(pixel, c, inside ? src[c] : 3e4f);
+  }
+  DevBufs bufs;
+  void *d_a = nullptr, *d_wx = nullptr, *d_b = nullptr, *d_wt = nullptr, *d_wtf = nullptr, *d_bx = nullptr, *d_out = nullptr;
+  const size_t row_bytes = split ? (size_t)3 * 512 * 2 : (size_t)512 * es;
+  const size_t out_bytes = (size_t)M * 1024 * oes, guard_bytes = (size_t)DBG_GUARD_ROWS * 1024 * oes;
+  int rc;
+  if ((rc = bufs.alloc(&d_a, hin.size())) || (rc = bufs.alloc(&d_wx, (size_t)512 * 1024 * 4)) || (rc = bufs.alloc(&d_b, 1024 * 4)) ||
+      (rc = bufs.alloc(&d_wt, 1024 * row_bytes)) || (half && (rc = bufs.alloc(&d_wtf, (size_t)1024 * 512 * 2))) || (rc = bufs.alloc(&d_bx, 1024 * 4)) ||
+      (rc = bufs.alloc(&d_out, out_bytes + guard_bytes))) return rc;
+  CTPN_HIP_TRY(hipMemcpy(d_a, hin.data(), hin.size(), hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemcpy(d_wx, wx, (size_t)512 * 1024 * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemcpy(d_b, bias, 1024 * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemset(d_out, DBG_FILL, out_bytes + guard_bytes));
+  CTPN_HIP_TRY(hipDeviceSynchronize());
+  // the product's weight chain (api_weights.hip) on wx [512][fw 512 | bw 512]: direction d's block starts at column 512 d, 1024 floats per row
+  const float* const kx[2] = {(const float*)d_wx, (const float*)d_wx + 512};
+  const float* const bx[2] = {(const float*)d_b, (const float*)d_b + 512};
+  if ((rc = pack_lstm_projection(kx, 1024, bx, t, d_wt, row_bytes, (float*)d_bx, d_wtf, nullptr))) return rc;
+  if (half) rc = launch_lstm_pre(d_a, d_wtf, (const float*)d_bx, d_out, t, n, hf, wf, nullptr, cu_count);
+  else {      // the set-up of api_forward.hip
+    IGemm g{};
+    g.a = d_a; g.wt = d_wt; g.bias = (const float*)d_bx; g.out = d_out;
+    g.M = M; g.Ci = split ? 1536 : 512; g.ntaps = 1; g.Co = 1024; g.a_plain = 0; g.H = hf; g.W = wf; g.tap_base_y = 1; g.tap_base_x = 1;
+    g.out_bordered = 0; g.ldc = 1024; g.relu = 0;
+    rc = launch_igemm(g, split ? DType::BF16 : t, DType::F32, nullptr);
+  }
+  if (rc) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_lstm_pre: kernel failed");
+  std::vector<char> tmp(out_bytes + guard_bytes);
+  CTPN_HIP_TRY(hipMemcpy(tmp.data(), d_out, tmp.size(), hipMemcpyDeviceToHost));
+  if (!dbg_fill_intact(tmp.data() + out_bytes, guard_bytes)) return fail(CTPN_ERR_STATE, "ctpn_debug_lstm_pre: a guard row behind the last cell was written");
+  for (long long m = 0; m < M; ++m)      // device layout: permuted gate columns -> TF's i | j | f | o order
+    for (int ch = 0; ch < 1024; ++ch) {
+      const size_t o = (size_t)m * 1024 + (ch & ~511) + lstm_gate_col(ch & 511);
+      float v;
+      if (half) { uint16_t b; std::memcpy(&b, &tmp[o * 2], 2); v = host_f16_to_f32(b); }
+      else std::memcpy(&v, &tmp[o * 4], 4);
+      out[(size_t)m * 1024 + ch] = v;
+    }
+  return CTPN_OK;
+}
+
+int ctpn_debug_bilstm(int device_id, const float* pre, const float* wh, int rows, int T, int split, int fast_gates, int pre_f16, float* out, int* form_out) {
+  if (!pre || !wh || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_bilstm: null pointer");
+  if (rows <= 0 || T <= 0 || (long long)rows * T > (1 << 22)) return fail(CTPN_ERR_ARG, "ctpn_debug_bilstm: rows, T positive, at most 2^22 positions");
+  split = split ? 1 : 0; fast_gates = fast_gates ? 1 : 0; pre_f16 = pre_f16 ? 1 : 0;
+  if (!split && fast_gates != pre_f16)
+    return fail(CTPN_ERR_ARG, "ctpn_debug_bilstm: the forward never launches exact gates on fp16 pre-activations or fast gates on fp32 ones (without split)");
+  if (form_out) *form_out = bilstm_plan(rows, split, fast_gates).form;
+  if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_bilstm: no HIP device visible (no CPU fallback)");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  const size_t pos = (size_t)rows * T;
+  const int pes = pre_f16 ? 2 : 4;
+  std::vector<char> hpre(pos * 1024 * pes);      // TF's i | j | f | o order -> the permuted order the kernels read, fp16 where asked
+  for (size_t p = 0; p < pos; ++p)
+    for (int ch = 0; ch < 1024; ++ch) {
+      const float v = pre[p * 1024 + ch];
+      const size_t o = p * 1024 + (ch & ~511) + lstm_gate_col(ch & 511);
+      if (pre_f16) { const uint16_t b = host_f32_to_f16(v); std::memcpy(&hpre[o * 2], &b, 2); }
+      else std::memcpy(&hpre[o * 4], &v, 4);
+    }
+  DevBufs bufs;
+  void *d_pre = nullptr, *d_wh = nullptr, *d_out = nullptr;
+  const size_t out_bytes = pos * 256 * 4, guard_bytes = (size_t)DBG_GUARD_ROWS * 256 * 4;
+  int rc;
+  if ((rc = bufs.alloc(&d_pre, hpre.size())) || (rc = bufs.alloc(&d_wh, (size_t)2 * 128 * 512 * 4)) || (rc = bufs.alloc(&d_out, out_bytes + guard_bytes))) return rc;
+  CTPN_HIP_TRY(hipMemcpy(d_pre, hpre.data(), hpre.size(), hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemcpy(d_wh, wh, (size_t)2 * 128 * 512 * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemset(d_out, DBG_FILL, out_bytes + guard_bytes));
+  CTPN_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = launch_bilstm(d_pre, pre_f16, (const float*)d_wh, (float*)d_out, rows, T, nullptr, split, fast_gates))) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_bilstm: kernel failed");
+  std::vector<char> guard(guard_bytes);
+  CTPN_HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+  CTPN_HIP_TRY(hipMemcpy(guard.data(), (const char*)d_out + out_bytes, guard_bytes, hipMemcpyDeviceToHost));
+  if (!dbg_fill_intact(guard.data(), guard_bytes)) return fail(CTPN_ERR_STATE, "ctpn_debug_bilstm: a guard row behind the last position was written");
+  return CTPN_OK;
+}
+
+int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* bias, int M, int K, int Co, int ldc, int in_precision, float* out) {
+  if (!a || !w || !bias || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_gemm: null pointer");
+  if (in_precision < CTPN_PREC_FP32 || in_precision > CTPN_PREC_FP16) return fail(CTPN_ERR_ARG, "ctpn_debug_gemm: in_precision is fp32, bf16 or fp16");
+  const DType t = prec_dtype(in_precision);
+  const int es = dtype_bytes(t);
+  if (M <= 0 || M > (1 << 22) || K <= 0 || K > 4096 || K % (128 / es) != 0 || Co <= 0 || Co > 4096 || Co % 4 != 0 || ldc < Co || ldc > 8192 || ldc % 4 != 0)
+    return fail(CTPN_ERR_ARG, "ctpn_debug_gemm: M <= 2^22, K a multiple of the 128-byte strip, Co and ldc multiples of 4, Co <= ldc");
+  if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_gemm: no HIP device visible (no CPU fallback)");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  std::vector<char> ha((size_t)M * K * es);      // operands rounded to the mode's type, as ctpn_debug_conv3x3 does
+  for (size_t i = 0; i < (size_t)M * K; ++i) {
+    if (t == DType::F32) std::memcpy(&ha[i * 4], &a[i], 4);
+    else { const uint16_t b = dbg_to16(t, a[i]); std::memcpy(&ha[i * 2], &b, 2); }
+  }
+  // weight rows and bias padded to the N tile with zeros, as the ctx allocates them: the 64-wide tile of Co = 60 reads rows 60 .. 63
+  const int co_pad = Co <= 64 ? 64 : (Co + 127) / 128 * 128;
+  DevBufs bufs;
+  void *d_a = nullptr, *d_w = nullptr, *d_wt = nullptr, *d_b = nullptr, *d_out = nullptr;
+  const size_t out_bytes = (size_t)M * ldc * 4, guard_bytes = (size_t)DBG_GUARD_ROWS * ldc * 4;
+  int rc;
+  if ((rc = bufs.alloc(&d_a, ha.size())) || (rc = bufs.alloc(&d_w, (size_t)K * Co * 4)) || (rc = bufs.alloc(&d_wt, (size_t)co_pad * K * es)) ||
+      (rc = bufs.alloc(&d_b, (size_t)co_pad * 4)) || (rc = bufs.alloc(&d_out, out_bytes + guard_bytes))) return rc;
+  CTPN_HIP_TRY(hipMemcpy(d_a, ha.data(), ha.size(), hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemcpy(d_w, w, (size_t)K * Co * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemset(d_wt, 0, (size_t)co_pad * K * es));
+  CTPN_HIP_TRY(hipMemset(d_b, 0, (size_t)co_pad * 4));
+  CTPN_HIP_TRY(hipMemcpy(d_b, bias, (size_t)Co * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemset(d_out, DBG_FILL, out_bytes + guard_bytes));
+  CTPN_HIP_TRY(hipDeviceSynchronize());
+  if ((rc = launch_pack_transpose((const float*)d_w, Co, d_wt, K, t, K, Co, nullptr))) return rc;
+  IGemm g{};
+  g.a = d_a; g.wt = d_wt; g.bias = (const float*)d_b; g.out = d_out;
+  g.M = M; g.Ci = K; g.ntaps = 1; g.Co = Co; g.a_plain = 1; g.lda = K; g.out_bordered = 0; g.ldc = ldc; g.relu = 0;
+  if ((rc = launch_igemm(g, t, DType::F32, nullptr))) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_gemm: kernel failed");
+  std::vector<char> guard(guard_bytes);
+  CTPN_HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));      // pad columns included: the caller sees the fill in them
+  CTPN_HIP_TRY(hipMemcpy(guard.data(), (const char*)d_out + out_bytes, guard_bytes, hipMemcpyDeviceToHost));
+  if (!dbg_fill_intact(guard.data(), guard_bytes)) return fail(CTPN_ERR_STATE, "ctpn_debug_gemm: a guard row behind the last row was written");
+  for (int m = 0; m < M; ++m)
+    if (ldc > Co && !dbg_fill_intact((const char*)(out + (size_t)m * ldc + Co), (size_t)(ldc - Co) * 4))
+      return fail(CTPN_ERR_STATE, "ctpn_debug_gemm: a pad column (Co .. ldc - 1) was written");
+  return CTPN_OK;
+}
+
 }  // extern "C"

@@ -38,6 +38,35 @@ static const ManifestEntry* find_entry(const std::string& name) {
 }
 
 // ---------------------------------------------------------------------------------------------
+int pack_lstm_projection(const float* const kx[2], long long kx_ld, const float* const bias[2], DType prec, void* wt_x, size_t row_bytes, float* b_x,
+                         void* wt_xf, hipStream_t s) {
+  int rc;
+  for (int d = 0; d < 2; ++d) {
+    // kernel[:512] ([512 in][512 gates]) -> wt_x rows d*512.. ([gate][in]; split precision: [gate][hi | hi | lo] against [hi | lo | hi] pixels)
+    char* dst = (char*)wt_x + (size_t)d * 512 * row_bytes;
+    if (prec == DType::SPLIT) { if ((rc = launch_pack_transpose_split(kx[d], kx_ld, dst, 1, 512, 512, s))) return rc; }
+    else if ((rc = launch_pack_transpose(kx[d], kx_ld, dst, 512, prec, 512, 512, s))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(b_x + d * 512, bias[d], 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  // gate columns of lstm_pre in the recurrence kernel's order (bilstm.hip: a lane's 4 gates x 4 units = one 64-byte run): permute
+  // the rows of the packed [1024][512] input-projection matrix and its bias once, here
+  void* tmp = nullptr;
+  const size_t wbytes = (size_t)1024 * row_bytes;
+  CTPN_HIP_TRY(hipMalloc(&tmp, wbytes));
+  auto chain = [&]() -> int {
+    CTPN_HIP_TRY(hipMemcpyAsync(tmp, wt_x, wbytes, hipMemcpyDeviceToDevice, s));
+    if ((rc = launch_lstm_permute_rows(tmp, wt_x, (int)row_bytes, s))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(tmp, b_x, 1024 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = launch_lstm_permute_rows(tmp, b_x, 4, s))) return rc;
+    if (wt_xf && (rc = launch_lstm_pre_pack(wt_x, wt_xf, s))) return rc;
+    CTPN_HIP_TRY(hipStreamSynchronize(s));
+    return CTPN_OK;
+  };
+  rc = chain();
+  (void)hipFree(tmp);
+  return rc;
+}
+
 static int pack_weights(ctpn_ctx* c) {
   hipStream_t s = c->stream;
   const float* A = c->arena;
@@ -55,30 +84,16 @@ static int pack_weights(ctpn_ctx* c) {
       else if ((rc = launch_pack_transpose(A + we->offset, Co, c->wt_conv[i], K, c->prec, K, Co, s))) return rc;
     }
   }
-  const char* dirs[2] = {"fw", "bw"};
-  for (int d = 0; d < 2; ++d) {
-    const ManifestEntry* ke = find_entry(std::string("lstm_o/bidirectional_rnn/") + dirs[d] + "/lstm_cell/kernel");
-    const ManifestEntry* be = find_entry(std::string("lstm_o/bidirectional_rnn/") + dirs[d] + "/lstm_cell/bias");
-    // kernel[:512] ([512 in][512 gates]) -> wt_x rows d*512.. ([gate][in]; split precision: [gate][hi | hi | lo] against [hi | lo | hi] pixels)
-    char* dst = (char*)c->wt_x + (size_t)d * 512 * c->wx_row_bytes;
-    if (c->prec == DType::SPLIT) { if ((rc = launch_pack_transpose_split(A + ke->offset, 512, dst, 1, 512, 512, s))) return rc; }
-    else if ((rc = launch_pack_transpose(A + ke->offset, 512, dst, 512, c->prec, 512, 512, s))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(c->wh + (size_t)d * 128 * 512, A + ke->offset + (size_t)512 * 512, (size_t)128 * 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CTPN_HIP_TRY(hipMemcpyAsync(c->b_x + d * 512, A + be->offset, 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  }
   {
-    // gate columns of lstm_pre in the recurrence kernel's order (bilstm.hip: a lane's 4 gates x 4 units = one 64-byte run): permute
-    // the rows of the packed [1024][512] input-projection matrix and its bias once, here
-    void* tmp = nullptr;
-    const size_t wbytes = (size_t)1024 * c->wx_row_bytes;
-    CTPN_HIP_TRY(hipMalloc(&tmp, wbytes));
-    CTPN_HIP_TRY(hipMemcpyAsync(tmp, c->wt_x, wbytes, hipMemcpyDeviceToDevice, s));
-    if ((rc = launch_lstm_permute_rows(tmp, c->wt_x, (int)c->wx_row_bytes, s))) { (void)hipFree(tmp); return rc; }
-    CTPN_HIP_TRY(hipMemcpyAsync(tmp, c->b_x, 1024 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if ((rc = launch_lstm_permute_rows(tmp, c->b_x, 4, s))) { (void)hipFree(tmp); return rc; }
-    if (c->wt_xf && (rc = launch_lstm_pre_pack(c->wt_x, c->wt_xf, s))) { (void)hipFree(tmp); return rc; }
-    CTPN_HIP_TRY(hipStreamSynchronize(s));
-    CTPN_HIP_TRY(hipFree(tmp));
+    const ManifestEntry* kf = find_entry("lstm_o/bidirectional_rnn/fw/lstm_cell/kernel");
+    const ManifestEntry* kb = find_entry("lstm_o/bidirectional_rnn/bw/lstm_cell/kernel");
+    const ManifestEntry* bf = find_entry("lstm_o/bidirectional_rnn/fw/lstm_cell/bias");
+    const ManifestEntry* bb = find_entry("lstm_o/bidirectional_rnn/bw/lstm_cell/bias");
+    const float* const kx[2] = {A + kf->offset, A + kb->offset};      // kernel[:512]: the first 512 of the 640 rows
+    const float* const bx[2] = {A + bf->offset, A + bb->offset};
+    for (int d = 0; d < 2; ++d)      // kernel[512:] = Wh, fp32 as it is
+      CTPN_HIP_TRY(hipMemcpyAsync(c->wh + (size_t)d * 128 * 512, kx[d] + (size_t)512 * 512, (size_t)128 * 512 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if ((rc = pack_lstm_projection(kx, 512, bx, c->prec, c->wt_x, c->wx_row_bytes, c->b_x, c->wt_xf, s))) return rc;
   }
   {
     const ManifestEntry* we = find_entry("lstm_o/weights");

@@ -378,16 +378,22 @@ int launch_lstm_permute_rows(const void* src, void* dst, int row_bytes, hipStrea
   return launch_status("lstm_permute_rows");
 }
 
+// form: index into launch_bilstm's kernel table (0 exact, 1 exact with fast gates, 2 split 16-row, 3 split 4-row)
+BilstmPlan bilstm_plan(int rows, int split_bf16, int fast_gates) {
+  int form = split_bf16 ? 2 : (fast_gates ? 1 : 0), per_wg = LSTM_ROWS;
+  // a few rows (one or two 600 x 900 images: 37 / 74): four rows per workgroup, the gate math spread over all lanes; identical bits
+  if (split_bf16 && rows <= 128) { form = 3; per_wg = LSTM_FEW; }
+  return BilstmPlan{form, per_wg};
+}
+
 int launch_bilstm(const void* xp, int xp_is_f16, const float* wh, float* out, int rows, int T, hipStream_t s, int split_bf16, int fast_gates) {
   if (rows <= 0 || T <= 0) return fail(CTPN_ERR_ARG, "bilstm: empty problem");
   typedef void (*Kernel)(const void*, const float*, float*, int, int);
   static const Kernel kernels[4][2] = {      // [form][xp_is_f16]
       {bilstm_kernel<false, false>, bilstm_kernel<false, true>}, {bilstm_kernel<true, false>, bilstm_kernel<true, true>},
       {bilstm_split_kernel<false>, bilstm_split_kernel<true>}, {bilstm_split_few_kernel<false>, bilstm_split_few_kernel<true>}};
-  int form = split_bf16 ? 2 : (fast_gates ? 1 : 0), per_wg = LSTM_ROWS;
-  // a few rows (one or two 600 x 900 images: 37 / 74): four rows per workgroup, the gate math spread over all lanes; identical bits
-  if (split_bf16 && rows <= 128) { form = 3; per_wg = LSTM_FEW; }
-  hipLaunchKernelGGL(kernels[form][xp_is_f16 ? 1 : 0], dim3((rows + per_wg - 1) / per_wg, 2), dim3(512), 0, s, xp, wh, out, rows, T);
+  const BilstmPlan p = bilstm_plan(rows, split_bf16, fast_gates);
+  hipLaunchKernelGGL(kernels[p.form][xp_is_f16 ? 1 : 0], dim3((rows + p.per_wg - 1) / p.per_wg, 2), dim3(512), 0, s, xp, wh, out, rows, T);
   return launch_status("bilstm");
 }
 

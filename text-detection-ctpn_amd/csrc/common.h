@@ -228,11 +228,30 @@ int launch_pack_transpose_split(const float* src, long long src_ld, void* dst, i
 // fast_gates: v_exp / v_rcp gate math in the exact-fp32 kernel (bf16 throughput mode)
 // xp_is_f16: the pre-activations are IEEE fp16 (16-bit throughput modes), else fp32
 int launch_bilstm(const void* xp, int xp_is_f16, const float* wh, float* out, int rows, int T, hipStream_t s, int split_bf16 = 0, int fast_gates = 0);
+// what launch_bilstm launches for a problem, and follows: form 0 exact-fp32 MFMA with library gates, 1 the same with v_exp / v_rcp gates, 2 split-bf16
+// product on 16 rows per workgroup, 3 on 4 rows per workgroup; host arithmetic only
+struct BilstmPlan { int form, per_wg; };
+BilstmPlan bilstm_plan(int rows, int split_bf16, int fast_gates);
 // lstm_pre.hip: the LSTM input projection of the 16-bit modes (resident weight slice, fp16 out): a = bordered NHWC map of n x hf x wf cells x 512
-int launch_lstm_pre(const void* a, const void* wt_frag, const float* bias, void* out, DType t, int n, int hf, int wf, hipStream_t s);
+// cu_count: the CU count the launch shape is planned for, 0 = the current device's (the product path; any other value is a test's)
+int launch_lstm_pre(const void* a, const void* wt_frag, const float* bias, void* out, DType t, int n, int hf, int wf, hipStream_t s, int cu_count = 0);
+// what launch_lstm_pre launches for `cells` feature-map cells on a device of ncu CUs, and follows; host arithmetic only
+struct LstmPrePlan {
+  int small;              // 1: lstm_pre_small_kernel (one wave per 32 cells x four column tiles), 0: lstm_pre_kernel
+  int waves;              // waves per workgroup (small form: 1)
+  long long workgroups;
+  int idle_waves;         // whole waves of the last workgroup that lie beyond the last cell (they still take part in every barrier and DMA)
+};
+LstmPrePlan lstm_pre_plan(long long cells, int ncu);
 int launch_lstm_pre_pack(const void* wt_x, void* wt_frag, hipStream_t s);      // [1024][512] 16-bit rows -> the kernel's fragment-major order (1 MB)
 int lstm_gate_col(int c);     // TF gate column (g * 128 + u) -> permuted column, per direction
 int launch_lstm_permute_rows(const void* src, void* dst, int row_bytes, hipStream_t s);
+// api_weights.hip: the input projection's weight chain, the one copy ctpn_load_weights_* and ctpn_debug_lstm_pre share. kx[d]: direction d's
+// [512 in][512 gates] fp32 block (kernel[:512]) with kx_ld floats per row, bias[d]: its 512 floats, all in TF's column order i | j | f | o ->
+// wt_x [1024][row_bytes] rows of prec's operand type (split precision: [hi | hi | lo]) and b_x [1024], both in lstm_gate_col's order, and
+// (wt_xf != nullptr: the 16-bit modes) launch_lstm_pre_pack's fragment-major copy of wt_x. Synchronises s.
+int pack_lstm_projection(const float* const kx[2], long long kx_ld, const float* const bias[2], DType prec, void* wt_x, size_t row_bytes, float* b_x,
+                         void* wt_xf, hipStream_t s);
 // proposal pipeline, one unit per stage: decode.hip, sort_keys.hip, nms.hip (device helpers they share: proposal_dev.h)
 struct ProposalCfg {
   int n, hf, wf;

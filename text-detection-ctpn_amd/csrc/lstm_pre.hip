@@ -237,25 +237,34 @@ int launch_lstm_pre_pack(const void* src, void* dst, hipStream_t s) {
   return launch_status("lstm_pre pack");
 }
 
+// The launch shape of lstm_pre for `cells` cells on ncu CUs (launch_lstm_pre follows it; ctpn_debug_lstm_pre_plan reports it)
+LstmPrePlan lstm_pre_plan(long long cells, int ncu) {
+  const long long groups = (cells + 31) / 32;                      // wave-groups of 32 cells
+  long long W = (groups + ncu - 1) / ncu;                          // waves per workgroup: one round of workgroups if 12 waves suffice
+  W = W < 1 ? 1 : (W > 12 ? 12 : W);
+  const long long cellblks = (groups + W - 1) / W;
+  if (cellblks * 2 <= ncu) {                                       // less than half a round of workgroups: one wave per (32 cells, four column tiles)
+    return LstmPrePlan{1, 1, groups * (32 / LPS_NT), 0};
+  }
+  return LstmPrePlan{0, (int)W, cellblks, (int)(cellblks * W - groups)};
+}
+
 // a: bordered NHWC 16-bit map of n x hf x wf cells x 512 channels (dtype t: BF16 or F16); wt: launch_lstm_pre_pack's output;
-// out: [n * hf * wf][1024] fp16
-int launch_lstm_pre(const void* a, const void* wt, const float* bias, void* out, DType t, int n, int hf, int wf, hipStream_t s) {
+// out: [n * hf * wf][1024] fp16; cu_count: plan for this many CUs (0: the current device's)
+int launch_lstm_pre(const void* a, const void* wt, const float* bias, void* out, DType t, int n, int hf, int wf, hipStream_t s, int cu_count) {
   if (!dtype_is_half(t)) return fail(CTPN_ERR_ARG, "lstm_pre: 16-bit modes only");
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "lstm_pre: cu_count is a CU count, or 0 for the current device's");
   LstmPre g{};
   g.a = a; g.wt = wt; g.bias = bias; g.out = out; g.M = (long long)n * hf * wf; g.hf = hf; g.wf = wf;
   if (g.M <= 0 || g.M > 0x7fffffffLL) return fail(CTPN_ERR_ARG, "lstm_pre: problem out of range");
 
-  int dev = 0, ncu = 0, rc;
-  if ((rc = current_device(dev)) || (rc = device_cu_count(dev, ncu))) return rc;
-  const long long groups = (g.M + 31) / 32;                        // wave-groups of 32 cells
-  long long W = (groups + ncu - 1) / ncu;                          // waves per workgroup: one round of workgroups if 12 waves suffice
-  W = W < 1 ? 1 : (W > 12 ? 12 : W);
-  // few cells (one image: 65 wave-groups): split the 32 column tiles of a cell range over 2 .. 8 workgroups so that the launch still fills the chip
-  const long long cellblks = (groups + W - 1) / W;
+  int dev = 0, ncu = cu_count, rc;
+  if ((rc = current_device(dev)) || (!ncu && (rc = device_cu_count(dev, ncu)))) return rc;
+  const LstmPrePlan p = lstm_pre_plan(g.M, ncu);
   g.cgroups = 1; g.nbuf = LP_NBUF;
-  if (cellblks * 2 <= ncu) {                                       // less than half a round of workgroups: one wave per (32 cells, four column tiles)
-    if (t == DType::F16) hipLaunchKernelGGL((lstm_pre_small_kernel<h_f16>), dim3((unsigned)(groups * (32 / LPS_NT))), dim3(64), 0, s, g);
-    else hipLaunchKernelGGL((lstm_pre_small_kernel<h_bf16>), dim3((unsigned)(groups * (32 / LPS_NT))), dim3(64), 0, s, g);
+  if (p.small) {
+    if (t == DType::F16) hipLaunchKernelGGL((lstm_pre_small_kernel<h_f16>), dim3((unsigned)p.workgroups), dim3(64), 0, s, g);
+    else hipLaunchKernelGGL((lstm_pre_small_kernel<h_bf16>), dim3((unsigned)p.workgroups), dim3(64), 0, s, g);
     return launch_status("lstm_pre (small)");
   }
   const int lds = g.nbuf * LP_TILE_B + 1024 * 4;
@@ -263,7 +272,7 @@ int launch_lstm_pre(const void* a, const void* wt, const float* bias, void* out,
     static bool done[CTPN_MAX_DEV] = {false};
     const int r = raise_dynamic_lds((const void*)kern, LP_NBUF * LP_TILE_B + 1024 * 4, done, dev);
     if (r) return r;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(cellblks * g.cgroups)), dim3(64 * W), lds, s, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(p.workgroups * g.cgroups)), dim3(64 * p.waves), lds, s, g);
     return CTPN_OK;
   };
   rc = t == DType::F16 ? launch(lstm_pre_kernel<h_f16>) : launch(lstm_pre_kernel<h_bf16>);

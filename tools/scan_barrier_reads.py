@@ -18,7 +18,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "text-detection-ctpn_amd", "csrc")
-MUST_BE_CLEAN = ("conv3x3_p_kernel", "conv3x3_kernel")
+MUST_BE_CLEAN = ("conv3x3_p_kernel", "conv3x3_kernel", "lstm_pre_kernel", "igemm_kernel")
 
 
 def scan(asm):

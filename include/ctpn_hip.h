@@ -330,7 +330,10 @@ int ctpn_detect(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int 
 /* Asynchronous form of ctpn_detect for throughput: submit enqueues the whole device part of a batch (forward on the
  * ctx stream; proposal layer + connector front end + D2H on a second stream) into slot 0 or 1 and returns at once;
  * collect waits for that slot, runs the host part of the connector and fills the outputs. With two slots the host
- * part of batch k and the latency-bound sort / NMS kernels overlap the convolutions of batch k+1. A slot must be
+ * part of batch k and the latency-bound sort / NMS kernels overlap the convolutions of batch k+1. A submit that finds the
+ * other slot in flight runs its forward on a second stream and a second set of forward buffers, allocated then (not with
+ * keep_acts = 1 or per-stage profiling; without the memory the ctx stays on one set): its first layers run beside the other
+ * batch's recurrent tail. Results do not depend on what runs beside what. A slot must be
  * collected before it is submitted to again; images must stay valid until the forward of that submit has run
  * (device pointers: until ctpn_sync or the matching collect). */
 int ctpn_detect_submit(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w,
@@ -422,6 +425,11 @@ const char* ctpn_debug_conv3x3_form_name(int kind, int id);
  *   in_precision: CTPN_PREC_FP32 / BF16 / FP16), w [K][Co], out [M][ldc]: columns Co .. ldc - 1 come back holding the fill (bytes 0xC3), and a
  *   pad column that changed is CTPN_ERR_STATE. K a multiple of 32 (fp32) / 64, Co and ldc of 4. */
 int ctpn_debug_lstm_pre_plan(long long cells, int cu_count, int* plan_out);
+/* The forward sets of a ctx (test hook; pure host read). A ctx owns one set of forward buffers and one forward stream from ctpn_create; the
+ * first ctpn_detect_submit* that finds the other slot in flight adds a second (see ctpn_detect_submit), unless keep_acts is set, per-stage
+ * profiling is on or the memory is not there. out4: [0] sets allocated (1 or 2)  [1] the set of the most recent forward (0 or 1)
+ * [2] device bytes of set 1 (0 without it)  [3] the set the batch in flight in slot 0 runs on | that of slot 1 << 8 (-1 for an idle slot, as 255). */
+int ctpn_debug_forward_sets(ctpn_ctx* ctx, long long* out4);
 int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const float* bias, int n, int hf, int wf, int precision, int cu_count,
                         float* out);
 int ctpn_debug_bilstm(int device_id, const float* pre, const float* wh, int rows, int T, int split, int fast_gates, int pre_f16, float* out,

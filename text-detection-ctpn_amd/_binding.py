@@ -115,6 +115,7 @@ def _declare(lib):
         "ctpn_debug_conv3x3_plan": (C.c_int, [C.c_int] * 13 + [i32p]),
         "ctpn_debug_conv3x3_form_name": (C.c_char_p, [C.c_int, C.c_int]),
         "ctpn_debug_lstm_pre_plan": (C.c_int, [C.c_longlong, C.c_int, i32p]),
+        "ctpn_debug_forward_sets": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
         "ctpn_debug_lstm_pre": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
         "ctpn_debug_bilstm": (C.c_int, [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, i32p]),
         "ctpn_debug_gemm": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
@@ -816,6 +817,14 @@ class Context:
         v = C.c_double(0.0)
         _check(self._lib.ctpn_get_param(self._h, name.encode(), C.byref(v)))
         return v.value
+
+    def forward_sets(self):
+        """ctpn_debug_forward_sets: (sets allocated, set of the most recent forward, device bytes of set 1, (set of slot 0's batch in flight or
+        None, set of slot 1's))."""
+        out = (C.c_longlong * 4)()
+        _check(self._lib.ctpn_debug_forward_sets(self._h, out))
+        in_flight = tuple(None if v == 255 else v for v in (int(out[3]) & 255, (int(out[3]) >> 8) & 255))
+        return int(out[0]), int(out[1]), int(out[2]), in_flight
 
     def host_threads(self):
         n = C.c_int(0)

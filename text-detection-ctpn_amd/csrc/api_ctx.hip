@@ -18,6 +18,21 @@ static int dev_alloc(ctpn_ctx* c, void** p, size_t bytes, bool zero) {
   return CTPN_OK;
 }
 
+// How two forwards on two sets (ctx.h, FwdSet) may overlap. 2, the product library's: a forward's conv stack starts behind the OTHER set's conv
+// stack -- its q-image is built beside that stack's last layer, its conv1_2 (dynamic tile claims) runs beside the other batch's lstm_pre,
+// recurrence and heads GEMM and takes the CUs they leave free. Measured on one box, five alternating runs each (profiles/ab_two_forwards.txt):
+// 3766 - 3776 images/s against the parent's 3710 - 3717, +1.5 %. The other modes exist in the measurement build only (make ablation,
+// CTPN_TWO_FORWARDS): 0 one set, the single-stream order (3712 - 3716); 1 the two forwards overlap freely -- two whole persistent conv kernels
+// side by side, each at half speed and a little worse (3585 - 3620, -2.8 %); 3 the gate behind the other set's lstm_pre (3741 - 3751, +0.9 %).
+int two_forwards_mode() {
+#ifdef CTPN_ABLATION
+  static const int v = env_int("CTPN_TWO_FORWARDS", 2);
+  return v < 0 || v > 3 ? 2 : v;
+#else
+  return 2;
+#endif
+}
+
 int debug_sync() { static const int v = env_int("CTPN_DEBUG_SYNC", 0); return v; }
 // CTPN_ROCTX=1: roctx ranges (rocprofv3 --marker-trace). librocprofiler-sdk-roctx.so is dlopen'ed on first use, so the library has no
 // link-time dependency on the profiler SDK: an install without it still loads, and CTPN_ROCTX=1 there is a silent no-op.
@@ -45,15 +60,36 @@ int roctx_on() { return roctx_api().push != nullptr; }
 
 static int prof_drain(ctpn_ctx* c) {
   if (c->pending.empty()) return CTPN_OK;
-  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(sync_forwards(c));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  // Mode 2's records (span: one [first conv start, last conv end] pair per forward) may come from two forwards that were in flight together, on
+  // two streams: their SUM would count the interleaved time twice. What is reported is the length of the UNION of the intervals -- the time during
+  // which a conv stack was running. Event times of one device are comparable across streams; intervals that do not overlap (every synchronous
+  // caller, one forward set) contribute exactly their own elapsed time, as before. Everything pending here has completed (the syncs above), and a
+  // later drain's forwards start after them, so the union per drain is the union over the run.
+  struct Span { double t0, t1; float own; };
+  std::vector<Span> spans;
+  hipEvent_t origin = nullptr;
   for (auto& r : c->pending) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-      c->prof_ms[r.kind] += ms; c->prof_n[r.kind] += r.launches; c->prof_work[r.kind] += r.work;
+      c->prof_n[r.kind] += r.launches; c->prof_work[r.kind] += r.work;
+      float off = 0.f;
+      if (!r.span) c->prof_ms[r.kind] += ms;
+      else if (!origin) { origin = r.a; spans.push_back({0.0, (double)ms, ms}); }
+      else if (hipEventElapsedTime(&off, origin, r.a) == hipSuccess) spans.push_back({(double)off, (double)off + (double)ms, ms});
+      else c->prof_ms[r.kind] += ms;
     }
-    c->free_events.push_back(r.a); c->free_events.push_back(r.b);
   }
+  std::sort(spans.begin(), spans.end(), [](const Span& x, const Span& y) { return x.t0 < y.t0; });
+  double covered = 0.0;
+  for (size_t i = 0; i < spans.size(); ++i) {
+    const Span& sp = spans[i];
+    if (i == 0 || sp.t0 >= covered) c->prof_ms[CTPN_KIND_CONV_GEMM] += sp.own;
+    else if (sp.t1 > covered) c->prof_ms[CTPN_KIND_CONV_GEMM] += sp.t1 - covered;
+    if (i == 0 || sp.t1 > covered) covered = sp.t1;
+  }
+  for (auto& r : c->pending) { c->free_events.push_back(r.a); c->free_events.push_back(r.b); }
   c->pending.clear();
   return CTPN_OK;
 }
@@ -122,7 +158,10 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   // (the proposal stream at the highest stream priority: measured in round 6 with the tail confined -- 1163 against 1164 images/s in split precision,
   // -0.2 % in bf16: the dispatcher does not hand CUs to the 1024-thread NMS workgroups any sooner. Not used.)
   if (hipStreamCreateWithFlags(&c->stream_p, hipStreamNonBlocking) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return fail(CTPN_ERR_HIP, "hipStreamCreate failed"); }
-  if (hipEventCreateWithFlags(&c->ev_conv, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess) {
+  ctpn_ctx::FwdSet& f0 = c->fs[0];      // today's allocation on `stream`
+  f0.stream = c->stream;
+  if (hipEventCreateWithFlags(&f0.ev_conv, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&f0.ev_tail, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&f0.ev_gate, hipEventDisableTiming) != hipSuccess) {
     ctpn_destroy(c); return fail(CTPN_ERR_HIP, "ctpn_create: events");
   }
   for (auto& sl : c->slot) {
@@ -174,8 +213,8 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
     const size_t pix_b = (size_t)kConvs[i].co * ((c->prec == DType::SPLIT && i == 13) ? 6 : c->es);
     c->act_conv_bytes[i] = ((size_t)max_batch * (hl + 2) * (wl + 2) + act_slack_pixels(wl)) * pix_b;
     const size_t front = act_front_pixels(wl) * pix_b;
-    A(&c->act_conv[i], front + c->act_conv_bytes[i], true);
-    if (c->act_conv[i]) c->act_conv[i] = (char*)c->act_conv[i] + front;     // allocs[] keeps the pointer hipFree needs
+    A(&f0.act_conv[i], front + c->act_conv_bytes[i], true);
+    if (f0.act_conv[i]) f0.act_conv[i] = (char*)f0.act_conv[i] + front;     // allocs[] keeps the pointer hipFree needs
   }
   {
     const int pool_src[4] = {1, 3, 6, 9};
@@ -183,11 +222,11 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
       const int hl = lvl(max_h, p + 1), wl = lvl(max_w, p + 1);
       c->act_pool_bytes[p] = ((size_t)max_batch * (hl + 2) * (wl + 2) + act_slack_pixels(wl)) * kConvs[pool_src[p]].co * c->es;
       const size_t front = act_front_pixels(wl) * kConvs[pool_src[p]].co * c->es;
-      A(&c->act_pool[p], front + c->act_pool_bytes[p], true);
-      if (c->act_pool[p]) c->act_pool[p] = (char*)c->act_pool[p] + front;
+      A(&f0.act_pool[p], front + c->act_pool_bytes[p], true);
+      if (f0.act_pool[p]) f0.act_pool[p] = (char*)f0.act_pool[p] + front;
     }
   }
-  if (dtype_is_half(c->prec)) { c->q_img_bytes = conv1_q_bytes(max_batch, max_h, max_w); A(&c->q_img, c->q_img_bytes, true); }
+  if (dtype_is_half(c->prec)) { c->q_img_bytes = conv1_q_bytes(max_batch, max_h, max_w); A(&f0.q_img, c->q_img_bytes, true); }
   A((void**)&c->img_dev, (size_t)max_batch * max_h * max_w * 3 * sizeof(float), false);
   c->img_dev_b[0] = c->img_dev;
   A((void**)&c->img_dev_b[1], (size_t)max_batch * max_h * max_w * 3 * sizeof(float), false);
@@ -197,10 +236,10 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
       ok = hipEventCreateWithFlags(&c->ev_copied[b], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_consumed[b], hipEventDisableTiming) == hipSuccess;
     if (!ok) rc = fail(CTPN_ERR_HIP, "ctpn_create: copy stream / events");
   }
-  A((void**)&c->xp, c->m5_max * 1024 * sizeof(float), false);
-  A((void**)&c->lstm_out, c->m5_max * 256 * sizeof(float), false);
-  A((void**)&c->fc_out, c->m5_max * 512 * sizeof(float), false);
-  A((void**)&c->heads, c->m5_max * 64 * sizeof(float), true);
+  A((void**)&f0.xp, c->m5_max * 1024 * sizeof(float), false);
+  A((void**)&f0.lstm_out, c->m5_max * 256 * sizeof(float), false);
+  A((void**)&f0.fc_out, c->m5_max * 512 * sizeof(float), false);
+  A((void**)&f0.heads, c->m5_max * 64 * sizeof(float), true);
   }  // !postproc_only
   A((void**)&c->cls_prob, c->m5_max * 20 * sizeof(float), false);
   A((void**)&c->bbox_pred, c->m5_max * 40 * sizeof(float), false);
@@ -239,6 +278,63 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   if (rc != CTPN_OK) { ctpn_destroy(c); return rc; }
   *out = c;
   return CTPN_OK;
+}
+
+// bytes in front of a bordered activation buffer (act_front_pixels): conv layer i / pooled map p
+static size_t conv_front_bytes(const ctpn_ctx* c, int i) {
+  return act_front_pixels(lvl(c->max_w, kConvs[i].level)) * (size_t)kConvs[i].co * ((c->prec == DType::SPLIT && i == 13) ? 6 : c->es);
+}
+static size_t pool_front_bytes(const ctpn_ctx* c, int p) {
+  const int pool_src[4] = {1, 3, 6, 9};
+  return act_front_pixels(lvl(c->max_w, p + 1)) * (size_t)kConvs[pool_src[p]].co * c->es;
+}
+
+// one zeroed block of forward set 1, on the set's stream (the forward that reads it follows on that stream); false: out of memory
+static bool set1_block(ctpn_ctx* c, ctpn_ctx::FwdSet& f, void** p, size_t front, size_t bytes) {
+  void* raw = nullptr;
+  if (hipMalloc(&raw, front + bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+  f.allocs.push_back(raw);
+  if (hipMemsetAsync(raw, 0, front + bytes, f.stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+  *p = (char*)raw + front;
+  c->set1_bytes += front + bytes;
+  return true;
+}
+
+// Forward set 1 (ctx.h, FwdSet), on the first submit that finds the other slot in flight: a stream, the two tail_overlap events and the buffers the
+// production path stores -- every unpooled layer's map but conv1_1's, the four pooled maps, the q-image, lstm_pre, lstm_out, heads, and lstm_o
+// where the heads GEMM is not folded (fp32, split precision). At 32 x 600 x 900 in bf16 that is 4.7 GB beside the 11.2 GB of set 0: the
+// full-resolution maps of the four pooled layers and conv1_1's are 6.4 GB. need_conv1: the forward about to run stores conv1_1's map (a ragged
+// batch, conv1_fuse = 0, fp32 / split precision): that one block is added when first asked for.
+// false: this ctx stays on set 0 (keep_acts stores maps set 1 has no room for; per-stage profiling times one stream; no memory) -- never an error.
+bool ensure_set1(ctpn_ctx* c, bool need_conv1) {
+  if (two_forwards_mode() == 0 || c->postproc_only || c->keep_acts || (c->prof && c->prof_mode == 1) || c->set1_state < 0) return false;
+  ctpn_ctx::FwdSet& f = c->fs[1];
+  if (c->set1_state == 0) {
+    bool ok = hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking) == hipSuccess &&
+              hipEventCreateWithFlags(&f.ev_conv, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&f.ev_tail, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&f.ev_gate, hipEventDisableTiming) == hipSuccess;
+    for (int i = 1; i < 14 && ok; ++i)
+      if (!kConvs[i].pool_after) ok = set1_block(c, f, &f.act_conv[i], conv_front_bytes(c, i), c->act_conv_bytes[i]);
+    for (int p = 0; p < 4 && ok; ++p) ok = set1_block(c, f, &f.act_pool[p], pool_front_bytes(c, p), c->act_pool_bytes[p]);
+    if (ok && dtype_is_half(c->prec)) ok = set1_block(c, f, &f.q_img, 0, c->q_img_bytes);
+    ok = ok && set1_block(c, f, (void**)&f.xp, 0, c->m5_max * 1024 * sizeof(float)) && set1_block(c, f, (void**)&f.lstm_out, 0, c->m5_max * 256 * sizeof(float)) &&
+         set1_block(c, f, (void**)&f.heads, 0, c->m5_max * 64 * sizeof(float));
+    if (ok && !dtype_is_half(c->prec)) ok = set1_block(c, f, (void**)&f.fc_out, 0, c->m5_max * 512 * sizeof(float));
+    if (!ok) {
+      (void)hipGetLastError();
+      if (f.stream) (void)hipStreamSynchronize(f.stream);
+      for (void* p : f.allocs) (void)hipFree(p);
+      for (hipEvent_t e : {f.ev_conv, f.ev_tail, f.ev_gate}) if (e) (void)hipEventDestroy(e);
+      if (f.stream) (void)hipStreamDestroy(f.stream);
+      f = ctpn_ctx::FwdSet();
+      c->set1_bytes = 0;
+      c->set1_state = -1;
+      return false;
+    }
+    c->set1_state = 1;
+  }
+  if (need_conv1 && !f.act_conv[0] && !set1_block(c, f, &f.act_conv[0], conv_front_bytes(c, 0), c->act_conv_bytes[0])) return false;      // this submit runs on set 0
+  return true;
 }
 
 // ---- options: behaviour switches of ONE ctx (two ctxs in a process can choose differently; nothing here is read from the environment) ----
@@ -305,10 +401,10 @@ int ctpn_set_option(ctpn_ctx* c, const char* key, int value) {
   if (c->*(o->member) == value) return CTPN_OK;
   // a switch changes what the queued work would read / which stream runs it: drain first
   CTPN_HIP_TRY(hipSetDevice(c->device));
-  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(sync_forwards(c));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
   for (auto& sl : c->slot) if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_set_option: a submitted batch has not been collected");
-  c->tail_pending = false;
+  for (auto& f : c->fs) f.tail_pending = false;
   c->nms_mw_dirty = true;           // both streams are drained: the next proposal launch re-zeroes the multi-workgroup NMS's scratch (8 KB memset)
   c->*(o->member) = value;
   return CTPN_OK;
@@ -330,10 +426,10 @@ int ctpn_set_param(ctpn_ctx* c, const char* name, double value) {
   if (c->tail_raw[idx] == value) return CTPN_OK;
   // the queued tail reads these (and lays its buffers out by RPN_POST_NMS_TOP_N): drain first
   CTPN_HIP_TRY(hipSetDevice(c->device));
-  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(sync_forwards(c));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
   for (auto& sl : c->slot) if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_set_param: a submitted batch has not been collected");
-  c->tail_pending = false;
+  for (auto& f : c->fs) f.tail_pending = false;
   c->nms_mw_dirty = true;
   c->tail_raw[idx] = value;
   switch (idx) {
@@ -363,6 +459,7 @@ int ctpn_destroy(ctpn_ctx* c) {
   if (!c) return CTPN_OK;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->fs[1].stream) (void)hipStreamSynchronize(c->fs[1].stream);
   if (c->stream_p) (void)hipStreamSynchronize(c->stream_p);
   if (c->stream_c) { (void)hipStreamSynchronize(c->stream_c); (void)hipStreamDestroy(c->stream_c); }
   for (int b = 0; b < 2; ++b) { if (c->pin_stage[b]) (void)hipHostFree(c->pin_stage[b]); if (c->ev_h2d_done[b]) (void)hipEventDestroy(c->ev_h2d_done[b]); }
@@ -371,9 +468,13 @@ int ctpn_destroy(ctpn_ctx* c) {
     for (void* p : {(void*)sl.pack, (void*)sl.im_info, (void*)sl.crecs, (void*)sl.ccnt}) if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {sl.ev_heads, sl.ev_decoded, sl.ev_done}) if (e) (void)hipEventDestroy(e);
   }
-  for (hipEvent_t e : {c->ev_conv, c->ev_tail}) if (e) (void)hipEventDestroy(e);
+  for (auto& f : c->fs) {
+    for (hipEvent_t e : {f.ev_conv, f.ev_tail, f.ev_gate}) if (e) (void)hipEventDestroy(e);
+    if (f.ragged_blob) (void)hipFree(f.ragged_blob);
+    for (void* p : f.allocs) (void)hipFree(p);
+  }
+  if (c->fs[1].stream) (void)hipStreamDestroy(c->fs[1].stream);
   for (auto& r : c->ragged) { if (r.host) (void)hipHostFree(r.host); if (r.dev) (void)hipFree(r.dev); if (r.ev_copied) (void)hipEventDestroy(r.ev_copied); }
-  if (c->ragged_blob) (void)hipFree(c->ragged_blob);
   for (auto& j : c->jpeg) {
     if (j.coef_host) (void)hipHostFree(j.coef_host);
     if (j.qt_host) (void)hipHostFree(j.qt_host);
@@ -407,7 +508,7 @@ int ctpn_destroy(ctpn_ctx* c) {
 
 int ctpn_sync(ctpn_ctx* c) {
   if (!c) return fail(CTPN_ERR_ARG, "null ctx");
-  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(sync_forwards(c));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
   if (c->stream_c) CTPN_HIP_TRY(hipStreamSynchronize(c->stream_c));      // staged copies, ctpn_decode_jpeg_batch
   return CTPN_OK;

@@ -203,6 +203,15 @@ struct DevBufs {      // hipFree on every way out
 }  // namespace
 extern "C" {
 
+int ctpn_debug_forward_sets(ctpn_ctx* c, long long* out4) {
+  if (!c || !out4) return fail(CTPN_ERR_ARG, "ctpn_debug_forward_sets: null pointer");
+  out4[0] = c->set1_state == 1 ? 2 : 1;
+  out4[1] = c->last == &c->fs[1] ? 1 : 0;
+  out4[2] = (long long)c->set1_bytes;
+  out4[3] = (c->slot[0].busy ? c->slot[0].set : 255) | (c->slot[1].busy ? c->slot[1].set : 255) << 8;
+  return CTPN_OK;
+}
+
 int ctpn_debug_lstm_pre_plan(long long cells, int cu_count, int* plan_out) {
   if (!plan_out) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre_plan: no output");
   if (cells <= 0 || cells > 0x7fffffffLL) return fail(CTPN_ERR_ARG, "ctpn_debug_lstm_pre_plan: cells out of range (1 .. 2^31 - 1)");

@@ -39,6 +39,22 @@ static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hip
   return CTPN_OK;
 }
 
+// The forward set a submit to `slot` runs on (ctx.h, FwdSet). Nothing else in flight: set 0, the synchronous callers' set. The other slot in flight:
+// the set that batch does NOT use, so that the two forwards run on two streams and write two sets of buffers -- if this ctx can have a second set
+// (ensure_set1: not with keep_acts, not under per-stage profiling, not without the memory) with room for what this forward stores; else set 0 again,
+// behind the batch in flight on the one stream, the order a ctx with one set always had. beside: the two forwards are on different sets.
+// Correctness needs no more cross-batch order than that: a set is reused by the batch two submits on, whose slot the host has collected (ev_done)
+// first. The gate forward_impl puts between the two sets' conv stacks is for speed alone (api_ctx.hip, two_forwards_mode).
+static ctpn_ctx::FwdSet& pick_set(ctpn_ctx* c, int slot, int n, int h, int w, const int* heights, bool& beside) {
+  const ctpn_ctx::Slot& other = c->slot[slot ^ 1];
+  beside = false;
+  if (!other.busy) return c->fs[0];
+  if (other.set == 1) { beside = true; return c->fs[0]; }
+  if (!ensure_set1(c, !forward_fuses_conv1(c, 0, n, h, w, heights))) return c->fs[0];
+  beside = true;
+  return c->fs[1];
+}
+
 // lone: a synchronous ctpn_detect with nothing else in flight on this ctx -- the proposal layer and the connector front end then follow the
 // forward on ITS stream instead of hopping to the proposal stream (an event record + a cross-queue wait: ~12 us of a lone image's millisecond;
 // the second stream exists to run the tail under the NEXT batch's convolutions, and there is no next batch here)
@@ -49,34 +65,37 @@ static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_
   if (slot < 0 || slot > 1) return fail(CTPN_ERR_ARG, "ctpn_detect_submit: slot must be 0 or 1");
   ctpn_ctx::Slot& sl = c->slot[slot];
   if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_detect_submit: slot still holds an uncollected batch");
-  int rc = forward_impl(c, images, 0, images_on_device, n, h, w, c->tail_overlap != 0, heights, slot);
+  bool beside = false;
+  ctpn_ctx::FwdSet& f = pick_set(c, slot, n, h, w, heights, beside);
+  int rc = forward_impl(c, f, images, 0, images_on_device, n, h, w, c->tail_overlap != 0, heights, slot, beside);
   if (rc) {
     // a forward that failed midway may have consumed the cross-stream hand-over state (tail_pending is cleared when the wait is ENQUEUED,
     // the events are recorded later): drain both streams so that a retry starts from a quiet ctx, keeping the first error text
     const std::string first = ctpn_last_error();
-    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stream_p);
-    c->tail_pending = false; c->ev_last_decoded = nullptr; c->ev_last_done = nullptr;
+    (void)sync_forwards(c); (void)hipStreamSynchronize(c->stream_p);
+    for (auto& g : c->fs) { g.tail_pending = false; g.ev_decoded = nullptr; g.dec_slot = -1; }
+    c->ev_last_done = nullptr;
     return fail(rc, first);
   }
   // im_info row i = [the image's own height, w, scale]: what the proposal layer clips to, and lines_prep, the connector's NMS and connect_kernel read
   sl.hts.assign(n, h);
   if (heights) sl.hts.assign(heights, heights + n);
   for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)sl.hts[i]; sl.im_info[3 * i + 1] = (float)w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
-  hipStream_t p = lone ? c->stream : c->stream_p;
+  hipStream_t p = lone ? f.stream : c->stream_p;
   if (!lone) {
-    CTPN_HIP_TRY(hipEventRecord(sl.ev_heads, c->stream));
+    CTPN_HIP_TRY(hipEventRecord(sl.ev_heads, f.stream));
     CTPN_HIP_TRY(hipStreamWaitEvent(p, sl.ev_heads, 0));
   }
   // cfg.TEST.RPN_* (reference lib/fast_rcnn/config.py:175-183): the ctx's parameters, those defaults unless ctpn_set_param changed them
-  rc = enqueue_proposals(c, c->heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded,
-                         c->fwd_ragged >= 0 ? c->ragged[c->fwd_ragged].dev + n : nullptr);
+  rc = enqueue_proposals(c, f.heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded,
+                         f.fwd_ragged >= 0 ? c->ragged[f.fwd_ragged].dev + n : nullptr);
   if (rc) return rc;
-  c->ev_last_decoded = sl.ev_decoded;
+  f.ev_decoded = sl.ev_decoded; f.dec_slot = slot;      // the reader of this set's `heads` (forward_impl: wait_decoded)
   if ((rc = enqueue_text_lines(c, sl, n, w, p))) return rc;
   CTPN_HIP_TRY(hipMemcpyAsync(sl.pack, c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));      // tl_* (host connector), rois, counts: one copy
   CTPN_HIP_TRY(hipEventRecord(sl.ev_done, p));
   c->ev_last_done = sl.ev_done;
-  sl.n = n; sl.h = h; sl.w = w; sl.busy = true;
+  sl.n = n; sl.h = h; sl.w = w; sl.busy = true; sl.set = (int)(&f - c->fs);
   return CTPN_OK;
 }
 static int detect_submit_impl(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const float* scales, int slot, bool lone,
@@ -139,7 +158,7 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
     if (roi_counts[i] < 0 || roi_counts[i] > post) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: 0 <= roi_counts[i] <= RPN_POST_NMS_TOP_N (1000) rows of [score,x1,y1,x2,y2]");
   if (c->slot[0].busy || c->slot[1].busy) return fail(CTPN_ERR_STATE, "ctpn_debug_text_lines: a submitted batch has not been collected");
   CTPN_HIP_TRY(hipSetDevice(c->device));
-  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));      // the proposal entry points use these buffers on the forward's stream
+  CTPN_HIP_TRY(sync_forwards(c));      // the proposal entry points use these buffers on the forward's stream
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
   ctpn_ctx::Slot& sl = c->slot[0];
   hipStream_t p = c->stream_p;

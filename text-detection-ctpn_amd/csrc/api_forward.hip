@@ -41,7 +41,18 @@ static int ragged_mask_act(void* buf, size_t pix_bytes, int level, const int* he
   return launch_ragged_mask(buf, m, heights_dev, n, pad, s);
 }
 
-int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p, const int* heights, int rset) {
+// One rule for forward_impl and for pick_set (api_detect.hip), which has to know whether the forward will store conv1_1's map before it
+// chooses the set: the uint8 feed of the 16-bit modes through the q-image ("conv1_kernel" = 2), "conv1_fuse", no keep_acts, a uniform batch,
+// a shape the fused launch takes
+bool forward_fuses_conv1(const ctpn_ctx* c, int is_f32, int n, int h, int w, const int* heights) {
+  bool ragged = false;
+  for (int i = 0; heights && i < n; ++i) ragged = ragged || heights[i] != h;
+  const bool via_q = !is_f32 && dtype_is_half(c->prec) && c->conv1_mfma >= 2 && c->fs[0].q_img != nullptr;
+  return via_q && c->conv1_fuse && !c->keep_acts && !ragged && conv1_fusable(c->prec, n, h, w, 64, 64, true, false);
+}
+
+int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p, const int* heights, int rset,
+                 bool beside) {
   if (!c || !images) return fail(CTPN_ERR_ARG, "null pointer");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_forward: post-processing-only ctx (ctpn_create_postproc) has no network");
   if (!c->weights_loaded) return fail(CTPN_ERR_STATE, "ctpn_forward: weights not loaded");
@@ -57,27 +68,35 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
     }
   }
   CTPN_HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
+  hipStream_t s = f.stream;
   int rc;
   hipStream_t ts = tail_on_p ? c->stream_p : s;      // stream of the recurrent tail
+  const ctpn_ctx::FwdSet* prev_set = c->last;       // the set of the forward enqueued in front of this one
   if (!tail_on_p) {
-    // a forward that keeps everything on `s` rewrites xp / lstm_out / heads there: after their readers on stream_p -- the previous
-    // asynchronous batch's tail (if it ran there) and its decode kernel. The decode kernel reads `heads` only, so that wait sits in front of
+    // a forward that keeps everything on `s` rewrites the set's xp / lstm_out / heads there: after their readers on stream_p -- the tail of the
+    // set's previous asynchronous batch (if it ran there) and its decode kernel. The decode kernel reads `heads` only, so that wait sits in front of
     // the GEMM that writes `heads`, at the END of this forward (at its start it put the cross-stream round trip heads -> decode -> next
     // forward, ~45 us, between every two batches: round 4's batch-1 and batch-32 timelines)
-    if (c->tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; }
+    if (f.tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, f.ev_tail, 0)); f.tail_pending = false; }
   }
+  // Cross-batch order of `heads`: its last reader is the decode kernel of the set's previous submit. Where the most recent forward ran on this
+  // set (one set in use: every synchronous caller, keep_acts, the fall-back) that is the batch just in front of this one and the wait stands, as
+  // it always did. Where the two slots alternate between the sets, the reader is the batch two submits back: its slot has been collected -- the
+  // host has seen ev_done, which stream_p records behind the decode kernel -- before this submit could reuse it, and no wait is enqueued (7.5 us
+  // of an idle stream in front of the heads GEMM). A reader whose slot is still uncollected gets the wait whichever set ran last.
+  const bool reader_live = f.ev_decoded && (prev_set == &f || (f.dec_slot >= 0 && c->slot[f.dec_slot].busy));
   auto wait_decoded = [&]() -> int {
-    if (!tail_on_p && c->ev_last_decoded) CTPN_HIP_TRY(hipStreamWaitEvent(ts, c->ev_last_decoded, 0));
+    if (!tail_on_p && reader_live) CTPN_HIP_TRY(hipStreamWaitEvent(ts, f.ev_decoded, 0));
     return CTPN_OK;
   };
   // borders must be zero for this geometry
-  if (c->gn != n || c->gh != h || c->gw != w) {
-    if (c->tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; }   // it still reads rpn_conv's output
-    for (int i = 0; i < 14; ++i) CTPN_HIP_TRY(hipMemsetAsync(c->act_conv[i], 0, c->act_conv_bytes[i], s));
-    for (int p = 0; p < 4; ++p) CTPN_HIP_TRY(hipMemsetAsync(c->act_pool[p], 0, c->act_pool_bytes[p], s));
-    if (c->q_img) CTPN_HIP_TRY(hipMemsetAsync(c->q_img, 0, c->q_img_bytes, s));      // the zero frame around every image (only image pixels are rewritten)
-    c->gn = n; c->gh = h; c->gw = w;
+  if (f.gn != n || f.gh != h || f.gw != w) {
+    if (f.tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, f.ev_tail, 0)); f.tail_pending = false; }   // it still reads rpn_conv's output
+    // (each set re-zeroes its own buffers, when its own geometry changes; set 1 has no buffer for a map the production path does not store)
+    for (int i = 0; i < 14; ++i) if (f.act_conv[i]) CTPN_HIP_TRY(hipMemsetAsync(f.act_conv[i], 0, c->act_conv_bytes[i], s));
+    for (int p = 0; p < 4; ++p) CTPN_HIP_TRY(hipMemsetAsync(f.act_pool[p], 0, c->act_pool_bytes[p], s));
+    if (f.q_img) CTPN_HIP_TRY(hipMemsetAsync(f.q_img, 0, c->q_img_bytes, s));      // the zero frame around every image (only image pixels are rewritten)
+    f.gn = n; f.gh = h; f.gw = w;
   }
   const void* img = images;
   int staged = -1;
@@ -114,8 +133,9 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
     CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_copied[staged], 0));
     img = c->img_dev_b[staged];
   }
-  c->n = n; c->h = h; c->w = w;
-  c->fwd_ragged = ragged ? rset : -1;
+  f.n = n; f.h = h; f.w = w;
+  c->last = &f;
+  f.fwd_ragged = ragged ? rset : -1;
   const int* hts_dev = nullptr;
   if (ragged) {
     if ((rc = ragged_upload(c, c->ragged[rset], heights, n, s))) return rc;
@@ -130,43 +150,44 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
       }
   bool via_q = false, fuse1 = false;
   {
-    Timed t(c, CTPN_KIND_CONV_FIRST, (double)n * h * w * (3.0 + 64.0 * c->es));
+    Timed t(c, CTPN_KIND_CONV_FIRST, (double)n * h * w * (3.0 + 64.0 * c->es), s);
     // 16-bit modes: "conv1_kernel" picks exact-pixel MFMA through the q-image (2, uint8 feed) / split-operand MFMA (1) / VALU (0); split precision always takes the
     // split-operand MFMA kernel (fp32-class sums, stored as (hi, lo) planes); fp32: the VALU kernel
     const bool frags = c->prec == DType::SPLIT || (c->conv1_mfma && dtype_is_half(c->prec));
     // uint8 feed of the 16-bit modes ("conv1_kernel" = 2): bytes -> q-image; conv1_1 then runs inside conv1_2's window stage (the production
     // path: its 69 MB per image are never stored) or, with keep_acts / "conv1_fuse" = 0, stand-alone from the q-image: the same bytes
-    via_q = !is_f32 && dtype_is_half(c->prec) && c->conv1_mfma >= 2 && c->q_img != nullptr;
+    via_q = !is_f32 && dtype_is_half(c->prec) && c->conv1_mfma >= 2 && f.q_img != nullptr;
     // a ragged batch takes the stand-alone form: the fused one never stores conv1_1, so nothing could be cleared below an image, where it
     // yields ReLU(bias) and not 0 (the two forms store the same bytes: option conv1_fuse)
-    fuse1 = via_q && c->conv1_fuse && !c->keep_acts && !ragged && conv1_fusable(c->prec, n, h, w, 64, 64, true, false);
+    fuse1 = forward_fuses_conv1(c, is_f32, n, h, w, ragged ? heights : nullptr);
+    if (!fuse1 && !f.act_conv[0]) return fail(CTPN_ERR_STATE, "ctpn_forward: the forward set has no buffer for conv1_1's map");      // pick_set vouches for it
     if (via_q) {
-      if ((rc = launch_image_to_q((const uint8_t*)img, c->q_img, c->prec, n, h, w, s))) return rc;
+      if ((rc = launch_image_to_q((const uint8_t*)img, f.q_img, c->prec, n, h, w, s))) return rc;
       if (ragged) {      // the q-image's rows below an image: all four channels, the 1.0 that says "inside the image" included
         RaggedMap m;
         m.row_bytes = (long long)conv1_q_w(w) * 8; m.img_bytes = (long long)conv1_q_h(h) * m.row_bytes;
         m.top = 2; m.left_bytes = 16; m.span_bytes = w * 8; m.rows = h; m.level = 0;
         int pad = 0;
         for (int i = 0; i < n; ++i) pad = std::max(pad, h - heights[i]);
-        if ((rc = launch_ragged_mask(c->q_img, m, hts_dev, n, pad, s))) return rc;
+        if ((rc = launch_ragged_mask(f.q_img, m, hts_dev, n, pad, s))) return rc;
       }
-      if (!fuse1 && (rc = launch_conv_first_from_q(c->q_img, conv1_p_frags(c->w_first_frags, c->prec), c->act_conv[0], c->prec, n, h, w, 0, w, s))) return rc;
+      if (!fuse1 && (rc = launch_conv_first_from_q(f.q_img, conv1_p_frags(c->w_first_frags, c->prec), f.act_conv[0], c->prec, n, h, w, 0, w, s))) return rc;
     } else if (ragged) {
       // the kernels that read raw pixels (fp32, split precision; the 16-bit modes with conv1_kernel < 2) take the float feed instead, which they
       // compute identically (ctpn_forward_blob): p - mean inside an image, 0.0f below it
       const size_t need = (size_t)n * h * w * 3 * sizeof(float);
-      if (need > c->ragged_blob_bytes) {
+      if (need > f.ragged_blob_bytes) {
         CTPN_HIP_TRY(hipStreamSynchronize(s));      // an earlier ragged forward may still read the block that goes
-        if ((rc = grow_dev((void**)&c->ragged_blob, c->ragged_blob_bytes, need))) return rc;
+        if ((rc = grow_dev((void**)&f.ragged_blob, f.ragged_blob_bytes, need))) return rc;
       }
-      if ((rc = launch_ragged_blob((const uint8_t*)img, c->ragged_blob, hts_dev, n, h, w, s))) return rc;
-      if ((rc = launch_conv_first(c->ragged_blob, 1, c->w_first, c->b_conv[0], c->act_conv[0], c->prec, n, h, w, s,
+      if ((rc = launch_ragged_blob((const uint8_t*)img, f.ragged_blob, hts_dev, n, h, w, s))) return rc;
+      if ((rc = launch_conv_first(f.ragged_blob, 1, c->w_first, c->b_conv[0], f.act_conv[0], c->prec, n, h, w, s,
                                   frags ? c->w_first_frags : nullptr))) return rc;
-    } else if ((rc = launch_conv_first(img, is_f32, c->w_first, c->b_conv[0], c->act_conv[0], c->prec, n, h, w, s,
+    } else if ((rc = launch_conv_first(img, is_f32, c->w_first, c->b_conv[0], f.act_conv[0], c->prec, n, h, w, s,
                                        frags ? c->w_first_frags : nullptr))) return rc;
-    if (ragged && (rc = ragged_mask_act(c->act_conv[0], (size_t)64 * c->es, 0, heights, hts_dev, n, h, w, s))) return rc;
+    if (ragged && (rc = ragged_mask_act(f.act_conv[0], (size_t)64 * c->es, 0, heights, hts_dev, n, h, w, s))) return rc;
   }
-  c->act_valid[0] = !fuse1;      // fused: conv1_1's map exists only inside conv1_2's LDS windows
+  f.act_valid[0] = !fuse1;      // fused: conv1_1's map exists only inside conv1_2's LDS windows
   if (jpeg_src >= 0) {           // the images came from ctpn_decode_jpeg_batch: its buffer may be rewritten once the first layer has read it
     CTPN_HIP_TRY(hipEventRecord(c->jpeg[jpeg_src].ev_consumed, s));
     c->jpeg[jpeg_src].consumed_valid = true;
@@ -177,9 +198,20 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
   }
   // the previous batch's tail (stream_p) overlaps conv1_1 only: the conv stack starts on an otherwise idle chip (its timed window too)
   // and rpn_conv's output, which lstm_pre reads, is not rewritten under it
-  if (c->tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; }
+  if (f.tail_pending) { CTPN_HIP_TRY(hipStreamWaitEvent(s, f.ev_tail, 0)); f.tail_pending = false; }
   if (c->tail_confine && c->ev_last_done) CTPN_HIP_TRY(hipStreamWaitEvent(s, c->ev_last_done, 0));      // option "tail_confine": see its declaration
-  const void* cur = c->act_conv[0];
+  // Cross-batch order of the two sets' forwards (two_forwards_mode(): 2; 3 in measurement builds): this forward's conv stack starts behind the other
+  // set's conv stack (3: behind its lstm_pre), so that only its q-image build and the head of its conv1_2 run beside the other batch's last kernels.
+  // Two whole forwards side by side measured 2.8 % SLOWER than one stream (mode 1). The strips fork as they do on one stream: the machine behind a
+  // main launch is empty again.
+  const int gate = beside ? two_forwards_mode() - 1 : 0;
+  if (gate > 0) {
+    ctpn_ctx::FwdSet& o = c->fs[&f == &c->fs[0] ? 1 : 0];
+    if (o.gate_valid) CTPN_HIP_TRY(hipStreamWaitEvent(s, o.ev_gate, 0));
+  }
+  f.gate_valid = false;
+  const bool own_strips = beside && gate == 0;
+  const void* cur = f.act_conv[0];
   int pool_i = 0;
   hipEvent_t stack_a = nullptr, stack_b = nullptr;
   double stack_flops = 0.0;
@@ -195,29 +227,30 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
     if (fuse1 && i == 1) flops += 2.0 * (double)n * h * w * 27.0 * 64.0;      // conv1_1 is part of this launch
     stack_flops += flops;
     const bool fuse = kConvs[i].pool_after != 0;
-    void* full = (!fuse || c->keep_acts) ? c->act_conv[i] : nullptr;
+    void* full = (!fuse || c->keep_acts) ? f.act_conv[i] : nullptr;
     {
-      Timed t(c, CTPN_KIND_CONV_GEMM, flops);
+      Timed t(c, CTPN_KIND_CONV_GEMM, flops, s);
       const bool f1 = fuse1 && i == 1;
-      if ((rc = launch_conv3x3(cur, c->wt_conv[i], c->b_conv[i], full, fuse ? c->act_pool[pool_i] : nullptr, c->prec, n, hl, wl,
+      if ((rc = launch_conv3x3(cur, c->wt_conv[i], c->b_conv[i], full, fuse ? f.act_pool[pool_i] : nullptr, c->prec, n, hl, wl,
                                kConvs[i].ci, kConvs[i].co, 1, s, (c->prec == DType::SPLIT && i == 13) ? 1 : 0,
-                               f1 ? c->q_img : nullptr, f1 ? conv1_p_frags(c->w_first_frags, c->prec) : nullptr, (c->conv_p64 ? 1 : 0) | (c->split_edge ? 2 : 0)))) return rc;
+                               f1 ? f.q_img : nullptr, f1 ? conv1_p_frags(c->w_first_frags, c->prec) : nullptr, (c->conv_p64 ? 1 : 0) | (c->split_edge ? 2 : 0) | (own_strips ? 4 : 0)))) return rc;
     }
-    c->act_valid[i] = full != nullptr;
+    f.act_valid[i] = full != nullptr;
     if (ragged) {      // every stored output, before the next layer reads it
       const size_t pix = (size_t)kConvs[i].co * ((c->prec == DType::SPLIT && i == 13) ? 6 : c->es);
       if (full && (rc = ragged_mask_act(full, pix, kConvs[i].level, heights, hts_dev, n, h, w, s))) return rc;
-      if (fuse && (rc = ragged_mask_act(c->act_pool[pool_i], (size_t)kConvs[i].co * c->es, kConvs[i].level + 1, heights, hts_dev, n, h, w, s))) return rc;
+      if (fuse && (rc = ragged_mask_act(f.act_pool[pool_i], (size_t)kConvs[i].co * c->es, kConvs[i].level + 1, heights, hts_dev, n, h, w, s))) return rc;
     }
-    cur = fuse ? c->act_pool[pool_i] : c->act_conv[i];
+    cur = fuse ? f.act_pool[pool_i] : f.act_conv[i];
     if (fuse) ++pool_i;
   }
   if (stack_timed) {
     CTPN_HIP_TRY(hipEventRecord(stack_b, s));
     ProfRec r{CTPN_KIND_CONV_GEMM, stack_a, stack_b, stack_flops};
-    r.launches = 13;
+    r.launches = 13; r.span = true;
     c->pending.push_back(r);
   }
+  if (two_forwards_mode() == 2 && f.ev_gate) { CTPN_HIP_TRY(hipEventRecord(f.ev_gate, s)); f.gate_valid = true; }
   const int hf = lvl(h, 4), wf = lvl(w, 4);
   const long long M5 = (long long)n * hf * wf;
   {  // lstm_pre: x_t @ kernel[:512] + bias for both directions (on `s` also when the tail overlaps: next to conv1_1 this MFMA GEMM took
@@ -225,30 +258,31 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
     IGemm g{};
     // split precision: rpn_conv/3x3 stored [hi | lo | hi] pixels, wt_x rows are [hi | hi | lo]: a plain bf16 GEMM over K = 1536
     const bool sp = c->prec == DType::SPLIT;
-    g.a = cur; g.wt = c->wt_x; g.bias = c->b_x; g.out = c->xp;
+    g.a = cur; g.wt = c->wt_x; g.bias = c->b_x; g.out = f.xp;
     g.M = M5; g.Ci = sp ? 1536 : 512; g.ntaps = 1; g.Co = 1024; g.a_plain = 0; g.H = hf; g.W = wf; g.tap_base_y = 1; g.tap_base_x = 1;
     g.out_bordered = 0; g.ldc = 1024; g.relu = 0;
-    Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 512 * 1024);
+    Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 512 * 1024, s);
     // 16-bit modes: lstm_pre is stored as fp16 (half the 272 MB round trip between this GEMM and the recurrence; see bilstm.hip) and
     // computed by the resident-weight-slice kernel (lstm_pre.hip); fp32 and split precision: the im2col GEMM
-    if (dtype_is_half(c->prec)) { if ((rc = launch_lstm_pre(cur, c->wt_xf, c->b_x, c->xp, c->prec, n, hf, wf, s))) return rc; }
+    if (dtype_is_half(c->prec)) { if ((rc = launch_lstm_pre(cur, c->wt_xf, c->b_x, f.xp, c->prec, n, hf, wf, s))) return rc; }
     else if ((rc = launch_igemm(g, sp ? DType::BF16 : c->prec, DType::F32, s))) return rc;
   }
+  if (two_forwards_mode() == 3 && f.ev_gate) { CTPN_HIP_TRY(hipEventRecord(f.ev_gate, s)); f.gate_valid = true; }
   if (tail_on_p) {
-    CTPN_HIP_TRY(hipEventRecord(c->ev_conv, s));
-    CTPN_HIP_TRY(hipStreamWaitEvent(ts, c->ev_conv, 0));
+    CTPN_HIP_TRY(hipEventRecord(f.ev_conv, s));
+    CTPN_HIP_TRY(hipStreamWaitEvent(ts, f.ev_conv, 0));
   }
   {
     Timed t(c, CTPN_KIND_BILSTM, (double)M5 * (1024.0 + 256.0) * 4.0, ts);
     // "lstm_split": the recurrent product on split-bf16 MFMAs (fp32-class; v_exp / v_rcp gate math, 1 ulp each) in every mode but the fp32 gate,
     // whose kernel (and split precision's with lstm_split = 0) is exact-fp32 MFMA with exact gates
     const bool half = dtype_is_half(c->prec);
-    if ((rc = launch_bilstm(c->xp, half ? 1 : 0, c->wh, c->lstm_out, n * hf, wf, ts, (c->lstm_split && c->prec != DType::F32) ? 1 : 0, half ? 1 : 0))) return rc;
+    if ((rc = launch_bilstm(f.xp, half ? 1 : 0, c->wh, f.lstm_out, n * hf, wf, ts, (c->lstm_split && c->prec != DType::F32) ? 1 : 0, half ? 1 : 0))) return rc;
   }
   const bool fold_heads = dtype_is_half(c->prec) && !c->keep_acts;
   if (fold_heads) {  // lstm_out (256) -> bbox (40) | cls (20) through the pre-multiplied FC x heads matrix
     IGemm g{};
-    g.a = c->lstm_out; g.wt = c->wt_fold; g.bias = c->b_fold; g.out = c->heads;
+    g.a = f.lstm_out; g.wt = c->wt_fold; g.bias = c->b_fold; g.out = f.heads;
     g.M = M5; g.Ci = 256; g.ntaps = 1; g.Co = 60; g.a_plain = 1; g.lda = 256; g.out_bordered = 0; g.ldc = 64; g.relu = 0;
     if ((rc = wait_decoded())) return rc;
     Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 256 * 60, ts);
@@ -256,22 +290,22 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
   } else {
   {  // lstm_o FC 256 -> 512 (no activation, reference network.py:110-113)
     IGemm g{};
-    g.a = c->lstm_out; g.wt = c->wt_fc; g.bias = c->b_fc; g.out = c->fc_out;
+    g.a = f.lstm_out; g.wt = c->wt_fc; g.bias = c->b_fc; g.out = f.fc_out;
     g.M = M5; g.Ci = 256; g.ntaps = 1; g.Co = 512; g.a_plain = 1; g.lda = 256; g.out_bordered = 0; g.ldc = 512; g.relu = 0;
     Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 256 * 512, ts);
     if ((rc = launch_igemm(g, DType::F32, DType::F32, ts))) return rc;
   }
   {  // rpn_bbox_pred (40) | rpn_cls_score (20) in one 512 -> 60 GEMM
     IGemm g{};
-    g.a = c->fc_out; g.wt = c->wt_h; g.bias = c->b_h; g.out = c->heads;
+    g.a = f.fc_out; g.wt = c->wt_h; g.bias = c->b_h; g.out = f.heads;
     g.M = M5; g.Ci = 512; g.ntaps = 1; g.Co = 60; g.a_plain = 1; g.lda = 512; g.out_bordered = 0; g.ldc = 64; g.relu = 0;
     if ((rc = wait_decoded())) return rc;
     Timed t(c, CTPN_KIND_GEMM, 2.0 * (double)M5 * 512 * 60, ts);
     if ((rc = launch_igemm(g, DType::F32, DType::F32, ts))) return rc;
   }
   }
-  if (tail_on_p) { CTPN_HIP_TRY(hipEventRecord(c->ev_tail, ts)); c->tail_pending = true; }
-  c->fc_valid = !fold_heads;
+  if (tail_on_p) { CTPN_HIP_TRY(hipEventRecord(f.ev_tail, ts)); f.tail_pending = true; }
+  f.fc_valid = !fold_heads;
   c->forward_done = true;
   c->proposals_done = false;
   return CTPN_OK;
@@ -282,21 +316,24 @@ int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_devi
 extern "C" {
 
 int ctpn_forward(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w) {
-  return forward_impl(c, images, 0, images_on_device, n, h, w);
+  if (!c) return fail(CTPN_ERR_ARG, "null pointer");
+  return forward_impl(c, c->fs[0], images, 0, images_on_device, n, h, w);
 }
 int ctpn_forward_blob(ctpn_ctx* c, const float* blob, int blob_on_device, int n, int h, int w) {
-  return forward_impl(c, blob, 1, blob_on_device, n, h, w);
+  if (!c) return fail(CTPN_ERR_ARG, "null pointer");
+  return forward_impl(c, c->fs[0], blob, 1, blob_on_device, n, h, w);
 }
 
 int ctpn_forward_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights) {
   if (!c || !canvas || !heights) return fail(CTPN_ERR_ARG, "ctpn_forward_ragged: null pointer");
-  return forward_impl(c, canvas, 0, canvas_on_device, n, hc, w, false, heights, 2);
+  return forward_impl(c, c->fs[0], canvas, 0, canvas_on_device, n, hc, w, false, heights, 2);
 }
 
 int ctpn_feat_shape(ctpn_ctx* c, int* n, int* hf, int* wf) {
   if (!c) return fail(CTPN_ERR_ARG, "null ctx");
   if (!c->forward_done) return fail(CTPN_ERR_STATE, "no forward yet");
-  if (n) *n = c->n; if (hf) *hf = lvl(c->h, 4); if (wf) *wf = lvl(c->w, 4);
+  const ctpn_ctx::FwdSet& f = *c->last;
+  if (n) *n = f.n; if (hf) *hf = lvl(f.h, 4); if (wf) *wf = lvl(f.w, 4);
   return CTPN_OK;
 }
 
@@ -304,20 +341,21 @@ int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capac
   if (!c || !name || !out_host) return fail(CTPN_ERR_ARG, "null pointer");
   if (!c->forward_done) return fail(CTPN_ERR_STATE, "ctpn_get_tensor: no forward yet");
   CTPN_HIP_TRY(hipSetDevice(c->device));
+  const ctpn_ctx::FwdSet& f = *c->last;      // the most recent forward's set, whichever slot submitted it
   const std::string nm(name);
-  const int n = c->n, hf = lvl(c->h, 4), wf = lvl(c->w, 4);
+  const int n = f.n, hf = lvl(f.h, 4), wf = lvl(f.w, 4);
   const void* src = nullptr; int H = 0, W = 0, C = 0, ld = 0; bool bordered = false; DType t = DType::F32;
-  for (int i = 0; i < 14; ++i) if (nm == kConvs[i].name && !c->act_valid[i])
+  for (int i = 0; i < 14; ++i) if (nm == kConvs[i].name && !f.act_valid[i])
     return fail(CTPN_ERR_STATE, "ctpn_get_tensor: " + nm + (i == 0 ? " is computed inside conv1_2's window stage" : " is fused with its max-pool") + " and not stored; set the ctx option keep_acts = 1 (ctpn_set_option)");
-  for (int i = 0; i < 14; ++i) if (nm == kConvs[i].name) { src = c->act_conv[i]; H = lvl(c->h, kConvs[i].level); W = lvl(c->w, kConvs[i].level); C = kConvs[i].co; ld = C; bordered = true; t = c->prec; }
+  for (int i = 0; i < 14; ++i) if (nm == kConvs[i].name) { src = f.act_conv[i]; H = lvl(f.h, kConvs[i].level); W = lvl(f.w, kConvs[i].level); C = kConvs[i].co; ld = C; bordered = true; t = c->prec; }
   const int pool_src[4] = {1, 3, 6, 9};
-  for (int p = 0; p < 4; ++p) if (nm == kPoolNames[p]) { src = c->act_pool[p]; H = lvl(c->h, p + 1); W = lvl(c->w, p + 1); C = kConvs[pool_src[p]].co; ld = C; bordered = true; t = c->prec; }
-  if (nm == "lstm_pre") { src = c->xp; H = hf; W = wf; C = 1024; ld = 1024; if (dtype_is_half(c->prec)) t = DType::F16; }
-  if (nm == "lstm_out") { src = c->lstm_out; H = hf; W = wf; C = 256; ld = 256; }
-  if (nm == "lstm_o" && !c->fc_valid)
+  for (int p = 0; p < 4; ++p) if (nm == kPoolNames[p]) { src = f.act_pool[p]; H = lvl(f.h, p + 1); W = lvl(f.w, p + 1); C = kConvs[pool_src[p]].co; ld = C; bordered = true; t = c->prec; }
+  if (nm == "lstm_pre") { src = f.xp; H = hf; W = wf; C = 1024; ld = 1024; if (dtype_is_half(c->prec)) t = DType::F16; }
+  if (nm == "lstm_out") { src = f.lstm_out; H = hf; W = wf; C = 256; ld = 256; }
+  if (nm == "lstm_o" && !f.fc_valid)
     return fail(CTPN_ERR_STATE, "ctpn_get_tensor: lstm_o is folded into the heads GEMM in the 16-bit modes; set the ctx option keep_acts = 1 (ctpn_set_option)");
-  if (nm == "lstm_o") { src = c->fc_out; H = hf; W = wf; C = 512; ld = 512; }
-  if (nm == "heads") { src = c->heads; H = hf; W = wf; C = 60; ld = 64; }
+  if (nm == "lstm_o") { src = f.fc_out; H = hf; W = wf; C = 512; ld = 512; }
+  if (nm == "heads") { src = f.heads; H = hf; W = wf; C = 60; ld = 64; }
   if (nm == "rpn_cls_prob_reshape") { src = c->cls_prob; H = hf; W = wf; C = 20; ld = 20; }
   if (nm == "rpn_bbox_pred") { src = c->bbox_pred; H = hf; W = wf; C = 40; ld = 40; }
   if (!src) return fail(CTPN_ERR_ARG, "ctpn_get_tensor: unknown tensor name " + nm);
@@ -326,11 +364,11 @@ int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capac
   const size_t need = (size_t)n * H * W * C;
   if (shape4) { shape4[0] = n; shape4[1] = H; shape4[2] = W; shape4[3] = C; }
   if (capacity < need) return fail(CTPN_ERR_CAPACITY, "ctpn_get_tensor: output buffer too small");
-  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(f.stream));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
   // split precision: a pixel is [hi(C) | lo(C)] bf16 (rpn_conv/3x3: [hi | lo | hi]); the value is hi + lo
   const bool split = t == DType::SPLIT;
-  if (split) ld = (src == c->act_conv[13] ? 3 : 2) * C;
+  if (split) ld = (src == f.act_conv[13] ? 3 : 2) * C;
   const int es = split ? 2 : dtype_bytes(t);
   const int Hs = bordered ? H + 2 : H, Ws = bordered ? W + 2 : W;
   const size_t bytes = (size_t)n * Hs * Ws * ld * es;
@@ -342,7 +380,7 @@ int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capac
       for (int x = 0; x < W; ++x) {
         const size_t sp = (((size_t)in * Hs + y + o) * Ws + x + o) * ld;
         float* d = out_host + (((size_t)in * H + y) * W + x) * C;
-        if (src == c->xp) {                      // device layout: permuted gate columns -> TF's i | j | f | o order (fp16 in the 16-bit modes)
+        if (src == f.xp) {                      // device layout: permuted gate columns -> TF's i | j | f | o order (fp16 in the 16-bit modes)
           if (es == 2) {
             const uint16_t* sh = (const uint16_t*)tmp.data() + sp;
             for (int ch = 0; ch < 1024; ++ch) d[ch] = host_f16_to_f32(sh[(ch & ~511) + lstm_gate_col(ch & 511)]);

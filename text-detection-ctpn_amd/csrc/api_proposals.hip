@@ -79,7 +79,7 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
     const int hv = c->debug_hog;
     const int usec = hv > 100000 ? hv - 100000 : hv > 50000 ? hv - 50000 : hv, touch = hv > 100000 ? 4 : hv > 50000 ? 2 : 0;
     const void* src = nullptr; size_t src_bytes = 0;
-    for (int i = 0; i < 14; ++i) if (c->act_conv[i] && c->act_conv_bytes[i] > src_bytes) { src = c->act_conv[i]; src_bytes = c->act_conv_bytes[i]; }
+    for (int i = 0; i < 14; ++i) if (c->fs[0].act_conv[i] && c->act_conv_bytes[i] > src_bytes) { src = c->fs[0].act_conv[i]; src_bytes = c->act_conv_bytes[i]; }
     if ((rc = launch_hog((unsigned*)(c->nms_colid), touch == 4 ? 2 * n : n, usec, touch, s, src, src_bytes))) return rc;       // (sink: never written; any device pointer)
   }
   {
@@ -149,8 +149,10 @@ int ctpn_proposals(ctpn_ctx* c, const float* im_info, int pre_nms_topn, int post
   if (!c->forward_done) return fail(CTPN_ERR_STATE, "ctpn_proposals: no forward yet");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   // after a ragged forward: that forward's feature rows per image (its set's second half), which a uniform forward forgets
-  const int* valid = c->fwd_ragged >= 0 ? c->ragged[c->fwd_ragged].dev + c->n : nullptr;
-  return run_proposals(c, c->heads, 0, c->n, lvl(c->h, 4), lvl(c->w, 4), im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size,
+  const ctpn_ctx::FwdSet& f = *c->last;      // the most recent forward's set; the proposal layer runs on `stream`, behind that forward
+  if (f.stream != c->stream) CTPN_HIP_TRY(hipStreamSynchronize(f.stream));
+  const int* valid = f.fwd_ragged >= 0 ? c->ragged[f.fwd_ragged].dev + f.n : nullptr;
+  return run_proposals(c, f.heads, 0, f.n, lvl(f.h, 4), lvl(f.w, 4), im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size,
                        rois_out, counts_out, valid);
 }
 

@@ -107,26 +107,23 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
   }
   // The strip (a few dozen workgroups) runs on its own stream, forked after the previous layer and joined before the next,
   // so it shares the machine with the main launch instead of adding 35-50 us of a nearly empty GPU per layer.
+  // split_opts bit 2 (two forwards overlapping freely on two streams: a measurement mode, api_ctx.hip two_forwards_mode): the machine behind
+  // the main launch is not empty then and every fork / join pair is 7 to 13 us of this stream standing still, so the strip follows the main
+  // launch in the layer's own stream -- the same kernel in the same form (plan.deep) on the same columns: only the stream differs, the stored
+  // bytes cannot.
   static hipStream_t sstream[16] = {nullptr};
   static hipEvent_t ev_fork[16] = {nullptr}, ev_join[16] = {nullptr};
   static std::mutex strip_mu[16];     // the helper stream and its two events are per device, shared by every ctx on it
   std::unique_lock<std::mutex> strip_lock;
-  const bool instream = strip && plan.deep != 0;      // the edge kernels' deep form, behind the main launch: no fork, no join
+  const bool deep = strip && plan.deep != 0;      // the edge kernels' deep form, behind the main launch: no fork, no join
+  const bool instream = deep || (strip && (split_opts & 4) != 0);
   auto run_edge = [&](void* dst, bool pooled) -> int {
     hipStream_t es = instream ? s : sstream[dev];
     if (split) return c3_edge_split(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, true, dup_hi, plan.edge_ks);      // always the deep form
-    return t == DType::F16 ? c3_edge_f16(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, instream)
-                           : c3_edge_bf16(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, instream);
+    return t == DType::F16 ? c3_edge_f16(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, deep)
+                           : c3_edge_bf16(in, wt, bias, dst, n, h, w, ci, co, relu, r, pooled, es, deep);
   };
-  if (strip && !instream) {
-    strip_lock = std::unique_lock<std::mutex>(strip_mu[dev]);   // held until the join is enqueued (event waits capture the record made before them)
-    if (!sstream[dev]) {
-      CTPN_HIP_TRY(hipStreamCreateWithFlags(&sstream[dev], hipStreamNonBlocking));
-      CTPN_HIP_TRY(hipEventCreateWithFlags(&ev_fork[dev], hipEventDisableTiming));
-      CTPN_HIP_TRY(hipEventCreateWithFlags(&ev_join[dev], hipEventDisableTiming));
-    }
-    CTPN_HIP_TRY(hipEventRecord(ev_fork[dev], s));
-    CTPN_HIP_TRY(hipStreamWaitEvent(sstream[dev], ev_fork[dev], 0));
+  auto run_strip = [&](hipStream_t es) -> int {
     if (edge_pool) {
       if ((rc = run_edge(pool_out, true))) return rc;
       if (out && (rc = run_edge(out, false))) return rc;
@@ -137,8 +134,20 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
       ig.a = in; ig.wt = wt; ig.bias = bias; ig.out = out;
       ig.M = (long long)n * h * r; ig.Ci = ci; ig.ntaps = 9; ig.Co = co;
       ig.a_plain = 0; ig.H = h; ig.W = w; ig.rx0 = w - r; ig.rw = r; ig.out_bordered = 1; ig.ldc = co; ig.relu = relu;
-      if ((rc = launch_igemm(ig, t, t, sstream[dev]))) return rc;
+      if ((rc = launch_igemm(ig, t, t, es))) return rc;
     }
+    return CTPN_OK;
+  };
+  if (strip && !instream) {
+    strip_lock = std::unique_lock<std::mutex>(strip_mu[dev]);   // held until the join is enqueued (event waits capture the record made before them)
+    if (!sstream[dev]) {
+      CTPN_HIP_TRY(hipStreamCreateWithFlags(&sstream[dev], hipStreamNonBlocking));
+      CTPN_HIP_TRY(hipEventCreateWithFlags(&ev_fork[dev], hipEventDisableTiming));
+      CTPN_HIP_TRY(hipEventCreateWithFlags(&ev_join[dev], hipEventDisableTiming));
+    }
+    CTPN_HIP_TRY(hipEventRecord(ev_fork[dev], s));
+    CTPN_HIP_TRY(hipStreamWaitEvent(sstream[dev], ev_fork[dev], 0));
+    if ((rc = run_strip(sstream[dev]))) return rc;
     CTPN_HIP_TRY(hipEventRecord(ev_join[dev], sstream[dev]));
   }
   switch (t) {
@@ -148,12 +157,8 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
     default: rc = c3_run_split(g, pool, plan.main_form, s); break;
   }
   if (rc) return rc;
-  if (instream) {
-    if (edge_pool) {
-      if ((rc = run_edge(pool_out, true))) return rc;
-      if (out && (rc = run_edge(out, false))) return rc;
-    } else if ((rc = run_edge(out, false))) return rc;
-  } else if (strip) CTPN_HIP_TRY(hipStreamWaitEvent(s, ev_join[dev], 0));
+  if (instream) { if ((rc = run_strip(s))) return rc; }
+  else if (strip) CTPN_HIP_TRY(hipStreamWaitEvent(s, ev_join[dev], 0));
   return CTPN_OK;
 }
 

@@ -32,7 +32,7 @@ static const ConvSpec kConvs[14] = {
     {"conv5_3", 512, 512, 4, 0}, {"rpn_conv/3x3", 512, 512, 4, 0}};
 static const char* kPoolNames[4] = {"pool1", "pool2", "pool3", "pool4"};
 
-struct ProfRec { int kind; hipEvent_t a, b; double work; int launches = 1; };
+struct ProfRec { int kind; hipEvent_t a, b; double work; int launches = 1; bool span = false; };      // span: see prof_drain (api_ctx.hip)
 
 // ---------------------------------------------------------------------------------------------
 // Host worker pool of one ctx: created once, sized by ctpn_host_thread_budget (cores of the node / ranks on the node).
@@ -122,7 +122,7 @@ struct ctpn_ctx {
   int max_batch = 0, max_h = 0, max_w = 0;
   DType prec = DType::BF16;
   int es = 2;                       // bytes per activation element (split precision: a (hi, lo) bf16 pair = 4)
-  hipStream_t stream = nullptr;     // network forward
+  hipStream_t stream = nullptr;     // network forward (forward set 0's stream, see FwdSet), weights, the synchronous entry points
   hipStream_t stream_p = nullptr;   // proposal layer + connector front end of the asynchronous detect path
   std::vector<void*> allocs;
   // asynchronous detect: two slots of pinned host buffers + events
@@ -135,9 +135,9 @@ struct ctpn_ctx {
     double* crecs = nullptr; int* ccnt = nullptr;      // device connector results: [n][2 modes][CONN_CAP][9], [n][3]
     hipEvent_t ev_heads = nullptr, ev_decoded = nullptr, ev_done = nullptr;
     int n = 0, h = 0, w = 0; bool busy = false;
+    int set = 0;               // the forward set the batch in flight runs on
     std::vector<int> hts;      // pixel height of every image of the batch (a ragged submit: the caller's heights; else h): what the host connector clips to
   } slot[2];
-  hipEvent_t ev_last_decoded = nullptr;  // decode of the most recent submit (it reads `heads`, which the next forward rewrites)
   hipEvent_t ev_last_done = nullptr;     // the whole proposal tail (stream_p) of the most recent submit
   // "tail_confine" (default 0; was 1 in split precision during round 6): forward k + 1 waits, BEHIND its conv1_1, for the proposal tail of batch k,
   // which then overlaps conv1_1 only. History: the reversed-batch test of round 6 found that a batch in flight could change another batch's bits --
@@ -152,9 +152,6 @@ struct ctpn_ctx {
   // instead of 0.46, and the proposal kernels, which start 0.8 ms later, now run under conv2_x (static persistent tiles) instead of
   // conv1_2 (dynamic tile claims): the conv stack loses 0.9 points of its roofline. Off by default.
   int tail_overlap = 0;
-  hipEvent_t ev_conv = nullptr;          // conv stack + lstm_pre of the batch in flight are done (stream -> stream_p)
-  hipEvent_t ev_tail = nullptr;          // the tail of the most recent submit is done (stream_p -> stream: before conv1_2 rewrites what it read)
-  bool tail_pending = false;
 
   // weights
   bool weights_loaded = false;
@@ -244,8 +241,7 @@ struct ctpn_ctx {
                                      // form: 3.56 ms instead of the non-persistent kernel's 4.53 at batch 32 (0 = that kernel, for A/B runs). It made a latent
                                      // race of the conv kernels frequent enough to find (see tail_confine)
   int conv1_fuse = 1;                // "conv1_fuse": with conv1_kernel = 2 and keep_acts = 0, compute conv1_1 inside conv1_2 (conv3x3_wr_kernel FUSE); 0 = stand-alone from the q-image (same bytes)
-  void* q_img = nullptr;             // the batch's q-image (common.h), 16-bit modes only
-  size_t q_img_bytes = 0;
+  size_t q_img_bytes = 0;            // the batch's q-image (common.h; FwdSet::q_img), 16-bit modes only
   int lstm_split = 0;                // "lstm_split": the recurrent product on split-bf16 MFMAs (fp32-class, |d| < 3e-5, 0.32 -> 0.16 ms). Default 1 in
                                      // the 16-bit modes and, since round 6, in split precision (set in create_impl), 0 in fp32 (exact-fp32 MFMA kernel)
   int nms_check = 0;                 // "nms_check": debug -- re-run the generic NMS kernel behind the column-decomposed one and fail on a mismatch
@@ -263,10 +259,41 @@ struct ctpn_ctx {
   float* wt_fold = nullptr;          // [64][256]: (lstm_o FC) x (heads) folded, bf16 throughput mode only
   float* b_fold = nullptr;           // [64]
 
-  // activations
-  void* act_conv[14] = {nullptr};
-  void* act_pool[4] = {nullptr};
-  bool act_valid[14] = {true, true, true, true, true, true, true, true, true, true, true, true, true, true};
+  // A forward set: a forward's stream and everything a forward writes. Set 0 is allocated by ctpn_create and runs on `stream`; every
+  // synchronous entry point uses it. Set 1 exists so that TWO submitted batches' forwards can be in flight at once: a forward is a chain of
+  // 20 dependent launches, and one ordered stream leaves the CUs idle at every cross-stream wait, in every partial last round of a persistent
+  // walk and beside the 148-workgroup recurrence; a second, independent chain on another hardware queue has workgroups ready for exactly those
+  // CUs. It is allocated by the first submit that finds the other slot in flight (api_detect.hip: pick_set), holds only what the production
+  // path stores (no full-resolution map of a pooled layer; conv1_1's map only once a forward needs it), and a ctx that cannot have it
+  // (keep_acts, out of memory, per-stage profiling) keeps both slots on set 0: the single-stream order.
+  // Weights, the image staging buffers and the proposal tail (stream_p, one set of buffers) are shared.
+  struct FwdSet {
+    hipStream_t stream = nullptr;
+    void* q_img = nullptr;             // the batch's q-image (common.h), 16-bit modes only
+    void* act_conv[14] = {nullptr};
+    void* act_pool[4] = {nullptr};
+    bool act_valid[14] = {true, true, true, true, true, true, true, true, true, true, true, true, true, true};
+    float* xp = nullptr;        // [M5][1024]
+    float* lstm_out = nullptr;  // [M5][256]
+    float* fc_out = nullptr;    // [M5][512]
+    float* heads = nullptr;     // [M5][64]
+    bool fc_valid = true;
+    float* ragged_blob = nullptr; size_t ragged_blob_bytes = 0;       // fp32 / split precision: a ragged canvas as a float feed, 0.0f below the images
+    int fwd_ragged = -1;               // the set's last forward was ragged: index of its RaggedSet (ctpn_proposals hands its feature rows to decode_kernel), else -1
+    int n = 0, h = 0, w = 0;           // the set's last forward
+    int gn = -1, gh = -1, gw = -1;     // geometry the set's borders are currently zeroed for
+    // option tail_overlap: conv stack + lstm_pre of the set's batch in flight are done (stream -> stream_p); the tail of the set's most recent
+    // forward is done (stream_p -> stream: before the set's next conv1_2 rewrites what it read)
+    hipEvent_t ev_conv = nullptr, ev_tail = nullptr;
+    bool tail_pending = false;
+    // the decode kernel (stream_p) that last read `heads`, which the set's next forward rewrites, and the slot whose submit recorded it
+    hipEvent_t ev_decoded = nullptr; int dec_slot = -1;
+    hipEvent_t ev_gate = nullptr; bool gate_valid = false;      // two_forwards_mode() 2 / 3: the point of this set's forward the other set's conv stack waits for
+    std::vector<void*> allocs;         // set 1: what ctpn_destroy frees (set 0's blocks are in the ctx's allocs)
+  } fs[2];
+  size_t set1_bytes = 0;             // device bytes of set 1
+  int set1_state = 0;                // 0: not asked for yet, 1: allocated, -1: could not be allocated (both slots stay on set 0)
+  FwdSet* last = &fs[0];             // the set of the most recent forward: what ctpn_get_tensor, ctpn_proposals, ctpn_feat_shape read
   size_t act_conv_bytes[14] = {0};
   size_t act_pool_bytes[4] = {0};
   uint8_t* img_dev = nullptr;        // staging of host images, buffer 0
@@ -279,10 +306,6 @@ struct ctpn_ctx {
   hipEvent_t ev_h2d_done[2] = {nullptr, nullptr};
   bool h2d_valid[2] = {false, false};
   int img_flip = 0;
-  float* xp = nullptr;      // [M5][1024]
-  float* lstm_out = nullptr;  // [M5][256]
-  float* fc_out = nullptr;  // [M5][512]
-  float* heads = nullptr;   // [M5][64]
   float* cls_prob = nullptr;  // [M5][20]
   float* bbox_pred = nullptr; // [M5][40]
   size_t m5_max = 0;
@@ -326,7 +349,6 @@ struct ctpn_ctx {
   bool postproc_only = false;        // ctpn_create_postproc: proposal / connector buffers only, no network
   std::unique_ptr<ctpn::HostPool> pool;
   int host_threads = 1;
-  bool fc_valid = true;
   int keep_acts = 0;      // "keep_acts": 1 = also store the full-resolution output of pool-fused convs, keep lstm_o (layer-wise parity)
   float* cls_in = nullptr;  // staging for proposals_from_host
   float* bbox_in = nullptr;
@@ -338,18 +360,14 @@ struct ctpn_ctx {
     int* host = nullptr; int* dev = nullptr;
     hipEvent_t ev_copied = nullptr; bool copied_valid = false;      // the copy that last read `host`
   } ragged[3];
-  float* ragged_blob = nullptr; size_t ragged_blob_bytes = 0;       // fp32 / split precision: the canvas as a float feed, 0.0f below the images
-  int fwd_ragged = -1;               // the last forward was ragged: index of its set (ctpn_proposals hands its feature rows to decode_kernel), else -1
 
-  // last forward geometry
-  int n = 0, h = 0, w = 0;
-  int gn = -1, gh = -1, gw = -1;  // geometry the borders are currently zeroed for
   bool forward_done = false;
 
   // profiling
   bool prof = false;
-  int prof_mode = 1;                 // 1: a pair of events around every stage; 2: ONE pair around the 13 conv3x3 launches of a forward only
-                                     // (an event pair per launch costs ~0.2 ms of bubbles per step, which a throughput run should not pay)
+  int prof_mode = 1;                 // 1: a pair of events around every stage (both slots then stay on forward set 0); 2: ONE pair around the 13 conv3x3
+                                     // launches of a forward only (an event pair per launch costs ~0.2 ms of bubbles per step, which a throughput run
+                                     // should not pay); conv_gemm's time is then the length of the UNION of the forwards' intervals (prof_drain)
   std::vector<ProfRec> pending;
   std::vector<hipEvent_t> free_events;
   double prof_ms[CTPN_KIND_COUNT] = {0};
@@ -429,8 +447,21 @@ struct Timed {
 // the network forward (api_forward.hip); tail_on_p: the recurrent tail runs on stream_p (option tail_overlap)
 // heights (nullable): a ragged batch -- h is the canvas height, image i is rows [0, heights[i]) of its slot; rset: which of the ctx's RaggedSets
 // carries them to the device. Heights that all equal h take the uniform path.
-int forward_impl(ctpn_ctx* c, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p = false,
-                 const int* heights = nullptr, int rset = 2);
+// f: the forward set it runs on and writes (the only one it touches). beside: another set's forward is in flight (its conv stack is then
+// gated behind that one's, see two_forwards_mode)
+int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f32, int images_on_device, int n, int h, int w, bool tail_on_p = false,
+                 const int* heights = nullptr, int rset = 2, bool beside = false);
+// whether that forward computes conv1_1 inside conv1_2's window stage, i.e. never stores conv1_1's map (heights: nullable, as above)
+bool forward_fuses_conv1(const ctpn_ctx* c, int is_f32, int n, int h, int w, const int* heights);
+int two_forwards_mode();      // api_ctx.hip: 2 in the product library
+// forward set 1 (api_ctx.hip), allocated on first call; need_conv1: with room for conv1_1's map. false: the caller stays on set 0
+bool ensure_set1(ctpn_ctx* c, bool need_conv1);
+// both forward streams drained (set 1's exists once the set does)
+static inline hipError_t sync_forwards(ctpn_ctx* c) {
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess || !c->fs[1].stream) return e;
+  return hipStreamSynchronize(c->fs[1].stream);
+}
 // the proposal layer in stream order on s (api_proposals.hip; null: the forward's stream); ev_decoded is recorded behind the decode kernel
 int enqueue_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
                       int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s = nullptr,

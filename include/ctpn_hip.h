@@ -787,6 +787,42 @@ int    ctpn_write_annotated_png_files(ctpn_ctx* ctx, const uint8_t* images, int 
                                       int line_capacity, const int* line_counts, double scale, const char* const* paths);
 int    ctpn_png_encode_device_stats(ctpn_ctx* ctx, long long* out4);
 
+/* ---- PNG files of MIXED sizes: a table of images over one source, ragged canvases and line crops. Additive to ABI 10. The writer above,
+ * given what the JPEG side has (ctpn_encode_jpeg_mixed, "Ragged batches out", ctpn_write_line_crops): image i is heights[i] x widths[i], its
+ * first pixel at source + offsets[i], its rows pitches[i] >= 3 widths[i] bytes apart. One set of kernels: the uniform calls above are
+ * tables of equal sizes at pitch 3 w. Every buffer of a call is laid out by prefix sums over its images (the call costs their sum, not n
+ * times the largest), and the histogram, length and write kernels run over a one-dimensional grid of work items, one workgroup = 256
+ * pieces of ONE image. The source is read BYTE-WISE: no byte outside an image's h x w x 3 pixels is touched, at any pitch or alignment
+ * (a weaker demand than the JPEG writer's aligned-dword read). File i is, byte for byte, ctpn_png_encode's file of image i.
+ *   ctpn_encode_png_mixed                  the contract of ctpn_encode_jpeg_mixed without `quality`: a host source is copied in the copy
+ *                                          queue and every image must lie inside source_bytes; a device source waits for a live decoder
+ *                                          batch. out[i] == NULL with capacity 0 sizes the file (CTPN_ERR_CAPACITY with bytes_out[i] set);
+ *                                          ctpn_png_encode_capacity(heights[i], widths[i]) always fits
+ *   ctpn_write_annotated_png_files_ragged  ctpn_write_annotated_files_ragged without `quality`, through the same pixel stage (canvas copy,
+ *                                          outlines per slot, every image resized by its own 1 / scales[i]). Image i's file is what
+ *                                          ctpn_write_annotated_png_files writes for that image alone (n = 1, rows [0, heights[i]), its
+ *                                          lines, its scale). Takes a host canvas too (canvas_on_device = 0: PNG files are decoded on the host)
+ *   ctpn_write_line_crops_png              ctpn_write_line_crops / ctpn_write_line_crops_ragged without `quality`: cut by the same kernel
+ *   ctpn_write_line_crops_png_ragged       into the ctx's buffer, crop k coded where it lies as a crop_h x widths[k] image at pitch
+ *                                          3 max_w -- the pad columns never enter a file --, lossless: file k decodes to ctpn_crop_lines'
+ *                                          crop k. Sizing form (paths == NULL), "no lines is CTPN_OK", *total_out always written and the
+ *                                          geometry limits as there
+ * CTPN_ERR_ARG, naming the image and before any device work: n <= 0 or a null pointer, a size outside 1 .. 65535, a pitch below 3 w, an
+ * image outside a host source, h (1 + 3 w) > 2^27, more than 2^31 - 1 work items or 2^32 pieces in one call. CTPN_ERR_STATE on a
+ * post-processing-only ctx. ctpn_png_encode_device_stats keeps its meaning. */
+int    ctpn_encode_png_mixed(ctpn_ctx* ctx, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights,
+                             const int* widths, const size_t* pitches, const size_t* offsets, uint8_t* const* out, const size_t* capacities,
+                             size_t* bytes_out);
+int    ctpn_write_annotated_png_files_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                                             const double* recs, int line_capacity, const int* line_counts, const double* scales,
+                                             const char* const* paths);
+int    ctpn_write_line_crops_png(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs,
+                                 int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, const char* const* paths,
+                                 int* widths_out, int* total_out);
+int    ctpn_write_line_crops_png_ragged(ctpn_ctx* ctx, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights,
+                                        const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value,
+                                        const char* const* paths, int* widths_out, int* total_out);
+
 #ifdef __cplusplus
 }
 #endif

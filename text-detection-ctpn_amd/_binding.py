@@ -176,6 +176,13 @@ def _declare(lib):
         "ctpn_encode_png_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
         "ctpn_write_annotated_png_files": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_double, C.POINTER(C.c_char_p)]),
         "ctpn_png_encode_device_stats": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
+        "ctpn_encode_png_mixed": (C.c_int, [vp, vp, C.c_int, C.c_size_t, C.c_int, i32p, i32p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(vp),
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+        "ctpn_write_annotated_png_files_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, f64p, C.POINTER(C.c_char_p)]),
+        "ctpn_write_line_crops_png": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_char_p),
+                                                i32p, i32p]),
+        "ctpn_write_line_crops_png_ragged": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, i32p, f64p, C.c_int, i32p, C.c_int, C.c_int, C.c_int,
+                                                       C.POINTER(C.c_char_p), i32p, i32p]),
         "ctpn_png_probe_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, i32p, C.c_int]),
         "ctpn_decode_png_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
         "ctpn_profile_enable": (C.c_int, [vp, C.c_int]),
@@ -1188,17 +1195,28 @@ class Context:
         file of its own size. File i is byte-equal to write_annotated_files of that image alone. The canvas is not modified.
         entropy="device": ctpn_write_annotated_files_ragged_device."""
         fn = self._lib.ctpn_write_annotated_files_ragged_device if self._entropy_form(entropy) else self._lib.ctpn_write_annotated_files_ragged
+        self._write_annotated_ragged(fn, "write_annotated_files_ragged", images, device_ptr, shape, heights, recs, scales, paths, (int(quality),))
+
+    def _write_annotated_ragged(self, fn, who, images, device_ptr, shape, heights, recs, scales, paths, tail):
+        """the ragged annotated writers' common call; tail: what the format's entry point takes behind the paths"""
         if heights is None or scales is None:
-            raise ValueError("write_annotated_files_ragged wants heights and scales")
+            raise ValueError(who + " wants heights and scales")
         ptr, on_dev, n, hc, w, hts, keep = self._canvas(images, heights, device_ptr, shape)
         sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
         paths = list(paths)
         if sc.shape[0] != n or len(paths) != n:
-            raise ValueError("write_annotated_files_ragged wants one scale and one path per image")
+            raise ValueError(who + " wants one scale and one path per image")
         packed, counts = _pack_lines(recs, None, n)
         keep_paths, arr = _path_array(paths)
         _check(fn(self._h, ptr, on_dev, n, hc, w, _ptr(hts, C.c_int), _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), _ptr(sc, C.c_double),
-                  arr, int(quality)))
+                  arr, *tail))
+
+    def write_annotated_png_files_ragged(self, images=None, device_ptr=None, shape=None, heights=None, recs=(), scales=None, paths=()):
+        """write_annotated_png_files for a RAGGED batch (ctpn_write_annotated_png_files_ragged): the arguments of write_annotated_files_ragged
+        without quality. images = the canvas (n, hc, w, 3) on the host (PNG files are decoded there), or device_ptr + shape. File i is
+        byte-equal to write_annotated_png_files of image i alone (rows [0, heights[i]), its lines, its scale). The canvas is not modified."""
+        self._write_annotated_ragged(self._lib.ctpn_write_annotated_png_files_ragged, "write_annotated_png_files_ragged", images, device_ptr, shape, heights, recs,
+                                     scales, paths, ())
 
     def png_encode_device_stats(self):
         """Of the last PNG call of this ctx (ctpn_png_encode_device_stats): dict(device=files coded on the device, host=files handed to the
@@ -1300,14 +1318,22 @@ class Context:
         return crops, widths[: total.value].copy()
 
     def write_line_crops(self, images=None, recs=(), line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None, paths=None,
-                         quality=95, entropy="host", heights=None):
+                         quality=95, entropy="host", heights=None, format="jpg"):
         """crop_lines with the crops written as JPEG files where they are cut (ctpn_write_line_crops): crop k, crop_h x widths[k], goes to
         paths[k] at `quality` -- image 0's lines first, then image 1's, ... --, byte-equal to Pillow's save(quality=quality, subsampling=2) of
         crop_lines' crops[k, :, :widths[k]]. No crop visits the host. paths=None sizes the call. -> widths (int32, one per line).
         entropy="device": ctpn_write_line_crops_device, the same files with the Huffman coding on the device.
-        heights: the batch is a ragged canvas, as in crop_lines (ctpn_write_line_crops_ragged / ctpn_write_line_crops_ragged_device)."""
+        heights: the batch is a ragged canvas, as in crop_lines (ctpn_write_line_crops_ragged / ctpn_write_line_crops_ragged_device).
+        format="png": lossless PNG files (ctpn_write_line_crops_png / ctpn_write_line_crops_png_ragged), file k byte-equal to png_encode of
+        crops[k, :, :widths[k]]; no quality, and no entropy="device" (ValueError)."""
+        if format not in ("jpg", "png"):
+            raise ValueError("format must be 'jpg' or 'png'")
         dev = self._entropy_form(entropy)
-        if heights is None:
+        if format == "png":
+            if dev:
+                raise ValueError("format='png' has no entropy='device' form")
+            fn = self._lib.ctpn_write_line_crops_png if heights is None else self._lib.ctpn_write_line_crops_png_ragged
+        elif heights is None:
             fn = self._lib.ctpn_write_line_crops_device if dev else self._lib.ctpn_write_line_crops
         else:
             fn = self._lib.ctpn_write_line_crops_ragged_device if dev else self._lib.ctpn_write_line_crops_ragged
@@ -1333,8 +1359,47 @@ class Context:
             keep, arr = _path_array(paths)
         hts, hts_arg = self._ragged_heights(heights, n)
         _check(fn(self._h, src, on_dev, n, h, w, *hts_arg, _ptr(packed, C.c_double), int(packed.shape[1]), _ptr(counts, C.c_int), int(crop_h), int(max_w),
-                  int(pad_value), int(quality), arr, _ptr(widths, C.c_int), C.byref(total)))
+                  int(pad_value), *(() if format == "png" else (int(quality),)), arr, _ptr(widths, C.c_int), C.byref(total)))
         return widths[: total.value].copy()
+
+    def encode_png_mixed(self, images=None, device_ptr=None, heights=None, widths=None, pitches=None, offsets=None):
+        """PNG files of n BGR uint8 images of ANY mix of sizes in one call (ctpn_encode_png_mixed). images: a list of (h_i, w_i, 3) arrays
+        (packed into one source buffer, image after image at pitch 3 w), or device_ptr with the tables heights / widths / pitches (bytes,
+        >= 3 w) / offsets (bytes into the buffer). -> list of n bytes objects, each byte-equal to png_encode of that image; lossless."""
+        if device_ptr is None:
+            images = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+            if any(im.ndim != 3 or im.shape[2] != 3 for im in images):
+                raise ValueError("encode_png_mixed wants a list of (h,w,3) uint8 images")
+            heights = [im.shape[0] for im in images]
+            widths = [im.shape[1] for im in images]
+            pitches = [3 * w for w in widths]
+            offsets = [int(v) for v in np.cumsum([0] + [im.size for im in images])[:-1]]
+            source = np.concatenate([im.reshape(-1) for im in images]) if images else np.zeros((1,), np.uint8)
+            src, on_dev, nbytes = source.ctypes.data_as(C.c_void_p), 0, source.size
+        else:
+            src, on_dev, nbytes = C.c_void_p(int(device_ptr)), 1, 0
+        ht = np.ascontiguousarray(heights, dtype=np.int32).reshape(-1)
+        wd = np.ascontiguousarray(widths, dtype=np.int32).reshape(-1)
+        n = int(ht.shape[0])
+        if wd.shape[0] != n or len(pitches) != n or len(offsets) != n:
+            raise ValueError("encode_png_mixed wants one height, width, pitch and offset per image")
+        pt = (C.c_size_t * max(n, 1))(*[int(v) for v in pitches])
+        of = (C.c_size_t * max(n, 1))(*[int(v) for v in offsets])
+        bounds = [png_encode_capacity(int(h), int(w)) for h, w in zip(ht, wd)]
+        sizes = (C.c_size_t * max(n, 1))()
+        rc = CTPN_OK
+        # first a little above the raw size: noise codes at just over 8 bits per byte, and ONE file above its buffer repeats the whole call;
+        # then the proven bound, twice the raw size
+        for proven in (False, True):
+            want = [b if proven else min(b, int(h) * int(w) * 3 * 65 // 64 + 4096) for b, h, w in zip(bounds, ht, wd)]
+            bufs = [np.empty((cap,), np.uint8) for cap in want]
+            ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+            caps = (C.c_size_t * max(n, 1))(*want)
+            rc = self._lib.ctpn_encode_png_mixed(self._h, src, on_dev, nbytes, n, _ptr(ht, C.c_int), _ptr(wd, C.c_int), pt, of, ptrs, caps, sizes)
+            if rc != CTPN_ERR_CAPACITY:
+                break
+        _check(rc)
+        return [bufs[i][: sizes[i]].tobytes() for i in range(n)]
 
     def encode_jpeg_mixed(self, images=None, quality=95, entropy="host", device_ptr=None, heights=None, widths=None, pitches=None, offsets=None):
         """JPEG files of n BGR uint8 images of ANY mix of sizes in one call (ctpn_encode_jpeg_mixed). images: a list of (h_i, w_i, 3) arrays

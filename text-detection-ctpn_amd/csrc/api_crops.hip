@@ -86,15 +86,16 @@ static int crop_cut(ctpn_ctx* c, const uint8_t* images, int images_on_device, in
   return launch_crop_lines(px, K.desc_dev, (int)total, out_dev, h, w, heights_dev, crop_h, max_w, pad_value, qs);
 }
 
-// ctpn_write_line_crops / ctpn_write_line_crops_device and their _ragged forms
+// ctpn_write_line_crops / ctpn_write_line_crops_device / ctpn_write_line_crops_png and their _ragged forms. format: the files'
+enum CropFormat { CROP_JPEG, CROP_PNG };      // (PNG: lossless, no quality, host-built codes only)
 static int write_line_crops_impl(ctpn_ctx* c, const char* who_, const uint8_t* images, int images_on_device, int n, int h, int w, const int* heights, bool ragged,
-                                 const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths,
+                                 const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, CropFormat format, int quality, const char* const* paths,
                                  int* widths_out, int* total_out, bool device_entropy) {
   const std::string who(who_);
   std::vector<int> widths;
   int rc;
   if ((rc = crop_plan(who_, c, n, h, w, heights, ragged, recs, line_capacity, line_counts, crop_h, max_w, pad_value, widths_out, total_out, widths))) return rc;
-  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
+  if (format == CROP_JPEG && (quality < 1 || quality > 100)) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
   if (!paths) return CTPN_OK;      // the sizing call
   const size_t total = widths.size();
   if (total == 0) return CTPN_OK;
@@ -104,14 +105,15 @@ static int write_line_crops_impl(ctpn_ctx* c, const char* who_, const uint8_t* i
   auto& K = c->crop;
   const size_t pitch = (size_t)max_w * 3, line_bytes = (size_t)crop_h * pitch;
   if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, total * line_bytes))) return rc;
-  // the encoder's aligned read (jenc_load4) stays inside a crop's pixels where its rows start 4-byte aligned: the buffer is a device
-  // allocation, a crop's offset and the pitch are multiples of 12 (max_w % 4 == 0, crop_check_geometry)
-  if (((uintptr_t)K.out_dev & 3) || (pitch & 3) || (line_bytes & 3)) return fail(CTPN_ERR_STATE, who + ": the crop rows are not 4-byte aligned");
+  // the JPEG encoder's aligned read (jenc_load4) stays inside a crop's pixels where its rows start 4-byte aligned: the buffer is a device
+  // allocation, a crop's offset and the pitch are multiples of 12 (max_w % 4 == 0, crop_check_geometry). (The PNG writer reads bytes.)
+  if (format == CROP_JPEG && (((uintptr_t)K.out_dev & 3) || (pitch & 3) || (line_bytes & 3))) return fail(CTPN_ERR_STATE, who + ": the crop rows are not 4-byte aligned");
   if ((rc = crop_cut(c, images, images_on_device, n, h, w, heights, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, K.out_dev))) return rc;
   // encoded where they lie, behind the kernel in the same queue: crop k is crop_h x widths[k] at pitch 3 max_w -- the pad columns never enter a file
   std::vector<int> crop_heights(total, crop_h);
   std::vector<size_t> pitches(total, pitch), offsets(total);
   for (size_t k = 0; k < total; ++k) offsets[k] = k * line_bytes;
+  if (format == CROP_PNG) return png_code_table(c, who_, K.out_dev, (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), nullptr, nullptr, nullptr, paths);
   return encode_mixed_dev(c, who_, K.out_dev, (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
 }
 
@@ -173,27 +175,39 @@ int ctpn_crop_lines_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_dev
 
 int ctpn_write_line_crops(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
                           int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out) {
-  return write_line_crops_impl(c, "ctpn_write_line_crops", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, quality, paths,
+  return write_line_crops_impl(c, "ctpn_write_line_crops", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, CROP_JPEG, quality, paths,
                                widths_out, total_out, false);
 }
 
 int ctpn_write_line_crops_device(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
                                  int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out) {
-  return write_line_crops_impl(c, "ctpn_write_line_crops_device", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, quality, paths,
+  return write_line_crops_impl(c, "ctpn_write_line_crops_device", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, CROP_JPEG, quality, paths,
                                widths_out, total_out, true);
+}
+
+int ctpn_write_line_crops_png(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity, const int* line_counts,
+                              int crop_h, int max_w, int pad_value, const char* const* paths, int* widths_out, int* total_out) {
+  return write_line_crops_impl(c, "ctpn_write_line_crops_png", images, images_on_device, n, h, w, nullptr, false, recs, line_capacity, line_counts, crop_h, max_w, pad_value, CROP_PNG, 0,
+                               paths, widths_out, total_out, false);
+}
+
+int ctpn_write_line_crops_png_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs, int line_capacity,
+                                     const int* line_counts, int crop_h, int max_w, int pad_value, const char* const* paths, int* widths_out, int* total_out) {
+  return write_line_crops_impl(c, "ctpn_write_line_crops_png_ragged", canvas, canvas_on_device, n, hc, w, heights, true, recs, line_capacity, line_counts, crop_h, max_w, pad_value,
+                               CROP_PNG, 0, paths, widths_out, total_out, false);
 }
 
 int ctpn_write_line_crops_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs, int line_capacity,
                                  const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths, int* widths_out, int* total_out) {
   return write_line_crops_impl(c, "ctpn_write_line_crops_ragged", canvas, canvas_on_device, n, hc, w, heights, true, recs, line_capacity, line_counts, crop_h, max_w, pad_value,
-                               quality, paths, widths_out, total_out, false);
+                               CROP_JPEG, quality, paths, widths_out, total_out, false);
 }
 
 int ctpn_write_line_crops_ragged_device(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs,
                                         int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value, int quality, const char* const* paths,
                                         int* widths_out, int* total_out) {
   return write_line_crops_impl(c, "ctpn_write_line_crops_ragged_device", canvas, canvas_on_device, n, hc, w, heights, true, recs, line_capacity, line_counts, crop_h, max_w,
-                               pad_value, quality, paths, widths_out, total_out, true);
+                               pad_value, CROP_JPEG, quality, paths, widths_out, total_out, true);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // C ABI of libctpn_hip.so, the annotated writer over a RAGGED canvas (include/ctpn_hip.h, "Ragged batches out"): images of one width and
 // different heights in the slots of one canvas (ctpn_decode_jpeg_*_ragged, ctpn_detect_submit_ragged), each written back at its own
-// file's size. The pixel stage in front of the mixed-size encoder (api_jpeg_out.hip, encode_mixed_dev):
+// file's size. The pixel stage (annotate_ragged) in front of the mixed-size coders, one per format (api_jpeg_out.hip, encode_mixed_dev;
+// api_png_out.hip, png_code_table):
 //   the canvas copied into a ctx-owned buffer (the decoder's may still feed a forward; a host canvas is staged the same way),
 //   outlines drawn slot by slot, bounded by each image's own height (jpeg_enc.hip, draw_boxes_ragged_kernel: draw_boxes_kernel's body),
 //   every image whose scale is not 1 resized by its own 1 / scale into a block of its own behind the canvas copy, in ONE launch
@@ -15,15 +16,15 @@ namespace ctpn {
 
 static inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// ctpn_write_annotated_files_ragged / ctpn_write_annotated_files_ragged_device
-static int write_annotated_ragged_impl(ctpn_ctx* c, const char* who_, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs,
-                                       int line_capacity, const int* line_counts, const double* scales, const char* const* paths, int quality, bool device_entropy) {
-  const std::string who(who_);
+// (ctx.h) the pixel stage both formats share
+int annotate_ragged(ctpn_ctx* c, const std::string& who, const char* format, StageTableCheck table_check, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w,
+                    const int* heights, const double* recs, int line_capacity, const int* line_counts, const double* scales, const char* const* paths, const uint8_t*& px,
+                    std::vector<int>& dh, std::vector<int>& dw, std::vector<size_t>& pitches, std::vector<size_t>& offsets) {
   if (!c || !canvas || !heights || !line_counts || !scales || !paths) return fail(CTPN_ERR_ARG, who + ": null pointer");
   if (n <= 0 || hc <= 0 || w <= 0 || hc > 65535 || w > 65535 || line_capacity < 0) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size");
-  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
   // per image: the size it is written at (demo.py:51: cv2.resize by fx = fy = 1 / scale; the identity is a copy there and no work here)
-  std::vector<int> dh((size_t)n), dw((size_t)n), resized;
+  std::vector<int> resized;
+  dh.assign((size_t)n, 0); dw.assign((size_t)n, 0);
   std::vector<double> inv_f((size_t)n, 1.0);
   for (int i = 0; i < n; ++i) {
     const std::string img = who + ": image " + std::to_string(i) + ": ";
@@ -36,12 +37,14 @@ static int write_annotated_ragged_impl(ctpn_ctx* c, const char* who_, const uint
     if (f != 1.0) {
       // (a double outside int's range does not convert: compared first)
       const double rh = std::nearbyint((double)heights[i] * f), rw = std::nearbyint((double)w * f);
-      if (!(rh >= 1.0) || !(rw >= 1.0) || rh > 65535.0 || rw > 65535.0) return fail(CTPN_ERR_ARG, img + "the resized image is empty or too large for a JPEG file");
+      if (!(rh >= 1.0) || !(rw >= 1.0) || rh > 65535.0 || rw > 65535.0) return fail(CTPN_ERR_ARG, img + "the resized image is empty or too large for a " + format + " file");
       dh[i] = resize_out_dim(heights[i], f); dw[i] = resize_out_dim(w, f);
       inv_f[i] = 1.0 / f;      // what launch_resize_linear hands its kernel
       resized.push_back(i);
     }
   }
+  int rc;
+  if (table_check && (rc = table_check(who, n, dh.data(), dw.data()))) return rc;
   if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   auto& S = c->stage;
@@ -49,7 +52,7 @@ static int write_annotated_ragged_impl(ctpn_ctx* c, const char* who_, const uint
   // ONE buffer: the canvas copy, then a block per resized image (256-byte aligned; rows at resize_mixed_pitch), then the encoder's slack
   const size_t slot_bytes = (size_t)hc * w * 3, canvas_bytes = (size_t)n * slot_bytes;
   const int m = (int)resized.size();
-  std::vector<size_t> pitches((size_t)n, (size_t)w * 3), offsets((size_t)n);
+  pitches.assign((size_t)n, (size_t)w * 3); offsets.assign((size_t)n, 0);
   for (int i = 0; i < n; ++i) offsets[i] = (size_t)i * slot_bytes;
   size_t at = up256(canvas_bytes + 4);
   for (int i : resized) {
@@ -57,7 +60,6 @@ static int write_annotated_ragged_impl(ctpn_ctx* c, const char* who_, const uint
     offsets[i] = at;
     at = up256(at + (size_t)dh[i] * pitches[i]);
   }
-  int rc;
   if ((rc = grow_dev((void**)&S.img_dev, S.img_bytes, at + 256))) return rc;
   if ((rc = grow_dev((void**)&S.recs_dev, S.recs_bytes, std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64)))) return rc;
   if ((rc = grow_dev((void**)&S.cnt_dev, S.cnt_bytes, (size_t)n * sizeof(int)))) return rc;
@@ -85,7 +87,23 @@ static int write_annotated_ragged_impl(ctpn_ctx* c, const char* who_, const uint
   CTPN_HIP_TRY(hipMemcpyAsync(S.cnt_dev, line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
   if ((rc = launch_draw_boxes_ragged(S.img_dev, S.recs_dev, S.cnt_dev, (const int*)S.rm_dev, line_capacity, n, hc, w, qs))) return rc;
   if (m && (rc = launch_resize_linear_mixed(S.img_dev, S.img_dev, S.rm_dev + tab_off, m, items, qs))) return rc;
-  return encode_mixed_dev(c, who_, S.img_dev, n, dh.data(), dw.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
+  px = S.img_dev;
+  return CTPN_OK;
+}
+
+// ctpn_write_annotated_files_ragged / ctpn_write_annotated_files_ragged_device
+static int write_annotated_ragged_impl(ctpn_ctx* c, const char* who_, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs,
+                                       int line_capacity, const int* line_counts, const double* scales, const char* const* paths, int quality, bool device_entropy) {
+  const std::string who(who_);
+  // (the stage's first two checks, repeated: the quality keeps its place behind them and in front of the per-image checks)
+  if (!c || !canvas || !heights || !line_counts || !scales || !paths) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0 || hc <= 0 || w <= 0 || hc > 65535 || w > 65535 || line_capacity < 0) return fail(CTPN_ERR_ARG, who + ": empty batch / bad size");
+  if (quality < 1 || quality > 100) return fail(CTPN_ERR_ARG, who + ": quality must be 1 .. 100");
+  const uint8_t* px;
+  std::vector<int> dh, dw;
+  std::vector<size_t> pitches, offsets;
+  if (int rc = annotate_ragged(c, who, "JPEG", nullptr, canvas, canvas_on_device, n, hc, w, heights, recs, line_capacity, line_counts, scales, paths, px, dh, dw, pitches, offsets)) return rc;
+  return encode_mixed_dev(c, who_, px, n, dh.data(), dw.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
 }
 
 }  // namespace ctpn
@@ -96,6 +114,16 @@ int ctpn_write_annotated_files_ragged(ctpn_ctx* c, const uint8_t* canvas, int ca
                                       const int* line_counts, const double* scales, const char* const* paths, int quality) {
   return write_annotated_ragged_impl(c, "ctpn_write_annotated_files_ragged", canvas, canvas_on_device, n, hc, w, heights, recs, line_capacity, line_counts, scales, paths, quality,
                                      false);
+}
+
+int ctpn_write_annotated_png_files_ragged(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs, int line_capacity,
+                                          const int* line_counts, const double* scales, const char* const* paths) {
+  const uint8_t* px;
+  std::vector<int> dh, dw;
+  std::vector<size_t> pitches, offsets;
+  if (int rc = annotate_ragged(c, "ctpn_write_annotated_png_files_ragged", "PNG", png_table_check, canvas, canvas_on_device, n, hc, w, heights, recs, line_capacity, line_counts, scales,
+                               paths, px, dh, dw, pitches, offsets)) return rc;
+  return png_code_table(c, "ctpn_write_annotated_png_files_ragged", px, n, dh.data(), dw.data(), pitches.data(), offsets.data(), nullptr, nullptr, nullptr, paths);
 }
 
 int ctpn_write_annotated_files_ragged_device(ctpn_ctx* c, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w, const int* heights, const double* recs,

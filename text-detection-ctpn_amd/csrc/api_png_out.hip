@@ -1,6 +1,8 @@
 // C ABI of libctpn_hip.so, PNG output unit: PNG writing of a batch on the device (kernels: png_enc.hip) -- the cv2.imwrite end of the
 // PNG-named result images of ctpn/demo.py:28-52 (outlines and resize: api_out_stage.hip) --, and the host form of the same file
-// (png_enc_dev.h: one text for both, so the two forms cannot disagree about a file).
+// (png_enc_dev.h: one text for both, so the two forms cannot disagree about a file). The coder takes a TABLE of images of any sizes and
+// pitches over one device source (png_code_table: ctpn_encode_png_mixed, the ragged annotated writer of api_out_ragged.hip, the crop
+// files of api_crops.hip); the uniform calls are tables of equal sizes at pitch 3 w.
 #include "ctx.h"
 #include "png_enc_dev.h"
 
@@ -22,71 +24,84 @@ static int png_device_size_check(const std::string& who, int h, int w) {      //
   return (uint64_t)h * (1u + 3u * (uint64_t)w) <= PNGE_MAX_STREAM ? CTPN_OK : fail(CTPN_ERR_ARG, who + ": h (1 + 3 w) above 2^27: ctpn_png_encode takes such images");
 }
 
-// n images of h x w x 3 at px (device, complete in the ctx's copy queue) -> n files, in the caller's buffers (out) or in files (paths)
-static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int h, int w, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths) {
+// (ctx.h) the device form's bounds on a table, host arithmetic only: every size, every image's stream, the work items and the pieces
+int png_table_check(const std::string& who, int n, const int* heights, const int* widths) {
+  PngeTotals t = PngeTotals();
+  for (int i = 0; i < n; ++i) {
+    const std::string img = who + ": image " + std::to_string(i);
+    if (!png_size_ok(heights[i], widths[i])) return fail(CTPN_ERR_ARG, img + ": bad size");
+    if (int rc = png_device_size_check(img, heights[i], widths[i])) return rc;
+    PngeImg d;
+    pnge_describe(d, heights[i], widths[i]);
+    t.pieces += d.npieces; t.items += pnge_groups(d);
+  }
+  return pnge_totals_ok(t) ? CTPN_OK : fail(CTPN_ERR_ARG, who + ": more than 2^31 - 1 work items or 2^32 pieces in one call");
+}
+
+// (ctx.h) n images over ONE device source px (complete in the ctx's copy queue, or produced in it): image i is heights[i] x widths[i] x 3
+// at px + offsets[i], rows pitches[i] bytes apart -> n files, in the caller's buffers (out) or in files (paths). Every buffer is laid out
+// by pnge_layout's prefix sums: a call costs the sum of its images, not n times the largest
+int png_code_table(ctpn_ctx* c, const char* who, const uint8_t* px, int n, const int* heights, const int* widths, const size_t* pitches, const size_t* offsets, uint8_t* const* out,
+                   const size_t* capacities, size_t* bytes_out, const char* const* paths) {
+  int rc;
+  if ((rc = png_table_check(who, n, heights, widths))) return rc;
   auto& P = c->pnge;
   hipStream_t qs = c->stream_c;
   if (!P.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&P.ev_done, hipEventDisableTiming));
   c->pnge_stats[0] = c->pnge_stats[1] = c->pnge_stats[2] = c->pnge_stats[3] = 0;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  PngeImg d0;
-  pnge_describe(d0, h, w);
-  const size_t nw = (size_t)pnge_words(d0), per_px = (size_t)h * w * 3;
-  if ((uint64_t)n * d0.npieces > 0xffffffffull || n > 65535) return fail(CTPN_ERR_ARG, std::string(who) + ": more than 65535 images or 2^32 pieces in one call");
   const size_t o_img = 0, o_hist = up(o_img + (size_t)n * sizeof(PngeImg)), o_res = o_hist + (size_t)n * PNGE_NSYM * 4, o_codes = up(o_res + (size_t)n * sizeof(PngeRes)),
-               host_total = o_codes + (size_t)n * sizeof(PngeCodes), o_len = up(host_total), o_words = up(o_len + (size_t)n * d0.npieces * sizeof(PngeLen)),
-               dev_total = o_words + (size_t)n * nw * 4;
-  int rc;
+               host_total = o_codes + (size_t)n * sizeof(PngeCodes);
   if ((rc = grow_host(&P.host, P.host_bytes, host_total))) return rc;
-  if ((rc = grow_dev((void**)&P.dev, P.dev_bytes, dev_total))) return rc;
   PngeImg* imgs = (PngeImg*)(P.host + o_img);
   uint32_t* hist = (uint32_t*)(P.host + o_hist);
   PngeRes* res = (PngeRes*)(P.host + o_res);
   PngeCodes* codes = (PngeCodes*)(P.host + o_codes);
-  for (int i = 0; i < n; ++i) imgs[i] = d0;
+  for (int i = 0; i < n; ++i) pnge_describe(imgs[i], heights[i], widths[i]);
   PngeTotals t;
-  pnge_layout(imgs, (size_t)n, t);      // (one size: image i's parts are the i-th of n equal ones)
+  pnge_layout(imgs, (size_t)n, t);
+  for (int i = 0; i < n; ++i) { imgs[i].pix_off = offsets[i]; imgs[i].pitch = pitches[i]; }      // the caller's source, not the dense packing
+  const size_t o_len = up(host_total), o_words = up(o_len + (size_t)t.pieces * sizeof(PngeLen)), dev_total = o_words + (size_t)t.words * 4;
+  if ((rc = grow_dev((void**)&P.dev, P.dev_bytes, dev_total))) return rc;
   // histograms -> the host, which builds every image's code and block header; one copy brings them back
   CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_img, imgs, (size_t)n * sizeof(PngeImg), hipMemcpyHostToDevice, qs));
   CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_hist, 0, (size_t)n * (PNGE_NSYM * 4 + sizeof(PngeRes)), qs));      // counters and result records
-  if ((rc = launch_png_hist((const PngeImg*)(P.dev + o_img), px, (uint32_t*)(P.dev + o_hist), n, d0.npieces, qs))) return rc;
+  if ((rc = launch_png_hist((const PngeImg*)(P.dev + o_img), px, (uint32_t*)(P.dev + o_hist), n, t.items, qs))) return rc;
   CTPN_HIP_TRY(hipMemcpyAsync(hist, P.dev + o_hist, (size_t)n * PNGE_NSYM * 4, hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
   c->pnge_stats[3] += (long long)n * PNGE_NSYM * 4;
   c->pool->run(n, [&](int i) { pnge_build_codes(imgs[i], hist + (size_t)i * PNGE_NSYM, codes[i]); });
   CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_codes, codes, (size_t)n * sizeof(PngeCodes), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_words, 0, (size_t)n * nw * 4, qs));      // the write pass ORs shared words into it
+  CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_words, 0, (size_t)t.words * 4, qs));      // the write pass ORs shared words into it
   if ((rc = launch_png_code((const PngeImg*)(P.dev + o_img), px, (const PngeCodes*)(P.dev + o_codes), (PngeLen*)(P.dev + o_len), (uint32_t*)(P.dev + o_words),
-                            (PngeRes*)(P.dev + o_res), n, d0.npieces, qs))) return rc;
+                            (PngeRes*)(P.dev + o_res), n, t.items, qs))) return rc;
   // the result records first, then exactly the bytes they name
   CTPN_HIP_TRY(hipMemcpyAsync(res, P.dev + o_res, (size_t)n * sizeof(PngeRes), hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
   c->pnge_stats[3] += (long long)n * (long long)sizeof(PngeRes);
-  std::vector<size_t> at((size_t)n, 0);
+  std::vector<size_t> at((size_t)n, 0), back_at((size_t)n, 0);
   std::vector<char> on_host((size_t)n, 0);
   size_t file_total = 0, back_total = 0;
   for (int i = 0; i < n; ++i) {
-    if (res[i].flag || (size_t)res[i].bytes > nw * 4) { on_host[i] = 1; back_total += per_px; continue; }
+    if (res[i].flag || (uint64_t)res[i].bytes > imgs[i].nwords * 4) { on_host[i] = 1; back_at[i] = back_total; back_total += (size_t)heights[i] * widths[i] * 3; continue; }
     at[i] = file_total;
     file_total += up((size_t)PNGE_FRAME_BYTES + res[i].bytes);
   }
   if ((rc = grow_host(&P.file_host, P.file_host_bytes, file_total))) return rc;
-  std::vector<uint8_t> back;      // the pixels of the images the host form codes (none, unless a flag is raised)
+  std::vector<uint8_t> back;      // the pixels of the images the host form codes (none, unless a flag is raised), each a dense block
   try { back.resize(back_total); } catch (const std::exception& e) { return fail(CTPN_ERR_CAPACITY, std::string(who) + ": " + e.what()); }
-  size_t bat = 0;
-  std::vector<size_t> back_at((size_t)n, 0);
   for (int i = 0; i < n; ++i) {
     if (on_host[i]) {
       ++c->pnge_stats[1];
-      back_at[i] = bat;
-      CTPN_HIP_TRY(hipMemcpyAsync(back.data() + bat, px + (size_t)i * per_px, per_px, hipMemcpyDeviceToHost, qs));
-      bat += per_px; c->pnge_stats[3] += (long long)per_px;
+      const size_t row = (size_t)widths[i] * 3;
+      CTPN_HIP_TRY(hipMemcpy2DAsync(back.data() + back_at[i], row, px + offsets[i], pitches[i], row, (size_t)heights[i], hipMemcpyDeviceToHost, qs));
+      c->pnge_stats[3] += (long long)(row * heights[i]);
       continue;
     }
-    ++c->pnge_stats[0]; c->pnge_stats[2] += d0.npieces;
-    CTPN_HIP_TRY(hipMemcpyAsync(P.file_host + at[i] + PNGE_FRAME_FRONT, P.dev + o_words + (size_t)i * nw * 4, res[i].bytes, hipMemcpyDeviceToHost, qs));
+    ++c->pnge_stats[0]; c->pnge_stats[2] += imgs[i].npieces;
+    CTPN_HIP_TRY(hipMemcpyAsync(P.file_host + at[i] + PNGE_FRAME_FRONT, P.dev + o_words + (size_t)imgs[i].word0 * 4, res[i].bytes, hipMemcpyDeviceToHost, qs));
     c->pnge_stats[3] += (long long)res[i].bytes;
   }
   CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
@@ -98,6 +113,7 @@ static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int 
     const size_t cap = paths ? 0 : capacities[i];
     size_t* bo = paths ? nullptr : bytes_out + i;
     const char* path = paths ? paths[i] : nullptr;
+    const int h = heights[i], w = widths[i];
     try {
       if (on_host[i]) {
         size_t need = 0;
@@ -113,6 +129,15 @@ static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int 
     } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }
   });
   return first_failure(who, st, msg);
+}
+
+// the uniform calls: n images of h x w x 3, dense at px -- a table of equal sizes at pitch 3 w
+static int png_code(ctpn_ctx* c, const char* who, const uint8_t* px, int n, int h, int w, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths) {
+  const size_t per_px = (size_t)h * w * 3;
+  std::vector<int> heights((size_t)n, h), widths((size_t)n, w);
+  std::vector<size_t> pitches((size_t)n, (size_t)w * 3), offsets((size_t)n);
+  for (int i = 0; i < n; ++i) offsets[i] = (size_t)i * per_px;
+  return png_code_table(c, who, px, n, heights.data(), widths.data(), pitches.data(), offsets.data(), out, capacities, bytes_out, paths);
 }
 
 }  // namespace ctpn
@@ -143,6 +168,32 @@ int ctpn_encode_png_batch(ctpn_ctx* c, const uint8_t* images, int images_on_devi
   const uint8_t* px;
   if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
   return png_code(c, "ctpn_encode_png_batch", px, n, h, w, out, capacities, bytes_out, nullptr);
+}
+
+int ctpn_encode_png_mixed(ctpn_ctx* c, const uint8_t* source, int source_on_device, size_t source_bytes, int n, const int* heights, const int* widths, const size_t* pitches,
+                          const size_t* offsets, uint8_t* const* out, const size_t* capacities, size_t* bytes_out) {
+  const std::string who("ctpn_encode_png_mixed");
+  if (!c || !source || !heights || !widths || !pitches || !offsets || !out || !capacities || !bytes_out) return fail(CTPN_ERR_ARG, who + ": null pointer");
+  if (n <= 0) return fail(CTPN_ERR_ARG, who + ": empty batch");
+  const size_t limit = (size_t)1 << 40;      // (offset + row * pitch cannot wrap)
+  for (int i = 0; i < n; ++i) {
+    const std::string img = who + ": image " + std::to_string(i);
+    if (!png_size_ok(heights[i], widths[i])) return fail(CTPN_ERR_ARG, img + ": bad size");
+    if (pitches[i] < (size_t)widths[i] * 3) return fail(CTPN_ERR_ARG, img + ": the pitch is below 3 * width");
+    if (pitches[i] >= limit || offsets[i] >= limit) return fail(CTPN_ERR_ARG, img + ": pitch or offset of 2^40 bytes or more");
+    if (!out[i] && capacities[i]) return fail(CTPN_ERR_ARG, img + ": null output pointer");
+    if (!source_on_device) {
+      const size_t span = (size_t)(heights[i] - 1) * pitches[i] + (size_t)widths[i] * 3;
+      if (pitches[i] > source_bytes || offsets[i] > source_bytes || span > source_bytes - offsets[i]) return fail(CTPN_ERR_ARG, img + " does not lie inside source_bytes");
+    }
+  }
+  int rc;
+  if ((rc = png_table_check(who, n, heights, widths))) return rc;
+  if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  const uint8_t* px;
+  if ((rc = stage_pixels(c, source, source_on_device, source_bytes, 0, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
+  return png_code_table(c, "ctpn_encode_png_mixed", px, n, heights, widths, pitches, offsets, out, capacities, bytes_out, nullptr);
 }
 
 int ctpn_write_annotated_png_files(ctpn_ctx* c, const uint8_t* images, int images_on_device, int n, int h, int w, const double* recs, int line_capacity,

@@ -421,8 +421,8 @@ int launch_crop_lines(const uint8_t* imgs_dev, const void* descs_dev, int total,
 // png_enc.hip: the DEFLATE block of PNG files on the device (per-piece source, the structures and the file's definition: png_enc_dev.h).
 // hist: the images' symbol counts (n x 286, cleared by the caller); code: lengths, prefix sum + Adler-32, write (words cleared by the caller)
 struct PngeImg; struct PngeCodes; struct PngeLen; struct PngeRes;
-int launch_png_hist(const PngeImg* imgs, const uint8_t* px, uint32_t* hist, int n, uint32_t max_pieces, hipStream_t s);
-int launch_png_code(const PngeImg* imgs, const uint8_t* px, const PngeCodes* codes, PngeLen* len, uint32_t* words, PngeRes* res, int n, uint32_t max_pieces, hipStream_t s);
+int launch_png_hist(const PngeImg* imgs, const uint8_t* px, uint32_t* hist, int n, uint64_t items, hipStream_t s);
+int launch_png_code(const PngeImg* imgs, const uint8_t* px, const PngeCodes* codes, PngeLen* len, uint32_t* words, PngeRes* res, int n, uint64_t items, hipStream_t s);
 // png.cpp: CRC-32 of the PNG chunks (the DEFLATE library's where one is loaded)
 uint32_t png_crc32(const uint8_t* p, size_t n);
 

@@ -486,6 +486,21 @@ int first_failure(const char* who, const std::vector<int>& st, const std::vector
 // on disk (paths); returns when they are written. The contract of ctpn_encode_jpeg_mixed behind its argument checks
 int encode_mixed_dev(ctpn_ctx* c, const char* who, const uint8_t* px_dev, int n, const int* heights, const int* widths, const size_t* pitches, const size_t* offsets,
                      int quality, uint8_t* const* out, const size_t* capacities, size_t* bytes_out, const char* const* paths, bool device_entropy);
+// api_png_out.hip: the PNG writer's table form, encode_mixed_dev's counterpart (ctpn_encode_png_mixed behind its argument checks). The source
+// is read byte-wise: nothing outside an image's pixels is touched, at any pitch or alignment. png_table_check: the device form's bounds
+// on a table -- sizes 1 .. 65535, h (1 + 3 w) <= 2^27 per image, at most 2^31 - 1 work items, fewer than 2^32 pieces --, host arithmetic
+// only, naming the image; png_code_table runs it first, a caller with device work in front of the coder runs it before that
+int png_table_check(const std::string& who, int n, const int* heights, const int* widths);
+int png_code_table(ctpn_ctx* c, const char* who, const uint8_t* px, int n, const int* heights, const int* widths, const size_t* pitches, const size_t* offsets, uint8_t* const* out,
+                   const size_t* capacities, size_t* bytes_out, const char* const* paths);
+// api_out_ragged.hip: the pixel stage of the annotated writers over a ragged canvas, both formats'. Argument checks (format: "JPEG" or "PNG",
+// for the message; table_check, nullable: the format's own check of the written sizes, before any device work), then the canvas copied
+// into the ctx's buffer, outlines drawn per slot, every image resized by its own 1 / scales[i]: image i is dh[i] x dw[i] at
+// px + offsets[i], rows pitches[i] bytes apart
+typedef int (*StageTableCheck)(const std::string& who, int n, const int* heights, const int* widths);
+int annotate_ragged(ctpn_ctx* c, const std::string& who, const char* format, StageTableCheck table_check, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w,
+                    const int* heights, const double* recs, int line_capacity, const int* line_counts, const double* scales, const char* const* paths, const uint8_t*& px,
+                    std::vector<int>& dh, std::vector<int>& dw, std::vector<size_t>& pitches, std::vector<size_t>& offsets);
 bool jpeg_read_file(const char* path, std::vector<uint8_t>& buf, size_t limit = 0);      // api_input.hip: a whole file (limit: its first bytes only); false if it cannot be read
 void jpeg_layout8(const JpegGeom& g, int* layout8);                                      // api_input.hip: the eight ints ctpn_jpeg_entropy_decode describes a file's layout with
 

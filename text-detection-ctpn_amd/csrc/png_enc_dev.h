@@ -15,6 +15,13 @@
 //            combined with an atomic OR into a buffer that was cleared before; the thread of the last piece adds EOB
 // The three passes run the SAME pnge_piece: they cannot disagree. Every loop is bounded before it starts (PNGE_P positions per piece, 258
 // bytes per candidate); every store is checked against the image's part of the buffer.
+//
+// A call is a TABLE of images of any sizes (PngeImg): image i's pixels begin at pix_off, its rows are `pitch` bytes apart (>= 3 w). The read
+// is byte-wise (pnge_byte): the writer never touches a byte outside an image's h x w x 3 pixels, at any pitch or alignment -- not the
+// pitch's padding, not a byte behind the last row's last pixel. That asks less of the caller than the JPEG writer's aligned-dword read
+// (jpeg_enc_mixed_dev.h, jenc_load4). The hist, length and write kernels run over a one-dimensional grid of WORK ITEMS: an item is one
+// workgroup, PNGE_GROUP pieces, of ONE image (the LDS counters and the staged code table belong to one image); image i has
+// ceil(npieces_i / PNGE_GROUP) of them from group0 on (pnge_layout), and pnge_locate finds an item's image (jem_locate's search).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -33,6 +40,7 @@ enum : uint32_t { PNGE_FLAG_STORE = BITS_FLAG_STORE, PNGE_FLAG_SIZE = BITS_FLAG_
 
 enum {
   PNGE_P = 256,             // stream bytes per piece
+  PNGE_GROUP = 256,         // pieces per work item (the threads of a workgroup)
   PNGE_NSYM = 286,          // literal/length symbols (HLIT = 29)
   PNGE_EOB = 256,
   PNGE_HDR_WORDS = 42,      // the block header: 17 + 57 + 4 (286 + 30) = 1338 bits at most
@@ -40,16 +48,19 @@ enum {
 };
 // the device form's limit of h (1 + 3 w): 15 bits per byte keep every bit offset below 2^31
 static const uint64_t PNGE_MAX_STREAM = (uint64_t)1 << 27;
+static const uint64_t PNGE_MAX_ITEMS = 0x7fffffffull;      // a one-dimensional grid holds no more workgroups
 
 struct PngeImg {            // one image of a call
-  uint64_t pix_off;         // byte offset of its h x w x 3 BGR pixels in the batch
+  uint64_t pix_off;         // byte offset of its first BGR pixel in the call's source
+  uint64_t pitch;           // bytes from one pixel row to the next, >= 3 w
   uint64_t n;               // stream bytes: h (1 + 3 w)
   uint64_t word0, nwords;   // its part of the DEFLATE words
   uint32_t h, w, stride;    // stride = 1 + 3 w
   uint32_t npieces, piece0; // pieces; its first entry in the per-piece arrays
   uint32_t far_ok;          // stride <= 32768: the row above is within DEFLATE's window
   uint32_t far_bits, far_len;      // a far match's distance: the 1-bit code of symbol S (a 1) with the extra bits behind it; their count
-  uint32_t dsym, pad_;      // S: the distance symbol of stride (the dummy symbol 1 when stride > 32768); HDIST covers 0 .. S
+  uint32_t dsym;            // S: the distance symbol of stride (the dummy symbol 1 when stride > 32768); HDIST covers 0 .. S
+  uint32_t group0;          // its first work item: prefix sum of the images' ceil(npieces / PNGE_GROUP)
 };
 
 struct PngeCodes {          // per image, built on the host from the histogram
@@ -67,11 +78,11 @@ struct PngeRes {            // what comes back per image
 
 struct PngeLen { uint32_t bits, a, b, pad_; };      // per piece: its bits (after the scan: its bit offset), sum b, sum (len - j) b_j
 
-// the filtered byte c of row y (c = 0: the filter type)
-PNGE_HD uint32_t pnge_byte(const uint8_t* img, uint32_t w, uint32_t y, uint32_t c) {
+// the filtered byte c of row y (c = 0: the filter type); rows are `pitch` bytes apart. Reads the pixel's byte and its left neighbour's
+PNGE_HD uint32_t pnge_byte(const uint8_t* img, uint64_t pitch, uint32_t y, uint32_t c) {
   if (c == 0) return 1u;
   const uint32_t x = c - 1u, q = x / 3u, k = x - 3u * q;
-  const uint8_t* p = img + ((size_t)y * w + q) * 3u + (2u - k);
+  const uint8_t* p = img + (size_t)y * (size_t)pitch + (size_t)q * 3u + (2u - k);
   uint32_t v = p[0];
   if (x >= 3u) v -= p[-3];
   return v & 0xffu;
@@ -93,7 +104,8 @@ template <class Sink>
 PNGE_HD void pnge_piece(const PngeImg& im, const uint8_t* img, uint64_t p, Sink& s) {
   const uint64_t p0 = p * (uint64_t)PNGE_P;
   const uint32_t len = (uint32_t)(im.n - p0 < (uint64_t)PNGE_P ? im.n - p0 : (uint64_t)PNGE_P);
-  const uint32_t stride = im.stride, w = im.w;
+  const uint32_t stride = im.stride;
+  const uint64_t w = im.pitch;      // (what pnge_byte addresses a row by)
   uint32_t y = (uint32_t)(p0 / stride), c = (uint32_t)(p0 - (uint64_t)y * stride);
   bool have_prev = p0 >= 1;
   uint32_t prev = 0;
@@ -191,6 +203,21 @@ struct PngeWrite : WordSink<uint64_t> {
   PNGE_HD void finish() { if (nb) { emit((uint32_t)acc, false); nb = 0; } }
 };
 
+struct PngeItem { uint32_t img, piece; };      // a work item: its image, and the first piece of its group
+
+// item: 0 <= item < the table's total (the grid covers exactly that many). Every image has at least one item, so group0 rises strictly:
+// the last image whose first item is not behind it, a search over at most log2(n) + 1 entries
+PNGE_HD PngeItem pnge_locate(const PngeImg* imgs, uint32_t n, uint32_t item) {
+  uint32_t lo = 0, hi = n - 1u;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1u) >> 1;
+    if (imgs[mid].group0 <= item) lo = mid; else hi = mid - 1u;
+  }
+  PngeItem p;
+  p.img = lo; p.piece = (item - imgs[lo].group0) * (uint32_t)PNGE_GROUP;
+  return p;
+}
+
 // ---- the passes, one call per thread -----------------------------------------------------------------------------------------------
 
 // hist pass: thread s of image im. cnt: the 286 counters this thread's workgroup shares
@@ -254,11 +281,13 @@ PNGE_HD void pnge_scan_finish(const PngeImg& im, uint32_t carry, uint64_t sa, ui
 
 // ---- host only: ONE copy for the library's host form, the device form's host half and the test program ------------------------------
 
-// the descriptor of an h x w image (pix_off, word0, nwords, piece0: pnge_layout)
+// the descriptor of an h x w image, dense (pitch 3 w; a table's caller sets pitch and, behind pnge_layout, pix_off); word0, nwords, piece0,
+// group0: pnge_layout
 inline void pnge_describe(PngeImg& I, int h, int w) {
   static const uint32_t dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
   I = PngeImg();
   I.h = (uint32_t)h; I.w = (uint32_t)w; I.stride = 1u + 3u * (uint32_t)w;
+  I.pitch = 3u * (uint64_t)w;
   I.n = (uint64_t)h * I.stride;
   I.npieces = (uint32_t)((I.n + PNGE_P - 1) / PNGE_P);
   I.far_ok = I.stride <= 32768u ? 1u : 0u;
@@ -273,16 +302,21 @@ inline void pnge_describe(PngeImg& I, int h, int w) {
 // 15 + 5 + 1 + 13 bits), EOB, and the last word
 inline uint64_t pnge_words(const PngeImg& I) { return (1338u + 15u * I.n + 15u + 31u) / 32u + 1u; }
 
-struct PngeTotals { uint64_t pix, pieces, words; };
-// every image's part of every buffer of a call (the images described, of any sizes; the caller keeps `pieces` below 2^32), and their sizes
+PNGE_HD uint32_t pnge_groups(const PngeImg& I) { return (I.npieces + (uint32_t)PNGE_GROUP - 1u) / (uint32_t)PNGE_GROUP; }
+
+struct PngeTotals { uint64_t pix, pieces, words, items; };
+// every image's part of every buffer of a call (the images described, of any sizes), its first work item, and the totals. pix_off is the
+// dense packing's (image after image at pitch 3 w); a table over a source of its own sets pix_off behind this call. The caller keeps
+// `pieces` below 2^32 and `items` at PNGE_MAX_ITEMS at most (pnge_totals_ok) before it uses piece0 / group0
 inline void pnge_layout(PngeImg* imgs, size_t m, PngeTotals& t) {
   t = PngeTotals();
   for (size_t k = 0; k < m; ++k) {
     PngeImg& I = imgs[k];
-    I.pix_off = t.pix; I.piece0 = (uint32_t)t.pieces; I.word0 = t.words; I.nwords = pnge_words(I);
-    t.pix += (uint64_t)I.h * I.w * 3u; t.pieces += I.npieces; t.words += I.nwords;
+    I.pix_off = t.pix; I.piece0 = (uint32_t)t.pieces; I.word0 = t.words; I.nwords = pnge_words(I); I.group0 = (uint32_t)t.items;
+    t.pix += (uint64_t)I.h * I.w * 3u; t.pieces += I.npieces; t.words += I.nwords; t.items += pnge_groups(I);
   }
 }
+inline bool pnge_totals_ok(const PngeTotals& t) { return t.items <= PNGE_MAX_ITEMS && t.pieces < ((uint64_t)1 << 32); }
 
 // code lengths of at most `limit` bits for the symbols with cnt > 0 (0 for the others): Huffman's lengths, and where they exceed the limit
 // the Kraft sum is repaired -- clipped codes overdraw it; the deepest codes below the limit are lengthened until it holds, then codes are

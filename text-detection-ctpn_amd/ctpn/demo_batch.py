@@ -24,6 +24,10 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
     (ctpn_write_annotated_files_ragged; the canvas is not fetched), and --crops cuts their lines from the canvas
     (ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged). Same names, same bytes as without --ragged.
 
+  * with --crops-format png the crops are lossless `<stem>_<k>.png` files (--crops-encode gpu: ctpn_write_line_crops_png[_ragged]), and
+    with --ragged-png (next to --ragged --ragged-outputs --png-encode gpu) the PNG files of the run share ragged batches too and are
+    written from their canvases (ctpn_write_annotated_png_files_ragged). Same names, same decoded pixels.
+
   * cfg.TEST.RPN_* of the loaded text.yml go into the ctx's tail parameters (ctpn_set_param), so the batched path honours the file like
     the single-image path; --connector NAME=VALUE (repeatable; TextLineCfg's names, MIN_LINE_WIDTH for TEXT_PROPOSALS_WIDTH *
     MIN_NUM_PROPOSALS) sets the connector's thresholds for the batches and for the images that take the single-image path.
@@ -132,7 +136,7 @@ def plan_ragged_batches(shapes, max_batch, waste=RAGGED_WASTE):
 PNG_LAYOUT, OTHER_LAYOUT = (-1, 0), (0, 0)      # plan_device_jobs: layouts of the files the JPEG decoder does not take
 
 
-def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE):
+def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE, ragged_png=False):
     """The batches of the device path (_run_gpu). entries: [(name, file (h, w), layout, resize_im factor, resized (h, w))] of the images that
     take the batched path; layout = (components, sampling | orientation) of a JPEG file the library takes, PNG_LAYOUT, or OTHER_LAYOUT
     (Pillow). -> jobs = [(size, kind, f, rs, names)]. A pure function.
@@ -140,9 +144,18 @@ def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE):
     rs = their resized shape -- one decode call each takes.
     ragged: the JPEG files the library takes are planned with plan_ragged_batches on their RESIZED shapes first, whatever their file size,
     layout and orientation: kind 'ragged', size = rs = the canvas (hc, wc), f = [(file h, file w, factor)] per name
-    (Context.decode_jpeg_ragged). What ends alone there, and every PNG and Pillow file, is size-grouped as without it."""
+    (Context.decode_jpeg_ragged). What ends alone there, and every PNG and Pillow file, is size-grouped as without it.
+    ragged_png: the PNG files are planned the same way into jobs of a kind of their own, 'ragged-png' (size, f, rs as for 'ragged'): their
+    canvas is built on the host (PNG files are decoded there) and written by ctpn_write_annotated_png_files_ragged."""
     entries = list(entries)
     jobs = []
+    if ragged_png:
+        pngs = [e for e in entries if tuple(e[2]) == PNG_LAYOUT and e[4][0] >= 16]
+        batches, _ = plan_ragged_batches([e[4] for e in pngs], batch, waste)
+        for (hc, wc), members in batches:
+            jobs.append(((hc, wc), "ragged-png", [(pngs[i][1][0], pngs[i][1][1], pngs[i][3]) for i in members], (hc, wc), [pngs[i][0] for i in members]))
+        batched = {pngs[i][0] for _, members in batches for i in members}
+        entries = [e for e in entries if e[0] not in batched]
     if ragged:
         jpegs = [e for e in entries if e[2][0] > 0 and e[4][0] >= 16]      # (a ragged image has at least one feature row)
         batches, _ = plan_ragged_batches([e[4] for e in jpegs], batch, waste)
@@ -159,12 +172,17 @@ def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE):
     return jobs
 
 
-def check_ragged_options(decode="host", encode="host", png_encode="host", crops_dir=None, decode_procs=0, decode_pool=None, ragged_outputs=False, ragged=True):
+def check_ragged_options(decode="host", encode="host", png_encode="host", crops_dir=None, decode_procs=0, decode_pool=None, ragged_outputs=False, ragged=True,
+                         ragged_png=False):
     """run(..., ragged=True) with these options: ValueError for the combinations that stay uniform. The process-pool decoder fills
     shared-memory batches of one shape; the library's writers (encode / png_encode = 'gpu') and the crops take uniform device batches.
     ragged_outputs: the JPEG writer and the crops take the ragged batches of the device path as well (ctpn_write_annotated_files_ragged,
     ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged) -- it needs ragged and decode='gpu' / 'gpu-entropy'; encode and crops_dir then
-    pass, png_encode='gpu' stays refused (no PNG writer over a canvas)."""
+    pass, png_encode='gpu' stays refused unless ragged_png is given.
+    ragged_png: the PNG files share ragged batches too and the PNG writer takes their canvases (ctpn_write_annotated_png_files_ragged) --
+    it needs ragged, ragged_outputs and png_encode='gpu'; png_encode='gpu' then passes."""
+    if ragged_png and not (ragged and ragged_outputs and png_encode == "gpu"):
+        raise ValueError("ragged_png writes the PNG files of ragged batches on the device: it needs ragged=True, ragged_outputs=True and png_encode='gpu'")
     if ragged_outputs and not ragged:
         raise ValueError("ragged_outputs writes the outputs of ragged batches: it needs ragged=True")
     if ragged_outputs and decode not in ("gpu", "gpu-entropy"):
@@ -175,7 +193,7 @@ def check_ragged_options(decode="host", encode="host", png_encode="host", crops_
     if decode in ("gpu", "gpu-entropy"):
         if encode != "host" and not ragged_outputs:
             raise ValueError("ragged device decode does not combine with encode='gpu' / 'gpu-entropy': ctpn_write_annotated_files takes uniform batches")
-        if png_encode != "host":
+        if png_encode != "host" and not ragged_png:
             raise ValueError("ragged device decode does not combine with png_encode='gpu': ctpn_write_annotated_png_files takes uniform batches")
         if crops_dir is not None and not ragged_outputs:
             raise ValueError("ragged device decode does not combine with crops_dir: ctpn_crop_lines takes uniform batches")
@@ -303,32 +321,39 @@ def _read(name):
         return f.read()
 
 
-def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None, encode="host", heights=None):
+def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, device_ptr=None, shape=None, encode="host", heights=None, format="jpg"):
     """The text lines of one batch as rectified crops of height crop_h (ctpn_crop_lines: cut out on the device, from host images or from
     a batch that lies there), each written as <stem>_<k>.jpg -- k counts the image's lines as its res file lists them --, trimmed to its
     width, by the host writer. A line longer than max_w columns at that height is squeezed to max_w. -> number of files
     encode='gpu': the library codes and writes the files where the crops are cut (ctpn_write_line_crops: no crop visits the host or Python);
     'gpu-entropy': the same with the Huffman coding on the device too (ctpn_write_line_crops_device). Same names, same bytes.
-    heights: images / device_ptr is a ragged canvas, image i in rows [0, heights[i]) of slot i (the *_ragged calls). Same names, same bytes."""
+    heights: images / device_ptr is a ragged canvas, image i in rows [0, heights[i]) of slot i (the *_ragged calls). Same names, same bytes.
+    format='png': <stem>_<k>.png, lossless -- by Pillow (encode='host') or by the library (encode='gpu': ctpn_write_line_crops_png[_ragged]);
+    the two writers' files decode to the same pixels. There is no 'gpu-entropy' form of it."""
     if encode not in ("host", "gpu", "gpu-entropy"):
         raise ValueError("encode must be 'host', 'gpu' or 'gpu-entropy'")
+    if format not in ("jpg", "png"):
+        raise ValueError("format must be 'jpg' or 'png'")
+    if format == "png" and encode == "gpu-entropy":
+        raise ValueError("format='png' has no encode='gpu-entropy' form: the PNG writer's codes are built on the host")
     if encode != "host":
-        paths = [os.path.join(crops_dir, '{}_{}.jpg'.format(os.path.basename(nm).split('.')[0], j)) for nm, rr in zip(names, recs) for j in range(len(rr))]
+        paths = [os.path.join(crops_dir, '{}_{}.{}'.format(os.path.basename(nm).split('.')[0], j, format)) for nm, rr in zip(names, recs) for j in range(len(rr))]
         ctx.write_line_crops(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape, paths=paths, quality=95,
-                             entropy="device" if encode == "gpu-entropy" else "host", heights=heights)
+                             entropy="device" if encode == "gpu-entropy" else "host", heights=heights, format=format)
         return len(paths)
     crops, widths = ctx.crop_lines(images, recs, crop_h=crop_h, max_w=max_w, device_ptr=device_ptr, shape=shape, heights=heights)
     k = 0
     for nm, rr in zip(names, recs):
         stem = os.path.basename(nm).split('.')[0]
         for j in range(len(rr)):
-            imutil.imwrite(os.path.join(crops_dir, '{}_{}.jpg'.format(stem, j)), crops[k, :, :widths[k]])
+            imutil.imwrite(os.path.join(crops_dir, '{}_{}.{}'.format(stem, j, format)), crops[k, :, :widths[k]])
             k += 1
     return k
 
 
 def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
-             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False):
+             encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False, crops_format="jpg",
+             ragged_png=False):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -360,7 +385,11 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     ragged_outputs (--ragged-outputs, with ragged): encode='gpu' writes the annotated images of ragged batches too, from the canvas where it
     lies, every image resized by its own 1 / scale (ctpn_write_annotated_files_ragged[_device]; the canvas is not fetched), and crops_dir
     cuts their lines from the canvas (ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged[_device]). A ragged batch that fell back to
-    the host decoder hands its host canvas to the same calls. Same names, same bytes as without ragged."""
+    the host decoder hands its host canvas to the same calls. Same names, same bytes as without ragged.
+    crops_format (--crops-format, with crops_dir): 'png' -- the crops are <stem>_<k>.png files (write_crops).
+    ragged_png (--ragged-png, with ragged, ragged_outputs and png_encode='gpu'): the PNG files are batched by their resized shapes as well
+    (plan_device_jobs, kind 'ragged-png'); a batch's canvas is built on the host, where PNG files are decoded, submitted with its heights,
+    and its annotated images are written from it at collect time (ctpn_write_annotated_png_files_ragged). Same names, same pixels."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -384,14 +413,15 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             entries.append((name, (h, w), layout, f, rs))
         else:
             singles.append(name)
-    jobs = plan_device_jobs(entries, batch, ragged, ragged_waste)
+    jobs = plan_device_jobs(entries, batch, ragged, ragged_waste, ragged_png=ragged_png)
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
         _set_tail_params(net, params)
-    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_png": 0, "enc_host": 0, "crops": 0}
+    results, meta, stats = {}, {}, {"gpu": 0, "png": 0, "host": 0, "enc_gpu": 0, "enc_png": 0, "enc_host": 0, "crops": 0, "rag_png": 0}
     png_batches = {}                                   # slot -> (device pointer or None, host images or None, shape, scale) of a batch whose PNG files the library writes
     dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
     crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images; heights of a ragged canvas
+    rag_png_batches = {}                               # slot -> (host canvas, heights, scales) of a ragged PNG batch whose images the library writes
     rag_batches = {}                                   # slot -> (device pointer or None, host canvas or None, shape, heights, scales) of a ragged batch whose images the library writes
     # PNG batches are decoded ONE JOB AHEAD on a helper thread (the C++ decode threads hang off that call; ctypes releases the GIL), so that
     # batch k + 1 inflates while batch k is submitted and batch k - 1 collected. Three batch buffers per shape in a ring: when batch k + 1
@@ -447,10 +477,17 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.write_annotated_files_ragged(images=host_canvas, device_ptr=ptr, shape=shape, heights=hts, recs=[results[nm] for nm in members], scales=scs,
                                                  paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members], entropy=encode_entropy)
             stats["enc_gpu"] += len(members)
+        if slot in rag_png_batches:                    # ... and into PNG files (ctpn_write_annotated_png_files_ragged)
+            host_canvas, hts, scs = rag_png_batches.pop(slot)
+            net.ctx.write_annotated_png_files_ragged(images=host_canvas, heights=hts, recs=[results[nm] for nm in members], scales=scs,
+                                                     paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members])
+            stats["enc_gpu"] += len(members)
+            stats["enc_png"] += len(members)
+            stats["rag_png"] += 1
         if slot in crop_src:                           # (a device batch is live until the second-next decode: this is one decode from its own)
             ptr, shape, imgs, hts = crop_src.pop(slot)
             stats["crops"] += write_crops(net.ctx, crops_dir, members, [results[nm] for nm in members], crop_h, images=imgs, device_ptr=ptr, shape=shape,
-                                          encode=crops_encode, heights=hts)
+                                          encode=crops_encode, heights=hts, format=crops_format)
         for nm in members:
             emit(nm)
 
@@ -493,6 +530,15 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                 if ragged_outputs and write_images and encode == "gpu" and all(_is_jpeg(nm) for nm in members):      # the host canvas through the same call
                     rag_batches[k & 1] = (None, canvas, canvas.shape[:3], heights, scales)
                 rag_crops = (None, None, canvas, heights)
+        if kind == "ragged-png":                       # the same shape of job over PNG files: the canvas is built on the host (ragged_png)
+            scales = [t[2] for t in f]
+            imgs = [_load(nm)[0] for nm in members]
+            canvas, heights = im_list_to_canvas(imgs)
+            net.ctx.detect_submit(images=canvas, heights=heights, slot=k & 1)
+            stats["host"] += len(members)
+            if write_images and png_encode == "gpu":
+                rag_png_batches[k & 1] = (canvas, heights, scales)
+            rag_crops = (None, None, canvas, heights)
         if kind == "jpg":
             try:
                 ptr = None
@@ -535,7 +581,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.detect_submit(images=imgs, slot=k & 1)
             stats["host"] += len(members)
         for i, nm in enumerate(members):
-            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches and (k & 1) not in rag_batches else None, scales[i])
+            meta[nm] = (imgs[i] if imgs is not None and write_images and (k & 1) not in png_batches and (k & 1) not in rag_batches and (k & 1) not in rag_png_batches else None,
+                        scales[i])
         if pending is not None:
             collect(pending)
         if crops_dir:
@@ -551,7 +598,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
         results[nm] = _text_detector(params).detect(boxes, scores[:, np.newaxis], img.shape[:2])
         meta[nm] = (img, scale)
         if crops_dir:
-            stats["crops"] += write_crops(net.ctx, crops_dir, [nm], [results[nm]], crop_h, images=img[None], encode=crops_encode)
+            stats["crops"] += write_crops(net.ctx, crops_dir, [nm], [results[nm]], crop_h, images=img[None], encode=crops_encode, format=crops_format)
         emit(nm)
     dt = time.time() - t0
     log('Detection of {:d} images in {:d} batches took {:.3f}s, result files included, after a header scan of {:.3f}s ({:.1f} images/s; {:d} decoded on the device, {:d} PNG files by the library, {:d} on the host)'.format(
@@ -561,6 +608,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             stats["enc_gpu"], stats["enc_host"]))
         if stats["enc_png"]:
             log('... of the library\'s, {:d} are PNG files, coded on the device'.format(stats["enc_png"]))
+        if stats["rag_png"]:
+            log('... written from {:d} ragged PNG batches (ctpn_write_annotated_png_files_ragged)'.format(stats["rag_png"]))
     if crops_dir:
         log('Text-line crops: {:d} of height {:d} cut out on the device, written by {}'.format(
             stats["crops"], crop_h, "the host writer (Pillow)" if crops_encode == "host" else "the library (device + C++ pool)"))
@@ -568,7 +617,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
 
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
-        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False):
+        encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False,
+        crops_format="jpg", ragged_png=False):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
@@ -590,7 +640,12 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     png_encode='gpu' or crops_dir, which take uniform batches (check_ragged_options: ValueError).
     ragged_outputs (off by default; needs ragged and decode='gpu' / 'gpu-entropy', else ValueError before any work): encode='gpu' /
     'gpu-entropy' and crops_dir (with any crops_encode) then combine with ragged -- the library writes the annotated images and the crops
-    of ragged batches from their canvases (_run_gpu). png_encode='gpu' stays refused. Same names, same bytes as without ragged."""
+    of ragged batches from their canvases (_run_gpu). png_encode='gpu' stays refused. Same names, same bytes as without ragged.
+    crops_format (default 'jpg'): 'png' -- the crops are lossless <stem>_<k>.png files, by Pillow (crops_encode='host') or by the library
+    (crops_encode='gpu': ctpn_write_line_crops_png, and ..._png_ragged for ragged batches); with crops_encode='gpu-entropy': ValueError.
+    ragged_png (off by default; needs ragged, ragged_outputs and png_encode='gpu', else ValueError before any work): png_encode='gpu' then
+    combines with ragged -- the PNG files share ragged batches and the library writes their annotated images from the canvases
+    (ctpn_write_annotated_png_files_ragged). Same names, same decoded pixels as without it."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config(params)
     if params:
@@ -615,14 +670,18 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         raise ValueError("crops_encode must be 'host', 'gpu' or 'gpu-entropy'")
     if crops_encode != "host" and (crops_dir is None or decode != "gpu"):
         raise ValueError("crops_encode='%s' writes the crops of crops_dir on the device: it needs crops_dir and decode='gpu'" % crops_encode)
-    if ragged or ragged_outputs:
-        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool, ragged_outputs=ragged_outputs, ragged=ragged)
+    if crops_format not in ("jpg", "png"):
+        raise ValueError("crops_format must be 'jpg' or 'png'")
+    if crops_format == "png" and crops_encode == "gpu-entropy":
+        raise ValueError("crops_format='png' has no crops_encode='gpu-entropy' form: the PNG writer's codes are built on the host")
+    if ragged or ragged_outputs or ragged_png:
+        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool, ragged_outputs=ragged_outputs, ragged=ragged, ragged_png=ragged_png)
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
                         entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste, crops_encode=crops_encode,
-                        ragged_outputs=ragged_outputs)
+                        ragged_outputs=ragged_outputs, crops_format=crops_format, ragged_png=ragged_png)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -788,6 +847,11 @@ def build_parser():
     ap.add_argument('--ragged-outputs', action='store_true',
                     help="with --ragged and --decode gpu / gpu-entropy: --encode gpu / gpu-entropy and --crops take the ragged batches too "
                          "(ctpn_write_annotated_files_ragged, ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged); same files")
+    ap.add_argument('--crops-format', default='jpg', choices=['jpg', 'png'],
+                    help="with --crops: 'png' = lossless <stem>_<k>.png crops (--crops-encode gpu: ctpn_write_line_crops_png; not with gpu-entropy)")
+    ap.add_argument('--ragged-png', action='store_true',
+                    help="with --ragged --ragged-outputs --png-encode gpu: the PNG files share ragged batches too and are written from their "
+                         "canvases (ctpn_write_annotated_png_files_ragged); same names, same pixels")
     ap.add_argument('--ragged-waste', type=float, default=RAGGED_WASTE, help="padded share of a ragged batch's rows at most")
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
@@ -820,7 +884,7 @@ def main(argv=None):
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
         decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height, crops_encode=args.crops_encode,
         params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)), ragged=args.ragged, ragged_waste=args.ragged_waste,
-        ragged_outputs=args.ragged_outputs)
+        ragged_outputs=args.ragged_outputs, crops_format=args.crops_format, ragged_png=args.ragged_png)
     net.close()
 
 

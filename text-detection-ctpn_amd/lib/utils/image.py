@@ -121,6 +121,18 @@ def imwrite_annotated_ragged(ctx, paths, canvas, heights, recs, scales, quality=
                                      quality=quality, entropy=entropy)
 
 
+def imencode_png_mixed(ctx, images):
+    """cv2.imencode('.png', img) for a list of BGR uint8 images of ANY mix of sizes in one call, on the GPU (ctpn_encode_png_mixed) -> list of
+    bytes objects, each byte-equal to imencode_png_batch of that image alone."""
+    return ctx.encode_png_mixed(images)
+
+
+def imwrite_annotated_png_ragged(ctx, paths, canvas, heights, recs, scales, device_ptr=None, shape=None):
+    """imwrite_annotated_ragged for PNG-named files (ctpn_write_annotated_png_files_ragged): lossless, image i byte-equal to the uniform PNG
+    writer's file of that image alone. canvas: (n, hc, w, 3) on the host (PNG files are decoded there), or device_ptr + shape."""
+    ctx.write_annotated_png_files_ragged(images=canvas, device_ptr=device_ptr, shape=shape, heights=heights, recs=recs, scales=scales, paths=list(paths))
+
+
 def crop_text_lines(ctx, images, recs, line_counts=None, crop_h=32, max_w=512, pad_value=0, device_ptr=None, shape=None):
     """The detected text lines of a batch as rectified images of height crop_h, one per line, for a recogniser -- cut out on the GPU
     (ctpn_crop_lines): the quadrilateral of every record mapped bilinearly onto crop_h x width pixels with cv2.resize's INTER_LINEAR uint8

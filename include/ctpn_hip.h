@@ -435,6 +435,34 @@ int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const fl
 int ctpn_debug_bilstm(int device_id, const float* pre, const float* wh, int rows, int T, int split, int fast_gates, int pre_f16, float* out,
                       int* form_out);
 int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* bias, int M, int K, int Co, int ldc, int in_precision, float* out);
+/* The proposal layer's kernels alone (test hooks): decode_kernel -> radix_sort_kernel (+ merge_rank_kernel) -> gather_kernel -> one of three NMS forms.
+ * Key order: ascending key = descending score, equal scores by ascending anchor index; the key orders the score's BITS, so -0.0 ranks below
+ *   +0.0 where a float comparison calls the two a tie (softmax never produces -0.0; only ctpn_proposals_from_host can hand one in).
+ * ctpn_debug_proposal_plan: what a ctpn_proposals* call launches -- the function the call itself computes once and follows (csrc/api_proposals.hip).
+ *   Pure host arithmetic, no device. For options nms_columns / nms_prefix, a ctx with (mw_scratch = 1) or without the multi-workgroup NMS's
+ *   scratch, n images and every map hf_first .. + hf_count - 1 x wf_first .. + wf_count - 1; im_widths: the n im_info widths (NULL: no image is
+ *   narrower than its map). plans[hf_count][wf_count][CTPN_PROPOSAL_PLAN_INTS]:
+ *   [0] npad, keys per image in the key buffers   [1] 1 = fill_keys_kernel pads the keys behind the image's anchors
+ *   [2] sort: 0 one workgroup per image, 1 segmented (eight workgroups + merge_rank_kernel)   [3] keys per sort workgroup   [4] keys of the last one
+ *   [5] merge_rank_kernel workgroups per image (0: none)   [6] NMS: 0 generic (nms_kernel), 1 column form on one workgroup per image, 2 column groups
+ *   [7] column-group workgroups per image (0 in the other forms)   [8] prefix pass: 0 none, 1 inside the kernel, 2 a prefix and a full launch
+ * ctpn_debug_proposal_fetch: one intermediate of the ctx's LAST ctpn_proposals / ctpn_proposals_from_host call (n images, per_img = hf x wf x 10
+ *   anchors, pre / post its top-N), copied to the host; synchronises the ctx's streams and reads only. CTPN_ERR_CAPACITY below the size given here:
+ *   CTPN_PF_BOXES4 n x per_img x 4 fp32 | SORTED_KEYS n x npad uint64, the buffer the gather read | SORTED_BOXES n x pre x 4 fp32 | SORTED_SCORES
+ *   n x pre fp32 | SORTED_ANCHOR n x pre int32 (rows of the three at and behind VALID_COUNTS[i] are stale) | VALID_COUNTS n int32 | COLID n x pre
+ *   bytes (CTPN_ERR_STATE unless plan [6] was 2) | KEEP_IDX n x post int32 | KEEP_COUNTS n int32 | MW_SCRATCH n x 2048 bytes, zero between calls.
+ * ctpn_debug_sort_keys: launch_sort_keys alone. keys: n_img x per_img; out: n_img x npad (npad = per_img rounded up to a power of two), the buffer
+ *   that holds the result. Both device buffers are CTPN_SORT_POISON (a key that reads as valid) wherever the caller's keys are not, and followed
+ *   by a guard row (a changed guard byte: CTPN_ERR_STATE). The one-workgroup form leaves [per_img, npad) alone (poison comes back); the segmented
+ *   form (segmented = 1; outside up to 4 images of 4097 .. 32768 keys: CTPN_ERR_ARG) pads it with invalid keys (all ones). */
+#define CTPN_PROPOSAL_PLAN_INTS 9
+#define CTPN_SORT_POISON 0x00000000C3C3C3C3ull
+enum { CTPN_PF_BOXES4 = 0, CTPN_PF_SORTED_KEYS, CTPN_PF_SORTED_BOXES, CTPN_PF_SORTED_SCORES, CTPN_PF_SORTED_ANCHOR, CTPN_PF_VALID_COUNTS, CTPN_PF_COLID,
+       CTPN_PF_KEEP_IDX, CTPN_PF_KEEP_COUNTS, CTPN_PF_MW_SCRATCH };
+int ctpn_debug_proposal_plan(int nms_columns, int nms_prefix, int mw_scratch, int n, int hf_first, int hf_count, int wf_first, int wf_count,
+                             int pre_nms_topn, int post_nms_topn, float nms_thresh, const float* im_widths, int* plans);
+int ctpn_debug_proposal_fetch(ctpn_ctx* ctx, int what, void* out, size_t capacity_bytes);
+int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_img, int per_img, int segmented, unsigned long long* out);
 /* TextDetector.detect (lib/text_connector/detectors.py:19-49) for ONE image with every step on the device -- score > 0.7 prefix and
  * boxes / scale (lines_prep_kernel), NMS 0.2 (nms_kernel), graph build / chains / line fit / filter_boxes (connect_kernel) -- i.e.
  * the device-connector form of the asynchronous detect path (option connect_device = 1). rois: r x 5 fp32 [score,x1,y1,x2,y2] in

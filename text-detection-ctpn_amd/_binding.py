@@ -119,6 +119,10 @@ def _declare(lib):
         "ctpn_debug_lstm_pre": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
         "ctpn_debug_bilstm": (C.c_int, [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, i32p]),
         "ctpn_debug_gemm": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+        "ctpn_debug_proposal_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                               f32p, i32p]),
+        "ctpn_debug_proposal_fetch": (C.c_int, [vp, C.c_int, C.c_void_p, C.c_size_t]),
+        "ctpn_debug_sort_keys": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
         "ctpn_jpeg_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_jpeg_coef_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_decode": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint16), i32p]),
@@ -786,6 +790,52 @@ def debug_gemm(a, w, bias, ldc=None, precision="fp32", device_id=0):
     return out
 
 
+ProposalPlan = collections.namedtuple("ProposalPlan", "npad fill_keys sort seg_len last_seg merge_wgs nms group_wgs prefix")
+PROPOSAL_SORT_FORMS = ("one_wg", "segmented")
+PROPOSAL_NMS_FORMS = ("generic", "one_wg", "groups")
+PROPOSAL_PREFIX = ("none", "in_kernel", "two_launches")
+SORT_POISON = 0x00000000C3C3C3C3
+KEY_INVALID = 0xFFFFFFFFFFFFFFFF
+# ctpn_debug_proposal_fetch: name -> (CTPN_PF_*, dtype, shape of one image from (per_img, npad, pre, post))
+PROPOSAL_FETCH = {
+    "boxes4": (0, np.float32, lambda a, p, pre, post: (a, 4)), "sorted_keys": (1, np.uint64, lambda a, p, pre, post: (p,)),
+    "sorted_boxes": (2, np.float32, lambda a, p, pre, post: (pre, 4)), "sorted_scores": (3, np.float32, lambda a, p, pre, post: (pre,)),
+    "sorted_anchor": (4, np.int32, lambda a, p, pre, post: (pre,)), "valid_counts": (5, np.int32, lambda a, p, pre, post: ()),
+    "colid": (6, np.uint8, lambda a, p, pre, post: (pre,)), "keep_idx": (7, np.int32, lambda a, p, pre, post: (post,)),
+    "keep_counts": (8, np.int32, lambda a, p, pre, post: ()), "mw_scratch": (9, np.uint8, lambda a, p, pre, post: (2048,)),
+}
+
+
+def proposal_plan_sweep(n, hf_first, hf_count, wf_first, wf_count, pre=12000, post=1000, thresh=0.7, nms_columns=1, nms_prefix=1, mw_scratch=True,
+                        im_widths=None):
+    """ctpn_debug_proposal_plan over a block of maps: int32 (hf_count, wf_count, 9), the raw plan of every map. No device."""
+    out = np.zeros((hf_count, wf_count, 9), np.int32)
+    w = None if im_widths is None else _f32(im_widths).reshape(n)
+    _check(load_library().ctpn_debug_proposal_plan(int(nms_columns), int(nms_prefix), 1 if mw_scratch else 0, int(n), int(hf_first), int(hf_count),
+                                                   int(wf_first), int(wf_count), int(pre), int(post), float(thresh),
+                                                   None if w is None else _ptr(w, C.c_float), _ptr(out, C.c_int)))
+    return out
+
+
+def proposal_plan(n, hf, wf, **kw):
+    """The plan of one ctpn_proposals* call as a ProposalPlan of names and numbers (see ctpn_debug_proposal_plan)."""
+    p = [int(v) for v in proposal_plan_sweep(n, hf, 1, wf, 1, **kw)[0, 0]]
+    return ProposalPlan(p[0], bool(p[1]), PROPOSAL_SORT_FORMS[p[2]], p[3], p[4], p[5], PROPOSAL_NMS_FORMS[p[6]], p[7], PROPOSAL_PREFIX[p[8]])
+
+
+def debug_sort_keys(keys, segmented, device_id=0):
+    """ctpn_debug_sort_keys: keys (n_img, per_img) uint64 -> (n_img, npad) uint64, the buffer that holds launch_sort_keys' result (behind per_img:
+    SORT_POISON in the one-workgroup form, KEY_INVALID in the segmented one)."""
+    k = np.ascontiguousarray(keys, np.uint64)
+    n_img, per_img = k.shape
+    npad = 1
+    while npad < per_img:
+        npad <<= 1
+    out = np.zeros((n_img, npad), np.uint64)
+    _check(load_library().ctpn_debug_sort_keys(int(device_id), _ptr(k, C.c_ulonglong), n_img, per_img, 1 if segmented else 0, _ptr(out, C.c_ulonglong)))
+    return out
+
+
 class Context:
     """One ctpn_ctx: a GPU, a stream and the HBM arena for up to max_batch images of max_h x max_w."""
 
@@ -968,6 +1018,17 @@ class Context:
                                         float(nms_thresh), float(min_size), _ptr(rois, C.c_float), _ptr(counts, C.c_int)))
         out = [rois[i, : counts[i]].copy() for i in range(n)]
         return (out, self._anchors(n, post_nms_topn, counts)) if want_anchors else out
+
+    def proposal_fetch(self, what, n, hf, wf, pre_nms_topn, post_nms_topn):
+        """ctpn_debug_proposal_fetch: intermediate `what` (a PROPOSAL_FETCH name) of the LAST proposals call, whose shapes the caller restates."""
+        code, dt, shape = PROPOSAL_FETCH[what]
+        per_img = hf * wf * 10
+        npad = 1
+        while npad < per_img:
+            npad <<= 1
+        out = np.zeros((n,) + shape(per_img, npad, int(pre_nms_topn), int(post_nms_topn)), dt)
+        _check(self._lib.ctpn_debug_proposal_fetch(self._h, code, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        return out
 
     def proposals_from_host(self, cls_prob, bbox_pred, im_info, pre_nms_topn=12000, post_nms_topn=1000,
                             nms_thresh=0.7, min_size=8.0, want_anchors=False):

@@ -1,5 +1,6 @@
 // C ABI of libctpn_hip.so, test hooks: ctpn_debug_* entry points that run one kernel on caller-supplied data, everything on the null stream.
 // Not on the product path.
+#include <algorithm>
 #include "ctx.h"
 #include "conv3x3_plan.h"
 
@@ -378,6 +379,92 @@ int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* 
   for (int m = 0; m < M; ++m)
     if (ldc > Co && !dbg_fill_intact((const char*)(out + (size_t)m * ldc + Co), (size_t)(ldc - Co) * 4))
       return fail(CTPN_ERR_STATE, "ctpn_debug_gemm: a pad column (Co .. ldc - 1) was written");
+  return CTPN_OK;
+}
+
+// ---- the proposal layer's kernels alone ------------------------------------------------------------------------
+int ctpn_debug_proposal_plan(int nms_columns, int nms_prefix, int mw_scratch, int n, int hf_first, int hf_count, int wf_first, int wf_count,
+                             int pre_nms_topn, int post_nms_topn, float nms_thresh, const float* im_widths, int* plans) {
+  if (!plans || hf_count <= 0 || wf_count <= 0) return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_plan: no output");
+  if (n <= 0 || n > 4096 || hf_first <= 0 || wf_first <= 0 || hf_first > 8192 - hf_count || wf_first > 8192 - wf_count || pre_nms_topn <= 0 || post_nms_topn <= 0)
+    return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_plan: n 1 .. 4096, maps up to 8191 x 8191, positive top-N");
+  if ((long long)(hf_first + hf_count - 1) * (wf_first + wf_count - 1) * 10 > (1 << 30)) return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_plan: more than 2^30 anchors per image");
+  std::vector<float> rows;
+  if (im_widths) { rows.assign((size_t)n * 3, 0.f); for (int i = 0; i < n; ++i) rows[3 * i + 1] = im_widths[i]; }
+  for (int a = 0; a < hf_count; ++a)
+    for (int b = 0; b < wf_count; ++b) {
+      const ProposalPlan p = proposal_plan(nms_columns, nms_prefix, mw_scratch != 0, n, hf_first + a, wf_first + b, pre_nms_topn, post_nms_topn, nms_thresh,
+                                           im_widths ? rows.data() : nullptr);
+      int* o = plans + ((size_t)a * wf_count + b) * CTPN_PROPOSAL_PLAN_INTS;
+      o[0] = p.npad; o[1] = p.fill_keys; o[2] = p.sort_form; o[3] = p.seg_len; o[4] = p.last_seg; o[5] = p.merge_wgs; o[6] = p.nms_form; o[7] = p.group_wgs;
+      o[8] = p.prefix_launches;
+    }
+  return CTPN_OK;
+}
+
+int ctpn_debug_proposal_fetch(ctpn_ctx* c, int what, void* out, size_t capacity_bytes) {
+  if (!c || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_fetch: null pointer");
+  if (c->last_prop_n <= 0) return fail(CTPN_ERR_STATE, "ctpn_debug_proposal_fetch: no ctpn_proposals / ctpn_proposals_from_host call yet");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  const ProposalPlan& p = c->last_plan;
+  const size_t n = (size_t)c->last_prop_n, per_img = (size_t)c->last_hf * c->last_wf * 10, pre = (size_t)c->last_pre, post = (size_t)c->last_post;
+  const void* src = nullptr;
+  size_t row = 0, pitch = 0;      // bytes per image handed out, and between the images on the device
+  switch (what) {
+    case CTPN_PF_BOXES4: src = c->boxes4; row = pitch = per_img * 16; break;
+    case CTPN_PF_SORTED_KEYS: src = p.sort_form == PP_SORT_SEGMENTED ? c->keys_tmp : c->keys; row = pitch = (size_t)p.npad * 8; break;
+    case CTPN_PF_SORTED_BOXES: src = c->sorted_boxes; row = pitch = pre * 16; break;
+    case CTPN_PF_SORTED_SCORES: src = c->sorted_scores; row = pitch = pre * 4; break;
+    case CTPN_PF_SORTED_ANCHOR: src = c->sorted_anchor; row = pitch = pre * 4; break;
+    case CTPN_PF_VALID_COUNTS: src = c->valid_counts; row = pitch = 4; break;
+    case CTPN_PF_COLID:
+      if (p.nms_form != PP_NMS_COLUMN_GROUPS) return fail(CTPN_ERR_STATE, "ctpn_debug_proposal_fetch: the last call wrote no column ids (not the multi-workgroup NMS)");
+      src = c->nms_colid; row = pre; pitch = (pre + 15) & ~(size_t)15; break;
+    case CTPN_PF_KEEP_IDX: src = c->keep_idx; row = post * 4; pitch = (size_t)c->topn_max * 4; break;
+    case CTPN_PF_KEEP_COUNTS: src = c->keep_counts; row = pitch = 4; break;
+    case CTPN_PF_MW_SCRATCH:
+      if (!c->nms_mw_scratch || n > (size_t)NMS_MW_CAP_BATCH) return fail(CTPN_ERR_STATE, "ctpn_debug_proposal_fetch: no multi-workgroup scratch for that many images");
+      src = c->nms_mw_scratch; row = pitch = NMS_MW_SCRATCH_BYTES; break;
+    default: return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_fetch: unknown intermediate");
+  }
+  if (capacity_bytes < n * row) return fail(CTPN_ERR_CAPACITY, "ctpn_debug_proposal_fetch: the intermediate takes " + std::to_string(n * row) + " bytes");
+  CTPN_HIP_TRY(hipMemcpy2D(out, row, src, pitch, row, n, hipMemcpyDeviceToHost));
+  return CTPN_OK;
+}
+
+int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_img, int per_img, int segmented, unsigned long long* out) {
+  if (!keys || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_sort_keys: null pointer");
+  if (n_img <= 0 || n_img > 64 || per_img <= 0 || per_img > (1 << 20)) return fail(CTPN_ERR_ARG, "ctpn_debug_sort_keys: 1 .. 64 images of 1 .. 2^20 keys");
+  if (segmented && !sort_is_segmented(n_img, per_img))
+    return fail(CTPN_ERR_ARG, "ctpn_debug_sort_keys: the segmented form takes up to 4 images of 4097 .. 32768 keys");
+  if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_sort_keys: no HIP device visible (no CPU fallback)");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  const size_t npad = (size_t)next_pow2(per_img), total = (size_t)n_img * npad, guard = npad;
+  // both buffers: the caller's keys (first buffer only), everything else CTPN_SORT_POISON, a key that reads as VALID; then a guard row of fill bytes
+  std::vector<unsigned long long> h0(total, CTPN_SORT_POISON), h1(total);
+  for (int i = 0; i < n_img; ++i) std::memcpy(&h0[(size_t)i * npad], keys + (size_t)i * per_img, (size_t)per_img * 8);
+  DevBufs bufs;
+  void *d0 = nullptr, *d1 = nullptr;
+  int rc;
+  if ((rc = bufs.alloc(&d0, (total + guard) * 8)) || (rc = bufs.alloc(&d1, (total + guard) * 8))) return rc;
+  CTPN_HIP_TRY(hipMemset(d0, DBG_FILL, (total + guard) * 8));
+  CTPN_HIP_TRY(hipMemset(d1, DBG_FILL, (total + guard) * 8));
+  CTPN_HIP_TRY(hipMemcpy(d0, h0.data(), total * 8, hipMemcpyHostToDevice));
+  std::fill(h1.begin(), h1.end(), CTPN_SORT_POISON);
+  CTPN_HIP_TRY(hipMemcpy(d1, h1.data(), total * 8, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipDeviceSynchronize());
+  int in_tmp = 0;
+  if ((rc = launch_sort_keys((unsigned long long*)d0, (unsigned long long*)d1, n_img, (int)npad, per_img, nullptr, segmented ? &in_tmp : nullptr))) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_sort_keys: kernel failed");
+  if (in_tmp != (segmented ? 1 : 0)) return fail(CTPN_ERR_STATE, "ctpn_debug_sort_keys: the sort did not take the form asked for");
+  std::vector<char> g(guard * 8);
+  for (void* d : {d0, d1}) {
+    CTPN_HIP_TRY(hipMemcpy(g.data(), (const char*)d + total * 8, guard * 8, hipMemcpyDeviceToHost));
+    if (!dbg_fill_intact(g.data(), guard * 8)) return fail(CTPN_ERR_STATE, "ctpn_debug_sort_keys: a guard row behind a key buffer was written");
+  }
+  CTPN_HIP_TRY(hipMemcpy(out, in_tmp ? d1 : d0, total * 8, hipMemcpyDeviceToHost));
   return CTPN_OK;
 }
 

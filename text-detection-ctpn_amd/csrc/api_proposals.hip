@@ -35,6 +35,31 @@ int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, cons
   return CTPN_OK;
 }
 
+// Every launch decision of the proposal layer, in one place: enqueue_proposals_impl computes this once and follows it. The conditions
+// themselves stay with their kernels (sort_is_segmented / sort_seg_len, nms_columns_ok, nms_multi_wg_ok, nms_prefix_launches).
+ProposalPlan proposal_plan(int nms_columns, int nms_prefix, bool has_mw_scratch, int n, int hf, int wf, int pre_nms_topn, int post_nms_topn,
+                           float nms_thresh, const float* im_info) {
+  ProposalPlan p{};
+  const int per_img = hf * wf * 10;
+  p.npad = next_pow2(per_img);
+  const bool seg_sort = !(nms_columns == 2 || nms_columns == 0);      // options 0 / 2 pin the one-workgroup forms of sort and NMS
+  p.sort_form = seg_sort && sort_is_segmented(n, per_img) ? PP_SORT_SEGMENTED : PP_SORT_ONE_WG;
+  // (the segmented sort of small batches never reads behind the image's keys and pads its merged buffer itself)
+  p.fill_keys = p.npad > per_img && p.sort_form != PP_SORT_SEGMENTED;
+  p.seg_len = p.sort_form == PP_SORT_SEGMENTED ? sort_seg_len(per_img) : per_img;
+  p.last_seg = p.sort_form == PP_SORT_SEGMENTED ? per_img - (per_img - 1) / p.seg_len * p.seg_len : per_img;
+  p.merge_wgs = p.sort_form == PP_SORT_SEGMENTED ? sort_merge_workgroups(per_img) : 0;
+  const bool cols = nms_columns && nms_columns_ok(wf, pre_nms_topn, nms_thresh);
+  bool mw = cols && nms_multi_wg_ok(has_mw_scratch, nms_columns, n, hf);
+  // boxes whose x was clipped onto the image's last pixel column (im_info narrower than the feature map: only ctpn_proposals_from_host can
+  // say so) pile up in ONE column group, which may then exceed the multi-workgroup kernel's list: those calls keep the one-workgroup form
+  for (int i = 0; im_info && i < n; ++i) mw = mw && im_info[3 * i + 1] >= (float)((wf - 1) * 16 + 1);
+  p.nms_form = !cols ? PP_NMS_GENERIC : (mw ? PP_NMS_COLUMN_GROUPS : PP_NMS_ONE_WG);
+  p.group_wgs = mw ? nms_column_group_workgroups(wf) : 0;
+  p.prefix_launches = cols ? nms_prefix_launches(mw, nms_prefix ? NMS_PREFIX_RANKS : 0, pre_nms_topn, post_nms_topn) : 0;
+  return p;
+}
+
 static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are_probs, int n, int hf, int wf, const float* im_info,
                                   int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, hipStream_t s, hipEvent_t ev_decoded,
                                   const int* valid_rows_dev) {
@@ -43,23 +68,23 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
   if (pre_nms_topn <= 0 || pre_nms_topn > c->topn_max) return fail(CTPN_ERR_CAPACITY, "proposals: pre_nms_topn must be in 1..12000");
   if (post_nms_topn <= 0 || post_nms_topn > c->post_max) return fail(CTPN_ERR_CAPACITY, "proposals: post_nms_topn must be in 1..1000");
   const int per_img = hf * wf * 10;
-  const int npad = next_pow2(per_img);
+  const ProposalPlan plan = proposal_plan(c->nms_columns, c->nms_prefix, c->nms_mw_scratch != nullptr, n, hf, wf, pre_nms_topn, post_nms_topn, nms_thresh, im_info);
+  const int npad = plan.npad;
   if (npad > c->npad_max) return fail(CTPN_ERR_CAPACITY, "proposals: feature map larger than the ctx was created for");
   if (n > 4) CTPN_HIP_TRY(hipMemcpyAsync(c->im_info_dev, im_info, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s));      // (<= 4: in decode_kernel's arguments)
   ProposalCfg pc{n, hf, wf, pre_nms_topn, post_nms_topn, nms_thresh, min_size};
   int rc;
-  bool mw = nms_multi_wg(c, n, hf) && nms_columns_ok(wf, pre_nms_topn, nms_thresh);
+  const bool mw = plan.nms_form == PP_NMS_COLUMN_GROUPS, seg_sort = plan.sort_form == PP_SORT_SEGMENTED;
   if (c->nms_mw_scratch && c->nms_mw_dirty) {
     // in stream order in front of everything that follows; both streams that ever use the block are drained by whoever set the flag
     CTPN_HIP_TRY(hipMemsetAsync(c->nms_mw_scratch, 0, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, s));
     c->nms_mw_dirty = false;
   }
-  const bool seg_sort = !(c->nms_columns == 2 || c->nms_columns == 0);      // options 0 / 2 pin the one-workgroup forms of sort and NMS
   const double nanch = (double)n * per_img;
   {
     Timed t(c, CTPN_KIND_DECODE, nanch * (60.0 * 4 / 10 + 8 + 16), s);
     if ((rc = launch_decode(heads, 64, heads_are_probs, c->cls_in, c->bbox_in, c->im_info_dev, heads_are_probs ? nullptr : c->cls_prob,
-                            heads_are_probs ? nullptr : c->bbox_pred, c->keys, c->boxes4, pc, npad, s, seg_sort && sort_is_segmented(n, per_img), n <= 4 ? im_info : nullptr, valid_rows_dev))) return rc;
+                            heads_are_probs ? nullptr : c->bbox_pred, c->keys, c->boxes4, pc, npad, s, !plan.fill_keys, n <= 4 ? im_info : nullptr, valid_rows_dev))) return rc;
   }
   if (ev_decoded) CTPN_HIP_TRY(hipEventRecord(ev_decoded, s));
   {
@@ -67,9 +92,7 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
     int in_tmp = 0;
     if ((rc = launch_sort_keys(c->keys, c->keys_tmp, n, npad, per_img, s, seg_sort ? &in_tmp : nullptr))) return rc;
     const unsigned long long* sorted_keys = in_tmp ? c->keys_tmp : c->keys;
-    // boxes whose x was clipped onto the image's last pixel column (im_info narrower than the feature map: only ctpn_proposals_from_host can
-    // say so) pile up in ONE column group, which may then exceed the multi-workgroup kernel's list: those calls keep the one-workgroup form
-    for (int i = 0; i < n; ++i) mw = mw && im_info[3 * i + 1] >= (float)((wf - 1) * 16 + 1);
+    if (in_tmp != (seg_sort ? 1 : 0)) return fail(CTPN_ERR_STATE, "proposals: the sort did not take the planned form");
     if ((rc = launch_gather_sorted(sorted_keys, c->boxes4, c->sorted_boxes, c->sorted_scores, c->sorted_anchor, c->valid_counts, n, npad, per_img, pre_nms_topn, s,
                                    mw ? c->nms_colid : nullptr, wf))) return rc;
   }
@@ -84,12 +107,12 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
   }
   {
     Timed t(c, CTPN_KIND_NMS, (double)n * pre_nms_topn * 24.0, s);
-    if (c->nms_columns && nms_columns_ok(wf, pre_nms_topn, nms_thresh)) {
+    if (plan.nms_form != PP_NMS_GENERIC) {
       // 16 waves per image (a 4-wave footprint that co-resides with the persistent convolutions took 1.9 ms instead of 0.66 ms and slowed
       // conv1_2 by 8 % through the shared SIMDs in round 2: removed)
       if ((rc = launch_nms_columns(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, c->keep_idx,
                                    c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, wf, s, c->sorted_anchor, c->roi_anchor, nullptr,
-                                   mw ? c->nms_mw_scratch : nullptr, mw ? c->nms_colid : nullptr, c->nms_prefix ? 4096 : 0, c->debug_nms))) return rc;
+                                   mw ? c->nms_mw_scratch : nullptr, mw ? c->nms_colid : nullptr, c->nms_prefix ? NMS_PREFIX_RANKS : 0, c->debug_nms))) return rc;
       if (c->nms_check) {
         // option "nms_check" (debug; synchronises the stream): the column decomposition presumes boxes on the 16-px anchor grid (common.h)
         std::vector<int> k1((size_t)n * c->topn_max), c1(n);
@@ -103,6 +126,7 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
                                 c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, s, c->sorted_anchor, c->roi_anchor))) return rc;
   }
   c->last_post = post_nms_topn; c->last_prop_n = n;
+  c->last_plan = plan; c->last_hf = hf; c->last_wf = wf; c->last_pre = pre_nms_topn;
   if (!heads_are_probs) c->proposals_done = true;
   return CTPN_OK;
 }

@@ -267,6 +267,8 @@ int launch_decode(const float* heads, int head_ld, int heads_are_probs, const fl
                   const float* im_info_host = nullptr /* n <= 4: the rows travel in the kernel arguments and decode_kernel writes im_info_dev itself */,
                   const int* valid_rows_dev = nullptr /* ragged batch: feature rows of every image; cells below them get KEY_INVALID */);
 bool sort_is_segmented(int n_img, int per_img);      // will launch_sort_keys(..., in_tmp != nullptr) take the segmented form?
+int sort_seg_len(int per_img);                        // ... with segments of this many keys (the last one holds the rest); sort_keys.hip
+int sort_merge_workgroups(int per_img);               // ... and this many merge_rank_kernel workgroups per image
 // stable radix sort of the first per_img keys of every npad-strided segment (tmp: same size as keys)
 // in_tmp != nullptr allows the segmented form for small batches; *in_tmp says which buffer holds the sorted keys afterwards
 int launch_sort_keys(unsigned long long* keys, unsigned long long* tmp, int n_img, int npad, int per_img, hipStream_t s, int* in_tmp = nullptr);
@@ -306,6 +308,33 @@ constexpr size_t NMS_MW_FLAG_OFF = 2032;            // prefix pass: "the prefix 
 constexpr int NMS_MW_MAX_BATCH = 4;                 // batches up to this size spread their columns over the machine; larger ones fill it with images
 constexpr int NMS_MW_CAP_BATCH = 32;                // ... unless option nms_columns = 3 asks for the multi-workgroup form explicitly: buffers are sized for this many images
 bool nms_columns_ok(int ncols, int stride, float thresh);
+// the multi-workgroup form for the proposal layer? nms_columns: the option; hf: rows of the feature map (a column holds hf x 10 candidates at most,
+// the kernel's list 1024), 0 for the connector's <= 1024 boxes
+static inline bool nms_multi_wg_ok(bool has_scratch, int nms_columns, int n, int hf) {
+  return has_scratch && hf * 10 <= 1024 && ((nms_columns == 3 && n <= NMS_MW_CAP_BATCH) || (nms_columns == 1 && n <= NMS_MW_MAX_BATCH));
+}
+// prefix launches of launch_nms_columns (proposal variant): 0 = one full pass, 1 = the one-workgroup kernel tries `prefix` ranks first, 2 = a prefix
+// launch and a full launch of the multi-workgroup kernel; nms.hip
+int nms_prefix_launches(bool multi_wg, int prefix, int stride, int max_keep);
+int nms_column_group_workgroups(int ncols);           // workgroups per image of the multi-workgroup form
+constexpr int NMS_PREFIX_RANKS = 4096;                // option nms_prefix: the ranks the prefix pass looks at
+
+// What one proposal-layer call launches: computed once by enqueue_proposals (api_proposals.hip), which then follows it; host arithmetic only
+// (ctpn_debug_proposal_plan hands it out). im_info: the images' rows [h, w, scale], of which the widths count (null: every image is as wide as the map).
+enum { PP_SORT_ONE_WG = 0, PP_SORT_SEGMENTED = 1 };
+enum { PP_NMS_GENERIC = 0, PP_NMS_ONE_WG = 1, PP_NMS_COLUMN_GROUPS = 2 };
+struct ProposalPlan {
+  int npad;                 // keys per image in the key buffers
+  int fill_keys;            // fill_keys_kernel pads the keys behind the image's anchors (else merge_rank_kernel pads the merged buffer)
+  int sort_form;            // PP_SORT_*
+  int seg_len, last_seg;    // keys per sort workgroup, and of the image's last one (one workgroup: both per_img)
+  int merge_wgs;            // merge_rank_kernel workgroups per image (0: no merge)
+  int nms_form;             // PP_NMS_*
+  int group_wgs;            // nms_column_groups_kernel workgroups per image (0 in the other forms)
+  int prefix_launches;      // nms_prefix_launches
+};
+ProposalPlan proposal_plan(int nms_columns, int nms_prefix, bool has_mw_scratch, int n, int hf, int wf, int pre_nms_topn, int post_nms_topn,
+                           float nms_thresh, const float* im_info);
 int launch_hog(unsigned* sink, int n_wg, int usec, int touch, hipStream_t s, const void* src = nullptr, size_t src_bytes = 0);      // diagnostic: the one-workgroup NMS's footprint without its work (hog.hip)
 bool nms_columns_tl_ok(int ncols, int stride, float thresh, float max_scale);
 

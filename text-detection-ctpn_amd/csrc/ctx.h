@@ -324,6 +324,7 @@ struct ctpn_ctx {
   int* sorted_anchor = nullptr;      // [n][12000] anchor index of every sorted row
   int* roi_anchor = nullptr;         // [n][1000]  anchor index of every roi (second return of proposal_layer)
   int last_post = 0, last_prop_n = 0;
+  ProposalPlan last_plan{}; int last_hf = 0, last_wf = 0, last_pre = 0;      // the last proposals call, for ctpn_debug_proposal_fetch
   float* im_info_dev = nullptr;
   char* out_pack = nullptr; size_t pack_bytes = 0;      // tl_boxes, tl_scores, tl_keep, tl_keep_counts, rois, keep_counts live here (pack_layout)
   float* tl_boxes = nullptr; float* tl_scores = nullptr; int* tl_counts = nullptr;  // connector front end
@@ -392,7 +393,7 @@ static inline size_t act_front_pixels(int w) { return (size_t)(w + 2) + 64; }   
 // pins one form for A/B runs and the tests
 // hf: rows of the feature map (a column holds hf x 10 candidates at most, the kernel's list 1024), 0 for the connector's <= 1024 boxes
 static inline bool nms_multi_wg(const ctpn_ctx* c, int n, int hf) {
-  return c->nms_mw_scratch && hf * 10 <= 1024 && ((c->nms_columns == 3 && n <= NMS_MW_CAP_BATCH) || (c->nms_columns == 1 && n <= NMS_MW_MAX_BATCH));
+  return nms_multi_wg_ok(c->nms_mw_scratch != nullptr, c->nms_columns, n, hf);
 }
 
 // a ctx-owned device buffer that grows to the largest size asked for (the output stages: api_out_stage.hip, the writers, api_crops.hip). Their calls return

@@ -554,6 +554,14 @@ __global__ __launch_bounds__(MW_WAVES * 64) void nms_column_groups_kernel(
   if (tid == 0) *(unsigned*)(blk + MW_TICKET_OFF) = 0u;
 }
 
+int nms_column_group_workgroups(int ncols) { return (ncols + MW_WAVES - 1) / MW_WAVES; }
+// the multi-workgroup form answers from a prefix launch only where the full launch behind it has more ranks to look at; the one-workgroup kernel
+// takes the prefix as an argument and decides on the image's count
+int nms_prefix_launches(bool multi_wg, int prefix, int stride, int max_keep) {
+  if (!(prefix > 0 && max_keep < prefix)) return 0;
+  return multi_wg ? (prefix < stride ? 2 : 0) : 1;
+}
+
 // col_scale (im_info rows [h, w, scale], nullable) selects the connector's variant (stride <= 1024, 4 waves).
 // PRECONDITION: boxes on the 16-px anchor grid (common.h); arbitrary boxes must go through launch_nms.
 int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, const int* counts_in, int stride, float thresh, int max_keep,
@@ -568,9 +576,9 @@ int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, co
     // colid: gather_kernel's column byte per rank, row pitch = stride rounded up to 16 -- null: the columns come from the boxes, <= 1024 of them)
     if (!colid && stride > MW_LIST) return fail(CTPN_ERR_ARG, "nms_columns: the multi-workgroup form needs column ids for more than 1024 candidates");
     const int maxn = col_scale ? NC_TL_MAXN : NC_MAXN;
-    const bool two = prefix > 0 && prefix < stride && max_keep < prefix;       // a prefix launch, then the full one that usually finds nothing to do
+    const bool two = nms_prefix_launches(true, prefix, stride, max_keep) == 2;       // a prefix launch, then the full one that usually finds nothing to do
     for (int stage = two ? 1 : 0; stage <= (two ? 2 : 0); ++stage)
-      hipLaunchKernelGGL(nms_column_groups_kernel, dim3((ncols + MW_WAVES - 1) / MW_WAVES, n_img), dim3(MW_WAVES * 64), 0, s, sorted_boxes, sorted_scores,
+      hipLaunchKernelGGL(nms_column_groups_kernel, dim3(nms_column_group_workgroups(ncols), n_img), dim3(MW_WAVES * 64), 0, s, sorted_boxes, sorted_scores,
                          colid, (stride + 15) & ~15, counts_in, stride, thresh, max_keep, keep_idx, keep_stride, keep_counts, rois_out, sorted_anchor, roi_anchor,
                          ncols, col_scale, maxn, (char*)mw_scratch, stage == 1 ? prefix : 0, stage);
   } else if (col_scale) {      // (stride <= NC_TL_MAXN: checked above)
@@ -579,7 +587,7 @@ int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, co
   } else {
     hipLaunchKernelGGL((nms_columns_kernel<16, NC_MAXN, 128>), dim3(n_img), dim3(1024), 0, s, sorted_boxes, sorted_scores, counts_in, stride, thresh,
                        max_keep, keep_idx, keep_stride, keep_counts, rois_out, (float4*)kept_spill, sorted_anchor, roi_anchor, ncols, nullptr,
-                       (prefix > 0 && max_keep < prefix) ? prefix : 0, dbg);
+                       nms_prefix_launches(false, prefix, stride, max_keep) ? prefix : 0, dbg);
   }
   return launch_status("nms_columns");
 }

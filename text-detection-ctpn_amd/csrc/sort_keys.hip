@@ -195,16 +195,17 @@ __global__ __launch_bounds__(1024) void merge_rank_kernel(const unsigned long lo
   out[rank] = key;
 }
 
+int sort_seg_len(int per_img) { return ((per_img + MG_SEGS - 1) / MG_SEGS + 63) & ~63; }
+int sort_merge_workgroups(int per_img) { return (per_img + 1023) / 1024; }
 bool sort_is_segmented(int n_img, int per_img) {
-  const int seg = ((per_img + MG_SEGS - 1) / MG_SEGS + 63) & ~63;
-  return n_img <= NMS_MW_MAX_BATCH && per_img > 4096 && seg <= MG_MAXSEG;
+  return n_img <= NMS_MW_MAX_BATCH && per_img > 4096 && sort_seg_len(per_img) <= MG_MAXSEG;
 }
 
 // sorted keys of every image: in `keys` on return, or -- *in_tmp = 1 -- in `tmp` (the merged form of small batches)
 int launch_sort_keys(unsigned long long* keys, unsigned long long* tmp, int n_img, int npad, int per_img, hipStream_t s, int* in_tmp) {
   if (!keys || !tmp) return fail(CTPN_ERR_ARG, "sort: null buffer");
   if (in_tmp) *in_tmp = 0;
-  const int seg = ((per_img + MG_SEGS - 1) / MG_SEGS + 63) & ~63;
+  const int seg = sort_seg_len(per_img);
   if (in_tmp && sort_is_segmented(n_img, per_img)) {
     static bool raised[CTPN_MAX_DEV] = {false};
     int dev = 0;
@@ -214,7 +215,7 @@ int launch_sort_keys(unsigned long long* keys, unsigned long long* tmp, int n_im
     int rc = raise_dynamic_lds((const void*)radix_sort_kernel<true>, lds, raised, dev);
     if (rc) return rc;
     hipLaunchKernelGGL(radix_sort_kernel<true>, dim3(MG_SEGS, n_img), dim3(RS_WAVES * 64), lds, s, keys, tmp, npad, per_img, seg);
-    hipLaunchKernelGGL(merge_rank_kernel, dim3((per_img + 1023) / 1024, n_img), dim3(1024), 0, s, keys, tmp, npad, per_img, seg);
+    hipLaunchKernelGGL(merge_rank_kernel, dim3(sort_merge_workgroups(per_img), n_img), dim3(1024), 0, s, keys, tmp, npad, per_img, seg);
     *in_tmp = 1;
   } else {
     hipLaunchKernelGGL(radix_sort_kernel<false>, dim3(1, n_img), dim3(RS_WAVES * 64), 0, s, keys, tmp, npad, per_img, per_img);

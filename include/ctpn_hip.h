@@ -430,6 +430,12 @@ int ctpn_debug_lstm_pre_plan(long long cells, int cu_count, int* plan_out);
  * profiling is on or the memory is not there. out4: [0] sets allocated (1 or 2)  [1] the set of the most recent forward (0 or 1)
  * [2] device bytes of set 1 (0 without it)  [3] the set the batch in flight in slot 0 runs on | that of slot 1 << 8 (-1 for an idle slot, as 255). */
 int ctpn_debug_forward_sets(ctpn_ctx* ctx, long long* out4);
+/* What the library's host side holds in this process right now (test hook; pure host read, no ctx, no device). Every device block, page-locked
+ * block, event and stream the host units create is owned by a handle type (csrc/owned.h) that counts it in and out. out4: [0] device bytes
+ * [1] page-locked bytes  [2] events  [3] streams. A ctx adds to all four while it lives and ctpn_destroy takes exactly that off again; a
+ * stateless entry point (ctpn_resize, ctpn_debug_*) leaves them as it found them, on success and on failure. What stays for the life of the
+ * process: ctpn_nms's per-device cache, once used. The kernel launchers' few process-wide scratch blocks are not counted. */
+int ctpn_debug_live_resources(long long* out4);
 int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const float* bias, int n, int hf, int wf, int precision, int cu_count,
                         float* out);
 int ctpn_debug_bilstm(int device_id, const float* pre, const float* wh, int rows, int T, int split, int fast_gates, int pre_f16, float* out,

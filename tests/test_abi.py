@@ -129,3 +129,37 @@ def test_no_null_stream_memset_in_the_launch_paths(root):
             head = api[:m.start()]
             fns = re.findall(r"\nint (ctpn_\w+)\(", head)
             assert fns and fns[-1].startswith("ctpn_debug_"), (f, fns[-1:])
+
+
+def test_hip_resources_are_created_and_released_in_owned_h_only(root):
+    """The host side owns every device block, page-locked block, event and stream through the four types of csrc/owned.h: a release has no
+    other spelling anywhere in csrc/, and in the host units (api_*.hip, ctx.h) neither has an acquisition. The hand-written idioms the
+    types replaced are gone by name, and ctpn_destroy is: select the device, drain the streams, delete the ctx.
+    The kernel units' launchers keep six acquisitions of process-wide scratch (tile-claim counters, a dump block, the strip stream and its two
+    events, conv1_1's constant block): made once per device, never released, not owned by a ctx. They are listed here, file by file, so that
+    the list cannot grow unseen; owned.h is not included by the kernel units."""
+    src = os.path.join(root, "text-detection-ctpn_amd", "csrc")
+    files = sorted(f for f in os.listdir(src) if f.endswith((".hip", ".h", ".cpp")))
+    assert "owned.h" in files and "ctx.h" in files
+    code = {f: re.sub(r"//[^\n]*", "", open(os.path.join(src, f)).read()) for f in files}
+    release = ["hipFree(", "hipHostFree(", "hipEventDestroy(", "hipStreamDestroy("]
+    acquire = ["hipMalloc(", "hipHostMalloc(", "hipEventCreate", "hipStreamCreate"]
+    for word in release + acquire:
+        assert word in code["owned.h"], word
+    launcher_scratch = {"conv3x3.hip": {"hipMalloc(": 2, "hipStreamCreate": 1, "hipEventCreate": 2}, "conv_first.hip": {"hipMalloc(": 1}}
+    for f in files:
+        if f == "owned.h":
+            continue
+        for word in release:
+            assert word not in code[f], (f, word)
+        host_unit = f.startswith("api_") or f == "ctx.h"
+        assert host_unit or "owned.h" not in code[f], f
+        for word in acquire:
+            allowed = 0 if host_unit else launcher_scratch.get(f, {}).get(word, 0)
+            assert code[f].count(word) == allowed, (f, word, code[f].count(word))
+    for f in files:
+        for name in ("grow_dev", "grow_host", "jpeg_grow_dev", "jpeg_grow_pair", "Free3", "DC_TRY", "RS_TRY", "DevBufs"):
+            assert not re.search(r"\b%s\b" % name, code[f]), (f, name)
+    body = re.search(r"\nint ctpn_destroy\(ctpn_ctx\* c\) \{\n(.*?)\n\}\n", code["api_ctx.hip"], flags=re.S).group(1)
+    assert "delete c;" in body and "hipSetDevice(c->device)" in body and body.count("hipStreamSynchronize(") == 4
+    assert not re.search(r"\b(for|while|do)\b", body), body

@@ -116,6 +116,7 @@ def _declare(lib):
         "ctpn_debug_conv3x3_form_name": (C.c_char_p, [C.c_int, C.c_int]),
         "ctpn_debug_lstm_pre_plan": (C.c_int, [C.c_longlong, C.c_int, i32p]),
         "ctpn_debug_forward_sets": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
+        "ctpn_debug_live_resources": (C.c_int, [C.POINTER(C.c_longlong)]),
         "ctpn_debug_lstm_pre": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
         "ctpn_debug_bilstm": (C.c_int, [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, i32p]),
         "ctpn_debug_gemm": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
@@ -668,6 +669,14 @@ def ragged_valid_rows(height, level):
 def host_thread_budget(cpu_count, local_world_size=1, requested=0):
     """ctpn_host_thread_budget: host workers per ctx (pure function of its arguments, no GPU needed)."""
     return int(load_library().ctpn_host_thread_budget(int(cpu_count), int(local_world_size), int(requested)))
+
+
+def live_resources():
+    """ctpn_debug_live_resources: (device bytes, page-locked bytes, events, streams) the library's host side holds in this process right now
+    (pure host read: no ctx, no GPU needed)."""
+    out = (C.c_longlong * 4)()
+    _check(load_library().ctpn_debug_live_resources(out))
+    return tuple(int(v) for v in out)
 
 
 def debug_cvt_bf16(x, use_hw=True, device_id=0):

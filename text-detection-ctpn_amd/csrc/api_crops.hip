@@ -23,14 +23,9 @@ static bool crop_finite(const double* rec9) {
 
 static int crop_reserve(ctpn_ctx* c, size_t desc_bytes) {
   auto& K = c->crop;
-  if (!K.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&K.ev_done, hipEventDisableTiming));
-  if (desc_bytes > K.desc_host_bytes) {
-    if (K.desc_host) CTPN_HIP_TRY(hipHostFree(K.desc_host));
-    K.desc_host = nullptr; K.desc_host_bytes = 0;
-    CTPN_HIP_TRY(hipHostMalloc(&K.desc_host, desc_bytes));
-    K.desc_host_bytes = desc_bytes;
-  }
-  return grow_dev(&K.desc_dev, K.desc_bytes, desc_bytes);
+  int rc;
+  if ((rc = K.ev_done.ensure()) || (rc = K.desc_host.grow(desc_bytes))) return rc;
+  return K.desc_dev.grow(desc_bytes);
 }
 
 // the argument checks of ctpn_crop_lines and pass 1, host only: every line's width (what the sizing call is for).
@@ -77,13 +72,13 @@ static int crop_cut(ctpn_ctx* c, const uint8_t* images, int images_on_device, in
   if ((rc = crop_reserve(c, table_bytes))) return rc;
   for (int i = 0, k = 0; i < n; ++i)
     for (int j = 0; j < line_counts[i]; ++j, ++k)
-      crop_fill_desc(recs + ((size_t)i * line_capacity + j) * 9, i, widths[k], (size_t)k * line_bytes, (char*)K.desc_host + (size_t)k * CROP_DESC_BYTES);
-  if (heights) std::memcpy((char*)K.desc_host + desc_bytes, heights, (size_t)n * sizeof(int));
-  CTPN_HIP_TRY(hipMemcpyAsync(K.desc_dev, K.desc_host, table_bytes, hipMemcpyHostToDevice, qs));
-  const int* heights_dev = heights ? (const int*)((const char*)K.desc_dev + desc_bytes) : nullptr;
+      crop_fill_desc(recs + ((size_t)i * line_capacity + j) * 9, i, widths[k], (size_t)k * line_bytes, K.desc_host.as<char>() + (size_t)k * CROP_DESC_BYTES);
+  if (heights) std::memcpy(K.desc_host.as<char>() + desc_bytes, heights, (size_t)n * sizeof(int));
+  CTPN_HIP_TRY(hipMemcpyAsync(K.desc_dev.get(), K.desc_host.get(), table_bytes, hipMemcpyHostToDevice, qs));
+  const int* heights_dev = heights ? (const int*)(K.desc_dev.as<char>() + desc_bytes) : nullptr;
   const uint8_t* px;
-  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 0, K.img_dev, K.img_bytes, qs, px))) return rc;
-  return launch_crop_lines(px, K.desc_dev, (int)total, out_dev, h, w, heights_dev, crop_h, max_w, pad_value, qs);
+  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 0, K.img_dev, qs, px))) return rc;
+  return launch_crop_lines(px, K.desc_dev.get(), (int)total, out_dev, h, w, heights_dev, crop_h, max_w, pad_value, qs);
 }
 
 // ctpn_write_line_crops / ctpn_write_line_crops_device / ctpn_write_line_crops_png and their _ragged forms. format: the files'
@@ -104,17 +99,17 @@ static int write_line_crops_impl(ctpn_ctx* c, const char* who_, const uint8_t* i
   CTPN_HIP_TRY(hipSetDevice(c->device));
   auto& K = c->crop;
   const size_t pitch = (size_t)max_w * 3, line_bytes = (size_t)crop_h * pitch;
-  if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, total * line_bytes))) return rc;
+  if ((rc = K.out_dev.grow(total * line_bytes))) return rc;
   // the JPEG encoder's aligned read (jenc_load4) stays inside a crop's pixels where its rows start 4-byte aligned: the buffer is a device
   // allocation, a crop's offset and the pitch are multiples of 12 (max_w % 4 == 0, crop_check_geometry). (The PNG writer reads bytes.)
-  if (format == CROP_JPEG && (((uintptr_t)K.out_dev & 3) || (pitch & 3) || (line_bytes & 3))) return fail(CTPN_ERR_STATE, who + ": the crop rows are not 4-byte aligned");
-  if ((rc = crop_cut(c, images, images_on_device, n, h, w, heights, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, K.out_dev))) return rc;
+  if (format == CROP_JPEG && (((uintptr_t)K.out_dev.get() & 3) || (pitch & 3) || (line_bytes & 3))) return fail(CTPN_ERR_STATE, who + ": the crop rows are not 4-byte aligned");
+  if ((rc = crop_cut(c, images, images_on_device, n, h, w, heights, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, K.out_dev.as<uint8_t>()))) return rc;
   // encoded where they lie, behind the kernel in the same queue: crop k is crop_h x widths[k] at pitch 3 max_w -- the pad columns never enter a file
   std::vector<int> crop_heights(total, crop_h);
   std::vector<size_t> pitches(total, pitch), offsets(total);
   for (size_t k = 0; k < total; ++k) offsets[k] = k * line_bytes;
-  if (format == CROP_PNG) return png_code_table(c, who_, K.out_dev, (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), nullptr, nullptr, nullptr, paths);
-  return encode_mixed_dev(c, who_, K.out_dev, (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
+  if (format == CROP_PNG) return png_code_table(c, who_, K.out_dev.as<uint8_t>(), (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), nullptr, nullptr, nullptr, paths);
+  return encode_mixed_dev(c, who_, K.out_dev.as<uint8_t>(), (int)total, crop_heights.data(), widths.data(), pitches.data(), offsets.data(), quality, nullptr, nullptr, nullptr, paths, device_entropy);
 }
 
 // ctpn_crop_lines / ctpn_crop_lines_ragged
@@ -137,11 +132,11 @@ static int crop_lines_impl(ctpn_ctx* c, const char* who_, const uint8_t* images,
   int rc;
   uint8_t* out = crops_out;
   if (!crops_on_device) {
-    if ((rc = grow_dev((void**)&K.out_dev, K.out_bytes, need))) return rc;
-    out = K.out_dev;
+    if ((rc = K.out_dev.grow(need))) return rc;
+    out = K.out_dev.as<uint8_t>();
   }
   if ((rc = crop_cut(c, images, images_on_device, n, h, w, heights, recs, line_capacity, line_counts, widths, crop_h, max_w, pad_value, out))) return rc;
-  if (!crops_on_device) CTPN_HIP_TRY(hipMemcpyAsync(crops_out, K.out_dev, need, hipMemcpyDeviceToHost, qs));
+  if (!crops_on_device) CTPN_HIP_TRY(hipMemcpyAsync(crops_out, K.out_dev.as<uint8_t>(), need, hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(K.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(K.ev_done));
   return CTPN_OK;

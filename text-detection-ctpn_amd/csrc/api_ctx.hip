@@ -12,8 +12,10 @@ static int env_int(const char* name, int dflt) { const char* v = std::getenv(nam
 
 static int dev_alloc(ctpn_ctx* c, void** p, size_t bytes, bool zero) {
   if (bytes == 0) bytes = 256;
-  CTPN_HIP_TRY(hipMalloc(p, bytes));
-  c->allocs.push_back(*p);
+  DevBuf b;
+  if (const int rc = b.alloc(bytes)) return rc;
+  *p = b.get();
+  c->allocs.push_back(std::move(b));
   if (zero) CTPN_HIP_TRY(hipMemsetAsync(*p, 0, bytes, c->stream));
   return CTPN_OK;
 }
@@ -89,7 +91,7 @@ static int prof_drain(ctpn_ctx* c) {
     else if (sp.t1 > covered) c->prof_ms[CTPN_KIND_CONV_GEMM] += sp.t1 - covered;
     if (i == 0 || sp.t1 > covered) covered = sp.t1;
   }
-  for (auto& r : c->pending) { c->free_events.push_back(r.a); c->free_events.push_back(r.b); }
+  for (auto& r : c->pending) { c->free_events.push_back(std::move(r.a)); c->free_events.push_back(std::move(r.b)); }
   c->pending.clear();
   return CTPN_OK;
 }
@@ -129,7 +131,10 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return fail(CTPN_ERR_NODEVICE, std::string("ctpn_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
 
-  ctpn_ctx* c = new ctpn_ctx();
+  // the one failure path: every return before `*out` is set hands the half-built ctx to ctpn_destroy, which drains its streams and lets it die
+  struct Destroy { void operator()(ctpn_ctx* x) const { (void)ctpn_destroy(x); } };
+  std::unique_ptr<ctpn_ctx, Destroy> owner(new ctpn_ctx());
+  ctpn_ctx* c = owner.get();
   c->device = device_id; c->max_batch = max_batch; c->max_h = max_h; c->max_w = max_w;
   c->prec = prec_dtype(precision);
   c->es = dtype_bytes(c->prec);
@@ -153,33 +158,22 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   }
   int rc = CTPN_OK;
   auto A = [&](void** p, size_t bytes, bool zero) { if (rc == CTPN_OK) rc = dev_alloc(c, p, bytes, zero); };
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(CTPN_ERR_HIP, "hipStreamCreate failed"); }
+  ctpn_ctx::FwdSet& f0 = c->fs[0];      // allocated here; set 1: ensure_set1
+  if ((rc = f0.stream.ensure()) || (rc = c->stream_p.ensure())) return rc;
+  c->stream = f0.stream;
   // (the proposal stream at the highest stream priority was measured in round 2: no effect -- placement is by free resources)
   // (the proposal stream at the highest stream priority: measured in round 6 with the tail confined -- 1163 against 1164 images/s in split precision,
   // -0.2 % in bf16: the dispatcher does not hand CUs to the 1024-thread NMS workgroups any sooner. Not used.)
-  if (hipStreamCreateWithFlags(&c->stream_p, hipStreamNonBlocking) != hipSuccess) { (void)hipStreamDestroy(c->stream); delete c; return fail(CTPN_ERR_HIP, "hipStreamCreate failed"); }
-  ctpn_ctx::FwdSet& f0 = c->fs[0];      // today's allocation on `stream`
-  f0.stream = c->stream;
-  if (hipEventCreateWithFlags(&f0.ev_conv, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&f0.ev_tail, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&f0.ev_gate, hipEventDisableTiming) != hipSuccess) {
-    ctpn_destroy(c); return fail(CTPN_ERR_HIP, "ctpn_create: events");
-  }
+  if (f0.ev_conv.ensure() != CTPN_OK || f0.ev_tail.ensure() != CTPN_OK || f0.ev_gate.ensure() != CTPN_OK) return fail(CTPN_ERR_HIP, "ctpn_create: events");
   for (auto& sl : c->slot) {
     const size_t mb = (size_t)max_batch;
     const PackLayout L = pack_layout(mb, (size_t)c->post_max);
-    bool ok = hipHostMalloc((void**)&sl.pack, L.total) == hipSuccess;
-    if (ok) {
-      sl.tlb = (float*)(sl.pack + L.tlb); sl.tls = (float*)(sl.pack + L.tls); sl.keep = (int*)(sl.pack + L.keep); sl.kcnt = (int*)(sl.pack + L.kcnt);
-      sl.rois = (float*)(sl.pack + L.rois); sl.rcnt = (int*)(sl.pack + L.rcnt);
-    }
-    ok = ok &&
-              hipHostMalloc((void**)&sl.im_info, mb * 3 * sizeof(float)) == hipSuccess &&
-              hipHostMalloc((void**)&sl.crecs, mb * 2 * CONN_CAP * 9 * sizeof(double)) == hipSuccess &&
-              hipHostMalloc((void**)&sl.ccnt, mb * 3 * sizeof(int)) == hipSuccess &&
-              hipEventCreateWithFlags(&sl.ev_heads, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&sl.ev_decoded, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { ctpn_destroy(c); return fail(CTPN_ERR_HIP, "ctpn_create: pinned host buffers / events"); }
+    const bool ok = sl.pack.alloc(L.total) == CTPN_OK && sl.im_info.alloc(mb * 3 * sizeof(float)) == CTPN_OK && sl.crecs.alloc(mb * 2 * CONN_CAP * 9 * sizeof(double)) == CTPN_OK &&
+                    sl.ccnt.alloc(mb * 3 * sizeof(int)) == CTPN_OK && sl.ev_heads.ensure() == CTPN_OK && sl.ev_decoded.ensure() == CTPN_OK && sl.ev_done.ensure() == CTPN_OK;
+    if (!ok) return fail(CTPN_ERR_HIP, "ctpn_create: pinned host buffers / events");
+    char* pack = sl.pack.as<char>();
+    sl.tlb = (float*)(pack + L.tlb); sl.tls = (float*)(pack + L.tls); sl.keep = (int*)(pack + L.keep); sl.kcnt = (int*)(pack + L.kcnt);
+    sl.rois = (float*)(pack + L.rois); sl.rcnt = (int*)(pack + L.rcnt);
   }
 
   const int hf = lvl(max_h, 4), wf = lvl(max_w, 4);
@@ -214,7 +208,7 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
     c->act_conv_bytes[i] = ((size_t)max_batch * (hl + 2) * (wl + 2) + act_slack_pixels(wl)) * pix_b;
     const size_t front = act_front_pixels(wl) * pix_b;
     A(&f0.act_conv[i], front + c->act_conv_bytes[i], true);
-    if (f0.act_conv[i]) f0.act_conv[i] = (char*)f0.act_conv[i] + front;     // allocs[] keeps the pointer hipFree needs
+    if (f0.act_conv[i]) f0.act_conv[i] = (char*)f0.act_conv[i] + front;     // allocs[] owns the block
   }
   {
     const int pool_src[4] = {1, 3, 6, 9};
@@ -231,9 +225,8 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   c->img_dev_b[0] = c->img_dev;
   A((void**)&c->img_dev_b[1], (size_t)max_batch * max_h * max_w * 3 * sizeof(float), false);
   if (rc == CTPN_OK) {
-    bool ok = hipStreamCreateWithFlags(&c->stream_c, hipStreamNonBlocking) == hipSuccess;
-    for (int b = 0; b < 2 && ok; ++b)
-      ok = hipEventCreateWithFlags(&c->ev_copied[b], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->ev_consumed[b], hipEventDisableTiming) == hipSuccess;
+    bool ok = c->stream_c.ensure() == CTPN_OK;
+    for (int b = 0; b < 2 && ok; ++b) ok = c->ev_copied[b].ensure() == CTPN_OK && c->ev_consumed[b].ensure() == CTPN_OK;
     if (!ok) rc = fail(CTPN_ERR_HIP, "ctpn_create: copy stream / events");
   }
   A((void**)&f0.xp, c->m5_max * 1024 * sizeof(float), false);
@@ -275,8 +268,8 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   A((void**)&c->conn_scratch, (size_t)max_batch * 1024 * 20 * sizeof(double), false);
   A((void**)&c->im_info_dev, (size_t)max_batch * 3 * sizeof(float), true);
   if (rc == CTPN_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_create: sync failed");
-  if (rc != CTPN_OK) { ctpn_destroy(c); return rc; }
-  *out = c;
+  if (rc != CTPN_OK) return rc;
+  *out = owner.release();
   return CTPN_OK;
 }
 
@@ -291,9 +284,10 @@ static size_t pool_front_bytes(const ctpn_ctx* c, int p) {
 
 // one zeroed block of forward set 1, on the set's stream (the forward that reads it follows on that stream); false: out of memory
 static bool set1_block(ctpn_ctx* c, ctpn_ctx::FwdSet& f, void** p, size_t front, size_t bytes) {
-  void* raw = nullptr;
-  if (hipMalloc(&raw, front + bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-  f.allocs.push_back(raw);
+  DevBuf b;
+  if (b.alloc(front + bytes) != CTPN_OK) { (void)hipGetLastError(); return false; }
+  void* raw = b.get();
+  f.allocs.push_back(std::move(b));
   if (hipMemsetAsync(raw, 0, front + bytes, f.stream) != hipSuccess) { (void)hipGetLastError(); return false; }
   *p = (char*)raw + front;
   c->set1_bytes += front + bytes;
@@ -310,9 +304,7 @@ bool ensure_set1(ctpn_ctx* c, bool need_conv1) {
   if (two_forwards_mode() == 0 || c->postproc_only || c->keep_acts || (c->prof && c->prof_mode == 1) || c->set1_state < 0) return false;
   ctpn_ctx::FwdSet& f = c->fs[1];
   if (c->set1_state == 0) {
-    bool ok = hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&f.ev_conv, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&f.ev_tail, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&f.ev_gate, hipEventDisableTiming) == hipSuccess;
+    bool ok = f.stream.ensure() == CTPN_OK && f.ev_conv.ensure() == CTPN_OK && f.ev_tail.ensure() == CTPN_OK && f.ev_gate.ensure() == CTPN_OK;
     for (int i = 1; i < 14 && ok; ++i)
       if (!kConvs[i].pool_after) ok = set1_block(c, f, &f.act_conv[i], conv_front_bytes(c, i), c->act_conv_bytes[i]);
     for (int p = 0; p < 4 && ok; ++p) ok = set1_block(c, f, &f.act_pool[p], pool_front_bytes(c, p), c->act_pool_bytes[p]);
@@ -323,10 +315,7 @@ bool ensure_set1(ctpn_ctx* c, bool need_conv1) {
     if (!ok) {
       (void)hipGetLastError();
       if (f.stream) (void)hipStreamSynchronize(f.stream);
-      for (void* p : f.allocs) (void)hipFree(p);
-      for (hipEvent_t e : {f.ev_conv, f.ev_tail, f.ev_gate}) if (e) (void)hipEventDestroy(e);
-      if (f.stream) (void)hipStreamDestroy(f.stream);
-      f = ctpn_ctx::FwdSet();
+      f = ctpn_ctx::FwdSet();      // the half-built set's blocks, events and stream go with it
       c->set1_bytes = 0;
       c->set1_state = -1;
       return false;
@@ -461,47 +450,8 @@ int ctpn_destroy(ctpn_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->fs[1].stream) (void)hipStreamSynchronize(c->fs[1].stream);
   if (c->stream_p) (void)hipStreamSynchronize(c->stream_p);
-  if (c->stream_c) { (void)hipStreamSynchronize(c->stream_c); (void)hipStreamDestroy(c->stream_c); }
-  for (int b = 0; b < 2; ++b) { if (c->pin_stage[b]) (void)hipHostFree(c->pin_stage[b]); if (c->ev_h2d_done[b]) (void)hipEventDestroy(c->ev_h2d_done[b]); }
-  for (int b = 0; b < 2; ++b) { if (c->ev_copied[b]) (void)hipEventDestroy(c->ev_copied[b]); if (c->ev_consumed[b]) (void)hipEventDestroy(c->ev_consumed[b]); }
-  for (auto& sl : c->slot) {
-    for (void* p : {(void*)sl.pack, (void*)sl.im_info, (void*)sl.crecs, (void*)sl.ccnt}) if (p) (void)hipHostFree(p);
-    for (hipEvent_t e : {sl.ev_heads, sl.ev_decoded, sl.ev_done}) if (e) (void)hipEventDestroy(e);
-  }
-  for (auto& f : c->fs) {
-    for (hipEvent_t e : {f.ev_conv, f.ev_tail, f.ev_gate}) if (e) (void)hipEventDestroy(e);
-    if (f.ragged_blob) (void)hipFree(f.ragged_blob);
-    for (void* p : f.allocs) (void)hipFree(p);
-  }
-  if (c->fs[1].stream) (void)hipStreamDestroy(c->fs[1].stream);
-  for (auto& r : c->ragged) { if (r.host) (void)hipHostFree(r.host); if (r.dev) (void)hipFree(r.dev); if (r.ev_copied) (void)hipEventDestroy(r.ev_copied); }
-  for (auto& j : c->jpeg) {
-    if (j.coef_host) (void)hipHostFree(j.coef_host);
-    if (j.qt_host) (void)hipHostFree(j.qt_host);
-    if (j.tab_host) (void)hipHostFree(j.tab_host);
-    for (void* p : {(void*)j.coef_dev, (void*)j.qt_dev, (void*)j.out_dev, (void*)j.tab_dev}) if (p) (void)hipFree(p);
-    for (hipEvent_t e : {j.ev_h2d, j.ev_ready, j.ev_consumed}) if (e) (void)hipEventDestroy(e);
-  }
-  for (void* p : {(void*)c->jpeg_planes, (void*)c->jpeg_raw}) if (p) (void)hipFree(p);
-  for (void* p : {(void*)c->jh.stage_dev, (void*)c->jh.work_dev}) if (p) (void)hipFree(p);
-  for (void* p : {(void*)c->jh.stage_host, (void*)c->jh.res_host}) if (p) (void)hipHostFree(p);
-  for (void* p : c->jpeg_retired) (void)hipFree(p);
-  for (void* p : {(void*)c->stage.img_dev, (void*)c->stage.rs_dev, (void*)c->stage.recs_dev, (void*)c->stage.cnt_dev, (void*)c->stage.rm_dev}) if (p) (void)hipFree(p);
-  if (c->stage.rm_host) (void)hipHostFree(c->stage.rm_host);
-  for (void* p : {(void*)c->enc.coef_dev, c->enc.qtab_dev, (void*)c->enc.huff_dev, c->enc.huff_tab_dev, (void*)c->enc.mix_dev}) if (p) (void)hipFree(p);
-  for (void* p : {(void*)c->enc.coef_host, c->enc.qtab_host, (void*)c->enc.huff_host, (void*)c->enc.scan_host, (void*)c->enc.mix_host}) if (p) (void)hipHostFree(p);
-  if (c->enc.ev_done) (void)hipEventDestroy(c->enc.ev_done);
-  if (c->pnge.dev) (void)hipFree(c->pnge.dev);
-  for (void* p : {(void*)c->pnge.host, (void*)c->pnge.file_host}) if (p) (void)hipHostFree(p);
-  if (c->pnge.ev_done) (void)hipEventDestroy(c->pnge.ev_done);
-  for (void* p : {(void*)c->crop.img_dev, (void*)c->crop.out_dev, c->crop.desc_dev}) if (p) (void)hipFree(p);
-  if (c->crop.desc_host) (void)hipHostFree(c->crop.desc_host);
-  if (c->crop.ev_done) (void)hipEventDestroy(c->crop.ev_done);
-  if (c->stream_p) (void)hipStreamDestroy(c->stream_p);
-  for (auto& r : c->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-  for (auto e : c->free_events) (void)hipEventDestroy(e);
-  for (void* p : c->allocs) (void)hipFree(p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (c->stream_c) (void)hipStreamSynchronize(c->stream_c);
+  // everything is idle: the members release what they own, in reverse declaration order (the host pool first, see ctx.h)
   delete c;
   return CTPN_OK;
 }

@@ -13,14 +13,13 @@ int ctpn_debug_cvt_bf16(int device_id, const float* in, uint16_t* out, int n, in
   if (!in || !out || n <= 0) return fail(CTPN_ERR_ARG, "ctpn_debug_cvt_bf16: bad argument");
   if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_cvt_bf16: no HIP device visible (no CPU fallback)");
   CTPN_HIP_TRY(hipSetDevice(device_id));
-  float* d_in = nullptr; uint16_t* d_out = nullptr;
-  CTPN_HIP_TRY(hipMalloc((void**)&d_in, (size_t)n * 4));
-  CTPN_HIP_TRY(hipMalloc((void**)&d_out, (size_t)n * 2 + 4));
-  CTPN_HIP_TRY(hipMemcpy(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice));
-  int rc = launch_cvt_bf16(d_in, d_out, n, use_hw_instruction, nullptr);
+  DevBuf d_in, d_out;
+  int rc;
+  if ((rc = d_in.alloc((size_t)n * 4)) || (rc = d_out.alloc((size_t)n * 2 + 4))) return rc;
+  CTPN_HIP_TRY(hipMemcpy(d_in.get(), in, (size_t)n * 4, hipMemcpyHostToDevice));
+  rc = launch_cvt_bf16(d_in.as<float>(), d_out.as<uint16_t>(), n, use_hw_instruction, nullptr);
   if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_debug_cvt_bf16: kernel failed");
-  if (!rc && hipMemcpy(out, d_out, (size_t)n * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_debug_cvt_bf16: copy failed");
-  (void)hipFree(d_in); (void)hipFree(d_out);
+  if (!rc && hipMemcpy(out, d_out.get(), (size_t)n * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_debug_cvt_bf16: copy failed");
   return rc;
 }
 
@@ -28,18 +27,15 @@ int ctpn_debug_lds_dma(int device_id, const uint8_t* src, size_t bytes, uint8_t*
   if (!src || !out_clobber || !out_keep || bytes == 0 || bytes % 1024 != 0 || bytes > ((size_t)1 << 30)) return fail(CTPN_ERR_ARG, "ctpn_debug_lds_dma: bytes must be a positive multiple of 1024 (<= 1 GiB)");
   if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_lds_dma: no HIP device visible (no CPU fallback)");
   CTPN_HIP_TRY(hipSetDevice(device_id));
-  char *d_in = nullptr, *d_a = nullptr, *d_b = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)d_in, (void*)d_a, (void*)d_b}) if (p) (void)hipFree(p); };
-  struct Guard { decltype(cleanup)& f; ~Guard() { f(); } } guard{cleanup};
-  CTPN_HIP_TRY(hipMalloc((void**)&d_in, bytes));
-  CTPN_HIP_TRY(hipMalloc((void**)&d_a, bytes));
-  CTPN_HIP_TRY(hipMalloc((void**)&d_b, bytes));
+  DevBuf b_in, b_a, b_b;
+  int rc;
+  if ((rc = b_in.alloc(bytes)) || (rc = b_a.alloc(bytes)) || (rc = b_b.alloc(bytes))) return rc;
+  char *d_in = b_in.as<char>(), *d_a = b_a.as<char>(), *d_b = b_b.as<char>();
   CTPN_HIP_TRY(hipMemcpy(d_in, src, bytes, hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemset(d_a, 0xA5, bytes));
   CTPN_HIP_TRY(hipMemset(d_b, 0x5A, bytes));
   CTPN_HIP_TRY(hipDeviceSynchronize());
-  int rc = launch_lds_dma_check(d_in, d_a, d_b, (int)(bytes / 1024), nullptr);
-  if (rc) return rc;
+  if ((rc = launch_lds_dma_check(d_in, d_a, d_b, (int)(bytes / 1024), nullptr))) return rc;
   if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_lds_dma: kernel failed");
   CTPN_HIP_TRY(hipMemcpy(out_clobber, d_a, bytes, hipMemcpyDeviceToHost));
   CTPN_HIP_TRY(hipMemcpy(out_keep, d_b, bytes, hipMemcpyDeviceToHost));
@@ -77,22 +73,16 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
       if (split) { const uint16_t l = host_f32_to_bf16(v - host_bf16_to_f32(b)); std::memcpy(&hin[(o + ci) * 2], &l, 2); }
     }
   }
-  void *d_in = nullptr, *d_out = nullptr, *d_pool = nullptr, *d_wt = nullptr; float *d_w = nullptr, *d_b = nullptr;
-  char* d_in_alloc = nullptr;
   hipStream_t s = nullptr;
-  int rc = CTPN_OK;
-  auto cleanup = [&]() { for (void* p : {(void*)d_in_alloc, d_out, d_pool, d_wt, (void*)d_w, (void*)d_b}) if (p) (void)hipFree(p); };
-  struct Guard { decltype(cleanup)& f; ~Guard() { f(); } } guard{cleanup};
   const size_t in_front = act_front_pixels(w) * cin_p * es;
   const size_t wt_bytes = (size_t)co_pad * 9 * ci * (split ? 6 : es);
-  CTPN_HIP_TRY(hipMalloc((void**)&d_in_alloc, in_front + in_elems * es));
-  CTPN_HIP_TRY(hipMemset(d_in_alloc, 0, in_front));
-  d_in = d_in_alloc + in_front;
-  CTPN_HIP_TRY(hipMalloc(&d_out, out_elems * es));
-  CTPN_HIP_TRY(hipMalloc(&d_pool, pool_elems * es + 256));
-  CTPN_HIP_TRY(hipMalloc(&d_wt, wt_bytes));
-  CTPN_HIP_TRY(hipMalloc((void**)&d_w, (size_t)9 * ci * co * 4));
-  CTPN_HIP_TRY(hipMalloc((void**)&d_b, (size_t)co_pad * 4));
+  DevBuf b_in, b_out, b_pool, b_wt, b_w, b_b;
+  int rc;
+  if ((rc = b_in.alloc(in_front + in_elems * es)) || (rc = b_out.alloc(out_elems * es)) || (rc = b_pool.alloc(pool_elems * es + 256)) || (rc = b_wt.alloc(wt_bytes)) ||
+      (rc = b_w.alloc((size_t)9 * ci * co * 4)) || (rc = b_b.alloc((size_t)co_pad * 4))) return rc;
+  CTPN_HIP_TRY(hipMemset(b_in.get(), 0, in_front));
+  void *d_in = b_in.as<char>() + in_front, *d_out = b_out.get(), *d_pool = b_pool.get(), *d_wt = b_wt.get();
+  float *d_w = b_w.as<float>(), *d_b = b_b.as<float>();
   CTPN_HIP_TRY(hipMemset(d_out, 0, out_elems * es));
   CTPN_HIP_TRY(hipMemset(d_pool, 0, pool_elems * es + 256));
   CTPN_HIP_TRY(hipMemset(d_wt, 0, wt_bytes));
@@ -192,17 +182,22 @@ bool dbg_fill_intact(const char* p, size_t n) {
 }
 // one fp32 value as the 16-bit operand of mode t (split precision: the hi half)
 inline uint16_t dbg_to16(DType t, float v) { return t == DType::F16 ? host_f32_to_f16(v) : host_f32_to_bf16(v); }
-struct DevBufs {      // hipFree on every way out
-  std::vector<void*> p;
-  ~DevBufs() { for (void* q : p) if (q) (void)hipFree(q); }
-  int alloc(void** out, size_t bytes) {
-    CTPN_HIP_TRY(hipMalloc(out, bytes));
-    p.push_back(*out);
-    return CTPN_OK;
-  }
-};
+// a device block for the length of a hook: `bufs`, a local of the hook, owns it; *out is a view
+int dbg_alloc(std::vector<DevBuf>& bufs, void** out, size_t bytes) {
+  DevBuf b;
+  if (const int rc = b.alloc(bytes)) return rc;
+  *out = b.get();
+  bufs.push_back(std::move(b));
+  return CTPN_OK;
+}
 }  // namespace
 extern "C" {
+
+int ctpn_debug_live_resources(long long* out4) {
+  if (!out4) return fail(CTPN_ERR_ARG, "ctpn_debug_live_resources: null pointer");
+  for (int k = 0; k < 4; ++k) out4[k] = live_read(k);
+  return CTPN_OK;
+}
 
 int ctpn_debug_forward_sets(ctpn_ctx* c, long long* out4) {
   if (!c || !out4) return fail(CTPN_ERR_ARG, "ctpn_debug_forward_sets: null pointer");
@@ -259,14 +254,14 @@ int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const fl
     const float* src = inside ? x + (((size_t)in * hf + (y - 1)) * wf + (xx - 1)) * 512 : nullptr;
     for (int c = 0; c < 512; ++c) put(pixel, c, inside ? src[c] : 3e4f);
   }
-  DevBufs bufs;
+  std::vector<DevBuf> bufs;
   void *d_a = nullptr, *d_wx = nullptr, *d_b = nullptr, *d_wt = nullptr, *d_wtf = nullptr, *d_bx = nullptr, *d_out = nullptr;
   const size_t row_bytes = split ? (size_t)3 * 512 * 2 : (size_t)512 * es;
   const size_t out_bytes = (size_t)M * 1024 * oes, guard_bytes = (size_t)DBG_GUARD_ROWS * 1024 * oes;
   int rc;
-  if ((rc = bufs.alloc(&d_a, hin.size())) || (rc = bufs.alloc(&d_wx, (size_t)512 * 1024 * 4)) || (rc = bufs.alloc(&d_b, 1024 * 4)) ||
-      (rc = bufs.alloc(&d_wt, 1024 * row_bytes)) || (half && (rc = bufs.alloc(&d_wtf, (size_t)1024 * 512 * 2))) || (rc = bufs.alloc(&d_bx, 1024 * 4)) ||
-      (rc = bufs.alloc(&d_out, out_bytes + guard_bytes))) return rc;
+  if ((rc = dbg_alloc(bufs, &d_a, hin.size())) || (rc = dbg_alloc(bufs, &d_wx, (size_t)512 * 1024 * 4)) || (rc = dbg_alloc(bufs, &d_b, 1024 * 4)) ||
+      (rc = dbg_alloc(bufs, &d_wt, 1024 * row_bytes)) || (half && (rc = dbg_alloc(bufs, &d_wtf, (size_t)1024 * 512 * 2))) || (rc = dbg_alloc(bufs, &d_bx, 1024 * 4)) ||
+      (rc = dbg_alloc(bufs, &d_out, out_bytes + guard_bytes))) return rc;
   CTPN_HIP_TRY(hipMemcpy(d_a, hin.data(), hin.size(), hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemcpy(d_wx, wx, (size_t)512 * 1024 * 4, hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemcpy(d_b, bias, 1024 * 4, hipMemcpyHostToDevice));
@@ -319,11 +314,11 @@ int ctpn_debug_bilstm(int device_id, const float* pre, const float* wh, int rows
       if (pre_f16) { const uint16_t b = host_f32_to_f16(v); std::memcpy(&hpre[o * 2], &b, 2); }
       else std::memcpy(&hpre[o * 4], &v, 4);
     }
-  DevBufs bufs;
+  std::vector<DevBuf> bufs;
   void *d_pre = nullptr, *d_wh = nullptr, *d_out = nullptr;
   const size_t out_bytes = pos * 256 * 4, guard_bytes = (size_t)DBG_GUARD_ROWS * 256 * 4;
   int rc;
-  if ((rc = bufs.alloc(&d_pre, hpre.size())) || (rc = bufs.alloc(&d_wh, (size_t)2 * 128 * 512 * 4)) || (rc = bufs.alloc(&d_out, out_bytes + guard_bytes))) return rc;
+  if ((rc = dbg_alloc(bufs, &d_pre, hpre.size())) || (rc = dbg_alloc(bufs, &d_wh, (size_t)2 * 128 * 512 * 4)) || (rc = dbg_alloc(bufs, &d_out, out_bytes + guard_bytes))) return rc;
   CTPN_HIP_TRY(hipMemcpy(d_pre, hpre.data(), hpre.size(), hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemcpy(d_wh, wh, (size_t)2 * 128 * 512 * 4, hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemset(d_out, DBG_FILL, out_bytes + guard_bytes));
@@ -353,12 +348,12 @@ int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* 
   }
   // weight rows and bias padded to the N tile with zeros, as the ctx allocates them: the 64-wide tile of Co = 60 reads rows 60 .. 63
   const int co_pad = Co <= 64 ? 64 : (Co + 127) / 128 * 128;
-  DevBufs bufs;
+  std::vector<DevBuf> bufs;
   void *d_a = nullptr, *d_w = nullptr, *d_wt = nullptr, *d_b = nullptr, *d_out = nullptr;
   const size_t out_bytes = (size_t)M * ldc * 4, guard_bytes = (size_t)DBG_GUARD_ROWS * ldc * 4;
   int rc;
-  if ((rc = bufs.alloc(&d_a, ha.size())) || (rc = bufs.alloc(&d_w, (size_t)K * Co * 4)) || (rc = bufs.alloc(&d_wt, (size_t)co_pad * K * es)) ||
-      (rc = bufs.alloc(&d_b, (size_t)co_pad * 4)) || (rc = bufs.alloc(&d_out, out_bytes + guard_bytes))) return rc;
+  if ((rc = dbg_alloc(bufs, &d_a, ha.size())) || (rc = dbg_alloc(bufs, &d_w, (size_t)K * Co * 4)) || (rc = dbg_alloc(bufs, &d_wt, (size_t)co_pad * K * es)) ||
+      (rc = dbg_alloc(bufs, &d_b, (size_t)co_pad * 4)) || (rc = dbg_alloc(bufs, &d_out, out_bytes + guard_bytes))) return rc;
   CTPN_HIP_TRY(hipMemcpy(d_a, ha.data(), ha.size(), hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemcpy(d_w, w, (size_t)K * Co * 4, hipMemcpyHostToDevice));
   CTPN_HIP_TRY(hipMemset(d_wt, 0, (size_t)co_pad * K * es));
@@ -445,10 +440,10 @@ int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_im
   // both buffers: the caller's keys (first buffer only), everything else CTPN_SORT_POISON, a key that reads as VALID; then a guard row of fill bytes
   std::vector<unsigned long long> h0(total, CTPN_SORT_POISON), h1(total);
   for (int i = 0; i < n_img; ++i) std::memcpy(&h0[(size_t)i * npad], keys + (size_t)i * per_img, (size_t)per_img * 8);
-  DevBufs bufs;
+  std::vector<DevBuf> bufs;
   void *d0 = nullptr, *d1 = nullptr;
   int rc;
-  if ((rc = bufs.alloc(&d0, (total + guard) * 8)) || (rc = bufs.alloc(&d1, (total + guard) * 8))) return rc;
+  if ((rc = dbg_alloc(bufs, &d0, (total + guard) * 8)) || (rc = dbg_alloc(bufs, &d1, (total + guard) * 8))) return rc;
   CTPN_HIP_TRY(hipMemset(d0, DBG_FILL, (total + guard) * 8));
   CTPN_HIP_TRY(hipMemset(d1, DBG_FILL, (total + guard) * 8));
   CTPN_HIP_TRY(hipMemcpy(d0, h0.data(), total * 8, hipMemcpyHostToDevice));

@@ -17,7 +17,8 @@ static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hip
     Timed t(c, CTPN_KIND_NMS, (double)n * post * 24.0, p);
     if ((rc = launch_lines_prep(c->rois, c->keep_counts, c->im_info_dev, post, c->conn.min_score, c->tl_boxes, c->tl_scores, c->tl_counts, n, p))) return rc;
     float max_scale = 0.f;
-    for (int i = 0; i < n; ++i) max_scale = sl.im_info[3 * i + 2] > max_scale ? sl.im_info[3 * i + 2] : max_scale;
+    const float* info = sl.im_info.as<float>();
+    for (int i = 0; i < n; ++i) max_scale = info[3 * i + 2] > max_scale ? info[3 * i + 2] : max_scale;
     if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, tl_thresh, max_scale)) {
       const bool mw = nms_multi_wg(c, n, 0);
       if (nms_form) *nms_form = mw ? 2 : 1;
@@ -33,8 +34,8 @@ static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hip
     // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect)
     if ((rc = launch_connect(c->tl_boxes, c->tl_scores, c->tl_keep, c->tl_keep_counts, post, c->im_info_dev, c->conn_recs, c->conn_counts,
                              c->conn_scratch, CONN_CAP, n, c->conn, p))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs, c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
-    CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt, c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs.as<double>(), c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt.as<int>(), c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
   }
   return CTPN_OK;
 }
@@ -80,19 +81,20 @@ static int detect_submit_body(ctpn_ctx* c, const uint8_t* images, int images_on_
   // im_info row i = [the image's own height, w, scale]: what the proposal layer clips to, and lines_prep, the connector's NMS and connect_kernel read
   sl.hts.assign(n, h);
   if (heights) sl.hts.assign(heights, heights + n);
-  for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)sl.hts[i]; sl.im_info[3 * i + 1] = (float)w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
+  float* info = sl.im_info.as<float>();
+  for (int i = 0; i < n; ++i) { info[3 * i] = (float)sl.hts[i]; info[3 * i + 1] = (float)w; info[3 * i + 2] = scales ? scales[i] : 1.0f; }
   hipStream_t p = lone ? f.stream : c->stream_p;
   if (!lone) {
     CTPN_HIP_TRY(hipEventRecord(sl.ev_heads, f.stream));
     CTPN_HIP_TRY(hipStreamWaitEvent(p, sl.ev_heads, 0));
   }
   // cfg.TEST.RPN_* (reference lib/fast_rcnn/config.py:175-183): the ctx's parameters, those defaults unless ctpn_set_param changed them
-  rc = enqueue_proposals(c, f.heads, 0, n, lvl(h, 4), lvl(w, 4), sl.im_info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded,
-                         f.fwd_ragged >= 0 ? c->ragged[f.fwd_ragged].dev + n : nullptr);
+  rc = enqueue_proposals(c, f.heads, 0, n, lvl(h, 4), lvl(w, 4), info, c->rpn_pre, c->rpn_post, c->rpn_nms_thresh, c->rpn_min_size, p, sl.ev_decoded,
+                         f.fwd_ragged >= 0 ? c->ragged[f.fwd_ragged].dev.as<int>() + n : nullptr);
   if (rc) return rc;
   f.ev_decoded = sl.ev_decoded; f.dec_slot = slot;      // the reader of this set's `heads` (forward_impl: wait_decoded)
   if ((rc = enqueue_text_lines(c, sl, n, w, p))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(sl.pack, c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));      // tl_* (host connector), rois, counts: one copy
+  CTPN_HIP_TRY(hipMemcpyAsync(sl.pack.get(), c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));      // tl_* (host connector), rois, counts: one copy
   CTPN_HIP_TRY(hipEventRecord(sl.ev_done, p));
   c->ev_last_done = sl.ev_done;
   sl.n = n; sl.h = h; sl.w = w; sl.busy = true; sl.set = (int)(&f - c->fs);
@@ -113,11 +115,12 @@ static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, int mode
   const ConnectorCfg cfg = c->conn;      // the workers' copy
   if (c->connect_device) {
     for (int i = 0; i < n; ++i) {
-      if (sl.ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
-      const int cnt = sl.ccnt[3 * i + (mode == CTPN_MODE_O ? 1 : 0)];
+      const int* ccnt = sl.ccnt.as<int>();
+      if (ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
+      const int cnt = ccnt[3 * i + (mode == CTPN_MODE_O ? 1 : 0)];
       line_counts[i] = cnt;
       if (cnt > line_capacity || cnt > CONN_CAP) return fail(CTPN_ERR_CAPACITY, "ctpn_detect: more lines than line_capacity");
-      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * CONN_CAP * 9, (size_t)cnt * 9 * sizeof(double));
+      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs.as<double>() + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * CONN_CAP * 9, (size_t)cnt * 9 * sizeof(double));
     }
     return CTPN_OK;
   }
@@ -163,18 +166,19 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
   ctpn_ctx::Slot& sl = c->slot[0];
   hipStream_t p = c->stream_p;
   sl.hts.assign(n, im_h);
-  for (int i = 0; i < n; ++i) { sl.im_info[3 * i] = (float)im_h; sl.im_info[3 * i + 1] = (float)im_w; sl.im_info[3 * i + 2] = scales ? scales[i] : 1.0f; }
+  float* info = sl.im_info.as<float>();
+  for (int i = 0; i < n; ++i) { info[3 * i] = (float)im_h; info[3 * i + 1] = (float)im_w; info[3 * i + 2] = scales ? scales[i] : 1.0f; }
   if (c->nms_mw_scratch && c->nms_mw_dirty) {       // as enqueue_proposals does in front of a submit's tail
     CTPN_HIP_TRY(hipMemsetAsync(c->nms_mw_scratch, 0, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, p));
     c->nms_mw_dirty = false;
   }
-  CTPN_HIP_TRY(hipMemcpyAsync(c->im_info_dev, sl.im_info, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, p));
+  CTPN_HIP_TRY(hipMemcpyAsync(c->im_info_dev, info, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, p));
   if (post == post_max) CTPN_HIP_TRY(hipMemcpyAsync(c->rois, rois, (size_t)n * post * 5 * sizeof(float), hipMemcpyHostToDevice, p));
   else CTPN_HIP_TRY(hipMemcpy2DAsync(c->rois, (size_t)post * 5 * sizeof(float), rois, (size_t)post_max * 5 * sizeof(float), (size_t)post * 5 * sizeof(float), n, hipMemcpyHostToDevice, p));
   CTPN_HIP_TRY(hipMemcpyAsync(c->keep_counts, roi_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, p));
   int form = 0, rc;
   if ((rc = enqueue_text_lines(c, sl, n, im_w, p, &form))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(sl.pack, c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));
+  CTPN_HIP_TRY(hipMemcpyAsync(sl.pack.get(), c->out_pack, c->pack_bytes, hipMemcpyDeviceToHost, p));
   CTPN_HIP_TRY(hipStreamSynchronize(p));
   for (int i = 0; i < n; ++i)
     if (sl.kcnt[i] < 0 || sl.kcnt[i] > post) return fail(CTPN_ERR_HIP, "ctpn_debug_text_lines: device returned an impossible keep count");
@@ -276,40 +280,37 @@ int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im
   CTPN_HIP_TRY(hipSetDevice(device_id));
   const int post = 1000;
   const ConnectorCfg cfg = default_connector_cfg();       // a stateless hook: the defaults
-  char* buf = nullptr;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
   const size_t o_rois = take((size_t)(post + 1) * 5 * 4), o_cnt = take(16), o_info = take(16), o_tlb = take((size_t)post * 16), o_tls = take((size_t)post * 4),
                o_tlc = take(16), o_keep = take((size_t)post * 4), o_kc = take(16), o_spill = take((size_t)post * 16),
                o_recs = take((size_t)2 * CONN_CAP * 9 * 8), o_cc = take(16), o_scr = take((size_t)1024 * 20 * 8);
-  CTPN_HIP_TRY(hipMalloc((void**)&buf, off));
-  hipStream_t st = nullptr;
-  int rc = CTPN_OK;
-  auto done = [&](int code) { if (st) (void)hipStreamDestroy(st); (void)hipFree(buf); return code; };
-#define DC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return done(fail(CTPN_ERR_HIP, std::string("ctpn_debug_connect: ") + hipGetErrorString(e_))); } while (0)
-  DC_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  DC_TRY(hipMemsetAsync(buf, 0, off, st));
+  Stream st;
+  DevBuf block;      // released before the stream, on every way out
+  int rc;
+  if ((rc = block.alloc(off)) || (rc = st.ensure())) return rc;
+  char* buf = block.as<char>();
+  CTPN_HIP_TRY(hipMemsetAsync(buf, 0, off, st));
   const float info[3] = {(float)im_h, (float)im_w, scale};
-  if (r) DC_TRY(hipMemcpyAsync(buf + o_rois, rois, (size_t)r * 5 * 4, hipMemcpyHostToDevice, st));
-  DC_TRY(hipMemcpyAsync(buf + o_cnt, &r, 4, hipMemcpyHostToDevice, st));
-  DC_TRY(hipMemcpyAsync(buf + o_info, info, 12, hipMemcpyHostToDevice, st));
+  if (r) CTPN_HIP_TRY(hipMemcpyAsync(buf + o_rois, rois, (size_t)r * 5 * 4, hipMemcpyHostToDevice, st));
+  CTPN_HIP_TRY(hipMemcpyAsync(buf + o_cnt, &r, 4, hipMemcpyHostToDevice, st));
+  CTPN_HIP_TRY(hipMemcpyAsync(buf + o_info, info, 12, hipMemcpyHostToDevice, st));
   if ((rc = launch_lines_prep((const float*)(buf + o_rois), (const int*)(buf + o_cnt), (const float*)(buf + o_info), post, cfg.min_score, (float*)(buf + o_tlb),
-                              (float*)(buf + o_tls), (int*)(buf + o_tlc), 1, st))) return done(rc);
+                              (float*)(buf + o_tls), (int*)(buf + o_tlc), 1, st))) return rc;
   if ((rc = launch_nms((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_tlc), post, cfg.nms_thresh, post, (int*)(buf + o_keep), post,
-                       (int*)(buf + o_kc), nullptr, (float*)(buf + o_spill), 1, st))) return done(rc);
+                       (int*)(buf + o_kc), nullptr, (float*)(buf + o_spill), 1, st))) return rc;
   if ((rc = launch_connect((const float*)(buf + o_tlb), (const float*)(buf + o_tls), (const int*)(buf + o_keep), (const int*)(buf + o_kc), post,
-                           (const float*)(buf + o_info), (double*)(buf + o_recs), (int*)(buf + o_cc), (double*)(buf + o_scr), CONN_CAP, 1, cfg, st))) return done(rc);
+                           (const float*)(buf + o_info), (double*)(buf + o_recs), (int*)(buf + o_cc), (double*)(buf + o_scr), CONN_CAP, 1, cfg, st))) return rc;
   int cc[3] = {0, 0, 0};
-  DC_TRY(hipMemcpyAsync(cc, buf + o_cc, 12, hipMemcpyDeviceToHost, st));
-  DC_TRY(hipStreamSynchronize(st));
-  if (cc[2] != 0) return done(fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)"));
+  CTPN_HIP_TRY(hipMemcpyAsync(cc, buf + o_cc, 12, hipMemcpyDeviceToHost, st));
+  CTPN_HIP_TRY(hipStreamSynchronize(st));
+  if (cc[2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
   const int cnt = cc[mode == CTPN_MODE_O ? 1 : 0];
   *count_out = cnt;
-  if (cnt > capacity || cnt > CONN_CAP) return done(fail(CTPN_ERR_CAPACITY, "ctpn_debug_connect: more lines than capacity"));
-  if (cnt && !recs_out) return done(fail(CTPN_ERR_ARG, "ctpn_debug_connect: recs_out is null"));
-  if (cnt) DC_TRY(hipMemcpy(recs_out, buf + o_recs + (size_t)(mode == CTPN_MODE_O ? 1 : 0) * CONN_CAP * 9 * 8, (size_t)cnt * 9 * 8, hipMemcpyDeviceToHost));
-#undef DC_TRY
-  return done(CTPN_OK);
+  if (cnt > capacity || cnt > CONN_CAP) return fail(CTPN_ERR_CAPACITY, "ctpn_debug_connect: more lines than capacity");
+  if (cnt && !recs_out) return fail(CTPN_ERR_ARG, "ctpn_debug_connect: recs_out is null");
+  if (cnt) CTPN_HIP_TRY(hipMemcpy(recs_out, buf + o_recs + (size_t)(mode == CTPN_MODE_O ? 1 : 0) * CONN_CAP * 9 * 8, (size_t)cnt * 9 * 8, hipMemcpyDeviceToHost));
+  return CTPN_OK;
 }
 
 int ctpn_debug_text_lines(ctpn_ctx* c, const float* rois, const int* roi_counts, int n, int im_h, int im_w, const float* scales, int mode,

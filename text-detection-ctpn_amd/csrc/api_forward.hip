@@ -17,14 +17,13 @@ static void parallel_memcpy(HostPool* pool, void* dst, const void* src, size_t b
 
 // a ragged batch's heights on their way to the device: [heights(n) | feature rows(n)] through the set's page-locked array, copied on s
 static int ragged_upload(ctpn_ctx* c, ctpn_ctx::RaggedSet& r, const int* heights, int n, hipStream_t s) {
-  if (!r.host) {
-    CTPN_HIP_TRY(hipHostMalloc((void**)&r.host, (size_t)c->max_batch * 2 * sizeof(int)));
-    CTPN_HIP_TRY(hipMalloc((void**)&r.dev, (size_t)c->max_batch * 2 * sizeof(int)));
-    CTPN_HIP_TRY(hipEventCreateWithFlags(&r.ev_copied, hipEventDisableTiming));
-  }
+  const size_t bytes = (size_t)c->max_batch * 2 * sizeof(int);
+  int rc;
+  if ((rc = r.host.grow(bytes)) || (rc = r.dev.grow(bytes)) || (rc = r.ev_copied.ensure())) return rc;      // on the set's first use
   if (r.copied_valid) CTPN_HIP_TRY(hipEventSynchronize(r.ev_copied));      // the copy that last read the page-locked array (long done)
-  for (int i = 0; i < n; ++i) { r.host[i] = heights[i]; r.host[n + i] = ragged_valid_rows(heights[i], 4); }
-  CTPN_HIP_TRY(hipMemcpyAsync(r.dev, r.host, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
+  int* host = r.host.as<int>();
+  for (int i = 0; i < n; ++i) { host[i] = heights[i]; host[n + i] = ragged_valid_rows(heights[i], 4); }
+  CTPN_HIP_TRY(hipMemcpyAsync(r.dev.get(), host, (size_t)n * 2 * sizeof(int), hipMemcpyHostToDevice, s));
   CTPN_HIP_TRY(hipEventRecord(r.ev_copied, s));
   r.copied_valid = true;
   return CTPN_OK;
@@ -116,16 +115,14 @@ int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f3
       // instead of 11.4 ms / step). Stage it here instead: host memcpy into a page-locked buffer of the ctx (this thread,
       // while the GPU works on the previous batch), then a truly asynchronous copy.
       (void)hipGetLastError();
-      if (c->pin_stage_bytes[staged] < bytes) {
-        if (c->pin_stage[staged]) { CTPN_HIP_TRY(hipStreamSynchronize(c->stream_c)); CTPN_HIP_TRY(hipHostFree(c->pin_stage[staged])); c->pin_stage[staged] = nullptr; }
-        CTPN_HIP_TRY(hipHostMalloc(&c->pin_stage[staged], bytes));
-        c->pin_stage_bytes[staged] = bytes;
-        if (!c->ev_h2d_done[staged]) CTPN_HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d_done[staged], hipEventDisableTiming));
+      if (c->pin_stage[staged].bytes() < bytes) {
+        if (c->pin_stage[staged]) CTPN_HIP_TRY(hipStreamSynchronize(c->stream_c));      // a copy may still read the block that goes
         c->h2d_valid[staged] = false;
+        if ((rc = c->pin_stage[staged].grow(bytes)) || (rc = c->ev_h2d_done[staged].ensure())) return rc;
       }
       if (c->h2d_valid[staged]) CTPN_HIP_TRY(hipEventSynchronize(c->ev_h2d_done[staged]));   // the copy that last read this staging buffer
-      parallel_memcpy(c->pool.get(), c->pin_stage[staged], images, bytes);
-      src = c->pin_stage[staged];
+      parallel_memcpy(c->pool.get(), c->pin_stage[staged].get(), images, bytes);
+      src = c->pin_stage[staged].get();
     }
     CTPN_HIP_TRY(hipMemcpyAsync(c->img_dev_b[staged], src, bytes, hipMemcpyHostToDevice, c->stream_c));
     if (!locked) { CTPN_HIP_TRY(hipEventRecord(c->ev_h2d_done[staged], c->stream_c)); c->h2d_valid[staged] = true; }
@@ -139,12 +136,12 @@ int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f3
   const int* hts_dev = nullptr;
   if (ragged) {
     if ((rc = ragged_upload(c, c->ragged[rset], heights, n, s))) return rc;
-    hts_dev = c->ragged[rset].dev;
+    hts_dev = c->ragged[rset].dev.as<int>();
   }
   int jpeg_src = -1;
   if (images_on_device && c->jpeg_ready)
     for (int b = 0; b < 2; ++b)
-      if (c->jpeg[b].ready_valid && images == (const void*)c->jpeg[b].out_dev) {      // decoded on stream_c: the forward waits for its kernels, not the host
+      if (c->jpeg[b].ready_valid && images == c->jpeg[b].out_dev.get()) {      // decoded on stream_c: the forward waits for its kernels, not the host
         CTPN_HIP_TRY(hipStreamWaitEvent(s, c->jpeg[b].ev_ready, 0));
         jpeg_src = b;
       }
@@ -176,12 +173,12 @@ int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f3
       // the kernels that read raw pixels (fp32, split precision; the 16-bit modes with conv1_kernel < 2) take the float feed instead, which they
       // compute identically (ctpn_forward_blob): p - mean inside an image, 0.0f below it
       const size_t need = (size_t)n * h * w * 3 * sizeof(float);
-      if (need > f.ragged_blob_bytes) {
+      if (need > f.ragged_blob.bytes()) {
         CTPN_HIP_TRY(hipStreamSynchronize(s));      // an earlier ragged forward may still read the block that goes
-        if ((rc = grow_dev((void**)&f.ragged_blob, f.ragged_blob_bytes, need))) return rc;
+        if ((rc = f.ragged_blob.grow(need))) return rc;
       }
-      if ((rc = launch_ragged_blob((const uint8_t*)img, f.ragged_blob, hts_dev, n, h, w, s))) return rc;
-      if ((rc = launch_conv_first(f.ragged_blob, 1, c->w_first, c->b_conv[0], f.act_conv[0], c->prec, n, h, w, s,
+      if ((rc = launch_ragged_blob((const uint8_t*)img, f.ragged_blob.as<float>(), hts_dev, n, h, w, s))) return rc;
+      if ((rc = launch_conv_first(f.ragged_blob.get(), 1, c->w_first, c->b_conv[0], f.act_conv[0], c->prec, n, h, w, s,
                                   frags ? c->w_first_frags : nullptr))) return rc;
     } else if ((rc = launch_conv_first(img, is_f32, c->w_first, c->b_conv[0], f.act_conv[0], c->prec, n, h, w, s,
                                        frags ? c->w_first_frags : nullptr))) return rc;
@@ -213,12 +210,11 @@ int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f3
   const bool own_strips = beside && gate == 0;
   const void* cur = f.act_conv[0];
   int pool_i = 0;
-  hipEvent_t stack_a = nullptr, stack_b = nullptr;
+  Event stack_a, stack_b;
   double stack_flops = 0.0;
   const bool stack_timed = c->prof && c->prof_mode == 2;
   if (stack_timed) {
-    auto get = [&]() { hipEvent_t e; if (!c->free_events.empty()) { e = c->free_events.back(); c->free_events.pop_back(); } else { (void)hipEventCreate(&e); } return e; };
-    stack_a = get(); stack_b = get();
+    stack_a = prof_event(c); stack_b = prof_event(c);
     CTPN_HIP_TRY(hipEventRecord(stack_a, s));
   }
   for (int i = 1; i < 14; ++i) {
@@ -246,9 +242,9 @@ int forward_impl(ctpn_ctx* c, ctpn_ctx::FwdSet& f, const void* images, int is_f3
   }
   if (stack_timed) {
     CTPN_HIP_TRY(hipEventRecord(stack_b, s));
-    ProfRec r{CTPN_KIND_CONV_GEMM, stack_a, stack_b, stack_flops};
+    ProfRec r{CTPN_KIND_CONV_GEMM, std::move(stack_a), std::move(stack_b), stack_flops};
     r.launches = 13; r.span = true;
-    c->pending.push_back(r);
+    c->pending.push_back(std::move(r));
   }
   if (two_forwards_mode() == 2 && f.ev_gate) { CTPN_HIP_TRY(hipEventRecord(f.ev_gate, s)); f.gate_valid = true; }
   const int hf = lvl(h, 4), wf = lvl(w, 4);

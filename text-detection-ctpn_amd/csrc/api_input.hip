@@ -101,21 +101,20 @@ int ctpn_resize(int device_id, const void* src, int src_is_f32, int src_on_devic
   CTPN_HIP_TRY(hipSetDevice(device_id));
   const size_t es = src_is_f32 ? 4 : 1;
   const size_t sbytes = (size_t)n * h * w * 3 * es, dbytes = (size_t)need * es;
-  void *ds = nullptr, *dd = nullptr;
-  hipStream_t st = nullptr;
-  auto cleanup = [&]() { if (ds) (void)hipFree(ds); if (dd) (void)hipFree(dd); if (st) (void)hipStreamDestroy(st); };
-#define RS_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return fail(CTPN_ERR_HIP, std::string("ctpn_resize: ") + hipGetErrorString(e_)); } } while (0)
-  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  Stream st;
+  DevBuf ds, dd;      // released before the stream, on every way out
+  if ((rc = st.ensure())) return rc;
   const void* s_in = src;
-  if (!src_on_device) { RS_TRY(hipMalloc(&ds, sbytes)); RS_TRY(hipMemcpyAsync(ds, src, sbytes, hipMemcpyHostToDevice, st)); s_in = ds; }
+  if (!src_on_device) {
+    if ((rc = ds.alloc(sbytes))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(ds.get(), src, sbytes, hipMemcpyHostToDevice, st));
+    s_in = ds.get();
+  }
   void* d_out = dst;
-  if (!dst_on_device) { RS_TRY(hipMalloc(&dd, dbytes)); d_out = dd; }
-  rc = launch_resize_linear(s_in, d_out, src_is_f32, n, h, w, dh, dw, fx, fy, st);
-  if (rc) { cleanup(); return rc; }
-  if (!dst_on_device) RS_TRY(hipMemcpyAsync(dst, dd, dbytes, hipMemcpyDeviceToHost, st));
-  RS_TRY(hipStreamSynchronize(st));
-#undef RS_TRY
-  cleanup();
+  if (!dst_on_device) { if ((rc = dd.alloc(dbytes))) return rc; d_out = dd.get(); }
+  if ((rc = launch_resize_linear(s_in, d_out, src_is_f32, n, h, w, dh, dw, fx, fy, st))) return rc;
+  if (!dst_on_device) CTPN_HIP_TRY(hipMemcpyAsync(dst, dd.get(), dbytes, hipMemcpyDeviceToHost, st));
+  CTPN_HIP_TRY(hipStreamSynchronize(st));
   return CTPN_OK;
 }
 

@@ -5,45 +5,26 @@
 
 namespace ctpn {
 
-// grow a device buffer to `need` bytes; the old allocation is retired (it may still be read by work in flight, or be held by the caller)
-static int jpeg_grow_dev(ctpn_ctx* c, void** p, size_t& have, size_t need) {
-  if (need <= have) return CTPN_OK;
-  void* q = nullptr;
-  CTPN_HIP_TRY(hipMalloc(&q, need));
-  if (*p) c->jpeg_retired.push_back(*p);
-  *p = q; have = need;
-  return CTPN_OK;
-}
-
-// a page-locked block and its device twin, `have` elements of elem_bytes each, grown to `need` elements (the copy that last read the
-// page-locked block has been waited for by the caller)
-static int jpeg_grow_pair(ctpn_ctx* c, void** host, void** dev, size_t& have, size_t need, size_t elem_bytes) {
-  if (need <= have) return CTPN_OK;
-  if (*host) CTPN_HIP_TRY(hipHostFree(*host));
-  *host = nullptr;
-  have = 0;                 // (a failed allocation below must not leave the old size standing next to a null block)
-  CTPN_HIP_TRY(hipHostMalloc(host, need * elem_bytes));
-  size_t dev_have = 0;      // the twin is as large as the block was, so it always grows: its predecessor is retired
-  if (const int rc = jpeg_grow_dev(c, dev, dev_have, need * elem_bytes)) return rc;
-  have = need;
-  return CTPN_OK;
-}
-
 // coef_total: int16 elements of the call's coefficient blocks (n x one capacity, or the sum of the files' own); tab: the ragged call's
 // descriptor table too
 static int jpeg_reserve(ctpn_ctx* c, ctpn_ctx::JpegBufs& J, size_t n, size_t coef_total, size_t raw_bytes, size_t out_bytes, bool tab) {
   if (!c->jpeg_ready) {
+    int rc;
     for (auto& j : c->jpeg)
-      for (hipEvent_t* e : {&j.ev_h2d, &j.ev_ready, &j.ev_consumed}) CTPN_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      for (Event* e : {&j.ev_h2d, &j.ev_ready, &j.ev_consumed}) if ((rc = e->ensure())) return rc;
     c->jpeg_ready = true;
   }
+  // a device block that grows is retired, not freed: work in flight may still read it, and the caller may hold a pointer into it
+  std::vector<DevBuf>& old = c->jpeg_retired;
+  // a page-locked block and its device twin (the copy that last read the page-locked block has been waited for by the caller)
+  auto pair = [&](PinnedBuf& host, DevBuf& dev, size_t bytes) { const int rc = host.grow(bytes); return rc ? rc : dev.grow_retiring(bytes, old); };
   int rc;
-  if ((rc = jpeg_grow_pair(c, (void**)&J.coef_host, (void**)&J.coef_dev, J.coef_elems, coef_total, sizeof(int16_t)))) return rc;
-  if (tab && (rc = jpeg_grow_pair(c, (void**)&J.tab_host, (void**)&J.tab_dev, J.tab_imgs, n, sizeof(JrImage)))) return rc;
-  if ((rc = jpeg_grow_pair(c, (void**)&J.qt_host, (void**)&J.qt_dev, J.qt_imgs, n, 192 * sizeof(uint16_t)))) return rc;
-  if ((rc = jpeg_grow_dev(c, (void**)&J.out_dev, J.out_bytes, out_bytes + 256))) return rc;
-  if ((rc = jpeg_grow_dev(c, (void**)&c->jpeg_planes, c->jpeg_planes_bytes, coef_total))) return rc;      // one byte per coefficient
-  if (raw_bytes && (rc = jpeg_grow_dev(c, (void**)&c->jpeg_raw, c->jpeg_raw_bytes, raw_bytes + 256))) return rc;
+  if ((rc = pair(J.coef_host, J.coef_dev, coef_total * sizeof(int16_t)))) return rc;
+  if (tab && (rc = pair(J.tab_host, J.tab_dev, n * sizeof(JrImage)))) return rc;
+  if ((rc = pair(J.qt_host, J.qt_dev, n * 192 * sizeof(uint16_t)))) return rc;
+  if ((rc = J.out_dev.grow_retiring(out_bytes + 256, old))) return rc;
+  if ((rc = c->jpeg_planes.grow_retiring(coef_total, old))) return rc;      // one byte per coefficient
+  if (raw_bytes && (rc = c->jpeg_raw.grow_retiring(raw_bytes + 256, old))) return rc;
   return CTPN_OK;
 }
 
@@ -83,30 +64,17 @@ static int jh_decode(ctpn_ctx* c, const uint8_t* const* data, const size_t* len,
   const size_t o_files = 0, o_segs = jh_up(o_files + m * sizeof(JhFile), 16), o_tabs = jh_up(o_segs + nseg * sizeof(JhSeg), 16),
                o_bytes = jh_up(o_tabs + ntab * sizeof(JhTable), 16), o_wg = jh_up(o_bytes + nbytes, 16), o_sub = o_wg + nsub_bound / WG * 4,
                stage_bound = o_sub + nsub_bound * 4;
-  if (stage_bound > W.stage_bytes) {
-    if (W.stage_host) CTPN_HIP_TRY(hipHostFree(W.stage_host));
-    if (W.stage_dev) CTPN_HIP_TRY(hipFree(W.stage_dev));
-    W.stage_host = W.stage_dev = nullptr; W.stage_bytes = 0;
-    const size_t want = stage_bound + stage_bound / 4;
-    CTPN_HIP_TRY(hipHostMalloc((void**)&W.stage_host, want));
-    CTPN_HIP_TRY(hipMalloc((void**)&W.stage_dev, want));
-    W.stage_bytes = want;
-  }
+  int rc;
+  // each block of the pair is tested on its own: where one grew and its twin could not, the next call tries the twin again
+  const size_t stage_want = stage_bound + stage_bound / 4;
+  if (stage_bound > W.stage_host.bytes() && (rc = W.stage_host.grow(stage_want))) return rc;
+  if (stage_bound > W.stage_dev.bytes() && (rc = W.stage_dev.grow(stage_want))) return rc;
   const size_t w_res = 0, w_st0 = jh_up(2 * m * 4, 16), w_st1 = w_st0 + nsub_bound * 8, w_entry = w_st1 + nsub_bound * 8, w_begun = w_entry + nsub_bound * 8,
                w_prefix = w_begun + nsub_bound * 4, work_bound = w_prefix + nsub_bound * 4;
-  if (work_bound > W.work_bytes) {
-    if (W.work_dev) CTPN_HIP_TRY(hipFree(W.work_dev));
-    W.work_dev = nullptr; W.work_bytes = 0;
-    CTPN_HIP_TRY(hipMalloc((void**)&W.work_dev, work_bound + work_bound / 4));
-    W.work_bytes = work_bound + work_bound / 4;
-  }
-  if (2 * m > W.res_words) {
-    if (W.res_host) CTPN_HIP_TRY(hipHostFree(W.res_host));
-    W.res_host = nullptr; W.res_words = 0;
-    CTPN_HIP_TRY(hipHostMalloc((void**)&W.res_host, 2 * m * 4 + 256));
-    W.res_words = 2 * m + 64;
-  }
-  uint8_t* H = W.stage_host;
+  if (work_bound > W.work_dev.bytes() && (rc = W.work_dev.grow(work_bound + work_bound / 4))) return rc;
+  if ((2 * m) * 4 > W.res_host.bytes() && (rc = W.res_host.grow(2 * m * 4 + 256))) return rc;
+  uint8_t* H = W.stage_host.as<uint8_t>();
+  uint32_t* res = W.res_host.as<uint32_t>();
   JhFile* hf = (JhFile*)(H + o_files); JhSeg* hs = (JhSeg*)(H + o_segs); JhTable* ht = (JhTable*)(H + o_tabs);
   uint32_t* hwg = (uint32_t*)(H + o_wg); uint32_t* hsub = (uint32_t*)(H + o_sub);
   // the linear pass: one file per worker
@@ -150,7 +118,7 @@ static int jh_decode(ctpn_ctx* c, const uint8_t* const* data, const size_t* len,
   if (nsub > nsub_bound) return fail(CTPN_ERR_STATE, "jpeg_huff: subsequence bound exceeded");
   for (uint32_t w = 0; w < nsub / WG; ++w) { const uint32_t si = hsub[(size_t)w * WG]; hwg[w] = si == 0xffffffffu ? 0xffffffffu : hs[si].file; }
   const size_t stage_used = o_sub + (size_t)nsub * 4;
-  uint8_t* D = W.stage_dev; uint8_t* K = W.work_dev;
+  uint8_t* D = W.stage_dev.as<uint8_t>(); uint8_t* K = W.work_dev.as<uint8_t>();
   JhBatchDev B;
   B.files = (const JhFile*)(D + o_files); B.segs = (const JhSeg*)(D + o_segs); B.tabs = (const JhTable*)(D + o_tabs);
   B.wg_file = (const uint32_t*)(D + o_wg); B.sub_seg = (const uint32_t*)(D + o_sub); B.bytes = D + o_bytes;
@@ -160,7 +128,6 @@ static int jh_decode(ctpn_ctx* c, const uint8_t* const* data, const size_t* len,
   B.coef = coef_dev; B.S = S; B.nsub = nsub; B.nseg = (uint32_t)nseg; B.nfiles = (uint32_t)m;
   CTPN_HIP_TRY(hipMemcpyAsync(D, H, stage_used, hipMemcpyHostToDevice, qs));
   CTPN_HIP_TRY(hipMemsetAsync(K + w_res, 0, 2 * m * 4, qs));
-  int rc;
   if ((rc = launch_jpeg_huff_round(B, 0, qs))) return rc;
   // sync rounds: a fixed few, then one check with the results; a file still unsettled then (rare: its components share their tables, or S is
   // small against its blocks) gets four times as many, up to the cap -- after `subsequences in the longest segment - 1` rounds every state
@@ -171,16 +138,16 @@ static int jh_decode(ctpn_ctx* c, const uint8_t* const* data, const size_t* len,
     CTPN_HIP_TRY(hipMemsetAsync(K + w_res, 0, m * 4, qs));                       // the flag words (not the rounds)
     CTPN_HIP_TRY(hipMemsetAsync(coef_dev, 0, coef_zero_elems * sizeof(int16_t), qs));
     if ((rc = launch_jpeg_huff_write(B, (int)rounds, qs))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(W.res_host, K + w_res, 2 * m * 4, hipMemcpyDeviceToHost, qs));
+    CTPN_HIP_TRY(hipMemcpyAsync(res, K + w_res, 2 * m * 4, hipMemcpyDeviceToHost, qs));
     CTPN_HIP_TRY(hipStreamSynchronize(qs));
     bool unsettled = false;
-    if (rounds < cap) for (size_t j = 0; j < m; ++j) if (W.res_host[m + j] >= rounds && rounds > 0) unsettled = true;
+    if (rounds < cap) for (size_t j = 0; j < m; ++j) if (res[m + j] >= rounds && rounds > 0) unsettled = true;
     if (!unsettled) break;
     target = (uint32_t)std::min<unsigned long long>(cap, (unsigned long long)rounds * 4);
   }
   long long ok = 0;
   for (size_t j = 0; j < m; ++j) {
-    flags_out[dev[j]] |= W.res_host[j];
+    flags_out[dev[j]] |= res[j];
     if (flags_out[dev[j]]) ++handed; else ++ok;
   }
   c->jh_stats[0] = ok; c->jh_stats[1] = handed; c->jh_stats[2] = real_subs; c->jh_stats[3] = rounds;
@@ -225,7 +192,7 @@ struct JpegDecode {
 
   // the host entropy decode of file i (bytes at dptr[i]) into its place in the page-locked blocks
   int host_file(int i, JpegGeom* g) {
-    const int rc = jpeg_entropy_decode(dptr[i], dlen[i], J->coef_host + host_off[i], cap[i], J->qt_host + (size_t)i * 192, g);
+    const int rc = jpeg_entropy_decode(dptr[i], dlen[i], J->coef_host.as<int16_t>() + host_off[i], cap[i], J->qt_host.as<uint16_t>() + (size_t)i * 192, g);
     return rc == CTPN_ERR_CAPACITY ? oversize_rc : rc;
   }
 
@@ -262,7 +229,7 @@ struct JpegDecode {
   }
 
   int copy_file(int i) {
-    CTPN_HIP_TRY(hipMemcpyAsync(J->coef_dev + dev_off[i], J->coef_host + host_off[i], (size_t)geo[i].coef_per_img * sizeof(int16_t), hipMemcpyHostToDevice, qs));
+    CTPN_HIP_TRY(hipMemcpyAsync(J->coef_dev.as<int16_t>() + dev_off[i], J->coef_host.as<int16_t>() + host_off[i], (size_t)geo[i].coef_per_img * sizeof(int16_t), hipMemcpyHostToDevice, qs));
     return CTPN_OK;
   }
 
@@ -274,8 +241,8 @@ struct JpegDecode {
     if (dev_entropy) {
       std::vector<int> use((size_t)n);
       std::vector<uint32_t> flags((size_t)n, 0u);
-      for (int i = 0; i < n; ++i) { use[i] = i; std::memcpy(J->qt_host + (size_t)i * 192, prep[i].qt, sizeof(prep[i].qt)); }
-      if ((rc = jh_decode(c, dptr.data(), dlen.data(), prep, use, JH_SUBSEQ_DEFAULT, J->coef_dev, dev_off, coef_dev_elems, qs, flags))) return rc;
+      for (int i = 0; i < n; ++i) { use[i] = i; std::memcpy(J->qt_host.as<uint16_t>() + (size_t)i * 192, prep[i].qt, sizeof(prep[i].qt)); }
+      if ((rc = jh_decode(c, dptr.data(), dlen.data(), prep, use, JH_SUBSEQ_DEFAULT, J->coef_dev.as<int16_t>(), dev_off, coef_dev_elems, qs, flags))) return rc;
       // a file with a raised flag is the host half's, alone: its status and message are the host's, its coefficients replace the device's
       for (int i = 0; i < n; ++i) {
         if (!flags[i]) continue;
@@ -283,13 +250,13 @@ struct JpegDecode {
         if ((rc = copy_file(i))) return rc;
       }
     } else if (strided)
-      CTPN_HIP_TRY(hipMemcpy2DAsync(J->coef_dev, (size_t)geo[0].coef_per_img * sizeof(int16_t), J->coef_host, cap[0] * sizeof(int16_t), (size_t)geo[0].coef_per_img * sizeof(int16_t),
+      CTPN_HIP_TRY(hipMemcpy2DAsync(J->coef_dev.as<int16_t>(), (size_t)geo[0].coef_per_img * sizeof(int16_t), J->coef_host.as<int16_t>(), cap[0] * sizeof(int16_t), (size_t)geo[0].coef_per_img * sizeof(int16_t),
                                     (size_t)n, hipMemcpyHostToDevice, qs));
     else
       for (int i = 0; i < n; ++i)      // every file's own coefficients (its capacity is the largest any layout of its size needs: up to twice as many)
         if ((rc = copy_file(i))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(J->qt_dev, J->qt_host, (size_t)n * 192 * sizeof(uint16_t), hipMemcpyHostToDevice, qs));
-    if (tab) CTPN_HIP_TRY(hipMemcpyAsync(J->tab_dev, J->tab_host, (size_t)n * sizeof(JrImage), hipMemcpyHostToDevice, qs));
+    CTPN_HIP_TRY(hipMemcpyAsync(J->qt_dev.as<uint16_t>(), J->qt_host.as<uint16_t>(), (size_t)n * 192 * sizeof(uint16_t), hipMemcpyHostToDevice, qs));
+    if (tab) CTPN_HIP_TRY(hipMemcpyAsync(J->tab_dev.get(), J->tab_host.get(), (size_t)n * sizeof(JrImage), hipMemcpyHostToDevice, qs));
     CTPN_HIP_TRY(hipEventRecord(J->ev_h2d, qs));
     J->h2d_valid = true;
     return CTPN_OK;
@@ -334,11 +301,11 @@ static int jpeg_decode_uniform(ctpn_ctx* c, const JpegSource& src, int n, int h,
   D.coef_dev_elems = (size_t)n * g.coef_per_img;
   if ((rc = D.upload())) return rc;
   auto& J = *D.J;
-  if ((rc = launch_jpeg_pixels(J.coef_dev, J.qt_dev, c->jpeg_planes, resize ? c->jpeg_raw : J.out_dev, g, n, D.qs))) return rc;
+  if ((rc = launch_jpeg_pixels(J.coef_dev.as<int16_t>(), J.qt_dev.as<uint16_t>(), c->jpeg_planes.as<uint8_t>(), resize ? c->jpeg_raw.as<uint8_t>() : J.out_dev.as<uint8_t>(), g, n, D.qs))) return rc;
   // resize_im (reference ctpn/demo.py:21-25: cv2.resize, INTER_LINEAR) of the decoded batch, in the same queue
-  if (resize && (rc = launch_resize_linear(c->jpeg_raw, J.out_dev, 0, n, h, w, dh, dw, fx, fy, D.qs))) return rc;
+  if (resize && (rc = launch_resize_linear(c->jpeg_raw.as<uint8_t>(), J.out_dev.as<uint8_t>(), 0, n, h, w, dh, dw, fx, fy, D.qs))) return rc;
   if ((rc = D.publish(dh, dw))) return rc;
-  *images_dev_out = J.out_dev;
+  *images_dev_out = J.out_dev.as<uint8_t>();
   if (out_h) *out_h = dh;
   if (out_w) *out_w = dw;
   return CTPN_OK;
@@ -380,7 +347,7 @@ static int jpeg_decode_ragged(ctpn_ctx* c, const JpegSource& src, int n, const i
       return fail(CTPN_ERR_ARG, who + "file " + std::to_string(i) + " is not " + std::to_string(file_h[i]) + " x " + std::to_string(file_w[i]) + " (as cv2.imread returns it: EXIF orientation applied)");
   auto& J = *D.J;
   // the descriptor table
-  JrImage* tab = (JrImage*)J.tab_host;
+  JrImage* tab = J.tab_host.as<JrImage>();
   long long blocks = 0;
   for (int i = 0; i < n; ++i) {
     JrImage& d = tab[i];
@@ -394,9 +361,9 @@ static int jpeg_decode_ragged(ctpn_ctx* c, const JpegSource& src, int n, const i
     blocks += D.geo[i].blocks_per_img;
   }
   if ((rc = D.upload())) return rc;
-  if ((rc = launch_jpeg_pixels_ragged(J.coef_dev, J.qt_dev, c->jpeg_planes, J.out_dev, (const JrImage*)J.tab_dev, n, blocks, hc, wc, D.qs))) return rc;
+  if ((rc = launch_jpeg_pixels_ragged(J.coef_dev.as<int16_t>(), J.qt_dev.as<uint16_t>(), c->jpeg_planes.as<uint8_t>(), J.out_dev.as<uint8_t>(), J.tab_dev.as<JrImage>(), n, blocks, hc, wc, D.qs))) return rc;
   if ((rc = D.publish(hc, wc))) return rc;
-  *canvas_dev_out = J.out_dev;
+  *canvas_dev_out = J.out_dev.as<uint8_t>();
   for (int i = 0; i < n; ++i) heights_out[i] = hts[i];
   return CTPN_OK;
 }
@@ -474,9 +441,10 @@ int ctpn_jpeg_entropy_decode_device(ctpn_ctx* c,const uint8_t* const* files, con
   }
   c->jh_stats[0] = c->jh_stats[1] = c->jh_stats[2] = c->jh_stats[3] = 0;
   if (use.empty()) return CTPN_OK;
-  int16_t* coef_dev = nullptr;
   const size_t elems = (size_t)n * coef_capacity_per_file;
-  CTPN_HIP_TRY(hipMalloc((void**)&coef_dev, elems * sizeof(int16_t)));
+  DevBuf coef_buf;      // released on every way out (the release waits for what the queue still does with it)
+  if (const int rc = coef_buf.alloc(elems * sizeof(int16_t))) return rc;
+  int16_t* coef_dev = coef_buf.as<int16_t>();
   hipStream_t qs = c->stream_c;
   int rc = jh_decode(c, files, sizes, prep, use, (uint32_t)subseq_bits, coef_dev, coef_base, elems, qs, flags);
   for (int i : use) {
@@ -486,7 +454,6 @@ int ctpn_jpeg_entropy_decode_device(ctpn_ctx* c,const uint8_t* const* files, con
       rc = fail(CTPN_ERR_HIP, "ctpn_jpeg_entropy_decode_device: copy of the coefficients failed");
   }
   if (!rc && hipStreamSynchronize(qs) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_jpeg_entropy_decode_device: queue failed");
-  (void)hipFree(coef_dev);
   if (rc) return rc;
   for (int i : use) {
     int* l8 = layout8_out + 8 * (size_t)i;
@@ -509,12 +476,12 @@ int ctpn_jpeg_entropy_device_stats(ctpn_ctx* c, long long* out4) {
 int ctpn_jpeg_batch_fetch(ctpn_ctx* c, const uint8_t* images_dev, uint8_t* host_out, size_t capacity) {
   if (!c || !images_dev || !host_out) return fail(CTPN_ERR_ARG, "ctpn_jpeg_batch_fetch: null pointer");
   for (auto& J : c->jpeg)
-    if (J.ready_valid && J.out_dev == images_dev) {
+    if (J.ready_valid && J.out_dev.as<uint8_t>() == images_dev) {
       const size_t bytes = (size_t)J.out_n * J.out_h * J.out_w * 3;
       if (capacity < bytes) return fail(CTPN_ERR_CAPACITY, "ctpn_jpeg_batch_fetch: capacity too small");
       CTPN_HIP_TRY(hipSetDevice(c->device));
       CTPN_HIP_TRY(hipEventSynchronize(J.ev_ready));
-      CTPN_HIP_TRY(hipMemcpy(host_out, J.out_dev, bytes, hipMemcpyDeviceToHost));
+      CTPN_HIP_TRY(hipMemcpy(host_out, J.out_dev.as<uint8_t>(), bytes, hipMemcpyDeviceToHost));
       return CTPN_OK;
     }
   return fail(CTPN_ERR_STATE, "ctpn_jpeg_batch_fetch: not a live batch of ctpn_decode_jpeg_batch");

@@ -12,31 +12,18 @@ namespace ctpn {
 // room for coef_elems coefficients on the device and in the page-locked block
 static int enc_reserve_coef(ctpn_ctx* c, size_t coef_elems) {
   auto& E = c->enc;
-  if (!E.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&E.ev_done, hipEventDisableTiming));
-  if (coef_elems > E.coef_elems) {
-    if (E.coef_host) CTPN_HIP_TRY(hipHostFree(E.coef_host));
-    E.coef_host = nullptr;
-    size_t have = E.coef_elems * sizeof(int16_t);
-    E.coef_elems = 0;
-    int rc = grow_dev((void**)&E.coef_dev, have, coef_elems * sizeof(int16_t));
-    if (rc) return rc;
-    CTPN_HIP_TRY(hipHostMalloc((void**)&E.coef_host, coef_elems * sizeof(int16_t)));
-    E.coef_elems = coef_elems;
-  }
-  return CTPN_OK;
+  int rc;
+  if ((rc = E.ev_done.ensure()) || (rc = E.coef_dev.grow(coef_elems * sizeof(int16_t)))) return rc;
+  return E.coef_host.grow(coef_elems * sizeof(int16_t));
 }
 
 static int enc_reserve(ctpn_ctx* c, size_t coef_elems, int quality) {
   auto& E = c->enc;
-  const int rc = enc_reserve_coef(c, coef_elems);
-  if (rc) return rc;
-  if (!E.qtab_dev) {
-    CTPN_HIP_TRY(hipMalloc(&E.qtab_dev, 128 * sizeof(JencQ)));
-    CTPN_HIP_TRY(hipHostMalloc(&E.qtab_host, 128 * sizeof(JencQ)));
-  }
+  int rc;
+  if ((rc = enc_reserve_coef(c, coef_elems)) || (rc = E.qtab_dev.grow(128 * sizeof(JencQ))) || (rc = E.qtab_host.grow(128 * sizeof(JencQ)))) return rc;      // the tables: on first use
   if (E.qtab_quality != quality) {      // (the copy of the previous call has long finished: that call waited for its coefficients)
-    jpeg_enc_qtables(quality, nullptr, (JencQ*)E.qtab_host);
-    CTPN_HIP_TRY(hipMemcpyAsync(E.qtab_dev, E.qtab_host, 128 * sizeof(JencQ), hipMemcpyHostToDevice, c->stream_c));
+    jpeg_enc_qtables(quality, nullptr, E.qtab_host.as<JencQ>());
+    CTPN_HIP_TRY(hipMemcpyAsync(E.qtab_dev.get(), E.qtab_host.get(), 128 * sizeof(JencQ), hipMemcpyHostToDevice, c->stream_c));
     E.qtab_quality = quality;
   }
   return CTPN_OK;
@@ -66,8 +53,8 @@ static int enc_stage_table(ctpn_ctx* c, const EncPlan& P, const EncSource& src, 
   auto& E = c->enc;
   const size_t bytes = (size_t)P.n() * sizeof(JemImage);
   int rc;
-  if ((rc = grow_host(&E.mix_host, E.mix_host_bytes, bytes)) || (rc = grow_dev((void**)&E.mix_dev, E.mix_bytes, bytes))) return rc;
-  JemImage* tab = (JemImage*)E.mix_host;
+  if ((rc = E.mix_host.grow(bytes)) || (rc = E.mix_dev.grow(bytes))) return rc;
+  JemImage* tab = E.mix_host.as<JemImage>();
   for (int i = 0; i < P.n(); ++i) {
     const JpegGeom& g = P.g[i];
     jem_describe(tab[i], g.h, g.w, (long long)src.pitches[i], (long long)src.offsets[i]);
@@ -78,7 +65,7 @@ static int enc_stage_table(ctpn_ctx* c, const EncPlan& P, const EncSource& src, 
   items = jem_prefix(tab, P.n(), &coef_total);
   if (items < 0) return fail(CTPN_ERR_ARG, "jpeg encode: more than 2^31 - 1 work items in one call");
   if ((size_t)coef_total != P.coef_elems) return fail(CTPN_ERR_STATE, "jpeg encode: descriptor and geometry disagree");
-  CTPN_HIP_TRY(hipMemcpyAsync(E.mix_dev, tab, bytes, hipMemcpyHostToDevice, c->stream_c));
+  CTPN_HIP_TRY(hipMemcpyAsync(E.mix_dev.get(), tab, bytes, hipMemcpyHostToDevice, c->stream_c));
   return CTPN_OK;
 }
 
@@ -90,13 +77,13 @@ static int enc_enqueue(ctpn_ctx* c, const uint8_t* pixels_dev, const EncPlan& P,
   if (rc) return rc;
   auto& E = c->enc;
   if (!src) {
-    if ((rc = launch_jpeg_fdct(pixels_dev, E.coef_dev, (const JencQ*)E.qtab_dev, P.g[0], P.n(), c->stream_c))) return rc;
+    if ((rc = launch_jpeg_fdct(pixels_dev, E.coef_dev.as<int16_t>(), E.qtab_dev.as<JencQ>(), P.g[0], P.n(), c->stream_c))) return rc;
   } else {
     long long items = 0;
     if ((rc = enc_stage_table(c, P, *src, items))) return rc;
-    if ((rc = launch_jpeg_fdct_mixed(pixels_dev, E.coef_dev, (const JencQ*)E.qtab_dev, (const JemImage*)E.mix_dev, P.n(), items, c->stream_c))) return rc;
+    if ((rc = launch_jpeg_fdct_mixed(pixels_dev, E.coef_dev.as<int16_t>(), E.qtab_dev.as<JencQ>(), E.mix_dev.as<JemImage>(), P.n(), items, c->stream_c))) return rc;
   }
-  if (!device_entropy) CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host, E.coef_dev, P.coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
+  if (!device_entropy) CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host.as<int16_t>(), E.coef_dev.as<int16_t>(), P.coef_elems * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
   CTPN_HIP_TRY(hipEventRecord(E.ev_done, c->stream_c));
   return CTPN_OK;
 }
@@ -142,29 +129,30 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
   const size_t m = use.size();
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   int rc;
-  if ((rc = grow_host(&E.huff_host, E.huff_host_bytes, m * (sizeof(JheImg) + sizeof(JheRes))))) return rc;
-  JheImg* imgs = (JheImg*)E.huff_host;
-  JheRes* res = (JheRes*)(E.huff_host + m * sizeof(JheImg));
+  if ((rc = E.huff_host.grow(m * (sizeof(JheImg) + sizeof(JheRes))))) return rc;
+  JheImg* imgs = E.huff_host.as<JheImg>();
+  JheRes* res = (JheRes*)(E.huff_host.as<uint8_t>() + m * sizeof(JheImg));
   for (size_t k = 0; k < m; ++k) imgs[k] = jobs[use[k]].img;
   JheTotals t;
   jhe_layout(imgs, m, t);
   const size_t o_img = 0, o_res = up(o_img + m * sizeof(JheImg)), o_len = up(o_res + m * sizeof(JheRes)), o_cnt = up(o_len + (size_t)t.blk * 4),
                o_uns = up(o_cnt + (size_t)t.chunks * 4), o_out = up(o_uns + (size_t)t.words * 4), total = o_out + t.outb;
-  if ((rc = grow_dev((void**)&E.huff_dev, E.huff_bytes, total))) return rc;
+  if ((rc = E.huff_dev.grow(total))) return rc;
+  uint8_t* huff = E.huff_dev.as<uint8_t>();
   if (!E.huff_tab_dev) {
     static const JheTables T = [] { JheTables t; jhe_build_tables(t); return t; }();
-    CTPN_HIP_TRY(hipMalloc(&E.huff_tab_dev, sizeof(JheTables)));
-    CTPN_HIP_TRY(hipMemcpy(E.huff_tab_dev, &T, sizeof(JheTables), hipMemcpyHostToDevice));
+    if ((rc = E.huff_tab_dev.alloc(sizeof(JheTables)))) return rc;
+    CTPN_HIP_TRY(hipMemcpy(E.huff_tab_dev.get(), &T, sizeof(JheTables), hipMemcpyHostToDevice));
   }
   JheBatchDev B;
-  B.imgs = (const JheImg*)(E.huff_dev + o_img); B.res = (JheRes*)(E.huff_dev + o_res); B.len = (uint32_t*)(E.huff_dev + o_len); B.cnt = (uint32_t*)(E.huff_dev + o_cnt);
-  B.uns = (uint32_t*)(E.huff_dev + o_uns); B.out = E.huff_dev + o_out; B.coef = E.coef_dev; B.tables = (const JheTables*)E.huff_tab_dev;
+  B.imgs = (const JheImg*)(huff + o_img); B.res = (JheRes*)(huff + o_res); B.len = (uint32_t*)(huff + o_len); B.cnt = (uint32_t*)(huff + o_cnt);
+  B.uns = (uint32_t*)(huff + o_uns); B.out = huff + o_out; B.coef = E.coef_dev.as<int16_t>(); B.tables = E.huff_tab_dev.as<JheTables>();
   B.n = (int)m; B.max_blocks = t.max_blocks; B.max_chunks = t.max_chunks;
-  CTPN_HIP_TRY(hipMemcpyAsync(E.huff_dev + o_img, imgs, m * sizeof(JheImg), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_res, 0, m * sizeof(JheRes), qs));
-  CTPN_HIP_TRY(hipMemsetAsync(E.huff_dev + o_uns, 0, (size_t)t.words * 4, qs));      // the write pass ORs shared words into it
+  CTPN_HIP_TRY(hipMemcpyAsync(huff + o_img, imgs, m * sizeof(JheImg), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(huff + o_res, 0, m * sizeof(JheRes), qs));
+  CTPN_HIP_TRY(hipMemsetAsync(huff + o_uns, 0, (size_t)t.words * 4, qs));      // the write pass ORs shared words into it
   if ((rc = launch_jpeg_huff_enc(B, zigzag, qs))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(res, E.huff_dev + o_res, m * sizeof(JheRes), hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(res, huff + o_res, m * sizeof(JheRes), hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(E.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
   c->jhe_stats[3] += (long long)(m * sizeof(JheRes));
@@ -176,7 +164,7 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
     J.scan_have = J.path ? J.scan_bytes : (J.out ? std::min(J.scan_bytes, J.capacity) : 0);
     scan_total += up(J.scan_have);
   }
-  if ((rc = grow_host(&E.scan_host, E.scan_host_bytes, scan_total))) return rc;
+  if ((rc = E.scan_host.grow(scan_total))) return rc;
   size_t at = 0;
   bool copies = false;
   for (size_t k = 0; k < m; ++k) {
@@ -185,14 +173,14 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
       ++c->jhe_stats[1];
       if (J.coef_host) continue;
       const size_t bytes = (size_t)imgs[k].nblk * 64 * sizeof(int16_t);
-      CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + J.img.coef_off, E.coef_dev + J.img.coef_off, bytes, hipMemcpyDeviceToHost, qs));
+      CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host.as<int16_t>() + J.img.coef_off, E.coef_dev.as<int16_t>() + J.img.coef_off, bytes, hipMemcpyDeviceToHost, qs));
       c->jhe_stats[3] += (long long)bytes; copies = true;
       continue;
     }
     ++c->jhe_stats[0]; c->jhe_stats[2] += imgs[k].nblk;
-    J.scan = E.scan_host + at;
+    J.scan = E.scan_host.as<uint8_t>() + at;
     if (J.scan_have) {
-      CTPN_HIP_TRY(hipMemcpyAsync(E.scan_host + at, E.huff_dev + o_out + imgs[k].out0, J.scan_have, hipMemcpyDeviceToHost, qs));
+      CTPN_HIP_TRY(hipMemcpyAsync(E.scan_host.as<uint8_t>() + at, huff + o_out + imgs[k].out0, J.scan_have, hipMemcpyDeviceToHost, qs));
       c->jhe_stats[3] += (long long)J.scan_have; copies = true;
     }
     at += up(J.scan_have);
@@ -208,7 +196,7 @@ static int enc_huff_group(ctpn_ctx* c, std::vector<EncJob>& jobs, const std::vec
 // the per-file outcomes are in the jobs
 static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
   auto& E = c->enc;
-  if (!E.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&E.ev_done, hipEventDisableTiming));
+  if (int rc = E.ev_done.ensure()) return rc;
   c->jhe_stats[0] = c->jhe_stats[1] = c->jhe_stats[2] = c->jhe_stats[3] = 0;
   const int n = (int)jobs.size();
   for (int i0 = 0; i0 < n;) {
@@ -220,7 +208,7 @@ static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
       if (nb > (uint64_t)JHE_MAX_BLOCKS) {      // offsets of 32 bits do not hold it: the host half's
         jobs[i1].on_host = true; ++c->jhe_stats[1];
         if (!jobs[i1].coef_host) {
-          CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host + jobs[i1].img.coef_off, E.coef_dev + jobs[i1].img.coef_off, (size_t)nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
+          CTPN_HIP_TRY(hipMemcpyAsync(E.coef_host.as<int16_t>() + jobs[i1].img.coef_off, E.coef_dev.as<int16_t>() + jobs[i1].img.coef_off, (size_t)nb * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream_c));
           CTPN_HIP_TRY(hipEventRecord(E.ev_done, c->stream_c));
           CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
           c->jhe_stats[3] += (long long)((size_t)nb * 64 * sizeof(int16_t));
@@ -236,7 +224,7 @@ static int enc_huff(ctpn_ctx* c, std::vector<EncJob>& jobs, bool zigzag) {
       EncJob& J = jobs[(size_t)i0 + k];
       const size_t bound = J.on_host ? jpeg_encode_capacity(J.h, J.w) : J.scan_bytes + 1024;
       if (J.on_host) {
-        const int16_t* coef = J.coef_host ? J.coef_host : E.coef_host + J.img.coef_off;
+        const int16_t* coef = J.coef_host ? J.coef_host : E.coef_host.as<int16_t>() + J.img.coef_off;
         const bool zz = !J.coef_host;
         enc_deliver(bound, J.out, J.capacity, J.bytes_out, J.path, J.st, J.msg, [&](uint8_t* buf, size_t cap, size_t* bytes) {
           return jpeg_entropy_encode(coef, zz, J.h, J.w, J.hs, J.vs, J.qt, buf, cap, bytes); });
@@ -274,7 +262,7 @@ static int enc_finish(ctpn_ctx* c, const char* who, const EncPlan& P, int qualit
     CTPN_HIP_TRY(hipEventSynchronize(E.ev_done));
     c->pool->run(n, [&](int i) {
       const JpegGeom& g = P.g[i];
-      const int16_t* coef = E.coef_host + P.coef0[i];
+      const int16_t* coef = E.coef_host.as<int16_t>() + P.coef0[i];
       enc_deliver(jpeg_encode_capacity(g.h, g.w), paths ? nullptr : out[i], paths ? 0 : capacities[i], paths ? nullptr : bytes_out + i, paths ? paths[i] : nullptr, st[i], msg[i],
                   [&](uint8_t* buf, size_t cap, size_t* bytes) { return jpeg_entropy_encode(coef, true, g.h, g.w, 2, 2, qt, buf, cap, bytes); });
     });
@@ -306,7 +294,7 @@ static int encode_batch_impl(ctpn_ctx* c, const char* who_, const uint8_t* image
   CTPN_HIP_TRY(hipSetDevice(c->device));
   const uint8_t* px;
   int rc;
-  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
+  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stream_c, px))) return rc;
   EncPlan P;
   for (int i = 0; i < n; ++i) P.add(h, w);
   if ((rc = enc_enqueue(c, px, P, nullptr, quality, device_entropy))) return rc;
@@ -345,7 +333,7 @@ static int encode_mixed_impl(ctpn_ctx* c, const char* who_, const uint8_t* sourc
   if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   const uint8_t* px;
-  if ((rc = stage_pixels(c, source, source_on_device, source_bytes, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
+  if ((rc = stage_pixels(c, source, source_on_device, source_bytes, 256, c->stage.img_dev, c->stream_c, px))) return rc;
   return encode_mixed_dev(c, who_, px, n, heights, widths, pitches, offsets, quality, out, capacities, bytes_out, nullptr, device_entropy);
 }
 
@@ -411,7 +399,7 @@ int ctpn_jpeg_entropy_encode_device(ctpn_ctx* c, const int16_t* const* coef, con
   int rc = enc_reserve_coef(c, elems);
   if (rc) return rc;
   for (const EncJob& J : jobs)
-    CTPN_HIP_TRY(hipMemcpyAsync(c->enc.coef_dev + J.img.coef_off, J.coef_host, (size_t)J.img.nblk * 64 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream_c));
+    CTPN_HIP_TRY(hipMemcpyAsync(c->enc.coef_dev.as<int16_t>() + J.img.coef_off, J.coef_host, (size_t)J.img.nblk * 64 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream_c));
   if ((rc = enc_huff(c, jobs, false))) return rc;
   for (size_t k = 0; k < jobs.size(); ++k) {
     status_out[owner[k]] = jobs[k].st;

@@ -60,13 +60,13 @@ int annotate_ragged(ctpn_ctx* c, const std::string& who, const char* format, Sta
     offsets[i] = at;
     at = up256(at + (size_t)dh[i] * pitches[i]);
   }
-  if ((rc = grow_dev((void**)&S.img_dev, S.img_bytes, at + 256))) return rc;
-  if ((rc = grow_dev((void**)&S.recs_dev, S.recs_bytes, std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64)))) return rc;
-  if ((rc = grow_dev((void**)&S.cnt_dev, S.cnt_bytes, (size_t)n * sizeof(int)))) return rc;
+  if ((rc = S.img_dev.grow(at + 256))) return rc;
+  if ((rc = S.recs_dev.grow(std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64)))) return rc;
+  if ((rc = S.cnt_dev.grow((size_t)n * sizeof(int)))) return rc;
   // the heights and the resize's descriptor table in one page-locked block and one copy (the block is free: every earlier call waited for its files)
   const size_t tab_off = up256((size_t)n * sizeof(int)), tab_bytes = tab_off + (size_t)m * RM_DESC_BYTES;
-  if ((rc = grow_host(&S.rm_host, S.rm_host_bytes, tab_bytes)) || (rc = grow_dev((void**)&S.rm_dev, S.rm_bytes, tab_bytes))) return rc;
-  std::memcpy(S.rm_host, heights, (size_t)n * sizeof(int));
+  if ((rc = S.rm_host.grow(tab_bytes)) || (rc = S.rm_dev.grow(tab_bytes))) return rc;
+  std::memcpy(S.rm_host.as<uint8_t>(), heights, (size_t)n * sizeof(int));
   long long items = 0;
   if (m) {
     std::vector<int> sh((size_t)m), sw((size_t)m, w), th((size_t)m), tw((size_t)m);
@@ -76,18 +76,18 @@ int annotate_ragged(ctpn_ctx* c, const std::string& who, const char* format, Sta
       const int i = resized[k];
       sh[k] = heights[i]; th[k] = dh[i]; tw[k] = dw[i]; so[k] = (long long)i * (long long)slot_bytes; to[k] = (long long)offsets[i]; fi[k] = inv_f[i];
     }
-    items = resize_mixed_fill(S.rm_host + tab_off, m, sh.data(), sw.data(), th.data(), tw.data(), so.data(), sp.data(), to.data(), fi.data());
+    items = resize_mixed_fill(S.rm_host.as<uint8_t>() + tab_off, m, sh.data(), sw.data(), th.data(), tw.data(), so.data(), sp.data(), to.data(), fi.data());
     if (items < 0) return fail(CTPN_ERR_ARG, who + ": more than 2^31 - 1 work items in one call");
   }
-  CTPN_HIP_TRY(hipMemcpyAsync(S.rm_dev, S.rm_host, tab_bytes, hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(S.rm_dev.as<uint8_t>(), S.rm_host.as<uint8_t>(), tab_bytes, hipMemcpyHostToDevice, qs));
   // the outlines go onto the ctx's copy: a live canvas (produced in this queue) may still feed a forward, and a caller's canvas is never modified
   if (canvas_on_device && (rc = wait_live_batch(c, canvas, qs))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(S.img_dev, canvas, canvas_bytes, canvas_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, qs));
-  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(S.recs_dev, recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemcpyAsync(S.cnt_dev, line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
-  if ((rc = launch_draw_boxes_ragged(S.img_dev, S.recs_dev, S.cnt_dev, (const int*)S.rm_dev, line_capacity, n, hc, w, qs))) return rc;
-  if (m && (rc = launch_resize_linear_mixed(S.img_dev, S.img_dev, S.rm_dev + tab_off, m, items, qs))) return rc;
-  px = S.img_dev;
+  CTPN_HIP_TRY(hipMemcpyAsync(S.img_dev.as<uint8_t>(), canvas, canvas_bytes, canvas_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, qs));
+  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(S.recs_dev.as<double>(), recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(S.cnt_dev.as<int>(), line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
+  if ((rc = launch_draw_boxes_ragged(S.img_dev.as<uint8_t>(), S.recs_dev.as<double>(), S.cnt_dev.as<int>(), S.rm_dev.as<int>(), line_capacity, n, hc, w, qs))) return rc;
+  if (m && (rc = launch_resize_linear_mixed(S.img_dev.as<uint8_t>(), S.img_dev.as<uint8_t>(), S.rm_dev.as<uint8_t>() + tab_off, m, items, qs))) return rc;
+  px = S.img_dev.as<uint8_t>();
   return CTPN_OK;
 }
 

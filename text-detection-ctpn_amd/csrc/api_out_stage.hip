@@ -6,16 +6,16 @@ namespace ctpn {
 
 // a live batch of ctpn_decode_jpeg_batch (or a live canvas of ctpn_decode_jpeg_*_ragged) was produced in the ctx's copy queue: qs waits for it. It is only read (a forward may read it too)
 int wait_live_batch(ctpn_ctx* c, const uint8_t* images_dev, hipStream_t qs) {
-  for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev == images_dev) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
+  for (auto& J : c->jpeg) if (J.ready_valid && J.out_dev.get() == images_dev) CTPN_HIP_TRY(hipStreamWaitEvent(qs, J.ev_ready, 0));
   return CTPN_OK;
 }
 
-int stage_pixels(ctpn_ctx* c, const uint8_t* images, int on_device, size_t bytes, size_t slack, uint8_t*& buf, size_t& buf_bytes, hipStream_t qs, const uint8_t*& px) {
+int stage_pixels(ctpn_ctx* c, const uint8_t* images, int on_device, size_t bytes, size_t slack, DevBuf& buf, hipStream_t qs, const uint8_t*& px) {
   px = images;
   if (on_device) return wait_live_batch(c, images, qs);
-  if (int rc = grow_dev((void**)&buf, buf_bytes, bytes + slack)) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(buf, images, bytes, hipMemcpyHostToDevice, qs));
-  px = buf;
+  if (int rc = buf.grow(bytes + slack)) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(buf.get(), images, bytes, hipMemcpyHostToDevice, qs));
+  px = buf.as<uint8_t>();
   return CTPN_OK;
 }
 
@@ -39,20 +39,20 @@ int annotate_batch(ctpn_ctx* c, const std::string& who, const char* format, Stag
   auto& S = c->stage;
   hipStream_t qs = c->stream_c;
   const size_t bytes = (size_t)n * h * w * 3;
-  if ((rc = grow_dev((void**)&S.img_dev, S.img_bytes, bytes + 256))) return rc;
-  if (f != 1.0 && (rc = grow_dev((void**)&S.rs_dev, S.rs_bytes, (size_t)n * dh * dw * 3 + 256))) return rc;
-  if ((rc = grow_dev((void**)&S.recs_dev, S.recs_bytes, std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64)))) return rc;
-  if ((rc = grow_dev((void**)&S.cnt_dev, S.cnt_bytes, (size_t)n * sizeof(int)))) return rc;
+  if ((rc = S.img_dev.grow(bytes + 256))) return rc;
+  if (f != 1.0 && (rc = S.rs_dev.grow((size_t)n * dh * dw * 3 + 256))) return rc;
+  if ((rc = S.recs_dev.grow(std::max<size_t>((size_t)n * line_capacity * 9 * sizeof(double), 64)))) return rc;
+  if ((rc = S.cnt_dev.grow((size_t)n * sizeof(int)))) return rc;
   // the outlines go onto a copy owned by the ctx: a live batch of ctpn_decode_jpeg_batch (produced in this queue) may still feed a forward
   if (on_device && (rc = wait_live_batch(c, images, qs))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(S.img_dev, images, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, qs));
-  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(S.recs_dev, recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemcpyAsync(S.cnt_dev, line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
-  if ((rc = launch_draw_boxes(S.img_dev, S.recs_dev, S.cnt_dev, line_capacity, n, h, w, qs))) return rc;
-  px = S.img_dev;
+  CTPN_HIP_TRY(hipMemcpyAsync(S.img_dev.as<uint8_t>(), images, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, qs));
+  if (recs && line_capacity > 0) CTPN_HIP_TRY(hipMemcpyAsync(S.recs_dev.as<double>(), recs, (size_t)n * line_capacity * 9 * sizeof(double), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(S.cnt_dev.as<int>(), line_counts, (size_t)n * sizeof(int), hipMemcpyHostToDevice, qs));
+  if ((rc = launch_draw_boxes(S.img_dev.as<uint8_t>(), S.recs_dev.as<double>(), S.cnt_dev.as<int>(), line_capacity, n, h, w, qs))) return rc;
+  px = S.img_dev.as<uint8_t>();
   if (f != 1.0) {
-    if ((rc = launch_resize_linear(S.img_dev, S.rs_dev, 0, n, h, w, dh, dw, f, f, qs))) return rc;
-    px = S.rs_dev;
+    if ((rc = launch_resize_linear(S.img_dev.as<uint8_t>(), S.rs_dev.as<uint8_t>(), 0, n, h, w, dh, dw, f, f, qs))) return rc;
+    px = S.rs_dev.as<uint8_t>();
   }
   return CTPN_OK;
 }

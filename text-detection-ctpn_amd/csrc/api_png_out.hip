@@ -47,37 +47,39 @@ int png_code_table(ctpn_ctx* c, const char* who, const uint8_t* px, int n, const
   if ((rc = png_table_check(who, n, heights, widths))) return rc;
   auto& P = c->pnge;
   hipStream_t qs = c->stream_c;
-  if (!P.ev_done) CTPN_HIP_TRY(hipEventCreateWithFlags(&P.ev_done, hipEventDisableTiming));
+  if (int rc = P.ev_done.ensure()) return rc;
   c->pnge_stats[0] = c->pnge_stats[1] = c->pnge_stats[2] = c->pnge_stats[3] = 0;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_img = 0, o_hist = up(o_img + (size_t)n * sizeof(PngeImg)), o_res = o_hist + (size_t)n * PNGE_NSYM * 4, o_codes = up(o_res + (size_t)n * sizeof(PngeRes)),
                host_total = o_codes + (size_t)n * sizeof(PngeCodes);
-  if ((rc = grow_host(&P.host, P.host_bytes, host_total))) return rc;
-  PngeImg* imgs = (PngeImg*)(P.host + o_img);
-  uint32_t* hist = (uint32_t*)(P.host + o_hist);
-  PngeRes* res = (PngeRes*)(P.host + o_res);
-  PngeCodes* codes = (PngeCodes*)(P.host + o_codes);
+  if ((rc = P.host.grow(host_total))) return rc;
+  uint8_t* host = P.host.as<uint8_t>();
+  PngeImg* imgs = (PngeImg*)(host + o_img);
+  uint32_t* hist = (uint32_t*)(host + o_hist);
+  PngeRes* res = (PngeRes*)(host + o_res);
+  PngeCodes* codes = (PngeCodes*)(host + o_codes);
   for (int i = 0; i < n; ++i) pnge_describe(imgs[i], heights[i], widths[i]);
   PngeTotals t;
   pnge_layout(imgs, (size_t)n, t);
   for (int i = 0; i < n; ++i) { imgs[i].pix_off = offsets[i]; imgs[i].pitch = pitches[i]; }      // the caller's source, not the dense packing
   const size_t o_len = up(host_total), o_words = up(o_len + (size_t)t.pieces * sizeof(PngeLen)), dev_total = o_words + (size_t)t.words * 4;
-  if ((rc = grow_dev((void**)&P.dev, P.dev_bytes, dev_total))) return rc;
+  if ((rc = P.dev.grow(dev_total))) return rc;
+  uint8_t* dev = P.dev.as<uint8_t>();
   // histograms -> the host, which builds every image's code and block header; one copy brings them back
-  CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_img, imgs, (size_t)n * sizeof(PngeImg), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_hist, 0, (size_t)n * (PNGE_NSYM * 4 + sizeof(PngeRes)), qs));      // counters and result records
-  if ((rc = launch_png_hist((const PngeImg*)(P.dev + o_img), px, (uint32_t*)(P.dev + o_hist), n, t.items, qs))) return rc;
-  CTPN_HIP_TRY(hipMemcpyAsync(hist, P.dev + o_hist, (size_t)n * PNGE_NSYM * 4, hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(dev + o_img, imgs, (size_t)n * sizeof(PngeImg), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(dev + o_hist, 0, (size_t)n * (PNGE_NSYM * 4 + sizeof(PngeRes)), qs));      // counters and result records
+  if ((rc = launch_png_hist((const PngeImg*)(dev + o_img), px, (uint32_t*)(dev + o_hist), n, t.items, qs))) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(hist, dev + o_hist, (size_t)n * PNGE_NSYM * 4, hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
   c->pnge_stats[3] += (long long)n * PNGE_NSYM * 4;
   c->pool->run(n, [&](int i) { pnge_build_codes(imgs[i], hist + (size_t)i * PNGE_NSYM, codes[i]); });
-  CTPN_HIP_TRY(hipMemcpyAsync(P.dev + o_codes, codes, (size_t)n * sizeof(PngeCodes), hipMemcpyHostToDevice, qs));
-  CTPN_HIP_TRY(hipMemsetAsync(P.dev + o_words, 0, (size_t)t.words * 4, qs));      // the write pass ORs shared words into it
-  if ((rc = launch_png_code((const PngeImg*)(P.dev + o_img), px, (const PngeCodes*)(P.dev + o_codes), (PngeLen*)(P.dev + o_len), (uint32_t*)(P.dev + o_words),
-                            (PngeRes*)(P.dev + o_res), n, t.items, qs))) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(dev + o_codes, codes, (size_t)n * sizeof(PngeCodes), hipMemcpyHostToDevice, qs));
+  CTPN_HIP_TRY(hipMemsetAsync(dev + o_words, 0, (size_t)t.words * 4, qs));      // the write pass ORs shared words into it
+  if ((rc = launch_png_code((const PngeImg*)(dev + o_img), px, (const PngeCodes*)(dev + o_codes), (PngeLen*)(dev + o_len), (uint32_t*)(dev + o_words),
+                            (PngeRes*)(dev + o_res), n, t.items, qs))) return rc;
   // the result records first, then exactly the bytes they name
-  CTPN_HIP_TRY(hipMemcpyAsync(res, P.dev + o_res, (size_t)n * sizeof(PngeRes), hipMemcpyDeviceToHost, qs));
+  CTPN_HIP_TRY(hipMemcpyAsync(res, dev + o_res, (size_t)n * sizeof(PngeRes), hipMemcpyDeviceToHost, qs));
   CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
   CTPN_HIP_TRY(hipEventSynchronize(P.ev_done));
   c->pnge_stats[3] += (long long)n * (long long)sizeof(PngeRes);
@@ -89,7 +91,8 @@ int png_code_table(ctpn_ctx* c, const char* who, const uint8_t* px, int n, const
     at[i] = file_total;
     file_total += up((size_t)PNGE_FRAME_BYTES + res[i].bytes);
   }
-  if ((rc = grow_host(&P.file_host, P.file_host_bytes, file_total))) return rc;
+  if ((rc = P.file_host.grow(file_total))) return rc;
+  uint8_t* file_host = P.file_host.as<uint8_t>();
   std::vector<uint8_t> back;      // the pixels of the images the host form codes (none, unless a flag is raised), each a dense block
   try { back.resize(back_total); } catch (const std::exception& e) { return fail(CTPN_ERR_CAPACITY, std::string(who) + ": " + e.what()); }
   for (int i = 0; i < n; ++i) {
@@ -101,7 +104,7 @@ int png_code_table(ctpn_ctx* c, const char* who, const uint8_t* px, int n, const
       continue;
     }
     ++c->pnge_stats[0]; c->pnge_stats[2] += imgs[i].npieces;
-    CTPN_HIP_TRY(hipMemcpyAsync(P.file_host + at[i] + PNGE_FRAME_FRONT, P.dev + o_words + (size_t)imgs[i].word0 * 4, res[i].bytes, hipMemcpyDeviceToHost, qs));
+    CTPN_HIP_TRY(hipMemcpyAsync(file_host + at[i] + PNGE_FRAME_FRONT, dev + o_words + (size_t)imgs[i].word0 * 4, res[i].bytes, hipMemcpyDeviceToHost, qs));
     c->pnge_stats[3] += (long long)res[i].bytes;
   }
   CTPN_HIP_TRY(hipEventRecord(P.ev_done, qs));
@@ -122,7 +125,7 @@ int png_code_table(ctpn_ctx* c, const char* who, const uint8_t* px, int n, const
         (void)pnge_encode_host(back.data() + back_at[i], h, w, file.data(), need, &need, png_crc32);
         png_deliver(file.data(), need, o, cap, bo, path, st[i], msg[i]);
       } else {
-        uint8_t* file = P.file_host + at[i];
+        uint8_t* file = file_host + at[i];
         pnge_frame(file, h, w, res[i].bytes, res[i].adler, png_crc32);
         png_deliver(file, (size_t)PNGE_FRAME_BYTES + res[i].bytes, o, cap, bo, path, st[i], msg[i]);
       }
@@ -166,7 +169,7 @@ int ctpn_encode_png_batch(ctpn_ctx* c, const uint8_t* images, int images_on_devi
   if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   const uint8_t* px;
-  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
+  if ((rc = stage_pixels(c, images, images_on_device, (size_t)n * h * w * 3, 256, c->stage.img_dev, c->stream_c, px))) return rc;
   return png_code(c, "ctpn_encode_png_batch", px, n, h, w, out, capacities, bytes_out, nullptr);
 }
 
@@ -192,7 +195,7 @@ int ctpn_encode_png_mixed(ctpn_ctx* c, const uint8_t* source, int source_on_devi
   if (c->postproc_only) return fail(CTPN_ERR_STATE, who + ": post-processing-only ctx");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   const uint8_t* px;
-  if ((rc = stage_pixels(c, source, source_on_device, source_bytes, 0, c->stage.img_dev, c->stage.img_bytes, c->stream_c, px))) return rc;
+  if ((rc = stage_pixels(c, source, source_on_device, source_bytes, 0, c->stage.img_dev, c->stream_c, px))) return rc;
   return png_code_table(c, "ctpn_encode_png_mixed", px, n, heights, widths, pitches, offsets, out, capacities, bytes_out, nullptr);
 }
 

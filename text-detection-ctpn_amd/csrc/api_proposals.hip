@@ -9,13 +9,11 @@ namespace ctpn {
 int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, const int* counts, int stride, float thresh, int post_topn,
                       const int* keep1, int keep_stride, const int* cnt1, int n, bool mw, hipStream_t s, const char* what) {
   std::vector<int> k2((size_t)n * keep_stride), c2(n);
-  int* keep2 = nullptr; int* cnt2 = nullptr; float* spill2 = nullptr;
-  struct Free3 { int*& a; int*& b; float*& c; ~Free3() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } guard{keep2, cnt2, spill2};   // every early return frees
-  CTPN_HIP_TRY(hipMalloc((void**)&keep2, k2.size() * sizeof(int)));
-  CTPN_HIP_TRY(hipMalloc((void**)&cnt2, c2.size() * sizeof(int)));
-  CTPN_HIP_TRY(hipMalloc((void**)&spill2, (size_t)n * keep_stride * 4 * sizeof(float)));
-  int rc = launch_nms(boxes, scores, counts, stride, thresh, post_topn, keep2, keep_stride, cnt2, nullptr, spill2, n, s);
-  if (rc) return rc;
+  DevBuf keep_buf, cnt_buf, spill_buf;
+  int rc;
+  if ((rc = keep_buf.alloc(k2.size() * sizeof(int))) || (rc = cnt_buf.alloc(c2.size() * sizeof(int))) || (rc = spill_buf.alloc((size_t)n * keep_stride * 4 * sizeof(float)))) return rc;
+  int* keep2 = keep_buf.as<int>(); int* cnt2 = cnt_buf.as<int>();
+  if ((rc = launch_nms(boxes, scores, counts, stride, thresh, post_topn, keep2, keep_stride, cnt2, nullptr, spill_buf.as<float>(), n, s))) return rc;
   CTPN_HIP_TRY(hipStreamSynchronize(s));
   CTPN_HIP_TRY(hipMemcpy(k2.data(), keep2, k2.size() * sizeof(int), hipMemcpyDeviceToHost));
   CTPN_HIP_TRY(hipMemcpy(c2.data(), cnt2, c2.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -158,11 +156,13 @@ static int run_proposals(ctpn_ctx* c, const float* heads, int heads_are_probs, i
 namespace {
 struct NmsCache {
   std::mutex mu;
-  hipStream_t stream = nullptr;
-  int cap = 0;
-  float* boxes = nullptr; float* spill = nullptr; int* keep = nullptr; int* counts = nullptr;  // counts[0] = n in, counts[1] = n kept
+  Stream stream;
+  int cap = 0;      // boxes the blocks have room for
+  DevBuf boxes, spill, keep, counts;      // float4, float4, int per box; counts: int [n in, n kept]
 };
-NmsCache g_nms[16];
+// one per device, for the life of the process: allocated once and deliberately never destroyed (at static-destruction time the HIP runtime may
+// already be gone, and a release would call into it)
+NmsCache* const g_nms = new NmsCache[16];
 }  // namespace
 
 extern "C" {
@@ -175,7 +175,7 @@ int ctpn_proposals(ctpn_ctx* c, const float* im_info, int pre_nms_topn, int post
   // after a ragged forward: that forward's feature rows per image (its set's second half), which a uniform forward forgets
   const ctpn_ctx::FwdSet& f = *c->last;      // the most recent forward's set; the proposal layer runs on `stream`, behind that forward
   if (f.stream != c->stream) CTPN_HIP_TRY(hipStreamSynchronize(f.stream));
-  const int* valid = f.fwd_ragged >= 0 ? c->ragged[f.fwd_ragged].dev + f.n : nullptr;
+  const int* valid = f.fwd_ragged >= 0 ? c->ragged[f.fwd_ragged].dev.as<int>() + f.n : nullptr;
   return run_proposals(c, f.heads, 0, f.n, lvl(f.h, 4), lvl(f.w, 4), im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size,
                        rois_out, counts_out, valid);
 }
@@ -214,27 +214,25 @@ int ctpn_nms(int* keep_out, int* num_out, const float* boxes_host, int boxes_num
   NmsCache& nc = g_nms[device_id];
   std::lock_guard<std::mutex> lk(nc.mu);
   CTPN_HIP_TRY(hipSetDevice(device_id));
-  if (!nc.stream) CTPN_HIP_TRY(hipStreamCreateWithFlags(&nc.stream, hipStreamNonBlocking));
+  int rc;
+  if ((rc = nc.stream.ensure())) return rc;
   if (nc.cap < boxes_num) {
-    if (nc.boxes) { (void)hipFree(nc.boxes); (void)hipFree(nc.spill); (void)hipFree(nc.keep); (void)hipFree(nc.counts); nc.boxes = nullptr; nc.cap = 0; }
-    const int cap = boxes_num < 16384 ? 16384 : boxes_num;
-    CTPN_HIP_TRY(hipMalloc((void**)&nc.boxes, (size_t)cap * 4 * sizeof(float)));
-    CTPN_HIP_TRY(hipMalloc((void**)&nc.spill, (size_t)cap * 4 * sizeof(float)));
-    CTPN_HIP_TRY(hipMalloc((void**)&nc.keep, (size_t)cap * sizeof(int)));
-    CTPN_HIP_TRY(hipMalloc((void**)&nc.counts, 2 * sizeof(int)));
-    nc.cap = cap;
+    const size_t cap = boxes_num < 16384 ? 16384 : boxes_num;
+    nc.cap = 0;
+    if ((rc = nc.boxes.grow(cap * 4 * sizeof(float))) || (rc = nc.spill.grow(cap * 4 * sizeof(float))) || (rc = nc.keep.grow(cap * sizeof(int))) || (rc = nc.counts.grow(2 * sizeof(int)))) return rc;
+    nc.cap = (int)cap;
   }
+  float* boxes = nc.boxes.as<float>(); int* counts = nc.counts.as<int>();
   std::vector<float> b4((size_t)boxes_num * 4);
   for (int i = 0; i < boxes_num; ++i) std::memcpy(&b4[(size_t)i * 4], boxes_host + (size_t)i * boxes_dim, 4 * sizeof(float));
-  CTPN_HIP_TRY(hipMemcpyAsync(nc.boxes, b4.data(), b4.size() * sizeof(float), hipMemcpyHostToDevice, nc.stream));
-  CTPN_HIP_TRY(hipMemcpyAsync(nc.counts, &boxes_num, sizeof(int), hipMemcpyHostToDevice, nc.stream));
-  int rc = launch_nms(nc.boxes, nullptr, nc.counts, boxes_num, thresh, boxes_num, nc.keep, boxes_num, nc.counts + 1, nullptr, nc.spill, 1, nc.stream);
-  if (rc) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(boxes, b4.data(), b4.size() * sizeof(float), hipMemcpyHostToDevice, nc.stream));
+  CTPN_HIP_TRY(hipMemcpyAsync(counts, &boxes_num, sizeof(int), hipMemcpyHostToDevice, nc.stream));
+  if ((rc = launch_nms(boxes, nullptr, counts, boxes_num, thresh, boxes_num, nc.keep.as<int>(), boxes_num, counts + 1, nullptr, nc.spill.as<float>(), 1, nc.stream))) return rc;
   int nk = 0;
-  CTPN_HIP_TRY(hipMemcpyAsync(&nk, nc.counts + 1, sizeof(int), hipMemcpyDeviceToHost, nc.stream));
+  CTPN_HIP_TRY(hipMemcpyAsync(&nk, counts + 1, sizeof(int), hipMemcpyDeviceToHost, nc.stream));
   CTPN_HIP_TRY(hipStreamSynchronize(nc.stream));
   if (nk < 0 || nk > boxes_num) return fail(CTPN_ERR_HIP, "ctpn_nms: device returned an impossible keep count");
-  CTPN_HIP_TRY(hipMemcpy(keep_out, nc.keep, (size_t)nk * sizeof(int), hipMemcpyDeviceToHost));
+  CTPN_HIP_TRY(hipMemcpy(keep_out, nc.keep.get(), (size_t)nk * sizeof(int), hipMemcpyDeviceToHost));
   *num_out = nk;
   return CTPN_OK;
 }

@@ -50,21 +50,17 @@ int pack_lstm_projection(const float* const kx[2], long long kx_ld, const float*
   }
   // gate columns of lstm_pre in the recurrence kernel's order (bilstm.hip: a lane's 4 gates x 4 units = one 64-byte run): permute
   // the rows of the packed [1024][512] input-projection matrix and its bias once, here
-  void* tmp = nullptr;
   const size_t wbytes = (size_t)1024 * row_bytes;
-  CTPN_HIP_TRY(hipMalloc(&tmp, wbytes));
-  auto chain = [&]() -> int {
-    CTPN_HIP_TRY(hipMemcpyAsync(tmp, wt_x, wbytes, hipMemcpyDeviceToDevice, s));
-    if ((rc = launch_lstm_permute_rows(tmp, wt_x, (int)row_bytes, s))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(tmp, b_x, 1024 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if ((rc = launch_lstm_permute_rows(tmp, b_x, 4, s))) return rc;
-    if (wt_xf && (rc = launch_lstm_pre_pack(wt_x, wt_xf, s))) return rc;
-    CTPN_HIP_TRY(hipStreamSynchronize(s));
-    return CTPN_OK;
-  };
-  rc = chain();
-  (void)hipFree(tmp);
-  return rc;
+  DevBuf tmp_buf;      // released on every way out (the release waits for what s still does with it)
+  if ((rc = tmp_buf.alloc(wbytes))) return rc;
+  void* tmp = tmp_buf.get();
+  CTPN_HIP_TRY(hipMemcpyAsync(tmp, wt_x, wbytes, hipMemcpyDeviceToDevice, s));
+  if ((rc = launch_lstm_permute_rows(tmp, wt_x, (int)row_bytes, s))) return rc;
+  CTPN_HIP_TRY(hipMemcpyAsync(tmp, b_x, 1024 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if ((rc = launch_lstm_permute_rows(tmp, b_x, 4, s))) return rc;
+  if (wt_xf && (rc = launch_lstm_pre_pack(wt_x, wt_xf, s))) return rc;
+  CTPN_HIP_TRY(hipStreamSynchronize(s));
+  return CTPN_OK;
 }
 
 static int pack_weights(ctpn_ctx* c) {

@@ -1,6 +1,9 @@
 // Internal to the host units of libctpn_hip.so (api_*.hip): the context struct, the small types and inline helpers more than one of them
 // uses, and the declarations of the few functions that cross them. The kernel units do not include this file; what they share with the host
 // units is in common.h.
+// Ownership: every device block, page-locked block, event and stream of a ctx is a member of one of owned.h's handle types (DevBuf,
+// PinnedBuf, Event, Stream, or a vector of them) and dies with the ctx; ctpn_destroy drains the streams and deletes the ctx, nothing else.
+// A raw pointer or raw handle among the members is a VIEW into such a block or an ALIAS of such a handle, and says so.
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -18,6 +21,7 @@
 #include <dlfcn.h>
 
 #include "common.h"
+#include "owned.h"
 
 namespace ctpn {
 
@@ -32,7 +36,7 @@ static const ConvSpec kConvs[14] = {
     {"conv5_3", 512, 512, 4, 0}, {"rpn_conv/3x3", 512, 512, 4, 0}};
 static const char* kPoolNames[4] = {"pool1", "pool2", "pool3", "pool4"};
 
-struct ProfRec { int kind; hipEvent_t a, b; double work; int launches = 1; bool span = false; };      // span: see prof_drain (api_ctx.hip)
+struct ProfRec { int kind; Event a, b; double work; int launches = 1; bool span = false; };      // span: see prof_drain (api_ctx.hip)
 
 // ---------------------------------------------------------------------------------------------
 // Host worker pool of one ctx: created once, sized by ctpn_host_thread_budget (cores of the node / ranks on the node).
@@ -122,23 +126,23 @@ struct ctpn_ctx {
   int max_batch = 0, max_h = 0, max_w = 0;
   DType prec = DType::BF16;
   int es = 2;                       // bytes per activation element (split precision: a (hi, lo) bf16 pair = 4)
-  hipStream_t stream = nullptr;     // network forward (forward set 0's stream, see FwdSet), weights, the synchronous entry points
-  hipStream_t stream_p = nullptr;   // proposal layer + connector front end of the asynchronous detect path
-  std::vector<void*> allocs;
+  hipStream_t stream = nullptr;     // ALIAS of fs[0].stream (not owned): network forward, weights, the synchronous entry points
+  Stream stream_p;                  // proposal layer + connector front end of the asynchronous detect path
+  std::vector<DevBuf> allocs;       // the blocks of fixed size ctpn_create makes; the typed pointers below are views into them
   // asynchronous detect: two slots of pinned host buffers + events
   struct Slot {
     // the batch's results in ONE page-locked block, laid out like the device's out_pack: a single device-to-host copy per submit
     // (six copies before: ~30 us of host calls per batch, which at batch 1 is 4 % of the step on a slow host)
-    char* pack = nullptr;
+    PinnedBuf pack;
     float* tlb = nullptr; float* tls = nullptr; int* keep = nullptr; int* kcnt = nullptr; float* rois = nullptr; int* rcnt = nullptr;      // views into pack
-    float* im_info = nullptr;
-    double* crecs = nullptr; int* ccnt = nullptr;      // device connector results: [n][2 modes][CONN_CAP][9], [n][3]
-    hipEvent_t ev_heads = nullptr, ev_decoded = nullptr, ev_done = nullptr;
+    PinnedBuf im_info;             // float [n][3]
+    PinnedBuf crecs, ccnt;         // device connector results: double [n][2 modes][CONN_CAP][9], int [n][3]
+    Event ev_heads, ev_decoded, ev_done;
     int n = 0, h = 0, w = 0; bool busy = false;
     int set = 0;               // the forward set the batch in flight runs on
     std::vector<int> hts;      // pixel height of every image of the batch (a ragged submit: the caller's heights; else h): what the host connector clips to
   } slot[2];
-  hipEvent_t ev_last_done = nullptr;     // the whole proposal tail (stream_p) of the most recent submit
+  hipEvent_t ev_last_done = nullptr;     // ALIAS of a slot's ev_done (not owned): the whole proposal tail (stream_p) of the most recent submit
   // "tail_confine" (default 0; was 1 in split precision during round 6): forward k + 1 waits, BEHIND its conv1_1, for the proposal tail of batch k,
   // which then overlaps conv1_1 only. History: the reversed-batch test of round 6 found that a batch in flight could change another batch's bits --
   // the proposal NMS of batch k running beside the persistent conv kernels of batch k + 1 (in split precision by default timing, in bf16 as soon as
@@ -164,69 +168,67 @@ struct ctpn_ctx {
   // ctpn_decode_jpeg_batch: two sets of buffers (decode of batch k + 1 while batch k's forward reads its images), allocated on first use and
   // grown on demand; a grown buffer's predecessor is retired, not freed (a pointer handed out earlier stays valid until ctpn_destroy)
   struct JpegBufs {
-    int16_t* coef_host = nullptr; uint16_t* qt_host = nullptr;      // page-locked: what the entropy decoders write
-    int16_t* coef_dev = nullptr; uint16_t* qt_dev = nullptr; uint8_t* out_dev = nullptr;
-    size_t coef_elems = 0, qt_imgs = 0, out_bytes = 0;              // capacities
-    uint8_t* tab_host = nullptr; uint8_t* tab_dev = nullptr; size_t tab_imgs = 0;      // ctpn_decode_jpeg_batch_ragged: per-image descriptors (page-locked / device)
+    PinnedBuf coef_host, qt_host;      // page-locked: what the entropy decoders write (int16 coefficients, uint16 tables)
+    DevBuf coef_dev, qt_dev, out_dev;
+    PinnedBuf tab_host; DevBuf tab_dev;      // ctpn_decode_jpeg_batch_ragged: per-image descriptors (page-locked / device)
     int out_n = 0, out_h = 0, out_w = 0;                            // what out_dev holds
-    hipEvent_t ev_h2d = nullptr, ev_ready = nullptr, ev_consumed = nullptr;
+    Event ev_h2d, ev_ready, ev_consumed;
     bool h2d_valid = false, consumed_valid = false, ready_valid = false;
   } jpeg[2];
-  uint8_t* jpeg_planes = nullptr;    // component planes between the two kernels (one set: the kernels of both buffers run on stream_c in order)
-  uint8_t* jpeg_raw = nullptr;       // the decoded batch at file size when a resize follows (one set, same reason)
-  size_t jpeg_planes_bytes = 0, jpeg_raw_bytes = 0;
-  std::vector<void*> jpeg_retired;   // device allocations replaced by larger ones
+  DevBuf jpeg_planes;                // component planes between the two kernels (one set: the kernels of both buffers run on stream_c in order)
+  DevBuf jpeg_raw;                   // the decoded batch at file size when a resize follows (one set, same reason)
+  std::vector<DevBuf> jpeg_retired;  // device allocations replaced by larger ones
   int jpeg_flip = 0;
   bool jpeg_ready = false;
   // ctpn_decode_jpeg_batch_device / ctpn_jpeg_entropy_decode_device (device Huffman decode, jpeg_huff.hip): ONE set -- these calls read the
   // files' flag words back before they return, so nothing of theirs is in flight when the next one stages its batch
   struct JhWork {
-    uint8_t* stage_host = nullptr; uint8_t* stage_dev = nullptr; size_t stage_bytes = 0;      // page-locked block and its device copy: descriptors + tables + bytes
-    uint8_t* work_dev = nullptr; size_t work_bytes = 0;                                      // per file flags / rounds, per subsequence states / counts
-    uint32_t* res_host = nullptr; size_t res_words = 0;                                      // page-locked: what comes back (2 words per file)
+    PinnedBuf stage_host; DevBuf stage_dev;      // page-locked block and its device copy: descriptors + tables + bytes
+    DevBuf work_dev;                             // per file flags / rounds, per subsequence states / counts
+    PinnedBuf res_host;                          // page-locked: what comes back (2 words per file)
   } jh;
   long long jh_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_device_stats
   // the output stage both writers share (api_out_stage.hip): ONE set of buffers -- every writer call returns when its files are coded, so
   // nothing of a call is in flight when the next one starts -- allocated on first use and grown to the largest batch seen
   struct StageBufs {
-    uint8_t* img_dev = nullptr; size_t img_bytes = 0;          // the batch's pixels: staged host images, or the copy the outlines are drawn on
-    uint8_t* rs_dev = nullptr; size_t rs_bytes = 0;            // ... resized by 1 / scale
-    double* recs_dev = nullptr; size_t recs_bytes = 0; int* cnt_dev = nullptr; size_t cnt_bytes = 0;      // the outlines' records and counts
+    DevBuf img_dev;            // the batch's pixels: staged host images, or the copy the outlines are drawn on
+    DevBuf rs_dev;             // ... resized by 1 / scale
+    DevBuf recs_dev, cnt_dev;  // the outlines' records (double) and counts (int)
     // ctpn_write_annotated_files_ragged (api_out_ragged.hip): [heights(n) | descriptors of the resized images], page-locked / device
-    uint8_t* rm_host = nullptr; size_t rm_host_bytes = 0; uint8_t* rm_dev = nullptr; size_t rm_bytes = 0;
+    PinnedBuf rm_host; DevBuf rm_dev;
   } stage;
   // ctpn_encode_jpeg_batch / ctpn_write_annotated_files (api_jpeg_out.hip): ONE set of buffers, for the reason the stage's set is one
   struct EncBufs {
-    int16_t* coef_dev = nullptr; int16_t* coef_host = nullptr; size_t coef_elems = 0;      // quantised coefficients; the host side is page-locked
-    void* qtab_dev = nullptr; void* qtab_host = nullptr; int qtab_quality = 0;               // JencQ[2][64] of the quality last used
-    hipEvent_t ev_done = nullptr;
+    DevBuf coef_dev; PinnedBuf coef_host;      // quantised coefficients (int16), both of one size; the host side is page-locked
+    DevBuf qtab_dev; PinnedBuf qtab_host; int qtab_quality = 0;               // JencQ[2][64] of the quality last used
+    Event ev_done;
     // the device-entropy form (jpeg_huff_enc.hip; ctpn_encode_jpeg_batch_device, ...): one device block for a launch group's descriptors,
     // result words, lengths, counts, unstuffed and stuffed streams; the code tables; page-locked: descriptors + result words, scan bytes
-    uint8_t* huff_dev = nullptr; size_t huff_bytes = 0;
-    void* huff_tab_dev = nullptr;
-    uint8_t* huff_host = nullptr; size_t huff_host_bytes = 0;
-    uint8_t* scan_host = nullptr; size_t scan_host_bytes = 0;
+    DevBuf huff_dev;
+    DevBuf huff_tab_dev;
+    PinnedBuf huff_host;
+    PinnedBuf scan_host;
     // images of mixed sizes (ctpn_encode_jpeg_mixed, ctpn_write_line_crops): the descriptor table with its prefix sums, page-locked / device
-    uint8_t* mix_host = nullptr; size_t mix_host_bytes = 0;
-    uint8_t* mix_dev = nullptr; size_t mix_bytes = 0;
+    PinnedBuf mix_host;
+    DevBuf mix_dev;
   } enc;
   long long jhe_stats[4] = {0, 0, 0, 0};      // ctpn_jpeg_entropy_encode_device_stats
   // ctpn_encode_png_batch / ctpn_write_annotated_png_files (api_png_out.hip): ONE set of buffers, for the same reason, grown likewise
   struct PngEncBufs {
-    uint8_t* dev = nullptr; size_t dev_bytes = 0;              // descriptors, histograms, codes, result records, per-piece array, DEFLATE words
-    uint8_t* host = nullptr; size_t host_bytes = 0;            // page-locked: descriptors, histograms, codes, result records
-    uint8_t* file_host = nullptr; size_t file_host_bytes = 0;  // page-locked: the DEFLATE blocks, each behind room for its file's front
-    hipEvent_t ev_done = nullptr;
+    DevBuf dev;                // descriptors, histograms, codes, result records, per-piece array, DEFLATE words
+    PinnedBuf host;            // page-locked: descriptors, histograms, codes, result records
+    PinnedBuf file_host;       // page-locked: the DEFLATE blocks, each behind room for its file's front
+    Event ev_done;
   } pnge;
   long long pnge_stats[4] = {0, 0, 0, 0};      // ctpn_png_encode_device_stats
   // ctpn_crop_lines (api_crops.hip): ONE set of buffers, for the reason the writer's set is one (the call returns when its crops are
   // complete), allocated on first use and grown to the largest call seen
   struct CropBufs {
-    uint8_t* img_dev = nullptr; size_t img_bytes = 0;          // staged host images
-    uint8_t* out_dev = nullptr; size_t out_bytes = 0;          // the crops of a call whose output goes to the host
-    void* desc_dev = nullptr; size_t desc_bytes = 0;           // one descriptor per line (common.h CROP_DESC_BYTES)
-    void* desc_host = nullptr; size_t desc_host_bytes = 0;     // ... page-locked
-    hipEvent_t ev_done = nullptr;
+    DevBuf img_dev;            // staged host images
+    DevBuf out_dev;            // the crops of a call whose output goes to the host
+    DevBuf desc_dev;           // one descriptor per line (common.h CROP_DESC_BYTES)
+    PinnedBuf desc_host;       // ... page-locked
+    Event ev_done;
   } crop;
   int debug_nms = 0;                 // "debug_nms" (diagnostic, WRONG proposals): parts mask of the one-workgroup proposal NMS, see nms_columns_kernel
   int debug_hog = 0;                 // "debug_hog" (diagnostic, 0 .. 200000; see the launch in enqueue_proposals_impl for the two upper ranges): launch a kernel with the one-workgroup NMS's footprint (1024 threads, 84 KB of LDS, one
@@ -259,7 +261,7 @@ struct ctpn_ctx {
   float* wt_fold = nullptr;          // [64][256]: (lstm_o FC) x (heads) folded, bf16 throughput mode only
   float* b_fold = nullptr;           // [64]
 
-  // A forward set: a forward's stream and everything a forward writes. Set 0 is allocated by ctpn_create and runs on `stream`; every
+  // A forward set: a forward's stream and everything a forward writes. Set 0 is allocated by ctpn_create; every
   // synchronous entry point uses it. Set 1 exists so that TWO submitted batches' forwards can be in flight at once: a forward is a chain of
   // 20 dependent launches, and one ordered stream leaves the CUs idle at every cross-stream wait, in every partial last round of a persistent
   // walk and beside the 148-workgroup recurrence; a second, independent chain on another hardware queue has workgroups ready for exactly those
@@ -268,7 +270,8 @@ struct ctpn_ctx {
   // (keep_acts, out of memory, per-stage profiling) keeps both slots on set 0: the single-stream order.
   // Weights, the image staging buffers and the proposal tail (stream_p, one set of buffers) are shared.
   struct FwdSet {
-    hipStream_t stream = nullptr;
+    Stream stream;
+    // views into blocks of `allocs` (set 0: the ctx's); act_conv / act_pool point `front` bytes into theirs, see act_front_pixels
     void* q_img = nullptr;             // the batch's q-image (common.h), 16-bit modes only
     void* act_conv[14] = {nullptr};
     void* act_pool[4] = {nullptr};
@@ -278,32 +281,31 @@ struct ctpn_ctx {
     float* fc_out = nullptr;    // [M5][512]
     float* heads = nullptr;     // [M5][64]
     bool fc_valid = true;
-    float* ragged_blob = nullptr; size_t ragged_blob_bytes = 0;       // fp32 / split precision: a ragged canvas as a float feed, 0.0f below the images
+    DevBuf ragged_blob;                // fp32 / split precision: a ragged canvas as a float feed, 0.0f below the images
     int fwd_ragged = -1;               // the set's last forward was ragged: index of its RaggedSet (ctpn_proposals hands its feature rows to decode_kernel), else -1
     int n = 0, h = 0, w = 0;           // the set's last forward
     int gn = -1, gh = -1, gw = -1;     // geometry the set's borders are currently zeroed for
     // option tail_overlap: conv stack + lstm_pre of the set's batch in flight are done (stream -> stream_p); the tail of the set's most recent
     // forward is done (stream_p -> stream: before the set's next conv1_2 rewrites what it read)
-    hipEvent_t ev_conv = nullptr, ev_tail = nullptr;
+    Event ev_conv, ev_tail;
     bool tail_pending = false;
     // the decode kernel (stream_p) that last read `heads`, which the set's next forward rewrites, and the slot whose submit recorded it
-    hipEvent_t ev_decoded = nullptr; int dec_slot = -1;
-    hipEvent_t ev_gate = nullptr; bool gate_valid = false;      // two_forwards_mode() 2 / 3: the point of this set's forward the other set's conv stack waits for
-    std::vector<void*> allocs;         // set 1: what ctpn_destroy frees (set 0's blocks are in the ctx's allocs)
+    hipEvent_t ev_decoded = nullptr; int dec_slot = -1;      // ALIAS of that slot's ev_decoded (not owned)
+    Event ev_gate; bool gate_valid = false;      // two_forwards_mode() 2 / 3: the point of this set's forward the other set's conv stack waits for
+    std::vector<DevBuf> allocs;        // set 1's blocks (set 0's are in the ctx's allocs, with everything else ctpn_create makes)
   } fs[2];
   size_t set1_bytes = 0;             // device bytes of set 1
   int set1_state = 0;                // 0: not asked for yet, 1: allocated, -1: could not be allocated (both slots stay on set 0)
   FwdSet* last = &fs[0];             // the set of the most recent forward: what ctpn_get_tensor, ctpn_proposals, ctpn_feat_shape read
   size_t act_conv_bytes[14] = {0};
   size_t act_pool_bytes[4] = {0};
-  uint8_t* img_dev = nullptr;        // staging of host images, buffer 0
+  uint8_t* img_dev = nullptr;        // staging of host images, buffer 0 (views into allocs, like the weights above)
   uint8_t* img_dev_b[2] = {nullptr, nullptr};   // ... double-buffered: batch k+1 crosses PCIe on stream_c while batch k is on the convolutions
-  hipStream_t stream_c = nullptr;
-  hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_consumed[2] = {nullptr, nullptr};
+  Stream stream_c;
+  Event ev_copied[2], ev_consumed[2];
   bool consumed_valid[2] = {false, false};
-  void* pin_stage[2] = {nullptr, nullptr};      // page-locked staging for pageable caller buffers (lazily allocated)
-  size_t pin_stage_bytes[2] = {0, 0};
-  hipEvent_t ev_h2d_done[2] = {nullptr, nullptr};
+  PinnedBuf pin_stage[2];            // page-locked staging for pageable caller buffers (lazily allocated)
+  Event ev_h2d_done[2];
   bool h2d_valid[2] = {false, false};
   int img_flip = 0;
   float* cls_prob = nullptr;  // [M5][20]
@@ -348,7 +350,6 @@ struct ctpn_ctx {
   ConnectorCfg conn = default_connector_cfg();
   bool proposals_done = false;
   bool postproc_only = false;        // ctpn_create_postproc: proposal / connector buffers only, no network
-  std::unique_ptr<ctpn::HostPool> pool;
   int host_threads = 1;
   int keep_acts = 0;      // "keep_acts": 1 = also store the full-resolution output of pool-fused convs, keep lstm_o (layer-wise parity)
   float* cls_in = nullptr;  // staging for proposals_from_host
@@ -358,8 +359,8 @@ struct ctpn_ctx {
   // page-locked array, as [heights(n) | feature rows(n)]. One set per detect slot and one for ctpn_forward_ragged (index 2): a slot's
   // decode kernel reads its set on stream_p while the next submit's forward already copies the other slot's. Allocated on the first ragged call.
   struct RaggedSet {
-    int* host = nullptr; int* dev = nullptr;
-    hipEvent_t ev_copied = nullptr; bool copied_valid = false;      // the copy that last read `host`
+    PinnedBuf host; DevBuf dev;      // int [heights(n) | feature rows(n)]
+    Event ev_copied; bool copied_valid = false;      // the copy that last read `host`
   } ragged[3];
 
   bool forward_done = false;
@@ -369,11 +370,15 @@ struct ctpn_ctx {
   int prof_mode = 1;                 // 1: a pair of events around every stage (both slots then stay on forward set 0); 2: ONE pair around the 13 conv3x3
                                      // launches of a forward only (an event pair per launch costs ~0.2 ms of bubbles per step, which a throughput run
                                      // should not pay); conv_gemm's time is then the length of the UNION of the forwards' intervals (prof_drain)
-  std::vector<ProfRec> pending;
-  std::vector<hipEvent_t> free_events;
+  std::vector<ProfRec> pending;      // owning; Timed hands out the raw handles
+  std::vector<Event> free_events;
   double prof_ms[CTPN_KIND_COUNT] = {0};
   long long prof_n[CTPN_KIND_COUNT] = {0};
   double prof_work[CTPN_KIND_COUNT] = {0};
+
+  // LAST member, so the first to die: the pool's threads are joined before any block above goes away. The pool is idle between calls
+  // (HostPool::run returns when its job is done), so this is a matter of order only.
+  std::unique_ptr<ctpn::HostPool> pool;
 };
 
 namespace ctpn {
@@ -396,27 +401,6 @@ static inline bool nms_multi_wg(const ctpn_ctx* c, int n, int hf) {
   return nms_multi_wg_ok(c->nms_mw_scratch != nullptr, c->nms_columns, n, hf);
 }
 
-// a ctx-owned device buffer that grows to the largest size asked for (the output stages: api_out_stage.hip, the writers, api_crops.hip). Their calls return
-// when their results are complete, so nothing reads the old block any more when one grows
-static inline int grow_dev(void** p, size_t& have, size_t need) {
-  if (need <= have) return CTPN_OK;
-  if (*p) CTPN_HIP_TRY(hipFree(*p));
-  *p = nullptr; have = 0;
-  CTPN_HIP_TRY(hipMalloc(p, need));
-  have = need;
-  return CTPN_OK;
-}
-
-// ... and a page-locked host block of the same kind
-static inline int grow_host(uint8_t** p, size_t& have, size_t need) {
-  if (need <= have) return CTPN_OK;
-  if (*p) CTPN_HIP_TRY(hipHostFree(*p));
-  *p = nullptr; have = 0;
-  CTPN_HIP_TRY(hipHostMalloc((void**)p, need));
-  have = need;
-  return CTPN_OK;
-}
-
 // CTPN_DEBUG_SYNC / CTPN_ROCTX: read once per process (api_ctx.hip)
 int debug_sync();
 struct RoctxApi { int (*push)(const char*) = nullptr; int (*pop)() = nullptr; };
@@ -424,16 +408,23 @@ const RoctxApi& roctx_api();
 int roctx_on();
 static const char* kKindNames[CTPN_KIND_COUNT + 1] = {"ctpn:conv_first", "ctpn:conv_gemm", "ctpn:pool", "ctpn:gemm", "ctpn:bilstm",
                                                      "ctpn:decode", "ctpn:sort", "ctpn:nms", "ctpn:conv_stack"};
+// a timed event for a profiler pair: a recycled one if there is one. Where the creation fails the event stays null, hipEventElapsedTime refuses
+// it and prof_drain drops that record; a null event that comes back through free_events is created here the next time
+static inline Event prof_event(ctpn_ctx* c) {
+  Event e;
+  if (!c->free_events.empty()) { e = std::move(c->free_events.back()); c->free_events.pop_back(); }
+  (void)e.ensure_timed();
+  return e;
+}
 struct Timed {
-  ctpn_ctx* c; int kind; double work; hipEvent_t a = nullptr, b = nullptr; bool on; hipStream_t st;
+  ctpn_ctx* c; int kind; double work; Event a, b; bool on; hipStream_t st;
   Timed(ctpn_ctx* c_, int kind_, double work_, hipStream_t st_ = nullptr) : c(c_), kind(kind_), work(work_), on(c_->prof && (c_->prof_mode == 1 || kind_ == CTPN_KIND_COUNT)), st(st_ ? st_ : c_->stream) {
     if (debug_sync()) { fprintf(stderr, "[ctpn] launch kind %d work %.3g\n", kind, work); fflush(stderr); }
     // CTPN_ROCTX=1: a roctx range around the enqueue of every stage (rocprofv3 --marker-trace shows them next to the kernels;
     // the reference's only instrumentation is the wall-clock Timer of ctpn/demo.py:56-66)
     if (roctx_on()) (void)roctx_api().push(kKindNames[kind]);
     if (!on) return;
-    auto get = [&]() { hipEvent_t e; if (!c->free_events.empty()) { e = c->free_events.back(); c->free_events.pop_back(); } else { (void)hipEventCreate(&e); } return e; };
-    a = get(); b = get();
+    a = prof_event(c); b = prof_event(c);
     (void)hipEventRecord(a, st);
   }
   ~Timed() {
@@ -441,7 +432,7 @@ struct Timed {
     if (debug_sync()) { hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[ctpn]   done kind %d: %s\n", kind, hipGetErrorString(e)); fflush(stderr); }
     if (!on) return;
     (void)hipEventRecord(b, st);
-    c->pending.push_back({kind, a, b, work});
+    c->pending.push_back({kind, std::move(a), std::move(b), work});
   }
 };
 
@@ -460,7 +451,7 @@ bool ensure_set1(ctpn_ctx* c, bool need_conv1);
 // both forward streams drained (set 1's exists once the set does)
 static inline hipError_t sync_forwards(ctpn_ctx* c) {
   const hipError_t e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess || !c->fs[1].stream) return e;
+  if (e != hipSuccess || !c->fs[1].stream.get()) return e;
   return hipStreamSynchronize(c->fs[1].stream);
 }
 // the proposal layer in stream order on s (api_proposals.hip; null: the forward's stream); ev_decoded is recorded behind the decode kernel
@@ -473,7 +464,7 @@ int nms_check_generic(ctpn_ctx* c, const float* boxes, const float* scores, cons
 // the output stage of the writers and the crops (api_out_stage.hip). stage_pixels: a call's pixels where its kernels on qs may read them --
 // host images copied into buf (ctx-owned, grown to bytes + slack), device images in place, behind a live ctpn_decode_jpeg_batch batch's event
 int wait_live_batch(ctpn_ctx* c, const uint8_t* images_dev, hipStream_t qs);      // qs waits for the decode that produced images_dev, if it is a live batch or canvas
-int stage_pixels(ctpn_ctx* c, const uint8_t* images, int on_device, size_t bytes, size_t slack, uint8_t*& buf, size_t& buf_bytes, hipStream_t qs, const uint8_t*& px);
+int stage_pixels(ctpn_ctx* c, const uint8_t* images, int on_device, size_t bytes, size_t slack, DevBuf& buf, hipStream_t qs, const uint8_t*& px);
 // the ctpn_write_annotated_* entry points up to the file format: their argument checks (format: "JPEG" or "PNG", for the message; size_check,
 // nullable: the format's own check of both sizes), then the ctx's copy of the images, outlines drawn, resized by 1 / scale, at px (dh x dw)
 typedef int (*StageSizeCheck)(const std::string& who, int h, int w);

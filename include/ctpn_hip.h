@@ -469,6 +469,27 @@ int ctpn_debug_proposal_plan(int nms_columns, int nms_prefix, int mw_scratch, in
                              int pre_nms_topn, int post_nms_topn, float nms_thresh, const float* im_widths, int* plans);
 int ctpn_debug_proposal_fetch(ctpn_ctx* ctx, int what, void* out, size_t capacity_bytes);
 int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_img, int per_img, int segmented, unsigned long long* out);
+/* The first layer's kernels alone (test hooks; null stream, buffers allocated and freed inside). The weights go through the chain
+ * ctpn_load_weights_* uses (w_hwio 3 x 3 x 3 x 64 as the [27][64] block, bias[64], pack_conv1_frags). The image, n x h x w x 3 (h, w >= 16 as in
+ * ctpn_forward; at most 64 images and 2^20 pixels), is copied to byte 64 + byte_offset of a device block whose every other byte -- 64 in front
+ * of the image, at least 64 behind it -- is the poison value 0x47 (pixel 71; as a float 5.1e4): the image pointer the kernels get is
+ * byte_offset mod 4, no dword they may fetch leaves the block, and a byte outside the image used as a pixel shows in the result. Bordered output
+ * maps are pre-filled with bytes 0xC3 and followed by 64 guard rows; a border pixel or guard byte that changed is CTPN_ERR_STATE.
+ * ctpn_debug_conv1: one conv1_1 kernel. image: uint8, or float32 (image_is_f32; the mean-subtracted blob, byte_offset 0 only). form:
+ *     0 conv_first_kernel                          fp32, bf16, fp16             both feeds
+ *     1 conv_first_mfma_kernel                     bf16, fp16, split            both feeds
+ *     2 image_to_q_kernel + conv_first_p_kernel    bf16, fp16                   uint8 feed
+ *   anything else: CTPN_ERR_ARG. out: n x h x w x 64 fp32 (split precision: hi + lo). out_bits (nullable; not fp32): the stored 16-bit values,
+ *   n x h x w x 64, split precision n x h x w x [hi(64) | lo(64)]. q_out (nullable; form 2): the whole q-image, n x Hq x Wq x 4 uint16 with
+ *   Hq = 8 ceil(h / 8) + 4, Wq = 64 ceil(w / 64) + 8, built into a buffer of 0xC3 bytes -- image pixel (y, x) is q pixel (y + 2, x + 2), the frame
+ *   comes back as the fill, and a frame pixel that changed is CTPN_ERR_STATE; the conv reads a second q-image built into zeros, as in the product.
+ * ctpn_debug_conv1_fused: the production chain of the 16-bit modes' uint8 feed: launch_image_to_q, then conv1_2 (w2_hwio 3 x 3 x 64 x 64, bias2[64])
+ *   with conv1_1 computed inside its window stage and the 2x2 pool fused (conv3x3_wr_kernel<FUSE>). precision bf16 or fp16. out_pool:
+ *   n x h/2 x w/2 x 64 fp32, out_bits (nullable) its stored 16-bit values. A shape whose plan has a strip is refused by the launcher: its error. */
+int ctpn_debug_conv1(int device_id, const void* image, int image_is_f32, int byte_offset, const float* w_hwio, const float* bias, int n, int h, int w,
+                     int precision, int form, float* out, uint16_t* out_bits, uint16_t* q_out);
+int ctpn_debug_conv1_fused(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio,
+                           const float* bias2, int n, int h, int w, int precision, float* out_pool, uint16_t* out_bits);
 /* TextDetector.detect (lib/text_connector/detectors.py:19-49) for ONE image with every step on the device -- score > 0.7 prefix and
  * boxes / scale (lines_prep_kernel), NMS 0.2 (nms_kernel), graph build / chains / line fit / filter_boxes (connect_kernel) -- i.e.
  * the device-connector form of the asynchronous detect path (option connect_device = 1). rois: r x 5 fp32 [score,x1,y1,x2,y2] in

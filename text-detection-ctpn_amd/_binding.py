@@ -124,6 +124,9 @@ def _declare(lib):
                                                f32p, i32p]),
         "ctpn_debug_proposal_fetch": (C.c_int, [vp, C.c_int, C.c_void_p, C.c_size_t]),
         "ctpn_debug_sort_keys": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+        "ctpn_debug_conv1": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
+                                       C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
+        "ctpn_debug_conv1_fused": (C.c_int, [C.c_int, u8p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_uint16)]),
         "ctpn_jpeg_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_jpeg_coef_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_decode": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint16), i32p]),
@@ -797,6 +800,47 @@ def debug_gemm(a, w, bias, ldc=None, precision="fp32", device_id=0):
     _check(load_library().ctpn_debug_gemm(int(device_id), _ptr(a, C.c_float), _ptr(w, C.c_float), _ptr(bias, C.c_float), M, K, Co, ldc,
                                           precision_code(precision), _ptr(out, C.c_float)))
     return out
+
+
+CONV1_FORMS = ("valu", "mfma", "q")      # ctpn_debug_conv1's form 0, 1, 2
+
+
+def conv1_q_shape(h, w):
+    """(Hq, Wq) of the q-image of an h x w image (csrc/common.h: conv1_q_h, conv1_q_w)"""
+    return (h + 7) // 8 * 8 + 4, (w + 63) // 64 * 64 + 8
+
+
+def debug_conv1(images, w_hwio, bias, precision="bf16", form=0, byte_offset=0, want_bits=False, want_q=False, device_id=0):
+    """ctpn_debug_conv1: one conv1_1 kernel on caller data. images (n, h, w, 3): uint8 = the uint8 feed, anything else = the float blob feed.
+    Returns (conv1_1 (n, h, w, 64) fp32, the stored 16-bit values (n, h, w, 64 | 128) uint16 or None, the q-image (n, Hq, Wq, 4) uint16 or None)."""
+    images = np.asarray(images)
+    is_f32 = images.dtype != np.uint8
+    images = np.ascontiguousarray(images, dtype=np.float32 if is_f32 else np.uint8)
+    w_hwio = _f32(w_hwio); bias = _f32(bias)
+    n, h, w, c = images.shape
+    assert c == 3 and w_hwio.shape == (3, 3, 3, 64) and bias.shape == (64,)
+    out = np.zeros((n, h, w, 64), np.float32)
+    bits = np.zeros((n, h, w, 128 if precision == "split" else 64), np.uint16) if want_bits else None
+    q = np.zeros((n,) + conv1_q_shape(h, w) + (4,), np.uint16) if want_q else None
+    _check(load_library().ctpn_debug_conv1(int(device_id), images.ctypes.data_as(C.c_void_p), 1 if is_f32 else 0, int(byte_offset), _ptr(w_hwio, C.c_float),
+                                           _ptr(bias, C.c_float), n, h, w, precision_code(precision), int(form), _ptr(out, C.c_float),
+                                           _ptr(bits, C.c_uint16) if want_bits else None, _ptr(q, C.c_uint16) if want_q else None))
+    return out, bits, q
+
+
+def debug_conv1_fused(images, w_hwio, bias, w2_hwio, bias2, precision="bf16", byte_offset=0, device_id=0):
+    """ctpn_debug_conv1_fused: uint8 images -> q-image -> conv1_2 with conv1_1 in its window stage and the pool fused.
+    Returns (pool1 (n, h // 2, w // 2, 64) fp32, its stored 16-bit values as uint16)."""
+    images = np.ascontiguousarray(images, dtype=np.uint8)
+    w_hwio = _f32(w_hwio); bias = _f32(bias); w2_hwio = _f32(w2_hwio); bias2 = _f32(bias2)
+    n, h, w, c = images.shape
+    assert c == 3 and w_hwio.shape == (3, 3, 3, 64) and bias.shape == (64,) and w2_hwio.shape == (3, 3, 64, 64) and bias2.shape == (64,)
+    out = np.zeros((n, h // 2, w // 2, 64), np.float32)
+    bits = np.zeros((n, h // 2, w // 2, 64), np.uint16)
+    _check(load_library().ctpn_debug_conv1_fused(int(device_id), _ptr(images, C.c_uint8), int(byte_offset), _ptr(w_hwio, C.c_float), _ptr(bias, C.c_float),
+                                                 _ptr(w2_hwio, C.c_float), _ptr(bias2, C.c_float), n, h, w, precision_code(precision), _ptr(out, C.c_float),
+                                                 _ptr(bits, C.c_uint16)))
+    return out, bits
 
 
 ProposalPlan = collections.namedtuple("ProposalPlan", "npad fill_keys sort seg_len last_seg merge_wgs nms group_wgs prefix")

@@ -463,4 +463,166 @@ int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_im
   return CTPN_OK;
 }
 
+// ---- the first layer's kernels alone ---------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// The caller's image inside a larger block, at byte DBG_IMG_PAD + byte_offset of it, every other byte of the block DBG_POISON (uint8: pixel 71;
+// four of them as a float: 5.1e4): a kernel that takes a byte outside the image for a pixel computes a visibly wrong value.
+// Why 64 bytes either side are enough: the first-layer kernels read the image as single elements inside it (conv_first_kernel, the float feed
+// of conv_first_mfma_kernel) or as 4-byte ALIGNED dwords that hold at least one image byte -- so at most 3 bytes in front of the first and 3
+// behind the last image byte -- or as the aligned dword of the image's first byte (the redirect of dwords that hold none). 64 >= 3 keeps all of
+// those inside the block for any byte_offset, with room for a 16-byte aligned vector around either end.
+constexpr int DBG_IMG_PAD = 64;
+constexpr int DBG_POISON = 0x47;
+int dbg_stage_image(std::vector<DevBuf>& bufs, const void* image, size_t bytes, int byte_offset, const void** img_dev) {
+  const size_t total = ((size_t)DBG_IMG_PAD + byte_offset + bytes + DBG_IMG_PAD + 3) & ~(size_t)3;
+  std::vector<unsigned char> h(total, (unsigned char)DBG_POISON);
+  std::memcpy(h.data() + DBG_IMG_PAD + byte_offset, image, bytes);
+  void* d = nullptr;
+  if (const int rc = dbg_alloc(bufs, &d, total)) return rc;
+  CTPN_HIP_TRY(hipMemcpy(d, h.data(), total, hipMemcpyHostToDevice));
+  *img_dev = (const char*)d + DBG_IMG_PAD + byte_offset;      // device blocks are aligned to 256 bytes: the pointer is byte_offset mod 4
+  return CTPN_OK;
+}
+// conv1_1's weights as the ctx holds them (api_weights.hip): w_first = HWIO flattened [27][64], the bias, and the fragment block of
+// pack_conv1_frags (split-bf16 fragments, then the q-image form's bf16 and fp16 sets: conv1_p_frags)
+int dbg_conv1_weights(std::vector<DevBuf>& bufs, const float* w_hwio, const float* bias, void** d_w, void** d_b, void** d_frags) {
+  int rc;
+  if ((rc = dbg_alloc(bufs, d_w, 27 * 64 * 4)) || (rc = dbg_alloc(bufs, d_b, 64 * 4)) || (rc = dbg_alloc(bufs, d_frags, CF_FRAGS_TOTAL))) return rc;
+  CTPN_HIP_TRY(hipMemcpy(*d_w, w_hwio, 27 * 64 * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemcpy(*d_b, bias, 64 * 4, hipMemcpyHostToDevice));
+  return pack_conv1_frags((const float*)*d_w, (const float*)*d_b, (uint4*)*d_frags);
+}
+// A bordered map [n][H + 2][W + 2] of pix-byte pixels followed by DBG_GUARD_ROWS rows of W + 2 pixels, all DBG_FILL before the launch
+size_t dbg_map_bytes(int n, int H, int W, size_t pix) { return ((size_t)n * (H + 2) + DBG_GUARD_ROWS) * (W + 2) * pix; }
+// ... fetched after it: every border pixel and every guard row must still hold the fill
+int dbg_fetch_map(const void* d_map, int n, int H, int W, size_t pix, std::vector<char>& host, const char* who) {
+  host.resize(dbg_map_bytes(n, H, W, pix));
+  CTPN_HIP_TRY(hipMemcpy(host.data(), d_map, host.size(), hipMemcpyDeviceToHost));
+  const size_t row = (size_t)(W + 2) * pix;
+  if (!dbg_fill_intact(host.data() + (size_t)n * (H + 2) * row, (size_t)DBG_GUARD_ROWS * row)) return fail(CTPN_ERR_STATE, std::string(who) + ": a guard row behind the map was written");
+  for (int in = 0; in < n; ++in)
+    for (int y = 0; y < H + 2; ++y) {
+      const char* r = host.data() + ((size_t)in * (H + 2) + y) * row;
+      const bool whole = y == 0 || y == H + 1;
+      if (!(whole ? dbg_fill_intact(r, row) : (dbg_fill_intact(r, pix) && dbg_fill_intact(r + row - pix, pix))))
+        return fail(CTPN_ERR_STATE, std::string(who) + ": a border pixel of the map was written (image " + std::to_string(in) + ", bordered row " + std::to_string(y) + ")");
+    }
+  return CTPN_OK;
+}
+// the interior of a fetched map as dense fp32 (split precision: hi + lo) and, where asked, its stored 16-bit values [pixel][planes x 64]
+void dbg_unpack_map(const std::vector<char>& host, DType t, int n, int H, int W, float* out, uint16_t* out_bits) {
+  const int planes = t == DType::SPLIT ? 2 : 1;
+  const size_t pix = (size_t)64 * planes * (t == DType::F32 ? 4 : 2);
+  for (int in = 0; in < n; ++in) for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) {
+    const char* p = host.data() + (((size_t)in * (H + 2) + y + 1) * (W + 2) + x + 1) * pix;
+    const size_t o = ((size_t)in * H + y) * W + x;
+    if (t == DType::F32) { std::memcpy(out + o * 64, p, 256); continue; }
+    if (out_bits) std::memcpy(out_bits + o * 64 * planes, p, pix);
+    for (int c = 0; c < 64; ++c) {
+      uint16_t b; std::memcpy(&b, p + 2 * c, 2);
+      float v = t == DType::F16 ? host_f16_to_f32(b) : host_bf16_to_f32(b);
+      if (planes == 2) { uint16_t l; std::memcpy(&l, p + 2 * (64 + c), 2); v += host_bf16_to_f32(l); }
+      out[o * 64 + c] = v;
+    }
+  }
+}
+int dbg_conv1_shape_ok(int n, int h, int w) { return n >= 1 && n <= 64 && h >= 16 && w >= 16 && h <= 8192 && w <= 8192 && (long long)n * h * w <= (1 << 20); }
+}  // namespace
+extern "C" {
+
+int ctpn_debug_conv1(int device_id, const void* image, int image_is_f32, int byte_offset, const float* w_hwio, const float* bias, int n, int h, int w,
+                     int precision, int form, float* out, uint16_t* out_bits, uint16_t* q_out) {
+  if (!image || !w_hwio || !bias || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: null pointer");
+  if (precision < CTPN_PREC_FP32 || precision > CTPN_PREC_SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: unknown precision");
+  const DType t = prec_dtype(precision);
+  const bool f32in = image_is_f32 != 0;
+  if (form < 0 || form > 2) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: form is 0 (conv_first_kernel), 1 (conv_first_mfma_kernel) or 2 (image_to_q_kernel + conv_first_p_kernel)");
+  if (form == 0 && t == DType::SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: conv_first_kernel (form 0) stores fp32, bf16 or fp16");
+  if (form == 1 && t == DType::F32) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: conv_first_mfma_kernel (form 1) stores bf16, fp16 or split precision");
+  if (form == 2 && (!dtype_is_half(t) || f32in)) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: the q-image form (form 2) is the uint8 feed of bf16 and fp16");
+  if (byte_offset < 0 || byte_offset > 3 || (f32in && byte_offset)) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: byte_offset is 0 .. 3, and 0 for the float feed");
+  if (!dbg_conv1_shape_ok(n, h, w)) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: n 1 .. 64, h and w 16 .. 8192, at most 2^20 pixels");
+  if (out_bits && t == DType::F32) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: fp32 stores no 16-bit values (out is the stored map)");
+  if (q_out && form != 2) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1: only form 2 builds a q-image");
+  if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_conv1: no HIP device visible (no CPU fallback)");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  std::vector<DevBuf> bufs;
+  const void* d_img = nullptr;
+  void *d_w = nullptr, *d_b = nullptr, *d_frags = nullptr, *d_out = nullptr, *d_qfill = nullptr, *d_q = nullptr;
+  const size_t pix = (size_t)(t == DType::SPLIT ? 128 : 64) * (t == DType::F32 ? 4 : 2), map_bytes = dbg_map_bytes(n, h, w, pix);
+  const size_t q_bytes = conv1_q_bytes(n, h, w);
+  int rc;
+  if ((rc = dbg_stage_image(bufs, image, (size_t)n * h * w * 3 * (f32in ? 4 : 1), byte_offset, &d_img)) || (rc = dbg_conv1_weights(bufs, w_hwio, bias, &d_w, &d_b, &d_frags)) ||
+      (rc = dbg_alloc(bufs, &d_out, map_bytes))) return rc;
+  CTPN_HIP_TRY(hipMemset(d_out, DBG_FILL, map_bytes));
+  if (form == 2) {
+    if ((rc = dbg_alloc(bufs, &d_qfill, q_bytes)) || (rc = dbg_alloc(bufs, &d_q, q_bytes))) return rc;
+    CTPN_HIP_TRY(hipMemset(d_qfill, DBG_FILL, q_bytes));
+    CTPN_HIP_TRY(hipMemset(d_q, 0, q_bytes));
+  }
+  CTPN_HIP_TRY(hipDeviceSynchronize());
+  if (form == 2) {
+    // the q-image twice: into a filled buffer, where a write outside the image's pixels shows, and into a zeroed one, the product's initial
+    // state, which the conv then reads
+    if ((rc = launch_image_to_q((const uint8_t*)d_img, d_qfill, t, n, h, w, nullptr)) || (rc = launch_image_to_q((const uint8_t*)d_img, d_q, t, n, h, w, nullptr)) ||
+        (rc = launch_conv_first_from_q(d_q, conv1_p_frags(d_frags, t), d_out, t, n, h, w, 0, w, nullptr))) return rc;
+  } else if ((rc = launch_conv_first(d_img, f32in ? 1 : 0, (const float*)d_w, (const float*)d_b, d_out, t, n, h, w, nullptr, form == 1 ? d_frags : nullptr))) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_conv1: kernel failed");
+  if (form == 2) {
+    const int hq = conv1_q_h(h), wq = conv1_q_w(w);
+    std::vector<char> hq_img(q_bytes);
+    CTPN_HIP_TRY(hipMemcpy(hq_img.data(), d_qfill, q_bytes, hipMemcpyDeviceToHost));
+    const size_t qrow = (size_t)wq * 8, used = (size_t)n * hq * qrow;
+    if (!dbg_fill_intact(hq_img.data() + used, q_bytes - used)) return fail(CTPN_ERR_STATE, "ctpn_debug_conv1: the q-image buffer was written behind the last image");
+    for (int in = 0; in < n; ++in)
+      for (int y = 0; y < hq; ++y) {
+        const char* r = hq_img.data() + ((size_t)in * hq + y) * qrow;
+        const bool inside = y >= 2 && y < 2 + h;
+        if (!(inside ? (dbg_fill_intact(r, 16) && dbg_fill_intact(r + (size_t)(2 + w) * 8, qrow - (size_t)(2 + w) * 8)) : dbg_fill_intact(r, qrow)))
+          return fail(CTPN_ERR_STATE, "ctpn_debug_conv1: a frame pixel of the q-image was written (image " + std::to_string(in) + ", q row " + std::to_string(y) + ")");
+      }
+    if (q_out) std::memcpy(q_out, hq_img.data(), used);
+  }
+  std::vector<char> host;
+  if ((rc = dbg_fetch_map(d_out, n, h, w, pix, host, "ctpn_debug_conv1"))) return rc;
+  dbg_unpack_map(host, t, n, h, w, out, out_bits);
+  return CTPN_OK;
+}
+
+int ctpn_debug_conv1_fused(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio, const float* bias2,
+                           int n, int h, int w, int precision, float* out_pool, uint16_t* out_bits) {
+  if (!image || !w_hwio || !bias || !w2_hwio || !bias2 || !out_pool) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: null pointer");
+  if (precision != CTPN_PREC_BF16 && precision != CTPN_PREC_FP16) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: the fused form is bf16 or fp16");
+  if (byte_offset < 0 || byte_offset > 3) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: byte_offset is 0 .. 3");
+  if (!dbg_conv1_shape_ok(n, h, w)) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: n 1 .. 64, h and w 16 .. 8192, at most 2^20 pixels");
+  if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_conv1_fused: no HIP device visible (no CPU fallback)");
+  CTPN_HIP_TRY(hipSetDevice(device_id));
+  const DType t = prec_dtype(precision);
+  const int ho = h / 2, wo = w / 2;
+  std::vector<DevBuf> bufs;
+  const void* d_img = nullptr;
+  void *d_w = nullptr, *d_b = nullptr, *d_frags = nullptr, *d_w2 = nullptr, *d_wt2 = nullptr, *d_b2 = nullptr, *d_q = nullptr, *d_pool = nullptr;
+  const size_t pix = 64 * 2, map_bytes = dbg_map_bytes(n, ho, wo, pix), q_bytes = conv1_q_bytes(n, h, w), wt_bytes = (size_t)128 * 9 * 64 * 2;
+  int rc;
+  if ((rc = dbg_stage_image(bufs, image, (size_t)n * h * w * 3, byte_offset, &d_img)) || (rc = dbg_conv1_weights(bufs, w_hwio, bias, &d_w, &d_b, &d_frags)) ||
+      (rc = dbg_alloc(bufs, &d_w2, (size_t)9 * 64 * 64 * 4)) || (rc = dbg_alloc(bufs, &d_wt2, wt_bytes)) || (rc = dbg_alloc(bufs, &d_b2, 128 * 4)) ||
+      (rc = dbg_alloc(bufs, &d_q, q_bytes)) || (rc = dbg_alloc(bufs, &d_pool, map_bytes))) return rc;
+  CTPN_HIP_TRY(hipMemcpy(d_w2, w2_hwio, (size_t)9 * 64 * 64 * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemset(d_wt2, 0, wt_bytes));      // weight rows and bias padded to 128 channels with zeros, as ctpn_debug_conv3x3 does
+  CTPN_HIP_TRY(hipMemset(d_b2, 0, 128 * 4));
+  CTPN_HIP_TRY(hipMemcpy(d_b2, bias2, 64 * 4, hipMemcpyHostToDevice));
+  CTPN_HIP_TRY(hipMemset(d_q, 0, q_bytes));          // the zero frame is the buffer's initial state
+  CTPN_HIP_TRY(hipMemset(d_pool, DBG_FILL, map_bytes));
+  CTPN_HIP_TRY(hipDeviceSynchronize());
+  // the production chain of api_forward.hip: bytes -> q-image, conv1_1 inside conv1_2's window stage (conv1_1's map is never stored: no `in`)
+  if ((rc = launch_pack_transpose((const float*)d_w2, 64, d_wt2, 9 * 64, t, 9 * 64, 64, nullptr)) || (rc = launch_image_to_q((const uint8_t*)d_img, d_q, t, n, h, w, nullptr)) ||
+      (rc = launch_conv3x3(nullptr, d_wt2, (const float*)d_b2, nullptr, d_pool, t, n, h, w, 64, 64, 1, nullptr, 0, d_q, conv1_p_frags(d_frags, t)))) return rc;
+  if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_conv1_fused: kernel failed");
+  std::vector<char> host;
+  if ((rc = dbg_fetch_map(d_pool, n, ho, wo, pix, host, "ctpn_debug_conv1_fused"))) return rc;
+  dbg_unpack_map(host, t, n, ho, wo, out_pool, out_bits);
+  return CTPN_OK;
+}
+
 }  // extern "C"

@@ -610,6 +610,43 @@ int    ctpn_decode_jpeg_batch_ragged(ctpn_ctx* ctx, const uint8_t* const* files,
 int    ctpn_decode_jpeg_files_ragged(ctpn_ctx* ctx, const char* const* paths, int n, const int* file_h, const int* file_w, const double* factors,
                                      int hc, int wc, int entropy_on_device, const uint8_t** canvas_dev_out, int* heights_out);
 
+/* ---- Decoded images and PNG files of MIXED sizes into one ragged device batch (canvas_pack.hip): additive to ABI 10, no option and no
+ * default changes. The two calls above build a ragged canvas from JPEG files; these two build it from every other source the library takes:
+ * BGR uint8 images already decoded, on the host or on the device, and PNG files. One kernel resizes every image by its own factor into its
+ * slot and writes the zeros below it: no per-image resize call, no canvas built on the host, no memset.
+ *   ctpn_pack_canvas               images[i]: img_h[i] x img_w[i] x 3 BGR uint8, rows pitches[i] bytes apart (pitches NULL: 3 x img_w[i]; a
+ *                                  pitch below that is CTPN_ERR_ARG); no alignment of pointer or pitch is required. factors[i]: the image's
+ *                                  resize_im factor, used as fx = fy (<= 0 or 1: no resize). Every width must map to the canvas's --
+ *                                  ctpn_resize_dims(img_h[i], img_w[i], factors[i], factors[i]) gives wc -- and every height to 16 .. hc;
+ *                                  otherwise CTPN_ERR_ARG naming the image, before any work, as is a NULL image. n above the ctx's max_batch
+ *                                  or a canvas above max_h x max_w is CTPN_ERR_ARG. Result: a canvas n x hc x wc x 3 BGR uint8 in device
+ *                                  memory owned by the ctx; slot i holds cv2.resize(image i, factors[i]) in rows [0, heights_out[i]) and
+ *                                  ZEROS below (lib/utils/blob.py im_list_to_canvas's canvas, byte for byte: image i's rows are what
+ *                                  ctpn_resize returns for it alone).
+ *                                  images_on_device = 0: the images are copied into a page-locked block of the ctx at prefix-summed
+ *                                  offsets (rows at pitch 3 w, on the ctx's host pool) and cross in ONE copy together with their
+ *                                  descriptors; they may be reused when the call returns. The zero-padded canvas never crosses.
+ *                                  images_on_device = 1: device pointers, read in place and never written; a pointer that is a live
+ *                                  batch of a decode call is waited for in the copy queue, any other memory must be complete when the
+ *                                  call is made and stay unchanged until work that reads the canvas has been waited for.
+ *                                  Buffers and events are ctpn_decode_jpeg_batch's -- the same two sets, in turn with the JPEG calls:
+ *                                  *canvas_dev_out is valid for ctpn_forward_ragged / ctpn_detect_submit_ragged(canvas_on_device = 1) --
+ *                                  which wait for it by pointer match, as for the JPEG canvas --, the ragged writers and crops and
+ *                                  ctpn_jpeg_batch_fetch (n x hc x wc x 3 bytes) until the second-next decode or pack call of any
+ *                                  kind. Everything runs on the ctx's copy queue; the call returns when the work is queued.
+ *   ctpn_decode_png_files_ragged   n PNG files of file_h[i] x file_w[i] (ctpn_png_probe_files) through the same path: the ctx's host pool
+ *                                  runs ctpn_png_decode's decoder, one file per worker, straight into the page-locked block at the file's
+ *                                  offset (gray, palette and RGBA files are expanded to BGR there). A file of another size than announced
+ *                                  is CTPN_ERR_ARG; a decoder error (bad CRC, a missing file, CTPN_ERR_UNSUPPORTED for 16-bit samples)
+ *                                  fails the call with that file's code; ctpn_last_error() names the file's index and path.
+ * A post-processing-only ctx is CTPN_ERR_STATE; a NULL ctx in a process without a device CTPN_ERR_NODEVICE (there is no host form).
+ * Rate (tools/canvas_pack_throughput.py, profiles/canvas_pack_throughput.json): on a folder of PNG files of 16 sizes, files to text lines,
+ * 2.5 - 3.2 x the size-grouped path and 11 - 14 x a canvas built on the host. The kernel alone has not been timed. */
+int    ctpn_pack_canvas(ctpn_ctx* ctx, const uint8_t* const* images, const int* img_h, const int* img_w, const long long* pitches /* NULL: 3 w */,
+                        int images_on_device, int n, const double* factors, int hc, int wc, const uint8_t** canvas_dev_out, int* heights_out);
+int    ctpn_decode_png_files_ragged(ctpn_ctx* ctx, const char* const* paths, int n, const int* file_h, const int* file_w, const double* factors,
+                                    int hc, int wc, const uint8_t** canvas_dev_out, int* heights_out);
+
 /* ---- cv2.imwrite for the annotated result images (reference ctpn/demo.py:28-52: draw_boxes, cv2.resize by 1 / scale, cv2.imwrite), the mirror
  * image of the JPEG reader above, split where the work splits: BGR -> YCbCr, 2 x 2 chroma downsampling, the 8 x 8 forward DCT and the
  * quantiser on the device (one launch; the outlines and the resize before it, so annotated pixels never visit the host), baseline Huffman

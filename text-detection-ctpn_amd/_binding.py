@@ -144,6 +144,8 @@ def _declare(lib):
         "ctpn_decode_jpeg_batch_ragged": (C.c_int, [vp, C.POINTER(u8p), C.POINTER(C.c_size_t), C.c_int, i32p, i32p, f64p, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(vp), i32p]),
         "ctpn_decode_jpeg_files_ragged": (C.c_int, [vp, C.POINTER(C.c_char_p), C.c_int, i32p, i32p, f64p, C.c_int, C.c_int, C.c_int, C.POINTER(vp), i32p]),
+        "ctpn_pack_canvas": (C.c_int, [vp, C.POINTER(vp), i32p, i32p, C.POINTER(C.c_longlong), C.c_int, C.c_int, f64p, C.c_int, C.c_int, C.POINTER(vp), i32p]),
+        "ctpn_decode_png_files_ragged": (C.c_int, [vp, C.POINTER(C.c_char_p), C.c_int, i32p, i32p, f64p, C.c_int, C.c_int, C.POINTER(vp), i32p]),
         "ctpn_jpeg_encode_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_encode": (C.c_int, [C.POINTER(C.c_int16), i32p, C.POINTER(C.c_uint16), u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
         "ctpn_encode_jpeg_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t),
@@ -419,6 +421,65 @@ def decode_png_files(paths, h, w, threads=0, out=None):
     assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape == (len(paths), int(h), int(w), 3)
     _check(lib.ctpn_decode_png_files(arr, len(paths), int(h), int(w), _ptr(out, C.c_uint8), int(threads)))
     return out
+
+
+def pack_canvas(ctx, images, factors, hc, wc):
+    """BGR uint8 images of mixed sizes, each resized by its own factor, into one ragged canvas on the device (ctpn_pack_canvas). images:
+    every item an (h, w, 3) uint8 array on the host (rows may be strided), or every item a device image (pointer, (h, w)) or (pointer,
+    (h, w), pitch in bytes), read in place. factors: one resize_im factor per image (<= 0 or 1: no resize); every width must map to wc and
+    every height to 16 .. hc. -> ((device pointer, (n, hc, wc)), heights int32), the form Context.decode_jpeg_ragged returns. ctx: a Context
+    (None: the call reports what the library says without one -- CTPN_ERR_NODEVICE where no GPU is visible; there is no host form)."""
+    lib = load_library()
+    items = list(images)
+    n = len(items)
+    on_dev = [isinstance(it, (tuple, list)) for it in items]
+    if any(on_dev) and not all(on_dev):
+        raise ValueError("pack_canvas wants all images as host arrays or all as device (pointer, (h, w)[, pitch]) items")
+    on_dev = bool(n) and all(on_dev)
+    keep, ptrs = [], (C.c_void_p * max(n, 1))()
+    hw = np.zeros((max(n, 1), 2), np.int32)
+    pitch = np.zeros((max(n, 1),), np.int64)
+    for i, it in enumerate(items):
+        if on_dev:
+            ptrs[i] = int(it[0]) if it[0] else None
+            hw[i] = (int(it[1][0]), int(it[1][1]))
+            pitch[i] = int(it[2]) if len(it) > 2 else 3 * int(it[1][1])
+            continue
+        a = np.asarray(it)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("pack_canvas wants (h, w, 3) uint8 images")
+        if a.size and (a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]):
+            a = np.ascontiguousarray(a)
+        keep.append(a)
+        ptrs[i] = a.ctypes.data
+        hw[i] = a.shape[:2]
+        pitch[i] = a.strides[0] if a.shape[0] > 1 else 3 * a.shape[1]
+    fh, fw = np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+    fac = np.ascontiguousarray(np.asarray(factors, np.float64).reshape(n))
+    fac = fac if n else np.zeros((1,), np.float64)
+    hts = np.zeros((max(n, 1),), np.int32)
+    out = C.c_void_p(0)
+    _check(lib.ctpn_pack_canvas(ctx._h if ctx is not None else None, ptrs, _ptr(fh, C.c_int), _ptr(fw, C.c_int), _ptr(pitch, C.c_longlong), 1 if on_dev else 0, n,
+                                _ptr(fac, C.c_double), int(hc), int(wc), C.byref(out), _ptr(hts, C.c_int)))
+    return (out.value, (n, int(hc), int(wc))), hts[:n]
+
+
+def decode_png_files_ragged(ctx, paths, shapes, factors, hc, wc):
+    """PNG files of mixed sizes into one ragged canvas on the device (ctpn_decode_png_files_ragged): the library's worker threads read and
+    decode the files into page-locked memory, one copy and one kernel build the canvas. shapes: one (h, w) per file as png_probe_files
+    reports it; factors, hc, wc and the result: as pack_canvas."""
+    lib = load_library()
+    paths = list(paths)
+    n = len(paths)
+    keep, arr = _path_array(paths)
+    hw = np.ascontiguousarray(np.asarray(shapes, np.int32).reshape(n, 2)) if n else np.zeros((1, 2), np.int32)
+    fh, fw = np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+    fac = np.ascontiguousarray(np.asarray(factors, np.float64).reshape(n)) if n else np.zeros((1,), np.float64)
+    hts = np.zeros((max(n, 1),), np.int32)
+    out = C.c_void_p(0)
+    _check(lib.ctpn_decode_png_files_ragged(ctx._h if ctx is not None else None, arr, n, _ptr(fh, C.c_int), _ptr(fw, C.c_int), _ptr(fac, C.c_double), int(hc), int(wc),
+                                            C.byref(out), _ptr(hts, C.c_int)))
+    return (out.value, (n, int(hc), int(wc))), hts[:n]
 
 
 def jpeg_entropy_decode(data):
@@ -1243,6 +1304,17 @@ class Context:
             _check(self._lib.ctpn_decode_jpeg_batch_ragged(self._h, ptrs, lens, n, _ptr(fh, C.c_int), _ptr(fw, C.c_int), _ptr(fac, C.c_double), int(hc), int(wc),
                                                            on_dev, C.byref(out), _ptr(hts, C.c_int)))
         return (out.value, (n, int(hc), int(wc))), hts
+
+    def pack_canvas(self, images, factors, hc, wc):
+        """Images of mixed sizes -- (h, w, 3) uint8 arrays, or device (pointer, (h, w)[, pitch]) items -- into one ragged canvas on the device
+        (ctpn_pack_canvas; see the module's pack_canvas). -> ((device pointer, (n, hc, wc)), heights int32), as decode_jpeg_ragged returns them;
+        the canvas stays valid until the second-next decode or pack call."""
+        return pack_canvas(self, images, factors, hc, wc)
+
+    def decode_png_ragged(self, paths, shapes, factors, hc, wc):
+        """PNG files of mixed sizes into one ragged canvas on the device (ctpn_decode_png_files_ragged; see the module's
+        decode_png_files_ragged). -> ((device pointer, (n, hc, wc)), heights int32), as decode_jpeg_ragged returns them."""
+        return decode_png_files_ragged(self, paths, shapes, factors, hc, wc)
 
     def jpeg_batch_fetch(self, device_ptr, shape):
         """The decoded batch as an (n, h, w, 3) uint8 array on the host (ctpn_jpeg_batch_fetch)."""

@@ -7,13 +7,17 @@ namespace ctpn {
 
 // coef_total: int16 elements of the call's coefficient blocks (n x one capacity, or the sum of the files' own); tab: the ragged call's
 // descriptor table too
+int jpeg_sets_ready(ctpn_ctx* c) {
+  if (c->jpeg_ready) return CTPN_OK;
+  int rc;
+  for (auto& j : c->jpeg)
+    for (Event* e : {&j.ev_h2d, &j.ev_ready, &j.ev_consumed}) if ((rc = e->ensure())) return rc;
+  c->jpeg_ready = true;
+  return CTPN_OK;
+}
+
 static int jpeg_reserve(ctpn_ctx* c, ctpn_ctx::JpegBufs& J, size_t n, size_t coef_total, size_t raw_bytes, size_t out_bytes, bool tab) {
-  if (!c->jpeg_ready) {
-    int rc;
-    for (auto& j : c->jpeg)
-      for (Event* e : {&j.ev_h2d, &j.ev_ready, &j.ev_consumed}) if ((rc = e->ensure())) return rc;
-    c->jpeg_ready = true;
-  }
+  if (const int rc = jpeg_sets_ready(c)) return rc;
   // a device block that grows is retired, not freed: work in flight may still read it, and the caller may hold a pointer into it
   std::vector<DevBuf>& old = c->jpeg_retired;
   // a page-locked block and its device twin (the copy that last read the page-locked block has been waited for by the caller)

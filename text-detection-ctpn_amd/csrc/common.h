@@ -215,6 +215,13 @@ size_t resize_mixed_pitch(int dw);
 long long resize_mixed_fill(void* table, int n, const int* h, const int* w, const int* dh, const int* dw, const long long* src_off, const long long* src_pitch,
                             const long long* dst_off, const double* inv_f);
 int launch_resize_linear_mixed(const uint8_t* src_dev, uint8_t* dst_dev, const void* tab_dev, int n, long long total_items, hipStream_t s);
+// canvas_pack.hip: the uint8 form over a table of images of different sizes, each by its own factor, into the slots of ONE ragged canvas
+// n x hc x wc x 3 (descriptor, per-thread text: canvas_pack_dev.h). canvas_pack_fill writes n descriptors of CP_DESC_BYTES each: image i is
+// h[i] x w[i] at src_off[i] bytes from the launch's source base, rows src_pitch[i] bytes apart, resized by f[i] (<= 0 or 1: copied) into rows
+// [0, dh[i]) of slot i; the kernel writes zeros below, i.e. every byte of the canvas
+constexpr size_t CP_DESC_BYTES = 40;
+void canvas_pack_fill(void* table, int n, const long long* src_off, const long long* src_pitch, const int* h, const int* w, const double* f, const int* dh);
+int launch_canvas_pack(const uint8_t* src_dev, uint8_t* canvas_dev, const void* tab_dev, int n, int hc, int wc, hipStream_t s);
 int launch_cvt_bf16(const float* in, uint16_t* out, int n, int hw, hipStream_t s);
 // the two LDS-DMA helper forms of conv3x3_base.h on `tiles` 1-KiB tiles of src (conv3x3.hip; test hook behind ctpn_debug_lds_dma)
 int launch_lds_dma_check(const void* src, void* out_clobber, void* out_keep, int tiles, hipStream_t s);
@@ -454,6 +461,9 @@ int launch_png_hist(const PngeImg* imgs, const uint8_t* px, uint32_t* hist, int 
 int launch_png_code(const PngeImg* imgs, const uint8_t* px, const PngeCodes* codes, PngeLen* len, uint32_t* words, PngeRes* res, int n, uint64_t items, hipStream_t s);
 // png.cpp: CRC-32 of the PNG chunks (the DEFLATE library's where one is loaded)
 uint32_t png_crc32(const uint8_t* p, size_t n);
+// png.cpp: one file read and decoded to want_h x want_w x 3 BGR bytes at bgr_out (ctpn_decode_png_files's work on one file; callable from
+// any thread). A file of another size is CTPN_ERR_ARG; `why` says what failed
+int png_decode_file(const char* path, uint8_t* bgr_out, size_t capacity, int want_h, int want_w, std::string& why);
 
 // ragged.hip: a canvas batch of images of one width and different heights (RaggedMap and the per-thread bodies: ragged_dev.h).
 // heights_dev: the batch's pixel heights; max_pad_rows: the most rows any image lacks at the map's level (0: no launch)

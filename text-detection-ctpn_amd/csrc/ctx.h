@@ -171,6 +171,9 @@ struct ctpn_ctx {
     PinnedBuf coef_host, qt_host;      // page-locked: what the entropy decoders write (int16 coefficients, uint16 tables)
     DevBuf coef_dev, qt_dev, out_dev;
     PinnedBuf tab_host; DevBuf tab_dev;      // ctpn_decode_jpeg_batch_ragged: per-image descriptors (page-locked / device)
+    // ctpn_pack_canvas / ctpn_decode_png_files_ragged (api_canvas_pack.hip): [descriptors(n) | host images at prefix-summed offsets, rows at pitch 3 w],
+    // page-locked, and the device copy ONE transfer makes of it
+    PinnedBuf src_host; DevBuf src_dev;
     int out_n = 0, out_h = 0, out_w = 0;                            // what out_dev holds
     Event ev_h2d, ev_ready, ev_consumed;
     bool h2d_valid = false, consumed_valid = false, ready_valid = false;
@@ -493,6 +496,7 @@ typedef int (*StageTableCheck)(const std::string& who, int n, const int* heights
 int annotate_ragged(ctpn_ctx* c, const std::string& who, const char* format, StageTableCheck table_check, const uint8_t* canvas, int canvas_on_device, int n, int hc, int w,
                     const int* heights, const double* recs, int line_capacity, const int* line_counts, const double* scales, const char* const* paths, const uint8_t*& px,
                     std::vector<int>& dh, std::vector<int>& dw, std::vector<size_t>& pitches, std::vector<size_t>& offsets);
+int jpeg_sets_ready(ctpn_ctx* c);      // api_jpeg_decode.hip: the events of the two decode buffer sets (c->jpeg) exist; the decode and the pack calls take the sets in turn
 bool jpeg_read_file(const char* path, std::vector<uint8_t>& buf, size_t limit = 0);      // api_input.hip: a whole file (limit: its first bytes only); false if it cannot be read
 void jpeg_layout8(const JpegGeom& g, int* layout8);                                      // api_input.hip: the eight ints ctpn_jpeg_entropy_decode describes a file's layout with
 

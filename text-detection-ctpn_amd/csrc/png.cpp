@@ -358,6 +358,16 @@ uint32_t ctpn::png_crc32(const uint8_t* p, size_t n) {
   return ~c;
 }
 
+int ctpn::png_decode_file(const char* path, uint8_t* bgr_out, size_t capacity, int want_h, int want_w, std::string& why) {
+  thread_local std::vector<uint8_t> buf;
+  try {
+    if (!png_read_file(path, buf, 0)) { why = std::string("cannot read ") + path; return CTPN_ERR_ARG; }
+    const int rc = png_decode(buf.data(), buf.size(), bgr_out, capacity, want_h, want_w, why);
+    if (buf.capacity() > ((size_t)16 << 20)) std::vector<uint8_t>().swap(buf);      // one huge file must not pin its size per worker for the run
+    return rc;
+  } catch (const std::exception& e) { why = e.what(); return CTPN_ERR_CAPACITY; }      // nothing may leave a worker thread
+}
+
 using namespace ctpn;
 
 extern "C" {
@@ -402,14 +412,7 @@ int ctpn_decode_png_files(const char* const* paths, int n, int h, int w, uint8_t
   std::vector<int> st((size_t)n, CTPN_OK);
   std::vector<std::string> msg((size_t)n);
   const size_t per = (size_t)h * w * 3;
-  PngPool::get().run(n, threads, [&](int i) {
-    thread_local std::vector<uint8_t> buf;
-    try {
-      if (!png_read_file(paths[i], buf, 0)) { st[i] = CTPN_ERR_ARG; msg[i] = std::string("cannot read ") + paths[i]; return; }
-      st[i] = png_decode(buf.data(), buf.size(), bgr_out + per * i, per, h, w, msg[i]);
-      if (buf.capacity() > ((size_t)16 << 20)) std::vector<uint8_t>().swap(buf);      // one huge file must not pin its size per worker for the run
-    } catch (const std::exception& e) { st[i] = CTPN_ERR_CAPACITY; msg[i] = e.what(); }      // nothing may leave a worker thread
-  });
+  PngPool::get().run(n, threads, [&](int i) { st[i] = png_decode_file(paths[i], bgr_out + per * i, per, h, w, msg[i]); });
   for (int i = 0; i < n; ++i) if (st[i]) return fail(st[i], "ctpn_decode_png_files: file " + std::to_string(i) + " (" + paths[i] + "): " + msg[i]);
   return CTPN_OK;
 }

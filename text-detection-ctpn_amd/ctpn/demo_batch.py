@@ -28,6 +28,10 @@ with the same per-image arithmetic as demo.ctpn() (reference ctpn/demo.py:55-68)
     with --ragged-png (next to --ragged --ragged-outputs --png-encode gpu) the PNG files of the run share ragged batches too and are
     written from their canvases (ctpn_write_annotated_png_files_ragged). Same names, same decoded pixels.
 
+  * with --ragged-pack gpu (next to --ragged and --decode gpu / gpu-entropy) the PNG files the library takes share ragged batches whose
+    canvases are built on the device: decoded by the library's pool into page-locked memory, resized into the canvas by one kernel
+    (ctpn_decode_png_files_ragged). Same result files; the default, host, is the run without the switch.
+
   * cfg.TEST.RPN_* of the loaded text.yml go into the ctx's tail parameters (ctpn_set_param), so the batched path honours the file like
     the single-image path; --connector NAME=VALUE (repeatable; TextLineCfg's names, MIN_LINE_WIDTH for TEXT_PROPOSALS_WIDTH *
     MIN_NUM_PROPOSALS) sets the connector's thresholds for the batches and for the images that take the single-image path.
@@ -136,7 +140,7 @@ def plan_ragged_batches(shapes, max_batch, waste=RAGGED_WASTE):
 PNG_LAYOUT, OTHER_LAYOUT = (-1, 0), (0, 0)      # plan_device_jobs: layouts of the files the JPEG decoder does not take
 
 
-def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE, ragged_png=False):
+def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE, ragged_png=False, ragged_pack="host"):
     """The batches of the device path (_run_gpu). entries: [(name, file (h, w), layout, resize_im factor, resized (h, w))] of the images that
     take the batched path; layout = (components, sampling | orientation) of a JPEG file the library takes, PNG_LAYOUT, or OTHER_LAYOUT
     (Pillow). -> jobs = [(size, kind, f, rs, names)]. A pure function.
@@ -146,14 +150,18 @@ def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE, ragged_pn
     layout and orientation: kind 'ragged', size = rs = the canvas (hc, wc), f = [(file h, file w, factor)] per name
     (Context.decode_jpeg_ragged). What ends alone there, and every PNG and Pillow file, is size-grouped as without it.
     ragged_png: the PNG files are planned the same way into jobs of a kind of their own, 'ragged-png' (size, f, rs as for 'ragged'): their
-    canvas is built on the host (PNG files are decoded there) and written by ctpn_write_annotated_png_files_ragged."""
+    canvas is built on the host (PNG files are decoded there) and written by ctpn_write_annotated_png_files_ragged.
+    ragged_pack='gpu' (with ragged): the PNG files are planned that way whether ragged_png is given or not, into jobs of kind
+    'ragged-png-gpu' (size, f, rs as for 'ragged'): their canvas is built on the device (Context.decode_png_ragged). 'host' (default): the
+    jobs are what they are without the argument."""
     entries = list(entries)
     jobs = []
-    if ragged_png:
+    pack_gpu = ragged and ragged_pack == "gpu"
+    if ragged_png or pack_gpu:
         pngs = [e for e in entries if tuple(e[2]) == PNG_LAYOUT and e[4][0] >= 16]
         batches, _ = plan_ragged_batches([e[4] for e in pngs], batch, waste)
         for (hc, wc), members in batches:
-            jobs.append(((hc, wc), "ragged-png", [(pngs[i][1][0], pngs[i][1][1], pngs[i][3]) for i in members], (hc, wc), [pngs[i][0] for i in members]))
+            jobs.append(((hc, wc), "ragged-png-gpu" if pack_gpu else "ragged-png", [(pngs[i][1][0], pngs[i][1][1], pngs[i][3]) for i in members], (hc, wc), [pngs[i][0] for i in members]))
         batched = {pngs[i][0] for _, members in batches for i in members}
         entries = [e for e in entries if e[0] not in batched]
     if ragged:
@@ -173,14 +181,20 @@ def plan_device_jobs(entries, batch, ragged=False, waste=RAGGED_WASTE, ragged_pn
 
 
 def check_ragged_options(decode="host", encode="host", png_encode="host", crops_dir=None, decode_procs=0, decode_pool=None, ragged_outputs=False, ragged=True,
-                         ragged_png=False):
+                         ragged_png=False, ragged_pack="host"):
     """run(..., ragged=True) with these options: ValueError for the combinations that stay uniform. The process-pool decoder fills
     shared-memory batches of one shape; the library's writers (encode / png_encode = 'gpu') and the crops take uniform device batches.
     ragged_outputs: the JPEG writer and the crops take the ragged batches of the device path as well (ctpn_write_annotated_files_ragged,
     ctpn_crop_lines_ragged, ctpn_write_line_crops_ragged) -- it needs ragged and decode='gpu' / 'gpu-entropy'; encode and crops_dir then
     pass, png_encode='gpu' stays refused unless ragged_png is given.
     ragged_png: the PNG files share ragged batches too and the PNG writer takes their canvases (ctpn_write_annotated_png_files_ragged) --
-    it needs ragged, ragged_outputs and png_encode='gpu'; png_encode='gpu' then passes."""
+    it needs ragged, ragged_outputs and png_encode='gpu'; png_encode='gpu' then passes.
+    ragged_pack: 'gpu' -- the canvases of the ragged PNG batches are built on the device (ctpn_decode_png_files_ragged); it needs ragged and
+    decode='gpu' / 'gpu-entropy' and is tied to no output option: what takes a device canvas takes these. 'host' (default): no change."""
+    if ragged_pack not in ("host", "gpu"):
+        raise ValueError("ragged_pack must be 'host' or 'gpu'")
+    if ragged_pack == "gpu" and not (ragged and decode in ("gpu", "gpu-entropy")):
+        raise ValueError("ragged_pack='gpu' builds the canvases of ragged PNG batches on the device: it needs ragged=True and decode='gpu' or 'gpu-entropy'")
     if ragged_png and not (ragged and ragged_outputs and png_encode == "gpu"):
         raise ValueError("ragged_png writes the PNG files of ragged batches on the device: it needs ragged=True, ragged_outputs=True and png_encode='gpu'")
     if ragged_outputs and not ragged:
@@ -353,7 +367,7 @@ def write_crops(ctx, crops_dir, names, recs, crop_h=32, max_w=512, images=None, 
 
 def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8, encode="host", crops_dir=None, crop_h=32, params=None, entropy="host",
              encode_entropy="host", png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False, crops_format="jpg",
-             ragged_png=False):
+             ragged_png=False, ragged_pack="host"):
     """decode='gpu': the JPEG files of the run are decoded AND resized on the device (ctpn_decode_jpeg_batch: Huffman decoding on the ctx's
     C++ worker pool, IDCT / chroma upsampling / colour conversion / cv2.resize as HIP kernels in the ctx's copy queue, ordered against the
     forward by events) -- neither the file bytes nor the pixels pass through Python, and the pixels never exist on the host unless
@@ -389,7 +403,12 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     crops_format (--crops-format, with crops_dir): 'png' -- the crops are <stem>_<k>.png files (write_crops).
     ragged_png (--ragged-png, with ragged, ragged_outputs and png_encode='gpu'): the PNG files are batched by their resized shapes as well
     (plan_device_jobs, kind 'ragged-png'); a batch's canvas is built on the host, where PNG files are decoded, submitted with its heights,
-    and its annotated images are written from it at collect time (ctpn_write_annotated_png_files_ragged). Same names, same pixels."""
+    and its annotated images are written from it at collect time (ctpn_write_annotated_png_files_ragged). Same names, same pixels.
+    ragged_pack='gpu' (--ragged-pack gpu, with ragged): the PNG files are batched by their resized shapes whether ragged_png is given or not
+    (kind 'ragged-png-gpu'), and a batch's canvas is built on the device: the files are decoded by the library's pool into page-locked
+    memory and one kernel resizes them into the canvas (ctpn_decode_png_files_ragged). The canvas is detected, written (png_encode='gpu'
+    with ragged_png) and cropped (crops_dir with ragged_outputs) where it lies, and fetched for the host writer otherwise. A batch the
+    library's PNG decoder does not take falls back to the host canvas. Same result files."""
     from ctpn_amd._binding import resize_dims
     mode = mode or cfg.TEST.DETECT_MODE
     os.makedirs(out_dir, exist_ok=True)
@@ -413,7 +432,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             entries.append((name, (h, w), layout, f, rs))
         else:
             singles.append(name)
-    jobs = plan_device_jobs(entries, batch, ragged, ragged_waste, ragged_png=ragged_png)
+    jobs = plan_device_jobs(entries, batch, ragged, ragged_waste, ragged_png=ragged_png, ragged_pack=ragged_pack)
     if jobs:
         net.ensure_capacity(max(len(j[4]) for j in jobs), max(j[3][0] for j in jobs), max(j[3][1] for j in jobs))
         _set_tail_params(net, params)
@@ -421,7 +440,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
     png_batches = {}                                   # slot -> (device pointer or None, host images or None, shape, scale) of a batch whose PNG files the library writes
     dev_batches = {}                                   # slot -> (device pointer, shape, scale) of a batch whose images the library writes
     crop_src = {}                                      # slot -> what the batch's crops are cut from: device pointer + shape, or host images; heights of a ragged canvas
-    rag_png_batches = {}                               # slot -> (host canvas, heights, scales) of a ragged PNG batch whose images the library writes
+    rag_png_batches = {}                               # slot -> (device pointer or None, host canvas or None, shape, heights, scales) of a ragged PNG batch whose images the library writes
     rag_batches = {}                                   # slot -> (device pointer or None, host canvas or None, shape, heights, scales) of a ragged batch whose images the library writes
     # PNG batches are decoded ONE JOB AHEAD on a helper thread (the C++ decode threads hang off that call; ctypes releases the GIL), so that
     # batch k + 1 inflates while batch k is submitted and batch k - 1 collected. Three batch buffers per shape in a ring: when batch k + 1
@@ -478,8 +497,8 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                                                  paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members], entropy=encode_entropy)
             stats["enc_gpu"] += len(members)
         if slot in rag_png_batches:                    # ... and into PNG files (ctpn_write_annotated_png_files_ragged)
-            host_canvas, hts, scs = rag_png_batches.pop(slot)
-            net.ctx.write_annotated_png_files_ragged(images=host_canvas, heights=hts, recs=[results[nm] for nm in members], scales=scs,
+            ptr, host_canvas, shape, hts, scs = rag_png_batches.pop(slot)
+            net.ctx.write_annotated_png_files_ragged(images=host_canvas, device_ptr=ptr, shape=shape, heights=hts, recs=[results[nm] for nm in members], scales=scs,
                                                      paths=[os.path.join(out_dir, os.path.basename(nm)) for nm in members])
             stats["enc_gpu"] += len(members)
             stats["enc_png"] += len(members)
@@ -530,6 +549,23 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
                 if ragged_outputs and write_images and encode == "gpu" and all(_is_jpeg(nm) for nm in members):      # the host canvas through the same call
                     rag_batches[k & 1] = (None, canvas, canvas.shape[:3], heights, scales)
                 rag_crops = (None, None, canvas, heights)
+        if kind == "ragged-png-gpu":                   # the same shape of job over PNG files, the canvas built on the device (ragged_pack='gpu')
+            sizes, scales = [t[:2] for t in f], [t[2] for t in f]
+            try:
+                (ptr, shape), heights = net.ctx.decode_png_ragged(members, sizes, scales, h, w)
+                net.ctx.detect_submit(device_ptr=ptr, shape=shape, heights=heights, slot=k & 1)
+                stats["png"] += len(members)
+                if write_images and png_encode == "gpu":      # (live until the second-next decode or pack: collected one from now; not fetched)
+                    rag_png_batches[k & 1] = (ptr, None, shape, heights, scales)
+                elif write_images:
+                    canvas = net.ctx.jpeg_batch_fetch(ptr, shape)
+                    imgs = [canvas[i, :heights[i]] for i in range(len(members))]
+                rag_crops = (ptr, shape, None, heights)
+            except B.CtpnError as e:                                       # e.g. a 16-bit file: the same canvas from the host decoder
+                if e.code not in (B.CTPN_ERR_UNSUPPORTED, -1):
+                    raise
+                rag_png_batches.pop(k & 1, None)
+                kind = "ragged-png"
         if kind == "ragged-png":                       # the same shape of job over PNG files: the canvas is built on the host (ragged_png)
             scales = [t[2] for t in f]
             imgs = [_load(nm)[0] for nm in members]
@@ -537,7 +573,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
             net.ctx.detect_submit(images=canvas, heights=heights, slot=k & 1)
             stats["host"] += len(members)
             if write_images and png_encode == "gpu":
-                rag_png_batches[k & 1] = (canvas, heights, scales)
+                rag_png_batches[k & 1] = (None, canvas, canvas.shape[:3], heights, scales)
             rag_crops = (None, None, canvas, heights)
         if kind == "jpg":
             try:
@@ -618,7 +654,7 @@ def _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=8
 
 def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, decode_threads=8, decode_procs=0, decode_pool=None, decode="host",
         encode="host", crops_dir=None, crop_h=32, params=None, png_encode="host", ragged=False, ragged_waste=RAGGED_WASTE, crops_encode="host", ragged_outputs=False,
-        crops_format="jpg", ragged_png=False):
+        crops_format="jpg", ragged_png=False, ragged_pack="host"):
     """-> {image name: (M,9) records}. decode_procs > 0 (or a warm decode_pool): decode in worker processes writing into shared-memory batch
     buffers (one batch ahead of the GPU) instead of on the thread pool. decode='gpu': JPEG decode + resize_im on the device (_run_gpu).
     encode='gpu' (needs decode='gpu'): the annotated JPEG images of device-decoded batches are written by the library
@@ -645,7 +681,11 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
     (crops_encode='gpu': ctpn_write_line_crops_png, and ..._png_ragged for ragged batches); with crops_encode='gpu-entropy': ValueError.
     ragged_png (off by default; needs ragged, ragged_outputs and png_encode='gpu', else ValueError before any work): png_encode='gpu' then
     combines with ragged -- the PNG files share ragged batches and the library writes their annotated images from the canvases
-    (ctpn_write_annotated_png_files_ragged). Same names, same decoded pixels as without it."""
+    (ctpn_write_annotated_png_files_ragged). Same names, same decoded pixels as without it.
+    ragged_pack ('host' by default: nothing changes; 'gpu' needs ragged and decode='gpu' / 'gpu-entropy', else ValueError before any work): the
+    PNG files the library takes share ragged batches whose canvases are built on the device (Context.decode_png_ragged; see _run_gpu),
+    with any output option that takes a device canvas. Same result files. Measured on a folder of PNG files of 16 sizes: 2.5 x the size-grouped
+    path, 13.8 x the host canvas (tools/canvas_pack_throughput.py, profiles/canvas_pack_throughput.json)."""
     from concurrent.futures import ThreadPoolExecutor
     _check_uint8_feed_config(params)
     if params:
@@ -674,14 +714,15 @@ def run(net, names, out_dir, batch=32, mode=None, write_images=True, log=print, 
         raise ValueError("crops_format must be 'jpg' or 'png'")
     if crops_format == "png" and crops_encode == "gpu-entropy":
         raise ValueError("crops_format='png' has no crops_encode='gpu-entropy' form: the PNG writer's codes are built on the host")
-    if ragged or ragged_outputs or ragged_png:
-        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool, ragged_outputs=ragged_outputs, ragged=ragged, ragged_png=ragged_png)
+    if ragged or ragged_outputs or ragged_png or ragged_pack != "host":
+        check_ragged_options(decode, encode, png_encode, crops_dir, decode_procs, decode_pool, ragged_outputs=ragged_outputs, ragged=ragged, ragged_png=ragged_png,
+                             ragged_pack=ragged_pack)
     if decode == "gpu":
         if crops_dir is not None:
             os.makedirs(crops_dir, exist_ok=True)
         return _run_gpu(net, names, out_dir, batch, mode, write_images, log, read_threads=decode_threads, encode=encode, crops_dir=crops_dir, crop_h=crop_h, params=params,
                         entropy=entropy, encode_entropy=encode_entropy, png_encode=png_encode, ragged=ragged, ragged_waste=ragged_waste, crops_encode=crops_encode,
-                        ragged_outputs=ragged_outputs, crops_format=crops_format, ragged_png=ragged_png)
+                        ragged_outputs=ragged_outputs, crops_format=crops_format, ragged_png=ragged_png, ragged_pack=ragged_pack)
     if decode_procs > 0 or decode_pool is not None:
         return _run_procs(net, names, out_dir, batch, mode, write_images, log, decode_procs, decode_pool, params=params)
     mode = mode or cfg.TEST.DETECT_MODE
@@ -852,6 +893,9 @@ def build_parser():
     ap.add_argument('--ragged-png', action='store_true',
                     help="with --ragged --ragged-outputs --png-encode gpu: the PNG files share ragged batches too and are written from their "
                          "canvases (ctpn_write_annotated_png_files_ragged); same names, same pixels")
+    ap.add_argument('--ragged-pack', default='host', choices=['host', 'gpu'],
+                    help="with --ragged and --decode gpu / gpu-entropy: 'gpu' = the PNG files share ragged batches whose canvases are built on the "
+                         "device (ctpn_decode_png_files_ragged); 'host' (default) = as without the switch. Same result files")
     ap.add_argument('--ragged-waste', type=float, default=RAGGED_WASTE, help="padded share of a ragged batch's rows at most")
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
@@ -884,7 +928,7 @@ def main(argv=None):
     run(net, names, args.out, batch=args.batch, mode=args.mode, write_images=not args.no_images, decode_threads=args.decode_threads,
         decode_procs=args.decode_procs, decode=args.decode, encode=args.encode, png_encode=args.png_encode, crops_dir=args.crops, crop_h=args.crop_height, crops_encode=args.crops_encode,
         params=dict(rpn_params_from_cfg(), **parse_connector_args(args.connector)), ragged=args.ragged, ragged_waste=args.ragged_waste,
-        ragged_outputs=args.ragged_outputs, crops_format=args.crops_format, ragged_png=args.ragged_png)
+        ragged_outputs=args.ragged_outputs, crops_format=args.crops_format, ragged_png=args.ragged_png, ragged_pack=args.ragged_pack)
     net.close()
 
 

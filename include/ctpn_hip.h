@@ -405,6 +405,26 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
 int ctpn_debug_conv3x3_plan(int precision, int n, int h, int w_first, int w_count, int ci, int co, int fuse_pool, int keep_full, int dup_hi,
                             int conv_p64, int split_edge, int cu_count, int* plans);
 const char* ctpn_debug_conv3x3_form_name(int kind, int id);
+/* The tile walk of the layer's main launch (csrc/conv3x3_plan.h c3_walk: the struct the persistent and the weights-in-registers launchers
+ * copy into their kernel argument, so what this reports is the launch). Arguments as ctpn_debug_conv3x3_plan; out: w_count x
+ * CTPN_CONV_WALK_INTS ints per width. p = a persistent form (p64, p_flat, p_flat64, p_16x16, p_8x32, p_8x32_half), wr = the
+ * weights-in-registers kernel; a form without a walk (t64, t_*) reports [1] .. [11], [13] as 0.
+ *   [0] main form (as above)   [1] tiles_x   [2] tiles_y (per image; stacked: of the whole bordered batch; flat windows: 0)
+ *   [3] tiles_n: channel slices   [4] stacked (p, 2D patches without a pool: tile rows run over the bordered batch)
+ *   [5] work items of whole tiles (p: pixel tiles x tiles_n; wr: pixel tiles, walked by every slice)
+ *   [6] workers (p: the grid; wr: workgroups per group and channel slice)
+ *   [7] ht_full: items [0, ht_full) are whole tiles   [8] ht_r: the tiles behind them run as two halves each (p forms that split, [13])
+ *   [9] groups (wr: tile ranges, one per XCD)   [10] per_group (wr: tiles per range; the last may be shorter or empty)
+ *   [11] workgroups of the launch   [12] 128-byte K chunks per tap (p: window refills per tile)   [13] 1 = the form splits tail tiles
+ * ctpn_debug_conv3x3_walk: ctpn_debug_conv3x3 through the product kernels (impl 1, 3) with the main launch planned and walked as on a device of
+ * cu_count CUs (1 .. the device's own, else CTPN_ERR_ARG; 0 = the device's). Both output maps and 64 guard rows behind each hold 0xC3 bytes
+ * before the launch; a border pixel or guard row that changed is CTPN_ERR_STATE naming image and bordered row. At most 2^22 bordered pixels.
+ * No product caller passes a CU count: this hook and ctpn_debug_conv1_fused_walk are the only ones. */
+#define CTPN_CONV_WALK_INTS 14
+int ctpn_debug_conv3x3_walk_plan(int precision, int n, int h, int w_first, int w_count, int ci, int co, int fuse_pool, int keep_full, int dup_hi,
+                                 int conv_p64, int split_edge, int cu_count, int* out);
+int ctpn_debug_conv3x3_walk(int device_id, const float* in_nhwc, const float* w_hwio, const float* bias, int n, int h, int w,
+                            int ci, int co, int precision, int impl, int fuse_pool, int cu_count, float* out_full, float* out_pool);
 /* The kernels behind the conv stack, one at a time on caller data (test hooks; null stream, buffers allocated and freed inside). Every output
  * buffer is followed by 64 guard rows and pre-filled with one byte value; a guard byte that changed is CTPN_ERR_STATE.
  *
@@ -490,6 +510,9 @@ int ctpn_debug_conv1(int device_id, const void* image, int image_is_f32, int byt
                      int precision, int form, float* out, uint16_t* out_bits, uint16_t* q_out);
 int ctpn_debug_conv1_fused(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio,
                            const float* bias2, int n, int h, int w, int precision, float* out_pool, uint16_t* out_bits);
+/* ... with conv1_2's launch laid out for cu_count CUs (as ctpn_debug_conv3x3_walk; 0 = the device's own: ctpn_debug_conv1_fused) */
+int ctpn_debug_conv1_fused_walk(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio,
+                                const float* bias2, int n, int h, int w, int precision, int cu_count, float* out_pool, uint16_t* out_bits);
 /* TextDetector.detect (lib/text_connector/detectors.py:19-49) for ONE image with every step on the device -- score > 0.7 prefix and
  * boxes / scale (lines_prep_kernel), NMS 0.2 (nms_kernel), graph build / chains / line fit / filter_boxes (connect_kernel) -- i.e.
  * the device-connector form of the asynchronous detect path (option connect_device = 1). rois: r x 5 fp32 [score,x1,y1,x2,y2] in

@@ -114,6 +114,9 @@ def _declare(lib):
                                          C.c_int, f32p, f32p]),
         "ctpn_debug_conv3x3_plan": (C.c_int, [C.c_int] * 13 + [i32p]),
         "ctpn_debug_conv3x3_form_name": (C.c_char_p, [C.c_int, C.c_int]),
+        "ctpn_debug_conv3x3_walk_plan": (C.c_int, [C.c_int] * 13 + [i32p]),
+        "ctpn_debug_conv3x3_walk": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, f32p, f32p]),
         "ctpn_debug_lstm_pre_plan": (C.c_int, [C.c_longlong, C.c_int, i32p]),
         "ctpn_debug_forward_sets": (C.c_int, [vp, C.POINTER(C.c_longlong)]),
         "ctpn_debug_live_resources": (C.c_int, [C.POINTER(C.c_longlong)]),
@@ -127,6 +130,8 @@ def _declare(lib):
         "ctpn_debug_conv1": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
                                        C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
         "ctpn_debug_conv1_fused": (C.c_int, [C.c_int, u8p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_uint16)]),
+        "ctpn_debug_conv1_fused_walk": (C.c_int, [C.c_int, u8p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
+                                                  C.POINTER(C.c_uint16)]),
         "ctpn_jpeg_probe": (C.c_int, [u8p, C.c_size_t, i32p, i32p, i32p, i32p]),
         "ctpn_jpeg_coef_capacity": (C.c_size_t, [C.c_int, C.c_int]),
         "ctpn_jpeg_entropy_decode": (C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int16), C.c_size_t, C.POINTER(C.c_uint16), i32p]),
@@ -815,6 +820,41 @@ def conv3x3_plan(precision, n, h, w, ci, co, pool, keep_full=True, dup_hi=False,
     return ConvPlan(mains[p[0]], strips[p[1]], p[2], p[3], p[4], p[5])
 
 
+CONV_WALK_INTS = 14     # CTPN_CONV_WALK_INTS
+ConvWalk = collections.namedtuple("ConvWalk", "main tiles_x tiles_y tiles_n stacked total workers ht_full ht_r groups per_group grid chunks ht")
+
+
+def conv3x3_walk_sweep(precision, n, h, w_first, w_count, ci, co, pool, keep_full=True, dup_hi=False, conv_p64=1, split_edge=1, cu_count=0):
+    """ctpn_debug_conv3x3_walk_plan: int32 array [w_count, CONV_WALK_INTS] -- the tile walks of the main launch for the widths w_first ..
+    w_first + w_count - 1 (the fields of ConvWalk; main as an id). cu_count 0 asks the current device; any other value needs no device."""
+    lib = load_library()
+    out = np.zeros((int(w_count), CONV_WALK_INTS), np.int32)
+    _check(lib.ctpn_debug_conv3x3_walk_plan(precision_code(precision), int(n), int(h), int(w_first), int(w_count), int(ci), int(co), 1 if pool else 0,
+                                            1 if keep_full else 0, 1 if dup_hi else 0, int(conv_p64), int(split_edge), int(cu_count), _ptr(out, C.c_int)))
+    return out
+
+
+def conv3x3_walk_plan(precision, n, h, w, ci, co, pool, keep_full=True, dup_hi=False, conv_p64=1, split_edge=1, cu_count=0):
+    """The tile walk of one layer shape's main launch as a ConvWalk (main: the form's name)."""
+    p = [int(v) for v in conv3x3_walk_sweep(precision, n, h, w, 1, ci, co, pool, keep_full, dup_hi, conv_p64, split_edge, cu_count)[0]]
+    return ConvWalk(conv3x3_form_names()[0][p[0]], *p[1:])
+
+
+def debug_conv3x3_walk(x, w_hwio, bias, precision="fp32", fuse_pool=False, want_full=True, cu_count=0, device_id=0, dup_hi=False):
+    """ctpn_debug_conv3x3_walk: debug_conv3x3 through the product kernels with the main launch laid out for cu_count CUs (0: the device's own)
+    and guarded output maps (a written border pixel or guard row raises CtpnError, CTPN_ERR_STATE). Returns (full or None, pooled or None)."""
+    lib = load_library()
+    x = _f32(x); w_hwio = _f32(w_hwio); bias = _f32(bias)
+    n, h, w, ci = x.shape
+    co = w_hwio.shape[3]
+    full = np.zeros((n, h, w, co), np.float32) if want_full else None
+    pooled = np.zeros((n, h // 2, w // 2, co), np.float32) if fuse_pool else None
+    _check(lib.ctpn_debug_conv3x3_walk(int(device_id), _ptr(x, C.c_float), _ptr(w_hwio, C.c_float), _ptr(bias, C.c_float), n, h, w, ci,
+                                       co, precision_code(precision), 3 if dup_hi else 1, 1 if fuse_pool else 0, int(cu_count),
+                                       _ptr(full, C.c_float) if want_full else None, _ptr(pooled, C.c_float) if fuse_pool else None))
+    return full, pooled
+
+
 LstmPrePlan = collections.namedtuple("LstmPrePlan", "form waves workgroups idle_waves")
 LSTM_PRE_FORMS = ("small", "lds")
 BILSTM_FORMS = ("exact", "exact_fast_gates", "split_16", "split_few")
@@ -889,8 +929,9 @@ def debug_conv1(images, w_hwio, bias, precision="bf16", form=0, byte_offset=0, w
     return out, bits, q
 
 
-def debug_conv1_fused(images, w_hwio, bias, w2_hwio, bias2, precision="bf16", byte_offset=0, device_id=0):
+def debug_conv1_fused(images, w_hwio, bias, w2_hwio, bias2, precision="bf16", byte_offset=0, device_id=0, cu_count=None):
     """ctpn_debug_conv1_fused: uint8 images -> q-image -> conv1_2 with conv1_1 in its window stage and the pool fused.
+    cu_count (not None: ctpn_debug_conv1_fused_walk): conv1_2's launch laid out for that many CUs, 0 = the device's own.
     Returns (pool1 (n, h // 2, w // 2, 64) fp32, its stored 16-bit values as uint16)."""
     images = np.ascontiguousarray(images, dtype=np.uint8)
     w_hwio = _f32(w_hwio); bias = _f32(bias); w2_hwio = _f32(w2_hwio); bias2 = _f32(bias2)
@@ -898,9 +939,12 @@ def debug_conv1_fused(images, w_hwio, bias, w2_hwio, bias2, precision="bf16", by
     assert c == 3 and w_hwio.shape == (3, 3, 3, 64) and bias.shape == (64,) and w2_hwio.shape == (3, 3, 64, 64) and bias2.shape == (64,)
     out = np.zeros((n, h // 2, w // 2, 64), np.float32)
     bits = np.zeros((n, h // 2, w // 2, 64), np.uint16)
-    _check(load_library().ctpn_debug_conv1_fused(int(device_id), _ptr(images, C.c_uint8), int(byte_offset), _ptr(w_hwio, C.c_float), _ptr(bias, C.c_float),
-                                                 _ptr(w2_hwio, C.c_float), _ptr(bias2, C.c_float), n, h, w, precision_code(precision), _ptr(out, C.c_float),
-                                                 _ptr(bits, C.c_uint16)))
+    head = (int(device_id), _ptr(images, C.c_uint8), int(byte_offset), _ptr(w_hwio, C.c_float), _ptr(bias, C.c_float), _ptr(w2_hwio, C.c_float),
+            _ptr(bias2, C.c_float), n, h, w, precision_code(precision))
+    if cu_count is None:
+        _check(load_library().ctpn_debug_conv1_fused(*head, _ptr(out, C.c_float), _ptr(bits, C.c_uint16)))
+    else:
+        _check(load_library().ctpn_debug_conv1_fused_walk(*head, int(cu_count), _ptr(out, C.c_float), _ptr(bits, C.c_uint16)))
     return out, bits
 
 

@@ -4,6 +4,15 @@
 #include "ctx.h"
 #include "conv3x3_plan.h"
 
+namespace {
+// Guarded output buffers (the recurrent tail's, the first layer's and the conv walk's hooks): followed by DBG_GUARD_ROWS guard rows and filled
+// with DBG_FILL bytes before the launch; dbg_map_bytes / dbg_fetch_map (below, with the first layer's hooks) size and check a bordered map
+constexpr int DBG_GUARD_ROWS = 64;
+constexpr int DBG_FILL = 0xC3;
+size_t dbg_map_bytes(int n, int H, int W, size_t pix);
+int dbg_fetch_map(const void* d_map, int n, int H, int W, size_t pix, std::vector<char>& host, const char* who);
+}  // namespace
+
 extern "C" {
 
 // ---- diagnostics ---------------------------------------------------------------------------------------------
@@ -42,8 +51,13 @@ int ctpn_debug_lds_dma(int device_id, const uint8_t* src, size_t bytes, uint8_t*
   return CTPN_OK;
 }
 
-int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio, const float* bias, int n, int h, int w, int ci,
-                       int co, int precision, int impl, int fuse_pool, float* out_full, float* out_pool) {
+}  // extern "C"
+namespace {
+// ctpn_debug_conv3x3 (guard = false: zeroed outputs, the interior fetched) and ctpn_debug_conv3x3_walk (guard = true: both output maps and
+// DBG_GUARD_ROWS rows behind each hold DBG_FILL before the launch, and every border pixel and guard row must still hold it afterwards;
+// cu_count: launch_conv3x3's)
+int dbg_conv3x3_body(int device_id, const float* in_nhwc, const float* w_hwio, const float* bias, int n, int h, int w, int ci,
+                     int co, int precision, int impl, int fuse_pool, float* out_full, float* out_pool, bool guard, int cu_count) {
   if (!in_nhwc || !w_hwio || !bias) return fail(CTPN_ERR_ARG, "null pointer");
   if (precision < CTPN_PREC_FP32 || precision > CTPN_PREC_SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3: unknown precision");
   if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_conv3x3: no HIP device visible (no CPU fallback)");
@@ -78,13 +92,16 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
   const size_t wt_bytes = (size_t)co_pad * 9 * ci * (split ? 6 : es);
   DevBuf b_in, b_out, b_pool, b_wt, b_w, b_b;
   int rc;
-  if ((rc = b_in.alloc(in_front + in_elems * es)) || (rc = b_out.alloc(out_elems * es)) || (rc = b_pool.alloc(pool_elems * es + 256)) || (rc = b_wt.alloc(wt_bytes)) ||
+  const size_t pix_out = (size_t)(cout_p + (dup ? co : 0)) * es, pix_pool = (size_t)cout_p * es;
+  const size_t out_bytes = guard ? dbg_map_bytes(n, h, w, pix_out) : out_elems * es, pool_bytes = guard ? dbg_map_bytes(n, ho, wo, pix_pool) : pool_elems * es + 256;
+  const char* const who = guard ? "ctpn_debug_conv3x3_walk" : "ctpn_debug_conv3x3";
+  if ((rc = b_in.alloc(in_front + in_elems * es)) || (rc = b_out.alloc(out_bytes)) || (rc = b_pool.alloc(pool_bytes)) || (rc = b_wt.alloc(wt_bytes)) ||
       (rc = b_w.alloc((size_t)9 * ci * co * 4)) || (rc = b_b.alloc((size_t)co_pad * 4))) return rc;
   CTPN_HIP_TRY(hipMemset(b_in.get(), 0, in_front));
   void *d_in = b_in.as<char>() + in_front, *d_out = b_out.get(), *d_pool = b_pool.get(), *d_wt = b_wt.get();
   float *d_w = b_w.as<float>(), *d_b = b_b.as<float>();
-  CTPN_HIP_TRY(hipMemset(d_out, 0, out_elems * es));
-  CTPN_HIP_TRY(hipMemset(d_pool, 0, pool_elems * es + 256));
+  CTPN_HIP_TRY(hipMemset(d_out, guard ? DBG_FILL : 0, out_bytes));
+  CTPN_HIP_TRY(hipMemset(d_pool, guard ? DBG_FILL : 0, pool_bytes));
   CTPN_HIP_TRY(hipMemset(d_wt, 0, wt_bytes));
   CTPN_HIP_TRY(hipMemset(d_b, 0, (size_t)co_pad * 4));
   CTPN_HIP_TRY(hipMemcpy(d_in, hin.data(), in_elems * es, hipMemcpyHostToDevice));
@@ -94,7 +111,8 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
   bool host_pool = false;
   if (!rc) {
     if (impl == 1) {
-      rc = launch_conv3x3(d_in, d_wt, d_b, (out_full || !fuse_pool) ? d_out : nullptr, fuse_pool ? d_pool : nullptr, t, n, h, w, ci, co, 1, s, dup);
+      rc = launch_conv3x3(d_in, d_wt, d_b, (out_full || !fuse_pool) ? d_out : nullptr, fuse_pool ? d_pool : nullptr, t, n, h, w, ci, co, 1, s, dup,
+                          nullptr, nullptr, 3, cu_count);
     } else {
       // impl 0: the im2col GEMM (igemm.hip) as an independent reference of the same layer; its pool is taken on the host from the stored map
       IGemm g{};
@@ -108,8 +126,13 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
   auto fetch = [&](void* dsrc, int H2, int W2, float* dst, int dup_plane) -> int {
     const int pitch = cout_p + (dup_plane ? co : 0);
     const size_t elems = (size_t)n * (H2 + 2) * (W2 + 2) * pitch;
-    std::vector<char> tmp(elems * es);
-    CTPN_HIP_TRY(hipMemcpy(tmp.data(), dsrc, elems * es, hipMemcpyDeviceToHost));
+    std::vector<char> tmp;
+    if (guard) {
+      if (const int frc = dbg_fetch_map(dsrc, n, H2, W2, (size_t)pitch * es, tmp, who)) return frc;
+    } else {
+      tmp.resize(elems * es);
+      CTPN_HIP_TRY(hipMemcpy(tmp.data(), dsrc, elems * es, hipMemcpyDeviceToHost));
+    }
     for (int in = 0; in < n; ++in) for (int y = 0; y < H2; ++y) for (int x = 0; x < W2; ++x) for (int c = 0; c < co; ++c) {
       const size_t o = (((size_t)in * (H2 + 2) + y + 1) * (W2 + 2) + x + 1) * pitch + c;
       float v;
@@ -120,7 +143,7 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
         else {
           v = host_bf16_to_f32(b);
           if (split) { uint16_t l; std::memcpy(&l, &tmp[(o + co) * 2], 2); v += host_bf16_to_f32(l); }
-          if (dup_plane && std::memcmp(&tmp[(o + 2 * co) * 2], &b, 2) != 0) return fail(CTPN_ERR_STATE, "ctpn_debug_conv3x3: the dup_hi plane differs from the hi plane");
+          if (dup_plane && std::memcmp(&tmp[(o + 2 * co) * 2], &b, 2) != 0) return fail(CTPN_ERR_STATE, std::string(who) + ": the dup_hi plane differs from the hi plane");
         }
       }
       dst[(((size_t)in * H2 + y) * W2 + x) * co + c] = v;
@@ -139,7 +162,32 @@ int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio,
       }
   }
   if (!rc && out_pool && fuse_pool && !host_pool) rc = fetch(d_pool, ho, wo, out_pool, 0);
+  if (!rc && guard) {
+    // a map the caller did not ask for (or the launch does not store) has borders and guard rows all the same
+    std::vector<char> host;
+    if (!out_full) rc = dbg_fetch_map(d_out, n, h, w, pix_out, host, who);
+    if (!rc && !(out_pool && fuse_pool)) rc = dbg_fetch_map(d_pool, n, ho, wo, pix_pool, host, who);
+  }
   return rc;
+}
+}  // namespace
+extern "C" {
+
+int ctpn_debug_conv3x3(int device_id, const float* in_nhwc, const float* w_hwio, const float* bias, int n, int h, int w, int ci,
+                       int co, int precision, int impl, int fuse_pool, float* out_full, float* out_pool) {
+  return dbg_conv3x3_body(device_id, in_nhwc, w_hwio, bias, n, h, w, ci, co, precision, impl, fuse_pool, out_full, out_pool, false, 0);
+}
+
+// ctpn_debug_conv3x3 through the product kernels (impl 1, 3) with the main launch's plan and tile walk laid out for cu_count CUs (1 .. the
+// device's own; 0 = the device's), and with guarded outputs: a store into a border pixel of the full or the pooled map, or behind either, is
+// CTPN_ERR_STATE naming the image and the bordered row.
+int ctpn_debug_conv3x3_walk(int device_id, const float* in_nhwc, const float* w_hwio, const float* bias, int n, int h, int w, int ci,
+                            int co, int precision, int impl, int fuse_pool, int cu_count, float* out_full, float* out_pool) {
+  if (impl != 1 && impl != 3) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk: impl is 1 (the product kernels) or 3 (1 with the dup_hi layout)");
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk: cu_count is 1 .. the device's CU count, or 0 for the device's");
+  if (!out_full && !out_pool) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk: no output");
+  if (n <= 0 || h <= 0 || w <= 0 || (long long)n * (h + 2) * (w + 2) > (1 << 22)) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk: n, h, w positive, at most 2^22 bordered pixels");
+  return dbg_conv3x3_body(device_id, in_nhwc, w_hwio, bias, n, h, w, ci, co, precision, impl, fuse_pool, out_full, out_pool, true, cu_count);
 }
 
 // The plan of launch_conv3x3 (conv3x3_plan.h) for the widths w_first .. w_first + w_count - 1 of one layer: what ctpn_debug_conv3x3 and the
@@ -174,8 +222,6 @@ const char* ctpn_debug_conv3x3_form_name(int kind, int id) { return kind == 0 ? 
 // behind its last row, or into the pad columns of a row, changes a byte that the hook then finds changed (CTPN_ERR_STATE).
 }  // extern "C"
 namespace {
-constexpr int DBG_GUARD_ROWS = 64;
-constexpr int DBG_FILL = 0xC3;
 bool dbg_fill_intact(const char* p, size_t n) {
   for (size_t i = 0; i < n; ++i) if ((unsigned char)p[i] != DBG_FILL) return false;
   return true;
@@ -590,8 +636,11 @@ int ctpn_debug_conv1(int device_id, const void* image, int image_is_f32, int byt
   return CTPN_OK;
 }
 
-int ctpn_debug_conv1_fused(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio, const float* bias2,
-                           int n, int h, int w, int precision, float* out_pool, uint16_t* out_bits) {
+}  // extern "C"
+namespace {
+// ctpn_debug_conv1_fused (cu_count 0) and ctpn_debug_conv1_fused_walk (conv1_2's launch laid out for cu_count CUs: launch_conv3x3's argument)
+int dbg_conv1_fused_body(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio, const float* bias2,
+                         int n, int h, int w, int precision, int cu_count, float* out_pool, uint16_t* out_bits) {
   if (!image || !w_hwio || !bias || !w2_hwio || !bias2 || !out_pool) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: null pointer");
   if (precision != CTPN_PREC_BF16 && precision != CTPN_PREC_FP16) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: the fused form is bf16 or fp16");
   if (byte_offset < 0 || byte_offset > 3) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused: byte_offset is 0 .. 3");
@@ -617,11 +666,57 @@ int ctpn_debug_conv1_fused(int device_id, const uint8_t* image, int byte_offset,
   CTPN_HIP_TRY(hipDeviceSynchronize());
   // the production chain of api_forward.hip: bytes -> q-image, conv1_1 inside conv1_2's window stage (conv1_1's map is never stored: no `in`)
   if ((rc = launch_pack_transpose((const float*)d_w2, 64, d_wt2, 9 * 64, t, 9 * 64, 64, nullptr)) || (rc = launch_image_to_q((const uint8_t*)d_img, d_q, t, n, h, w, nullptr)) ||
-      (rc = launch_conv3x3(nullptr, d_wt2, (const float*)d_b2, nullptr, d_pool, t, n, h, w, 64, 64, 1, nullptr, 0, d_q, conv1_p_frags(d_frags, t)))) return rc;
+      (rc = launch_conv3x3(nullptr, d_wt2, (const float*)d_b2, nullptr, d_pool, t, n, h, w, 64, 64, 1, nullptr, 0, d_q, conv1_p_frags(d_frags, t), 3, cu_count))) return rc;
   if (hipDeviceSynchronize() != hipSuccess) return fail(CTPN_ERR_HIP, "ctpn_debug_conv1_fused: kernel failed");
   std::vector<char> host;
   if ((rc = dbg_fetch_map(d_pool, n, ho, wo, pix, host, "ctpn_debug_conv1_fused"))) return rc;
   dbg_unpack_map(host, t, n, ho, wo, out_pool, out_bits);
+  return CTPN_OK;
+}
+}  // namespace
+extern "C" {
+
+int ctpn_debug_conv1_fused(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio, const float* bias2,
+                           int n, int h, int w, int precision, float* out_pool, uint16_t* out_bits) {
+  return dbg_conv1_fused_body(device_id, image, byte_offset, w_hwio, bias, w2_hwio, bias2, n, h, w, precision, 0, out_pool, out_bits);
+}
+
+int ctpn_debug_conv1_fused_walk(int device_id, const uint8_t* image, int byte_offset, const float* w_hwio, const float* bias, const float* w2_hwio, const float* bias2,
+                                int n, int h, int w, int precision, int cu_count, float* out_pool, uint16_t* out_bits) {
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv1_fused_walk: cu_count is 1 .. the device's CU count, or 0 for the device's");
+  return dbg_conv1_fused_body(device_id, image, byte_offset, w_hwio, bias, w2_hwio, bias2, n, h, w, precision, cu_count, out_pool, out_bits);
+}
+
+// The tile walk of the main launch of one conv3x3 layer (c3_walk, conv3x3_plan.h: what c3_launch_p / c3_launch_wr copy into the kernel
+// argument) for the widths w_first .. w_first + w_count - 1; arguments as ctpn_debug_conv3x3_plan. Host arithmetic only.
+int ctpn_debug_conv3x3_walk_plan(int precision, int n, int h, int w_first, int w_count, int ci, int co, int fuse_pool, int keep_full, int dup_hi,
+                                 int conv_p64, int split_edge, int cu_count, int* out) {
+  if (!out || w_count <= 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: no output");
+  if (precision < CTPN_PREC_FP32 || precision > CTPN_PREC_SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: unknown precision");
+  const DType t = prec_dtype(precision);
+  if (n <= 0 || h <= 0 || w_first <= 0 || w_first > 0x7fffffff - w_count || ci <= 0 || ci % (t == DType::F32 ? 32 : 64) != 0 || co <= 0 || co % (t == DType::F32 ? 4 : 8) != 0)
+    return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: shape out of range (Ci a multiple of 32 / 64, Co of 4 / 8)");
+  if (dup_hi && t != DType::SPLIT) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: dup_hi is a split-precision layout");
+  if (cu_count < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: cu_count is a CU count, or 0 for the current device's");
+  if (cu_count == 0) {
+    if (ctpn_device_count() <= 0) return fail(CTPN_ERR_NODEVICE, "ctpn_debug_conv3x3_walk_plan: cu_count 0 asks the current device, and no HIP device is visible");
+    int dev = 0, rc;
+    if ((rc = current_device(dev)) || (rc = device_cu_count(dev, cu_count))) return rc;
+  }
+  const bool pool = fuse_pool != 0, keep = keep_full != 0 || !pool;
+  for (int i = 0; i < w_count; ++i) {
+    const int w = w_first + i;
+    const C3Plan p = c3_plan(t, n, h, w, ci, co, pool, keep, dup_hi, true, true, (conv_p64 ? 1 : 0) | (split_edge ? 2 : 0), cu_count);
+    if (p.main_form == C3M_NONE) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: no kernel for this shape (split precision: Co <= 64 or a multiple of 128)");
+    const C3Walk k = c3_walk(p.main_form, n, h, w, co, pool, keep, p.w_cover, cu_count);
+    if (k.ptiles_total > 0x7fffffffLL || k.grid > 0x7fffffffLL) return fail(CTPN_ERR_ARG, "ctpn_debug_conv3x3_walk_plan: more than 2^31 - 1 tiles");
+    int* o = out + (size_t)i * CTPN_CONV_WALK_INTS;
+    o[0] = k.main_form; o[1] = k.tiles_x; o[2] = k.tiles_y; o[3] = k.tiles_n; o[4] = k.stacked; o[5] = (int)k.ptiles_total; o[6] = (int)k.workers;
+    o[7] = (int)k.ht_full; o[8] = k.ht_r; o[9] = k.groups; o[10] = k.per_group; o[11] = (int)k.grid;
+    // 128-byte K chunks per tap = window refills per tile of the persistent kernel (split precision: three K blocks, hi / lo / hi)
+    o[12] = (t == DType::SPLIT ? 3 * ci : ci) / (t == DType::F32 ? 32 : 64);
+    o[13] = k.ht;
+  }
   return CTPN_OK;
 }
 

@@ -181,7 +181,9 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
                    const void* q1_frags = nullptr, int split_opts = 3 /* split precision. Bit 0 (option conv_p64): Co = 64 through the persistent kernel's 64-channel form
                                                                       instead of the non-persistent kernel; bit 1 (option split_edge): ragged tile columns through the edge
                                                                       kernel instead of a padded tile column. Every precision, bit 2: a forked strip
-                                                                      runs behind the main launch on s instead (two forwards overlapping freely) */);
+                                                                      runs behind the main launch on s instead (two forwards overlapping freely) */,
+                   int cu_count = 0 /* test launches only (ctpn_debug_conv3x3_walk): plan and walk as on a device of this many CUs, 1 .. the device's own.
+                                       0 = ask the device, which is what every product caller passes */);
 bool conv1_fusable(DType t, int n, int h, int w, int ci, int co, bool pool, bool keep_full);
 // mfma_frags != nullptr: conv1_1 on the matrix cores with split-bf16 operands (pack_conv1_frags; fp32-class sums; SPLIT stores
 // [hi(64) | lo(64)] per pixel); nullptr: the VALU kernel. (The uint8 feed of the 16-bit modes goes through the q-image instead, below.)

@@ -74,8 +74,10 @@ bool conv1_fusable(DType t, int n, int h, int w, int ci, int co, bool pool, bool
 // (pack_transpose_split); dup_hi: the output pixel is [hi | lo | hi] (the layer that feeds the LSTM input-projection GEMM).
 // q1 / q1_frags (conv1_2 of the 16-bit modes, uint8 feed, production path): conv1_1 is computed inside the launch's window stage from the
 // batch's q-image (conv3x3_wr_kernel FUSE); `in` (conv1_1's map) is not touched
+// cu_count (test launches, ctpn_debug_conv3x3_walk): the plan and the walk of the main launch as on a device of that many CUs, 1 .. the device's
+// own; 0 = the device's, what every product caller passes. The strips do not depend on it.
 int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out, void* pool_out, DType t, int n, int h, int w,
-                   int ci, int co, int relu, hipStream_t s, int dup_hi, const void* q1, const void* q1_frags, int split_opts) {
+                   int ci, int co, int relu, hipStream_t s, int dup_hi, const void* q1, const void* q1_frags, int split_opts, int cu_count) {
   const int bke = (t == DType::F32) ? 32 : 64;
   if (ci <= 0 || ci % bke != 0) return fail(CTPN_ERR_ARG, "conv3x3: Ci must be a multiple of the 128-byte strip");
   const int epc = (t == DType::F32) ? 4 : 8;
@@ -96,6 +98,8 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
   const bool split = t == DType::SPLIT;
   int dev = 0, ncu = 0, rc;
   if ((rc = current_device(dev)) || (rc = device_cu_count(dev, ncu))) return rc;
+  if (cu_count < 0 || cu_count > ncu) return fail(CTPN_ERR_ARG, "conv3x3: cu_count is 1 .. the device's CU count, or 0 for the device's");
+  if (cu_count) ncu = cu_count;
   const C3Plan plan = c3_plan(t, n, h, w, ci, co, pool, out != nullptr, dup_hi, relu != 0, bias != nullptr, split_opts, ncu);
   if (plan.main_form == C3M_NONE) return fail(CTPN_ERR_ARG, "conv3x3 (split precision): Co must be <= 64 or a multiple of 128, with ReLU");
   const bool strip = plan.strip != C3S_NONE, edge = plan.strip == C3S_EDGE, edge_pool = plan.strip == C3S_EDGE_POOL;
@@ -151,10 +155,10 @@ int launch_conv3x3(const void* in, const void* wt, const float* bias, void* out,
     CTPN_HIP_TRY(hipEventRecord(ev_join[dev], sstream[dev]));
   }
   switch (t) {
-    case DType::F32: rc = c3_run_f32(g, pool, plan.main_form, s); break;
-    case DType::BF16: rc = c3_run_bf16(g, pool, plan.main_form, s); break;
-    case DType::F16: rc = c3_run_f16(g, pool, plan.main_form, s); break;
-    default: rc = c3_run_split(g, pool, plan.main_form, s); break;
+    case DType::F32: rc = c3_run_f32(g, pool, plan.main_form, s, ncu); break;
+    case DType::BF16: rc = c3_run_bf16(g, pool, plan.main_form, s, ncu); break;
+    case DType::F16: rc = c3_run_f16(g, pool, plan.main_form, s, ncu); break;
+    default: rc = c3_run_split(g, pool, plan.main_form, s, ncu); break;
   }
   if (rc) return rc;
   if (instream) { if ((rc = run_strip(s))) return rc; }

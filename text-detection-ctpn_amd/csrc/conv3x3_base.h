@@ -180,11 +180,11 @@ __device__ __forceinline__ int c3_tw16_col(int l31) { return (l31 & 16) ? ((l31 
 static inline void c3_extent(const Conv3& g, bool pool, int& he, int& we) { c3_extent_of(g.H, g.W, pool, g.out != nullptr, g.w_cover, he, we); }
 
 // ---- per-type entry points: one translation unit each (conv3x3_<type>.hip), called by launch_conv3x3 (conv3x3.hip) ----
-// (form: the plan's main_form, C3Main; ks: the plan's edge_ks)
-int c3_run_f32(const Conv3& g, bool pool, int form, hipStream_t s);          // exact-fp32 MFMA kernels
-int c3_run_bf16(const Conv3& g, bool pool, int form, hipStream_t s);         // C3M_WR: the weights-in-registers kernel (Ci = 64)
-int c3_run_f16(const Conv3& g, bool pool, int form, hipStream_t s);
-int c3_run_split(const Conv3& g, bool pool, int form, hipStream_t s);        // (hi, lo) bf16 planes, three MFMA terms
+// (form: the plan's main_form, C3Main; ks: the plan's edge_ks; ncu: the CU count the plan was made for -- the walk, c3_walk, takes the same)
+int c3_run_f32(const Conv3& g, bool pool, int form, hipStream_t s, int ncu);          // exact-fp32 MFMA kernels
+int c3_run_bf16(const Conv3& g, bool pool, int form, hipStream_t s, int ncu);         // C3M_WR: the weights-in-registers kernel (Ci = 64)
+int c3_run_f16(const Conv3& g, bool pool, int form, hipStream_t s, int ncu);
+int c3_run_split(const Conv3& g, bool pool, int form, hipStream_t s, int ncu);        // (hi, lo) bf16 planes, three MFMA terms
 int c3_edge_bf16(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep);
 int c3_edge_f16(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep);
 int c3_edge_split(const void* in, const void* wt, const float* bias, void* out, int n, int h, int w, int ci, int co, int relu, int r, bool pooled, hipStream_t s, bool deep, int dup_hi, int ks);

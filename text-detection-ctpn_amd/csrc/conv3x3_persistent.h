@@ -631,62 +631,32 @@ __global__ __launch_bounds__(512) void conv3x3_p_kernel(Conv3 g) {
 }
 
 template <typename T, bool FLAT, bool POOL, int TW, bool SPLIT = false, int BN_T = 128, int BM_T = 256, bool HT32 = false>
-static int c3_launch_p(Conv3 g, hipStream_t s) {
+static int c3_launch_p(Conv3 g, hipStream_t s, const C3Walk& wk) {
   constexpr int BN = BN_T;
   constexpr int BMF = BM_T;                    // pixels per flat-window tile (256; 64: the one-image form)
+  constexpr bool HTF = ((FLAT || TW == 16) && BMF == 256) || HT32;      // the kernel's HT
+  // the walk (tiles, stacked tile rows, the grid, the half-tile tail: c3_walk, conv3x3_plan.h) was laid out for this instantiation
+  if (wk.flat != (FLAT ? 1 : 0) || wk.tw != TW || wk.bn != BN || wk.bm != BMF || wk.ht != (HTF ? 1 : 0))
+    return fail(CTPN_ERR_STATE, "conv3x3: the walk was planned for another form of the persistent kernel");
   const int Wp = g.W + 2;
   const int rows = FLAT ? (BMF + 2 * Wp + 2) : (C3_BM / TW + 2) * (TW + 2);
   g.a_rows = (rows + 7) & ~7;
   constexpr int AG_MAX = FLAT ? ((BMF == 64 ? 37 : 61) + 7) / 8 : (43 + 7) / 8;
   if ((g.a_rows >> 3) > AG_MAX * 8) return fail(CTPN_ERR_ARG, "conv3x3: input window does not fit the staging plan");
-  g.tiles_n = (g.Co + BN - 1) / BN;
-  long long ptiles;
-  if (FLAT) {
-    g.m_total = (long long)g.N * (g.H + 2) * Wp;
-    ptiles = (g.m_total + BMF - 1) / BMF;
-  } else {
-    int he, we;
-    c3_extent(g, POOL, he, we);
-    g.tiles_x = (we + TW - 1) / TW;
-    g.tiles_y = (he + C3_BM / TW - 1) / (C3_BM / TW);
-    ptiles = (long long)g.N * g.tiles_x * g.tiles_y;
-    // Stacked tile rows (no fused pool): the bordered NHWC batch is ONE tall image of N (H + 2) rows -- image i's bottom border row is
-    // followed by image i + 1's top border row, which is exactly the zero halo both need -- so tile rows can run over the batch's
-    // N (H + 2) - 2 rows instead of restarting per image: 75-row maps in 16-row patches pay 80 rows per image, stacked 2462 rows pay 2464
-    // (conv4_1 / conv4_2: 1078 instead of 1120 tiles). Border rows that fall inside a tile are computed and not stored (the output's
-    // borders must stay zero).
-    g.stacked = 0;
-    if constexpr (!POOL) {
-      const int th = C3_BM / TW;
-      const long long ty_st = ((long long)g.N * (g.H + 2) - 2 + th - 1) / th;
-      if (g.H >= 16 && g.N > 1 && ty_st < (long long)g.N * g.tiles_y && ty_st * g.tiles_x < 0x7fffffffLL) {
-        g.stacked = 1;
-        g.tiles_y = (int)ty_st;
-        ptiles = (long long)g.tiles_x * g.tiles_y;
-      }
-    }
-  }
-  g.ptiles_total = ptiles * g.tiles_n;
+  g.tiles_n = wk.tiles_n;
+  if (FLAT) g.m_total = wk.m_total;
+  else { g.tiles_x = wk.tiles_x; g.tiles_y = wk.tiles_y; g.stacked = wk.stacked; }
+  g.ptiles_total = wk.ptiles_total;
 #ifdef CTPN_ABLATION
   { static const int abl = [] { const char* e = std::getenv("CTPN_C3_P_ABL"); return e ? std::atoi(e) : 0; }(); g.abl = abl; }
 #endif
   if (g.ptiles_total <= 0 || (long long)g.N * (g.H + 2) * Wp > 0x7fffffffLL) return fail(CTPN_ERR_ARG, "conv3x3: problem out of range");
   const int lds = 2 * g.a_rows * 128 + 3 * BN * 128 + g.tiles_n * BN * 4;
   if (lds > C3_LDS_MAX) return fail(CTPN_ERR_ARG, "conv3x3: LDS budget exceeded");
-  int dev = 0, ncu = 0, rc;
-  if ((rc = current_device(dev)) || (rc = device_cu_count(dev, ncu))) return rc;
-  long long workers = g.ptiles_total < ncu ? g.ptiles_total : ncu;
-  // half-tile tail (kernel comment): the r tiles of a last partial round as 2 r halves; a launch with at most half as many tiles as CUs
-  // (small batches: conv5_x of ONE 600 x 900 image is 36 tiles) is split into halves altogether -- a half runs one wave per SIMD and takes
-  // 0.59 of a tile's time. Same K order per output either way: results do not depend on the split.
-  g.ht_full = g.ptiles_total; g.ht_r = 0;
-  if constexpr (((FLAT || TW == 16) && BMF == 256) || HT32) {
-    if (2 * g.ptiles_total <= ncu) { g.ht_full = 0; g.ht_r = (int)g.ptiles_total; workers = 2 * g.ptiles_total; }
-    else {
-      const long long r = g.ptiles_total % workers;
-      if (r > 0 && 2 * r <= workers) { g.ht_r = (int)r; g.ht_full = g.ptiles_total - r; }
-    }
-  }
+  int dev = 0, rc;
+  if ((rc = current_device(dev))) return rc;
+  const long long workers = wk.workers;
+  g.ht_full = wk.ht_full; g.ht_r = wk.ht_r;
   // Every form of the kernel reads its fragments one k-slice group ahead of the MFMAs through a second register set, with no LDS read in
   // flight across a barrier. History: round 3 had kept a plain loop for 16 x 16 patches and flat windows (+-0 / +1 % there) -- but it was only
   // as fast as it was because hipcc let the last k-slice group's reads straddle the barrier, which is a write-after-read race against the

@@ -170,4 +170,103 @@ static inline C3Plan c3_plan(DType t, int n, int h, int w, int ci, int co, bool 
   return p;
 }
 
+// c3_walk: how the main launch of a persistent form (conv3x3_p_kernel) or of the weights-in-registers kernel (conv3x3_wr_kernel) walks its
+// tiles, again as a function of the shape and the CU count alone. c3_dispatch / c3_launch_wr compute it and the launchers copy it into the
+// kernel argument, so what ctpn_debug_conv3x3_walk_plan reports IS the launch. tests/conv_walks.py enumerates the situations of the walk.
+struct C3Walk {
+  int main_form;            // C3Main; a form without a walk (t64, t_*) leaves everything below zero
+  // the kernel instantiation the form names (c3_launch_p checks them against its template arguments)
+  int flat, tw, bn, bm, ht; // flat windows / patch width / channels and pixels of one tile / does the form split its tail tiles into halves
+  int tiles_x, tiles_y;     // 2D patches: tile columns; tile rows per image (stacked: of the whole bordered batch). wr: per image
+  int tiles_n;              // channel slices (p: of bn channels; wr: of 64)
+  int stacked;              // p, 2D patches without a fused pool: tile rows run over the bordered rows of the whole batch
+  long long m_total;        // p, flat windows: bordered pixels of the batch
+  long long ptiles;         // pixel tiles
+  long long ptiles_total;   // p: work items of whole tiles = ptiles x tiles_n. wr: = ptiles (every slice walks all of them)
+  long long workers;        // p: the grid. wr: workgroups per group and channel slice
+  long long grid;           // workgroups of the launch
+  long long ht_full;        // p: tiles [0, ht_full) are walked whole ...
+  int ht_r;                 // ... and the ht_r tiles behind them as two halves each (0: no halves)
+  int groups, per_group;    // wr: tile ranges (one per XCD) and tiles per range; the last range may be shorter, or empty
+};
+
+// the instantiation of conv3x3_p_kernel behind a main form (c3_dispatch's table): false for a form the persistent kernel does not serve
+static inline bool c3_walk_p_shape(int form, C3Walk& k) {
+  k.flat = 0; k.tw = 32; k.bn = 128; k.bm = C3_BM; k.ht = 0;
+  switch (form) {
+    case C3M_P64: k.bn = 64; return true;
+    case C3M_P_FLAT: k.flat = 1; k.ht = 1; return true;
+    case C3M_P_FLAT64: k.flat = 1; k.bm = 64; return true;
+    case C3M_P_16X16: k.tw = 16; k.ht = 1; return true;
+    case C3M_P_8X32: return true;
+    case C3M_P_8X32_HALF: k.ht = 1; return true;
+    default: return false;
+  }
+}
+
+// n, h, w, co: the layer (split precision: its channel count, not the planes'). keep_full: the full-resolution map is stored.
+// w_cover: the plan's (columns of the main launch; 0 = all). ncu: the CU count the launch is laid out for (> 0).
+static inline C3Walk c3_walk(int form, int n, int h, int w, int co, bool pool, bool keep_full, int w_cover, int ncu) {
+  C3Walk k{};
+  k.main_form = form;
+  int he, we;
+  c3_extent_of(h, w, pool, keep_full, w_cover, he, we);
+  if (form == C3M_WR) {
+    k.tw = 32; k.bn = 64; k.bm = C3_BM;
+    k.tiles_x = (we + 31) / 32;
+    k.tiles_y = (he + 7) / 8;
+    k.tiles_n = co / 64;
+    k.ptiles = (long long)n * k.tiles_x * k.tiles_y;
+    k.ptiles_total = k.ptiles;
+    k.groups = 8;                                                      // one tile range per XCD (kernel comment)
+    const long long per_group = (k.ptiles + k.groups - 1) / k.groups;
+    k.per_group = (int)(per_group < 0x7fffffffLL ? per_group : 0x7fffffffLL);
+    long long workers = k.tiles_n > 0 ? (ncu / k.tiles_n) / (long long)k.groups : 0;      // per group and channel slice
+    if (workers < 1) workers = 1;
+    if (workers > per_group) workers = per_group;
+    k.workers = workers;
+    k.grid = workers * k.groups * k.tiles_n;
+    return k;
+  }
+  if (!c3_walk_p_shape(form, k)) { k.tw = k.bn = k.bm = 0; return k; }
+  k.tiles_n = (co + k.bn - 1) / k.bn;
+  if (k.flat) {
+    k.m_total = (long long)n * (h + 2) * (w + 2);
+    k.ptiles = (k.m_total + k.bm - 1) / k.bm;
+  } else {
+    const int th = C3_BM / k.tw;
+    k.tiles_x = (we + k.tw - 1) / k.tw;
+    k.tiles_y = (he + th - 1) / th;
+    k.ptiles = (long long)n * k.tiles_x * k.tiles_y;
+    // Stacked tile rows (no fused pool): the bordered NHWC batch is ONE tall image of N (H + 2) rows -- image i's bottom border row is
+    // followed by image i + 1's top border row, which is exactly the zero halo both need -- so tile rows can run over the batch's
+    // N (H + 2) - 2 rows instead of restarting per image: 75-row maps in 16-row patches pay 80 rows per image, stacked 2462 rows pay 2464
+    // (conv4_1 / conv4_2: 1078 instead of 1120 tiles). Border rows that fall inside a tile are computed and not stored (the output's
+    // borders must stay zero).
+    if (!pool) {
+      const long long ty_st = ((long long)n * (h + 2) - 2 + th - 1) / th;
+      if (h >= 16 && n > 1 && ty_st < (long long)n * k.tiles_y && ty_st * k.tiles_x < 0x7fffffffLL) {
+        k.stacked = 1;
+        k.tiles_y = (int)ty_st;
+        k.ptiles = (long long)k.tiles_x * k.tiles_y;
+      }
+    }
+  }
+  k.ptiles_total = k.ptiles * k.tiles_n;
+  k.workers = k.ptiles_total < ncu ? k.ptiles_total : ncu;
+  // half-tile tail (kernel comment): the r tiles of a last partial round as 2 r halves; a launch with at most half as many tiles as CUs
+  // (small batches: conv5_x of ONE 600 x 900 image is 36 tiles) is split into halves altogether -- a half runs one wave per SIMD and takes
+  // 0.59 of a tile's time. Same K order per output either way: results do not depend on the split.
+  k.ht_full = k.ptiles_total; k.ht_r = 0;
+  if (k.ht && k.ptiles_total > 0) {
+    if (2 * k.ptiles_total <= ncu) { k.ht_full = 0; k.ht_r = (int)k.ptiles_total; k.workers = 2 * k.ptiles_total; }
+    else {
+      const long long r = k.ptiles_total % k.workers;
+      if (r > 0 && 2 * r <= k.workers) { k.ht_r = (int)r; k.ht_full = k.ptiles_total - r; }
+    }
+  }
+  k.grid = k.workers;
+  return k;
+}
+
 }  // namespace ctpn

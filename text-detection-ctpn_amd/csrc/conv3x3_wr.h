@@ -764,30 +764,27 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wr_kernel(Conv3WR g) {
 int c3_wr_resources(int dev, hipStream_t s, char** dump, unsigned** claim);
 
 template <typename H>
-static int c3_launch_wr(const Conv3& c, bool pool, hipStream_t s) {
+static int c3_launch_wr(const Conv3& c, bool pool, hipStream_t s, int ncu) {
   Conv3WR g{};
   g.in = c.in; g.wt = c.wt; g.bias = c.bias; g.out = c.out; g.pool_out = c.pool_out;
   g.N = c.N; g.H = c.H; g.W = c.W; g.Co = c.Co;
-  int he, we;
-  c3_extent(c, pool, he, we);
-  g.tiles_x = (we + 31) / 32;
-  g.tiles_y = (he + 7) / 8;
-  g.tiles_n = c.Co / 64;
-  const long long ptiles = (long long)c.N * g.tiles_x * g.tiles_y;
+  // tiles, the eight per-XCD tile ranges and the workers of each: c3_walk (conv3x3_plan.h), for ncu CUs (the device's, or a test launch's)
+  const C3Walk wk = c3_walk(C3M_WR, c.N, c.H, c.W, c.Co, pool, c.out != nullptr, c.w_cover, ncu);
+  g.tiles_x = wk.tiles_x;
+  g.tiles_y = wk.tiles_y;
+  g.tiles_n = wk.tiles_n;
+  const long long ptiles = wk.ptiles;
   const long long per_img = (long long)g.tiles_x * g.tiles_y;
   if (ptiles <= 0 || ptiles * per_img >= (1LL << 32) || (long long)c.N * (c.H + 2) * (c.W + 2) * 128 >= (1LL << 40))
     return fail(CTPN_ERR_ARG, "conv3x3_wr: problem out of range");
   g.ptiles = (unsigned)ptiles;
   g.magic_img = (unsigned)((1ULL << 32) / (unsigned long long)per_img + 1ULL);
   g.magic_row = (unsigned)((1ULL << 32) / (unsigned long long)g.tiles_x + 1ULL);
-  int dev = 0, ncu = 0, rc;
-  if ((rc = current_device(dev)) || (rc = device_cu_count(dev, ncu))) return rc;
-  g.groups = 8u;                                                     // one tile range per XCD (kernel comment)
-  g.per_group = (unsigned)((ptiles + g.groups - 1) / g.groups);
-  long long workers = (ncu / g.tiles_n) / (long long)g.groups;      // per group and channel slice
-  if (workers < 1) workers = 1;
-  if (workers > (long long)g.per_group) workers = g.per_group;
-  workers *= g.groups;                                              // per channel slice
+  int dev = 0, rc;
+  if ((rc = current_device(dev))) return rc;
+  g.groups = (unsigned)wk.groups;
+  g.per_group = (unsigned)wk.per_group;
+  const long long workers = wk.workers * wk.groups;                  // per channel slice
   if (workers * g.tiles_n > 1024) return fail(CTPN_ERR_ARG, "conv3x3_wr: more workgroups than dump pages");
   if (g.tiles_n > 4) return fail(CTPN_ERR_ARG, "conv3x3_wr: more channel slices than claim counters per slot");
   if ((rc = c3_wr_resources(dev, s, &g.dump, &g.claim))) return rc;

@@ -534,7 +534,10 @@ int ctpn_debug_text_lines(ctpn_ctx* ctx, const float* rois, const int* roi_count
 /* ---- cv2.imread for JPEG files (reference ctpn/demo.py:59), split where the work splits: marker parsing and Huffman decoding on the host
  * (the ctx's worker pool, one image per thread), dequantisation + inverse DCT + chroma upsampling + YCbCr -> BGR on the device. The pixel
  * arithmetic is libjpeg's integer arithmetic (islow IDCT, h2v2 / h2v1 / h1v2 "fancy" upsampling, 16-bit fixed-point colour conversion): the
- * images equal what cv2 / Pillow (libjpeg-turbo) return, bit for bit. Supported: 8-bit Huffman-coded files, sequential (SOF0 / SOF1) and
+ * images equal what cv2 / Pillow (libjpeg-turbo) return, bit for bit. The IDCT restates libjpeg-turbo's x86 SIMD islow code (16-bit lanes:
+ * coef x q keeps its low 16 bits, four sums per pass wrap, each pass saturates to int16, a block whose rows 1 .. 7 are zero takes row 0 << 2
+ * wrapped), which equals jidctint.c on every coefficient an encoder writes from 8-bit pixels and is the pin beyond that (scaled or 16-bit
+ * tables, hand-made coefficients); a libjpeg-turbo running WITHOUT SIMD follows jidctint.c's masked range-limit table there and differs. Supported: 8-bit Huffman-coded files, sequential (SOF0 / SOF1) and
  * progressive (SOF2: it differs in the host half only), 1 component or YCbCr 4:4:4 / 4:4:0 / 4:2:2 / 4:2:0, restart intervals, and the
  * eight EXIF orientations, applied the way cv2.imread applies them (an index map in the colour kernel: every size below is the TURNED
  * image's) -- i.e. every JPEG file of the reference's own data/demo. Anything else (CMYK, 4:1:1, arithmetic coding, 12-bit, three components

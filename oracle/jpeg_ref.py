@@ -7,8 +7,12 @@ with the same defaults (JDCT_ISLOW, do_fancy_upsampling = TRUE), and is the pin:
 for bit on every case and against tests/golden/jpeg_cases.npz (files + Pillow's decode, written by oracle/make_jpeg_golden.py), so
 "parity with the reference's imread" is anchored on libjpeg-turbo's output of the same files.
 
-The algorithm restated is the published libjpeg one (IJG libjpeg 6b, files named per function below; libjpeg-turbo's SIMD paths are
-bit-exact with that C code for well-formed streams):
+The algorithm restated is the published libjpeg one (IJG libjpeg 6b, files named per function below). libjpeg-turbo's SIMD paths are
+bit-exact with that C code on every coefficient an encoder writes from 8-bit pixels; beyond that range (quantisation tables scaled up,
+16-bit tables, hand-made coefficients) the x86 SIMD islow IDCT's 16-bit lanes show, and since that code is what Pillow and cv2 run, its
+picture is the pin: idct_islow restates it (from the published algorithm of libjpeg-turbo's simd/x86_64/jidctint-sse2.asm / -avx2.asm and
+from black-box comparison with the Pillow installed here; nothing of the reference tree), idct_islow_fullwidth keeps the C arithmetic in
+full-width integers, which is what this file and the device computed before:
     jdmarker.c   marker parsing (SOI, DQT, DHT, SOF0/1/2, DRI, SOS)
     jdhuff.c     sequential Huffman entropy decoding, DC prediction, restart intervals
     jdphuff.c    progressive Huffman entropy decoding: DC / AC, first / refinement scans (spectral selection, successive approximation)
@@ -382,6 +386,7 @@ _F = dict(F298=2446, F390=3196, F541=4433, F765=6270, F899=7373, F1175=9633, F15
 
 
 def _idct_1d(x, descale):
+    """One 1-D pass of jidctint.c in full-width integers (no wrap anywhere)."""
     F = _F
     z2, z3 = x[..., 2], x[..., 6]
     z1 = (z2 + z3) * F["F541"]
@@ -400,19 +405,76 @@ def _idct_1d(x, descale):
                      (tmp13 - t0 + r) >> descale, (tmp12 - t1 + r) >> descale, (tmp11 - t2 + r) >> descale, (tmp10 - t3 + r) >> descale], -1)
 
 
-def idct_islow(coef):
-    """(..., 64) dequantised coefficients, natural order -> (..., 8, 8) uint8 samples. jpeg_idct_islow: pass 1 over columns (descale by
-    CONST_BITS - PASS1_BITS), pass 2 over rows (descale by CONST_BITS + PASS1_BITS + 3), + 128, range limit."""
+def idct_islow_fullwidth(coef):
+    """(..., 64) dequantised coefficients, natural order -> (..., 8, 8) uint8 samples. jidctint.c's jpeg_idct_islow in full-width integers
+    with a clamp to 0 .. 255 in place of its range-limit table: pass 1 over columns (descale by CONST_BITS - PASS1_BITS), pass 2 over rows
+    (descale by CONST_BITS + PASS1_BITS + 3), + 128. What the device computed before it took idct_islow's arithmetic; kept because on every
+    coefficient an encoder can write from 8-bit pixels the two agree, and the tests of the out-of-range cases (tests/jpeg_beyond_cases.py)
+    assert that each of them tells the two apart."""
     c = np.asarray(coef).reshape(np.shape(coef)[:-1] + (8, 8)).astype(np.int64)
     ws = np.swapaxes(_idct_1d(np.swapaxes(c, -1, -2), 13 - 2), -1, -2)
     return np.clip(_idct_1d(ws, 13 + 2 + 3) + 128, 0, 255).astype(np.uint8)
 
 
-def component_planes(blocks, qts):
-    """[(bh, bw, 64) quantised blocks], [(64,) quantisation table per component] -> [(8 bh, 8 bw) uint8 plane per component]."""
+def _w16(v):
+    """the low 16 bits as a signed value (a 16-bit SIMD lane: pmullw, paddw, psubw, psllw)"""
+    return ((np.asarray(v, np.int64) + 32768) & 0xFFFF) - 32768
+
+
+def _w32(v):
+    """the low 32 bits as a signed value (a 32-bit SIMD lane: pmaddwd, paddd, psubd)"""
+    return ((np.asarray(v, np.int64) + (1 << 31)) & 0xFFFFFFFF) - (1 << 31)
+
+
+def _idct_1d_simd(x, descale):
+    """One 1-D pass of the x86 SIMD islow IDCT (libjpeg-turbo, simd/x86_64/jidctint-sse2.asm / -avx2.asm) on eight 16-bit lanes x[..., k].
+    Four sums are 16-bit lanes and wrap: in0 + in4 and in0 - in4 (then widened by << 13), in7 + in3 and in5 + in1. Everything else is a
+    pair of 16 x 16 products summed in a 32-bit lane (pmaddwd with the constants folded pairwise: the values of jidctint.c's factoring,
+    mod 2^32). Each output is (sum + rounding) >> descale, arithmetic, then packed with signed saturation to int16 (packssdw)."""
+    F = _F
+    z2, z3 = x[..., 2], x[..., 6]
+    tmp3 = _w32(z2 * (F["F541"] + F["F765"]) + z3 * F["F541"])
+    tmp2 = _w32(z2 * F["F541"] + z3 * (F["F541"] - F["F1847"]))
+    tmp0, tmp1 = _w16(x[..., 0] + x[..., 4]) << 13, _w16(x[..., 0] - x[..., 4]) << 13
+    tmp10, tmp13, tmp11, tmp12 = tmp0 + tmp3, tmp0 - tmp3, tmp1 + tmp2, tmp1 - tmp2
+    t0, t1, t2, t3 = x[..., 7], x[..., 5], x[..., 3], x[..., 1]
+    z3, z4 = _w16(t0 + t2), _w16(t1 + t3)
+    z3, z4 = _w32(z3 * (F["F1175"] - F["F1961"]) + z4 * F["F1175"]), _w32(z3 * F["F1175"] + z4 * (F["F1175"] - F["F390"]))
+    o0 = _w32(t0 * (F["F298"] - F["F899"]) - t3 * F["F899"]) + z3
+    o1 = _w32(t1 * (F["F2053"] - F["F2562"]) - t2 * F["F2562"]) + z4
+    o2 = _w32(-t1 * F["F2562"] + t2 * (F["F3072"] - F["F2562"])) + z3
+    o3 = _w32(-t0 * F["F899"] + t3 * (F["F1501"] - F["F899"])) + z4
+    r = 1 << (descale - 1)
+    out = [tmp10 + o3, tmp11 + o2, tmp12 + o1, tmp13 + o0, tmp13 - o0, tmp12 - o1, tmp11 - o2, tmp10 - o3]
+    return np.stack([np.clip(_w32(_w32(v) + r) >> descale, -32768, 32767) for v in out], -1)
+
+
+def idct_islow(quant, q):
+    """(..., 64) QUANTISED coefficients and their (64,) table, natural order -> (..., 8, 8) uint8 samples: the islow IDCT as libjpeg-turbo's
+    x86 SIMD code computes it (jsimd_idct_islow_sse2 / _avx2; the published algorithm, restated from its description and pinned by
+    black-box comparison with Pillow's decode -- tests/test_jpeg.py), which is what Pillow and cv2 return on x86-64. Inside the range an
+    8-bit encoder can reach it equals jidctint.c (idct_islow_fullwidth); beyond it the 16-bit lanes show:
+      dequantisation  coef * q keeps its low 16 bits, signed (pmullw);
+      pass 1          _idct_1d_simd over columns, descale CONST_BITS - PASS1_BITS, saturated to int16 -- unless rows 1 .. 7 of the block's
+                      QUANTISED coefficients are all zero: then every row of the workspace is row 0 << PASS1_BITS, wrapped to 16 bits and
+                      not saturated (the whole-block shortcut; jidctint.c's per-column shortcut is not taken);
+      pass 2          _idct_1d_simd over rows, descale CONST_BITS + PASS1_BITS + 3, saturated to -128 .. 127 (packsswb), + 128.
+    A build of libjpeg-turbo that runs without SIMD follows jidctint.c and its masked range-limit table instead and differs out of range."""
+    quant = np.asarray(quant).astype(np.int64)
+    c = _w16(quant * np.asarray(q).astype(np.int64)).reshape(quant.shape[:-1] + (8, 8))
+    ws = np.swapaxes(_idct_1d_simd(np.swapaxes(c, -1, -2), 13 - 2), -1, -2)
+    flat = ~np.any(quant.reshape(quant.shape[:-1] + (8, 8))[..., 1:, :] != 0, axis=(-1, -2))
+    short = np.broadcast_to(_w16(c[..., :1, :] << 2), c.shape)
+    ws = np.where(flat[..., None, None], short, ws)
+    return (np.clip(_idct_1d_simd(ws, 13 + 2 + 3), -128, 127) + 128).astype(np.uint8)
+
+
+def component_planes(blocks, qts, fullwidth=False):
+    """[(bh, bw, 64) quantised blocks], [(64,) quantisation table per component] -> [(8 bh, 8 bw) uint8 plane per component].
+    fullwidth: idct_islow_fullwidth in place of idct_islow."""
     out = []
     for b, q in zip(blocks, qts):
-        px = idct_islow(np.asarray(b).astype(np.int64) * np.asarray(q).astype(np.int64))
+        px = idct_islow_fullwidth(np.asarray(b).astype(np.int64) * np.asarray(q).astype(np.int64)) if fullwidth else idct_islow(b, q)
         bh, bw = px.shape[:2]
         out.append(px.transpose(0, 2, 1, 3).reshape(bh * 8, bw * 8))
     return out
@@ -482,11 +544,11 @@ def ycc_to_bgr(y, cb, cr):
 
 
 # ---------------------------------------------------------------------------------------------------------------- whole pipeline
-def pixels_from_coefficients(blocks, qts, h, w, hs, vs=None):
+def pixels_from_coefficients(blocks, qts, h, w, hs, vs=None, fullwidth=False):
     """The device half: quantised blocks per component + tables -> (h, w, 3) BGR uint8. hs, vs = luma sampling factors: 1 x 1 (4:4:4),
     2 x 2 (4:2:0; vs defaults to hs), 2 x 1 (4:2:2), 1 x 2 (4:4:0)."""
     vs = hs if vs is None else vs
-    pl = component_planes(blocks, qts)
+    pl = component_planes(blocks, qts, fullwidth)
     if len(pl) == 1:
         y = pl[0][:h, :w]
         return np.stack([y, y, y], -1)
@@ -510,8 +572,8 @@ def pixels_from_coefficients(blocks, qts, h, w, hs, vs=None):
     return ycc_to_bgr(pl[0][:h, :w], cb[:h, :w], cr[:h, :w])
 
 
-def imread_bgr(data):
-    """cv2.imread(file, IMREAD_COLOR) of a sequential or progressive JPEG given as bytes."""
+def imread_bgr(data, fullwidth=False):
+    """cv2.imread(file, IMREAD_COLOR) of a sequential or progressive JPEG given as bytes. fullwidth: with idct_islow_fullwidth."""
     f, blocks = coefficients(data)
     comps = f["comps"]
     if len(comps) == 3:
@@ -524,5 +586,5 @@ def imread_bgr(data):
             raise Unsupported("sampling factors")
     elif len(comps) != 1:
         raise Unsupported("component count")
-    img = pixels_from_coefficients(blocks, [f["qt"][c[3]] for c in comps], f["h"], f["w"], comps[0][1], comps[0][2])
+    img = pixels_from_coefficients(blocks, [f["qt"][c[3]] for c in comps], f["h"], f["w"], comps[0][1], comps[0][2], fullwidth)
     return np.ascontiguousarray(apply_orientation(img, f["marks"].get("orientation", 1)))

@@ -30,9 +30,10 @@ extern "C" int jpeg_pixels_host(const int16_t* coef, const uint16_t* qt3x64, con
       for (int bx = 0; bx < g.bw[c]; ++bx) {
         const int16_t* blk = coef + g.coef_off[c] + ((long long)by * g.bw[c] + bx) * 64;
         const uint16_t* q = qt3x64 + 64 * c;
-        int ws[8][8], x[8], o[8];
+        int ws[8][8], col[8][8], x[8], o[8], ac = 0;
+        for (int t = 0; t < 8; ++t) ac |= jidct_load(blk, q, true, t, col[t]);      // the block's flag from all eight columns (the kernels' shuffles)
         for (int t = 0; t < 8; ++t) {                      // pass 1: thread t takes column t
-          jidct_pass1(blk, q, true, t, o);
+          jidct_pass1(col[t], ac, o);
           for (int k = 0; k < 8; ++k) ws[k][t] = o[k];
         }
         for (int t = 0; t < 8; ++t) {                      // pass 2: thread t takes row t

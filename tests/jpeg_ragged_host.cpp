@@ -79,11 +79,16 @@ int main(int argc, char** argv) {
   for (long long bx = 0; bx < wgs; ++bx) {
     static int ws[JR_BLOCKS_PER_WG][8][9];
     JrBlockPos pos[256];
+    static int col[256][8];
+    int ac[JR_BLOCKS_PER_WG] = {0};
+    for (int tid = 0; tid < 256; ++tid) {      // the loads, and each block's flag from its eight columns (the kernel's shuffles)
+      pos[tid] = jr_block_locate(tab.data(), n, blocks, bx * JR_BLOCKS_PER_WG + (tid >> 3));
+      ac[tid >> 3] |= jr_idct_load(tab.data(), coef_exact.data(), qt.data(), pos[tid], tid & 7, col[tid]);
+    }
     for (int tid = 0; tid < 256; ++tid) {
       const int lb = tid >> 3, t = tid & 7;
-      pos[tid] = jr_block_locate(tab.data(), n, blocks, bx * JR_BLOCKS_PER_WG + lb);
       int o[8];
-      jr_idct_pass1(tab.data(), coef_exact.data(), qt.data(), pos[tid], t, o);
+      jidct_pass1(col[tid], ac[lb], o);
       for (int k = 0; k < 8; ++k) ws[lb][k][t] = o[k];
     }
     if (pos[0].live && pos[255].live && pos[0].img != pos[255].img) ++straddling;

@@ -286,3 +286,106 @@ def test_batch_cli_with_device_decode_writes_the_host_decode_paths_files(tmp_pat
             assert np.array_equal(np.asarray(Image.open(str(out_g / base))), np.asarray(Image.open(str(out_h / base)))), base
     finally:
         net.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Beyond the range an encoder reaches (tests/jpeg_beyond_cases.py): the IDCT kernel's 16-bit arithmetic (csrc/jpeg_pixel.h), the block's
+# zero-rows flag across its eight lanes, workgroups that mix block kinds, dead lanes.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+import jpeg_beyond_cases as BC  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def beyond(golden_dir):
+    """{name: (file bytes, committed pixels)} from tests/golden/jpeg_beyond_cases.npz, each checked once against the oracle
+    (oracle/jpeg_ref.py); read-only.
+
+    NOT compared with a live Pillow: out of range libjpeg-turbo's answer belongs to its x86 SIMD code, and a GPU host whose build runs
+    without SIMD would follow jidctint.c's masked range-limit table instead. For these cases the committed vectors carry the pin
+    (tests/test_jpeg.py checks them against Pillow where the CPU tests run); the in-range tests above keep asking the live Pillow."""
+    from oracle import jpeg_ref as J
+    g = np.load(os.path.join(golden_dir, "jpeg_beyond_cases.npz"))
+    assert list(g["names"]) == list(BC.cases())
+    out = {}
+    for name in g["names"]:
+        data, want = g["file_" + name].tobytes(), g["bgr_" + name]
+        assert np.array_equal(J.imread_bgr(data), want), name
+        want.setflags(write=False)
+        out[str(name)] = (data, want)
+    return out
+
+
+def _beyond_batches(fam):
+    """the family's cases grouped by what one uniform call takes (size, layout, orientation), in batches of 2 to 5; a case alone in its group
+    is batched with itself"""
+    groups = {}
+    for name, c in BC.family(fam).items():
+        groups.setdefault(B.jpeg_probe(c.data), []).append(name)
+    out = []
+    for names in groups.values():
+        if len(names) == 1:
+            names = names * 2
+        k = -(-len(names) // 5)
+        per = -(-len(names) // k)
+        out += [names[i:i + per] if len(names[i:i + per]) > 1 else names[i - 1:i + per] for i in range(0, len(names), per)]
+    assert all(2 <= len(b) <= 5 for b in out)
+    return out
+
+
+def _beyond_decode(ctx, beyond, names, entropy):
+    """The batch through ctpn_decode_jpeg_batch (entropy = "host") or ctpn_decode_jpeg_batch_device ("device"). The device Huffman decoder
+    takes sequential files only: a batch that holds a progressive file must be refused there (CTPN_ERR_UNSUPPORTED -- within the contract),
+    and its sequential files are decoded without it. -> (the names decoded, their images)"""
+    datas = [beyond[n][0] for n in names]
+    if entropy == "device" and any(b"\xff\xc2" in d for d in datas):
+        with pytest.raises(B.CtpnError) as e:
+            ctx.decode_jpeg_batch(datas, entropy="device")
+        assert e.value.code == B.CTPN_ERR_UNSUPPORTED and "progressive" in str(e.value)
+        names = [n for n in names if b"\xff\xc2" not in beyond[n][0]]
+        datas = [beyond[n][0] for n in names]
+        if not names:
+            return [], []
+    ptr, shape = ctx.decode_jpeg_batch(datas, entropy=entropy)
+    assert shape == (len(names),) + beyond[names[0]][1].shape[:2]
+    got = ctx.jpeg_batch_fetch(ptr, shape)
+    if entropy == "device":      # the device decoder itself wrote the (int16_t) blocks the IDCT read: no file went to the host half
+        stats = ctx.jpeg_entropy_device_stats()
+        assert stats["device"] == len(names) and stats["host"] == 0, (names, stats)
+    return names, got
+
+
+@pytest.mark.parametrize("entropy", ["host", "device"])
+@pytest.mark.parametrize("fam", list("abcde"))
+def test_beyond_range_cases_alone_equal_the_committed_vectors(ctx, beyond, fam, entropy):
+    """Every case of the family in a call of its own: one image's blocks, the last workgroup's dead lanes."""
+    decoded = 0
+    for name in BC.family(fam):
+        names, got = _beyond_decode(ctx, beyond, [name], entropy)
+        for n, im in zip(names, got):
+            d = np.argwhere(im != beyond[n][1])
+            assert d.size == 0, "%s: %d bytes differ, first at %s: %d vs %d" % (n, len(d), d[0], im[tuple(d[0])], beyond[n][1][tuple(d[0])])
+            decoded += 1
+    assert decoded == sum(1 for c in BC.family(fam).values() if entropy == "host" or b"\xff\xc2" not in c.data)
+
+
+@pytest.mark.parametrize("entropy", ["host", "device"])
+@pytest.mark.parametrize("fam", list("abcde"))
+def test_beyond_range_cases_in_batches_equal_the_committed_vectors(ctx, beyond, fam, entropy):
+    """The family's cases in batches of 2 to 5: workgroups hold blocks of different kinds and of two images."""
+    for batch in _beyond_batches(fam):
+        names, got = _beyond_decode(ctx, beyond, batch, entropy)
+        for n, im in zip(names, got):
+            assert np.array_equal(im, beyond[n][1]), (batch, n, int((im != beyond[n][1]).any(-1).sum()))
+
+
+def test_beyond_range_batch_decoded_twice_is_the_same_batch(ctx, beyond):
+    """No state survives between calls: a batch, another batch of other block kinds in between (it takes the other buffer set), the first
+    batch again (the first set, reused) -- ctpn_jpeg_batch_fetch returns the same bytes both times, and they are the committed ones."""
+    first, other = _beyond_batches("c")[0], _beyond_batches("b")[-1]
+    _, a = _beyond_decode(ctx, beyond, first, "host")
+    _beyond_decode(ctx, beyond, other, "host")
+    _beyond_decode(ctx, beyond, other, "host")
+    _, b = _beyond_decode(ctx, beyond, first, "host")
+    assert np.array_equal(a, b)
+    for n, im in zip(first, b):
+        assert np.array_equal(im, beyond[n][1]), n

@@ -260,3 +260,34 @@ def test_demo_batch_ragged_device_decode_writes_the_same_result_files(weights, t
     assert any(len(outs[True][n]) > 0 for n in res)
     if decode == "gpu":      # the annotated images too: cut from the fetched canvas, written by the host writer -- the same files
         assert sorted(n for n in outs[True] if not n.startswith("res_")) == ["page%d.jpg" % i for i in range(8)] + ["page8.png"]
+
+
+def test_beyond_range_files_of_mixed_layouts_equal_each_file_alone(ctx, golden_dir):
+    """tests/jpeg_beyond_cases.py RAGGED: five files whose coefficients leave the range an encoder reaches (16-bit tables, wrapping products,
+    row-0-only and column-0-only blocks; 4:2:0, 4:2:2, 4:4:0, gray, an EXIF transpose; 32 and 16 and 24 rows) in one ragged call at
+    factor 1, host and device entropy decoding: every slot equals the uniform call on that file alone, and both equal the committed vectors
+    (tests/golden/jpeg_beyond_cases.npz). Not compared with a live Pillow: out of range the pin is libjpeg-turbo's x86 SIMD arithmetic, which
+    a host without SIMD would not reproduce; the vectors carry it."""
+    import os
+    import jpeg_beyond_cases as BC
+    g = np.load(os.path.join(golden_dir, "jpeg_beyond_cases.npz"))
+    names = list(BC.RAGGED)
+    files = [g["file_" + n].tobytes() for n in names]
+    want = [g["bgr_" + n] for n in names]
+    sizes = [B.jpeg_probe(d)[:2] for d in files]
+    assert [tuple(w.shape[:2]) for w in want] == sizes and {s[1] for s in sizes} == {BC.RAGGED_WC} and len({s[0] for s in sizes}) == 3
+    lone = []
+    for d in files:
+        ptr, shape = ctx.decode_jpeg_batch([d])
+        lone.append(ctx.jpeg_batch_fetch(ptr, shape)[0])
+    for entropy in ("host", "device"):
+        for order in (list(range(5)), [4, 3, 2, 1, 0]):
+            (ptr, shape), heights = ctx.decode_jpeg_ragged([files[i] for i in order], [sizes[i] for i in order], [1.0] * 5, BC.RAGGED_HC, BC.RAGGED_WC, entropy=entropy)
+            assert shape == (5, BC.RAGGED_HC, BC.RAGGED_WC) and list(heights) == [sizes[i][0] for i in order]
+            got = ctx.jpeg_batch_fetch(ptr, shape)
+            for k, i in enumerate(order):
+                assert np.array_equal(got[k, :heights[k]], lone[i]), (entropy, order, names[i])
+                assert np.array_equal(got[k, :heights[k]], want[i]), (entropy, order, names[i])
+                assert not got[k, heights[k]:].any()
+            if entropy == "device":
+                assert ctx.jpeg_entropy_device_stats()["device"] == 5

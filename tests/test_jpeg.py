@@ -4,6 +4,7 @@
   library host half (ctpn_jpeg_entropy_decode, C++)  ==  oracle entropy decoder, coefficient for coefficient       (bit-exact)
   library host half -> oracle pixel half  ==  Pillow                                                             (bit-exact)
   library host half -> the device half's per-sample source (csrc/jpeg_pixel.h) compiled for the host  ==  Pillow  (bit-exact)
+  all of the above once more on tests/jpeg_beyond_cases.py: coefficients beyond what an encoder writes, where the IDCT's 16-bit lanes show
 
 The device half (IDCT / upsampling / colour kernels) is the GPU suite's: tests/test_gpu_jpeg.py. Nothing here needs a GPU or
 /root/reference.
@@ -600,3 +601,126 @@ def test_demo_golden_is_what_its_generator_makes_from_the_reference_tree(golden_
     for k in a.files:
         if k != "decoder":
             assert np.array_equal(a[k], b[k]), k
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Beyond the range an encoder reaches (tests/jpeg_beyond_cases.py): tables scaled up, 16-bit tables, coefficient-level files. There the pin is
+# the 16-bit arithmetic of libjpeg-turbo's x86 SIMD islow IDCT, which oracle/jpeg_ref.py idct_islow and csrc/jpeg_pixel.h restate.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+import jpeg_beyond_cases as BC  # noqa: E402
+
+BEYOND = list(BC.cases())
+
+
+@pytest.fixture(scope="module")
+def beyond_pillow():
+    """Pillow's decode (turned by the EXIF orientation) of every case, once; read-only. A warning from Pillow is an error here: every file is
+    meant to be a valid one."""
+    import warnings
+    out = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        for name, c in BC.cases().items():
+            out[name] = cv2_like_bgr(c.data)
+            out[name].setflags(write=False)
+    return out
+
+
+def test_beyond_case_table_is_what_its_docstring_says():
+    t = BC.cases()
+    assert {k[0] for k in t} == set("abcde") and all(len(BC.family(f)) >= 4 for f in "abcde")
+    assert [k for k, c in t.items() if c.control] == list(BC.CONTROLS) and all(k[0] in "cd" for k in BC.CONTROLS)
+    assert 4 * len(BC.CONTROLS) <= len(t)
+    sizes = [B.jpeg_probe(c.data)[:2] for c in t.values()]
+    assert all(16 <= min(s) and max(s) <= 56 for s in sizes)
+    assert any(b"\xff\xc2" in c.data for c in t.values()) and any(b"\xff\xdd" in c.data for c in t.values())
+    for k, c in BC.family("d").items():                       # 16-bit tables under an SOF1 frame
+        i = c.data.index(b"\xff\xdb")
+        assert c.data[i + 4] >> 4 == 1 and b"\xff\xc1" in c.data, k
+    layouts = {(B.jpeg_probe(c.data)[2], B.jpeg_probe(c.data)[3] & 0xff) for c in BC.family("e").values()}
+    assert layouts >= {(3, 2), (3, 0x21), (3, 0x12)}
+    assert {(B.jpeg_probe(c.data)[3] >> 8) + 1 for c in BC.family("e").values()} >= {1, 5, 6}
+
+
+@pytest.mark.parametrize("name", BEYOND)
+def test_beyond_oracle_equals_pillow(name, beyond_pillow):
+    got = J.imread_bgr(BC.cases()[name].data)
+    want = beyond_pillow[name]
+    assert got.shape == want.shape
+    assert np.array_equal(got, want), "%d pixels differ" % int((got != want).any(-1).sum())
+
+
+@pytest.mark.parametrize("name", BEYOND)
+def test_beyond_each_case_bites(name, beyond_pillow):
+    """The arithmetic the device had before (full-width integers, a clamp: oracle idct_islow_fullwidth) gives another picture than Pillow on
+    every case but the named in-range controls, where it gives the same one: a case that drifts back into range does not pass unnoticed."""
+    c = BC.cases()[name]
+    old = J.imread_bgr(c.data, fullwidth=True)
+    differing = int((old != beyond_pillow[name]).any(-1).sum())
+    assert (differing == 0) if c.control else (differing > 0), differing
+
+
+@pytest.mark.parametrize("name", BEYOND)
+def test_beyond_library_host_half_then_oracle_pixels_equals_pillow(name, beyond_pillow):
+    data = BC.cases()[name].data
+    frame, want = J.coefficients(data)
+    planes, qt, lay = B.jpeg_entropy_decode(data)
+    for g, o in zip(planes, want):
+        assert np.array_equal(g.astype(np.int32), o)
+    for c, comp in enumerate(frame["comps"]):
+        assert np.array_equal(qt[c].astype(np.int64), frame["qt"][comp[3]])      # uint16 entries up to 65535 arrive whole
+    got = J.pixels_from_coefficients(planes, [qt[c] for c in range(lay["ncomp"])], lay["h"], lay["w"], lay["hs"], lay["vs"])
+    assert np.array_equal(J.apply_orientation(got, lay["orientation"]), beyond_pillow[name])
+
+
+@pytest.mark.parametrize("name", BEYOND)
+def test_beyond_device_source_compiled_for_the_host_equals_pillow(name, beyond_pillow, device_source_on_host):
+    got = device_source_on_host(BC.cases()[name].data)
+    want = beyond_pillow[name]
+    assert np.array_equal(got, want), "%d pixels differ" % int((got != want).any(-1).sum())
+
+
+def test_beyond_committed_vectors(golden_dir, beyond_pillow, device_source_on_host):
+    """tests/golden/jpeg_beyond_cases.npz (oracle/make_jpeg_beyond_golden.py: the files and Pillow's decode of them where the recipe ran): the
+    case module still writes the committed bytes, and the oracle, the device source compiled for the host and the Pillow installed here all
+    reproduce the committed pixels. The GPU tests compare with these vectors, not with a live Pillow."""
+    g = np.load(os.path.join(golden_dir, "jpeg_beyond_cases.npz"))
+    assert list(g["names"]) == BEYOND
+    for name in BEYOND:
+        data, want = g["file_" + name].tobytes(), g["bgr_" + name]
+        assert data == BC.cases()[name].data, name
+        assert np.array_equal(J.imread_bgr(data), want), name
+        assert np.array_equal(device_source_on_host(data), want), name
+        assert np.array_equal(beyond_pillow[name], want), name
+
+
+@pytest.fixture(scope="module")
+def idct_ubsan_program(root, tmp_path_factory):
+    """tests/jpeg_idct_ubsan_host.cpp: csrc/jpeg_pixel.h's two passes in a program of its own under UBSan (nothing preloaded, nothing loaded
+    into Python)."""
+    import subprocess
+    exe = str(tmp_path_factory.mktemp("jpeg_idct_ubsan") / "jpeg_idct_ubsan_host")
+    subprocess.run(["g++", "-O1", "-g", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-fsanitize=undefined", "-fno-sanitize-recover=all", "-o", exe,
+                    os.path.join(root, "tests", "jpeg_idct_ubsan_host.cpp")], check=True)
+    return exe
+
+
+@pytest.mark.parametrize("fam", ["c", "d"])
+def test_beyond_idct_has_no_undefined_overflow(fam, idct_ubsan_program, tmp_path):
+    """Every block of families c and d (products up to 1023 x 65535, wraps, both saturations) through the two passes under
+    -fsanitize=undefined -fno-sanitize-recover=all: no report, and the planes are the oracle's."""
+    import struct
+    import subprocess
+    blob, want, n = b"", [], 0
+    for name, c in BC.family(fam).items():
+        planes, qt, lay = B.jpeg_entropy_decode(c.data)
+        for ci, p in enumerate(planes):
+            blk = np.ascontiguousarray(p.reshape(-1, 64))
+            blob += b"".join(qt[ci].astype("<u2").tobytes() + b_.astype("<i2").tobytes() for b_ in blk)
+            want.append(J.idct_islow(blk, qt[ci]).reshape(-1, 64))
+            n += len(blk)
+    (tmp_path / "blocks.bin").write_bytes(struct.pack("<i", n) + blob)
+    r = subprocess.run([idct_ubsan_program, str(tmp_path / "blocks.bin"), str(tmp_path / "planes.out")], capture_output=True, text=True)
+    assert r.stderr == "" and r.returncode == 0, r.stderr[-3000:]
+    got = np.frombuffer((tmp_path / "planes.out").read_bytes(), np.uint8).reshape(n, 64)
+    assert np.array_equal(got, np.concatenate(want))

@@ -19,8 +19,7 @@ NAMES = ("ctpn_decode_jpeg_batch_ragged", "ctpn_decode_jpeg_files_ragged")
 @pytest.fixture(scope="module")
 def program(root, tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("jpeg_ragged_host") / "jpeg_ragged_host")
-    # C++20: jidct_1d shifts negative values left like libjpeg's jidctint.c does, which is defined (two's complement) from C++20 on and what
-    # hipcc's target does; -ffp-contract=off as the kernels' unit is built
+    # -ffp-contract=off as the kernels' unit is built
     subprocess.run(["g++", "-O1", "-g", "-std=c++20", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-o", exe, os.path.join(root, "tests", "jpeg_ragged_host.cpp")], check=True)
     return exe
@@ -77,6 +76,39 @@ def test_kernels_per_thread_source_under_sanitizers(program, tmp_path, order, hc
     for k in range(len(order)):
         assert np.array_equal(got[k], want[k]), (order[k], np.argwhere(got[k] != want[k])[:4])
         assert not got[k, heights[k]:].any()
+
+
+@pytest.mark.parametrize("order", [(0, 1, 2, 3, 4), (4, 3, 2, 1, 0)])
+def test_beyond_range_files_through_the_kernels_source_under_sanitizers(program, tmp_path, order):
+    """tests/jpeg_beyond_cases.py RAGGED -- five files of different layouts and heights whose coefficients leave the range an encoder reaches
+    (wrapping products, 16-bit tables, row-0-only and column-0-only blocks) -- as one ragged batch at factor 1 through both kernels' per-thread
+    source: IDCT workgroups hold blocks of two images and of both kinds, the block's zero-rows flag comes from its eight columns. The canvas
+    equals Pillow's decode of each file and the committed vectors; nothing from ASan or UBSan (no signed overflow on the way)."""
+    import jpeg_beyond_cases as BC
+    import util_jpeg as U
+    names = [BC.RAGGED[i] for i in order]
+    files = [BC.cases()[n].data for n in names]
+    want = [U.cv2_like_bgr(d) for d in files]
+    assert {w.shape[1] for w in want} == {BC.RAGGED_WC} and len({w.shape[0] for w in want}) == 3
+    blob = struct.pack("<3i", len(files), BC.RAGGED_HC, BC.RAGGED_WC)
+    for d in files:
+        l8, qt, coef = _entropy(d)
+        blob += l8.tobytes() + struct.pack("<di", 1.0, coef.size) + qt.tobytes() + coef.tobytes()
+    (tmp_path / "batch.bin").write_bytes(blob)
+    r = subprocess.run([program, str(tmp_path / "batch.bin"), str(tmp_path / "canvas.out")], capture_output=True, text=True)
+    assert r.stderr == "", r.stderr[-3000:]
+    assert r.returncode == 0, r.stdout[-2000:]
+    words = r.stdout.split()
+    assert words[-1] == "ok" and int(words[words.index("straddling") + 1]) >= 1
+    raw = (tmp_path / "canvas.out").read_bytes()
+    assert list(np.frombuffer(raw[:4 * len(files)], np.int32)) == [w.shape[0] for w in want]
+    got = np.frombuffer(raw[4 * len(files):], np.uint8).reshape(len(files), BC.RAGGED_HC, BC.RAGGED_WC, 3)
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_beyond_cases.npz"))
+    for k, n in enumerate(names):
+        h = want[k].shape[0]
+        assert np.array_equal(got[k, :h], want[k]), (n, np.argwhere(got[k, :h] != want[k])[:4])
+        assert np.array_equal(got[k, :h], g["bgr_" + n]), n
+        assert not got[k, h:].any()
 
 
 def test_symbols_bindings_and_null_arguments(root):

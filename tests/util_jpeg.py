@@ -120,7 +120,6 @@ def with_exif_orientation(data, orientation, big_endian=False):
 def encode_custom(img, hs=1, vs=2, q=8, restart=0, orientation=None):
     """(h, w, 3) RGB uint8 (or (h, w) gray) -> baseline JPEG bytes with luma sampling hs x vs and 1 x 1 chroma. q: the quantisation step
     of the low frequencies (it grows with the frequency)."""
-    import struct
     from scipy.fft import dctn
     img = np.asarray(img)
     gray = img.ndim == 2
@@ -150,6 +149,14 @@ def encode_custom(img, hs=1, vs=2, q=8, restart=0, orientation=None):
         co[..., 1:8, :] = np.clip(co[..., 1:8, :], -1023, 1023)
         co[..., 0, 1:] = np.clip(co[..., 0, 1:], -1023, 1023)
         blocks.append(co.reshape(H // 8, W // 8, 64))
+    return _write_baseline(blocks, samp, [qt.reshape(-1)], [0] * len(planes), h, w, restart=restart, orientation=orientation)
+
+
+def _write_baseline(blocks, samp, tables, tq, h, w, pq=0, restart=0, orientation=None):
+    """The file around quantised coefficients: blocks[c] (block rows, block columns, 64) in natural order, whole MCUs; samp[c] = (hs, vs);
+    tables: (64,) quantisation tables in natural order, tq[c] the one component c uses. pq = 1: 16-bit table entries and an SOF1 frame."""
+    import struct
+    mcux, mcuy = -(-w // (8 * samp[0][0])), -(-h // (8 * samp[0][1]))
     bits = []
 
     def put(code, n):
@@ -179,20 +186,21 @@ def encode_custom(img, hs=1, vs=2, q=8, restart=0, orientation=None):
             if byte == 0xFF:
                 out.append(0)
         bits.clear()
-    pred = [0] * len(planes)
+    pred = [0] * len(blocks)
     nm = 0
     for my in range(mcuy):
         for mx in range(mcux):
             if restart and nm and nm % restart == 0:
                 flush_bits()
                 out += bytes([0xFF, 0xD0 + ((nm // restart - 1) & 7)])
-                pred = [0] * len(planes)
+                pred = [0] * len(blocks)
             nm += 1
             for ci, (ch, cv) in enumerate(samp):
                 for by in range(cv):
                     for bx in range(ch):
                         blk = blocks[ci][my * cv + by, mx * ch + bx]
                         t, v = mag(blk[0] - pred[ci])
+                        assert t <= 11, "DC difference beyond the table's categories"
                         pred[ci] = int(blk[0])
                         put(t, 4)
                         if t:
@@ -218,15 +226,54 @@ def encode_custom(img, hs=1, vs=2, q=8, restart=0, orientation=None):
     head = b"\xff\xd8" + seg(0xE0, b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0")
     if orientation is not None:
         head += exif_app1(orientation)
-    head += seg(0xDB, bytes([0]) + bytes(int(qt.reshape(-1)[_ZZ[k]]) for k in range(64)))
-    nc = len(planes)
-    head += seg(0xC0, struct.pack(">BHHB", 8, h, w, nc) + b"".join(bytes([ci + 1, (ch << 4) | cv, 0]) for ci, (ch, cv) in enumerate(samp)))
+    for k, tbl in enumerate(tables):
+        zz = [int(tbl[_ZZ[i]]) for i in range(64)]
+        head += seg(0xDB, bytes([(pq << 4) | k]) + (struct.pack(">64H", *zz) if pq else bytes(zz)))
+    nc = len(blocks)
+    head += seg(0xC1 if pq else 0xC0,
+                struct.pack(">BHHB", 8, h, w, nc) + b"".join(bytes([ci + 1, (ch << 4) | cv, tq[ci]]) for ci, (ch, cv) in enumerate(samp)))
     head += seg(0xC4, bytes([0x00]) + bytes([0, 0, 0, 12] + [0] * 12) + bytes(range(12)))
     head += seg(0xC4, bytes([0x10]) + bytes([0] * 7 + [len(_AC_SYMS)] + [0] * 8) + bytes(_AC_SYMS))
     if restart:
         head += seg(0xDD, struct.pack(">H", restart))
     head += seg(0xDA, bytes([nc]) + b"".join(bytes([ci + 1, 0x00]) for ci in range(nc)) + bytes([0, 63, 0]))
     return head + bytes(out) + b"\xff\xd9"
+
+
+def encode_coefficients(blocks, qts, h, w, hs=1, vs=1, pq=0, restart=0):
+    """A baseline file straight from QUANTISED coefficients: blocks[c] (block rows, block columns, 64) integers in natural order for 1 (gray)
+    or 3 components, whole MCUs of luma sampling hs x vs with 1 x 1 chroma; qts[c] that component's (64,) table in natural order, entries
+    1 .. 255, or 1 .. 65535 with pq = 1 (16-bit entries, written under an SOF1 frame). The Huffman tables are encode_custom's: DC
+    differences up to 11 bits, AC magnitudes up to 1023. Nothing is transformed or rounded, so the decoder's coef * q is exactly what the
+    caller chose -- values no forward DCT of 8-bit pixels produces included."""
+    blocks = [np.asarray(b, np.int64) for b in blocks]
+    qts = [np.asarray(q, np.int64).reshape(64) for q in qts]
+    assert len(blocks) == len(qts) and len(blocks) in (1, 3)
+    samp = [(1, 1)] if len(blocks) == 1 else [(hs, vs), (1, 1), (1, 1)]
+    mcux, mcuy = -(-w // (8 * samp[0][0])), -(-h // (8 * samp[0][1]))
+    for b, (ch, cv) in zip(blocks, samp):
+        assert b.shape == (mcuy * cv, mcux * ch, 64), (b.shape, (mcuy * cv, mcux * ch, 64))
+        assert np.abs(b[..., 1:]).max(initial=0) <= 1023
+    for q in qts:
+        assert q.min() >= 1 and q.max() <= (65535 if pq else 255)
+    return _write_baseline(blocks, samp, qts, list(range(len(blocks))), h, w, pq=pq, restart=restart)
+
+
+def with_dqt(data, fn):
+    """The file with every entry v of every DQT segment (8-bit tables: Pq stays 0) replaced by fn(v), kept inside 1 .. 255."""
+    out, i = bytearray(data), 2
+    while data[i + 1] != 0xDA:
+        assert data[i] == 0xFF
+        L = int.from_bytes(data[i + 2:i + 4], "big")
+        if data[i + 1] == 0xDB:
+            j = i + 4
+            while j < i + 2 + L:
+                assert data[j] >> 4 == 0
+                for k in range(j + 1, j + 65):
+                    out[k] = min(255, max(1, int(fn(data[k]))))
+                j += 65
+        i += 2 + L
+    return bytes(out)
 
 
 # files Pillow cannot write (tests/golden/jpeg_cases.npz holds them next to CASES): name -> bytes. 4:4:0 is the layout of two of the

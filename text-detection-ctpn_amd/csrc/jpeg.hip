@@ -2,8 +2,10 @@
 //   host   : marker parsing and Huffman entropy decoding (sequential by nature: one image per worker thread of the ctx's pool) into
 //            quantised DCT coefficient blocks, int16, natural order -- about as many bytes as the decoded pixels;
 //   device : dequantisation + the 8 x 8 inverse DCT (jpeg_idct_kernel), chroma upsampling + YCbCr -> BGR (jpeg_color_kernel).
-// The pixel arithmetic is libjpeg's, integer for integer, so that the result equals what Pillow / cv2 (both libjpeg-turbo, whose SIMD paths
-// are bit-exact with its C code) return: jidctint.c's "islow" IDCT (CONST_BITS 13, PASS1_BITS 2), jdsample.c's h2v2 "fancy" (triangle)
+// The pixel arithmetic is libjpeg's, integer for integer, so that the result equals what Pillow / cv2 (both libjpeg-turbo) return: the
+// "islow" IDCT (CONST_BITS 13, PASS1_BITS 2) as libjpeg-turbo's x86 SIMD code computes it -- jidctint.c's factoring in 16-bit lanes (jpeg_pixel.h
+// lists the wraps, the two saturations and the whole-block shortcut), equal to jidctint.c on every coefficient an encoder writes from 8-bit
+// pixels and the pin beyond that range; jidctint.c WITHOUT SIMD (its masked range-limit table) differs there --, jdsample.c's h2v2 "fancy" (triangle)
 // upsampling with its alternating + 8 / + 7 rounding and edge replication (4:2:2: h2v1, + 1 / + 2), jdcolor.c's 16-bit fixed-point YCbCr -> RGB. Restated from the
 // published algorithms (libjpeg 6b API level, which libjpeg-turbo implements); checked bit for bit against Pillow on the CPU through
 // oracle/jpeg_ref.py and on the GPU through the C ABI (tests/test_jpeg.py, tests/test_gpu_jpeg.py).
@@ -519,7 +521,8 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
   const int16_t* blk = coef + (long long)img * g.coef_per_img + g.coef_off[c] + b * 64;
   const uint16_t* q = qt + ((long long)img * 3 + c) * 64;
   int x[8], o[8];
-  jidct_pass1(blk, q, live, t, o);
+  const int ac = jidct_load(blk, q, live, t, x);
+  jidct_pass1(x, jidct_group8_or(ac), o);                               // (every lane shuffles, dead ones with zero)
 #pragma unroll
   for (int k = 0; k < 8; ++k) ws[lb][k][t] = o[k];                      // ws[row][col]
   __syncthreads();

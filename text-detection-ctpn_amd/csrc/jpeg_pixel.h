@@ -17,22 +17,36 @@ struct JpegGeom {
   long long blocks_per_img;
 };
 
+// The IDCT restates libjpeg-turbo's x86 SIMD "islow" (jsimd_idct_islow_sse2 / _avx2: what Pillow and cv2 run on x86-64), not jidctint.c in
+// full-width integers. On every coefficient an encoder can write from 8-bit pixels the two agree; beyond that range (tables scaled up,
+// 16-bit tables, coefficients no forward DCT produces) the SIMD code's 16-bit lanes show, and its picture is the pin:
+//   coef * q keeps its low 16 bits, signed (pmullw);   in0 + in4, in0 - in4, in7 + in3 and in5 + in1 are 16-bit lanes and wrap;
+//   every other sum is a pair of 16 x 16 products in a 32-bit lane (pmaddwd, the constants folded pairwise);
+//   each pass ends in (sum + rounding) >> descale, saturated to int16 (packssdw); pass 2 then saturates to -128 .. 127 and adds 128
+//   (pass 2 below saturates once, to -128 .. 127: the same value);
+//   a block whose rows 1 .. 7 are all zero skips pass 1: every workspace row is row 0 << PASS1_BITS, wrapped to 16 bits, not saturated.
+// A libjpeg-turbo that runs without SIMD follows jidctint.c's masked range-limit table instead and differs from both out of range.
+// No signed overflow anywhere: int16 x uint16 is at most 32768 x 65535 = 2 147 450 880 < 2^31, and the inputs of a pass are 16-bit values,
+// so every sum below stays inside 31 bits (largest: 2 115 960 832). Nothing needs unsigned arithmetic; tests/jpeg_idct_ubsan_host.cpp
+// runs both passes under UBSan.
+__host__ __device__ __forceinline__ int jidct_wrap16(int v) { return (int)(int16_t)(uint16_t)(uint32_t)v; }
+__host__ __device__ __forceinline__ int jidct_sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+__host__ __device__ __forceinline__ int jidct_sat8(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }
+
+// x: eight 16-bit values; o: (sum + rounding) >> descale, not yet saturated
 __host__ __device__ __forceinline__ void jidct_1d(const int (&x)[8], int (&o)[8], int descale) {
-  // jidctint.c: even part
-  int z2 = x[2], z3 = x[6];
-  int z1 = (z2 + z3) * 4433;
-  const int tmp2 = z1 + z3 * (-15137), tmp3 = z1 + z2 * 6270;
-  z2 = x[0]; z3 = x[4];
-  const int tmp0 = (z2 + z3) << 13, tmp1 = (z2 - z3) << 13;
+  // even part: tmp2 = z2 * F0.541 + z3 * (F0.541 - F1.847), tmp3 = z2 * (F0.541 + F0.765) + z3 * F0.541
+  const int tmp2 = x[2] * 4433 + x[6] * (-10704), tmp3 = x[2] * 10703 + x[6] * 4433;
+  const int tmp0 = jidct_wrap16(x[0] + x[4]) * 8192, tmp1 = jidct_wrap16(x[0] - x[4]) * 8192;
   const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-  // odd part
-  int t0 = x[7], t1 = x[5], t2 = x[3], t3 = x[1];
-  z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
-  int z4 = t1 + t3;
-  const int z5 = (z3 + z4) * 9633;
-  t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
-  z1 *= -7373; z2 *= -20995; z3 = z3 * (-16069) + z5; z4 = z4 * (-3196) + z5;
-  t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+  // odd part: z3 = in7 + in3, z4 = in5 + in1 (16-bit); z5 folded into both
+  const int z3w = jidct_wrap16(x[7] + x[3]), z4w = jidct_wrap16(x[5] + x[1]);
+  const int z3 = z3w * (-6436) + z4w * 9633, z4 = z3w * 9633 + z4w * 6437;
+  const int t0 = x[7] * (-4927) + x[1] * (-7373) + z3;
+  const int t1 = x[5] * (-4176) + x[3] * (-20995) + z4;
+  const int t2 = x[5] * (-20995) + x[3] * 4177 + z3;
+  const int t3 = x[7] * (-7373) + x[1] * 4926 + z4;
   const int r = 1 << (descale - 1);
   o[0] = (tmp10 + t3 + r) >> descale; o[7] = (tmp10 - t3 + r) >> descale;
   o[1] = (tmp11 + t2 + r) >> descale; o[6] = (tmp11 - t2 + r) >> descale;
@@ -43,28 +57,76 @@ __host__ __device__ __forceinline__ void jidct_1d(const int (&x)[8], int (&o)[8]
 // The two passes of one 8 x 8 block's IDCT as thread t of the block's eight runs them. The caller finds the block (blk: its 64 coefficients,
 // q: its component's table, dst: row t of the block in its plane, 8-byte aligned), keeps the transpose buffer and puts its barrier between
 // the passes. A lane that is not live computes on zeros and neither loads nor stores: its pointers are never dereferenced.
-// pass 1: column t (elements t, t + 8, ...), dequantised; o[k] goes to row k, column t of the transpose buffer
-__host__ __device__ __forceinline__ void jidct_pass1(const int16_t* __restrict__ blk, const uint16_t* __restrict__ q, bool live, int t, int (&o)[8]) {
-  int x[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+// load: column t (elements t, t + 8, ...) dequantised into x; returns the OR of the column's seven RAW coefficients of rows 1 .. 7. The
+// caller ORs the eight columns' answers (the kernels: jidct_group8_or; a host loop: over t) -- zero means the block takes the shortcut
+__host__ __device__ __forceinline__ int jidct_load(const int16_t* __restrict__ blk, const uint16_t* __restrict__ q, bool live, int t, int (&x)[8]) {
+  int ac = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x[k] = 0;
   if (live) {      // (one branch around the sixteen loads, not a select per element: a load cannot be hoisted out of a select)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = (int)blk[8 * k + t] * (int)q[8 * k + t];
+    for (int k = 0; k < 8; ++k) {
+      const int c = blk[8 * k + t];
+      if (k) ac |= c;
+      x[k] = jidct_wrap16(c * (int)q[8 * k + t]);      // (|c| <= 32768, q <= 65535: the product stays inside 31 bits)
+    }
   }
-  jidct_1d(x, o, 13 - 2);
+  return ac;
+}
+
+#if defined(__HIPCC__)
+// the OR of v over the eight consecutive lanes of a block's threads (tid >> 3 names the block, so a group is one half of a DPP row and
+// never straddles a wave): an xor butterfly over lane distances 1, 2, 4 as three DPP moves -- quad_perm [1,0,3,2], quad_perm [2,3,0,1],
+// then row_half_mirror (lane i of the eight reads lane 7 - i, i.e. the other quad, whose four lanes agree by then). No LDS, no barrier.
+// Every lane of the wave runs it, dead lanes with v = 0: the kernels call it outside any branch, with the whole workgroup active
+__device__ __forceinline__ int jidct_group8_or(int v) {
+  v |= __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+  v |= __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+  return v;
+}
+#endif
+
+// pass 1: x from jidct_load, block_ac the block's OR; o[k] goes to row k, column t of the transpose buffer.
+// The shortcut without a second path: with rows 1 .. 7 zero the general pass gives every o[k] = sat16(4 x[0]) exactly
+// ((x[0] * 8192 + 1024) >> 11 = 4 x[0]), where the shortcut wants wrap16(4 x[0]). wrap16(4 x[0]) is 4 times x[0]'s low 14 bits taken as a
+// signed value, which the general pass reproduces without saturating -- so a flat block only swaps x[0] for that (one select, no branch:
+// a wave mixes both kinds of block)
+__host__ __device__ __forceinline__ void jidct_pass1(const int (&x)[8], int block_ac, int (&o)[8]) {
+  int y[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) y[k] = x[k];
+  y[0] = block_ac == 0 ? jidct_wrap16(x[0] * 4) >> 2 : x[0];
+  jidct_1d(y, o, 13 - 2);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = jidct_sat16(o[k]);
+}
+
+// pass 1 in one call, for a caller that runs a block's columns one after the other and has no lanes to exchange the flag between (a host
+// loop over t that keeps no per-column state): the block's flag is read from the block itself, rows 1 .. 7 of all eight columns. Same
+// loads, same flag, same pass as the three-step form above; the kernels do not use it (56 loads per thread instead of 7 and three moves)
+__host__ __device__ __forceinline__ void jidct_pass1(const int16_t* __restrict__ blk, const uint16_t* __restrict__ q, bool live, int t, int (&o)[8]) {
+  int x[8], ac = 0;
+  jidct_load(blk, q, live, t, x);
+  if (live)
+    for (int k = 8; k < 64; ++k) ac |= blk[k];
+  jidct_pass1(x, ac, o);
 }
 
 struct alignas(8) JpegVec8 { uint32_t lo, hi; };
 
-// pass 2: row t (x: that row of the transpose buffer); eight clamped samples as one 8-byte store
+// pass 2: row t (x: that row of the transpose buffer); eight samples as one 8-byte store
 __host__ __device__ __forceinline__ void jidct_pass2(uint8_t* __restrict__ dst, bool live, const int (&x)[8]) {
-  int o[8];
-  jidct_1d(x, o, 13 + 2 + 3);
+  int y[8], o[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) y[k] = jidct_wrap16(x[k]);      // (pass 1's results are 16-bit values already; saying so buys 24-bit multiplies)
+  jidct_1d(y, o, 13 + 2 + 3);
   if (!live) return;
   uint32_t lo = 0, hi = 0;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int v = o[k] + 128; v = v < 0 ? 0 : (v > 255 ? 255 : v); lo |= (uint32_t)v << (8 * k);
-    int u = o[k + 4] + 128; u = u < 0 ? 0 : (u > 255 ? 255 : u); hi |= (uint32_t)u << (8 * k);
+  for (int k = 0; k < 4; ++k) {      // (packssdw, then packsswb: saturating to int16 first changes nothing)
+    lo |= (uint32_t)(jidct_sat8(o[k]) + 128) << (8 * k);
+    hi |= (uint32_t)(jidct_sat8(o[k + 4]) + 128) << (8 * k);
   }
   *(JpegVec8*)dst = JpegVec8{lo, hi};
 }

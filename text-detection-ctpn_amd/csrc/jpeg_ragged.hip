@@ -20,7 +20,8 @@ __global__ __launch_bounds__(256) void jpeg_idct_ragged_kernel(const int16_t* __
   const int tid = threadIdx.x, lb = tid >> 3, t = tid & 7;
   const JrBlockPos p = jr_block_locate(tab, n, total_blocks, (long long)blockIdx.x * JR_BLOCKS_PER_WG + lb);
   int x[8], o[8];
-  jr_idct_pass1(tab, coef, qt, p, t, o);
+  const int ac = jr_idct_load(tab, coef, qt, p, t, x);
+  jidct_pass1(x, jidct_group8_or(ac), o);                               // (every lane shuffles, padding lanes with zero)
 #pragma unroll
   for (int k = 0; k < 8; ++k) ws[lb][k][t] = o[k];                      // ws[row][col]
   __syncthreads();

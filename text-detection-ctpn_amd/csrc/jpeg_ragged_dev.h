@@ -1,7 +1,7 @@
 // JPEG files of mixed sizes into one ragged canvas (include/ctpn_hip.h, ctpn_decode_jpeg_batch_ragged): the per-thread text of
 // jpeg_ragged.hip's two kernels as __host__ __device__ functions. The kernels call them with their thread indices;
 // tests/jpeg_ragged_host.cpp compiles this same text with g++ under ASan + UBSan and calls them from loops over those indices.
-//   IDCT            jpeg_idct_kernel's two passes (jpeg_pixel.h: jidct_pass1 by column, the caller's transpose, jidct_pass2 by row with the
+//   IDCT            jpeg_idct_kernel's two passes (jpeg_pixel.h: jidct_load + jidct_pass1 by column, the block's zero-rows flag in between, the caller's transpose, jidct_pass2 by row with the
 //                   clamp and one 8-byte store) with the image found per 8 x 8 block from a descriptor table instead of one JpegGeom for
 //                   the batch. The kernel's barrier (the host's loop over a workgroup's threads) stands between the passes.
 //   colour + resize jpeg_color_kernel followed by resize_linear_kernel (preprocess.hip) in one pass over the CANVAS: every canvas pixel is
@@ -57,6 +57,15 @@ RS_HD JrBlockPos jr_block_locate(const JrImage* __restrict__ tab, int n, long lo
 
 // the two passes (jpeg_pixel.h) on the block jr_block_locate found. A padding lane reads no descriptor and hands the pass null pointers,
 // which a lane that is not live never dereferences
+// (load: the dequantised column and the OR of its raw rows 1 .. 7; the caller ORs the block's eight and runs jidct_pass1)
+RS_HD int jr_idct_load(const JrImage* __restrict__ tab, const int16_t* __restrict__ coef, const uint16_t* __restrict__ qt /* [n][3][64] */,
+                       const JrBlockPos& p, int t, int (&x)[8]) {
+  const int16_t* blk = nullptr;
+  if (p.live) { const JrImage& d = tab[p.img]; blk = coef + d.coef_base + d.g.coef_off[p.c] + p.b * 64; }
+  return jidct_load(blk, qt + ((long long)p.img * 3 + p.c) * 64, p.live != 0, t, x);
+}
+
+// (pass 1 in one call, the flag read from the block itself: jpeg_pixel.h's form for a caller that runs the columns one after the other)
 RS_HD void jr_idct_pass1(const JrImage* __restrict__ tab, const int16_t* __restrict__ coef, const uint16_t* __restrict__ qt /* [n][3][64] */,
                          const JrBlockPos& p, int t, int (&o)[8]) {
   const int16_t* blk = nullptr;

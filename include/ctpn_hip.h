@@ -476,7 +476,16 @@ int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* 
  *   anchors, pre / post its top-N), copied to the host; synchronises the ctx's streams and reads only. CTPN_ERR_CAPACITY below the size given here:
  *   CTPN_PF_BOXES4 n x per_img x 4 fp32 | SORTED_KEYS n x npad uint64, the buffer the gather read | SORTED_BOXES n x pre x 4 fp32 | SORTED_SCORES
  *   n x pre fp32 | SORTED_ANCHOR n x pre int32 (rows of the three at and behind VALID_COUNTS[i] are stale) | VALID_COUNTS n int32 | COLID n x pre
- *   bytes (CTPN_ERR_STATE unless plan [6] was 2) | KEEP_IDX n x post int32 | KEEP_COUNTS n int32 | MW_SCRATCH n x 2048 bytes, zero between calls.
+ *   bytes (CTPN_ERR_STATE unless plan [6] was 2) | KEEP_IDX n x post int32 | KEEP_COUNTS n int32 | MW_SCRATCH n x 2048 bytes, zero between calls |
+ *   IM_INFO n x 3 fp32, the im_info rows on the device for the kernels behind decode_kernel (up to four images: decode_kernel publishes them).
+ * ctpn_debug_proposals_from_heads: ctpn_proposals on caller-supplied heads instead of a forward's -- decode_kernel's production branch (the
+ *   pair softmax inside the kernel, rows of 64 floats, the ragged filter), which ctpn_proposals_from_host enters behind. Any ctx, a
+ *   ctpn_create_postproc one included. heads: n x hf x wf rows of 64 fp32 as the heads GEMM stores them: [0, 40) ten anchors' (dx, dy, dw, dh),
+ *   [40, 60) their (bg, fg) logit pairs, [60, 64) unused (never read). valid_rows: NULL, or n ints -- feature rows of every image of a ragged
+ *   batch; the anchors of the rows at and below valid_rows[i] get invalid keys. Shape and pointer checks as ctpn_proposals_from_host. rois_out
+ *   n x post x 5, counts_out n; cls_prob_out (n x hf x wf x 20) and bbox_pred_out (n x hf x wf x 40): NULL or what the kernel stored for
+ *   rpn_cls_prob_reshape / rpn_bbox_pred. Afterwards ctpn_debug_proposal_fetch and ctpn_proposal_anchors read this call. On a ctx with a
+ *   network, ctpn_get_tensor's two proposal tensors are this call's until the next forward.
  * ctpn_debug_sort_keys: launch_sort_keys alone. keys: n_img x per_img; out: n_img x npad (npad = per_img rounded up to a power of two), the buffer
  *   that holds the result. Both device buffers are CTPN_SORT_POISON (a key that reads as valid) wherever the caller's keys are not, and followed
  *   by a guard row (a changed guard byte: CTPN_ERR_STATE). The one-workgroup form leaves [per_img, npad) alone (poison comes back); the segmented
@@ -484,11 +493,14 @@ int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* 
 #define CTPN_PROPOSAL_PLAN_INTS 9
 #define CTPN_SORT_POISON 0x00000000C3C3C3C3ull
 enum { CTPN_PF_BOXES4 = 0, CTPN_PF_SORTED_KEYS, CTPN_PF_SORTED_BOXES, CTPN_PF_SORTED_SCORES, CTPN_PF_SORTED_ANCHOR, CTPN_PF_VALID_COUNTS, CTPN_PF_COLID,
-       CTPN_PF_KEEP_IDX, CTPN_PF_KEEP_COUNTS, CTPN_PF_MW_SCRATCH };
+       CTPN_PF_KEEP_IDX, CTPN_PF_KEEP_COUNTS, CTPN_PF_MW_SCRATCH, CTPN_PF_IM_INFO };
 int ctpn_debug_proposal_plan(int nms_columns, int nms_prefix, int mw_scratch, int n, int hf_first, int hf_count, int wf_first, int wf_count,
                              int pre_nms_topn, int post_nms_topn, float nms_thresh, const float* im_widths, int* plans);
 int ctpn_debug_proposal_fetch(ctpn_ctx* ctx, int what, void* out, size_t capacity_bytes);
 int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_img, int per_img, int segmented, unsigned long long* out);
+int ctpn_debug_proposals_from_heads(ctpn_ctx* ctx, const float* heads, int n, int hf, int wf, const float* im_info, const int* valid_rows,
+                                    int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* rois_out, int* counts_out,
+                                    float* cls_prob_out, float* bbox_pred_out);
 /* The first layer's kernels alone (test hooks; null stream, buffers allocated and freed inside). The weights go through the chain
  * ctpn_load_weights_* uses (w_hwio 3 x 3 x 3 x 64 as the [27][64] block, bias[64], pack_conv1_frags). The image, n x h x w x 3 (h, w >= 16 as in
  * ctpn_forward; at most 64 images and 2^20 pixels), is copied to byte 64 + byte_offset of a device block whose every other byte -- 64 in front

@@ -127,6 +127,8 @@ def _declare(lib):
                                                f32p, i32p]),
         "ctpn_debug_proposal_fetch": (C.c_int, [vp, C.c_int, C.c_void_p, C.c_size_t]),
         "ctpn_debug_sort_keys": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+        "ctpn_debug_proposals_from_heads": (C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, i32p, C.c_int, C.c_int, C.c_float, C.c_float, f32p, i32p,
+                                                      f32p, f32p]),
         "ctpn_debug_conv1": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p,
                                        C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
         "ctpn_debug_conv1_fused": (C.c_int, [C.c_int, u8p, C.c_int, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_uint16)]),
@@ -961,6 +963,7 @@ PROPOSAL_FETCH = {
     "sorted_anchor": (4, np.int32, lambda a, p, pre, post: (pre,)), "valid_counts": (5, np.int32, lambda a, p, pre, post: ()),
     "colid": (6, np.uint8, lambda a, p, pre, post: (pre,)), "keep_idx": (7, np.int32, lambda a, p, pre, post: (post,)),
     "keep_counts": (8, np.int32, lambda a, p, pre, post: ()), "mw_scratch": (9, np.uint8, lambda a, p, pre, post: (2048,)),
+    "im_info": (10, np.float32, lambda a, p, pre, post: (3,)),
 }
 
 
@@ -1202,6 +1205,27 @@ class Context:
                                                   _ptr(counts, C.c_int)))
         out = [rois[i, : counts[i]].copy() for i in range(n)]
         return (out, self._anchors(n, post_nms_topn, counts)) if want_anchors else out
+
+    def proposals_from_heads(self, heads, im_info, valid_rows=None, pre_nms_topn=12000, post_nms_topn=1000, nms_thresh=0.7, min_size=8.0):
+        """ctpn_debug_proposals_from_heads: heads (n, hf, wf, 64) float32, the heads GEMM's rows -> (rois per image, anchors per image,
+        cls_prob (n, hf, wf, 20), bbox_pred (n, hf, wf, 40)) of decode_kernel's production branch. valid_rows: n feature-row counts (ragged)."""
+        hd = _f32(heads)
+        n, hf, wf, ld = hd.shape
+        if ld != 64:
+            raise ValueError("heads rows hold 64 floats")
+        info = _f32(im_info).reshape(-1, 3)
+        vr = None if valid_rows is None else np.ascontiguousarray(valid_rows, dtype=np.int32).reshape(-1)
+        if info.shape[0] != n or (vr is not None and vr.shape[0] != n):
+            raise ValueError("one im_info row (and one valid_rows entry) per image")
+        rois = np.zeros((n, post_nms_topn, 5), np.float32)
+        counts = np.zeros((n,), np.int32)
+        cls = np.zeros((n, hf, wf, 20), np.float32)
+        bbox = np.zeros((n, hf, wf, 40), np.float32)
+        _check(self._lib.ctpn_debug_proposals_from_heads(self._h, _ptr(hd, C.c_float), n, hf, wf, _ptr(info, C.c_float),
+                                                         None if vr is None else _ptr(vr, C.c_int), int(pre_nms_topn), int(post_nms_topn),
+                                                         float(nms_thresh), float(min_size), _ptr(rois, C.c_float), _ptr(counts, C.c_int),
+                                                         _ptr(cls, C.c_float), _ptr(bbox, C.c_float)))
+        return [rois[i, : counts[i]].copy() for i in range(n)], self._anchors(n, post_nms_topn, counts), cls, bbox
 
     # ---- whole path
     def detect(self, images=None, scales=None, mode="H", line_capacity=512, device_ptr=None, shape=None,

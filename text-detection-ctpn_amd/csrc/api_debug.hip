@@ -468,11 +468,42 @@ int ctpn_debug_proposal_fetch(ctpn_ctx* c, int what, void* out, size_t capacity_
     case CTPN_PF_MW_SCRATCH:
       if (!c->nms_mw_scratch || n > (size_t)NMS_MW_CAP_BATCH) return fail(CTPN_ERR_STATE, "ctpn_debug_proposal_fetch: no multi-workgroup scratch for that many images");
       src = c->nms_mw_scratch; row = pitch = NMS_MW_SCRATCH_BYTES; break;
+    case CTPN_PF_IM_INFO: src = c->im_info_dev; row = pitch = 12; break;
     default: return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_fetch: unknown intermediate");
   }
   if (capacity_bytes < n * row) return fail(CTPN_ERR_CAPACITY, "ctpn_debug_proposal_fetch: the intermediate takes " + std::to_string(n * row) + " bytes");
   CTPN_HIP_TRY(hipMemcpy2D(out, row, src, pitch, row, n, hipMemcpyDeviceToHost));
   return CTPN_OK;
+}
+
+// decode_kernel's production branch (heads != nullptr: the in-kernel pair softmax, head_ld = 64, valid_rows) on caller-supplied heads: what
+// ctpn_proposals runs behind a forward, here behind an upload. A post-processing-only ctx has no heads buffer, so the rows live in a block of
+// this call's own.
+int ctpn_debug_proposals_from_heads(ctpn_ctx* c, const float* heads, int n, int hf, int wf, const float* im_info, const int* valid_rows,
+                                    int pre_nms_topn, int post_nms_topn, float nms_thresh, float min_size, float* rois_out, int* counts_out,
+                                    float* cls_prob_out, float* bbox_pred_out) {
+  if (!c || !heads || !im_info || !rois_out || !counts_out) return fail(CTPN_ERR_ARG, "ctpn_debug_proposals_from_heads: null pointer");
+  if (n <= 0 || n > c->max_batch || hf <= 0 || wf <= 0 || (size_t)n * hf * wf > c->m5_max)
+    return fail(CTPN_ERR_CAPACITY, "ctpn_debug_proposals_from_heads: shape outside what the ctx was created for");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  const size_t m = (size_t)n * hf * wf;
+  DevBuf d_heads, d_valid;
+  int rc;
+  if ((rc = d_heads.alloc(m * 64 * sizeof(float))) || (valid_rows && (rc = d_valid.alloc((size_t)n * sizeof(int))))) return rc;
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));   // the asynchronous detect path shares the proposal buffers
+  CTPN_HIP_TRY(hipMemcpy(d_heads.get(), heads, m * 64 * sizeof(float), hipMemcpyHostToDevice));
+  if (valid_rows) CTPN_HIP_TRY(hipMemcpy(d_valid.get(), valid_rows, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  hipStream_t s = c->stream;
+  rc = enqueue_proposals(c, d_heads.as<float>(), /*heads_are_probs*/ 0, n, hf, wf, im_info, pre_nms_topn, post_nms_topn, nms_thresh, min_size, nullptr, nullptr,
+                         valid_rows ? d_valid.as<int>() : nullptr);
+  // (the blocks above are released on return: nothing of this call may still be in flight then, whatever it returns)
+  if (!rc && (hipMemcpyAsync(counts_out, c->keep_counts, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+              hipMemcpyAsync(rois_out, c->rois, (size_t)n * post_nms_topn * 5 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+              (cls_prob_out && hipMemcpyAsync(cls_prob_out, c->cls_prob, m * 20 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+              (bbox_pred_out && hipMemcpyAsync(bbox_pred_out, c->bbox_pred, m * 40 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess)))
+    rc = fail(CTPN_ERR_HIP, "ctpn_debug_proposals_from_heads: copy failed");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(CTPN_ERR_HIP, "ctpn_debug_proposals_from_heads: kernel failed");
+  return rc;
 }
 
 int ctpn_debug_sort_keys(int device_id, const unsigned long long* keys, int n_img, int per_img, int segmented, unsigned long long* out) {

@@ -119,7 +119,7 @@ const char* ctpn_option_name(int index);
  * computes bit for bit what it did while the values were compiled in.
  *   name                       default  accepted
  *   RPN_PRE_NMS_TOP_N          12000    integral, 1 .. 12000 (the ctx's buffers are sized for the default)
- *   RPN_POST_NMS_TOP_N         1000     integral, 1 .. 1000  (likewise; the device connector holds 1024 proposals per image in LDS)
+ *   RPN_POST_NMS_TOP_N         1000     integral, 1 .. capacity (ctpn_reserve_proposals; 1000 on a fresh ctx)
  *   RPN_NMS_THRESH             0.7      0 .. 1 (below 0.1 the generic NMS kernel runs instead of the column decomposition: same keep lists)
  *   RPN_MIN_SIZE               8        >= 0
  *   TEXT_PROPOSALS_MIN_SCORE   0.7      finite
@@ -135,13 +135,27 @@ const char* ctpn_option_name(int index);
  * |value| <= 3e38); MIN_RATIO, LINE_MIN_SCORE and MIN_LINE_WIDTH are compared in fp64 (filter_boxes). No kernel bounds a value more tightly
  * than the table says. ctpn_set_param follows ctpn_set_option's contract: the ctx drains its streams first, CTPN_ERR_STATE while a submitted
  * batch is uncollected, CTPN_ERR_ARG for an unknown name, a NaN or a value outside its range. ctpn_get_param returns the value as set.
- * With RPN_POST_NMS_TOP_N below 1000, rois_out / keep_out of ctpn_detect*, ctpn_debug_text_lines still hold 1000 rows per image (fewer of
- * them valid). ctpn_param_count / ctpn_param_name enumerate the names; ctpn_param_default needs no ctx and no device. */
+ * With RPN_POST_NMS_TOP_N below the capacity, rois_out / keep_out of ctpn_detect*, ctpn_debug_text_lines still hold capacity rows per image
+ * (fewer of them valid). ctpn_param_count / ctpn_param_name enumerate the names; ctpn_param_default needs no ctx and no device. */
 int         ctpn_set_param(ctpn_ctx* ctx, const char* name, double value);
 int         ctpn_get_param(ctpn_ctx* ctx, const char* name, double* value_out);
 int         ctpn_param_count(void);
 const char* ctpn_param_name(int index);
 int         ctpn_param_default(const char* name, double* value_out);
+/* The proposal capacity of ONE ctx (additive in ABI 10): the rows per image of rois_out, keep_out and anchors_out towards the caller, and the
+ * upper bound of RPN_POST_NMS_TOP_N and of every post_nms_topn argument. The reference reads cfg.TEST.RPN_POST_NMS_TOP_N at run time and
+ * takes any value (lib/rpn_msr/proposal_layer_tf.py:55; lib/fast_rcnn/config.py:180 sets 1000); a proposal is a 16-pixel slice of a line, so
+ * 1000 of them cover about 17 full-width lines of a 600 x 900 page, and a dense page needs more. A fresh ctx has capacity 1000 and refuses
+ * 1001 everywhere, as ever. ctpn_reserve_proposals(ctx, post_capacity), 1000 .. CTPN_POST_NMS_CAPACITY_MAX, replaces every buffer of the
+ * tail that is laid out by the capacity (the slots' page-locked blocks among them); results of earlier ctpn_proposals* calls are no longer
+ * readable afterwards (ctpn_proposal_anchors, ctpn_debug_proposal_fetch: CTPN_ERR_STATE). ctpn_set_option's contract: the ctx drains its streams
+ * first, CTPN_ERR_STATE while a submitted batch is uncollected; CTPN_ERR_ARG outside the range or below the ctx's current
+ * RPN_POST_NMS_TOP_N; a failed allocation (CTPN_ERR_HIP) leaves the ctx as it was. Works on a ctpn_create_postproc ctx too. Above 1024 rows
+ * per image (RPN_POST_NMS_TOP_N, not the capacity) the text-line tail takes other kernel forms (ctpn_debug_text_line_plan); the device
+ * connector returns up to capacity / 2 lines per image and mode. ctpn_proposal_capacity reports the capacity. */
+#define CTPN_POST_NMS_CAPACITY_MAX 4096
+int         ctpn_reserve_proposals(ctpn_ctx* ctx, int post_capacity);
+int         ctpn_proposal_capacity(ctpn_ctx* ctx, int* rows_out);
 /* Host worker threads of a ctx (per-image connector work of ctpn_detect_collect, staging copies of pageable images): one
  * persistent pool per ctx, created in ctpn_create. Size = ctpn_host_thread_budget(hardware cores, LOCAL_WORLD_SIZE of the
  * launcher (torchrun), CTPN_HOST_THREADS): `requested` if > 0, else cores / ranks-on-this-node clamped to [1, 32].
@@ -321,7 +335,7 @@ int ctpn_draw_boxes(uint8_t* img_bgr, int h, int w, const double* recs, int n_li
  * Replaces the body of ctpn() in ctpn/demo.py:55-68 between imread/resize and draw_boxes for a
  * batch: forward -> proposals -> (boxes / scale) -> text lines. scales: n floats (im_scales[0] of
  * lib/fast_rcnn/test.py:57, 1.0 when the image is already at network resolution).
- * recs_out: n x line_capacity x 9 float64, line_counts: n ints; rois_out (n x 1000 x 5) / roi_counts may be NULL.
+ * recs_out: n x line_capacity x 9 float64, line_counts: n ints; rois_out (n x capacity x 5, ctpn_proposal_capacity) / roi_counts may be NULL.
  * The proposal layer's four values and the connector's thresholds are the ctx's parameters (ctpn_set_param). */
 int ctpn_detect(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w,
                 const float* scales, int mode, double* recs_out, int line_capacity, int* line_counts,
@@ -472,6 +486,7 @@ int ctpn_debug_gemm(int device_id, const float* a, const float* w, const float* 
  *   [2] sort: 0 one workgroup per image, 1 segmented (eight workgroups + merge_rank_kernel)   [3] keys per sort workgroup   [4] keys of the last one
  *   [5] merge_rank_kernel workgroups per image (0: none)   [6] NMS: 0 generic (nms_kernel), 1 column form on one workgroup per image, 2 column groups
  *   [7] column-group workgroups per image (0 in the other forms)   [8] prefix pass: 0 none, 1 inside the kernel, 2 a prefix and a full launch
+ *       (none above post_nms_topn = 1024: the 4096 best-scored ranks would rarely hold that many survivors, and the pass would run twice)
  * ctpn_debug_proposal_fetch: one intermediate of the ctx's LAST ctpn_proposals / ctpn_proposals_from_host call (n images, per_img = hf x wf x 10
  *   anchors, pre / post its top-N), copied to the host; synchronises the ctx's streams and reads only. CTPN_ERR_CAPACITY below the size given here:
  *   CTPN_PF_BOXES4 n x per_img x 4 fp32 | SORTED_KEYS n x npad uint64, the buffer the gather read | SORTED_BOXES n x pre x 4 fp32 | SORTED_SCORES
@@ -534,12 +549,22 @@ int ctpn_debug_connect(int device_id, const float* rois, int r, int im_h, int im
 /* The text-line tail of ctpn_detect_submit / ctpn_detect_collect on caller-supplied rois: the SAME enqueue function the submit calls
  * (lines_prep_kernel, the connector's NMS 0.2 in the form options nms_columns and the batch size select, connect_kernel with option
  * connect_device = 1) on the ctx's proposal stream, then what the collect does (device records, or connect_lines on the host with
- * connect_device = 0). Works on any ctx, a ctpn_create_postproc one included. rois: n x 1000 x 5 fp32 [score,x1,y1,x2,y2] per image in
+ * connect_device = 0). Works on any ctx, a ctpn_create_postproc one included. rois: n x capacity x 5 fp32 [score,x1,y1,x2,y2] per image in
  * descending score order, roi_counts[n] rows of each are valid (0 .. RPN_POST_NMS_TOP_N); n <= max_batch; im_h x im_w is every image's network size
  * (im_w / 16 columns of the anchor grid), scales[n] (NULL: 1.0) the im_info scale the boxes are divided by. recs_out: n x line_capacity
  * x 9, line_counts[n] as ctpn_detect_collect returns them (the true count also where CTPN_ERR_CAPACITY is returned). keep_out
- * (nullable): n x 1000 indices into the image's rois that survived the connector's NMS, keep_counts[n] of them. With option nms_check
- * = 1 a column-decomposed NMS is followed by the generic kernel on the same boxes and a difference is CTPN_ERR_STATE. Test hook. */
+ * (nullable): n x capacity indices into the image's rois that survived the connector's NMS, keep_counts[n] of them. With option nms_check
+ * = 1 a column-decomposed NMS is followed by the generic kernel on the same boxes and a difference is CTPN_ERR_STATE. Test hook.
+ * ctpn_debug_text_line_plan: what that tail launches -- the function enqueue_text_lines itself computes once and follows. Pure host arithmetic,
+ * no device. For options nms_columns / connect_device, a ctx with (mw_scratch = 1) or without the multi-workgroup NMS's scratch, n images of
+ * `rows` rows each (RPN_POST_NMS_TOP_N, 1 .. CTPN_POST_NMS_CAPACITY_MAX) on a map wf columns wide, TEXT_PROPOSALS_NMS_THRESH and the largest
+ * im_info scale of the batch. plan[CTPN_TEXT_LINE_PLAN_INTS]:
+ *   [0] NMS: 0 generic (nms_kernel), 1 column form on one workgroup of 4 waves per image, 2 column groups, 3 column form on one workgroup of 16
+ *       waves per image (more than 1024 rows)
+ *   [1] connector: 0 host (connect_lines at collect), 1 connect_kernel (all pairs, up to 1024 rows), 2 connect_large_kernel (anchor-column buckets)
+ *   [2] column-group workgroups per image (0 in the other forms) */
+#define CTPN_TEXT_LINE_PLAN_INTS 3
+int ctpn_debug_text_line_plan(int nms_columns, int connect_device, int mw_scratch, int n, int wf, int rows, float nms_thresh, float max_scale, int* plan);
 int ctpn_debug_text_lines(ctpn_ctx* ctx, const float* rois, const int* roi_counts, int n, int im_h, int im_w, const float* scales, int mode,
                           double* recs_out, int line_capacity, int* line_counts, int* keep_out, int* keep_counts);
 

@@ -64,6 +64,9 @@ def _declare(lib):
         "ctpn_param_count": (C.c_int, []),
         "ctpn_param_name": (C.c_char_p, [C.c_int]),
         "ctpn_param_default": (C.c_int, [C.c_char_p, f64p]),
+        "ctpn_reserve_proposals": (C.c_int, [vp, C.c_int]),
+        "ctpn_proposal_capacity": (C.c_int, [vp, i32p]),
+        "ctpn_debug_text_line_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, i32p]),
         "ctpn_last_error": (C.c_char_p, []),
         "ctpn_device_count": (C.c_int, []),
         "ctpn_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -978,6 +981,34 @@ def proposal_plan_sweep(n, hf_first, hf_count, wf_first, wf_count, pre=12000, po
     return out
 
 
+POST_NMS_CAPACITY_MAX = 4096      # CTPN_POST_NMS_CAPACITY_MAX
+TEXT_LINE_NMS_FORMS = ("generic", "one_wg", "column_groups", "one_wg_large")
+TEXT_LINE_CONN_FORMS = ("host", "all_pairs", "buckets")
+
+
+def text_line_plan(n, wf, rows, thresh=0.2, max_scale=1.0, nms_columns=1, connect_device=0, mw_scratch=True):
+    """ctpn_debug_text_line_plan: (NMS form, connector form, column-group workgroups per image) of the text-line tail. No device."""
+    out = np.zeros((3,), np.int32)
+    _check(load_library().ctpn_debug_text_line_plan(int(nms_columns), int(connect_device), 1 if mw_scratch else 0, int(n), int(wf), int(rows),
+                                                    float(thresh), float(max_scale), _ptr(out, C.c_int)))
+    return TEXT_LINE_NMS_FORMS[out[0]], TEXT_LINE_CONN_FORMS[out[1]], int(out[2])
+
+
+def check_post_nms_topn(post_nms_topn):
+    """cfg.TEST.RPN_POST_NMS_TOP_N as the mirror modules read it: the reference takes any value, this library up to POST_NMS_CAPACITY_MAX."""
+    post = int(post_nms_topn)
+    if post > POST_NMS_CAPACITY_MAX:
+        raise ValueError("RPN_POST_NMS_TOP_N = %d exceeds the limit of %d proposals per image (CTPN_POST_NMS_CAPACITY_MAX)" % (post, POST_NMS_CAPACITY_MAX))
+    return post
+
+
+def reserve_for(ctx, post_nms_topn):
+    """What the mirror modules do before a proposal call: raise the ctx's capacity where cfg.TEST.RPN_POST_NMS_TOP_N exceeds it."""
+    post = check_post_nms_topn(post_nms_topn)
+    if post > ctx.proposal_capacity:
+        ctx.reserve_proposals(post)
+
+
 def proposal_plan(n, hf, wf, **kw):
     """The plan of one ctpn_proposals* call as a ProposalPlan of names and numbers (see ctpn_debug_proposal_plan)."""
     p = [int(v) for v in proposal_plan_sweep(n, hf, 1, wf, 1, **kw)[0, 0]]
@@ -1034,6 +1065,20 @@ class Context:
     def get_param(self, name):
         v = C.c_double(0.0)
         _check(self._lib.ctpn_get_param(self._h, name.encode(), C.byref(v)))
+        return v.value
+
+    def reserve_proposals(self, n):
+        """ctpn_reserve_proposals: room for RPN_POST_NMS_TOP_N up to n (1000 .. POST_NMS_CAPACITY_MAX) proposals per image."""
+        n = int(n)
+        if n > POST_NMS_CAPACITY_MAX:
+            raise ValueError("proposal capacity %d exceeds the limit of %d (CTPN_POST_NMS_CAPACITY_MAX)" % (n, POST_NMS_CAPACITY_MAX))
+        _check(self._lib.ctpn_reserve_proposals(self._h, n))
+
+    @property
+    def proposal_capacity(self):
+        """ctpn_proposal_capacity: rows per image of the rois / keep / anchor arrays (1000 on a fresh ctx)."""
+        v = C.c_int(0)
+        _check(self._lib.ctpn_proposal_capacity(self._h, C.byref(v)))
         return v.value
 
     def forward_sets(self):
@@ -1243,7 +1288,7 @@ class Context:
         sc = _f32(scales if scales is not None else np.ones((n,), np.float32)).reshape(-1)
         recs = np.zeros((n, line_capacity, 9), np.float64)
         lcnt = np.zeros((n,), np.int32)
-        rois = np.zeros((n, 1000, 5), np.float32) if want_rois else None
+        rois = np.zeros((n, self.proposal_capacity, 5), np.float32) if want_rois else None
         rcnt = np.zeros((n,), np.int32) if want_rois else None
         m = MODE_O if str(mode).upper().startswith("O") else MODE_H
         _check(self._lib.ctpn_detect(self._h, ptr, on_dev, int(n), int(h), int(w), _ptr(sc, C.c_float), m,
@@ -1262,7 +1307,7 @@ class Context:
         sc = _f32(scales if scales is not None else np.ones((n,), np.float32)).reshape(-1)
         recs = np.zeros((n, line_capacity, 9), np.float64)
         lcnt = np.zeros((n,), np.int32)
-        rois = np.zeros((n, 1000, 5), np.float32) if want_rois else None
+        rois = np.zeros((n, self.proposal_capacity, 5), np.float32) if want_rois else None
         rcnt = np.zeros((n,), np.int32) if want_rois else None
         m = MODE_O if str(mode).upper().startswith("O") else MODE_H
         _check(self._lib.ctpn_detect_ragged(self._h, ptr, on_dev, n, hc, w, _ptr(hts, C.c_int), _ptr(sc, C.c_float), m,
@@ -1279,7 +1324,7 @@ class Context:
         -> (lines, keeps): per image the (M, 9) records of `mode` and the roi indices the connector's NMS kept. On CTPN_ERR_CAPACITY the
         raised CtpnError carries the true counts as .line_counts."""
         n = len(rois)
-        packed = np.zeros((n, 1000, 5), np.float32)
+        packed = np.zeros((n, self.proposal_capacity, 5), np.float32)
         rcnt = np.zeros((n,), np.int32)
         for i, r in enumerate(rois):
             r = _f32(r).reshape(-1, 5)
@@ -1290,7 +1335,7 @@ class Context:
             raise ValueError("one scale per image")
         recs = np.zeros((n, max(line_capacity, 1), 9), np.float64)
         lcnt = np.zeros((n,), np.int32)
-        keep = np.zeros((n, 1000), np.int32)
+        keep = np.zeros((n, self.proposal_capacity), np.int32)
         kcnt = np.zeros((n,), np.int32)
         m = MODE_O if str(mode).upper().startswith("O") else MODE_H
         try:
@@ -1733,7 +1778,7 @@ class Context:
         n = self._slot_n[slot]
         recs = np.zeros((n, line_capacity, 9), np.float64)
         lcnt = np.zeros((n,), np.int32)
-        rois = np.zeros((n, 1000, 5), np.float32) if want_rois else None
+        rois = np.zeros((n, self.proposal_capacity, 5), np.float32) if want_rois else None
         rcnt = np.zeros((n,), np.int32) if want_rois else None
         m = MODE_O if str(mode).upper().startswith("O") else MODE_H
         _check(self._lib.ctpn_detect_collect(self._h, int(slot), m, _ptr(recs, C.c_double), int(line_capacity), _ptr(lcnt, C.c_int),

@@ -111,6 +111,46 @@ static PackLayout pack_layout(size_t mb, size_t post) {
   return L;
 }
 
+// Everything of a ctx that is laid out by its proposal capacity (ctx.h, post_max): built as a whole, then adopted as a whole, so that a failed
+// allocation in ctpn_reserve_proposals leaves the ctx as it was.
+struct TailSet { ctpn_ctx::TailBufs dev; PinnedBuf pack[2], crecs[2]; };
+static int tail_alloc(int max_batch, int post, TailSet& t) {
+  const size_t mb = (size_t)max_batch, rows = (size_t)post, cap = rows / 2;
+  const PackLayout L = pack_layout(mb, rows);
+  const size_t work = connect_work_bytes(post);
+  int rc;
+  if ((rc = t.dev.out_pack.alloc(L.total)) || (rc = t.dev.roi_anchor.alloc(mb * rows * sizeof(int))) || (rc = t.dev.tl_spill.alloc(mb * rows * 4 * sizeof(float))) ||
+      (rc = t.dev.conn_recs.alloc(mb * 2 * cap * 9 * sizeof(double))) || (rc = t.dev.conn_scratch.alloc(mb * (rows < 1024 ? 1024 : rows) * 20 * sizeof(double))) ||
+      (work && (rc = t.dev.conn_work.alloc(mb * work)))) return rc;
+  for (int k = 0; k < 2; ++k)
+    if ((rc = t.pack[k].alloc(L.total)) || (rc = t.crecs[k].alloc(mb * 2 * cap * 9 * sizeof(double)))) return rc;
+  return CTPN_OK;
+}
+// the ctx is idle (streams drained or not yet used); the new device blocks are zeroed on the ctx's stream where create always zeroed them
+static int tail_adopt(ctpn_ctx* c, int post, TailSet& t) {
+  const PackLayout L = pack_layout((size_t)c->max_batch, (size_t)post);
+  CTPN_HIP_TRY(hipMemsetAsync(t.dev.out_pack.get(), 0, L.total, c->stream));
+  CTPN_HIP_TRY(hipMemsetAsync(t.dev.roi_anchor.get(), 0, t.dev.roi_anchor.bytes(), c->stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
+  c->tail = std::move(t.dev);
+  c->post_max = post; c->conn_cap = post / 2;
+  c->pack_bytes = L.total;
+  c->out_pack = c->tail.out_pack.as<char>();
+  c->tl_boxes = (float*)(c->out_pack + L.tlb); c->tl_scores = (float*)(c->out_pack + L.tls); c->tl_keep = (int*)(c->out_pack + L.keep);
+  c->tl_keep_counts = (int*)(c->out_pack + L.kcnt); c->rois = (float*)(c->out_pack + L.rois); c->keep_counts = (int*)(c->out_pack + L.rcnt);
+  c->roi_anchor = c->tail.roi_anchor.as<int>(); c->tl_spill = c->tail.tl_spill.as<float>();
+  c->conn_recs = c->tail.conn_recs.as<double>(); c->conn_scratch = c->tail.conn_scratch.as<double>(); c->conn_work = c->tail.conn_work.as<char>();
+  for (int k = 0; k < 2; ++k) {
+    ctpn_ctx::Slot& sl = c->slot[k];
+    sl.pack = std::move(t.pack[k]); sl.crecs = std::move(t.crecs[k]);
+    char* pack = sl.pack.as<char>();
+    sl.tlb = (float*)(pack + L.tlb); sl.tls = (float*)(pack + L.tls); sl.keep = (int*)(pack + L.keep); sl.kcnt = (int*)(pack + L.kcnt);
+    sl.rois = (float*)(pack + L.rois); sl.rcnt = (int*)(pack + L.rcnt);
+  }
+  c->last_post = 0; c->last_prop_n = 0;      // what ctpn_proposal_anchors / ctpn_debug_proposal_fetch would read is gone
+  return CTPN_OK;
+}
+
 static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, int max_w, int precision, bool postproc_only) {
   if (!out) return fail(CTPN_ERR_ARG, "ctpn_create: out is null");
   *out = nullptr;
@@ -167,13 +207,15 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   if (f0.ev_conv.ensure() != CTPN_OK || f0.ev_tail.ensure() != CTPN_OK || f0.ev_gate.ensure() != CTPN_OK) return fail(CTPN_ERR_HIP, "ctpn_create: events");
   for (auto& sl : c->slot) {
     const size_t mb = (size_t)max_batch;
-    const PackLayout L = pack_layout(mb, (size_t)c->post_max);
-    const bool ok = sl.pack.alloc(L.total) == CTPN_OK && sl.im_info.alloc(mb * 3 * sizeof(float)) == CTPN_OK && sl.crecs.alloc(mb * 2 * CONN_CAP * 9 * sizeof(double)) == CTPN_OK &&
+    const bool ok = sl.im_info.alloc(mb * 3 * sizeof(float)) == CTPN_OK &&
                     sl.ccnt.alloc(mb * 3 * sizeof(int)) == CTPN_OK && sl.ev_heads.ensure() == CTPN_OK && sl.ev_decoded.ensure() == CTPN_OK && sl.ev_done.ensure() == CTPN_OK;
     if (!ok) return fail(CTPN_ERR_HIP, "ctpn_create: pinned host buffers / events");
-    char* pack = sl.pack.as<char>();
-    sl.tlb = (float*)(pack + L.tlb); sl.tls = (float*)(pack + L.tls); sl.keep = (int*)(pack + L.keep); sl.kcnt = (int*)(pack + L.kcnt);
-    sl.rois = (float*)(pack + L.rois); sl.rcnt = (int*)(pack + L.rcnt);
+  }
+  {
+    // what the proposal capacity lays out (the slots' packs and connector records among it), at the default capacity
+    TailSet t;
+    if (tail_alloc(max_batch, c->post_max, t) != CTPN_OK) return fail(CTPN_ERR_HIP, "ctpn_create: pinned host buffers / events");
+    if ((rc = tail_adopt(c, c->post_max, t))) return rc;
   }
 
   const int hf = lvl(max_h, 4), wf = lvl(max_w, 4);
@@ -246,26 +288,14 @@ static int create_impl(ctpn_ctx** out, int device_id, int max_batch, int max_h, 
   A((void**)&c->sorted_scores, (size_t)max_batch * c->topn_max * sizeof(float), false);
   A((void**)&c->valid_counts, (size_t)max_batch * sizeof(int), true);
   A((void**)&c->keep_idx, (size_t)max_batch * c->topn_max * sizeof(int), false);
-  {
-    // what a submitted batch hands back to the host -- connector front end (tl_*), rois and their counts -- as views into one block
-    const PackLayout L = pack_layout((size_t)max_batch, (size_t)c->post_max);
-    c->pack_bytes = L.total;
-    A((void**)&c->out_pack, L.total, true);
-    if (c->out_pack) {
-      c->tl_boxes = (float*)(c->out_pack + L.tlb); c->tl_scores = (float*)(c->out_pack + L.tls); c->tl_keep = (int*)(c->out_pack + L.keep);
-      c->tl_keep_counts = (int*)(c->out_pack + L.kcnt); c->rois = (float*)(c->out_pack + L.rois); c->keep_counts = (int*)(c->out_pack + L.rcnt);
-    }
-  }
+  // (what a submitted batch hands back to the host -- connector front end (tl_*), rois and their counts -- and the other blocks laid out by the
+  // proposal capacity: tail_adopt above)
   A((void**)&c->kept_spill, (size_t)max_batch * c->topn_max * 4 * sizeof(float), false);
   A((void**)&c->sorted_anchor, (size_t)max_batch * c->topn_max * sizeof(int), false);
-  A((void**)&c->roi_anchor, (size_t)max_batch * c->post_max * sizeof(int), true);
   A((void**)&c->tl_counts, (size_t)max_batch * sizeof(int), true);
-  A((void**)&c->tl_spill, (size_t)max_batch * c->post_max * 4 * sizeof(float), false);
   A((void**)&c->nms_mw_scratch, (size_t)NMS_MW_CAP_BATCH * NMS_MW_SCRATCH_BYTES, true);
   A((void**)&c->nms_colid, (size_t)NMS_MW_CAP_BATCH * ((c->topn_max + 15) & ~15), true);
-  A((void**)&c->conn_recs, (size_t)max_batch * 2 * CONN_CAP * 9 * sizeof(double), false);
   A((void**)&c->conn_counts, (size_t)max_batch * 3 * sizeof(int), true);
-  A((void**)&c->conn_scratch, (size_t)max_batch * 1024 * 20 * sizeof(double), false);
   A((void**)&c->im_info_dev, (size_t)max_batch * 3 * sizeof(float), true);
   if (rc == CTPN_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(CTPN_ERR_HIP, "ctpn_create: sync failed");
   if (rc != CTPN_OK) return rc;
@@ -411,7 +441,9 @@ int ctpn_set_param(ctpn_ctx* c, const char* name, double value) {
   if (!c || !name) return fail(CTPN_ERR_ARG, "ctpn_set_param: null pointer");
   const int idx = tail_param_index(name);
   if (idx < 0) return fail(CTPN_ERR_ARG, std::string("ctpn_set_param: unknown parameter ") + name);
-  if (!tail_param_ok(idx, value)) return fail(CTPN_ERR_ARG, std::string("ctpn_set_param: value out of range for ") + name);
+  // RPN_POST_NMS_TOP_N: 1 .. the ctx's proposal capacity (1000 on a fresh ctx, the table's bound; ctpn_reserve_proposals raises it)
+  const bool ok = idx == TP_RPN_POST_NMS_TOP_N ? (value >= 1.0 && value <= (double)c->post_max && value == std::floor(value)) : tail_param_ok(idx, value);
+  if (!ok) return fail(CTPN_ERR_ARG, std::string("ctpn_set_param: value out of range for ") + name);
   if (c->tail_raw[idx] == value) return CTPN_OK;
   // the queued tail reads these (and lays its buffers out by RPN_POST_NMS_TOP_N): drain first
   CTPN_HIP_TRY(hipSetDevice(c->device));
@@ -430,6 +462,32 @@ int ctpn_set_param(ctpn_ctx* c, const char* name, double value) {
   }
   return CTPN_OK;
 }
+// ---- the proposal capacity: ctpn_set_option's contract ----
+int ctpn_reserve_proposals(ctpn_ctx* c, int post_capacity) {
+  if (!c) return fail(CTPN_ERR_ARG, "ctpn_reserve_proposals: null ctx");
+  if (post_capacity < 1000 || post_capacity > CTPN_POST_NMS_CAPACITY_MAX) return fail(CTPN_ERR_ARG, "ctpn_reserve_proposals: post_capacity must be in 1000.." + std::to_string(CTPN_POST_NMS_CAPACITY_MAX));
+  if (post_capacity < c->rpn_post) return fail(CTPN_ERR_ARG, "ctpn_reserve_proposals: post_capacity is below the ctx's RPN_POST_NMS_TOP_N (" + std::to_string(c->rpn_post) + "); lower the parameter first");
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(sync_forwards(c));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  for (auto& sl : c->slot) if (sl.busy) return fail(CTPN_ERR_STATE, "ctpn_reserve_proposals: a submitted batch has not been collected");
+  if (post_capacity == c->post_max) return CTPN_OK;
+  TailSet t;
+  int rc;
+  if ((rc = tail_alloc(c->max_batch, post_capacity, t))) {      // (t dies here: the ctx is as it was)
+    (void)hipGetLastError();
+    return fail(rc, std::string("ctpn_reserve_proposals: ") + ctpn_last_error());
+  }
+  for (auto& f : c->fs) f.tail_pending = false;
+  c->nms_mw_dirty = true;
+  return tail_adopt(c, post_capacity, t);
+}
+int ctpn_proposal_capacity(ctpn_ctx* c, int* rows_out) {
+  if (!c || !rows_out) return fail(CTPN_ERR_ARG, "ctpn_proposal_capacity: null pointer");
+  *rows_out = c->post_max;
+  return CTPN_OK;
+}
+
 int ctpn_get_param(ctpn_ctx* c, const char* name, double* value_out) {
   if (!c || !name || !value_out) return fail(CTPN_ERR_ARG, "ctpn_get_param: null pointer");
   const int idx = tail_param_index(name);

@@ -443,6 +443,15 @@ int ctpn_debug_proposal_plan(int nms_columns, int nms_prefix, int mw_scratch, in
   return CTPN_OK;
 }
 
+int ctpn_debug_text_line_plan(int nms_columns, int connect_device, int mw_scratch, int n, int wf, int rows, float nms_thresh, float max_scale, int* plan) {
+  if (!plan) return fail(CTPN_ERR_ARG, "ctpn_debug_text_line_plan: no output");
+  if (nms_columns < 0 || nms_columns > 3 || n <= 0 || wf <= 0 || rows <= 0 || rows > CTPN_POST_NMS_CAPACITY_MAX)
+    return fail(CTPN_ERR_ARG, "ctpn_debug_text_line_plan: nms_columns 0 .. 3, n and wf positive, rows 1 .. 4096");
+  const TextLinePlan p = text_line_plan(nms_columns, connect_device != 0, mw_scratch != 0, n, wf, rows, nms_thresh, max_scale);
+  plan[0] = p.nms_form; plan[1] = p.conn_form; plan[2] = p.group_wgs;
+  return CTPN_OK;
+}
+
 int ctpn_debug_proposal_fetch(ctpn_ctx* c, int what, void* out, size_t capacity_bytes) {
   if (!c || !out) return fail(CTPN_ERR_ARG, "ctpn_debug_proposal_fetch: null pointer");
   if (c->last_prop_n <= 0) return fail(CTPN_ERR_STATE, "ctpn_debug_proposal_fetch: no ctpn_proposals / ctpn_proposals_from_host call yet");

@@ -12,6 +12,7 @@ namespace ctpn {
 static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hipStream_t p, int* nms_form = nullptr) {
   const int post = c->rpn_post;
   const float tl_thresh = c->conn.nms_thresh;
+  TextLinePlan plan{};
   int rc;
   {
     Timed t(c, CTPN_KIND_NMS, (double)n * post * 24.0, p);
@@ -19,22 +20,27 @@ static int enqueue_text_lines(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, hip
     float max_scale = 0.f;
     const float* info = sl.im_info.as<float>();
     for (int i = 0; i < n; ++i) max_scale = info[3 * i + 2] > max_scale ? info[3 * i + 2] : max_scale;
-    if (c->nms_columns && nms_columns_tl_ok(lvl(w, 4), post, tl_thresh, max_scale)) {
-      const bool mw = nms_multi_wg(c, n, 0);
+    const int wf = lvl(w, 4);
+    plan = text_line_plan(c->nms_columns, c->connect_device, c->nms_mw_scratch != nullptr, n, wf, post, tl_thresh, max_scale);
+    if (plan.nms_form != TL_NMS_GENERIC) {
+      const bool mw = plan.nms_form == TL_NMS_COLUMN_GROUPS;
       if (nms_form) *nms_form = mw ? 2 : 1;
       if ((rc = launch_nms_columns(c->tl_boxes, c->tl_scores, c->tl_counts, post, tl_thresh, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
-                                   c->tl_spill, n, lvl(w, 4), p, nullptr, nullptr, c->im_info_dev, mw ? c->nms_mw_scratch : nullptr))) return rc;
+                                   c->tl_spill, n, wf, p, nullptr, nullptr, c->im_info_dev, mw ? c->nms_mw_scratch : nullptr))) return rc;
     } else {
       if (nms_form) *nms_form = 0;
       if ((rc = launch_nms(c->tl_boxes, c->tl_scores, c->tl_counts, post, tl_thresh, post, c->tl_keep, post, c->tl_keep_counts, nullptr,
                            c->tl_spill, n, p))) return rc;
     }
   }
-  if (c->connect_device) {
-    // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect)
+  if (plan.conn_form != TL_CONN_HOST) {
+    // graph build, chains, line fit and filter_boxes on the device too, for both DETECT_MODEs (the mode is chosen at collect); above 1024 rows per
+    // image the large form (its anchor columns: the map's, the last one taking what lies beyond 256)
+    if (plan.conn_form == TL_CONN_BUCKETS && !c->conn_work) return fail(CTPN_ERR_STATE, "text_lines: no state block for the large connector");
+    const int wf = lvl(w, 4);
     if ((rc = launch_connect(c->tl_boxes, c->tl_scores, c->tl_keep, c->tl_keep_counts, post, c->im_info_dev, c->conn_recs, c->conn_counts,
-                             c->conn_scratch, CONN_CAP, n, c->conn, p))) return rc;
-    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs.as<double>(), c->conn_recs, (size_t)n * 2 * CONN_CAP * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
+                             c->conn_scratch, c->conn_cap, n, c->conn, p, c->conn_work, wf > 256 ? 256 : wf))) return rc;
+    CTPN_HIP_TRY(hipMemcpyAsync(sl.crecs.as<double>(), c->conn_recs, (size_t)n * 2 * c->conn_cap * 9 * sizeof(double), hipMemcpyDeviceToHost, p));
     CTPN_HIP_TRY(hipMemcpyAsync(sl.ccnt.as<int>(), c->conn_counts, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, p));
   }
   return CTPN_OK;
@@ -119,8 +125,8 @@ static int lines_of_slot(ctpn_ctx* c, ctpn_ctx::Slot& sl, int n, int w, int mode
       if (ccnt[3 * i + 2] != 0) return fail(CTPN_ERR_ARG, "text_lines: proposal x1 outside the image (reference raises IndexError)");
       const int cnt = ccnt[3 * i + (mode == CTPN_MODE_O ? 1 : 0)];
       line_counts[i] = cnt;
-      if (cnt > line_capacity || cnt > CONN_CAP) return fail(CTPN_ERR_CAPACITY, "ctpn_detect: more lines than line_capacity");
-      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs.as<double>() + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * CONN_CAP * 9, (size_t)cnt * 9 * sizeof(double));
+      if (cnt > line_capacity || cnt > c->conn_cap) return fail(CTPN_ERR_CAPACITY, "ctpn_detect: more lines than line_capacity");
+      if (cnt) std::memcpy(recs_out + (size_t)i * line_capacity * 9, sl.crecs.as<double>() + ((size_t)i * 2 + (mode == CTPN_MODE_O ? 1 : 0)) * c->conn_cap * 9, (size_t)cnt * 9 * sizeof(double));
     }
     return CTPN_OK;
   }
@@ -158,7 +164,7 @@ static int debug_text_lines_body(ctpn_ctx* c, const float* rois, const int* roi_
   if (im_h < 1 || im_w < 16 || line_capacity < 0) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: im_h >= 1, im_w >= 16, line_capacity >= 0 required");
   const int post = c->rpn_post, post_max = c->post_max;      // rows per image on the device / in the caller's arrays
   for (int i = 0; i < n; ++i)
-    if (roi_counts[i] < 0 || roi_counts[i] > post) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: 0 <= roi_counts[i] <= RPN_POST_NMS_TOP_N (1000) rows of [score,x1,y1,x2,y2]");
+    if (roi_counts[i] < 0 || roi_counts[i] > post) return fail(CTPN_ERR_ARG, "ctpn_debug_text_lines: 0 <= roi_counts[i] <= RPN_POST_NMS_TOP_N (" + std::to_string(post) + ") rows of [score,x1,y1,x2,y2]");
   if (c->slot[0].busy || c->slot[1].busy) return fail(CTPN_ERR_STATE, "ctpn_debug_text_lines: a submitted batch has not been collected");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   CTPN_HIP_TRY(sync_forwards(c));      // the proposal entry points use these buffers on the forward's stream
@@ -232,7 +238,7 @@ int ctpn_detect_collect(ctpn_ctx* c, int slot, int mode, double* recs_out, int l
   CTPN_HIP_TRY(hipEventSynchronize(sl.ev_done));
   sl.busy = false;
   const int n = sl.n, w = sl.w, post = c->rpn_post, post_max = c->post_max;
-  // rois_out keeps post_max (1000) rows per image whatever RPN_POST_NMS_TOP_N is; the slot holds them packed
+  // rois_out keeps post_max rows per image (the ctx's proposal capacity) whatever RPN_POST_NMS_TOP_N is; the slot holds them packed
   if (rois_out) for (int i = 0; i < n; ++i) std::memcpy(rois_out + (size_t)i * post_max * 5, sl.rois + (size_t)i * post * 5, (size_t)post * 5 * sizeof(float));
   if (roi_counts) std::memcpy(roi_counts, sl.rcnt, (size_t)n * sizeof(int));
   return lines_of_slot(c, sl, n, w, mode, recs_out, line_capacity, line_counts);

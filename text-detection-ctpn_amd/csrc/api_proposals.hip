@@ -54,7 +54,7 @@ ProposalPlan proposal_plan(int nms_columns, int nms_prefix, bool has_mw_scratch,
   for (int i = 0; im_info && i < n; ++i) mw = mw && im_info[3 * i + 1] >= (float)((wf - 1) * 16 + 1);
   p.nms_form = !cols ? PP_NMS_GENERIC : (mw ? PP_NMS_COLUMN_GROUPS : PP_NMS_ONE_WG);
   p.group_wgs = mw ? nms_column_group_workgroups(wf) : 0;
-  p.prefix_launches = cols ? nms_prefix_launches(mw, nms_prefix ? NMS_PREFIX_RANKS : 0, pre_nms_topn, post_nms_topn) : 0;
+  p.prefix_launches = cols ? nms_prefix_launches(mw, nms_prefix_ranks(nms_prefix, post_nms_topn), pre_nms_topn, post_nms_topn) : 0;
   return p;
 }
 
@@ -64,7 +64,7 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
   if (!s) s = c->stream;
   if (!im_info) return fail(CTPN_ERR_ARG, "proposals: null pointer");
   if (pre_nms_topn <= 0 || pre_nms_topn > c->topn_max) return fail(CTPN_ERR_CAPACITY, "proposals: pre_nms_topn must be in 1..12000");
-  if (post_nms_topn <= 0 || post_nms_topn > c->post_max) return fail(CTPN_ERR_CAPACITY, "proposals: post_nms_topn must be in 1..1000");
+  if (post_nms_topn <= 0 || post_nms_topn > c->post_max) return fail(CTPN_ERR_CAPACITY, "proposals: post_nms_topn must be in 1.." + std::to_string(c->post_max));
   const int per_img = hf * wf * 10;
   const ProposalPlan plan = proposal_plan(c->nms_columns, c->nms_prefix, c->nms_mw_scratch != nullptr, n, hf, wf, pre_nms_topn, post_nms_topn, nms_thresh, im_info);
   const int npad = plan.npad;
@@ -110,7 +110,7 @@ static int enqueue_proposals_impl(ctpn_ctx* c, const float* heads, int heads_are
       // conv1_2 by 8 % through the shared SIMDs in round 2: removed)
       if ((rc = launch_nms_columns(c->sorted_boxes, c->sorted_scores, c->valid_counts, pre_nms_topn, nms_thresh, post_nms_topn, c->keep_idx,
                                    c->topn_max, c->keep_counts, c->rois, c->kept_spill, n, wf, s, c->sorted_anchor, c->roi_anchor, nullptr,
-                                   mw ? c->nms_mw_scratch : nullptr, mw ? c->nms_colid : nullptr, c->nms_prefix ? NMS_PREFIX_RANKS : 0, c->debug_nms))) return rc;
+                                   mw ? c->nms_mw_scratch : nullptr, mw ? c->nms_colid : nullptr, nms_prefix_ranks(c->nms_prefix, post_nms_topn), c->debug_nms))) return rc;
       if (c->nms_check) {
         // option "nms_check" (debug; synchronises the stream): the column decomposition presumes boxes on the 16-px anchor grid (common.h)
         std::vector<int> k1((size_t)n * c->topn_max), c1(n);

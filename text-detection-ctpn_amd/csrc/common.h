@@ -327,6 +327,7 @@ static inline bool nms_multi_wg_ok(bool has_scratch, int nms_columns, int n, int
 int nms_prefix_launches(bool multi_wg, int prefix, int stride, int max_keep);
 int nms_column_group_workgroups(int ncols);           // workgroups per image of the multi-workgroup form
 constexpr int NMS_PREFIX_RANKS = 4096;                // option nms_prefix: the ranks the prefix pass looks at
+int nms_prefix_ranks(int nms_prefix, int max_keep);   // ... for this post_nms_topn: NMS_PREFIX_RANKS up to 1024, 0 (no prefix pass) above; nms.hip
 
 // What one proposal-layer call launches: computed once by enqueue_proposals (api_proposals.hip), which then follows it; host arithmetic only
 // (ctpn_debug_proposal_plan hands it out). im_info: the images' rows [h, w, scale], of which the widths count (null: every image is as wide as the map).
@@ -376,11 +377,20 @@ int text_lines_host(const float* boxes, const float* scores, int r, int im_h, in
 int connect_lines(const float* kept_boxes, const float* kept_scores, int n, int im_h, int im_w, int mode,
                   const ConnectorCfg& cfg, std::vector<double>& recs);
 // rois [n_img][post][5] (descending score) -> per image: boxes/scale of the score > min_score prefix + its length
-constexpr int CONN_CAP = 512;   // text lines per image and mode the device connector can return (chains <= proposals / 2 = 500)
+constexpr int CONN_CAP = 512;   // text lines per image and mode the stateless hook ctpn_debug_connect can return (chains <= proposals / 2 = 500); a ctx: capacity / 2
 // text-line connector on the device (connect.hip): recs [n_img][2 modes][cap][9] float64, counts [n_img][3] = lines H, lines O, status;
 // scratch [n_img][1024][20] float64
+// stride (rows per image) above 1024: the large form (connect_dev.h) -- scratch [n_img][stride][20], work: n_img x connect_work_bytes(stride) bytes of
+// state, ncols: anchor columns of the images' width
 int launch_connect(const float* boxes, const float* scores, const int* keep, const int* keep_counts, int stride, const float* im_info,
-                   double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s);
+                   double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s, char* work = nullptr, int ncols = 0);
+size_t connect_work_bytes(int stride);      // 0 up to 1024 rows
+// What the text-line tail launches for n images of `rows` rows each (RPN_POST_NMS_TOP_N) on a map wf columns wide: enqueue_text_lines
+// (api_detect.hip) computes this once and follows it; host arithmetic only (ctpn_debug_text_line_plan hands it out)
+enum { TL_NMS_GENERIC = 0, TL_NMS_ONE_WG = 1, TL_NMS_COLUMN_GROUPS = 2, TL_NMS_ONE_WG_LARGE = 3 };
+enum { TL_CONN_HOST = 0, TL_CONN_ALL_PAIRS = 1, TL_CONN_BUCKETS = 2 };
+struct TextLinePlan { int nms_form, conn_form, group_wgs; };
+TextLinePlan text_line_plan(int nms_columns, int connect_device, bool has_mw_scratch, int n, int wf, int rows, float nms_thresh, float max_scale);
 int launch_lines_prep(const float* rois, const int* roi_counts, const float* im_info, int post, float min_score,
                       float* tl_boxes, float* tl_scores, int* tl_counts, int n_img, hipStream_t s);
 // host greedy NMS used by the connector when device_id < 0 (same predicate as the device kernel)

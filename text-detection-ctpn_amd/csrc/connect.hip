@@ -1,5 +1,6 @@
 // Text-line tail on device: the connector's front end (score filter, boxes / im_scale) and the connector itself; its NMS 0.2 is nms.hip's.
 #include "common.h"
+#include "connect_dev.h"      // ConnectArgs; the large form's per-thread bodies
 
 #pragma clang fp contract(off)
 
@@ -52,15 +53,7 @@ int launch_lines_prep(const float* rois, const int* roi_counts, const float* im_
 //     (sums in chain order: the fp32 / fp64 results do not depend on the thread count);
 //   * records of BOTH modes are produced (DETECT_MODE is an argument of ctpn_detect_collect, not of the submit).
 // ---------------------------------------------------------------------------------------------
-constexpr int CONN_MAX = 1024;          // proposals per image held in LDS (RPN_POST_NMS_TOP_N = 1000)
-
-// connect_kernel's share of ConnectorCfg, by value in the kernel arguments: wave-uniform, read from SGPRs. gap_f = (float)gap (exact: the
-// gap is at most 4096), what the reference's `x1 - MAX_HORIZONTAL_GAP` subtracts from the fp32 x1.
-struct ConnectArgs {
-  int gap; float gap_f;              // MAX_HORIZONTAL_GAP
-  float min_v_overlaps, min_size_sim;
-  double min_ratio, line_min_score, min_width;
-};
+constexpr int CONN_MAX = 1024;          // proposals per image held in LDS (RPN_POST_NMS_TOP_N up to 1024; above: connect_large_kernel, below)
 
 __device__ __forceinline__ bool conn_meet_v_iou(const float* y1, const float* y2, const float* hh, int a, int b, const ConnectArgs& ca) {
   const float h1 = hh[a], h2 = hh[b];
@@ -277,12 +270,89 @@ __global__ __launch_bounds__(256) void connect_kernel(const float* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The large form: 1025 .. CONNL_MAX kept proposals per image (a ctx whose ctpn_reserve_proposals raised its capacity). One workgroup of
+// 1024 threads per image; the image's state lives in its own block of `work` (global memory, a few hundred KB: L2-resident), the bucket
+// starts in LDS. Every per-thread body is connect_dev.h's, where the scheme is described; every loop there runs over a range fixed before it
+// starts (n, a bucket range, a chain of at most n nodes), no workgroup waits on another, and every index stored to is below n <= cap rows.
+// ---------------------------------------------------------------------------------------------
+constexpr int CONNL_THREADS = 1024;
+__global__ __launch_bounds__(CONNL_THREADS) void connect_large_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                                      const int* __restrict__ keep, const int* __restrict__ keep_counts, int stride,
+                                                                      const float* __restrict__ im_info, double* __restrict__ recs, int* __restrict__ counts,
+                                                                      double* __restrict__ scratch, char* __restrict__ work, int cap, int ncols, const ConnectArgs ca) {
+  __shared__ int s_sub[CONNL_THREADS], s_cnt[CONNL_MAXCOL], s_base[CONNL_MAXCOL + 1];
+  __shared__ int s_cm[2][CONNL_THREADS], s_gt[2][32], s_gb[2][33];
+  __shared__ int sbad;
+  const int img = blockIdx.x, tid = threadIdx.x;
+  int n = keep_counts[img];
+  n = n < 0 ? 0 : (n > stride ? stride : n);
+  const int im_h = (int)im_info[3 * img], im_w = (int)im_info[3 * img + 1];
+  const float cs = im_info[3 * img + 2];
+  const ConnlState st = connl_views(work + (size_t)img * connl_state_bytes(stride), stride);
+  if (tid == 0) sbad = 0;
+  __syncthreads();
+  for (int i = tid; i < n; i += CONNL_THREADS)
+    if (connl_load(i, boxes + (size_t)img * stride * 4, scores + (size_t)img * stride, keep + (size_t)img * stride, stride, cs, ncols, im_w, st)) sbad = 1;
+  __syncthreads();
+  int* cnt2 = counts + (size_t)img * 3;                    // lines H, lines O, status
+  if (sbad) { if (tid == 0) { cnt2[0] = 0; cnt2[1] = 0; cnt2[2] = -1; } return; }
+  {   // buckets: thread (c, q) = (tid / parts, tid % parts) takes column c's proposals of index segment q; ncols x parts <= 1024 threads
+    const int parts = CONNL_THREADS / ncols < 16 ? CONNL_THREADS / ncols : 16;
+    const int seg = (n + parts - 1) / parts;
+    const int c = tid / parts, q = tid % parts;
+    const bool active = c < ncols;
+    const int lo = q * seg < n ? q * seg : n, hi = lo + seg < n ? lo + seg : n;
+    if (active) s_sub[tid] = connl_count(c, lo, hi, st.col);
+    __syncthreads();
+    if (tid < ncols) s_cnt[tid] = connl_group_total(tid, parts, s_sub);
+    __syncthreads();
+    if (tid == 0) connl_scan(ncols, s_cnt, s_base);
+    __syncthreads();
+    if (tid < ncols) connl_group_starts(tid, parts, s_base[tid], s_sub);
+    __syncthreads();
+    if (active) connl_fill(c, lo, hi, st.col, s_sub[tid], s_base[c + 1], st.list);
+    __syncthreads();
+  }
+  for (int b = tid; b < n; b += CONNL_THREADS) connl_precursor(b, st, s_base, cs, ncols, ca);
+  __syncthreads();
+  for (int i = tid; i < n; i += CONNL_THREADS) connl_successor(i, st, s_base, cs, ncols, im_w, ca);
+  __syncthreads();
+  double* scr = scratch + (size_t)img * stride * CONNL_REC;
+  for (int i = tid; i < n; i += CONNL_THREADS) connl_chain(i, n, st, im_h, im_w, ca, scr + (size_t)i * CONNL_REC);
+  __syncthreads();
+  {   // ordered compaction: thread t's contiguous share of the roots, 32 groups of 32 threads, one scan per mode
+    const int per = (n + CONNL_THREADS - 1) / CONNL_THREADS;
+    const int lo = tid * per < n ? tid * per : n, hi = lo + per < n ? lo + per : n;
+    for (int m = 0; m < 2; ++m) s_cm[m][tid] = connl_compact_count(m, lo, hi, scr);
+    __syncthreads();
+    if (tid < 64) s_gt[tid >> 5][tid & 31] = connl_group_total(tid & 31, 32, s_cm[tid >> 5]);
+    __syncthreads();
+    if (tid < 2) connl_scan(32, s_gt[tid], s_gb[tid]);
+    __syncthreads();
+    if (tid < 64) connl_group_starts(tid & 31, 32, s_gb[tid >> 5][tid & 31], s_cm[tid >> 5]);
+    __syncthreads();
+    for (int m = 0; m < 2; ++m) connl_compact_write(m, lo, hi, scr, s_cm[m][tid], recs + ((size_t)img * 2 + m) * cap * 9, cap);
+    if (tid < 2) cnt2[tid] = s_gb[tid][32];
+    if (tid == 0) cnt2[2] = 0;
+  }
+}
+
+// stride <= 1024: connect_kernel (scratch [n_img][1024][20]); above: connect_large_kernel (scratch [n_img][stride][20], work n_img x
+// connl_state_bytes(stride), ncols = anchor columns of the widest image)
 int launch_connect(const float* boxes, const float* scores, const int* keep, const int* keep_counts, int stride, const float* im_info,
-                   double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s) {
-  if (stride > CONN_MAX) return fail(CTPN_ERR_ARG, "connect: more proposals per image than the kernel holds in LDS");
+                   double* recs, int* counts, double* scratch, int cap, int n_img, const ConnectorCfg& cfg, hipStream_t s, char* work, int ncols) {
   const ConnectArgs ca{cfg.max_gap, (float)cfg.max_gap, cfg.min_v_overlaps, cfg.min_size_sim, cfg.min_ratio, cfg.line_min_score, cfg.min_width};
+  if (stride > CONN_MAX) {
+    if (stride > CONNL_MAX || !work || ncols < 1 || ncols > CONNL_MAXCOL)
+      return fail(CTPN_ERR_ARG, "connect: the large form takes up to 4096 proposals per image in up to 256 anchor columns, and needs its state block");
+    hipLaunchKernelGGL(connect_large_kernel, dim3(n_img), dim3(CONNL_THREADS), 0, s, boxes, scores, keep, keep_counts, stride, im_info, recs, counts, scratch,
+                       work, cap, ncols, ca);
+    return launch_status("connect_large");
+  }
   hipLaunchKernelGGL(connect_kernel, dim3(n_img), dim3(256), 0, s, boxes, scores, keep, keep_counts, stride, im_info, recs, counts, scratch, cap, ca);
   return launch_status("connect");
 }
+size_t connect_work_bytes(int stride) { return stride > CONN_MAX ? connl_state_bytes(stride) : 0; }
 
 }  // namespace ctpn

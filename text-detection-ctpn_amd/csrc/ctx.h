@@ -136,7 +136,7 @@ struct ctpn_ctx {
     PinnedBuf pack;
     float* tlb = nullptr; float* tls = nullptr; int* keep = nullptr; int* kcnt = nullptr; float* rois = nullptr; int* rcnt = nullptr;      // views into pack
     PinnedBuf im_info;             // float [n][3]
-    PinnedBuf crecs, ccnt;         // device connector results: double [n][2 modes][CONN_CAP][9], int [n][3]
+    PinnedBuf crecs, ccnt;         // device connector results: double [n][2 modes][conn_cap][9], int [n][3]
     Event ev_heads, ev_decoded, ev_done;
     int n = 0, h = 0, w = 0; bool busy = false;
     int set = 0;               // the forward set the batch in flight runs on
@@ -316,7 +316,11 @@ struct ctpn_ctx {
   size_t m5_max = 0;
 
   // proposal buffers
-  int npad_max = 0, topn_max = 12000, post_max = 1000;
+  // post_max: the ctx's proposal capacity -- rows per image of everything the tail lays out by RPN_POST_NMS_TOP_N, and of rois_out / keep_out /
+  // anchors_out towards the caller. 1000 on a fresh ctx; ctpn_reserve_proposals (api_ctx.hip) replaces the blocks of `tail` and the slots' pack /
+  // crecs by larger ones. conn_cap = post_max / 2: lines per image and mode the device connector returns (a chain has two proposals at least)
+  int npad_max = 0, topn_max = 12000, post_max = 1000, conn_cap = 500;
+  struct TailBufs { DevBuf out_pack, roi_anchor, tl_spill, conn_recs, conn_scratch, conn_work; } tail;      // the views below point into these
   unsigned long long* keys = nullptr; unsigned long long* keys_tmp = nullptr;
   float* boxes4 = nullptr;
   float* sorted_boxes = nullptr;
@@ -327,7 +331,7 @@ struct ctpn_ctx {
   float* rois = nullptr;
   float* kept_spill = nullptr;
   int* sorted_anchor = nullptr;      // [n][12000] anchor index of every sorted row
-  int* roi_anchor = nullptr;         // [n][1000]  anchor index of every roi (second return of proposal_layer)
+  int* roi_anchor = nullptr;         // [n][post_max]  anchor index of every roi (second return of proposal_layer)
   int last_post = 0, last_prop_n = 0;
   ProposalPlan last_plan{}; int last_hf = 0, last_wf = 0, last_pre = 0;      // the last proposals call, for ctpn_debug_proposal_fetch
   float* im_info_dev = nullptr;
@@ -335,6 +339,7 @@ struct ctpn_ctx {
   float* tl_boxes = nullptr; float* tl_scores = nullptr; int* tl_counts = nullptr;  // connector front end
   int* tl_keep = nullptr; int* tl_keep_counts = nullptr; float* tl_spill = nullptr;
   double* conn_recs = nullptr; int* conn_counts = nullptr; double* conn_scratch = nullptr;   // device connector (connect_kernel)
+  char* conn_work = nullptr;         // ... its large form's state (connect_large_kernel), null up to 1024 rows
   int nms_columns = 1;               // "nms_columns": 1 = column-decomposed NMS (one workgroup per image; batches <= NMS_MW_MAX_BATCH: one column per
                                      // wave over ncols / 4 workgroups per image), 0 = nms_kernel (A/B), 2 / 3 = force the one-workgroup / the multi-workgroup form
   char* nms_mw_scratch = nullptr;    // NMS_MW_CAP_BATCH x NMS_MW_SCRATCH_BYTES

@@ -252,7 +252,10 @@ __device__ __forceinline__ void nms_emit_survivors(Word word, NmsShare sh, int c
 //   <16, 12288, 128>  the proposal layer's 12 000 candidates, 16 waves, column list in LDS;
 //   <4, 1024, 48>     the connector's <= 1000 candidates: 256 threads, <= 64 VGPRs, ~11 KB of LDS: fits on a CU NEXT TO a persistent
 //                     convolution workgroup (those hold 144 KB of LDS and 432 of a SIMD's 512 registers), so it starts at once instead of
-//                     waiting for a free CU.
+//                     waiting for a free CU;
+//   <16, 4096, 64>    the connector's candidates on a ctx whose capacity was raised above 1024 rows (ctpn_reserve_proposals): 16 waves over the
+//                     page's columns, 46 KB of LDS (the rank list and the histograms scale with MAXN and WAVES; a dense page keeps a few
+//                     dozen boxes per column, beyond 64 the spill slice serves).
 // col_scale != nullptr (the connector's NMS 0.2 over boxes / im_scale, detectors.py:28): the column is recovered as
 // int(x1 * scale + 0.5) >> 4 -- x1 * scale is within an ulp or two of the multiple of 16 it came from.
 template <int WAVES, int MAXN, int KCAP>
@@ -570,8 +573,13 @@ int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, co
   if (!kept_spill) return fail(CTPN_ERR_ARG, "nms: spill buffer (n_img x stride x 4 floats) required");
   if (ncols < 1 || ncols > NC_MAXCOL || stride > NC_MAXN || !(thresh >= 0.1f)) return fail(CTPN_ERR_ARG, "nms_columns: outside the column decomposition's domain");
   if (roi_anchor && (!sorted_anchor || !rois_out)) return fail(CTPN_ERR_ARG, "nms: roi_anchor needs sorted_anchor and rois_out");
-  if (col_scale && stride > NC_TL_MAXN) return fail(CTPN_ERR_ARG, "nms_columns: connector variant takes at most 1024 candidates per image");
-  if (mw_scratch) {
+  if (col_scale && stride > NC_TL_LARGE_MAXN) return fail(CTPN_ERR_ARG, "nms_columns: connector variant takes at most 4096 candidates per image");
+  if (col_scale && stride > NC_TL_MAXN) {
+    // more rows than the 4-wave form's lists and the multi-workgroup form's per-column list hold: the one-workgroup form sized for 4096
+    if (mw_scratch) return fail(CTPN_ERR_ARG, "nms_columns: the multi-workgroup form takes at most 1024 connector candidates per image");
+    hipLaunchKernelGGL((nms_columns_kernel<16, NC_TL_LARGE_MAXN, 64>), dim3(n_img), dim3(1024), 0, s, sorted_boxes, sorted_scores, counts_in, stride, thresh,
+                       max_keep, keep_idx, keep_stride, keep_counts, rois_out, (float4*)kept_spill, sorted_anchor, roi_anchor, ncols, col_scale, 0, 0);
+  } else if (mw_scratch) {
     // small batches: one column per wave, ncols / 4 workgroups per image (mw_scratch: n_img x NMS_MW_SCRATCH_BYTES, zero on entry and on exit;
     // colid: gather_kernel's column byte per rank, row pitch = stride rounded up to 16 -- null: the columns come from the boxes, <= 1024 of them)
     if (!colid && stride > MW_LIST) return fail(CTPN_ERR_ARG, "nms_columns: the multi-workgroup form needs column ids for more than 1024 candidates");
@@ -592,11 +600,27 @@ int launch_nms_columns(const float* sorted_boxes, const float* sorted_scores, co
   return launch_status("nms_columns");
 }
 
+// nms_prefix_launches' choice of the prefix: the 4096 best-scored ranks hold `max_keep` survivors only if max_keep is well below them -- the pass
+// pays off where it usually answers (survivors / ranks was ~0.4 on the images it was measured on), so it is asked for up to max_keep = 1024 and
+// skipped above, where a prefix pass would nearly always be followed by the full one. The keep lists are identical either way.
+int nms_prefix_ranks(int nms_prefix, int max_keep) { return nms_prefix && max_keep <= 1024 ? NMS_PREFIX_RANKS : 0; }
+
 bool nms_columns_ok(int ncols, int stride, float thresh) { return ncols >= 1 && ncols <= NC_MAXCOL && stride <= NC_MAXN && thresh >= 0.1f; }
 // the connector's NMS (boxes already divided by im_scale): adjacent columns overlap by one scaled pixel of 16 / scale + 1, so
 // IoU <= 1 / (32 / scale + 1) <= 1/9 for scale <= 4 -- far below the 0.2 threshold
 bool nms_columns_tl_ok(int ncols, int stride, float thresh, float max_scale) {
-  return ncols >= 1 && ncols <= NC_MAXCOL && stride <= NC_TL_MAXN && thresh >= 0.15f && max_scale > 0.f && max_scale <= 4.0f;
+  return ncols >= 1 && ncols <= NC_MAXCOL && stride <= NC_TL_LARGE_MAXN && thresh >= 0.15f && max_scale > 0.f && max_scale <= 4.0f;
+}
+
+// Every launch decision of the text-line tail, in one place (common.h): enqueue_text_lines computes this once and follows it
+TextLinePlan text_line_plan(int nms_columns, int connect_device, bool has_mw_scratch, int n, int wf, int rows, float nms_thresh, float max_scale) {
+  TextLinePlan p{};
+  p.nms_form = TL_NMS_GENERIC;
+  if (nms_columns && nms_columns_tl_ok(wf, rows, nms_thresh, max_scale))
+    p.nms_form = rows > NC_TL_MAXN ? TL_NMS_ONE_WG_LARGE : (nms_multi_wg_ok(has_mw_scratch, nms_columns, n, 0) ? TL_NMS_COLUMN_GROUPS : TL_NMS_ONE_WG);
+  p.group_wgs = p.nms_form == TL_NMS_COLUMN_GROUPS ? nms_column_group_workgroups(wf) : 0;
+  p.conn_form = !connect_device ? TL_CONN_HOST : (connect_work_bytes(rows) ? TL_CONN_BUCKETS : TL_CONN_ALL_PAIRS);
+  return p;
 }
 
 }  // namespace ctpn

@@ -17,6 +17,7 @@ __device__ __forceinline__ float score_from_order_bits(unsigned int o) {
 
 // column group of a box for the column-decomposed NMS kernels of nms.hip (16-px anchor grid; cs = im_scale for the connector's boxes / scale)
 constexpr int NC_MAXN = 12288, NC_MAXCOL = 256, NC_TL_MAXN = 1024;
+constexpr int NC_TL_LARGE_MAXN = 4096;      // the connector's NMS on a ctx whose capacity ctpn_reserve_proposals raised (CTPN_POST_NMS_CAPACITY_MAX)
 __device__ __forceinline__ int nms_col_of(float x1, float cs, int ncols) {
   const int c = (int)(x1 * cs + 0.5f) >> 4;
   return c < 0 ? 0 : (c > ncols - 1 ? ncols - 1 : c);

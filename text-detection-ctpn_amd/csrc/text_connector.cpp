@@ -35,8 +35,9 @@ constexpr double kMinWidth = 16.0 * 2;   // TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPO
 ConnectorCfg default_connector_cfg() { return ConnectorCfg{kMinScore, kNmsThresh, kMaxGap, kMinVOverlaps, kMinSizeSim, kMinRatio, kLineMinScore, kMinWidth}; }
 
 // ---- the tail's run-time parameters (ctpn_set_param and friends; ctpn_text_lines_cfg's cfg8): names, defaults, ranges ----
-// RPN_*: cfg.TEST.* of the reference (lib/fast_rcnn/config.py:175-183); the rest: TextLineCfg (common.h ConnectorCfg). The two top-N values
-// stop at their defaults (what a ctx's buffers and the device connector's CONN_MAX are sized for); the NMS thresholds at 0 (the
+// RPN_*: cfg.TEST.* of the reference (lib/fast_rcnn/config.py:175-183); the rest: TextLineCfg (common.h ConnectorCfg). RPN_PRE_NMS_TOP_N
+// stops at its default (what a ctx's buffers and the sort are sized for); RPN_POST_NMS_TOP_N's bound here is a fresh ctx's proposal capacity,
+// and ctpn_set_param takes it up to the ctx's own (ctpn_reserve_proposals, api_ctx.hip); the NMS thresholds at 0 (the
 // column-decomposed NMS relies on boxes of non-adjacent columns never suppressing each other); values that are used as fp32 must stay
 // finite when rounded to it.
 static const TailParam kTailParams[TAIL_PARAM_COUNT] = {

@@ -260,6 +260,10 @@ def _set_tail_params(net, params):
     A run without params touches nothing unless an earlier run on this net left parameters behind (then they go back to the defaults)."""
     if params is None and not getattr(net, "_tail_params_set", False):
         return
+    # more proposals per image than a fresh ctx holds (1000): raise the ctx's capacity first, and only then (ctpn_reserve_proposals)
+    post = int((params or {}).get("RPN_POST_NMS_TOP_N", 0))
+    if post > 1000:
+        B.reserve_for(net.ctx, post)
     for name in B.param_names():
         net.ctx.set_param(name, (params or {}).get(name, B.param_default(name)))
     net._tail_params_set = params is not None
@@ -900,6 +904,9 @@ def build_parser():
     ap.add_argument('--precision', default=None, choices=['split', 'fp32', 'fp16', 'bf16'],
                     help="arithmetic of the conv stack; default: cfg.TEST.PRECISION (text.yml: split, the parity-grade mode). bf16 is the "
                          "throughput choice (3.2 x split's rate, outside the 1e-3 / 1 px bar)")
+    ap.add_argument('--rpn-post-nms-top-n', type=int, default=None, metavar='N',
+                    help="cfg.TEST.RPN_POST_NMS_TOP_N for this run (the reference's default, and text.yml's: 1000; up to %d). A dense page holds more "
+                         "16-pixel slices than that, and its lines break into fragments at the default" % B.POST_NMS_CAPACITY_MAX)
     ap.add_argument('--connector', action='append', default=[], metavar='NAME=VALUE', type=_connector_item,
                     help="a threshold of the text-line connector (the reference's TextLineCfg; repeatable): " + ", ".join(B.CONNECTOR_PARAM_NAMES) +
                          ". Sets the ctx's parameters for the batches and the detector of the single-image path")
@@ -920,6 +927,10 @@ def main(argv=None):
     cfg_from_file(yml)
     if args.precision:
         cfg.TEST.PRECISION = args.precision
+    if args.rpn_post_nms_top_n is not None:
+        if not 1 <= args.rpn_post_nms_top_n <= B.POST_NMS_CAPACITY_MAX:
+            raise SystemExit('--rpn-post-nms-top-n must be in 1..%d' % B.POST_NMS_CAPACITY_MAX)
+        cfg.TEST.RPN_POST_NMS_TOP_N = args.rpn_post_nms_top_n      # both paths read it: rpn_params_from_cfg below, lib/fast_rcnn/test.py
     net = get_network("VGGnet_test")
     D.load_weights(net, args.synthetic)
     names = list_images(args.input)

@@ -12,6 +12,7 @@ import numpy as np
 
 from .config import cfg
 from ..utils.image import resize_bilinear
+from ..._binding import reserve_for
 
 
 def _scale_for(shape):
@@ -58,5 +59,6 @@ def test_ctpn_batch(net, ims):
         net.ctx.forward_blob(batch)
         scales = np.full((n,), s, np.float32)
     im_info = np.stack([[h, w, sc] for sc in scales]).astype(np.float32)
+    reserve_for(net.ctx, c.RPN_POST_NMS_TOP_N)
     rois = net.ctx.proposals(im_info, c.RPN_PRE_NMS_TOP_N, c.RPN_POST_NMS_TOP_N, c.RPN_NMS_THRESH, c.RPN_MIN_SIZE)
     return [r[:, 0] for r in rois], [r[:, 1:5] / sc for r, sc in zip(rois, scales)]

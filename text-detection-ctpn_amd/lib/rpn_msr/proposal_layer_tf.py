@@ -6,7 +6,7 @@ Unlike the reference (assert batch == 1, :51-52) a leading batch > 1 is accepted
 import numpy as np
 
 from ..fast_rcnn.config import cfg
-from ..._binding import Context
+from ..._binding import Context, check_post_nms_topn, reserve_for
 
 _ctx_cache = {}
 
@@ -32,7 +32,9 @@ def proposal_layer(rpn_cls_prob_reshape, rpn_bbox_pred, im_info, cfg_key, _feat_
     n, hf, wf, _ = cls.shape
     c = cfg[cfg_key]
     info = np.ascontiguousarray(im_info, dtype=np.float32).reshape(-1, 3)
+    check_post_nms_topn(c.RPN_POST_NMS_TOP_N)      # (before a ctx is made for the call)
     ctx = _ctx_for(n, hf, wf)
+    reserve_for(ctx, c.RPN_POST_NMS_TOP_N)      # the reference takes any value (:55); a ctx holds 1000 per image until asked for more (up to 4096)
     rois, anchors = ctx.proposals_from_host(cls, box, info, c.RPN_PRE_NMS_TOP_N, c.RPN_POST_NMS_TOP_N, c.RPN_NMS_THRESH,
                                             c.RPN_MIN_SIZE, want_anchors=True)
     # bbox_deltas[order][keep] (reference :133-157): the kept anchors' rows of rpn_bbox_pred.reshape(-1, 4) -- exact, the

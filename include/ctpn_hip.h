@@ -175,8 +175,16 @@ int ctpn_stream(ctpn_ctx* ctx, void** stream_out);
  * concatenated in the order ctpn_weight_manifest() reports. */
 int ctpn_weight_manifest(int index, const char** name, int* rank, int shape4[4], size_t* offset_floats);
 int ctpn_weight_count(void);
+/* A ctx's weights are the LAST arena loaded: every load rewrites the ctx's copy of the arena and every layout packed from it, on a live ctx as
+ * on a fresh one (a server that swaps checkpoints), and changes nothing else -- options, parameters, the proposal capacity and the stored
+ * activations of the last forward stay. When a load is allowed: ctpn_load_weights_host, ctpn_load_weights_device, ctpn_broadcast_weights_rank
+ * and ctpn_broadcast_weights follow ctpn_set_option's contract -- the ctx drains its forward streams and the proposal stream first, and the call
+ * is refused with CTPN_ERR_STATE ("... a submitted batch has not been collected") while a ctpn_detect_submit* is uncollected in either slot,
+ * whatever the arena holds: a batch in flight reads the packed weights on streams the pack does not run on. Collect, then load. */
 int ctpn_load_weights_host(ctpn_ctx* ctx, const float* arena_host);
-/* arena already in this device's HBM (e.g. a torch tensor filled by an RCCL broadcast): packs in place */
+/* arena already in this device's HBM (e.g. a torch tensor filled by an RCCL broadcast, or another ctx's arena): copied into the ctx's own arena
+ * and packed from there. The copy runs on the ctx's stream, which knows nothing of the stream that filled arena_dev: the caller synchronises
+ * the producer first (torch.cuda.synchronize(), hipStreamSynchronize). The call returns after the pack; arena_dev may be released then. */
 int ctpn_load_weights_device(ctpn_ctx* ctx, const void* arena_dev);
 
 /* ---- weight broadcast (RCCL over xGMI) ----------------------------------------------------------
@@ -185,7 +193,8 @@ int ctpn_load_weights_device(ctpn_ctx* ctx, const void* arena_dev);
  * xGMI only"), nothing per batch. librccl.so is loaded on first use (dlopen by soname; CTPN_RCCL_LIB overrides the path).
  *
  * ctpn_broadcast_weights: one process, n ctxs on n DIFFERENT devices (SURVEY section 8b export list): handles[0] must have its weights
- * loaded; every other ctx receives the arena over RCCL (ncclCommInitAll + grouped ncclBroadcast on each ctx's stream) and packs it.
+ * loaded; every other ctx receives the arena over RCCL (ncclCommInitAll + grouped ncclBroadcast on each ctx's stream) and packs it. EVERY
+ * handle is drained and checked first (the weights block above): one uncollected batch on any of them is CTPN_ERR_STATE and nothing is sent.
  *
  * One process per GPU (torchrun; bench.py): the root calls ctpn_comm_unique_id and hands the CTPN_COMM_ID_BYTES bytes to the other
  * ranks by any side channel (bench.py: the torch.distributed store), then EVERY rank calls ctpn_broadcast_weights_rank, which
@@ -195,8 +204,9 @@ int ctpn_broadcast_weights(ctpn_ctx** handles, int n);
 int ctpn_comm_unique_id(char* id_out, size_t capacity);
 int ctpn_broadcast_weights_rank(ctpn_ctx* ctx, const char* unique_id, int rank, int world, int root);
 /* ctpn_broadcast_weights_rank is a COLLECTIVE with no timeout of its own: a rank whose local pre-checks fail (librccl not loadable, a
- * post-processing-only ctx, a root without weights) returns an error BEFORE joining the communicator, and every other rank then blocks in
- * ncclCommInitRank. The caller must either make sure all ranks pass the same pre-checks (same library, same kind of ctx, root loaded) or
+ * post-processing-only ctx, a root without weights, a submitted batch that has not been collected) returns an error BEFORE joining the
+ * communicator, and every other rank then blocks in ncclCommInitRank. The caller must either make sure all ranks pass the same pre-checks
+ * (same library, same kind of ctx, root loaded, both slots collected) or
  * run the call under its own watchdog -- bench.py does both (180 s timer, and the ranks agree on success over the side channel before
  * anyone proceeds; on failure all of them fall back to a host broadcast). */
 
@@ -349,7 +359,19 @@ int ctpn_detect(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int 
  * keep_acts = 1 or per-stage profiling; without the memory the ctx stays on one set): its first layers run beside the other
  * batch's recurrent tail. Results do not depend on what runs beside what. A slot must be
  * collected before it is submitted to again; images must stay valid until the forward of that submit has run
- * (device pointers: until ctpn_sync or the matching collect). */
+ * (device pointers: until ctpn_sync or the matching collect).
+ * Between a submit and its collect (tests/inflight_cases.py classifies every function that takes a ctx; tests/test_gpu_inflight.py holds it):
+ *  - MAY be called, changes neither batch in flight and gives what it gives on an idle ctx: a submit to the other slot and the collects;
+ *    ctpn_forward / ctpn_forward_blob / ctpn_forward_ragged, ctpn_get_tensor, ctpn_feat_shape, ctpn_proposals, ctpn_proposals_from_host,
+ *    ctpn_proposal_anchors (the "last forward" they read is then the most recent submit's, or the ctpn_forward* called since); ctpn_detect /
+ *    ctpn_detect_ragged, which take the free slot (with both slots busy: ctpn_detect_submit's CTPN_ERR_STATE); ctpn_sync, ctpn_stream,
+ *    ctpn_host_threads, ctpn_get_option, ctpn_get_param, ctpn_proposal_capacity, ctpn_profile_enable / _reset / _read,
+ *    ctpn_debug_forward_sets; the image I/O units, which run on the copy stream and their own buffers: ctpn_decode_jpeg_batch[_device],
+ *    ctpn_jpeg_batch_fetch, ctpn_pack_canvas, ctpn_crop_lines, ctpn_encode_jpeg_batch[_device], ctpn_encode_png_batch.
+ *  - REFUSED with CTPN_ERR_STATE ("<function>: a submitted batch has not been collected") while either slot is busy, after the ctx has drained
+ *    its streams, and harmless to the batches: ctpn_set_option, ctpn_set_param, ctpn_reserve_proposals, ctpn_debug_text_lines, and the weight
+ *    loads ctpn_load_weights_host, ctpn_load_weights_device, ctpn_broadcast_weights_rank, ctpn_broadcast_weights (see the weights block).
+ *  - ctpn_destroy drains the streams and drops what was in flight. */
 int ctpn_detect_submit(ctpn_ctx* ctx, const uint8_t* images, int images_on_device, int n, int h, int w,
                        const float* scales, int slot);
 int ctpn_detect_collect(ctpn_ctx* ctx, int slot, int mode, double* recs_out, int line_capacity, int* line_counts,

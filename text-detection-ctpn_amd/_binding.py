@@ -1120,6 +1120,8 @@ class Context:
         _check(self._lib.ctpn_load_weights_host(self._h, _ptr(a, C.c_float)))
 
     def load_weights_device(self, dev_ptr):
+        """ctpn_load_weights_device: the arena from this device's memory. The copy runs on the ctx's stream: synchronise whatever filled the
+        buffer first (torch.cuda.synchronize()). Like every weight load: CTPN_ERR_STATE while a submitted batch is uncollected."""
         _check(self._lib.ctpn_load_weights_device(self._h, C.c_void_p(int(dev_ptr))))
 
     def broadcast_weights_rank(self, unique_id, rank, world, root=0):

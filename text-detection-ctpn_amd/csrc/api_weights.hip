@@ -147,6 +147,18 @@ static int pack_weights(ctpn_ctx* c) {
   return CTPN_OK;
 }
 
+// ctpn_set_option's contract in front of everything that rewrites the arena and its packed copies: both forward streams and the proposal stream
+// read them (a submit beside a batch in flight runs on set 1's stream, the recurrence and the heads on stream_p with tail_overlap), the pack runs
+// on c->stream alone. Drain, refuse while a slot is busy, forget the cross-stream hand-over: the ctx is idle when the first byte is copied.
+static int weights_quiesce(ctpn_ctx* c, const char* who) {
+  CTPN_HIP_TRY(hipSetDevice(c->device));
+  CTPN_HIP_TRY(sync_forwards(c));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  for (auto& sl : c->slot) if (sl.busy) return fail(CTPN_ERR_STATE, std::string(who) + ": a submitted batch has not been collected");
+  for (auto& f : c->fs) f.tail_pending = false;
+  return CTPN_OK;
+}
+
 }  // namespace ctpn
 
 // ---------------------------------------------------------------------------------------------
@@ -218,14 +230,14 @@ int ctpn_weight_manifest(int index, const char** name, int* rank, int shape4[4],
 int ctpn_load_weights_host(ctpn_ctx* c, const float* arena_host) {
   if (!c || !arena_host) return fail(CTPN_ERR_ARG, "null pointer");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_load_weights_host: post-processing-only ctx (ctpn_create_postproc) has no network");
-  CTPN_HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = weights_quiesce(c, "ctpn_load_weights_host")) return rc;
   CTPN_HIP_TRY(hipMemcpyAsync(c->arena, arena_host, (size_t)CTPN_WEIGHT_FLOATS * sizeof(float), hipMemcpyHostToDevice, c->stream));
   return pack_weights(c);
 }
 int ctpn_load_weights_device(ctpn_ctx* c, const void* arena_dev) {
   if (!c || !arena_dev) return fail(CTPN_ERR_ARG, "null pointer");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_load_weights_device: post-processing-only ctx (ctpn_create_postproc) has no network");
-  CTPN_HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = weights_quiesce(c, "ctpn_load_weights_device")) return rc;
   CTPN_HIP_TRY(hipMemcpyAsync(c->arena, arena_dev, (size_t)CTPN_WEIGHT_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   return pack_weights(c);
 }
@@ -246,9 +258,10 @@ int ctpn_broadcast_weights_rank(ctpn_ctx* c, const char* unique_id, int rank, in
   if (world < 1 || rank < 0 || rank >= world || root < 0 || root >= world) return fail(CTPN_ERR_ARG, "ctpn_broadcast_weights_rank: rank / root outside [0, world)");
   if (c->postproc_only) return fail(CTPN_ERR_STATE, "ctpn_broadcast_weights_rank: post-processing-only ctx has no network");
   if (rank == root && !c->weights_loaded) return fail(CTPN_ERR_STATE, "ctpn_broadcast_weights_rank: the root's weights are not loaded");
+  // a local pre-check like the others: in front of the communicator, so that a rank with a batch in flight leaves before it joins
+  if (const int rc = weights_quiesce(c, "ctpn_broadcast_weights_rank")) return rc;
   const RcclApi& r = rccl_api();
   if (!r.ok) return fail(CTPN_ERR_NODEVICE, "ctpn_broadcast_weights_rank: librccl.so could not be loaded (set CTPN_RCCL_LIB or ROCM_PATH)");
-  CTPN_HIP_TRY(hipSetDevice(c->device));
   rccl_unique_id id;
   std::memcpy(id.internal, unique_id, CTPN_COMM_ID_BYTES);
   rccl_comm_t comm = nullptr;
@@ -271,6 +284,8 @@ int ctpn_broadcast_weights(ctpn_ctx** handles, int n) {
     for (int j = 0; j < i; ++j) if (devs[j] == devs[i]) return fail(CTPN_ERR_ARG, "ctpn_broadcast_weights: two ctxs on the same device (RCCL needs one rank per GPU)");
   }
   if (!handles[0]->weights_loaded) return fail(CTPN_ERR_STATE, "ctpn_broadcast_weights: handles[0] has no weights loaded");
+  for (int i = 0; i < n; ++i)      // every handle, the sender included: its arena is read while the others' are written
+    if (const int rc = weights_quiesce(handles[i], "ctpn_broadcast_weights")) return rc;
   if (n == 1) return CTPN_OK;
   const RcclApi& r = rccl_api();
   if (!r.ok) return fail(CTPN_ERR_NODEVICE, "ctpn_broadcast_weights: librccl.so could not be loaded (set CTPN_RCCL_LIB or ROCM_PATH)");

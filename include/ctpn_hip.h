@@ -332,6 +332,54 @@ int ctpn_text_lines_cfg(const float* boxes, const float* scores, int r, int im_h
  * TextDetector(config=...) is the way to run another configuration. Needs no device. */
 int ctpn_connector_constants(double* out8);
 
+/* ---- pages in tiles ---------------------------------------------------------------------------
+ * No counterpart in the reference, whose resize_im (ctpn/demo.py:21-25) shrinks every image to 600 px on its short side. A page larger than a
+ * ctx's max_h x max_w is detected at its own resolution as overlapping tiles: CTPN's proposals are 16-px columns on a 16-px grid, x is never
+ * regressed and the connector sees proposals only, so with tile origins on multiples of 16 every tile's anchor grid is the page's, each page
+ * cell is owned by exactly one tile, and a text line across a seam is one chain of columns to the ordinary connector. The five functions are
+ * stateless (no ctx; plan and merge need no device); the forward on the tiles is ctpn_detect_submit / ctpn_detect_collect at scale 1.
+ *
+ * ctpn_page_plan. tile_h, tile_w: multiples of 16; overlap: a multiple of 32 in 0 .. min(tile_h, tile_w) / 2; page sides 16 .. 16384; anything
+ * else is CTPN_ERR_ARG. Per axis of length L with tile T and overlap V: L <= T is one tile at origin 0; otherwise the stride is S = T - V and
+ * k = ceil((L - T) / S) + 1 tiles sit at j S (the last tile's valid part is wider than V). valid = min(T, L - origin). Tile j owns the
+ * half-open range from origin_j + V / 2 (0 for the first tile) to origin_{j+1} + V / 2 (L for the last). Tiles are numbered row-major;
+ * tiles8: one record {oy, ox, valid_h, valid_w, own_y0, own_y1, own_x0, own_x1} of eight ints per tile, page coordinates. The owned rectangles
+ * partition the page; origins and own bounds other than the page's end are multiples of 16. count_out = tiles (written even when capacity
+ * is too small: CTPN_ERR_CAPACITY; tiles8 == NULL only counts), grid2 (nullable) = {tile rows, tile columns}.
+ *
+ * ctpn_page_cut. Tiles first .. first + n - 1 of tiles8 out of the page (page_h x page_w x 3 BGR uint8, rows pitch_bytes >= 3 page_w apart;
+ * neither the pointer nor the pitch needs any alignment; host or device memory) into out: n x tile_h x tile_w x 3 bytes, host or device memory
+ * (a device buffer 4-byte aligned), ready for ctpn_detect_submit(images_on_device = 1). Bytes outside the page are round(PIXEL_MEANS) =
+ * {103, 116, 123}: what the 16-bit modes' feed turns into exactly zero, the nearest thing to im_list_to_blob's zero padding that a uint8 feed
+ * allows. Every byte of out's n tiles is written, none beyond. Synchronous, on a stream of its own.
+ *
+ * ctpn_page_merge. rois: n_tiles x roi_capacity x 5 rows [score, x1, y1, x2, y2] as ctpn_detect_collect returns them at scale 1, roi_counts
+ * their numbers. A roi of tile t is kept iff its column is owned -- with c = int(x1) >> 4, own_x0 <= 16 c + ox < own_x1 -- and its centre row
+ * is: cy = (y1 + y2) * 0.5f in fp32, tile coordinates, (float)(own_y0 - oy) <= cy < (float)(own_y1 - oy). A kept roi is translated by fp32
+ * adds of (ox, oy), clipped to x2 <= page_w - 1 and y2 <= page_h - 1, and dropped if x2 - x1 + 1 or y2 - y1 + 1 is below min_size (the
+ * proposal layer's filter, again after the page clip). Output in tile order, then roi order: boxes_out capacity x 4, scores_out, src_out =
+ * tile * roi_capacity + row. count_out may exceed capacity -> CTPN_ERR_CAPACITY with count_out set.
+ *
+ * ctpn_page_nms. ctpn_nms's contract and signature, by the page form of the column-decomposed kernels: up to 2^20 boxes in up to 1024 columns
+ * int(x1) >> 4, partitioned over many workgroups, one wave per column over the whole chip. The keep list equals ctpn_nms's on every input of
+ * its domain: thresh >= 0.1; every box's x-extent inside [16 c, 16 c + 16] of its column c < 1024 (x1 <= x2); of two neighbouring columns
+ * at least one without a box narrower than 10 px (neighbours share one pixel column, which is then below a tenth of the wider box). Checked
+ * on the host; outside the domain: CTPN_ERR_ARG (ctpn_nms takes anything). Device buffers are cached per device, like ctpn_nms's.
+ *
+ * ctpn_page_text_lines. ctpn_text_lines_cfg's contract and its records bit for bit -- the same score filter, stable sort and connector --
+ * with the NMS in between chosen by nms_form: 0 = ctpn_nms, 1 = ctpn_page_nms (then its domain applies). device_id < 0: host C++, either form.
+ *
+ * Known limit: a tile clips its proposals to the tile, so a box taller than the overlap whose centre is owned near a seam is cut at the
+ * tile's edge: choose the overlap >= the tallest text expected. */
+int ctpn_page_plan(int page_h, int page_w, int tile_h, int tile_w, int overlap, int* tiles8, int capacity, int* count_out, int* grid2);
+int ctpn_page_cut(int device_id, const uint8_t* page, int page_on_device, int page_h, int page_w, long long pitch_bytes, const int* tiles8,
+                  int first, int n, int tile_h, int tile_w, uint8_t* out, int out_on_device, long long capacity_bytes);
+int ctpn_page_merge(const int* tiles8, int n_tiles, const float* rois, int roi_capacity, const int* roi_counts, int page_h, int page_w,
+                    float min_size, float* boxes_out, float* scores_out, int* src_out, int capacity, int* count_out);
+int ctpn_page_nms(int* keep_out, int* num_out, const float* boxes_host, int boxes_num, int boxes_dim, float nms_overlap_thresh, int device_id);
+int ctpn_page_text_lines(const float* boxes, const float* scores, int r, int page_h, int page_w, int mode, int device_id, const double* cfg8,
+                         int nms_form, double* recs_out, int capacity, int* count_out);
+
 /* ---- result files ---------------------------------------------------------------------------
  * Replaces draw_boxes (ctpn/demo.py:28-52), host C++: the text of data/results/res_<stem>.txt -- one "min_x,min_y,max_x,max_y\r\n" line
  * per text line, coordinates int(coord / scale) (truncation, :43-46), lines skipped where |box[0] - box[1]| < 5 or |box[3] - box[0]| < 5
@@ -490,7 +538,7 @@ int ctpn_debug_forward_sets(ctpn_ctx* ctx, long long* out4);
  * block, event and stream the host units create is owned by a handle type (csrc/owned.h) that counts it in and out. out4: [0] device bytes
  * [1] page-locked bytes  [2] events  [3] streams. A ctx adds to all four while it lives and ctpn_destroy takes exactly that off again; a
  * stateless entry point (ctpn_resize, ctpn_debug_*) leaves them as it found them, on success and on failure. What stays for the life of the
- * process: ctpn_nms's per-device cache, once used. The kernel launchers' few process-wide scratch blocks are not counted. */
+ * process: ctpn_nms's and ctpn_page_nms's per-device caches, once used. The kernel launchers' few process-wide scratch blocks are not counted. */
 int ctpn_debug_live_resources(long long* out4);
 int ctpn_debug_lstm_pre(int device_id, const float* x, const float* wx, const float* bias, int n, int hf, int wf, int precision, int cu_count,
                         float* out);

@@ -8,6 +8,7 @@ but every compute entry point raises CtpnError when the HIP library or a gfx950 
 """
 from ._binding import CtpnError, lib_path, load_library, Context  # noqa: F401
 from .weights import MANIFEST, WEIGHT_FLOATS, make_synthetic_arena, arena_views  # noqa: F401
+from .page import detect_page, PageResult  # noqa: F401
 
 __all__ = ["CtpnError", "lib_path", "load_library", "Context", "MANIFEST", "WEIGHT_FLOATS",
-           "make_synthetic_arena", "arena_views"]
+           "make_synthetic_arena", "arena_views", "detect_page", "PageResult"]

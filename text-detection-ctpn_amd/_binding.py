@@ -107,6 +107,11 @@ def _declare(lib):
         "ctpn_text_lines": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, i32p]),
         "ctpn_text_lines_cfg": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p, f64p, C.c_int, i32p]),
         "ctpn_connector_constants": (C.c_int, [f64p]),
+        "ctpn_page_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int, i32p, i32p]),
+        "ctpn_page_cut": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_longlong, i32p, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_longlong]),
+        "ctpn_page_merge": (C.c_int, [i32p, C.c_int, f32p, C.c_int, i32p, C.c_int, C.c_int, C.c_float, f32p, f32p, i32p, C.c_int, i32p]),
+        "ctpn_page_nms": (C.c_int, [i32p, i32p, f32p, C.c_int, C.c_int, C.c_float, C.c_int]),
+        "ctpn_page_text_lines": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, f64p, C.c_int, i32p]),
         "ctpn_detect": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f64p, C.c_int, i32p,
                                   f32p, i32p]),
         "ctpn_detect_submit": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int]),
@@ -660,6 +665,93 @@ def text_lines(boxes, scores, size, mode="H", device_id=0, capacity=4096, config
         _check(lib.ctpn_text_lines_cfg(_ptr(b, C.c_float), _ptr(s, C.c_float), int(b.shape[0]), int(size[0]), int(size[1]), m,
                                        int(device_id), _ptr(cfg8, C.c_double), _ptr(recs, C.c_double), capacity, C.byref(cnt)))
     return recs[: cnt.value].copy()
+
+
+# ---- pages in tiles (ctpn_page_*; the orchestration over a ctx: page.py) ----
+def page_plan(page_h, page_w, tile_h, tile_w, overlap):
+    """ctpn_page_plan -> (tiles, (rows, columns)): tiles (k, 8) int32 records {oy, ox, valid_h, valid_w, own_y0, own_y1, own_x0, own_x1}, row-major.
+    Host arithmetic of the library, needs no GPU."""
+    lib = load_library()
+    cnt, grid = C.c_int(0), np.zeros((2,), np.int32)
+    args = (int(page_h), int(page_w), int(tile_h), int(tile_w), int(overlap))
+    _check(lib.ctpn_page_plan(*args, None, 0, C.byref(cnt), _ptr(grid, C.c_int)))
+    tiles = np.zeros((cnt.value, 8), np.int32)
+    _check(lib.ctpn_page_plan(*args, _ptr(tiles, C.c_int), cnt.value, C.byref(cnt), _ptr(grid, C.c_int)))
+    return tiles, (int(grid[0]), int(grid[1]))
+
+
+def page_cut(page, tiles, first, n, tile_h, tile_w, device_id=0, out_ptr=None, page_ptr=None, page_shape=None, pitch=None):
+    """ctpn_page_cut: tiles first .. first + n - 1 of the plan out of the page. page: an (h, w, 3) uint8 array whose rows may lie `pitch` bytes
+    apart (a view of a wider buffer), or page_ptr / page_shape = (h, w) / pitch for a page in device memory. out_ptr: a device buffer of
+    n x tile_h x tile_w x 3 bytes to fill (returns None); without it the tiles come back as an (n, tile_h, tile_w, 3) array."""
+    lib = load_library()
+    t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 8)
+    if first < 0 or n <= 0 or first + n > t.shape[0]:
+        raise ValueError("page_cut: tiles %d .. %d of a plan of %d" % (first, first + n - 1, t.shape[0]))
+    if page_ptr is not None:
+        h, w = page_shape
+        src, on_dev, pb = C.c_void_p(int(page_ptr)), 1, int(pitch if pitch is not None else 3 * w)
+    else:
+        if page.dtype != np.uint8 or page.ndim != 3 or page.shape[2] != 3 or page.strides[1:] != (3, 1) or (page.shape[0] > 1 and page.strides[0] < 3 * page.shape[1]):
+            raise ValueError("page_cut wants an (h, w, 3) uint8 page with contiguous rows")
+        h, w = page.shape[:2]
+        src, on_dev, pb = C.c_void_p(page.ctypes.data), 0, int(page.strides[0])
+    need = int(n) * int(tile_h) * int(tile_w) * 3
+    out = None
+    if out_ptr is None:
+        out = np.empty((int(n), int(tile_h), int(tile_w), 3), np.uint8)
+    dst, dst_dev = (C.c_void_p(int(out_ptr)), 1) if out_ptr is not None else (out.ctypes.data_as(C.c_void_p), 0)
+    _check(lib.ctpn_page_cut(int(device_id), src, on_dev, int(h), int(w), pb, _ptr(t, C.c_int), int(first), int(n), int(tile_h), int(tile_w), dst, dst_dev, need))
+    return out
+
+
+def page_merge(tiles, rois, roi_counts, page_h, page_w, min_size):
+    """ctpn_page_merge: rois (n_tiles, capacity, 5) rows [score, x1, y1, x2, y2] in tile coordinates + their counts -> (boxes (m, 4), scores (m,),
+    src (m,) = tile * capacity + row) in page coordinates, each page cell's proposals from the one tile that owns it. Needs no GPU."""
+    lib = load_library()
+    t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 8)
+    r = _f32(rois)
+    c = np.ascontiguousarray(roi_counts, dtype=np.int32).reshape(-1)
+    if r.ndim != 3 or r.shape[2] != 5 or r.shape[0] != t.shape[0] or c.shape[0] != t.shape[0]:
+        raise ValueError("page_merge wants rois (n_tiles, capacity, 5) and n_tiles counts")
+    cap = max(int(c.clip(0, None).sum()), 1)
+    boxes, scores, src = np.zeros((cap, 4), np.float32), np.zeros((cap,), np.float32), np.zeros((cap,), np.int32)
+    cnt = C.c_int(0)
+    _check(lib.ctpn_page_merge(_ptr(t, C.c_int), int(t.shape[0]), _ptr(r, C.c_float), int(r.shape[1]), _ptr(c, C.c_int), int(page_h), int(page_w), float(min_size),
+                               _ptr(boxes, C.c_float), _ptr(scores, C.c_float), _ptr(src, C.c_int), cap, C.byref(cnt)))
+    return boxes[: cnt.value].copy(), scores[: cnt.value].copy(), src[: cnt.value].copy()
+
+
+def page_nms_sorted(boxes_sorted, thresh, device_id=0):
+    """ctpn_page_nms: nms_sorted's contract by the page form of the column NMS (boxes on the 16-px column grid, thresh >= 0.1)."""
+    lib = load_library()
+    b = _f32(boxes_sorted)
+    n = int(b.shape[0])
+    if n == 0:
+        return np.zeros((0,), np.int32)
+    keep = np.zeros((n,), np.int32)
+    num = C.c_int(0)
+    _check(lib.ctpn_page_nms(_ptr(keep, C.c_int), C.byref(num), _ptr(b, C.c_float), n, int(b.shape[1]), float(thresh), int(device_id)))
+    return keep[: num.value]
+
+
+def page_text_lines(boxes, scores, size, mode="H", device_id=0, capacity=4096, config=None, nms_form=0):
+    """ctpn_page_text_lines: text_lines' contract and records, the NMS inside by nms_form: 0 = ctpn_nms, 1 = ctpn_page_nms."""
+    lib = load_library()
+    cfg8 = connector_cfg8(config)
+    b = _f32(boxes).reshape(-1, 4)
+    s = _f32(scores).reshape(-1)
+    m = MODE_O if str(mode).upper().startswith("O") else MODE_H
+    while True:
+        recs = np.zeros((capacity, 9), np.float64)
+        cnt = C.c_int(0)
+        rc = lib.ctpn_page_text_lines(_ptr(b, C.c_float), _ptr(s, C.c_float), int(b.shape[0]), int(size[0]), int(size[1]), m, int(device_id),
+                                      None if cfg8 is None else _ptr(cfg8, C.c_double), int(nms_form), _ptr(recs, C.c_double), capacity, C.byref(cnt))
+        if rc == CTPN_ERR_CAPACITY and cnt.value > capacity:      # a page holds more lines than an image: once more with room for all
+            capacity = cnt.value
+            continue
+        _check(rc)
+        return recs[: cnt.value].copy()
 
 
 CONNECTOR_CONSTANT_NAMES = ("TEXT_PROPOSALS_WIDTH * MIN_NUM_PROPOSALS", "MIN_RATIO", "LINE_MIN_SCORE", "MAX_HORIZONTAL_GAP", "TEXT_PROPOSALS_MIN_SCORE",

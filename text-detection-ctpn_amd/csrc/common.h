@@ -317,6 +317,15 @@ constexpr size_t NMS_MW_FLAG_OFF = 2032;            // prefix pass: "the prefix 
 constexpr int NMS_MW_MAX_BATCH = 4;                 // batches up to this size spread their columns over the machine; larger ones fill it with images
 constexpr int NMS_MW_CAP_BATCH = 32;                // ... unless option nms_columns = 3 asks for the multi-workgroup form explicitly: buffers are sized for this many images
 bool nms_columns_ok(int ncols, int stride, float thresh);
+// the PAGE form of the column decomposition (nms.hip, nms_page_columns_kernel): ONE list of up to NMS_PAGE_MAXN score-sorted boxes in up to
+// NMS_PAGE_MAXCOL columns int(x1) >> 4 -- a page's merged proposals (ctpn_page_nms). Partition over many workgroups, one wave per column over the
+// whole chip, keep list in rank order. Same PRECONDITION as above, checked by the caller on the host (api_page.hip). Scratch, all device memory:
+// list n ints, hist ncols x nms_page_units(n) words, colbase ncols + 1 words, spill n x 4 floats, alive (n + 31) / 32 words (zeroed here);
+// keep: n ints, count: one int
+constexpr int NMS_PAGE_MAXN = 1 << 20, NMS_PAGE_MAXCOL = 1024;
+int nms_page_units(int n);
+int launch_nms_page_columns(const float* sorted_boxes, int n, int ncols, float thresh, int* list, unsigned* hist, unsigned* colbase, float* spill,
+                            unsigned* alive, int* keep, int* count, hipStream_t s);
 // the multi-workgroup form for the proposal layer? nms_columns: the option; hf: rows of the feature map (a column holds hf x 10 candidates at most,
 // the kernel's list 1024), 0 for the connector's <= 1024 boxes
 static inline bool nms_multi_wg_ok(bool has_scratch, int nms_columns, int n, int hf) {
@@ -372,8 +381,10 @@ bool tail_param_ok(int index, double v);                         // finite, insi
 void connector_cfg_set(ConnectorCfg& c, int index, double v);    // the TP_* of the connector; others are ignored
 int connector_cfg_from8(const double* cfg8, ConnectorCfg& out);  // ctpn_connector_constants' order; null: the defaults
 // host text connector (text_connector.cpp)
+// nms: the device NMS between the sort and connect_lines where device_id >= 0 -- null: ctpn_nms; ctpn_page_text_lines passes the form it was asked for
+typedef int (*TextLinesNms)(int* keep_out, int* num_out, const float* boxes_host, int boxes_num, int boxes_dim, float thresh, int device_id);
 int text_lines_host(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode,
-                    int device_id, const ConnectorCfg& cfg, std::vector<double>& recs);
+                    int device_id, const ConnectorCfg& cfg, std::vector<double>& recs, TextLinesNms nms = nullptr);
 int connect_lines(const float* kept_boxes, const float* kept_scores, int n, int im_h, int im_w, int mode,
                   const ConnectorCfg& cfg, std::vector<double>& recs);
 // rois [n_img][post][5] (descending score) -> per image: boxes/scale of the score > min_score prefix + its length
@@ -481,6 +492,11 @@ int png_decode_file(const char* path, uint8_t* bgr_out, size_t capacity, int wan
 // heights_dev: the batch's pixel heights; max_pad_rows: the most rows any image lacks at the map's level (0: no launch)
 int launch_ragged_mask(void* base, const RaggedMap& m, const int* heights_dev, int n, int max_pad_rows, hipStream_t s);
 int launch_ragged_blob(const uint8_t* canvas, float* blob, const int* heights_dev, int n, int hc, int w, hipStream_t s);
+
+// page.hip: tiles of a page larger than the network input, cut at native resolution (the plan's arithmetic, PgTile and the per-thread text:
+// page_dev.h). tiles_dev: n records in device memory; out_dev: n x tile_h x tile_w x 3 bytes, 4-byte aligned, every one of them written
+struct PgTile;
+int launch_page_cut(const uint8_t* page_dev, long long pitch, const PgTile* tiles_dev, int n, int tile_h, int tile_w, uint8_t* out_dev, hipStream_t s);
 
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 

@@ -1,6 +1,8 @@
 // Proposal layer on device, third stage: greedy NMS over score-sorted boxes (sort_keys.hip) -- the generic kernel and the column-decomposed
 // forms, which also serve the text connector's NMS 0.2 (connect.hip). Bit parity with the reference: decode.hip's head comment.
 #include "proposal_dev.h"      // (brings common.h)
+#include "nms_column_dev.h"    // iou_gt and the per-column body of the column forms
+#include "wg_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -21,14 +23,6 @@ namespace ctpn {
 // ---------------------------------------------------------------------------------------------
 constexpr int NMS_WAVES = 16;
 constexpr int NMS_KCAP = 2048;
-
-__device__ __forceinline__ bool iou_gt(const float4& a, float sa, const float4& b, float sb, float thr) {
-  const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-  const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-  const float width = fmaxf(right - left + 1.f, 0.f), height = fmaxf(bottom - top + 1.f, 0.f);
-  const float inter = width * height;
-  return inter / (sa + sb - inter) > thr;
-}
 
 __global__ __launch_bounds__(NMS_WAVES * 64) void nms_kernel(const float* __restrict__ sorted_boxes,
                                                              const float* __restrict__ sorted_scores,
@@ -169,37 +163,7 @@ int launch_nms(const float* sorted_boxes, const float* sorted_scores, const int*
 // The predicate and its fp32 evaluation order are nms_kernel's / devIoU's (reference nms_kernel.cu:24-32, :71).
 // ---------------------------------------------------------------------------------------------
 
-// The per-column body of both column kernels, one copy. Is this lane's candidate suppressed by one of the column's K kept boxes? (wave-uniform
-// loop, LDS broadcast; beyond(k) fetches the kept box at position k >= cap, the LDS capacity: from the spill slice, or the sorted boxes by kept rank)
-template <typename Beyond>
-__device__ __forceinline__ bool nms_kept_suppress(const float4* kept, const float* karea, int cap, int K, const float4& bx, float ar, float thr, Beyond beyond) {
-  bool supp = false;
-  for (int k = 0; k < K; ++k) {
-    float4 kb; float ka;
-    if (k < cap) { kb = kept[k]; ka = karea[k]; }
-    else { kb = beyond(k); ka = (kb.z - kb.x + 1.f) * (kb.w - kb.y + 1.f); }
-    supp = supp || iou_gt(kb, ka, bx, ar, thr);
-  }
-  return supp;
-}
-
-// In-chunk greedy resolution over live candidates, ascending: `alive` = the lanes whose candidate passed the kept list; returns the lanes
-// that survive each other too. (Round 5 also measured the two-part form -- the suppression rows of every candidate that passed the kept
-// list first, lane i parking row i, then a walk that only reads rows: 100 us against 92 for the proposal layer's launch, 15 against 11 for
-// the connector's: the rows of candidates that die inside the chunk are wasted work, and they outnumber what the shorter dependent chain saves.)
-__device__ __forceinline__ unsigned long long nms_resolve_chunk(const float4& bx, float ar, unsigned long long alive, int lane, float thr) {
-  unsigned long long rem = alive;
-  while (rem) {
-    const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rem));
-    auto rl = [&](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), i)); };
-    const float4 bi = make_float4(rl(bx.x), rl(bx.y), rl(bx.z), rl(bx.w));
-    const float ai = rl(ar);
-    const bool ov = lane > i && ((alive >> lane) & 1ull) && iou_gt(bi, ai, bx, ar, thr);
-    alive &= ~__ballot(ov);
-    rem = alive & ~((2ull << i) - 1ull);
-  }
-  return alive;
-}
+// The per-column body of the column kernels, one copy: nms_column_dev.h (nms_kept_suppress, nms_resolve_chunk).
 
 // Step 3 over the rank-indexed survivor mask (word(j) = ranks 32 j ..: LDS, or an agent-scope load): every wave counts its contiguous share of the words ...
 struct NmsShare { int w_lo, w_hi; unsigned basepos, total; };      // the wave's words, the survivors before them, the survivors of all
@@ -610,6 +574,169 @@ bool nms_columns_ok(int ncols, int stride, float thresh) { return ncols >= 1 && 
 // IoU <= 1 / (32 / scale + 1) <= 1/9 for scale <= 4 -- far below the 0.2 threshold
 bool nms_columns_tl_ok(int ncols, int stride, float thresh, float max_scale) {
   return ncols >= 1 && ncols <= NC_MAXCOL && stride <= NC_TL_LARGE_MAXN && thresh >= 0.15f && max_scale > 0.f && max_scale <= 4.0f;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same decomposition for a PAGE (ctpn_page_nms: the merged proposals of a page's tiles in front of the connector's NMS 0.2): ONE list
+// of up to 2^20 score-sorted boxes in up to 1024 columns int(x1) >> 4 -- more ranks than a workgroup's LDS lists hold and more columns than its
+// histograms, so every step is a launch of its own and the launch boundaries are the only hand-offs between workgroups:
+//   1. an order-preserving partition of the ranks by column. The unit is a WAVE over a contiguous segment of ranks: page_hist_kernel counts every
+//      unit's ranks per column (rs_match's scheme on ten column bits), page_scan_kernel scans the counts column-major, unit-minor in one
+//      workgroup (wg_scan.h) -- a unit's start inside every column, and the columns' starts --, page_scatter_kernel walks the segments again and
+//      writes the ranks: ascending rank inside a column because units, and a unit's 64-rank steps, are taken in rank order;
+//   2. nms_page_columns_kernel: one wave per column, ncols / 4 workgroups (1024 columns = 1024 waves: four on every CU), nms_column_greedy
+//      (nms_column_dev.h) over the column's ranks: kept boxes in the wave's LDS, beyond PGN_KCAP in the column's slice of the spill block;
+//      survivors are bits of a rank-indexed mask in HBM (agent-scope atomicOr; read by the next launch only);
+//   3. page_emit_kernel: a popcount scan over the mask writes the keep list in rank order, and its length.
+// Same predicate, same order of evaluation per column: the keep list is launch_nms's on every input of the precondition (launch_nms_columns').
+// ---------------------------------------------------------------------------------------------
+constexpr int PGN_WAVES = 4, PGN_KCAP = 128, PGN_MAXUNITS = 256;
+
+__device__ __forceinline__ int pgn_col_of(float x1, int ncols) {
+  const int c = (int)x1 >> 4;
+  return c < 0 ? 0 : (c > ncols - 1 ? ncols - 1 : c);      // (the caller checked every box: a clamp never changes a column)
+}
+// rs_match on ten bits: the lanes (valid ones) whose column is this lane's
+__device__ __forceinline__ unsigned long long pgn_match(unsigned c, bool valid) {
+  unsigned long long mask = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 10; ++b) {
+    const bool bit = (c >> b) & 1u;
+    const unsigned long long bal = __ballot(bit);
+    mask &= bit ? bal : ~bal;
+  }
+  return mask;
+}
+
+// unit u = blockIdx.x * PGN_WAVES + wave owns ranks [u seg, u seg + seg) below n (seg a multiple of 64); hist: [ncols][units]
+__global__ __launch_bounds__(PGN_WAVES * 64) void page_hist_kernel(const float4* __restrict__ boxes, int n, int seg, int units, int ncols, unsigned* __restrict__ hist) {
+  __shared__ unsigned s_hist[PGN_WAVES][NMS_PAGE_MAXCOL];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int unit = blockIdx.x * PGN_WAVES + wave;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  for (int i = lane; i < ncols; i += 64) s_hist[wave][i] = 0u;
+  __syncthreads();
+  const long long lo64 = (long long)unit * seg;
+  const int lo = lo64 < n ? (int)lo64 : n;
+  const int hi = lo + seg < n ? lo + seg : n;
+  for (int base = lo; base < hi; base += 64) {
+    const int r = base + lane;
+    const bool valid = r < hi;
+    const unsigned c = valid ? (unsigned)pgn_col_of(boxes[r].x, ncols) : 0u;
+    const unsigned long long m = pgn_match(c, valid);
+    if (valid && (m & lt) == 0ull) s_hist[wave][c] += (unsigned)__popcll(m);
+  }
+  __syncthreads();
+  if (unit < units)
+    for (int i = lane; i < ncols; i += 64) hist[(size_t)i * units + unit] = s_hist[wave][i];
+}
+
+// hist [ncols][units], read as one row of ncols x units counts -> the exclusive prefix sums in place; colbase[c] = column c's start, colbase[ncols] = n
+__global__ __launch_bounds__(256) void page_scan_kernel(unsigned* __restrict__ hist, int units, int ncols, unsigned* __restrict__ colbase) {
+  const int total = ncols * units;
+  const int per = (total + 255) / 256;
+  const int lo = (int)threadIdx.x * per < total ? (int)threadIdx.x * per : total;
+  const int hi = lo + per < total ? lo + per : total;
+  uint32_t sum = 0;
+  for (int i = lo; i < hi; ++i) sum += hist[i];
+  uint32_t all = 0;
+  uint32_t run = wg_scan256(sum, all) - sum;
+  for (int i = lo; i < hi; ++i) {
+    const unsigned v = hist[i];
+    hist[i] = run;
+    if (i % units == 0) colbase[i / units] = run;
+    run += v;
+  }
+  if (threadIdx.x == 0) colbase[ncols] = all;
+}
+
+__global__ __launch_bounds__(PGN_WAVES * 64) void page_scatter_kernel(const float4* __restrict__ boxes, int n, int seg, int units, int ncols,
+                                                                      const unsigned* __restrict__ hist, int* __restrict__ list) {
+  __shared__ unsigned s_off[PGN_WAVES][NMS_PAGE_MAXCOL];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int unit = blockIdx.x * PGN_WAVES + wave;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  if (unit < units)
+    for (int i = lane; i < ncols; i += 64) s_off[wave][i] = hist[(size_t)i * units + unit];
+  __syncthreads();
+  const long long lo64 = (long long)unit * seg;
+  const int lo = lo64 < n ? (int)lo64 : n;
+  const int hi = lo + seg < n ? lo + seg : n;
+  for (int base = lo; base < hi; base += 64) {
+    const int r = base + lane;
+    const bool valid = r < hi;
+    const unsigned c = valid ? (unsigned)pgn_col_of(boxes[r].x, ncols) : 0u;
+    const unsigned long long m = pgn_match(c, valid);
+    if (valid) {
+      const unsigned off = s_off[wave][c];
+      const unsigned at = off + (unsigned)__popcll(m & lt);
+      if (at < (unsigned)n) list[at] = r;      // (always: the counts are page_hist_kernel's of the same columns)
+      if ((m >> lane) == 1ull) s_off[wave][c] = off + (unsigned)__popcll(m);
+    }
+  }
+}
+
+__global__ __launch_bounds__(PGN_WAVES * 64) void nms_page_columns_kernel(const float4* __restrict__ boxes, const int* __restrict__ list,
+                                                                          const unsigned* __restrict__ colbase, int n, int ncols, float thr,
+                                                                          float4* __restrict__ spill, unsigned* __restrict__ alive) {
+  __shared__ float4 s_kept[PGN_WAVES][PGN_KCAP];
+  __shared__ float s_karea[PGN_WAVES][PGN_KCAP];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int col = blockIdx.x * PGN_WAVES + wave; col < ncols; col += gridDim.x * PGN_WAVES) {
+    const int start = (int)colbase[col], end = (int)colbase[col + 1];
+    if (start < 0 || end > n || end <= start) continue;      // (wave-uniform; an empty column)
+    // (a rank outside the list cannot come out of the partition; were the scratch ever stale, it must still not become an address)
+    nms_column_greedy(boxes, [&](int ci) { const int r = list[start + ci]; return (unsigned)r < (unsigned)n ? r : 0; }, end - start, s_kept[wave], s_karea[wave], PGN_KCAP, spill + start, thr, lane,
+                      [&](int rank) { __hip_atomic_fetch_or(&alive[rank >> 5], 1u << (rank & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
+  }
+}
+
+// alive: (n + 31) / 32 words, bits at and beyond n clear -> keep: the set bits' ranks, ascending; count[0]: how many
+__global__ __launch_bounds__(256) void page_emit_kernel(const unsigned* __restrict__ alive, int n, int* __restrict__ keep, int* __restrict__ count) {
+  const int nwords = (n + 31) >> 5;
+  const int per = (nwords + 255) / 256;
+  const int lo = (int)threadIdx.x * per < nwords ? (int)threadIdx.x * per : nwords;
+  const int hi = lo + per < nwords ? lo + per : nwords;
+  uint32_t cnt = 0;
+  for (int j = lo; j < hi; ++j) cnt += (uint32_t)__popc(alive[j]);
+  uint32_t all = 0;
+  uint32_t pos = wg_scan256(cnt, all) - cnt;
+  for (int j = lo; j < hi; ++j) {
+    unsigned w = alive[j];
+    while (w) {
+      const int b = __builtin_ctz(w);
+      w &= w - 1u;
+      if (pos < (uint32_t)n) keep[pos] = j * 32 + b;
+      ++pos;
+    }
+  }
+  if (threadIdx.x == 0) count[0] = (int)all;
+}
+
+int nms_page_units(int n) {
+  int u = (n + 1023) / 1024;
+  u = u < 1 ? 1 : (u > PGN_MAXUNITS ? PGN_MAXUNITS : u);
+  return (u + PGN_WAVES - 1) / PGN_WAVES * PGN_WAVES;
+}
+
+int launch_nms_page_columns(const float* sorted_boxes, int n, int ncols, float thresh, int* list, unsigned* hist, unsigned* colbase, float* spill,
+                            unsigned* alive, int* keep, int* count, hipStream_t s) {
+  if (n < 1 || n > NMS_PAGE_MAXN || ncols < 1 || ncols > NMS_PAGE_MAXCOL || !(thresh >= 0.1f)) return fail(CTPN_ERR_ARG, "nms_page_columns: outside the column decomposition's domain");
+  if (!list || !hist || !colbase || !spill || !alive || !keep || !count) return fail(CTPN_ERR_ARG, "nms_page_columns: null scratch");
+  const int units = nms_page_units(n);
+  const int seg = (((n + units - 1) / units) + 63) & ~63;
+  const float4* boxes = (const float4*)sorted_boxes;
+  CTPN_HIP_TRY(hipMemsetAsync(alive, 0, (size_t)((n + 31) >> 5) * sizeof(unsigned), s));
+  hipLaunchKernelGGL(page_hist_kernel, dim3(units / PGN_WAVES), dim3(PGN_WAVES * 64), 0, s, boxes, n, seg, units, ncols, hist);
+  hipLaunchKernelGGL(page_scan_kernel, dim3(1), dim3(256), 0, s, hist, units, ncols, colbase);
+  hipLaunchKernelGGL(page_scatter_kernel, dim3(units / PGN_WAVES), dim3(PGN_WAVES * 64), 0, s, boxes, n, seg, units, ncols, (const unsigned*)hist, list);
+  hipLaunchKernelGGL(nms_page_columns_kernel, dim3((ncols + PGN_WAVES - 1) / PGN_WAVES), dim3(PGN_WAVES * 64), 0, s, boxes, (const int*)list, (const unsigned*)colbase,
+                     n, ncols, thresh, (float4*)spill, alive);
+  hipLaunchKernelGGL(page_emit_kernel, dim3(1), dim3(256), 0, s, (const unsigned*)alive, n, keep, count);
+  return launch_status("nms_page_columns");
 }
 
 // Every launch decision of the text-line tail, in one place (common.h): enqueue_text_lines computes this once and follows it

@@ -212,7 +212,7 @@ void nms_host(const float* boxes, int n, int dim, float thresh, std::vector<int>
 }
 
 int text_lines_host(const float* boxes, const float* scores, int r, int im_h, int im_w, int mode, int device_id,
-                    const ConnectorCfg& cfg, std::vector<double>& recs) {
+                    const ConnectorCfg& cfg, std::vector<double>& recs, TextLinesNms nms) {
   recs.clear();
   if (r < 0 || im_h <= 0 || im_w <= 0) return fail(CTPN_ERR_ARG, "text_lines: bad size");
   if (mode != CTPN_MODE_H && mode != CTPN_MODE_O) return fail(CTPN_ERR_ARG, "text_lines: mode must be H(0) or O(1)");
@@ -234,7 +234,7 @@ int text_lines_host(const float* boxes, const float* scores, int r, int im_h, in
   if (device_id >= 0) {
     keep.resize(n0);
     int nk = 0;
-    const int rc = ctpn_nms(keep.data(), &nk, dets.data(), n0, 5, cfg.nms_thresh, device_id);
+    const int rc = (nms ? nms : ctpn_nms)(keep.data(), &nk, dets.data(), n0, 5, cfg.nms_thresh, device_id);
     if (rc) return rc;
     keep.resize(nk);
   } else {

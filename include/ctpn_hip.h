@@ -1048,6 +1048,85 @@ int    ctpn_write_line_crops_png_ragged(ctpn_ctx* ctx, const uint8_t* canvas, in
                                         const double* recs, int line_capacity, const int* line_counts, int crop_h, int max_w, int pad_value,
                                         const char* const* paths, int* widths_out, int* total_out);
 
+/* ---- anchor targets and the RPN loss: the label side of ctpn/train_net.py on the device. Additive to ABI 10, no option, no parameter name, no
+ * ctx: like ctpn_page_cut the calls take a device_id, run on a stream of their own and synchronise once, at their end. That stream is
+ * non-blocking and waits for no other: with on_device = 1 the work that produces the input arrays must be COMPLETE before the call (synchronise
+ * the producing stream first); the outputs are complete when the call returns. Like ctpn_page_cut the calls leave device_id the calling
+ * thread's current device. Every call allocates its device blocks and releases them before it returns, and releasing a block waits for the
+ * whole device: the results of a ctx's work in flight are not touched, but that work is held up for the moment. What is rebuilt:
+ * lib/utils/bbox.pyx (bbox_overlaps, bbox_intersections), lib/rpn_msr/anchor_target_layer_tf.py:10-276 and Network.build_loss with
+ * smooth_l1_dist (lib/networks/network.py:367-404) up to model_loss, plus the gradient of model_loss at the heads, where a backward pass would
+ * start. Not rebuilt: the backward pass through the network, the optimiser, the data layers, and total_loss's weight-decay term (it depends on
+ * the weights alone). Kernels: csrc/targets.hip; their per-thread text, pinned on the CPU: csrc/targets_dev.h.
+ *
+ *   ctpn_target_config_default  cfg12 = the CTPN_TARGET_CFG_DOUBLES settings of ctpn/text.yml over lib/fast_rcnn/config.py (TRAIN.*):
+ *       [0] RPN_NEGATIVE_OVERLAP 0.3   [1] RPN_POSITIVE_OVERLAP 0.7   [2] RPN_CLOBBER_POSITIVES 0   [3] RPN_FG_FRACTION 0.5
+ *       [4] RPN_BATCHSIZE 300 (0: no subsampling, the deterministic form for scoring)   [5] DONTCARE_AREA_INTERSECTION_HI 0.5
+ *       [6] PRECLUDE_HARD_SAMPLES 1   [7..10] RPN_BBOX_INSIDE_WEIGHTS 0, 1, 0, 1
+ *       [11] RPN_POSITIVE_WEIGHT -1: only negative values are built (the uniform weighting of anchor_target_layer_tf.py:211-217: outside
+ *            weight 1 on fg, 0 elsewhere); a value >= 0 is CTPN_ERR_UNSUPPORTED.
+ *
+ *   ctpn_bbox_overlaps  the lib/utils/bbox.pyx seam. boxes n x 4, query k x 4, out n x k, float64 host arrays. intersections = 0: bbox_overlaps
+ *       (bbox.pyx:15-55), out[i][j] = iw ih / (area(box i) + area(query j) - iw ih); intersections = 1: bbox_intersections (:57-93),
+ *       iw ih / area(query j). Bit-equal to the reference's arithmetic: widths and heights with + 1, the iw > 0 and ih > 0 gates (0 otherwise),
+ *       one IEEE double division, no FMA contraction. n = 0 or k = 0 returns CTPN_OK and writes nothing.
+ *
+ *   ctpn_anchor_targets  anchor_target_layer for n images that share one feature map hf x wf. im_info n x 3 (height, width, scale); ground truth
+ *       ragged: gt_boxes total x 5 (x1, y1, x2, y2, class) with gt_offsets (n + 1 ints from 0, never falling), gt_hard (total ints, nullable),
+ *       dontcare totalD x 4 with dc_offsets (both nullable); cfg12 (NULL: the defaults); seed for the subsampling. Outputs in the reference's
+ *       layouts: labels (n, hf, wf, 10); bbox_targets, inside_weights, outside_weights (n, hf, wf, 40); stats n x 6 = {inside anchors, fg before
+ *       sampling, bg before, fg after, bg after, anchors disabled by dontcare / hard}. Nullable stage outputs: labels_presample (like labels),
+ *       max_overlap (a double per anchor, 0 outside the image), argmax (an int per anchor, -1 outside). on_device = 1: every tensor-sized array,
+ *       in and out (gt_boxes, gt_hard, dontcare, the four outputs, the three stage outputs) is a device pointer on device_id, the
+ *       (n, hf, wf, 40) ones 16-byte aligned; im_info, the offsets, cfg12 and stats are always the host's.
+ *       The reference's semantics in its order of operations, quirks included:
+ *         - anchors: generate_anchors' ten (the proposal layer's table) on the 16-px grid; inside the image means x1 >= 0, y1 >= 0,
+ *           x2 < im_info width, y2 < im_info height (_allowed_border = 0). Everything below concerns inside anchors only;
+ *         - ground truth is cast float -> double before any arithmetic; overlaps are ctpn_bbox_overlaps' expression;
+ *         - argmax is numpy's: the first maximum wins;
+ *         - "gt_argmax_overlaps" is EVERY anchor whose overlap equals its column's maximum (np.where(overlaps == gt_max_overlaps), :136): a
+ *           ground-truth box that overlaps no inside anchor has maximum 0 and makes every anchor with overlap 0 to it foreground;
+ *         - label order: bg (max overlap < NEGATIVE), column-maximum fg, threshold fg (>= POSITIVE); with CLOBBER the bg rule last. Then
+ *           dontcare: -1 where the sum over the areas, in index order, of the covered fraction of the anchor exceeds INTERSECTION_HI. Then hard
+ *           boxes (gt_hard == 1, with PRECLUDE_HARD_SAMPLES): -1 where the maximum over the hard boxes is >= POSITIVE, and every hard box
+ *           disables its FIRST maximal anchor even at overlap 0;
+ *         - subsampling (RPN_BATCHSIZE > 0) is this library's own rule, numpy's Mersenne-Twister permutation is not reproduced:
+ *             key(image, anchor) = z ^ (z >> 31), z = (z ^ (z >> 27)) * 0x94D049BB133111EB, z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9,
+ *             z = seed ^ ((uint64)image << 32 | anchor)      (splitmix64's finaliser; image is the index in the call, anchor (y wf + x) 10 + a)
+ *           if fg exceeds int(FG_FRACTION * BATCHSIZE), the fg anchors with the smallest (key, anchor) pairs stay and the rest become -1; then
+ *           the same for bg with BATCHSIZE - fg_after. The finaliser is a bijection, so one image's keys never tie. npr.choice picks another
+ *           set of the same size;
+ *         - bbox_targets = bbox_transform(anchor, gt[argmax]) rounded to float, for EVERY inside anchor, in the reference's mixed precision:
+ *           the anchor's side and the differences, quotients and logs are double, but gt's width, height and centre are float32 arithmetic,
+ *           because bbox_transform gets the layer's float32 gt_boxes (only bbox_overlaps is given a float64 copy);
+ *         - inside weights: cfg12[7..10] on fg, 0 elsewhere; outside weights: 1 on fg, 0 elsewhere (:207-226);
+ *         - outside anchors: label -1, targets and weights 0;
+ *         - extension: with no ground-truth box the reference crashes on an empty argmax. Here an image with G = 0 gets label 0 on every inside
+ *           anchor (dontcare and sampling apply), zero targets, max_overlap 0 and argmax -1.
+ *
+ *   ctpn_rpn_loss  build_loss without the regulariser. heads: n x hf x wf rows of ld floats, ld 60 or 64 -- ctpn_get_tensor("heads") or the
+ *       heads GEMM's rows: [0, 40) ten (dx, dy, dw, dh), [40, 60) ten (bg, fg) logit pairs, [60, ld) never read. The four target arrays as
+ *       ctpn_anchor_targets writes them; on_device as there (heads, the four, d_heads). losses n x 3 doubles = {rpn_cross_entropy, rpn_loss_box,
+ *       model_loss}, counts n x 2 ints = {kept anchors (label != -1), fg anchors}, both the host's. d_heads (nullable): d model_loss / d heads
+ *       as float in the shape of heads, columns [60, ld) written as 0. Double arithmetic from the float inputs: ce = logsumexp(pair) -
+ *       pair[label] in the max-shifted form (stable for logits of +-1e4), its mean over the kept anchors; the box loss = the sum over kept
+ *       anchors of outside * smooth_l1(inside * (pred - target)) / (fg + 1), smooth_l1 with sigma2 = 9 and the strict < of network.py:370
+ *       (|x| = 1/9 takes the linear branch). An image with no kept anchor gets cross entropy 0.0 and counts[0] = 0 (TensorFlow's mean of
+ *       nothing is NaN). Sums run in a fixed order that depends on hf x wf alone: image i of a batch gives the bytes of image i alone.
+ *
+ * CTPN_ERR_ARG, before any device work: a null pointer, offsets that do not start at 0 or fall, hf x wf x 10 > 2^24 or n x hf x wf x 40 > 2^32,
+ * n > 65535, a cfg12 value that is not finite, a threshold or fraction outside [0, 1], a batch size that is negative or not whole, ld other
+ * than 60 / 64. CTPN_ERR_NODEVICE without a device: there is no CPU fallback. */
+#define CTPN_TARGET_CFG_DOUBLES 12
+int    ctpn_target_config_default(double* cfg12);
+int    ctpn_bbox_overlaps(int device_id, const double* boxes, int n, const double* query, int k, double* out, int intersections);
+int    ctpn_anchor_targets(int device_id, int n, int hf, int wf, const float* im_info, const float* gt_boxes, const int* gt_offsets, const int* gt_hard,
+                           const float* dontcare, const int* dc_offsets, const double* cfg12, unsigned long long seed, int on_device, float* labels,
+                           float* bbox_targets, float* inside_weights, float* outside_weights, int* stats, float* labels_presample,
+                           double* max_overlap, int* argmax);
+int    ctpn_rpn_loss(int device_id, int n, int hf, int wf, const float* heads, int ld, const float* labels, const float* bbox_targets,
+                     const float* inside_weights, const float* outside_weights, int on_device, double* losses, int* counts, float* d_heads);
+
 #ifdef __cplusplus
 }
 #endif

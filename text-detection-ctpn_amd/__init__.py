@@ -9,6 +9,9 @@ but every compute entry point raises CtpnError when the HIP library or a gfx950 
 from ._binding import CtpnError, lib_path, load_library, Context  # noqa: F401
 from .weights import MANIFEST, WEIGHT_FLOATS, make_synthetic_arena, arena_views  # noqa: F401
 from .page import detect_page, PageResult  # noqa: F401
+from .targets import (target_config_default, bbox_overlaps, bbox_intersections, anchor_targets, rpn_loss, score_pages,  # noqa: F401
+                      AnchorTargets, RpnLoss)
 
 __all__ = ["CtpnError", "lib_path", "load_library", "Context", "MANIFEST", "WEIGHT_FLOATS",
-           "make_synthetic_arena", "arena_views", "detect_page", "PageResult"]
+           "make_synthetic_arena", "arena_views", "detect_page", "PageResult",
+           "target_config_default", "bbox_overlaps", "bbox_intersections", "anchor_targets", "rpn_loss", "score_pages", "AnchorTargets", "RpnLoss"]

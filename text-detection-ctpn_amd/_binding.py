@@ -112,6 +112,11 @@ def _declare(lib):
         "ctpn_page_merge": (C.c_int, [i32p, C.c_int, f32p, C.c_int, i32p, C.c_int, C.c_int, C.c_float, f32p, f32p, i32p, C.c_int, i32p]),
         "ctpn_page_nms": (C.c_int, [i32p, i32p, f32p, C.c_int, C.c_int, C.c_float, C.c_int]),
         "ctpn_page_text_lines": (C.c_int, [f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f64p, C.c_int, f64p, C.c_int, i32p]),
+        "ctpn_target_config_default": (C.c_int, [f64p]),
+        "ctpn_bbox_overlaps": (C.c_int, [C.c_int, f64p, C.c_int, f64p, C.c_int, f64p, C.c_int]),
+        "ctpn_anchor_targets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, f32p, vp, i32p, vp, vp, i32p, f64p, C.c_ulonglong, C.c_int, vp, vp, vp, vp, i32p,
+                                          vp, vp, vp]),
+        "ctpn_rpn_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, f64p, i32p, vp]),
         "ctpn_detect": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f64p, C.c_int, i32p,
                                   f32p, i32p]),
         "ctpn_detect_submit": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int]),

@@ -498,6 +498,22 @@ int launch_ragged_blob(const uint8_t* canvas, float* blob, const int* heights_de
 struct PgTile;
 int launch_page_cut(const uint8_t* page_dev, long long pitch, const PgTile* tiles_dev, int n, int tile_h, int tile_w, uint8_t* out_dev, hipStream_t s);
 
+// targets.hip: the label side of training (the per-thread text, TgCfg and the sizes: targets_dev.h). Every pointer is device memory.
+//   launch_bbox_overlaps   out[n][k] = tg_overlap(boxes[i], query[j]) of lib/utils/bbox.pyx, both forms
+//   launch_anchor_targets  anchor_target_layer for n images on one hf x wf map. im_info [n][3]; gt [total][5] with offs [n + 1]; hard [total] or
+//                          null; dc [totalD][4] with dc_offs [n + 1], or null; scratch: colmax [max(total, 1)] (zeroed by the caller),
+//                          hardfirst [max(total, 1)] (filled with 0x7f bytes by the caller), flags [n * A] bytes; stats [n][6]; presample nullable; max_overlap and
+//                          argmax are the hand-over between the two passes and always given
+//   launch_rpn_loss        losses [n][3], counts [n][2], d_heads nullable
+struct TgCfg;
+int launch_bbox_overlaps(const double* boxes, int n, const double* query, int k, double* out, int intersections, hipStream_t s);
+int launch_anchor_targets(int n, int hf, int wf, const float* im_info, const float* gt, const int* offs, int max_g, const int* hard, const float* dc,
+                          const int* dc_offs, const TgCfg& cfg, unsigned long long seed, unsigned long long* colmax, int* hardfirst, uint8_t* flags,
+                          float* labels, float* targets, float* inside_w, float* outside_w, int* stats, float* presample, double* max_overlap, int* argmax,
+                          hipStream_t s);
+int launch_rpn_loss(int n, int hf, int wf, const float* heads, int ld, const float* labels, const float* targets, const float* inside_w,
+                    const float* outside_w, double* losses, int* counts, float* d_heads, hipStream_t s);
+
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 }  // namespace ctpn

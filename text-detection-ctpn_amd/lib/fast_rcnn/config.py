@@ -1,7 +1,8 @@
 """Global `cfg` for the inference hot path; same key names, defaults and merge rules as the reference's
 lib/fast_rcnn/config.py (cfg :7-226, _merge_a_into_b :256-286, cfg_from_file :288-294, cfg_from_list :296-316), so
-the reference's ctpn/text.yml is readable as-is. TRAIN.* keys are accepted and stored but nothing here reads them
-(training is out of scope).
+the reference's ctpn/text.yml is readable as-is. TRAIN.* keys are accepted and stored; the one reader is
+lib/rpn_msr/anchor_target_layer_tf.py (the RPN_* / DONTCARE / PRECLUDE settings of the anchor target layer; a key missing here takes the
+reference's config.py default there). The rest of training is out of scope.
 """
 import os.path as osp
 from ast import literal_eval

@@ -1127,6 +1127,51 @@ int    ctpn_anchor_targets(int device_id, int n, int hf, int wf, const float* im
 int    ctpn_rpn_loss(int device_id, int n, int hf, int wf, const float* heads, int ld, const float* labels, const float* bbox_targets,
                      const float* inside_weights, const float* outside_weights, int on_device, double* losses, int* counts, float* d_heads);
 
+/* ---- the recurrent tail: forward with saved activations, backward ----
+ * What ctpn_rpn_loss's d_heads is for: the gradient of model_loss at the weights people fine-tune, everything behind rpn_conv/3x3 -- the BiLSTM,
+ * the lstm_o FC and the two heads, the LAST TEN manifest entries, CTPN_TAIL_FLOATS contiguous floats at the arena's end (arena[17 074 496:]).
+ * Two stateless calls with ctpn_anchor_targets' conventions (no ctx, own non-blocking stream, one synchronisation at the end, device blocks
+ * allocated and released by the call, the caller's current device put back, on_device = 1: every tensor-sized array is a device pointer, no CPU
+ * fallback). All arithmetic is fp32, matrix products on the exact-fp32 MFMA. No floating-point atomics: two calls on the same inputs give the
+ * same bytes. Not built: the backward of rpn_conv/3x3 and the 13 VGG convs (d_x is where it would start), Adam, RMSProp, weight decay, the
+ * data layers; ctpn/finetune_tail.py is the Momentum branch of lib/fast_rcnn/train.py on the host.
+ *
+ *   x     rpn_conv/3x3's output, a plain n x hf x wf x 512 array: what ctpn_get_tensor("rpn_conv/3x3") returns.
+ *   tail  the ten tensors in manifest order and TF's layout: fw kernel [640][512] (rows 0..511 the input part, 512..639 the recurrent part;
+ *         gate columns i | j | f | o), fw bias [512], bw kernel, bw bias, lstm_o/weights [256][512], lstm_o/biases [512], rpn_bbox_pred/weights
+ *         [512][40], /biases [40], rpn_cls_score/weights [512][20], /biases [20]. Packing, the gate-column permutation and the transposes happen
+ *         inside the call.
+ *   saved caller-owned plain memory, ctpn_tail_saved_floats(n, hf, wf) = 2048 floats per cell, M = n hf wf cells in (image, row, column) order:
+ *             [0, 256 M)         lstm_out  [M][256]      fw 128 | bw 128
+ *             [256 M, 768 M)     lstm_o    [M][512]
+ *             [768 M, 2048 M)    gates     [M][2 directions][5][128]: the activated i, j (tanh), f (= sigmoid(z_f + 1.0)), o, and the cell state c
+ *
+ *   ctpn_tail_forward   heads: n hf wf rows of 64 floats, columns 0..39 rpn_bbox_pred, 40..59 rpn_cls_score, 60..63 zero. saved: nullable. The
+ *       projection, the FC and the heads are the fp32 forward's own GEMM launches, the recurrence is its exact-gate kernel in a form that also
+ *       stores the gates: heads and the saved lstm_out are the bytes of a CTPN_PREC_FP32 ctx's "heads" and "lstm_out" for that ctx's own
+ *       "rpn_conv/3x3".
+ *   ctpn_tail_backward  d_heads: rows of 64 floats, columns 60..63 ignored (they may hold anything). d_tail: CTPN_TAIL_FLOATS floats in tail's
+ *       layout, every one written. d_x (nullable): n x hf x wf x 512. BPTT of the TF-1.3 LSTMCell from the saved activations (forget bias 1.0,
+ *       zero initial state, bw runs right to left). The reduction over cells in every weight and bias gradient runs in a FIXED ORDER THAT DEPENDS
+ *       ON n hf wf ALONE: the cells are cut into consecutive blocks of B = 256 cells, B doubled until at most 32 blocks cover them; inside a
+ *       block an element is an fma chain over the cells in ascending order (a bias: eight interleaved running sums, added pairwise), and the blocks' partial sums are added left to
+ *       right. So a call on M <= 256 cells returns one block's sum, and the gradient of M = 256 k cells whose blocks end at sequence ends is
+ *       exactly ((g_1 + g_2) + ...) + g_k of the calls on the blocks alone.
+ *
+ * CTPN_ERR_ARG, before any device work: a null pointer (saved of the forward and d_x excepted), n, hf or wf < 1, n x hf x wf > 2^21 cells,
+ * on_device other than 0 / 1, a device pointer that is not 16-byte aligned. ctpn_tail_saved_floats returns -1 for such a shape.
+ * CTPN_ERR_NODEVICE without a device.
+ *
+ * ctpn_debug_tail_bptt (test hook, host arrays): the backward recurrence alone. gates [rows * T][2][5][128] (the saved block's third part),
+ *   d_lstm_out [rows * T][256], tail as above (only the two recurrent parts kernel[512:640] are read) -> d_pre [rows * T][1024], the gradient
+ *   at the gate pre-activations in TF's column order (fw i | j | f | o, then bw): the stage ctpn_tail_backward keeps to itself. */
+#define CTPN_TAIL_FLOATS 818748
+long long ctpn_tail_saved_floats(int n, int hf, int wf);
+int    ctpn_tail_forward(int device_id, int n, int hf, int wf, const float* x, const float* tail, int on_device, float* heads, float* saved);
+int    ctpn_tail_backward(int device_id, int n, int hf, int wf, const float* x, const float* tail, const float* saved, const float* d_heads,
+                          int on_device, float* d_tail, float* d_x);
+int    ctpn_debug_tail_bptt(int device_id, int rows, int T, const float* d_lstm_out, const float* gates, const float* tail, float* d_pre);
+
 #ifdef __cplusplus
 }
 #endif

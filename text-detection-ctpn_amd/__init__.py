@@ -11,7 +11,10 @@ from .weights import MANIFEST, WEIGHT_FLOATS, make_synthetic_arena, arena_views 
 from .page import detect_page, PageResult  # noqa: F401
 from .targets import (target_config_default, bbox_overlaps, bbox_intersections, anchor_targets, rpn_loss, score_pages,  # noqa: F401
                       AnchorTargets, RpnLoss)
+from .tail_grad import (tail_forward, tail_backward, tail_views, tail_gradients, momentum_step, TailForward, TailBackward,  # noqa: F401
+                        TAIL_FLOATS, TAIL_OFFSET)
 
 __all__ = ["CtpnError", "lib_path", "load_library", "Context", "MANIFEST", "WEIGHT_FLOATS",
            "make_synthetic_arena", "arena_views", "detect_page", "PageResult",
-           "target_config_default", "bbox_overlaps", "bbox_intersections", "anchor_targets", "rpn_loss", "score_pages", "AnchorTargets", "RpnLoss"]
+           "target_config_default", "bbox_overlaps", "bbox_intersections", "anchor_targets", "rpn_loss", "score_pages", "AnchorTargets", "RpnLoss",
+           "tail_forward", "tail_backward", "tail_views", "tail_gradients", "momentum_step", "TailForward", "TailBackward", "TAIL_FLOATS", "TAIL_OFFSET"]

@@ -91,10 +91,11 @@ __device__ __forceinline__ void lstm_pre_values(const LstmPreRaw<PRE16>& raw, f3
     for (int g = 0; g < 4; ++g) pre[g] = raw.v[g];
   }
 }
-template <bool FAST, bool PRE16>
-__global__ __launch_bounds__(512) void bilstm_kernel(const void* __restrict__ xp, const float* __restrict__ wh,
-                                                     float* __restrict__ out, int rows, int T) {
-  __shared__ __attribute__((aligned(16))) float hbuf[2][LSTM_ROWS][LSTM_HPITCH];
+// SAVE: also stores what a backward pass needs, at gates [rows * T][2 directions][5: i, j, f, o, c][128] -- the activated gates and the cell state
+// of every step, the values the update below computes anyway (the exact-gate fp32 form only: launch_bilstm_save). Nothing else differs.
+template <bool FAST, bool PRE16, bool SAVE>
+__device__ __forceinline__ void bilstm_body(float (&hbuf)[2][LSTM_ROWS][LSTM_HPITCH], const void* __restrict__ xp, const float* __restrict__ wh,
+                                            float* __restrict__ out, int rows, int T, float* __restrict__ gates) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int dir = blockIdx.y;
@@ -153,6 +154,7 @@ __global__ __launch_bounds__(512) void bilstm_kernel(const void* __restrict__ xp
           acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[g][qq * 4 + e], hf[qq][e], acc[g], 0, 0, 0);
     // cell update: acc[g][e] is gate g of unit u0+e for row (lane&15)
     f32x4 h;
+    f32x4 sv[SAVE ? 5 : 1];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float ig = FAST ? fast_sigmoid(acc[0][e]) : sigmoidf_(acc[0][e]);
@@ -162,11 +164,30 @@ __global__ __launch_bounds__(512) void bilstm_kernel(const void* __restrict__ xp
       const float cn = fg * c[e] + ig * jg;
       c[e] = cn;
       h[e] = og * (FAST ? fast_tanh(cn) : tanhf_(cn));
+      if constexpr (SAVE) { sv[0][e] = ig; sv[1][e] = jg; sv[2][e] = fg; sv[3][e] = og; sv[4][e] = cn; }
     }
     *(f32x4*)(&hbuf[cur ^ 1][row_l][u0]) = h;
     if (row_ok) *(f32x4*)(orow + (size_t)t * 256) = h;
+    if constexpr (SAVE) {
+      if (row_ok) {
+        float* g = gates + (((size_t)row_c * T + t) * 2 + dir) * 5 * 128 + u0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) *(f32x4*)(g + k * 128) = sv[k];
+      }
+    }
     __syncthreads();
   }
+}
+template <bool FAST, bool PRE16>
+__global__ __launch_bounds__(512) void bilstm_kernel(const void* __restrict__ xp, const float* __restrict__ wh,
+                                                     float* __restrict__ out, int rows, int T) {
+  __shared__ __attribute__((aligned(16))) float hbuf[2][LSTM_ROWS][LSTM_HPITCH];
+  bilstm_body<FAST, PRE16, false>(hbuf, xp, wh, out, rows, T, nullptr);
+}
+__global__ __launch_bounds__(512) void bilstm_save_kernel(const void* __restrict__ xp, const float* __restrict__ wh, float* __restrict__ out,
+                                                          int rows, int T, float* __restrict__ gates) {
+  __shared__ __attribute__((aligned(16))) float hbuf[2][LSTM_ROWS][LSTM_HPITCH];
+  bilstm_body<false, false, true>(hbuf, xp, wh, out, rows, T, gates);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -384,6 +405,14 @@ BilstmPlan bilstm_plan(int rows, int split_bf16, int fast_gates) {
   // a few rows (one or two 600 x 900 images: 37 / 74): four rows per workgroup, the gate math spread over all lanes; identical bits
   if (split_bf16 && rows <= 128) { form = 3; per_wg = LSTM_FEW; }
   return BilstmPlan{form, per_wg};
+}
+
+// the exact-gate fp32 recurrence (form 0 on fp32 pre-activations: the same MFMA sequence, the same gate forms, the same lstm_out bits) that also
+// fills gates [rows * T][2][5][128] (tail_grad_dev.h tb_gate_index)
+int launch_bilstm_save(const float* xp, const float* wh, float* out, float* gates, int rows, int T, hipStream_t s) {
+  if (rows <= 0 || T <= 0) return fail(CTPN_ERR_ARG, "bilstm: empty problem");
+  hipLaunchKernelGGL(bilstm_save_kernel, dim3((rows + LSTM_ROWS - 1) / LSTM_ROWS, 2), dim3(512), 0, s, (const void*)xp, wh, out, rows, T, gates);
+  return launch_status("bilstm_save");
 }
 
 int launch_bilstm(const void* xp, int xp_is_f16, const float* wh, float* out, int rows, int T, hipStream_t s, int split_bf16, int fast_gates) {

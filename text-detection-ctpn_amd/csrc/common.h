@@ -514,6 +514,21 @@ int launch_anchor_targets(int n, int hf, int wf, const float* im_info, const flo
 int launch_rpn_loss(int n, int hf, int wf, const float* heads, int ld, const float* labels, const float* targets, const float* inside_w,
                     const float* outside_w, double* losses, int* counts, float* d_heads, hipStream_t s);
 
+// the backward pass through the recurrent tail (tail_grad.hip; the per-thread text, the saved block and the d_tail offsets: tail_grad_dev.h).
+// Every pointer is device memory; `tail` is the arena's last ten tensors in TF's layout.
+//   launch_bilstm_save  bilstm.hip: launch_bilstm's exact-gate fp32 form, which also fills gates [rows * T][2][5][128]
+//   launch_bptt         d_pre [rows * T][1024] (TF column order, fw | bw) from d_lstm_out [rows * T][256] and the saved gates
+//   launch_tail_tn      out [K][ldo] (N columns) = A^T dY over M cells in blocks of tb_block_cells(M); parts: scratch of partials x K x N floats;
+//                       shift -1 / +1: A's row is the cell one step before / after in its sequence of T, zero at the sequence's end
+//   launch_tail_colsum  out [N] = column sums of dY in the same block order; parts: partials x N floats
+//   launch_mask_dheads  out [M][64] = d_heads with columns 60..63 cleared; launch_heads_rows: out [512][64] = bbox | cls | 0 rows
+int launch_bilstm_save(const float* xp, const float* wh, float* out, float* gates, int rows, int T, hipStream_t s);
+int launch_bptt(const float* d_lstm_out, const float* gates, const float* tail, float* d_pre, int rows, int T, hipStream_t s);
+int launch_tail_tn(const float* a, int lda, int shift, const float* dy, int ldy, long long M, int T, int K, int N, float* parts, float* out, int ldo, hipStream_t s);
+int launch_tail_colsum(const float* dy, int ldy, long long M, int N, float* parts, float* out, hipStream_t s);
+int launch_mask_dheads(const float* d_heads, float* out, long long M, hipStream_t s);
+int launch_heads_rows(const float* tail, float* out, hipStream_t s);
+
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 }  // namespace ctpn

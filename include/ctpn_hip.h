@@ -3,7 +3,9 @@
  *
  * Every entry point is `extern "C"`, takes plain pointers and sizes, returns an int status
  * (0 = CTPN_OK, negative = error; ctpn_last_error() gives the text) and never throws.
- * One ctpn_ctx per GPU / per host thread; a ctx owns its HIP stream and its HBM arena.
+ * A ctx owns its HIP streams and its HBM arena. Threads: any number of ctxs per device; each ctx is used by one host thread at a time;
+ * distinct ctxs, and the calls that take no ctx, may run concurrently from different host threads (what they share per device is
+ * guarded inside the library: INTEGRATION.md, "Threads"). One ctx used from two threads at once is outside the contract.
  *
  * Each declaration cites the reference interface (paths relative to the upstream tree of
  * eragonruan/text-detection-ctpn) that it replaces; INTEGRATION.md shows the ctypes stub a

@@ -107,10 +107,11 @@ static inline uint16_t host_f32_to_bf16(float f) {
 static inline uint16_t host_f32_to_f16(float f) { const _Float16 h = (_Float16)f; uint16_t b; std::memcpy(&b, &h, 2); return b; }
 
 // ---------------------------------------------------------------------------------------------
-// Launch state is PER DEVICE: the ABI promises one ctx per GPU, and one process may hold ctxs on several GPUs. The CU count and the
+// Launch state is PER DEVICE: the ABI allows any number of ctxs per device (each used by one host thread at a time; distinct ctxs and the
+// stateless calls may run concurrently), and one process may hold ctxs on several GPUs. The CU count and the
 // "MaxDynamicSharedMemorySize already raised for this kernel" flags are indexed by the current device (a function attribute set on
-// device 0 does not carry over to device 1), under one mutex. `done` is one flag array per kernel instantiation (a function-local
-// static of the launcher template).
+// device 0 does not carry over to device 1), under one mutex, which is what two ctxs launching from two host threads meet in. `done` is one
+// flag array per kernel instantiation (a function-local static of the launcher template).
 // ---------------------------------------------------------------------------------------------
 constexpr int CTPN_MAX_DEV = 16;
 inline std::mutex& launch_state_mutex() { static std::mutex mu; return mu; }

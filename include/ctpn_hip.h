@@ -1135,8 +1135,8 @@ int    ctpn_rpn_loss(int device_id, int n, int hf, int wf, const float* heads, i
  * Two stateless calls with ctpn_anchor_targets' conventions (no ctx, own non-blocking stream, one synchronisation at the end, device blocks
  * allocated and released by the call, the caller's current device put back, on_device = 1: every tensor-sized array is a device pointer, no CPU
  * fallback). All arithmetic is fp32, matrix products on the exact-fp32 MFMA. No floating-point atomics: two calls on the same inputs give the
- * same bytes. Not built: the backward of rpn_conv/3x3 and the 13 VGG convs (d_x is where it would start), Adam, RMSProp, weight decay, the
- * data layers; ctpn/finetune_tail.py is the Momentum branch of lib/fast_rcnn/train.py on the host.
+ * same bytes. d_x is where the backward of rpn_conv/3x3 and the 13 VGG convs starts ("the conv stack: backward", below). Not built: Adam,
+ * RMSProp, weight decay, the data layers; ctpn/finetune_tail.py is the Momentum branch of lib/fast_rcnn/train.py on the host.
  *
  *   x     rpn_conv/3x3's output, a plain n x hf x wf x 512 array: what ctpn_get_tensor("rpn_conv/3x3") returns.
  *   tail  the ten tensors in manifest order and TF's layout: fw kernel [640][512] (rows 0..511 the input part, 512..639 the recurrent part;
@@ -1173,6 +1173,43 @@ int    ctpn_tail_forward(int device_id, int n, int hf, int wf, const float* x, c
 int    ctpn_tail_backward(int device_id, int n, int hf, int wf, const float* x, const float* tail, const float* saved, const float* d_heads,
                           int on_device, float* d_tail, float* d_x);
 int    ctpn_debug_tail_bptt(int device_id, int rows, int T, const float* d_lstm_out, const float* gates, const float* tail, float* d_pre);
+
+/* ---- the conv stack: backward ----
+ * Where ctpn_tail_backward's d_x goes on: the gradient through rpn_conv/3x3 and the 13 VGG convs back to conv1_1, one layer per call, so that
+ * all 17 893 244 weights have a gradient (the reference trains all of them: lib/networks/VGGnet_train.py freezes no conv). Stateless calls with
+ * the tail's conventions (no ctx, own non-blocking stream, one synchronisation at the end, device blocks allocated and released by the call, the
+ * caller's current device put back, on_device = 1: every tensor-sized array is a device pointer, 16-byte aligned; no CPU fallback). All
+ * arithmetic is fp32, products on the exact-fp32 MFMA, no floating-point atomics: two calls on the same inputs give the same bytes.
+ * ctpn_amd.network_gradients (Python) walks these calls over a ctx's stored activations. Not built: weight decay, Adam, RMSProp, the
+ * learning-rate schedule, the data layers, a device-resident ctpn_get_tensor (network_gradients round-trips activations through the host).
+ *
+ * Tensors are plain and dense: activations NHWC, w_hwio TF's [3][3][ci][co], padding SAME (zeros outside the image; a tap never crosses from
+ * one image of the batch into the next). ci is 3 (conv1_1; d_x must then be NULL) or a multiple of 32, co a multiple of 64, both <= 2048.
+ *
+ *   ctpn_conv3x3_backward   the layer y = relu(conv(x, w) + b). x: n h w ci, the layer's input; y: n h w co, its stored post-ReLU output;
+ *       d_y: the gradient at y. With dZ = d_y where y > 0 and 0 elsewhere:
+ *         d_x[n,i,j,c]    = sum over ky, kx, o of dZ[n, i-ky+1, j-kx+1, o] w[ky][kx][c][o]     (nullable) one fma chain per element
+ *         d_w[ky][kx][c][o] = sum over pixels of x[n, i+ky-1, j+kx-1, c] dZ[n,i,j,o]
+ *         d_b[o]          = sum over pixels of dZ[n,i,j,o]
+ *       The sums over pixels run in a FIXED ORDER THAT DEPENDS ON (n, h, w, ci, co) ALONE, never on the device: the n h w pixels are cut, in
+ *       (image, row, column) order, into `blocks` consecutive blocks of `block_pixels` (the last one may be short); inside a block an element
+ *       of d_w is an fma chain over the pixels in ascending order (of d_b: eight interleaved running sums, added pairwise, as in the tail), and
+ *       the blocks' partial sums are added left to right.
+ *   ctpn_conv3x3_backward_plan   that plan, pure host arithmetic, no device: with tiles = ceil(ci / 16) (co / 64), the blocks wanted are
+ *       ceil(1024 / tiles) held to 1 .. 32; block_pixels = ceil(n h w / wanted) rounded up to a multiple of 64; blocks = ceil(n h w /
+ *       block_pixels) <= 32. (conv1_2 at 600 x 900: 32 blocks of 16 896 pixels; conv5_x: 4 blocks of 576.) Scratch is blocks copies of d_w.
+ *   ctpn_maxpool2x2_backward   the 2x2 / stride 2 VALID max-pool. y_full: n h w c, the pool's input; d_pool: n (h/2) (w/2) c; d_full: n h w c,
+ *       EVERY element written: d_pool at the FIRST maximum of each window in (row, column) scan order (torch's rule; exact ties are real in
+ *       ReLU data), zero elsewhere, zero in the last row / column of an odd-sized map. c is a multiple of 4. With h or w = 1 the pooled map
+ *       is empty: d_full is all zeros, d_pool is not read and may be NULL.
+ *
+ * CTPN_ERR_ARG, before any device work: a null pointer (d_x, and d_pool of an empty pooled map, excepted), a size < 1, other channel counts, a
+ * non-NULL d_x with ci = 3, on_device other than 0 / 1, a device pointer that is not 16-byte aligned, n h w beyond 2^28 pixels.
+ * CTPN_ERR_NODEVICE without a device. */
+int    ctpn_conv3x3_backward(int device_id, int n, int h, int w, int ci, int co, const float* x, const float* w_hwio, const float* y,
+                             const float* d_y, int on_device, float* d_w, float* d_b, float* d_x);
+int    ctpn_maxpool2x2_backward(int device_id, int n, int h, int w, int c, const float* y_full, const float* d_pool, int on_device, float* d_full);
+int    ctpn_conv3x3_backward_plan(int n, int h, int w, int ci, int co, long long* block_pixels, int* blocks);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,9 @@ def _declare(lib):
         "ctpn_tail_forward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
         "ctpn_tail_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]),
         "ctpn_debug_tail_bptt": (C.c_int, [C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p]),
+        "ctpn_conv3x3_backward": (C.c_int, [C.c_int] * 6 + [vp, vp, vp, vp, C.c_int, vp, vp, vp]),
+        "ctpn_maxpool2x2_backward": (C.c_int, [C.c_int] * 5 + [vp, vp, C.c_int, vp]),
+        "ctpn_conv3x3_backward_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
         "ctpn_detect": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f64p, C.c_int, i32p,
                                   f32p, i32p]),
         "ctpn_detect_submit": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int]),
@@ -1219,7 +1222,8 @@ class Context:
         if a.size != WEIGHT_FLOATS:
             raise ValueError("weight arena must hold %d floats, got %d" % (WEIGHT_FLOATS, a.size))
         _check(self._lib.ctpn_load_weights_host(self._h, _ptr(a, C.c_float)))
-        self.tail_weights = a[-818748:].copy()      # the last ten tensors (tail_grad.TAIL_FLOATS): what tail_gradients differentiates at
+        self.arena_weights = a.copy()               # what network_gradients differentiates at
+        self.tail_weights = self.arena_weights[-818748:]      # the last ten tensors (tail_grad.TAIL_FLOATS): what tail_gradients differentiates at
 
     def load_weights_device(self, dev_ptr):
         """ctpn_load_weights_device: the arena from this device's memory. The copy runs on the ctx's stream: synchronise whatever filled the

@@ -530,6 +530,17 @@ int launch_tail_colsum(const float* dy, int ldy, long long M, int N, float* part
 int launch_mask_dheads(const float* d_heads, float* out, long long M, hipStream_t s);
 int launch_heads_rows(const float* tail, float* out, hipStream_t s);
 
+// the backward pass through one conv + bias + ReLU and through the 2x2 max-pool (conv_grad.hip; the per-thread text and the block plan:
+// conv_grad_dev.h). Every pointer is device memory, plain dense fp32: activations [M = n h w][channels], w [9][ci][co].
+//   launch_conv_grad_mask  dz = d_y (y > 0)
+//   launch_conv_grad_dx    dx [M][ci] from dz and w; ci a multiple of 32
+//   launch_conv_grad_dw    d_w [9][ci][co] and d_b [co] from x and dz in cg_plan's blocks; parts: blocks x 9 ci co floats, bparts: blocks x co
+//   launch_pool_grad       d_full [n][h][w][c] from the full map y and d_pool [n][h / 2][w / 2][c]
+int launch_conv_grad_mask(const float* d_y, const float* y, float* dz, long long M, int co, hipStream_t s);
+int launch_conv_grad_dx(const float* dz, const float* wt, int h, int w, int ci, int co, long long M, float* dx, hipStream_t s);
+int launch_conv_grad_dw(const float* x, const float* dz, int h, int w, int ci, int co, long long M, float* parts, float* bparts, float* d_w, float* d_b, hipStream_t s);
+int launch_pool_grad(const float* y, const float* d_pool, int n, int h, int w, int c, float* d_full, hipStream_t s);
+
 static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 }  // namespace ctpn

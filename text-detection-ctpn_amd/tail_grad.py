@@ -1,8 +1,8 @@
 """The backward pass through the recurrent tail over the C ABI (include/ctpn_hip.h, "the recurrent tail: forward with saved activations,
 backward"): the gradient of the RPN loss at the BiLSTM, the lstm_o FC and the two heads -- the arena's last ten tensors, TAIL_FLOATS floats.
 tail_forward / tail_backward take numpy arrays, or torch tensors on the device, which go through on_device = 1 with no host copy;
-tail_gradients chains a ctx's forward into targets, loss and gradient. Not built: the backward of the 14 convs in front of the tail (d_x is
-where it would start), Adam, RMSProp, weight decay, the data layers (ctpn/finetune_tail.py is the Momentum branch on the host)."""
+tail_gradients chains a ctx's forward into targets, loss and gradient. The backward of the 14 convs in front of the tail starts at d_x:
+conv_grad.py. Not built: Adam, RMSProp, weight decay, the data layers (ctpn/finetune_tail.py is the Momentum branch on the host)."""
 import collections
 import ctypes as C
 

@@ -260,6 +260,7 @@ int ctpn_feat_shape(ctpn_ctx* ctx, int* n, int* hf, int* wf);
  * names: conv1_1 .. conv5_3, pool1..pool4, rpn_conv/3x3, lstm_pre, lstm_out, lstm_o, heads,
  * rpn_cls_prob_reshape (n,hf,wf,20), rpn_bbox_pred (n,hf,wf,40). Synchronises the stream. */
 int ctpn_get_tensor(ctpn_ctx* ctx, const char* name, float* out_host, size_t capacity_floats, int shape4[4]);
+/* The same tensor left in HBM, unpacked by a kernel: the training-side companion header, ctpn_hip_train.h. */
 
 /* ---- proposal layer -----------------------------------------------------------------------
  * Replaces: Network.proposal_layer / proposal_layer (lib/networks/network.py:207-222,
@@ -1135,8 +1136,8 @@ int    ctpn_rpn_loss(int device_id, int n, int hf, int wf, const float* heads, i
  * Two stateless calls with ctpn_anchor_targets' conventions (no ctx, own non-blocking stream, one synchronisation at the end, device blocks
  * allocated and released by the call, the caller's current device put back, on_device = 1: every tensor-sized array is a device pointer, no CPU
  * fallback). All arithmetic is fp32, matrix products on the exact-fp32 MFMA. No floating-point atomics: two calls on the same inputs give the
- * same bytes. d_x is where the backward of rpn_conv/3x3 and the 13 VGG convs starts ("the conv stack: backward", below). Not built: Adam,
- * RMSProp, weight decay, the data layers; ctpn/finetune_tail.py is the Momentum branch of lib/fast_rcnn/train.py on the host.
+ * same bytes. d_x is where the backward of rpn_conv/3x3 and the 13 VGG convs starts ("the conv stack: backward", below). The optimisers:
+ * "the solver step"; ctpn/finetune_tail.py is the Momentum branch of lib/fast_rcnn/train.py on the host. Not built: the data layers.
  *
  *   x     rpn_conv/3x3's output, a plain n x hf x wf x 512 array: what ctpn_get_tensor("rpn_conv/3x3") returns.
  *   tail  the ten tensors in manifest order and TF's layout: fw kernel [640][512] (rows 0..511 the input part, 512..639 the recurrent part;
@@ -1180,8 +1181,8 @@ int    ctpn_debug_tail_bptt(int device_id, int rows, int T, const float* d_lstm_
  * the tail's conventions (no ctx, own non-blocking stream, one synchronisation at the end, device blocks allocated and released by the call, the
  * caller's current device put back, on_device = 1: every tensor-sized array is a device pointer, 16-byte aligned; no CPU fallback). All
  * arithmetic is fp32, products on the exact-fp32 MFMA, no floating-point atomics: two calls on the same inputs give the same bytes.
- * ctpn_amd.network_gradients (Python) walks these calls over a ctx's stored activations. Not built: weight decay, Adam, RMSProp, the
- * learning-rate schedule, the data layers, a device-resident ctpn_get_tensor (network_gradients round-trips activations through the host).
+ * ctpn_amd.network_gradients (Python) walks these calls over a ctx's stored activations fetched to the host; network_gradients_device walks
+ * them over the tensors of ctpn_hip_train.h's device-resident form of ctpn_get_tensor, and "the solver step" (below) is the optimiser. Not built: the data layers.
  *
  * Tensors are plain and dense: activations NHWC, w_hwio TF's [3][3][ci][co], padding SAME (zeros outside the image; a tap never crosses from
  * one image of the batch into the next). ci is 3 (conv1_1; d_x must then be NULL) or a multiple of 32, co a multiple of 64, both <= 2048.
@@ -1210,6 +1211,45 @@ int    ctpn_conv3x3_backward(int device_id, int n, int h, int w, int ci, int co,
                              const float* d_y, int on_device, float* d_w, float* d_b, float* d_x);
 int    ctpn_maxpool2x2_backward(int device_id, int n, int h, int w, int c, const float* y_full, const float* d_pool, int on_device, float* d_full);
 int    ctpn_conv3x3_backward_plan(int n, int h, int w, int ci, int co, long long* block_pixels, int* blocks);
+
+/* ---- the solver step ----
+ * What the gradient is for: one step of lib/fast_rcnn/train.py's optimiser over a flat fp32 vector -- the arena, or the part of it that is
+ * trained -- with the gradient of total_loss = model_loss + the L2 terms formed on the way: tf.clip_by_global_norm(grads, clip), then
+ * tf.train.MomentumOptimizer, AdamOptimizer (ApplyAdam) or RMSPropOptimizer (ApplyRMSProp). Stateless calls with the gradient units'
+ * conventions (no ctx, own non-blocking stream, device blocks allocated and released by the call, the caller's current device put back, no CPU
+ * fallback). on_device = 1: w, g, s1, s2 are device pointers, at ANY 4-byte alignment (16-byte aligned vectors are read and written 16 bytes
+ * at a time; others 4 bytes at a time by the same threads in the same order); seg_end, seg_decay, hyper8 and out2 are always host arrays.
+ *
+ *   ctpn_solver_plan      pure host arithmetic: the vector is cut into `blocks` consecutive blocks of `block_floats` (the last may be short),
+ *       block_floats = ceil(count / 2048) rounded up to a multiple of 1024, blocks <= 2048. THE ORDER OF BOTH SUMS DEPENDS ON count ALONE:
+ *       inside a block, lane l of 256 adds the terms of elements 4 q .. 4 q + 3 for q = l, l + 256, ... in ascending order to one running
+ *       double; the 256 lane sums are added pairwise (v[i] += v[i + stride], stride 128, 64, .. 1); the blocks' sums are added left to right on
+ *       the host. No atomics: two calls on the same inputs give the same bytes.
+ *   ctpn_solver_defaults  hyper8 of a solver: [0] lr  [1] momentum | beta1 | decay  [2] - | beta2 | RMS momentum  [3] - | epsilon | epsilon
+ *       [4] clip norm  [5] the value s1 starts at  [6] the value s2 starts at  [7] zero. Momentum: 0.001, 0.9. Adam: 0.001, 0.9, 0.999, 1e-8.
+ *       RMS: 0.001, 0.9, 0.0, 1e-10, and [5] = 1.0: TF's `rms` slot starts at ONES. Clip norm 10.0 for all three.
+ *   ctpn_solver_step      updates w, s1, s2 (s1: the momentum accumulator | Adam's m | RMS's ms; s2: unused and nullable | v | mom) in place.
+ *       seg_end[n_seg] ascending, the last equal to count; element e belongs to the first segment with e < seg_end; seg_decay[n_seg] is the
+ *       segment's weight decay d. t is the 1-based step (Adam's bias correction). Per element, fp32, every operation rounded on its own:
+ *         ge = g + d w                       (d = 0: ge = g, the product is not formed)
+ *         out2[0] = sum ge^2,  out2[1] = sum d w^2 / 2      in double, in the plan's order, of the weights BEFORE the update
+ *         norm = sqrt(out2[0]) in double;  gc = ge (float)(clip / norm) if norm > clip, else ge
+ *         Momentum   s1 = mu s1 + gc;  w = w - lr s1
+ *         Adam       lr_t = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)) in double on the host;
+ *                    s1 += (gc - s1)(1.0f - beta1);  s2 += (gc gc - s2)(1.0f - beta2);  w -= (s1 lr_t) / (sqrtf(s2) + eps)
+ *         RMS        s1 += (gc gc - s1)(1.0f - decay);  s2 = s2 momentum + (gc lr) / sqrtf(s1 + eps);  w -= s2
+ *       A non-finite out2[0] is CTPN_ERR_ARG with out2 filled and w, s1, s2 untouched.
+ *
+ * CTPN_ERR_ARG, before any device work: an unknown solver, count outside 1 .. 2^40, a null pointer (s2 of Momentum excepted), n_seg outside
+ * 1 .. 64, segments not ascending or not ending at count, a non-finite decay or hyper value, a clip norm <= 0, t < 1, on_device other than
+ * 0 / 1, a pointer that is not 4-byte aligned. CTPN_ERR_NODEVICE without a device (ctpn_solver_plan and ctpn_solver_defaults need none). */
+#define CTPN_SOLVER_MOMENTUM 0
+#define CTPN_SOLVER_ADAM     1
+#define CTPN_SOLVER_RMS      2
+int    ctpn_solver_plan(long long count, long long* block_floats, int* blocks);
+int    ctpn_solver_defaults(int solver, double* hyper8);
+int    ctpn_solver_step(int device_id, int solver, long long count, float* w, const float* g, float* s1, float* s2, const long long* seg_end,
+                        const float* seg_decay, int n_seg, const double* hyper8, long long t, int on_device, double* out2);
 
 #ifdef __cplusplus
 }

@@ -14,9 +14,12 @@ from .targets import (target_config_default, bbox_overlaps, bbox_intersections, 
 from .tail_grad import (tail_forward, tail_backward, tail_views, tail_gradients, momentum_step, TailForward, TailBackward,  # noqa: F401
                         TAIL_FLOATS, TAIL_OFFSET)
 from .conv_grad import conv_backward, pool_backward, conv_backward_plan, network_gradients, ConvBackward  # noqa: F401
+from .solver import solver_plan, solver_defaults, solver_step, decay_table  # noqa: F401
+from .train import network_gradients_device, Trainer  # noqa: F401
 
 __all__ = ["CtpnError", "lib_path", "load_library", "Context", "MANIFEST", "WEIGHT_FLOATS",
            "make_synthetic_arena", "arena_views", "detect_page", "PageResult",
            "target_config_default", "bbox_overlaps", "bbox_intersections", "anchor_targets", "rpn_loss", "score_pages", "AnchorTargets", "RpnLoss",
            "tail_forward", "tail_backward", "tail_views", "tail_gradients", "momentum_step", "TailForward", "TailBackward", "TAIL_FLOATS", "TAIL_OFFSET",
-           "conv_backward", "pool_backward", "conv_backward_plan", "network_gradients", "ConvBackward"]
+           "conv_backward", "pool_backward", "conv_backward_plan", "network_gradients", "ConvBackward",
+           "solver_plan", "solver_defaults", "solver_step", "decay_table", "network_gradients_device", "Trainer"]

@@ -124,6 +124,10 @@ def _declare(lib):
         "ctpn_conv3x3_backward": (C.c_int, [C.c_int] * 6 + [vp, vp, vp, vp, C.c_int, vp, vp, vp]),
         "ctpn_maxpool2x2_backward": (C.c_int, [C.c_int] * 5 + [vp, vp, C.c_int, vp]),
         "ctpn_conv3x3_backward_plan": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+        "ctpn_solver_plan": (C.c_int, [C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+        "ctpn_solver_defaults": (C.c_int, [C.c_int, f64p]),
+        "ctpn_solver_step": (C.c_int, [C.c_int, C.c_int, C.c_longlong, vp, vp, vp, vp, C.POINTER(C.c_longlong), f32p, C.c_int, f64p, C.c_longlong,
+                                       C.c_int, f64p]),
         "ctpn_detect": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int, f64p, C.c_int, i32p,
                                   f32p, i32p]),
         "ctpn_detect_submit": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32p, C.c_int]),
@@ -233,6 +237,16 @@ def _declare(lib):
     return sig
 
 
+def _declare_train(lib):
+    """include/ctpn_hip_train.h: the training-side calls that take a ctx"""
+    sig = {"ctpn_get_tensor_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)])}
+    for name, (res, args) in sig.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return sig
+
+
 def load_library():
     """Load libctpn_hip.so once. Raises CtpnError if it has not been built (no silent fallback)."""
     global _LIB
@@ -251,6 +265,7 @@ def load_library():
             pass
     _LIB = C.CDLL(path, mode=C.RTLD_GLOBAL)
     _declare(_LIB)
+    _declare_train(_LIB)
     return _LIB
 
 
@@ -1315,6 +1330,21 @@ class Context:
         _check(self._lib.ctpn_get_tensor(self._h, name.encode(), _ptr(out, C.c_float), out.size, shape))
         shp = tuple(shape[i] for i in range(4))
         return out[: int(np.prod(shp))].reshape(shp)
+
+    def get_tensor_device(self, name):
+        """ctpn_get_tensor_device: get_tensor's tensor, same shape and bytes, as a float32 torch tensor on cuda:device_id -- unpacked by a
+        kernel, nothing crosses to the host. The call returns when the tensor is complete."""
+        import torch
+        shape = (C.c_int * 4)()
+        probe = torch.empty((4,), dtype=torch.float32, device=torch.device("cuda", int(self.device_id)))
+        rc = self._lib.ctpn_get_tensor_device(self._h, name.encode(), C.c_void_p(probe.data_ptr()), 0, shape)
+        if rc not in (CTPN_OK, -4):
+            _check(rc)
+        shp = tuple(shape[i] for i in range(4))
+        out = torch.empty(shp, dtype=torch.float32, device=probe.device)
+        if out.numel():
+            _check(self._lib.ctpn_get_tensor_device(self._h, name.encode(), C.c_void_p(out.data_ptr()), out.numel(), shape))
+        return out
 
     # ---- proposals
     def _anchors(self, n, post_nms_topn, counts):

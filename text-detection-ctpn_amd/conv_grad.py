@@ -2,8 +2,8 @@
 ReLU layer (the data gradient, the weight and the bias gradient), pool_backward the 2x2 max-pool, conv_backward_plan the fixed order of the
 weight gradient's sum over pixels. They take numpy arrays, or torch tensors on the device, which go through on_device = 1 with no host copy.
 network_gradients chains a ctx's forward into targets, loss, the tail's backward and these calls: the gradient of model_loss at every tensor of
-the arena. Not built: weight decay, Adam, RMSProp, the learning-rate schedule, the data layers, a device-resident get_tensor
-(network_gradients round-trips activations through the host; the stateless calls on device tensors are the measured path)."""
+the arena. network_gradients fetches the stored activations through get_tensor, onto the host and back; ctpn_amd.train has the same chain
+on device tensors (network_gradients_device) and the optimisers around it. Not built: the data layers."""
 import collections
 import ctypes as C
 
@@ -36,10 +36,11 @@ def _nhwc(x, what):
     return tuple(int(v) for v in x.shape)
 
 
-def conv_backward(x, w, y, d_y, want_dx=True, device_id=0):
+def conv_backward(x, w, y, d_y, want_dx=True, device_id=0, out=None):
     """ctpn_conv3x3_backward for the layer y = relu(conv(x, w) + b) -> ConvBackward(d_w (3, 3, ci, co), d_b (co,), d_x (n, h, w, ci) or None).
     x: (n, h, w, ci) float32, the layer's input; w: (3, 3, ci, co) in TF's HWIO; y: (n, h, w, co), the stored post-ReLU output; d_y: the gradient at
-    y. ci = 3 is conv1_1: want_dx must be False. All numpy, or all torch tensors on cuda:device_id (the results are then tensors there)."""
+    y. ci = 3 is conv1_1: want_dx must be False. All numpy, or all torch tensors on cuda:device_id (the results are then tensors there).
+    out: (d_w, d_b), device tensors of 9 ci co and co floats the two gradients are written to (views of a flat gradient vector)."""
     lib = B.load_library()
     n, h, wd, ci = _nhwc(x, "x")
     co = int(w.shape[3]) if w.ndim == 4 else -1
@@ -49,13 +50,22 @@ def conv_backward(x, w, y, d_y, want_dx=True, device_id=0):
         import torch
         dev = torch.device("cuda", int(device_id))
         ptrs = [_dev_ptr(t, torch.float32, device_id, name) for t, name in ((x, "x"), (w, "w"), (y, "y"), (d_y, "d_y"))]
-        d_w = torch.empty((3, 3, ci, co), dtype=torch.float32, device=dev)
-        d_b = torch.empty((co,), dtype=torch.float32, device=dev)
+        if out is None:
+            d_w = torch.empty((3, 3, ci, co), dtype=torch.float32, device=dev)
+            d_b = torch.empty((co,), dtype=torch.float32, device=dev)
+        else:
+            d_w, d_b = out
+            _dev_ptr(d_w, torch.float32, device_id, "out[0]"), _dev_ptr(d_b, torch.float32, device_id, "out[1]")
+            if d_w.numel() != 9 * ci * co or d_b.numel() != co:
+                raise ValueError("conv_backward: out is (9 ci co floats, co floats)")
+            d_w = d_w.view(3, 3, ci, co)
         d_x = torch.empty((n, h, wd, ci), dtype=torch.float32, device=dev) if want_dx else None
         outs = [C.c_void_p(d_w.data_ptr()), C.c_void_p(d_b.data_ptr()), None if d_x is None else C.c_void_p(d_x.data_ptr())]
         torch.cuda.current_stream(dev).synchronize()      # the call runs on a stream of its own: what torch queued for these tensors is done first
         on_dev = 1
     else:
+        if out is not None:
+            raise ValueError("conv_backward: out= goes with device tensors")
         x, w, y, d_y = B._f32(x), B._f32(w), B._f32(y), B._f32(d_y)
         d_w, d_b = np.empty((3, 3, ci, co), np.float32), np.empty((co,), np.float32)
         d_x = np.empty((n, h, wd, ci), np.float32) if want_dx else None
@@ -91,10 +101,11 @@ def pool_backward(y_full, d_pool, device_id=0):
     return d_full
 
 
-def conv_stack_backward(acts, blob, weights, d_top, from_layer="conv1_1", device_id=0, each=None):
+def conv_stack_backward(acts, blob, weights, d_top, from_layer="conv1_1", device_id=0, each=None, outs=None):
     """The walk from rpn_conv/3x3 back to from_layer. acts: {name: stored post-ReLU output (n, h, w, c)} for the convs walked, and for the convs
     a pool follows (their full-resolution maps) and the pools in between; blob: conv1_1's input; weights: {name + "/weights": HWIO}; d_top: the
-    gradient at rpn_conv/3x3's output. each(name, x, y, d_y, result) is called per conv, each(pool, y_full, None, d_pool, d_full) per pool (tests). -> {name + "/weights" | "/biases": gradient}"""
+    gradient at rpn_conv/3x3's output. each(name, x, y, d_y, result) is called per conv, each(pool, y_full, None, d_pool, d_full) per pool (tests).
+    outs: {name + "/weights" | "/biases": device tensor the gradient is written to} (conv_backward's out=). -> {name + "/weights" | "/biases": gradient}"""
     if from_layer not in CONVS:
         raise ValueError("from_layer is one of " + ", ".join(CONVS))
     first = CONVS.index(from_layer)
@@ -109,7 +120,8 @@ def conv_stack_backward(acts, blob, weights, d_top, from_layer="conv1_1", device
         else:
             x = acts[CONVS[k - 1]]
         want_dx = k > first
-        r = conv_backward(x, weights[name + "/weights"], acts[name], d_y, want_dx, device_id)
+        out = None if outs is None else (outs[name + "/weights"], outs[name + "/biases"])
+        r = conv_backward(x, weights[name + "/weights"], acts[name], d_y, want_dx, device_id, out)
         if each:
             each(name, x, acts[name], d_y, r)
         grads[name + "/weights"], grads[name + "/biases"] = r.d_w, r.d_b

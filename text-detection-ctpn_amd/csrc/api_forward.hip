@@ -1,5 +1,7 @@
 // C ABI of libctpn_hip.so, forward unit: image staging, the network forward on the ctx's streams, tensor read-back.
 #include "ctx.h"
+#include "../../include/ctpn_hip_train.h"
+#include "unpack_dev.h"
 
 namespace ctpn {
 
@@ -333,8 +335,14 @@ int ctpn_feat_shape(ctpn_ctx* c, int* n, int* hf, int* wf) {
   return CTPN_OK;
 }
 
-int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capacity, int shape4[4]) {
-  if (!c || !name || !out_host) return fail(CTPN_ERR_ARG, "null pointer");
+namespace {
+// a tensor name of the most recent forward -> where it is stored and in which form: the refusals, the shape and the capacity check that
+// ctpn_get_tensor and ctpn_get_tensor_device share. ld and es are the stored pixel's value count and value size (split precision: 2 C or 3 C
+// 16-bit values, the value is hi + lo)
+struct StoredTensor { const void* src = nullptr; int n = 0, H = 0, W = 0, C = 0, ld = 0, es = 4; bool bordered = false, split = false, gates = false; DType t = DType::F32; };
+
+int find_tensor(ctpn_ctx* c, const char* name, const void* out, size_t capacity, int shape4[4], StoredTensor& st) {
+  if (!c || !name || !out) return fail(CTPN_ERR_ARG, "null pointer");
   if (!c->forward_done) return fail(CTPN_ERR_STATE, "ctpn_get_tensor: no forward yet");
   CTPN_HIP_TRY(hipSetDevice(c->device));
   const ctpn_ctx::FwdSet& f = *c->last;      // the most recent forward's set, whichever slot submitted it
@@ -360,12 +368,24 @@ int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capac
   const size_t need = (size_t)n * H * W * C;
   if (shape4) { shape4[0] = n; shape4[1] = H; shape4[2] = W; shape4[3] = C; }
   if (capacity < need) return fail(CTPN_ERR_CAPACITY, "ctpn_get_tensor: output buffer too small");
+  // split precision: a pixel is [hi(C) | lo(C)] bf16 (rpn_conv/3x3: [hi | lo | hi]); the value is hi + lo
+  st.split = t == DType::SPLIT;
+  if (st.split) ld = (src == f.act_conv[13] ? 3 : 2) * C;
+  st.src = src; st.n = n; st.H = H; st.W = W; st.C = C; st.ld = ld; st.es = st.split ? 2 : dtype_bytes(t); st.bordered = bordered; st.gates = src == f.xp; st.t = t;
+  return CTPN_OK;
+}
+}  // namespace
+
+int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capacity, int shape4[4]) {
+  StoredTensor st;
+  if (const int rc = find_tensor(c, name, out_host, capacity, shape4, st)) return rc;
+  const ctpn_ctx::FwdSet& f = *c->last;
+  const void* src = st.src;
+  const int n = st.n, H = st.H, W = st.W, C = st.C, ld = st.ld, es = st.es;
+  const bool bordered = st.bordered, split = st.split;
+  const DType t = st.t;
   CTPN_HIP_TRY(hipStreamSynchronize(f.stream));
   CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
-  // split precision: a pixel is [hi(C) | lo(C)] bf16 (rpn_conv/3x3: [hi | lo | hi]); the value is hi + lo
-  const bool split = t == DType::SPLIT;
-  if (split) ld = (src == f.act_conv[13] ? 3 : 2) * C;
-  const int es = split ? 2 : dtype_bytes(t);
   const int Hs = bordered ? H + 2 : H, Ws = bordered ? W + 2 : W;
   const size_t bytes = (size_t)n * Hs * Ws * ld * es;
   std::vector<char> tmp(bytes);
@@ -393,6 +413,21 @@ int ctpn_get_tensor(ctpn_ctx* c, const char* name, float* out_host, size_t capac
           else for (int ch = 0; ch < C; ++ch) d[ch] = host_bf16_to_f32(sb[ch]);
         }
       }
+  return CTPN_OK;
+}
+
+// ctpn_get_tensor with the unpacking done by a kernel (unpack.hip) and the result left in HBM: same names, shapes, refusals and values
+int ctpn_get_tensor_device(ctpn_ctx* c, const char* name, float* out_dev, size_t capacity, int shape4[4]) {
+  StoredTensor st;
+  if (const int rc = find_tensor(c, name, out_dev, capacity, shape4, st)) return rc;
+  const ctpn_ctx::FwdSet& f = *c->last;
+  CTPN_HIP_TRY(hipStreamSynchronize(f.stream));
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream_p));
+  UnpackDesc d{};
+  d.n = st.n; d.H = st.H; d.W = st.W; d.C = st.C; d.ld = st.ld; d.border = st.bordered ? 1 : 0; d.gates = st.gates ? 1 : 0;
+  d.kind = st.split ? UP_SPLIT : st.es == 4 ? UP_F32 : st.t == DType::F16 ? UP_F16 : UP_BF16;
+  if (const int rc = launch_unpack(st.src, d, out_dev, c->stream)) return rc;
+  CTPN_HIP_TRY(hipStreamSynchronize(c->stream));
   return CTPN_OK;
 }
 

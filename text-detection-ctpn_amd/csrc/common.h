@@ -256,6 +256,14 @@ struct LstmPrePlan {
 LstmPrePlan lstm_pre_plan(long long cells, int ncu);
 int launch_lstm_pre_pack(const void* wt_x, void* wt_frag, hipStream_t s);      // [1024][512] 16-bit rows -> the kernel's fragment-major order (1 MB)
 int lstm_gate_col(int c);     // TF gate column (g * 128 + u) -> permuted column, per direction
+// unpack.hip: a stored activation -> dense fp32 NHWC in HBM (unpack_dev.h: the block's description and the per-thread text)
+struct UnpackDesc;
+int launch_unpack(const void* src, const UnpackDesc& d, float* out, hipStream_t s);
+// solver.hip: the two passes of ctpn_solver_step over flat fp32 vectors (solver_dev.h: the plan, the parameters, the per-element text)
+struct SvSegments;
+struct SvParams;
+int launch_solver_sums(const float* w, const float* g, long long count, const SvSegments& segs, double* partials, hipStream_t s);
+int launch_solver_update(float* w, const float* g, float* s1, float* s2, long long count, const SvSegments& segs, const SvParams& p, hipStream_t s);
 int launch_lstm_permute_rows(const void* src, void* dst, int row_bytes, hipStream_t s);
 // api_weights.hip: the input projection's weight chain, the one copy ctpn_load_weights_* and ctpn_debug_lstm_pre share. kx[d]: direction d's
 // [512 in][512 gates] fp32 block (kernel[:512]) with kx_ld floats per row, bias[d]: its 512 floats, all in TF's column order i | j | f | o ->

@@ -2,7 +2,7 @@
 backward"): the gradient of the RPN loss at the BiLSTM, the lstm_o FC and the two heads -- the arena's last ten tensors, TAIL_FLOATS floats.
 tail_forward / tail_backward take numpy arrays, or torch tensors on the device, which go through on_device = 1 with no host copy;
 tail_gradients chains a ctx's forward into targets, loss and gradient. The backward of the 14 convs in front of the tail starts at d_x:
-conv_grad.py. Not built: Adam, RMSProp, weight decay, the data layers (ctpn/finetune_tail.py is the Momentum branch on the host)."""
+conv_grad.py. ctpn/finetune_tail.py is the Momentum branch on the host; the optimisers on the device: solver.py, train.py. Not built: the data layers."""
 import collections
 import ctypes as C
 
@@ -82,9 +82,10 @@ def tail_forward(x, tail, want_saved=True, device_id=0):
     return TailForward(heads, saved)
 
 
-def tail_backward(x, tail, saved, d_heads, want_dx=False, device_id=0):
+def tail_backward(x, tail, saved, d_heads, want_dx=False, device_id=0, out=None):
     """ctpn_tail_backward -> TailBackward(d_tail TAIL_FLOATS (tail_views names it), d_x (n, hf, wf, 512) or None). saved: tail_forward's block
-    for the same x and tail; d_heads: (n, hf, wf, 64), columns 60..63 ignored (rpn_loss(want_grad=True).d_heads of 64-wide heads)."""
+    for the same x and tail; d_heads: (n, hf, wf, 64), columns 60..63 ignored (rpn_loss(want_grad=True).d_heads of 64-wide heads). out: a
+    device tensor of TAIL_FLOATS floats d_tail is written to (a view of a flat gradient vector)."""
     lib = B.load_library()
     n, hf, wf = _shape4(x, 512, "x")
     ns = _saved_floats(lib, n, hf, wf)
@@ -96,12 +97,20 @@ def tail_backward(x, tail, saved, d_heads, want_dx=False, device_id=0):
         ptrs = [_dev_ptr(t, torch.float32, device_id, w) for t, w in ((x, "x"), (tail, "tail"), (saved, "saved"), (d_heads, "d_heads"))]
         if tail.numel() != TAIL_FLOATS or saved.numel() != ns:
             raise ValueError("tail holds %d floats, saved %d" % (TAIL_FLOATS, ns))
-        d_tail = torch.empty((TAIL_FLOATS,), dtype=torch.float32, device=dev)
+        if out is None:
+            d_tail = torch.empty((TAIL_FLOATS,), dtype=torch.float32, device=dev)
+        else:
+            d_tail = out
+            _dev_ptr(d_tail, torch.float32, device_id, "out")
+            if d_tail.dim() != 1 or d_tail.numel() != TAIL_FLOATS:
+                raise ValueError("tail_backward: out holds %d floats" % TAIL_FLOATS)
         d_x = torch.empty((n, hf, wf, 512), dtype=torch.float32, device=dev) if want_dx else None
         pg, pdx = C.c_void_p(d_tail.data_ptr()), None if d_x is None else C.c_void_p(d_x.data_ptr())
         torch.cuda.current_stream(dev).synchronize()
         on_dev = 1
     else:
+        if out is not None:
+            raise ValueError("tail_backward: out= goes with device tensors")
         x, tail, saved, d_heads = B._f32(x), B._f32(tail).reshape(-1), B._f32(saved).reshape(-1), B._f32(d_heads)
         if tail.shape[0] != TAIL_FLOATS or saved.shape[0] != ns:
             raise ValueError("tail holds %d floats, saved %d" % (TAIL_FLOATS, ns))

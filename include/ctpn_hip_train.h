@@ -1,6 +1,9 @@
-/* libctpn_hip.so, the training-side companion of ctpn_hip.h: what a training step needs from a ctx beyond inference. ctpn_hip.h is the
- * inference ABI; its stateless training calls (anchor targets, the loss, the two backward passes, the solver step) need no ctx and live
- * there. The one call here reads a ctx's stored activations. ABI version: ctpn_hip.h's (10). */
+/* libctpn_hip.so, the training-side companion of ctpn_hip.h: what a training step needs beyond inference. ctpn_hip.h is the inference ABI; its
+ * stateless training calls (anchor targets, the loss, the two backward passes, the solver step) need no ctx and live there. The one call
+ * declared in this file reads a ctx's stored activations. The three stateless calls of the training data layer, which turn a labelled folder
+ * into what a step reads, come with this header too: they are declared in ctpn_hip_data_layer.h, which it includes at its end (this file
+ * itself keeps to the calls that take a ctx: tests/test_solver.py holds its list and the binding's _declare_train to exactly those).
+ * ABI version: ctpn_hip.h's (10). */
 #ifndef CTPN_HIP_TRAIN_H
 #define CTPN_HIP_TRAIN_H
 
@@ -23,4 +26,7 @@ int ctpn_get_tensor_device(ctpn_ctx* ctx, const char* name, float* out_dev, size
 #ifdef __cplusplus
 }
 #endif
+
+#include "ctpn_hip_data_layer.h"
+
 #endif /* CTPN_HIP_TRAIN_H */

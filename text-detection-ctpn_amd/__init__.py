@@ -16,10 +16,12 @@ from .tail_grad import (tail_forward, tail_backward, tail_views, tail_gradients,
 from .conv_grad import conv_backward, pool_backward, conv_backward_plan, network_gradients, ConvBackward  # noqa: F401
 from .solver import solver_plan, solver_defaults, solver_step, decay_table  # noqa: F401
 from .train import network_gradients_device, Trainer  # noqa: F401
+from .data_layer import split_labels, split_label_dims, train_page, train_boxes, DataLayer  # noqa: F401
 
 __all__ = ["CtpnError", "lib_path", "load_library", "Context", "MANIFEST", "WEIGHT_FLOATS",
            "make_synthetic_arena", "arena_views", "detect_page", "PageResult",
            "target_config_default", "bbox_overlaps", "bbox_intersections", "anchor_targets", "rpn_loss", "score_pages", "AnchorTargets", "RpnLoss",
            "tail_forward", "tail_backward", "tail_views", "tail_gradients", "momentum_step", "TailForward", "TailBackward", "TAIL_FLOATS", "TAIL_OFFSET",
            "conv_backward", "pool_backward", "conv_backward_plan", "network_gradients", "ConvBackward",
-           "solver_plan", "solver_defaults", "solver_step", "decay_table", "network_gradients_device", "Trainer"]
+           "solver_plan", "solver_defaults", "solver_step", "decay_table", "network_gradients_device", "Trainer",
+           "split_labels", "split_label_dims", "train_page", "train_boxes", "DataLayer"]

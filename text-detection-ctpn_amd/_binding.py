@@ -247,6 +247,20 @@ def _declare_train(lib):
     return sig
 
 
+def _declare_data_layer(lib):
+    """include/ctpn_hip_data_layer.h (which ctpn_hip_train.h includes): the training data layer's three stateless calls"""
+    i32p = C.POINTER(C.c_int)
+    sig = {"ctpn_split_labels": (C.c_int, [C.c_int, C.c_int, i32p, C.c_void_p, i32p, C.c_int, C.c_void_p, C.c_longlong, i32p, C.c_void_p]),
+           "ctpn_train_page": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.c_int]),
+           "ctpn_train_boxes": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p])}
+    for name, (res, args) in sig.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return sig
+
+
 def load_library():
     """Load libctpn_hip.so once. Raises CtpnError if it has not been built (no silent fallback)."""
     global _LIB
@@ -266,6 +280,7 @@ def load_library():
     _LIB = C.CDLL(path, mode=C.RTLD_GLOBAL)
     _declare(_LIB)
     _declare_train(_LIB)
+    _declare_data_layer(_LIB)
     return _LIB
 
 

@@ -3,7 +3,7 @@ ReLU layer (the data gradient, the weight and the bias gradient), pool_backward 
 weight gradient's sum over pixels. They take numpy arrays, or torch tensors on the device, which go through on_device = 1 with no host copy.
 network_gradients chains a ctx's forward into targets, loss, the tail's backward and these calls: the gradient of model_loss at every tensor of
 the arena. network_gradients fetches the stored activations through get_tensor, onto the host and back; ctpn_amd.train has the same chain
-on device tensors (network_gradients_device) and the optimisers around it. Not built: the data layers."""
+on device tensors (network_gradients_device) and the optimisers around it; the data layers: data_layer.py."""
 import collections
 import ctypes as C
 

@@ -264,6 +264,15 @@ struct SvSegments;
 struct SvParams;
 int launch_solver_sums(const float* w, const float* g, long long count, const SvSegments& segs, double* partials, hipStream_t s);
 int launch_solver_update(float* w, const float* g, float* s1, float* s2, long long count, const SvSegments& segs, const SvParams& p, hipStream_t s);
+// data_layer.hip: the training data layer (data_layer_dev.h: the per-thread text). split labels: count (spans: nq DlSpan, counts: nq), scan
+// (one workgroup; scan: nq + 1 ints, page_offs: pages + 1), write (total strips). train page: src -> image_out and, unless null, blob_out.
+// train boxes: *bad is set where a strip holds a value outside uint16
+struct DlPage;
+int launch_split_count(const double* quads, int nq, const int* quad_offs, int pages, const int* dims, void* spans, uint32_t* counts, hipStream_t s);
+int launch_split_scan(const uint32_t* counts, int nq, int* scan, const int* quad_offs, int pages, int* page_offs, hipStream_t s);
+int launch_split_write(const void* spans, const int* scan, int nq, int total, float* strips, hipStream_t s);
+int launch_train_page(const uint8_t* src, const DlPage& p, uint8_t* image_out, float* blob_out, hipStream_t s);
+int launch_train_boxes(const float* strips, int n, int page_width, int flip, double scale, float* out, int* bad, hipStream_t s);
 int launch_lstm_permute_rows(const void* src, void* dst, int row_bytes, hipStream_t s);
 // api_weights.hip: the input projection's weight chain, the one copy ctpn_load_weights_* and ctpn_debug_lstm_pre share. kx[d]: direction d's
 // [512 in][512 gates] fp32 block (kernel[:512]) with kx_ld floats per row, bias[d]: its 512 floats, all in TF's column order i | j | f | o ->

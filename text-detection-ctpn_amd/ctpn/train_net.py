@@ -1,14 +1,20 @@
 """`python ctpn/train_net.py IMAGES LABELS --steps N [--solver Momentum|Adam|RMS] [--lr LR] [--weight-decay WD] [--from LAYER] [--cfg YML]
-[--snapshot-iters K] [--restore SNAPSHOT.npz] [--out PREFIX] [--synthetic SEED]` -- the reference's ctpn/train_net.py on the device: one page per
-step, one JSON line per step (ctpn_amd.train.RECORD_FIELDS and the page).
+[--snapshot-iters K] [--restore SNAPSHOT.npz] [--out PREFIX] [--synthetic SEED] [--data-layer [--no-flip] [--shuffle-seed S] [--no-prefetch]]` -- the
+reference's ctpn/train_net.py on the device: one page per step, one JSON line per step (ctpn_amd.train.RECORD_FIELDS and the page).
 
 It is lib/fast_rcnn/train.py's loop over ctpn_amd.Trainer: the gradient of total_loss (model_loss plus TRAIN.WEIGHT_DECAY's L2 terms),
 tf.clip_by_global_norm(grads, 10.0), then the optimiser TRAIN.SOLVER names with TRAIN.LEARNING_RATE (and TRAIN.MOMENTUM), the learning-rate
 schedule of TRAIN.STEPSIZE / TRAIN.GAMMA (which only Momentum follows, as in the reference), a snapshot every TRAIN.SNAPSHOT_ITERS steps.
 Activations, gradients, the optimiser's state and the weights stay on the device from step to step. The defaults are cfg.TRAIN's; --cfg reads
 a yml on top of ctpn/text.yml (the reference's own ctpn/text.yml selects Adam, 1e-5, 5e-4). --out PREFIX writes PREFIX_iter_K.npz snapshots
-and PREFIX.npy, the final arena; --restore continues from a snapshot (its solver and settings win). Not built: the data layers (no shuffling, no
-flipping: page k % pages at step k). IMAGES and LABELS as in ctpn/score_pages.py.
+and PREFIX.npy, the final arena; --restore continues from a snapshot (its solver and settings win).
+
+Without --data-layer, IMAGES and LABELS are as in ctpn/score_pages.py -- labels already cut into 16-px strips, pages of one size -- and step k
+visits page k % pages. With --data-layer the run is the reference's from an ICDAR-style folder on: LABELS holds gt_<stem>.txt / <stem>.txt
+files of `x1,y1,x2,y2,x3,y3,x4,y4[,...]` lines (further comma fields are ignored, as lib/prepare_training_data/split_label.py:37 does), the
+pages may resize to any mix of sizes, and ctpn_amd.DataLayer serves them in RoIDataLayer's shuffled order with the mirrored copies of
+TRAIN.USE_FLIPPED (--no-flip: without them; --shuffle-seed: default cfg.RNG_SEED; --no-prefetch: the next file is not decoded ahead). The
+JSON line then also carries page, flipped, h and w. A restored run starts the layer's order from its beginning.
 """
 from __future__ import print_function
 
@@ -59,6 +65,22 @@ def run(trainer, pages, steps, seed=0, emit=None, snapshot_iters=0, out=None):
     return records
 
 
+def run_layer(trainer, layer, steps, seed=0, emit=None, snapshot_iters=0, out=None):
+    """run() over a DataLayer: `steps` Trainer.step_record steps on the layer's records; the records gain page, flipped, h and w"""
+    records = []
+    for _ in range(int(steps)):
+        k = trainer.iter
+        page = layer.next()
+        rec = trainer.step_record(page, seed=seed + k)
+        rec["page"], rec["flipped"], rec["h"], rec["w"] = page.page, page.flipped, page.hw[0], page.hw[1]
+        records.append(rec)
+        if emit:
+            emit(rec)
+        if out and snapshot_iters > 0 and trainer.iter % snapshot_iters == 0:
+            trainer.snapshot("%s_iter_%d.npz" % (out, trainer.iter))
+    return records
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("images")
@@ -80,6 +102,10 @@ def main(argv=None):
     g.add_argument("--no-sample", dest="sample", action="store_false", help="RPN_BATCHSIZE 0 (the default)")
     g.add_argument("--sample", dest="sample", action="store_true", help="subsample to the library's RPN_BATCHSIZE")
     ap.set_defaults(sample=False)
+    ap.add_argument("--data-layer", action="store_true", help="LABELS holds quadrilaterals; shuffle, mirror and mix sizes as the reference's data layer does")
+    ap.add_argument("--no-flip", dest="flip", action="store_false", help="with --data-layer: no mirrored copies (TRAIN.USE_FLIPPED off)")
+    ap.add_argument("--shuffle-seed", type=int, default=None, metavar="S", help="with --data-layer: the order's seed; default: cfg.RNG_SEED")
+    ap.add_argument("--no-prefetch", dest="prefetch", action="store_false", help="with --data-layer: decode each file when its step comes")
     args = ap.parse_args(argv)
     if args.from_layer not in CONVS:
         raise SystemExit("train_net: --from is one of " + ", ".join(CONVS))
@@ -109,8 +135,36 @@ def main(argv=None):
     tcfg = ctpn_amd.target_config_default()
     if not args.sample:
         tcfg[4] = 0.0
+    emit = lambda r: print(json.dumps(r))      # noqa: E731
+    make_trainer = lambda: (ctpn_amd.Trainer.restore(net.ctx, restore) if restore else      # noqa: E731
+                            ctpn_amd.Trainer(net.ctx, net._arena, name, hyper, wd, args.from_layer, stepsize, gamma, tcfg))
+    fnames = sorted(glob.glob(os.path.join(images, "*.png")) + glob.glob(os.path.join(images, "*.jpg")))
+    if args.data_layer:
+        from ctpn_amd.data_layer import quad_label_path, read_quads
+        paths, quads = [], []
+        for fname in fnames:
+            lp = quad_label_path(labels, fname)
+            if lp is None:
+                print(json.dumps({"image": os.path.basename(fname), "error": "no label file"}))
+                continue
+            paths.append(fname)
+            quads.append(read_quads(lp))
+        if not paths:
+            raise SystemExit("train_net: no labelled image under %s" % images)
+        with ctpn_amd.DataLayer(net.device_id, paths, quads, flipped=args.flip and bool(cfg.TRAIN.USE_FLIPPED),
+                                seed=cfg.RNG_SEED if args.shuffle_seed is None else args.shuffle_seed, scales=cfg.TRAIN.SCALES, max_size=cfg.TRAIN.MAX_SIZE,
+                                prefetch=args.prefetch, label_scale=TextLineCfg.SCALE, label_max_size=TextLineCfg.MAX_SCALE) as layer:
+            h, w = layer.max_shape()      # the ctx's capacity: the largest page; every forward takes its own page's size
+            net.ensure_capacity(1, int(h), int(w))
+            if net.ctx.get_option("keep_acts") != 1:
+                net.ctx.set_option("keep_acts", 1)
+            trainer = make_trainer()
+            run_layer(trainer, layer, args.steps, args.seed, emit=emit, snapshot_iters=snap, out=out)
+        if out:
+            np.save(out + ".npy", trainer.arena())
+        return
     pages = []
-    for fname in sorted(glob.glob(os.path.join(images, "*.png")) + glob.glob(os.path.join(images, "*.jpg"))):
+    for fname in fnames:
         lp = label_path(labels, fname)
         if lp is None:
             print(json.dumps({"image": os.path.basename(fname), "error": "no label file"}))
@@ -126,11 +180,8 @@ def main(argv=None):
     net.ensure_capacity(1, int(h), int(w))
     if net.ctx.get_option("keep_acts") != 1:
         net.ctx.set_option("keep_acts", 1)      # this program's own ctx: the gradient needs every activation stored
-    if restore:
-        trainer = ctpn_amd.Trainer.restore(net.ctx, restore)
-    else:
-        trainer = ctpn_amd.Trainer(net.ctx, net._arena, name, hyper, wd, args.from_layer, stepsize, gamma, tcfg)
-    run(trainer, pages, args.steps, args.seed, emit=lambda r: print(json.dumps(r)), snapshot_iters=snap, out=out)
+    trainer = make_trainer()
+    run(trainer, pages, args.steps, args.seed, emit=emit, snapshot_iters=snap, out=out)
     if out:
         np.save(out + ".npy", trainer.arena())
 

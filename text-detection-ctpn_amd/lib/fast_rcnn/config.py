@@ -62,7 +62,8 @@ __C.TRAIN = AttrDict(dict(
     DISPLAY=10, SNAPSHOT_ITERS=5000, HAS_RPN=True, LEARNING_RATE=0.001, MOMENTUM=0.9, GAMMA=0.1, STEPSIZE=50000,
     IMS_PER_BATCH=2, BBOX_NORMALIZE_TARGETS_PRECOMPUTED=False, RPN_POSITIVE_OVERLAP=0.7, PROPOSAL_METHOD='selective_search',
     BG_THRESH_LO=0.1, PRECLUDE_HARD_SAMPLES=True, BBOX_INSIDE_WEIGHTS=[1.0, 1.0, 1.0, 1.0],
-    RPN_BBOX_INSIDE_WEIGHTS=[1.0, 1.0, 1.0, 1.0], RPN_POSITIVE_WEIGHT=-1.0, FG_FRACTION=0.25, WEIGHT_DECAY=0.0005))
+    RPN_BBOX_INSIDE_WEIGHTS=[1.0, 1.0, 1.0, 1.0], RPN_POSITIVE_WEIGHT=-1.0, FG_FRACTION=0.25, WEIGHT_DECAY=0.0005,
+    SCALES=(600,), MAX_SIZE=1000, USE_FLIPPED=True))
 
 __C.TEST = AttrDict()
 __C.TEST.checkpoints_path = "checkpoints/"

@@ -2,7 +2,7 @@
 backward"): the gradient of the RPN loss at the BiLSTM, the lstm_o FC and the two heads -- the arena's last ten tensors, TAIL_FLOATS floats.
 tail_forward / tail_backward take numpy arrays, or torch tensors on the device, which go through on_device = 1 with no host copy;
 tail_gradients chains a ctx's forward into targets, loss and gradient. The backward of the 14 convs in front of the tail starts at d_x:
-conv_grad.py. ctpn/finetune_tail.py is the Momentum branch on the host; the optimisers on the device: solver.py, train.py. Not built: the data layers."""
+conv_grad.py. ctpn/finetune_tail.py is the Momentum branch on the host; the optimisers on the device: solver.py, train.py; the data layers: data_layer.py."""
 import collections
 import ctypes as C
 

@@ -11,7 +11,10 @@ cfg.TRAIN.SOLVER (Momentum, Adam, RMS), the weight decay of total_loss and tf.cl
 The learning-rate schedule is the reference's, oddity included: at `iter != 0 and iter % STEPSIZE == 0` the loop multiplies the `lr`
 VARIABLE by GAMMA, but only MomentumOptimizer was built on that variable -- AdamOptimizer and RMSPropOptimizer were given the constant
 cfg.TRAIN.LEARNING_RATE (lib/fast_rcnn/train.py:94-102), so their rate never changes. Trainer keeps that: `lr` in the record is the rate
-the step used. Not built: the data layers (shuffling, flipping); one ctx shape per Trainer."""
+the step used.
+
+The data layers are ctpn_amd.data_layer: Trainer.step_record takes a DataLayer record -- the page, its blob and its boxes already on the
+device -- and a Trainer steps on pages of different sizes in one run: the ctx's capacity is the largest, each forward takes its page's."""
 import collections
 
 import numpy as np
@@ -47,11 +50,15 @@ def _ragged_dev(rows, width, np_dtype, dev):
     return torch.from_numpy(flat).to(dev), offs
 
 
-def network_gradients_device(ctx, images, gt_boxes, gt_hard=None, dontcare=None, cfg=None, seed=0, arena_dev=None, from_layer="conv1_1", out=None, mark=None):
+def network_gradients_device(ctx, images, gt_boxes, gt_hard=None, dontcare=None, cfg=None, seed=0, arena_dev=None, from_layer="conv1_1", out=None, mark=None,
+                             images_dev=None, blob_dev=None, gt_dev=None, gt_offsets=None):
     """conv_grad.network_gradients with everything tensor-sized on the device. arena_dev: the WEIGHT_FLOATS weights as a float32 tensor on
     cuda:ctx.device_id -- the weights the ctx has loaded (ctx.load_weights_device(arena_dev.data_ptr())). The ctx option keep_acts must be 1.
     out: a float32 device vector of WEIGHT_FLOATS - trained_offset(from_layer) floats to write into (default: a new one). mark(leg) is called
     when "forward", "fetch" and "backward" are complete on the device (tools/train_step_throughput.py times the legs with it).
+    images_dev (a uint8 tensor (n, h, w, 3) on the ctx's device), blob_dev (its float32 blob, image - PIXEL_MEANS; None: formed here) and
+    gt_dev (a float32 tensor (total, 5)) with gt_offsets (n + 1 ints) replace images and gt_boxes, which are then None: the forward runs
+    from the device pointer and no image, blob or box array is built on the host (a DataLayer record's fields, see Trainer.step_record).
     -> (one dict per image as network_gradients returns, the gradient of the batch's summed model_loss at arena[trained_offset(from_layer):]
     as one flat device tensor in manifest order: the concatenation of network_gradients' arrays, bit for bit)."""
     import torch
@@ -69,9 +76,21 @@ def network_gradients_device(ctx, images, gt_boxes, gt_hard=None, dontcare=None,
     views = lambda flat, base: {name: flat[off - base: off - base + int(np.prod(shape))].view(shape) for name, shape, off in MANIFEST if off >= base}      # noqa: E731
     weights, g_views = views(arena_dev, 0), views(out, first_off)
     tail = arena_dev[TAIL_OFFSET:]
-    images = np.ascontiguousarray(images, dtype=np.uint8)
-    n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
-    ctx.forward(images)
+    if images_dev is not None:
+        if images is not None or gt_boxes is not None or gt_dev is None or gt_offsets is None:
+            raise ValueError("network_gradients_device: images_dev comes with gt_dev and gt_offsets, in place of images and gt_boxes")
+        if not images_dev.is_cuda or images_dev.device != dev or images_dev.dtype != torch.uint8 or images_dev.dim() != 4 or images_dev.shape[3] != 3 or \
+                not images_dev.is_contiguous():
+            raise ValueError("network_gradients_device: images_dev is a contiguous uint8 tensor (n, h, w, 3) on cuda:%d" % ctx.device_id)
+        n, h, w = int(images_dev.shape[0]), int(images_dev.shape[1]), int(images_dev.shape[2])
+        if blob_dev is not None and (tuple(blob_dev.shape) != tuple(images_dev.shape) or blob_dev.dtype != torch.float32 or blob_dev.device != dev):
+            raise ValueError("network_gradients_device: blob_dev is images_dev's float32 blob")
+        torch.cuda.current_stream(dev).synchronize()      # the ctx runs on streams of its own: what torch queued for these tensors is done first
+        ctx.forward(None, device_ptr=images_dev.data_ptr(), shape=(n, h, w))
+    else:
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+        ctx.forward(images)
     if mark:
         ctx.sync()
         mark("forward")
@@ -88,18 +107,25 @@ def network_gradients_device(ctx, images, gt_boxes, gt_hard=None, dontcare=None,
         mark("fetch")
     blob = None
     if first == 0:      # image - PIXEL_MEANS in float64, rounded once to float32: numpy's in-place subtraction in network_gradients
-        means = torch.tensor(PIXEL_MEANS.reshape(-1), dtype=torch.float64, device=dev)
-        blob = (torch.from_numpy(images).to(dev).to(torch.float64) - means).to(torch.float32)
+        if images_dev is not None and blob_dev is not None:
+            blob = blob_dev.contiguous()
+        else:
+            means = torch.tensor(PIXEL_MEANS.reshape(-1), dtype=torch.float64, device=dev)
+            blob = ((images_dev if images_dev is not None else torch.from_numpy(images).to(dev)).to(torch.float64) - means).to(torch.float32)
     x = acts["rpn_conv/3x3"]
     fwd = tail_forward(x, tail, True, ctx.device_id)
-    gts = []
-    for g in gt_boxes:
-        g = np.asarray(g, np.float32).reshape(-1, np.asarray(g).shape[-1] if np.asarray(g).size else 5)
-        if g.shape[1] == 4:
-            g = np.concatenate([g, np.ones((g.shape[0], 1), np.float32)], axis=1)
-        gts.append(g)
     info = np.array([[h, w, 1.0]] * n, np.float32)
-    gt_dev, gt_offs = _ragged_dev(gts, 5, np.float32, dev)
+    if images_dev is not None:
+        gt_offs = np.ascontiguousarray(gt_offsets, dtype=np.int32).reshape(-1)
+        gt_dev = gt_dev.reshape(-1, 5)
+    else:
+        gts = []
+        for g in gt_boxes:
+            g = np.asarray(g, np.float32).reshape(-1, np.asarray(g).shape[-1] if np.asarray(g).size else 5)
+            if g.shape[1] == 4:
+                g = np.concatenate([g, np.ones((g.shape[0], 1), np.float32)], axis=1)
+            gts.append(g)
+        gt_dev, gt_offs = _ragged_dev(gts, 5, np.float32, dev)
     hard_dev = None if gt_hard is None else _ragged_dev(gt_hard, 1, np.int32, dev)[0]
     dc_dev, dc_offs = (None, None) if dontcare is None else _ragged_dev(dontcare, 4, np.float32, dev)
     t = anchor_targets(hf, wf, info, gt_dev, hard_dev, dc_dev, cfg, seed, ctx.device_id, gt_offsets=gt_offs, dc_offsets=dc_offs)
@@ -152,14 +178,22 @@ class Trainer(object):
         torch.cuda.current_stream(self.arena_dev.device).synchronize()
         self.ctx.load_weights_device(self.arena_dev.data_ptr())
 
-    def step(self, images, gt_boxes, seed=0, gt_hard=None, dontcare=None, mark=None):
+    def step_record(self, rec, seed=0, mark=None):
+        """one iteration on a DataLayer record: step() with the page, its blob and its boxes taken from the device as they are. The pages of
+        one run may differ in size, within the ctx's capacity."""
+        g = int(rec.gt_dev.shape[0])
+        return self.step(None, None, seed=seed, mark=mark, images_dev=rec.image_dev[None], blob_dev=None if rec.blob_dev is None else rec.blob_dev[None],
+                         gt_dev=rec.gt_dev, gt_offsets=np.array([0, g], np.int32))
+
+    def step(self, images, gt_boxes, seed=0, gt_hard=None, dontcare=None, mark=None, images_dev=None, blob_dev=None, gt_dev=None, gt_offsets=None):
         """one iteration on `images` ((n, h, w, 3) uint8 BGR) and their boxes -> the record: RECORD_FIELDS. The losses are the batch's sums
         BEFORE the update; reg_loss is the sum of weight_decay w^2 / 2 over the decayed tensors trained, total_loss = model_loss + reg_loss
         is what the clipped gradient belongs to; sumsq is its squared global norm. mark: network_gradients_device's hook, also called
-        with "update" and "load"."""
+        with "update" and "load". images_dev, blob_dev, gt_dev, gt_offsets: network_gradients_device's device form (images, gt_boxes None)."""
         if self.iter != 0 and self.iter % self.stepsize == 0:
             self.lr = float(np.float32(np.float64(np.float32(self.lr)) * self.gamma))
-        losses, _ = network_gradients_device(self.ctx, images, gt_boxes, gt_hard, dontcare, self.cfg, seed, self.arena_dev, self.from_layer, out=self.grad, mark=mark)
+        losses, _ = network_gradients_device(self.ctx, images, gt_boxes, gt_hard, dontcare, self.cfg, seed, self.arena_dev, self.from_layer, out=self.grad, mark=mark,
+                                             images_dev=images_dev, blob_dev=blob_dev, gt_dev=gt_dev, gt_offsets=gt_offsets)
         hyper = self.hyper.copy()
         if self.solver == "Momentum":
             hyper[0] = self.lr
